@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- processed edges/sec of the R-GCN encoder forward+backward (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-extra-workloads]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full [--no-extra-workloads]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -9,7 +9,11 @@ One "step" = one pass of the hot path over one minibatch graph already resident 
 device-side graph preparation of the fed [E,3] triples + 2-layer encoder forward (train mode, generated
 self-loop dropout) + backward for every encoder weight (rgcn_step_device).  value = E_g * steps / s.
 
-Rank 0 prints ONE COMPACT JSON line LAST on stdout (a few KB: tests hold it under 8 KB).  Besides the contract keys:
+A plain run sets up, runs W untimed and K timed steps, writes the last timed step's outputs (codes and encoder weight
+gradients, see write_outputs) when --dump-outputs is given, and prints the result line: the contract keys and
+gpu_event_ms_per_step.  Everything below is measured only with --full.
+
+Rank 0 prints ONE COMPACT JSON line LAST on stdout (a few KB: tests hold it under 8 KB).  With --full, besides the contract keys:
   "roofline":     the dominant kernel against its gfx950 roofline (live HIP-event durations; fractions on COMPULSORY
                   bytes / ALGORITHMIC flops, design and PMC bytes beside them),
   "step_roofline": the whole step against the chip,
@@ -26,7 +30,7 @@ Rank 0 prints ONE COMPACT JSON line LAST on stdout (a few KB: tests hold it unde
   "train_loop":   (same run) the reference's whole iteration through the training driver: host neighbourhood sampler
                   (k builder threads) + upload + device step + loss read-back: ms / iteration, device idle fraction.
 Everything else -- the per-kernel tables of every workload and train step, notes -- goes to bench_details.json next to
-this file (and to gpurun_out/ when that directory exists), never to the result line.
+this file (and to a copy in the output directory when one exists), never to the result line.
 
 `python bench.py --gpus N` with no WORLD_SIZE in the environment spawns its own N ranks (one per GPU) and relays rank 0's
 line; under torch.distributed.run it is one of the ranks.
@@ -123,9 +127,15 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="fb237_block", choices=sorted(WORKLOADS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the codes and encoder weight gradients of the last timed step to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: per-kernel accounting and rooflines, steady state, "
+                         "the fp32-MFMA reference run, the CPU baselines, the other workloads, train steps, evaluation "
+                         "and the training loop (default: the timed steps only)")
     ap.add_argument("--no-extra-workloads", action="store_true",
-                    help="only the --workload line (default: the single-GPU run of the headline workload also "
-                         "measures the other BASELINE configurations into \"workloads\")")
+                    help="only the --workload line (default with --full: the single-GPU run of the headline workload "
+                         "also measures the other BASELINE configurations into \"workloads\")")
     ap.add_argument("--extra-steps", type=int, default=20, help="timed steps of each extra workload")
     ap.add_argument("--cpu-steps", type=int, default=12, help="timed CPU-oracle steps (0 disables)")
     ap.add_argument("--no-kernel-profile", action="store_true")
@@ -140,7 +150,10 @@ def parse_args():
     ap.add_argument("--gemm-mode", type=int, default=int(os.environ.get("RGCN_GEMM_MODE", "6")), choices=[0, 6, 9],
                     help="arithmetic of the dense contractions (include/rgcn.h rgcn_set_gemm_mode): 6 / 9 = exact "
                          "bf16 operand split with 6 / 9 partial products on the bf16 matrix cores, 0 = fp32 MFMA")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 class Ranks:
@@ -624,6 +637,13 @@ class EncoderBench:
             data = "real graph structure (fixture %s of tests/golden/graphs.npz, %d edges; SURVEY 8d), " % (graph_name, E_g)
         return dataset, data, graph_spec or {"kind": "fixture", "name": graph_name}
 
+    def outputs(self):
+        """what a caller of the step receives, as left by the last step: the codes H_L and the gradient of every encoder
+        weight (W_relation is the decoder's: the step never touches its gradient)"""
+        out = {"codes": self.eng.codes()}
+        out.update(("grad_" + n, g) for n, g in self.eng.get_grads().items() if n != "W_relation")
+        return out
+
     def close(self):
         self.tri_dev.free()
         self.tri_dev_b.free()
@@ -633,10 +653,11 @@ class EncoderBench:
         self.eng.close()
 
 
-def measure(workload, args, rk, steps, warmup, full):
+def measure(workload, args, rk, steps, warmup, headline):
     """One workload on this rank's engine: W untimed steps, then EXACTLY `steps` timed ones (barrier + sync on both sides,
-    max over ranks) -- `value` comes from that region and nothing else --, then the informative legs and the per-kernel
-    passes.  full = the headline extras (steady state, fp32-MFMA reference run, CPU baseline)."""
+    max over ranks) -- `value` comes from that region and nothing else --, then (--full only) the informative legs and the
+    per-kernel passes.  headline = the run's --workload: its outputs are dumped (--dump-outputs) and, with --full, it gets
+    the headline extras (steady state, fp32-MFMA reference run, CPU baseline)."""
     b = EncoderBench(workload, args, rk)
     rank, world = b.rank, b.world
     b.run(warmup, 1000)
@@ -648,12 +669,15 @@ def measure(workload, args, rk, steps, warmup, full):
     wall, gpu_ms = b.timed(steps, 2000, gpu_timer=True)
     ms_per_step = wall * 1e3 / steps
     value = b.E_g * steps / wall
+    if headline and args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, b.outputs())
 
-    steady = b.steady_state(warmup + steps) if full and world == 1 else None
-    fp32_ref = b.fp32_reference(steps) if full and args.gemm_mode != 0 and not args.no_fp32_reference else None
-    kernels, roofline = ([], None) if args.no_kernel_profile else b.kernel_accounting(steps)
+    extras = headline and args.full
+    steady = b.steady_state(warmup + steps) if extras and world == 1 else None
+    fp32_ref = b.fp32_reference(steps) if extras and args.gemm_mode != 0 and not args.no_fp32_reference else None
+    kernels, roofline = ([], None) if args.no_kernel_profile or not args.full else b.kernel_accounting(steps)
     step_roofline = b.step_roofline(kernels, ms_per_step) if kernels else None
-    cpu = b.cpu_baseline() if full and rank == 0 and world == 1 and args.cpu_steps > 0 else None
+    cpu = b.cpu_baseline() if extras and rank == 0 and world == 1 and args.cpu_steps > 0 else None
 
     out = None
     if rank == 0:
@@ -692,6 +716,8 @@ def measure(workload, args, rk, steps, warmup, full):
         }
         if cpu:
             out["speedup_vs_cpu"] = round(value / cpu["value"], 1)
+        if not args.full:      # nothing measured the collectives
+            del out["comm_ms_per_step"], out["collectives"]
     b.close()
     return out
 
@@ -1064,15 +1090,18 @@ def spawn_ranks(args):
         sys.exit("bench.py --gpus %d: rank(s) failed: %s" % (n, ", ".join("rank %d rc %d" % b for b in bad)))
 
 
-def compact_line(out):
-    """The one line the driver parses: contract keys + roofline + cpu_baseline(s) + step_roofline + summaries.
-    Kept to a few KB (tests/test_gpu_multiprocess.py holds it under 8 KB); the tables live in bench_details.json."""
+def compact_line(out, full=True):
+    """The one line the driver parses: contract keys (a plain run stops there) + roofline + cpu_baseline(s) +
+    step_roofline + summaries.  Kept to a few KB (tests/test_gpu_multiprocess.py holds it under 8 KB); the tables live in
+    bench_details.json."""
     line = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                 "scaling", "vs_baseline", "dtype", "data", "config")}
     for k in ("gpu_event_ms_per_step", "comm_ms_per_step", "rccl_ranks", "collectives", "message_edges_per_s",
               "speedup_vs_cpu"):
         if k in out:
             line[k] = out[k]
+    if not full:
+        return line
     rf = out.get("roofline")
     line["roofline"] = ({k: v for k, v in rf.items() if k != "basis"} if rf else None)
     sr = out.get("step_roofline")
@@ -1135,6 +1164,30 @@ def reference_code_baseline():
         return None
 
 
+DUMP_MAX_ENTRIES = 1 << 21      # 8 MB of float32 per array: the headline workload's outputs take 27 MB, fb15k_block's 50
+DUMP_MAX_BYTES = 64 << 20
+
+
+def write_outputs(dirname, arrays):
+    """{name: float32 array} -> dirname/<name>.npy.  An array of more than DUMP_MAX_ENTRIES entries is written as a 1-D
+    sample: its entries at DUMP_MAX_ENTRIES flat positions drawn without replacement by a generator of fixed seed and
+    sorted, so that two runs with the same arguments write the same positions."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size > DUMP_MAX_ENTRIES:
+            pick = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ENTRIES, replace=False))
+            a = a.reshape(-1)[pick]
+        out[name] = a
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def write_details(out):
     """per-kernel tables of every workload / train step: a side file, not the result line"""
     paths = [os.path.join(ROOT, "bench_details.json")]
@@ -1170,12 +1223,13 @@ def main():
     if os.environ.get("RGCN_BENCH_IMPORT_TORCH") == "1":
         import torch  # noqa: F401  (test knob: exercise a torch-first load order on one GPU)
 
-    out = measure(args.workload, args, rk, args.steps, args.warmup, full=True)
+    out = measure(args.workload, args, rk, args.steps, args.warmup, headline=True)
     extras = []
-    widen = rk.world == 1 and args.workload == "fb237_block" and not args.no_extra_workloads and not args.hipgraph
+    widen = (args.full and rk.world == 1 and args.workload == "fb237_block" and not args.no_extra_workloads
+             and not args.hipgraph)
     if widen:
         for w in EXTRA_WORKLOADS:
-            o = measure(w, args, rk, args.extra_steps, min(args.warmup, 5), full=False)
+            o = measure(w, args, rk, args.extra_steps, min(args.warmup, 5), headline=False)
             for drop in ("cpu_baseline", "fp32_mfma_reference", "higher_is_better", "vs_baseline"):
                 o.pop(drop, None)
             extras.append(o)
@@ -1187,9 +1241,9 @@ def main():
     evaluation_encodes = measure_evaluation_encodes(args) if widen else []
     train_loop = (measure_train_loop(args, train_steps[0]["minibatch_step"]["ms_per_step"],
                                      iterations=max(20, 6 * args.extra_steps)) if widen else None)
-    if rk.rank == 0 and rk.world == 1 and not args.no_live_traffic and not args.no_kernel_profile:
+    if args.full and rk.rank == 0 and rk.world == 1 and not args.no_live_traffic and not args.no_kernel_profile:
         apply_live_traffic(out, args)
-    if rk.rank == 0:
+    if args.full and rk.rank == 0:
         out["workloads"] = extras
         out["train_steps"] = train_steps
         out["evaluation"] = evaluation
@@ -1222,8 +1276,9 @@ def main():
                 if os.path.exists(p):
                     os.remove(p)
     if rk.rank == 0:
-        out["details"] = write_details(out)
-        print(json.dumps(compact_line(out), separators=(",", ":")), flush=True)
+        if args.full:
+            out["details"] = write_details(out)
+        print(json.dumps(compact_line(out, args.full), separators=(",", ":")), flush=True)
 
 
 if __name__ == "__main__":

@@ -203,3 +203,27 @@ def test_bench_result_line_stays_compact_and_self_spawns():
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--cpu-steps", "0"],
                            capture_output=True, text=True, env=env, timeout=300)
         assert r.returncode != 0 and "rank(s) failed" in r.stderr and "must be launched" not in r.stderr
+
+
+def test_bench_dump_outputs_are_a_fixed_sample_within_64_mb(tmp_path):
+    """bench.write_outputs: small arrays as they are, a larger one as the same seeded sample of DUMP_MAX_ENTRIES entries on
+    every call, float32; more than 64 MB in all is refused before anything is written."""
+    import importlib.util
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_module3", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = bench.DUMP_MAX_ENTRIES
+    big = np.arange(n + 5, dtype=np.float64)
+    small = np.random.RandomState(0).randn(7, 3)
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.shape == (n,) and np.array_equal(a, b)
+    assert len(np.unique(a)) == n and np.all(np.diff(a) > 0)             # distinct positions, in order
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), small.astype(np.float32))
+    with pytest.raises(ValueError):
+        bench.write_outputs(str(tmp_path / "c"), {"x%d" % i: big for i in range(9)})
+    assert not (tmp_path / "c").exists()

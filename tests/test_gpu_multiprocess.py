@@ -79,7 +79,7 @@ def check_multi_rank_line(r, world):
 @pytest.mark.parametrize("world", [2, 4])
 def test_bench_multi_rank_prints_one_json_line_last(collective, world):
     r = launch(world, 29650 + world, ["bench.py", "--gpus", str(world), "--steps", "4", "--warmup", "1",
-                                      "--cpu-steps", "0"], collective, {"RGCN_BENCH_SHARE_GPU": "1"})
+                                      "--cpu-steps", "0", "--full"], collective, {"RGCN_BENCH_SHARE_GPU": "1"})
     check_multi_rank_line(r, world)
 
 
@@ -100,17 +100,17 @@ def test_bench_spawns_its_own_ranks_without_a_launcher(collective, world):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     env.update(RGCN_RCCL_LIBRARY=collective, RGCN_LIBRARY="devtools", RGCN_BENCH_SHARE_GPU="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "1",
-                        "--cpu-steps", "0"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
+                        "--cpu-steps", "0", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     check_multi_rank_line(r, world)
 
 
 def test_bench_single_gpu_line_carries_every_section():
-    """The driver's call with small counts: ONE compact JSON line (the last line of stdout, under 8 KB) with the contract
+    """The --full call with small counts: ONE compact JSON line (the last line of stdout, under 8 KB) with the contract
     keys, the roofline and cpu_baseline objects, one-line summaries of the other BASELINE configurations ("workloads"),
     the device train steps ("train_steps", config 5's captured step among them) and the evaluation pass ("evaluation");
     the per-kernel tables in bench_details.json."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--extra-steps", "2",
-                        "--cpu-steps", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--cpu-steps", "1", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]
     assert len(lines[-1]) < 8192, len(lines[-1])
@@ -148,3 +148,25 @@ def test_bench_single_gpu_line_carries_every_section():
              [t["minibatch_step"]["kernels"] for t in full["train_steps"]]
     assert all(k["frac"] <= 1.0 for tab in tables for k in tab), [k for tab in tables for k in tab if k["frac"] > 1.0]
     assert all({"compulsory_bytes", "design_bytes", "traffic"} <= set(k) for k in full["kernels"])
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """The driver's call (no --full): the contract keys and nothing that needs runs of its own, the steps it was asked for,
+    no side file; --dump-outputs writes the codes and every encoder weight gradient of the last timed step, float32, within
+    64 MB (arrays over bench.DUMP_MAX_ENTRIES entries as a fixed sample of that many)."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert {"metric", "unit", "higher_is_better", "dtype"} <= set(d)
+    assert not {"roofline", "kernels", "cpu_baseline", "workloads", "train_steps", "steady_state", "details"} & set(d)
+    files = {f.name: np.load(f) for f in out.iterdir()}
+    assert {"codes.npy", "grad_W_emb.npy", "grad_W_self1.npy", "grad_W_f2.npy", "grad_b_emb.npy"} <= set(files)
+    assert "grad_W_relation.npy" not in files
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert files["codes.npy"].shape == (1 << 21,) and files["grad_W_self1.npy"].shape == (500, 500)
+    assert np.abs(files["grad_W_self1.npy"]).max() > 0
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20

@@ -11,6 +11,7 @@ import pytest
 
 import oracle
 import helpers
+import kernel_grid as kg
 from helpers import assert_close, make_case
 
 pytestmark = pytest.mark.gpu
@@ -317,6 +318,34 @@ def test_basis_encoder_matches_oracle(native, V, R, d, L, B, E, norm):
     compare(acts, grads, oacts, ograds, tag="basis")
 
 
+# ------------------------------------------------------------------ every compiled row-kernel variant
+# tests/kernel_grid.py: one case per (SD, GW) cell of k_block_rows (every long-row tile size TS, every d = 500 block count,
+# the group-width boundaries) and per (VEC, TPR) cell of the basis kernels, each with rows of 33, 3 TS + 7 and 400 slots
+GRID_PARITY = ([(n, "intended") for n in sorted(kg.GRID_CASES)] +
+               [(n, "tf_as_executed") for n in sorted(kg.GRID_CASES) if kg.GRID_CASES[n]["d"] == 500])
+
+
+@pytest.mark.parametrize("name,norm", GRID_PARITY)
+def test_kernel_grid_encoder_matches_oracle(native, name, norm):
+    """Every activation and every gradient against the oracle, with test_block_encoder_matches_oracle's tolerances.  A
+    gradient miss is re-checked, as in the full-size parity tests, against the oracle's reverse mode of the engine's own
+    forward -- only when a few relu gates sit within rounding of zero, and then with no spike allowance (block_sd1_nb500
+    in tf_as_executed: one H1 gate, 7.7e-8 on the engine and 0 in the oracle, moves W_emb's gradient by 1.5 % of its
+    scale; at the engine's own gates the two agree within 7e-7)."""
+    c = dict(kg.GRID_CASES[name])
+    c["params"], c["triples"], c["masks"], c["dcodes"] = kg.grid_inputs(c)
+    oacts, ograds = oracle.encoder_step(c["params"], c["triples"], c["V"], c["L"], c["kind"], c["dcodes"], keep_prob=0.8,
+                                        dropout_masks=c["masks"], norm_mode=norm)
+    acts, grads = run_engine(native, c["V"], c["R"], c["d"], c["L"], c["kind"], c["nb"], c["params"], c["triples"],
+                             c["masks"], c["dcodes"], norm=norm)
+    try:
+        compare(acts, grads, oacts, ograds, tag="%s %s" % (name, kg.cell_of(c)))
+    except AssertionError as direct:
+        if "grad" not in str(direct):
+            raise
+        gate_aware_gradient_check(c, acts, grads, norm, direct)
+
+
 def test_basis_hub_and_test_mode(native):
     V, R, d, L, B = 60, 12, 20, 2, 3
     params, _, masks, dcodes = make_case(V, R, d, L, "basis", B, 10, seed=19)
@@ -468,6 +497,18 @@ def test_errors_are_loud(native):
         eng.close()
     with pytest.raises(native.RgcnError):
         native.Engine(10, 3, 10, 1, "block", 3, max_edges=4)   # d % nb != 0
+    # configurations no kernel is compiled for: refused when the engine is created, not at first use
+    for d, kind, nb, why in [(500, "block", 50, "sd 10"), (12, "block", 2, "sd 6"), (14, "block", 2, "sd 7"),
+                             (513, "block", 513, "nb > 512"), (8, "basis", 65, "B > 64")]:
+        with pytest.raises(native.RgcnError) as e:
+            native.Engine(10, 3, d, 1, kind, nb, max_edges=4)
+        assert e.value.status == 5, (why, str(e.value))         # RGCN_ERR_UNSUPPORTED
+    # and a valid engine in the same process still runs
+    V, R, d, L, nb, E = 40, 5, 20, 2, 4, 100
+    params, triples, masks, dcodes = make_case(V, R, d, L, "block", nb, E, seed=5)
+    acts, grads = run_engine(native, V, R, d, L, "block", nb, params, triples, masks, dcodes)
+    oacts, ograds = oracle.encoder_step(params, triples, V, L, "block", dcodes, dropout_masks=masks)
+    compare(acts, grads, oacts, ograds, tag="after refusals")
 
 
 # ------------------------------------------------------------------ golden fixtures (reference-free)
@@ -603,11 +644,22 @@ F64_CASES = {
     "fb237_basis_B2_L2": lambda: helpers.golden_inputs("fb237_basis_B2_L2"),
     "fb237_basis_B5_L2": lambda: helpers.golden_inputs("fb237_basis_B5_L2"),
 }
+# tests/kernel_grid.py cases: the other d = 500 block counts (GW 16 / 32 / 64), the long-row tiles of 16 and 8 slots
+# (GW 64 x SD 4, GW 64 x SD 8, GW 32 x SD 8), basis at (VEC 1, TPR 256) and at B = 64 (eight passes)
+for _n in ("block_sd4_nb125", "block_sd2_nb250", "block_sd1_nb500", "block_sd4_nb300", "block_sd8_nb260",
+           "block_sd8_nb136", "basis_d301_B17", "basis_d20_B64"):
+    F64_CASES["grid_" + _n] = (lambda n: lambda: _grid_case(n))(_n)
 
 
 def _made_case(V, R, d, L, kind, nb, E, seed):
     params, triples, masks, dcodes = make_case(V, R, d, L, kind, nb, E, seed=seed)
     return dict(V=V, R=R, d=d, L=L, kind=kind, nb=nb, params=params, masks=masks, dcodes=dcodes, triples=triples)
+
+
+def _grid_case(name):
+    c = dict(kg.GRID_CASES[name])
+    c["params"], c["triples"], c["masks"], c["dcodes"] = kg.grid_inputs(c)
+    return c
 
 
 @pytest.mark.parametrize("name,gemm_mode", [(n, 6) for n in sorted(F64_CASES)] +
@@ -847,6 +899,26 @@ def test_single_pass_layer_equals_the_two_kernel_form(native, V, R, d, nb, E, hu
         for h in range(hubs):                       # a few vertices with hundreds (or thousands) of incident edges
             idx = rng.choice(E, size=min(E // 4, 1500 if V == 1100 else 300), replace=False)
             triples[idx, 2 if h % 2 == 0 else 0] = h
+    _single_pass_equals_two_kernel_form(native, V, R, d, nb, params, triples, masks, dcodes, gen_dropout)
+
+
+# one grid case per (SD, GW) cell of k_block_rows: every group width at every block size, every long-row tile size
+GRID_CELLS = sorted({kg.cell_of(c)[1:3]: c["name"] for c in reversed(kg.BLOCK_GRID)}.values())
+
+
+@pytest.mark.parametrize("name", GRID_CELLS)
+@pytest.mark.parametrize("gen_dropout", [False, True])
+def test_single_pass_layer_equals_the_two_kernel_form_on_the_grid(native, name, gen_dropout):
+    """test_single_pass_layer_equals_the_two_kernel_form on tests/kernel_grid.py's cases (rows of 33, 3 TS + 7 and 400
+    slots): bitwise, at every (SD, GW) cell."""
+    c = kg.GRID_CASES[name]
+    params, triples, masks, dcodes = kg.grid_inputs(c)
+    _single_pass_equals_two_kernel_form(native, c["V"], c["R"], c["d"], c["nb"], params, triples, masks, dcodes,
+                                        gen_dropout)
+
+
+def _single_pass_equals_two_kernel_form(native, V, R, d, nb, params, triples, masks, dcodes, gen_dropout):
+    E = len(triples)
     out = []
     for fuse in (1, 0):
         eng = native.Engine(V, R, d, 2, "block", nb, keep_prob=0.8, max_edges=max(E, 1))

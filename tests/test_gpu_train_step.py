@@ -214,9 +214,14 @@ def numpy_clip_adam(params, grads, names, lr, b1, b2, eps, max_norm, steps_state
     return out, gn
 
 
-@pytest.mark.parametrize("kind,nb", [("block", 4), ("basis", 2)])
-def test_train_step_device_with_clip_and_adam(native, kind, nb):
-    V, R, d, L, E = 80, 8, 20, 2, 300
+@pytest.mark.parametrize("kind,nb,d", [
+    pytest.param("block", 4, 20, id="block-4"), pytest.param("basis", 2, 20, id="basis-2"),
+    # every block count of the shipped d = 500 but 100: group widths 16 / 32 / 64 of k_block_rows, whose band-tiled
+    # weight copy is rebuilt after every Adam update (and k_block_transpose carries the updated weights)
+    pytest.param("block", 125, 500, id="block-125-d500"), pytest.param("block", 250, 500, id="block-250-d500"),
+    pytest.param("block", 500, 500, id="block-500-d500")])
+def test_train_step_device_with_clip_and_adam(native, kind, nb, d):
+    V, R, L, E = 80, 8, 2, 300
     params, triples, _, _ = make_case(V, R, d, L, kind, nb, E, seed=77)
     rng = np.random.RandomState(2)
     X, Y = decoder_batch(rng, triples, V)

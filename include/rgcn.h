@@ -419,8 +419,7 @@ rgcn_status rgcn_set_fusion(rgcn_ctx* ctx, int32_t mode);
  *       error against float64 equals the fp32-MFMA path's (tests/test_gpu_parity.py::test_gemm_modes).
  *   9 : all 9 partial products - the products of exact fp32 arithmetic in another summation order
  *   0 : fp32 MFMA (v_mfma_f32_32x32x2_f32), 1/16 of the bf16 rate on gfx950
- *   3 : hi*hi, hi*mid, mid*hi only (about 2^-17; NOT fp32 - experiments only)
- * RGCN_GEMM_MODE in the environment overrides the default at create. */
+ *   3 : hi*hi, hi*mid, mid*hi only (about 2^-17; NOT fp32 - experiments only) */
 rgcn_status rgcn_set_gemm_mode(rgcn_ctx* ctx, int32_t mode);
 
 /* Per-kernel profile: when enabled every launch is bracketed by HIP events on the context's stream.

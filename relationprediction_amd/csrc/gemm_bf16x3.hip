@@ -15,7 +15,7 @@
 //                                               equals the fp32 MFMA's (test_gemm_modes_are_fp32_accurate)
 // K = 16 of one 32x32 tile costs 6 (9) x 32 cycles against 8 x 64 on the fp32 MFMA.
 //
-// What the measurements on MI355X say about this kernel's shape (tools/mfma_fill.hip, profiles/):
+// What the measurements on MI355X say about this kernel's shape (profiles/, e.g. r01_mfma_valu_fill.log):
 //   * VALU work is NOT hidden behind the matrix pipe: every plain VALU instruction issued on a SIMD adds
 //     ~2 cycles to that SIMD's MFMA stream, whichever wave issues it (v_dot2c_f32_bf16: ~10).  So the
 //     split is done ONCE per element, when the tile goes to LDS (11 plain VALU per element pair), not per
@@ -462,13 +462,9 @@ template <bool A_KC, bool B_KC, bool VEC, int TERMS, bool B_PRE = false>
 hipError_t launch_one(rgcn_ctx* c, const XArgs& g) {
   constexpr size_t bytes = lds_bytes(A_KC, B_KC, B_PRE);
   auto kern = k_gemm_bf16x3<A_KC, B_KC, VEC, TERMS, B_PRE>;
-  static bool configured = false;     // per instantiation; contexts are single-threaded per process
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return e;
-    configured = true;
-  }
+  static uint64_t configured = 0;
+  const hipError_t e = set_dynamic_lds(reinterpret_cast<const void*>(kern), (int)bytes, c->cfg.device, configured);
+  if (e != hipSuccess) return e;
   const int gx = g.swizzle == 2 ? ((g.tiles_m + 7) / 8) * 8 * g.tiles_n : g.tiles_m * g.tiles_n * g.splits;
   hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)g.batch.groups), dim3(NTH), bytes, c->stream, g);
   return hipGetLastError();
@@ -566,7 +562,8 @@ hipError_t gemm_bf16x3_launch(rgcn_ctx* c, int terms, bool a_kc, bool b_kc, bool
   g.tiles_n = (N + BN - 1) / BN;
   g.nt32 = bfrag_nt32(N);
   // a weight on the B side: the eight-wavefront kernel (gemm_bf16x3_w8.hip), bitwise the same product
-  // (devtools knob RGCN_GEMM_W8: 0 never, 1 where the call site asks for it, 2 / 3 everywhere, >= 1000 the lab's variants)
+  // (devtools knob RGCN_GEMM_W8: 0 never, 1 where the call site asks for it, 2 / 3 everywhere).  The kernel reads
+  // batch.limit as a row limit only.
   const int w8 = knob("RGCN_GEMM_W8", 1);
   bool wide = g.batch.wide != 0;
   if (wide && g.batch.limit == nullptr) {
@@ -576,7 +573,7 @@ hipError_t gemm_bf16x3_launch(rgcn_ctx* c, int terms, bool a_kc, bool b_kc, bool
     const long t = (long)((M + 127) / 128) * ((N + 255) / 256) * g.batch.groups;
     wide = t <= 256 && t >= 160;
   }
-  if (g.bfrag != nullptr && (terms == 6 || terms == 9) && (w8 >= 2 || (w8 == 1 && wide)))
+  if (g.bfrag != nullptr && !g.batch.limit_on_k && (terms == 6 || terms == 9) && (w8 >= 2 || (w8 == 1 && wide)))
     return gemm_bf16x3_w8_launch(c, terms, M, N, K, A, lda, C, ldc, swizzle, vecC, g.batch);
   if (terms == 9) return vec ? launch_form<true, 9>(c, a_kc, b_kc, g) : launch_form<false, 9>(c, a_kc, b_kc, g);
   if (terms == 3) return vec ? launch_form<true, 3>(c, a_kc, b_kc, g) : launch_form<false, 3>(c, a_kc, b_kc, g);

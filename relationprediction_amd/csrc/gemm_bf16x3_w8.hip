@@ -50,11 +50,6 @@ __device__ __forceinline__ void aload(f32x4& dst, const float* p) {
 __device__ __forceinline__ void aload_s(f32x4& dst, uint32_t voff, const float* sbase) {
   asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(sbase) : "memory");
 }
-// DBG (devtools builds only; 0 in the product): ablation switches and the per-wavefront timeline of tools/gemm_w8_lab.py
-enum : int { DBG_NO_MFMA = 1, DBG_NO_SPLIT = 2, DBG_NO_FRAG = 4, DBG_NO_DMA = 8, DBG_NO_ALOAD = 16, DBG_NO_STORE = 32,
-              DBG_TIMELINE = 64, DBG_FINE = 128, DBG_NT_STORE = 256 };
-constexpr int TL_SLOTS = 24;      // 8-byte stamps per wavefront
-
 // one 1 KB piece (PIECE = 0, 1, 2: the immediate offset moves the source and the destination alike)
 template <int PIECE>
 __device__ __forceinline__ void dma1(uint32_t voff, const u32x4* sbase, uint32_t lds_addr) {
@@ -72,7 +67,7 @@ __device__ __forceinline__ void dma1(uint32_t voff, const u32x4* sbase, uint32_t
 
 // (192 registers, not the 193 the allocator would take: two wavefronts of this kernel then leave a SIMD 128 registers, one
 // wavefront of the 126-128-register layer kernels)
-template <int TERMS, int DBG = 0>
+template <int TERMS>
 __global__ void __launch_bounds__(WNTH, 2) __attribute__((amdgpu_num_vgpr(192))) k_gemm_w8(XArgs g) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
 
@@ -107,15 +102,6 @@ __global__ void __launch_bounds__(WNTH, 2) __attribute__((amdgpu_num_vgpr(192)))
   const int wm = (wave >> 2) * 64, wn = (wave & 3) * 64;
   const int li = lane & 31, h = lane >> 5;
   const uint32_t lds0 = (uint32_t)(uintptr_t)lds;
-  uint64_t tl[TL_SLOTS];
-  auto stamp = [&](auto slot) {
-    if constexpr ((DBG & (DBG_TIMELINE | DBG_FINE)) != 0) tl[decltype(slot)::value] = __builtin_amdgcn_s_memtime();
-  };
-  if constexpr ((DBG & (DBG_TIMELINE | DBG_FINE)) != 0) {
-#pragma unroll
-    for (int i = 0; i < TL_SLOTS; ++i) tl[i] = 0;
-  }
-  stamp(std::integral_constant<int, 0>{});
 
   f32x16 acc[2][2];
 #pragma unroll
@@ -154,18 +140,14 @@ __global__ void __launch_bounds__(WNTH, 2) __attribute__((amdgpu_num_vgpr(192)))
     constexpr int Q = decltype(part)::value;
     const bool live = s < nkt;
     if constexpr (Q < 3) {
-      if constexpr (!(DBG & DBG_NO_DMA)) dma1<Q>(voff, live ? sb : szero, lds0 + P * ST_SZ + b_wr);
+      dma1<Q>(voff, live ? sb : szero, lds0 + P * ST_SZ + b_wr);
       if constexpr (Q == 2) sb += sb_step;
     } else {
-      if constexpr (!(DBG & DBG_NO_ALOAD)) {
-        if (s >= nfull) {      // the partial last tile and the stages past the end: zeros where there is no A
-          const float* p = (live && atail_ok) ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(sa) + a_off) : g.zeros;
-          aload(ra[P], p);
-        } else {
-          aload_s(ra[P], a_off, sa);
-        }
+      if (s >= nfull) {      // the partial last tile and the stages past the end: zeros where there is no A
+        const float* p = (live && atail_ok) ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(sa) + a_off) : g.zeros;
+        aload(ra[P], p);
       } else {
-        ra[P] = f32x4{1.0f, 2.0f, 3.0f, 4.0f};
+        aload_s(ra[P], a_off, sa);
       }
       sa += BK;
     }
@@ -221,9 +203,7 @@ __global__ void __launch_bounds__(WNTH, 2) __attribute__((amdgpu_num_vgpr(192)))
   // stage t + 2 and the split of its A.  MF = false: the same without MFMAs (pipeline fill).
   auto step = [&](int t, auto slot, auto mf) {
     constexpr int P = decltype(slot)::value;
-    constexpr bool MF = decltype(mf)::value && !(DBG & DBG_NO_MFMA);
-    const bool fine = (DBG & DBG_FINE) != 0 && t == 12;      // one step of the middle of the loop in detail
-    if (fine) stamp(std::integral_constant<int, 12>{});
+    constexpr bool MF = decltype(mf)::value;
     if (MF && (t == flip[0] || t == flip[1] || t == flip[2])) negate_acc();
     const uint32_t negmask = __builtin_amdgcn_readfirstlane((sign_group(t + 2) & 1) ? 0x80000000u : 0u);
     const uint32_t* st_rd = lds + ((P + 1) & 3) * (ST_SZ / 4);
@@ -239,39 +219,15 @@ __global__ void __launch_bounds__(WNTH, 2) __attribute__((amdgpu_num_vgpr(192)))
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fc[i * 3 + pa_[tt]], fc[6 + j * 3 + pb_[tt]], acc[i][j], 0, 0, 0);
       }
       if constexpr (m < 8 && m % 2 == 1) issue_part(t + 4, slot, std::integral_constant<int, m / 2>{});
-      if constexpr (m == 7) {
-        if (fine) stamp(std::integral_constant<int, 13>{});
-      }
-      if constexpr (m < 12 && !(DBG & DBG_NO_FRAG)) read_frag(mi, st_rd, fn);
-      if constexpr (m == M_WAIT) {
-        if (fine) stamp(std::integral_constant<int, 14>{});
-        // two steps' loads stay in flight: 2 x (3 DMA + 1 A); fewer in the ablations that drop a kind of load
-        constexpr int VMW = 2 * (((DBG & DBG_NO_DMA) ? 0 : 3) + ((DBG & DBG_NO_ALOAD) ? 0 : 1));
-        if constexpr (VMW == 8) asm volatile("s_waitcnt vmcnt(8)" : "+v"(rs) : : "memory");
-        else if constexpr (VMW == 6) asm volatile("s_waitcnt vmcnt(6)" : "+v"(rs) : : "memory");
-        else if constexpr (VMW == 2) asm volatile("s_waitcnt vmcnt(2)" : "+v"(rs) : : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" : "+v"(rs) : : "memory");
-        if (fine) stamp(std::integral_constant<int, 15>{});
-      }
-      if constexpr (m > M_WAIT && (m - M_WAIT) % 2 == 1 && (m - M_WAIT) / 2 < 5 && !(DBG & DBG_NO_SPLIT))
+      if constexpr (m < 12) read_frag(mi, st_rd, fn);
+      // two steps' loads stay in flight: 2 x (3 DMA + 1 A)
+      if constexpr (m == M_WAIT) asm volatile("s_waitcnt vmcnt(8)" : "+v"(rs) : : "memory");
+      if constexpr (m > M_WAIT && (m - M_WAIT) % 2 == 1 && (m - M_WAIT) / 2 < 5)
         split_piece(std::integral_constant<int, (m - M_WAIT) / 2>{}, rs, st_wr, negmask);
-      if constexpr (m == 5 || m == NM - 1) {
-        if (fine) stamp(std::integral_constant<int, m == 5 ? 16 : 17>{});
-      }
       __builtin_amdgcn_sched_barrier(0);
     };
     static_for<0, NM>(weave);
-    if constexpr ((DBG & DBG_NO_MFMA) != 0 && !(DBG & DBG_NO_FRAG)) {      // keep the fragment reads alive
-#pragma unroll
-      for (int n = 0; n < 12; ++n) asm volatile("" : : "v"(fn[n]));
-    }
-    if constexpr ((DBG & DBG_NO_SPLIT) != 0) asm volatile("" : : "v"(rs));
-    if (fine) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      stamp(std::integral_constant<int, 18>{});
-    }
     lds_barrier();
-    if (fine) stamp(std::integral_constant<int, 19>{});
   };
 
   using I0 = std::integral_constant<int, 0>;
@@ -283,7 +239,6 @@ __global__ void __launch_bounds__(WNTH, 2) __attribute__((amdgpu_num_vgpr(192)))
   issue(1, I1{});
   step(-2, I2{}, std::false_type{});      // (loads stage 2; "reads" stage -1: nothing yet, harmless; splits stage 0)
   step(-1, I3{}, std::false_type{});      // loads stage 3, reads stage 0, splits stage 1
-  stamp(std::integral_constant<int, 1>{});
   // ---- the contraction
   int t = 0;
   for (; t + 4 <= nkt; t += 4) {
@@ -291,13 +246,6 @@ __global__ void __launch_bounds__(WNTH, 2) __attribute__((amdgpu_num_vgpr(192)))
     step(t + 1, I1{}, std::true_type{});
     step(t + 2, I2{}, std::true_type{});
     step(t + 3, I3{}, std::true_type{});
-    if constexpr ((DBG & DBG_TIMELINE) != 0) {      // after steps 4, 8, 16, 24, 32
-      if (t == 0) stamp(std::integral_constant<int, 2>{});
-      if (t == 4) stamp(std::integral_constant<int, 3>{});
-      if (t == 12) stamp(std::integral_constant<int, 4>{});
-      if (t == 20) stamp(std::integral_constant<int, 5>{});
-      if (t == 28) stamp(std::integral_constant<int, 6>{});
-    }
   }
   if (t < nkt) step(t, I0{}, std::true_type{});
   if (t + 1 < nkt) step(t + 1, I1{}, std::true_type{});
@@ -307,9 +255,7 @@ __global__ void __launch_bounds__(WNTH, 2) __attribute__((amdgpu_num_vgpr(192)))
   // (and every asm load's destination stays reserved until here: a register the compiler believed free would be overwritten
   // when a load of a stage past the end lands)
   asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]) : : "memory");
-  stamp(std::integral_constant<int, 7>{});
   __syncthreads();
-  stamp(std::integral_constant<int, 8>{});
 
   // ---- epilogue: acc register r of lane l holds C[row = (r&3) + 8*(r>>2) + 4*(l>>5)][col = l&31]; two passes of 64 rows
   // (pass = the i of every wavefront) through LDS, written out as float4 rows
@@ -332,13 +278,10 @@ __global__ void __launch_bounds__(WNTH, 2) __attribute__((amdgpu_num_vgpr(192)))
       const int row = f / C4, c4 = f % C4;
       // staged row -> row of the tile: rows 0..31 belong to the wavefronts with wm = 0, 32..63 to wm = 64
       const int grow = m0 + (row >> 5) * 64 + 32 * pass + (row & 31), gcol = n0 + 4 * c4;
-      if (grow < Mlim && gcol < g.N && !((DBG & DBG_NO_STORE) != 0 && g.M > 0)) {
+      if (grow < Mlim && gcol < g.N) {
         const float4 v = *reinterpret_cast<const float4*>(stage + row * WEPI_LD + 4 * c4);
         if (g.vecC) {
-          if constexpr ((DBG & DBG_NT_STORE) != 0)
-            __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(C + (size_t)grow * g.ldc + gcol));
-          else
-            *reinterpret_cast<float4*>(C + (size_t)grow * g.ldc + gcol) = v;
+          *reinterpret_cast<float4*>(C + (size_t)grow * g.ldc + gcol) = v;
         } else {
           float* o = C + (size_t)grow * g.ldc + gcol;
           o[0] = v.x;
@@ -350,29 +293,14 @@ __global__ void __launch_bounds__(WNTH, 2) __attribute__((amdgpu_num_vgpr(192)))
     }
     __syncthreads();
   }
-  if constexpr ((DBG & (DBG_TIMELINE | DBG_FINE)) != 0) {
-    stamp(std::integral_constant<int, 9>{});
-    if (g.tl != nullptr && lane == 0) {
-      uint32_t xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      tl[20] = ((uint64_t)(xcc & 0xf) << 32) | (uint32_t)__builtin_amdgcn_s_getreg(/*HW_ID*/ 4 | (0 << 6) | (31 << 11));
-      uint64_t* o = g.tl + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 8 + wave) * TL_SLOTS;
-#pragma unroll
-      for (int i = 0; i < TL_SLOTS; ++i) o[i] = tl[i];
-    }
-  }
 }
 
-template <int TERMS, int DBG = 0>
+template <int TERMS>
 hipError_t launch_w8(rgcn_ctx* c, const XArgs& g) {
-  auto kern = k_gemm_w8<TERMS, DBG>;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       W_LDS_BYTES);
-    if (e != hipSuccess) return e;
-    configured = true;
-  }
+  auto kern = k_gemm_w8<TERMS>;
+  static uint64_t configured = 0;
+  const hipError_t e = set_dynamic_lds(reinterpret_cast<const void*>(kern), W_LDS_BYTES, c->cfg.device, configured);
+  if (e != hipSuccess) return e;
   const int gx = g.swizzle == 2 ? ((g.tiles_m + 7) / 8) * 8 * g.tiles_n : g.tiles_m * g.tiles_n;
   hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)g.batch.groups), dim3(WNTH), W_LDS_BYTES, c->stream, g);
   return hipGetLastError();
@@ -380,7 +308,8 @@ hipError_t launch_w8(rgcn_ctx* c, const XArgs& g) {
 
 }  // namespace
 
-// A k-contiguous with 16-byte rows, B pre-split (batch->bfrag), no split over K: the caller (gemm_bf16x3_launch) checks.
+// A k-contiguous with 16-byte rows, B pre-split (batch->bfrag), no split over K, batch.limit on the rows: the caller
+// (gemm_bf16x3_launch) checks.
 hipError_t gemm_bf16x3_w8_launch(rgcn_ctx* c, int terms, int M, int N, int K, const float* A, int lda, float* C, int ldc,
                                  int swizzle, int vecC, const GemmBatch& batch) {
   XArgs g;
@@ -392,28 +321,8 @@ hipError_t gemm_bf16x3_w8_launch(rgcn_ctx* c, int terms, int M, int N, int K, co
   g.tiles_m = (M + WBM - 1) / WBM;
   g.tiles_n = (N + WBN - 1) / WBN;
   g.nt32 = bfrag_nt32(N);
-  g.tl = nullptr;
-#ifdef RGCN_DEVTOOLS
-  // RGCN_GEMM_W8 = 1000 + DBG: the ablations and timelines of tools/gemm_w8_lab.py (mode 6 only)
-  const int v = knob("RGCN_GEMM_W8", 1);
-  if (v == 4 && terms == 6) return launch_w8<6, DBG_NT_STORE>(c, g);
-  if (v >= 1000 && terms == 6) {
-    g.tl = reinterpret_cast<uint64_t*>(c->debug_buf);
-    switch (v - 1000) {
-#define W8_CASE(D) case D: return launch_w8<6, D>(c, g);
-      W8_CASE(1) W8_CASE(2) W8_CASE(4) W8_CASE(8) W8_CASE(16) W8_CASE(32) W8_CASE(3) W8_CASE(7) W8_CASE(15) W8_CASE(31)
-      W8_CASE(63) W8_CASE(64) W8_CASE(128) W8_CASE(24) W8_CASE(26) W8_CASE(256) W8_CASE(320)
-#undef W8_CASE
-      default: break;
-    }
-  }
-#endif
   if (terms == 9) return launch_w8<9>(c, g);
   return launch_w8<6>(c, g);
-}
-
-size_t gemm_w8_timeline_bytes(int M, int N, int groups) {
-  return (size_t)((M + WBM - 1) / WBM + 8) * ((N + WBN - 1) / WBN) * groups * 8 * TL_SLOTS * 8;
 }
 
 }  // namespace rgcn

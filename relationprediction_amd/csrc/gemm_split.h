@@ -31,8 +31,18 @@ struct XArgs {
   GemmBatch batch;    // groups (blockIdx.y) and their device-side extents
   const u32x4* bfrag; // B_PRE instantiations: B pre-split into MFMA fragments (k_presplit_b), [ktiles][nt32][3][2][32]
   int nt32;           // 32-column tiles of the fragment table (bfrag_nt32(N))
-  uint64_t* tl;       // devtools builds: per-wavefront timeline of k_gemm_w8<.., DBG_TIMELINE>, else nullptr
 };
+
+// Raise a kernel's dynamic-LDS limit on the current device (the context's: every API entry selects it) the first time it
+// launches there.  hipFuncSetAttribute acts on one device, so `done` holds one bit per device id (one word per kernel;
+// contexts are single-threaded per process); past 64 devices the attribute is set on every launch.
+inline hipError_t set_dynamic_lds(const void* kern, int bytes, int device, uint64_t& done) {
+  const uint64_t bit = device < 64 ? 1ull << device : 0;
+  if (done & bit) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) done |= bit;
+  return e;
+}
 
 constexpr int BM = 128, BN = 128, BK = 16, NTH = 256;
 constexpr int KC_LD = 12;                 // dwords per row of a k-contiguous plane (8 + 4 pad)
@@ -50,7 +60,7 @@ using f32x2 = __attribute__((ext_vector_type(2))) float;
 // difference is exactly representable: no rounding happens at any level and x = hi + mid + lo + (a
 // remainder below 2^-26 |x| that is zero unless all three roundings went the same way).
 // (v_dot2c_f32_bf16 against the pairs (-1, -0), (-0, -1) computes the same residuals in one instruction,
-// but it holds up the matrix pipe for ~10 cycles where a plain VALU op costs 2: tools/mfma_fill.hip.)
+// but it holds up the matrix pipe for ~10 cycles where a plain VALU op costs 2: profiles/r01_mfma_valu_fill.log.)
 // negmask (0 or 0x80000000, first level of the A operand only) splits -x instead of x: see the accumulator sign groups
 // in the kernel.
 template <int I0, int I1>

@@ -56,7 +56,7 @@ StreamScope::~StreamScope() { c->stream = saved; }
 
 rgcn_status stream_join(rgcn_ctx* c, int k) {
   if (c->stream != c->main_stream) return RGCN_OK;
-  // a join costs the main stream ~3.6 us even when the side stream is idle (tools/anyorder_probe.hip): skip it when
+  // a join costs the main stream ~3.6 us even when the side stream is idle (profiles/r02_anyorder_probe.log): skip it when
   // nothing went to that stream since its last join (side streams switched off, or no fork taken)
   if (!c->aux_dirty[k]) return RGCN_OK;
   c->aux_dirty[k] = false;
@@ -1016,11 +1016,9 @@ rgcn_status rgcn_capture_begin(rgcn_ctx* c) {
   // A captured step is recorded as ONE chain on the main stream (only the prefetch of the next graph forks off):
   // the replayed graph pays more than streams do for every cross-stream edge (measured, profiles/r02_hipgraph_ab.log:
   // 0.687 ms per step with the side streams captured, 0.634-0.640 as a chain, 0.614-0.631 stream-launched), and
-  // the side streams buy the stream-launched step under 3 %.
-  // (devtools knob RGCN_CAPTURE_STREAMS=1 records the stream-launched step's own fork / join DAG instead: the A/B of
-  // every round, tools/gpu_r6_capture_ab.sh)
+  // the side streams buy the stream-launched step under 3 % (the last A/B of the two captures: profiles/r06_hipgraph_ab.md).
   c->use_aux_before_capture = c->use_aux;
-  if (knob("RGCN_CAPTURE_STREAMS", 0) != 1) c->use_aux = false;
+  c->use_aux = false;
   hipLaunchKernelGGL(k_bump_counter, dim3(1), dim3(1), 0, c->main_stream, c->replay_counter);
   return RGCN_OK;
 }

@@ -1,8 +1,5 @@
 // Entry points that exist in librgcn_devtools.so only (include/rgcn_devtools.h): the dense contractions on their own, the
 // XCD placement probe.  The product library compiles this file to nothing.
-#include <cstdio>
-#include <vector>
-
 #include "rgcn_api_internal.h"
 
 using namespace rgcn;
@@ -79,19 +76,6 @@ rgcn_status rgcn_debug_gemm_presplit(rgcn_ctx* c, int32_t tb, int32_t M, int32_t
     s = gemm_f32(c, "debug_gemm", true, tb != 0, M, N, K, A, K, B, tb ? K : N, C, N, 1, &gb);
     if (s != RGCN_OK) break;
     if ((s = to_host(c, c_host, C, sizeof(float) * (size_t)M * N)) != RGCN_OK) break;
-    // RGCN_GEMM_TL_FILE: the per-wavefront stamps of ONE more launch (k_gemm_w8<.., DBG_TIMELINE / DBG_FINE>), raw uint64
-    if (const char* tlf = getenv("RGCN_GEMM_TL_FILE")) {
-      const size_t tb_bytes = gemm_w8_timeline_bytes(M, N, 1);
-      if (hipMalloc(&c->debug_buf, tb_bytes) != hipSuccess) { s = RGCN_ERR_NOMEM; break; }
-      (void)hipMemsetAsync(c->debug_buf, 0, tb_bytes, c->stream);
-      s = gemm_f32(c, "debug_gemm", true, tb != 0, M, N, K, A, K, B, tb ? K : N, C, N, 1, &gb);
-      std::vector<char> hb(tb_bytes);
-      if (s == RGCN_OK) s = to_host(c, hb.data(), c->debug_buf, tb_bytes);
-      (void)hipFree(c->debug_buf);
-      c->debug_buf = nullptr;
-      if (s != RGCN_OK) break;
-      if (FILE* f = fopen(tlf, "wb")) { fwrite(hb.data(), 1, tb_bytes, f); fclose(f); }
-    }
     if (iters > 0 && avg_ms) {
       if ((s = rgcn_timer_start(c)) != RGCN_OK) break;
       for (int it = 0; it < iters && s == RGCN_OK; ++it)

@@ -370,7 +370,6 @@ struct rgcn_ctx {
   float* colsum_part = nullptr;
   size_t colsum_part_floats = 0;
   int32_t colsum_parts = 0;    // > 0: the last block_rows backward launch left that many [d] partial rows in colsum_part
-  void* debug_buf = nullptr;             // devtools builds: where k_gemm_w8<.., DBG_TIMELINE> leaves its stamps
   float* zeros = nullptr;                // 1024 zero floats (masked-lane load target of the GEMMs; 3 KB for a masked LDS-DMA)
 
   rgcn::GraphBufs g;                     // ACTIVE graph structures
@@ -433,7 +432,7 @@ namespace rgcn {
 // prefetched graph structures, the decoder batch, the sampler's state).  A default hipEventRecord is a barrier packet with a
 // system-scope release and acquire; what these events order is kernels of one device, each of which already carries its
 // agent-scope fences, so on one GPU the event's own fence is dropped: 0.528-0.534 ms per headline step against 0.535-0.543,
-// three interleaved runs each on one box (release-to-device scope: 0.538-0.540; tools/gpu_r5_evflag.sh).  A sharded
+// three interleaved runs each on one box (release-to-device scope: 0.538-0.540).  A sharded
 // context, whose buffers other ranks' kernels read and write, keeps the default.
 // kernel_only: the event orders kernels against kernels (fork, join).  Events that can also order copy-engine work -- a
 // graph set's ready / free (host staging copies and memsets on the prefetch stream), the sampler's draw, the decoder batch's
@@ -533,7 +532,6 @@ hipError_t gemm_bf16x3_launch(rgcn_ctx* c, int terms, bool a_kc, bool b_kc, bool
 // gemm_bf16x3_w8.hip: the form for a pre-split weight on the B side (A k-contiguous with 16-byte rows, no split over K)
 hipError_t gemm_bf16x3_w8_launch(rgcn_ctx* c, int terms, int M, int N, int K, const float* A, int lda, float* C, int ldc,
                                  int swizzle, int vecC, const GemmBatch& batch);
-size_t gemm_w8_timeline_bytes(int M, int N, int groups);
 
 // ---- block_msgs.hip
 rgcn_status block_geometry(rgcn_ctx* c);

@@ -1,9 +1,13 @@
 #!/usr/bin/env python
-"""Readable table of a bench.py JSON line (headline workload, the workloads array, per-kernel durations)."""
+"""Readable table of a bench.py --full run (headline workload, the workloads array, per-kernel durations): the JSON line
+    python tools/bench_table.py LINE_FILE [-v]
+and the bench_details.json its "details" names, where the tables are."""
 import json
 import sys
 
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
+if "kernels" not in d and d.get("details"):
+    d = json.load(open(d["details"]))
 
 
 def line(o):

@@ -17,17 +17,6 @@ forms = {
     "TN Ht.dS": (True, False, D, D, V),
 }
 eng = nat.Engine(64, 3, 20, 1, "block", 4, max_edges=16, devtools=True)
-if os.environ.get("RGCN_PROBE_ONLY"):
-    # NT form at one and two tiles per CU (mode 6): the lone-workgroup critical path under RGCN_GEMM_ABLATE
-    eng.set_gemm_mode(6)
-    line = "ablate %s:" % os.environ.get("RGCN_GEMM_ABLATE", "0")
-    for M in (8192, 16384):
-        a = rng.normal(0, 1, (M, D)).astype(np.float32)
-        b = rng.normal(0, 0.19, (D, D)).astype(np.float32)
-        line += "  %d tiles %.1f us" % (M // 128 * 4, eng.debug_gemm_time(a, b, trans_b=True, iters=iters) * 1e3)
-    print(line, flush=True)
-    eng.close()
-    sys.exit(0)
 for name, (ta, tb, M, N, K) in forms.items():
     # activations like the encoder's: relu'd normal mixture for A-side, N(0, 0.19) weights / small grads
     a = rng.normal(0, 1, (K, M) if ta else (M, K)).astype(np.float32)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Summarise rocprofv3 (rocpd sqlite) outputs of tools/gpu_profile.sh into a markdown table.
 
-    python tools/rocprof_summary.py gpurun_out/prof_r01 profiles/r01_rocprof_summary.md
+    python tools/rocprof_summary.py run_logs/prof_TAG_WORKLOAD run_logs/TAG_rocprof_WORKLOAD.md [command]
 
 kernel-trace pass -> calls / average duration per kernel; PMC passes -> FETCH_SIZE / WRITE_SIZE (KB per
 dispatch).  Bytes per launch = (2*FETCH_SIZE + WRITE_SIZE) * 1024: on gfx950 FETCH_SIZE reports
@@ -49,7 +49,7 @@ def counter_avg(db, counter):
 
 def main():
     d, outp = sys.argv[1], sys.argv[2]
-    cmd = sys.argv[3] if len(sys.argv) > 3 else "python bench.py --steps 20 --warmup 5 --cpu-steps 0 --no-kernel-profile"
+    cmd = sys.argv[3] if len(sys.argv) > 3 else "python bench.py --steps 20 --warmup 5"
     ks = kernel_stats(d + "/trace/trace_results.db")
     try:
         fetch = counter_avg(d + "/pmc_fetch/fetch_results.db", "FETCH_SIZE")

@@ -200,7 +200,10 @@ rgcn_status rgcn_step_device(rgcn_ctx* ctx, const int32_t* triples_dev, int64_t 
  * the train graph: BilinearDiag.get_loss + local_get_regularization (code/decoders/bilinear_diag.py:27-34,
  * 63-69) and their tf.gradients.  Needs rgcn_decoder_reserve(max N) once and a completed rgcn_forward.
  * Leaves dL/dcodes in rgcn_dcodes_device() (feed it to rgcn_backward_device) and dL/dW_relation in the
- * gradient of the last parameter; rgcn_get_loss returns loss + regulariser (synchronises). */
+ * gradient of the last parameter; rgcn_get_loss returns loss + regulariser (synchronises).
+ * max_triples (and a tiled batch's n * (rate + 1)) may not exceed RGCN_MAX_DECODER_TRIPLES: the decoder's kernels
+ * index with 32-bit ints, whose largest expressions are 3 N + 2 and 2 N + 255. */
+#define RGCN_MAX_DECODER_TRIPLES ((int64_t)1 << 29)
 rgcn_status rgcn_decoder_reserve(rgcn_ctx* ctx, int64_t max_triples);
 rgcn_status rgcn_decoder_loss_backward_device(rgcn_ctx* ctx, const int32_t* x_dev, const float* y_dev,
                                               int64_t num_triples, float regularization_parameter);

@@ -713,7 +713,7 @@ rgcn_status rgcn_step_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t E, int
 // ---- decoder / optimizer / whole train step ("next" rows f1, f2) ---------------------------------
 rgcn_status rgcn_decoder_reserve(rgcn_ctx* c, int64_t max_triples) {
   RGCN_NEED(c);
-  if (max_triples <= 0 || max_triples > ((int64_t)1 << 30)) RGCN_FAIL(c, RGCN_ERR_INVALID, "max_triples out of range");
+  if (max_triples <= 0 || max_triples > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "max_triples out of range");
   RGCN_TRY(sync_all(c));
   return decoder_reserve(c, max_triples);
 }
@@ -758,7 +758,7 @@ rgcn_status rgcn_negative_sample_device(rgcn_ctx* c, const int32_t* batch_dev, i
   RGCN_NEED(c);
   if (n < 0 || rate < 0 || rate > 1024 || (n > 0 && (!batch_dev || !x_out_dev || !y_out_dev)))
     RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
-  if (n * (int64_t)(rate + 1) > ((int64_t)1 << 30)) RGCN_FAIL(c, RGCN_ERR_INVALID, "batch too large");
+  if (n * (int64_t)(rate + 1) > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "batch too large");
   return negative_sample(c, batch_dev, n, rate, seed, x_out_dev, y_out_dev);
 }
 

@@ -1,0 +1,172 @@
+"""The decoder's kernel-variant table (tests/decoder_grid.py) covers every compiled variant of decoder_compute, and every
+case's batch holds the rows and relations it claims.  No GPU: a later edit of the table that drops a cell fails here,
+naming the cell."""
+import os
+
+import numpy as np
+import pytest
+
+import decoder_grid as dg
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "relationprediction_amd", "csrc")
+
+
+def _cells(stage):
+    return {dg.cell_of(c)[stage] for c in dg.DECODER_GRID}
+
+
+def test_every_energy_kernel_variant_is_in_the_table():
+    have = _cells(0)
+    missing = [cell for cell in dg.ENERGY_CELLS if cell not in have]
+    assert not missing, "energy / relation-partial variants without a case: %s" % missing
+
+
+def test_every_entity_gradient_variant_is_in_the_table():
+    have = _cells(1)
+    missing = [cell for cell in dg.ENTITY_CELLS if cell not in have]
+    assert not missing, "entity-gradient variants without a case: %s" % missing
+
+
+def test_every_variant_meets_long_rows():
+    """k_dec_long_finish<VEC> follows the vector width: both widths need a case whose batch has pieces."""
+    have = {dg.vec_width(c["d"]) for c in dg.DECODER_GRID if c["n"] > 1}
+    assert have == {1, 4}, "k_dec_long_finish widths without a long row: %s" % sorted({1, 4} - have)
+
+
+def test_dispatch_boundaries_are_in_the_table():
+    # plain cases: the shipped relation count, an untiled batch, unscaled weights
+    ds = {c["d"] for c in dg.DECODER_GRID if c["R"] == dg.R_DEC and c["rate"] is None and not c["saturate"]}
+    missing = [d for d in (20, 256, 260, 500, 512, 516, 1024, 1028, 9, 63, 66, 126, 130, 255, 258, 1030) if d not in ds]
+    assert not missing, "widths d at the dispatch boundaries without a case: %s" % missing
+    # the line form: one partial band; eight bands in one pass; two, three and five passes
+    assert any(dg.bands(d) == 1 and d % dg.LINE for d in ds if dg.vec_width(d) == 4)
+    passes = {dg.band_passes(d) for d in ds if dg.vec_width(d) == 4}
+    missing = [p for p in (1, 2, 3, 5) if p not in passes]
+    assert not missing, "band-pass counts of k_dec_entity_lines without a case: %s" % missing
+    assert any(dg.bands(d) == 8 for d in ds if dg.vec_width(d) == 4)
+    # k_dec_rel_partial: three column passes at VEC 4, nine at VEC 1
+    assert {dg.rel_partial_passes(d) for d in ds if dg.energy_cell(d)[0] == "energy"} >= {3, 9}
+
+
+def test_relation_table_boundaries_are_in_the_table():
+    have = {(c["d"], c["R"]) for c in dg.DECODER_GRID}
+    missing = [k for k in ((20, 512), (20, 513), (260, 512), (260, 513), (1028, 513)) if k not in have]
+    assert not missing, "(d, R) cases at the 64 KB LDS bound without a case: %s" % missing
+    assert dg.relation_lds(512) and not dg.relation_lds(513)
+
+
+def test_saturation_and_tiled_batches_are_in_the_table():
+    assert any(c["saturate"] and c["saturate"] > 90 for c in dg.DECODER_GRID), "no saturated-energy case"
+    tiled = {(c["rate"], c["n"] > 1) for c in dg.DECODER_GRID if c["rate"] is not None}
+    missing = [k for k in ((10, True), (1, True), (0, True)) if k not in tiled]
+    assert not missing, "tiled batches (rate, n > 1) without a case: %s" % missing
+    assert any(c["n"] == 1 and dg.copies(c) == 1 for c in dg.DECODER_GRID), "no single-triple (untiled) sampler batch"
+
+
+def test_train_step_subset():
+    cells = {dg.cell_of(dg.DECODER_CASES[n]) for n in dg.TRAIN_STEP_CASES}
+    energy = {e for e, _ in cells}
+    entity = {f for _, f in cells}
+    assert {("energy_rel", 1, 2), ("energy_rel", 1, 4), ("energy", 1, None), ("energy", 4, None)} <= energy
+    assert {("lines", True), ("lines", False), ("rows", 1, 128), ("rows", 1, 256)} <= entity
+    assert all(dg.DECODER_CASES[n]["rate"] is None for n in dg.TRAIN_STEP_CASES)
+
+
+@pytest.mark.parametrize("name", sorted(dg.DECODER_CASES))
+def test_case_batch_has_its_counts(name):
+    """Counted over both sides of the batch (the first copies of a tiled one): every entity row and relation count of
+    the table, the hub reached as subject and as object, s == o triples, ids in range."""
+    c = dg.DECODER_CASES[name]
+    X, Y = dg.case_batch(c)
+    assert X.shape == (c["n"], 3) and X.dtype == np.int32
+    assert X[:, [0, 2]].min() >= 0 and X[:, [0, 2]].max() < c["V"] and X[:, 1].min() >= 0 and X[:, 1].max() < c["R"]
+    assert (Y is None) == (c["rate"] is not None)
+    if c["n"] == 1:
+        return
+    inc = dg.incidences(X, c["V"])
+    assert inc.sum() == 2 * c["n"]
+    for e, want in enumerate(dg.ENTITY_COUNTS):
+        assert inc[e] == want, "%s: entity %d has %d incidences, not %d" % (name, e, inc[e], want)
+    assert inc[len(dg.ENTITY_COUNTS):].max() <= dg.LONG_ROW, "%s: an ordinary entity took a long row" % name
+    assert [dg.pieces(n) for n in dg.ENTITY_COUNTS] == [0, 0, 0, 1, 1, 2, 3]
+    hub = len(dg.ENTITY_COUNTS) - 1
+    assert ((X[:, 0] == hub) & (X[:, 2] != hub)).any() and ((X[:, 2] == hub) & (X[:, 0] != hub)).any(), name
+    assert (X[:, 0] == X[:, 2]).sum() >= dg.SELF_EDGES + 1 and ((X[:, 0] == hub) & (X[:, 2] == hub)).any(), name
+    rc = np.bincount(X[:, 1], minlength=c["R"])
+    want = dg.rel_counts(c)
+    assert list(rc[:len(want)]) == list(want), "%s: relation counts %s, not %s" % (name, list(rc[:len(want)]), want)
+    # decoded (x copies): an empty relation, a partial chunk, a chunk boundary hit exactly and one passed by at most one
+    # copy, and a relation of at least five chunks (k_dec_rel_reduce's 4-way turn and its tail)
+    k = dg.copies(c)
+    decoded = [n * k for n in want]
+    assert 0 in decoded and any(0 < n < dg.CHUNK for n in decoded)
+    assert any(n and n % dg.CHUNK == 0 for n in decoded)
+    assert any(n > dg.CHUNK and 0 < n % dg.CHUNK <= k for n in decoded)
+    assert max(dg.chunks(n) for n in decoded) >= 5
+    if Y is not None:
+        assert 0 < Y.sum() < len(Y)
+
+
+def test_host_tiled_layout():
+    X, _ = dg.case_batch(dg.DECODER_CASES["dec_d20_rate10"])
+    T, Y = dg.host_tiled(X, 10, dg.V_DEC, 1)
+    n = len(X)
+    assert T.shape == (11 * n, 3) and np.array_equal(T[:n], X) and (Y[:n] == 1).all() and not Y[n:].any()
+    assert np.array_equal(T[:, 1], np.tile(X[:, 1], 11))
+    assert not ((T[n:, 0] != np.tile(X, (10, 1))[:, 0]) & (T[n:, 2] != np.tile(X, (10, 1))[:, 2])).any()
+
+
+def test_case_shapes_are_valid_configurations():
+    for name, c in dg.DECODER_CASES.items():
+        assert c["d"] % c["nb"] == 0 and c["d"] // c["nb"] in dg.BLOCK_SIZES and c["nb"] <= dg.MAX_BLOCKS, name
+        assert c["V"] % 8 != 0 and c["L"] == 1 and c["kind"] == "block", name
+        assert c["R"] <= c["V"], name           # relation ids index W_relation, which has V rows
+
+
+@pytest.mark.parametrize("source,text", [
+    ("decoder.hip", "const bool fused = nvec_e <= 256;"),
+    ("decoder.hip", "const int T = nvec_e <= 64 ? 1 : (nvec_e <= 128 ? 2 : 4);"),
+    ("decoder.hip", "const int tpr = nvec <= 64 ? 64 : (nvec <= 128 ? 128 : 256);"),
+    ("decoder.hip", "const bool rlds = lds <= 64 * 1024;"),
+    ("decoder.hip", "const size_t lds = (size_t)R * kLine * sizeof(float);"),
+    ("decoder.hip", "const bool vec4 = (d % 4 == 0) && aligned16(codes)"),
+    ("decoder.hip", "const bool lines = vec4 && knob(\"RGCN_DEC_LINES\", 1) != 0"),
+    ("decoder.hip", "for (int band = x, pass = 0; band < b.nbands; band += 8, ++pass) {"),
+    ("decoder.hip", "q.nbands = (int32_t)((d + kLine - 1) / kLine);"),
+    ("decoder.hip", "const int np = (end - beg + kDecPiece - 1) / kDecPiece;"),
+    ("decoder.hip", "for (int c0 = 0; c0 < nvec; c0 += 128) {"),
+    ("decoder.hip", "q.tiled_period > 1 &&"),
+    ("decoder.hip", "constexpr int kDecLongRow = 256;"),
+    ("decoder.hip", "constexpr int kDecPiece = 512;"),
+    ("decoder.hip", "constexpr int kDecChunk = 128;"),
+    ("decoder.hip", "constexpr int kLine = 32;"),
+    ("../../include/rgcn.h", "#define RGCN_MAX_DECODER_TRIPLES ((int64_t)1 << 29)"),
+    ("rgcn_api.hip", "if (max_triples <= 0 || max_triples > RGCN_MAX_DECODER_TRIPLES)"),
+    ("rgcn_api.hip", "if (n * (int64_t)(rate + 1) > RGCN_MAX_DECODER_TRIPLES)"),
+])
+def test_host_mirrors_follow_the_kernel_sources(source, text):
+    """The mirrors in decoder_grid.py are copies of these dispatch lines: when one changes, the table has to be
+    re-derived."""
+    with open(os.path.join(CSRC, source)) as f:
+        assert text in f.read(), "%s no longer holds `%s`: update tests/decoder_grid.py's mirror" % (source, text)
+
+
+def test_batch_bound_keeps_the_decoder_indices_in_int32():
+    """The largest int expressions of the decoder path at N = the bound: 3 N + 2 (X[3 * n + 2]) and the launch size
+    2 N + 255 (k_dec_keys, k_dec_slots; lower_bound_u32 over 2 N keys)."""
+    N = dg.MAX_DECODER_TRIPLES
+    assert 3 * (N - 1) + 2 < 2 ** 31 and 2 * N + 255 < 2 ** 31
+    assert 3 * (2 ** 30 - 1) + 2 >= 2 ** 31                  # the old bound did overflow
+
+
+def test_mirrors_on_known_configurations():
+    assert [dg.energy_cell(d) for d in (20, 256, 260, 512, 516, 1024, 1028)] == \
+        [("energy_rel", 4, 1)] * 2 + [("energy_rel", 4, 2)] * 2 + [("energy_rel", 4, 4)] * 2 + [("energy", 4, None)]
+    assert [dg.energy_cell(d) for d in (9, 63, 66, 126, 130, 255, 258)] == \
+        [("energy_rel", 1, 1)] * 2 + [("energy_rel", 1, 2)] * 2 + [("energy_rel", 1, 4)] * 2 + [("energy", 1, None)]
+    assert [dg.entity_tpr(d) for d in (9, 63, 66, 126, 130, 255, 258)] == [64, 64, 128, 128, 256, 256, 256]
+    assert [dg.bands(d) for d in (20, 256, 260, 516, 1028)] == [1, 8, 9, 17, 33]
+    assert [dg.band_passes(d) for d in (20, 256, 260, 516, 1028)] == [1, 1, 2, 3, 5]
+    assert dg.rel_partial_passes(1028) == 3 and dg.rel_partial_passes(1030) == 9
+    assert dg.entity_cell(500, 237) == ("lines", True) and dg.entity_cell(20, 513) == ("lines", False)

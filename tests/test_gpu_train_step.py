@@ -5,6 +5,7 @@ import pytest
 
 import oracle
 import helpers
+import decoder_grid as dg
 from helpers import assert_close, make_case
 
 pytestmark = pytest.mark.gpu
@@ -652,4 +653,219 @@ def test_train_step_at_baseline_scale_optimizer_replay(native):
         for b in (bd, xd, yd):
             b.free()
     finally:
+        eng.close()
+
+
+# ------------------------------------------------------------------ the decoder's kernel variants (tests/decoder_grid.py)
+def _grid_energies(codes, w_rel, X):
+    c, w = codes.astype(np.float64), w_rel.astype(np.float64)
+    return (c[X[:, 0]] * w[X[:, 1]] * c[X[:, 2]]).sum(1)
+
+
+def _grid_decoder(native, c):
+    """A test-mode forward and the device decoder on a grid case: (codes, W_relation, X, Y, loss, dcodes, dW_relation).
+    A tiled case's batch goes through the device negative sampler; a saturating one has W_relation scaled (after a
+    first forward: the codes do not depend on it) until its largest |energy| is c["saturate"]."""
+    V, R, d, nb = c["V"], c["R"], c["d"], c["nb"]
+    params, triples, _, _ = make_case(V, R, d, 1, "block", nb, 4 * V, seed=c["seed"])
+    batch, Y = dg.case_batch(c)
+    eng = native.Engine(V, R, d, 1, "block", nb, max_edges=len(triples))
+    bufs = []
+    try:
+        eng.set_params(params)
+        eng.set_graph(triples)
+        eng.forward(train=False)
+        if c["saturate"]:
+            x = _grid_energies(eng.codes(), params["W_relation"], batch)
+            params["W_relation"] = (params["W_relation"] * (c["saturate"] / np.abs(x).max())).astype(np.float32)
+            eng.set_params(params)
+            eng.forward(train=False)
+        codes = eng.codes()
+        if c["rate"] is None:
+            X, N = batch, len(batch)
+            eng.decoder_reserve(N)
+            xd, yd = eng.to_device(X), eng.to_device(Y)
+            bufs += [xd, yd]
+        else:
+            N = c["n"] * (c["rate"] + 1)
+            eng.decoder_reserve(N)
+            bd, xd, yd = eng.to_device(batch), eng.alloc(12 * N), eng.alloc(4 * N)
+            bufs += [bd, xd, yd]
+            eng.negative_sample_device(bd, c["n"], c["rate"], c["seed"], xd, yd)
+            X, Y = xd.download(np.int32, (N, 3)), yd.download(np.float32, (N,))
+            assert np.array_equal(X[:c["n"]], batch)
+        eng.decoder_loss_backward_device(xd, yd, N, 0.01)
+        out = codes, params["W_relation"], X, Y, eng.loss(), eng.dcodes(), eng.get_grad("W_relation")
+    finally:
+        for b in bufs:
+            b.free()
+        eng.close()
+    return out
+
+
+@pytest.mark.parametrize("name", sorted(dg.DECODER_CASES))
+def test_decoder_grid_matches_float64(native, name):
+    """Every compiled variant of decoder_compute (tests/decoder_grid.py) against the float64 restatement at the engine's
+    own codes, at test_decoder_at_baseline_scale's bar: loss to 2e-6, every entry of dL/dcodes and dL/dW_relation within
+    5e-6 of the tensor's scale (no excused fraction), l2 error no worse than 4x the fp32 oracle's; exact zeros where no
+    triple reaches: entities without an incidence, relations without a triple, the rows >= R of W_relation."""
+    c = dg.DECODER_CASES[name]
+    codes, w_rel, X, Y, loss, dcodes, dwrel = _grid_decoder(native, c)
+    R, V = c["R"], c["V"]
+    if c["saturate"]:
+        assert np.abs(_grid_energies(codes, w_rel, X)).max() > 90
+    oloss, odcodes, odwrel = helpers.chunked_distmult_float64(codes, w_rel, X, Y, 0.01)
+    floss, fdcodes, fdwrel = oracle.distmult_loss_and_grads(codes, w_rel, X, Y, 0.01)
+    report, bad = ["loss %.1e" % (abs(loss - oloss) / abs(oloss))], []
+    if not abs(loss - oloss) <= 2e-6 * abs(oloss):
+        bad.append("loss %.9g, float64 %.9g" % (loss, oloss))
+    for got, want, fp32, what in ((dcodes, odcodes, fdcodes, "dcodes"), (dwrel, odwrel, fdwrel, "dW_relation")):
+        worst, l2 = helpers.error_against(want, got)
+        oworst, ol2 = helpers.error_against(want, fp32)
+        report.append("%s %.1e/%.1e (oracle %.1e/%.1e)" % (what, worst, l2, oworst, ol2))
+        if not worst <= 5e-6:
+            bad.append("%s against float64: max %.2e of scale" % (what, worst))
+        if not l2 <= 4 * ol2 + 1e-7:
+            bad.append("%s: l2 %.2e, the fp32 oracle's %.2e" % (what, l2, ol2))
+    print(name, dg.cell_of(c), "; ".join(report))
+    assert not bad, bad
+    inc = dg.incidences(X, V)
+    assert (inc == 0).any() or c["n"] == 1 or c["rate"] is not None
+    assert not dcodes[inc == 0].any() and dcodes[inc > 0].any(axis=1).all()
+    rc = np.bincount(X[:, 1], minlength=R)
+    assert (rc == 0).any()
+    assert not dwrel[:R][rc == 0].any() and dwrel[:R][rc > 0].any(axis=1).all()
+    assert not dwrel[R:].any()
+
+
+@pytest.mark.parametrize("name", sorted(n for n, c in dg.DECODER_CASES.items() if dg.vec_width(c["d"]) == 4))
+def test_entity_gradient_forms_are_bitwise_equal_on_the_grid(native, name):
+    """test_entity_gradient_forms_are_bitwise_equal on every float4 case of the grid: k_dec_entity_lines (R <= 512: the
+    relation band in LDS, R = 513: from global memory) against k_dec_entity_grad<4, TPR> at every TPR, pieces of every
+    count.  A tiled case's rows are laid out on the host as the sampler lays them out."""
+    c = dg.DECODER_CASES[name]
+    X, Y = dg.case_batch(c)
+    if c["rate"] is not None:
+        X, Y = dg.host_tiled(X, c["rate"], c["V"], c["seed"])
+    a = _decoder_grads(native, c["V"], c["R"], c["d"], c["nb"], X, Y, lines=False, seed=c["seed"])
+    b = _decoder_grads(native, c["V"], c["R"], c["d"], c["nb"], X, Y, lines=True, seed=c["seed"])
+    assert a[0] == b[0]
+    assert np.array_equal(a[1], b[1]), float(np.abs(a[1] - b[1]).max())
+    assert np.array_equal(a[2], b[2])
+    assert np.abs(a[1]).max() > 0
+
+
+def _grid_train_steps(native, c, params, triples, X, Y, steps, max_norm=None, eps=1e-8):
+    """`steps` train steps (L = 2, keep_prob 0.8) on one context; clip + Adam only when max_norm is given.  Per step:
+    the activations, dropout masks, gradients and the weights after it."""
+    V, R, d, nb, L = c["V"], c["R"], c["d"], c["nb"], 2
+    eng = native.Engine(V, R, d, L, "block", nb, keep_prob=0.8, max_edges=len(triples))
+    bufs, out = [], []
+    try:
+        eng.set_params(params)
+        eng.decoder_reserve(len(X))
+        if max_norm is not None:
+            eng.optimizer_config(lr=0.01, beta1=0.9, beta2=0.999, eps=eps, max_grad_norm=max_norm)
+        td, xd, yd = eng.to_device(triples), eng.to_device(X), eng.to_device(Y)
+        bufs += [td, xd, yd]
+        for step in range(steps):
+            eng.train_step_device(td, len(triples), xd, yd, len(X), seed=60 + step, reg_param=0.01)
+            out.append(dict(acts=[eng.activation(l) for l in range(L + 1)],
+                            masks=[eng.dropout_mask(l) for l in range(1, L + 1)],
+                            grads=eng.get_grads(), params=eng.get_params()))
+    finally:
+        for b in bufs:
+            b.free()
+        eng.close()
+    return out
+
+
+@pytest.mark.parametrize("name", dg.TRAIN_STEP_CASES)
+def test_train_step_grid_matches_float64(native, name):
+    """What consumes the decoder in a train step, on the grid's scalar T 2 / T 4 / unfused cases, the float4 d = 260 and
+    1028 and the global relation band (R = 513), each with its 1025-incidence hub (k_dec_long_finish): on one GPU the
+    entity-gradient kernel also writes dL/dcodes x dropout for the top layer's self-loop GEMMs (ds_ready,
+    store_dcodes).  Every encoder gradient against the float64 reverse mode at the engine's own activations, fed with the
+    float64 decoder gradient: max 5e-6 of scale, l2 2e-6 (test_float64_tie_break's bar).  Then clip + Adam with the clip
+    active, inactive and disabled (max_grad_norm = 0), two steps each replayed in float64 from the device gradients."""
+    c = dg.DECODER_CASES[name]
+    V, R, d, nb, L = c["V"], c["R"], c["d"], c["nb"], 2
+    params, triples, _, _ = make_case(V, R, d, L, "block", nb, 4 * V, seed=c["seed"])
+    X, Y = dg.case_batch(c)
+    names = [k for k in oracle.weight_names("block", L) if not (k.startswith("b") and k != "b_emb")]
+    s = _grid_train_steps(native, c, params, triples, X, Y, 1)[0]
+    _, dc64, dw64 = helpers.chunked_distmult_float64(s["acts"][-1], params["W_relation"], X, Y, 0.01)
+    g64 = helpers.float64_grads_at(dict(V=V, R=R, d=d, L=L, kind="block", nb=nb, params=params, triples=triples,
+                                        masks=s["masks"], dcodes=dc64), s["acts"])
+    g64["W_relation"] = dw64
+    report, bad = [], []
+    for k in names:
+        assert np.abs(g64[k]).max() > 0, k
+        worst, l2 = helpers.error_against(g64[k], s["grads"][k])
+        report.append("%s %.1e/%.1e" % (k, worst, l2))
+        if not (worst <= 5e-6 and l2 <= 2e-6):
+            bad.append("%s grad %s against float64: max %.2e l2 %.2e" % (name, k, worst, l2))
+    print(name, "; ".join(report))
+    assert not bad, bad
+    # clip + Adam (tensorflow_backend/algorithms.py:27-42,58-68) from the device's own gradients.  eps = the RMS gradient
+    # entry: Adam's update m / (sqrt(v) + eps) then depends on the clip scale (with eps << |g| it would be ~ sign(g)
+    # whatever the scale), so that a wrong scale cannot pass the replay
+    gn1 = np.sqrt(sum(float((s["grads"][k].astype(np.float64) ** 2).sum()) for k in names))
+    eps = float(np.float32(gn1 / np.sqrt(sum(s["grads"][k].size for k in names))))
+    for regime, max_norm in (("active", float(np.float32(0.1 * gn1))), ("inactive", float(np.float32(10 * gn1))),
+                             ("disabled", 0.0)):
+        cur = {k: v.astype(np.float64) for k, v in params.items()}
+        m = {k: np.zeros_like(cur[k]) for k in names}
+        v = {k: np.zeros_like(cur[k]) for k in names}
+        runs = _grid_train_steps(native, c, params, triples, X, Y, 2, max_norm=max_norm, eps=eps)
+        for step, r in enumerate(runs, 1):
+            grads = {k: r["grads"][k].astype(np.float64) for k in names}
+            gn = np.sqrt(sum(float((g ** 2).sum()) for g in grads.values()))
+            scale = max_norm / max(gn, max_norm) if max_norm > 0 else 1.0
+            assert (scale < 0.5) if regime == "active" else (scale == 1.0), (regime, step, gn, max_norm)
+            lr_t = 0.01 * np.sqrt(1 - 0.999 ** step) / (1 - 0.9 ** step)
+            unclipped = 0.0
+            for k in names:
+                g = grads[k] * scale
+                m[k] = 0.9 * m[k] + 0.1 * g
+                v[k] = 0.999 * v[k] + 0.001 * g * g
+                want = cur[k] - lr_t * m[k] / (np.sqrt(v[k]) + eps)
+                err = float(np.abs(r["params"][k] - want).max())
+                assert err <= 1e-3 * lr_t, (regime, step, k, err)
+                if step == 1:        # the same first step without the clip
+                    alt = cur[k] - lr_t * (0.1 * grads[k]) / (np.sqrt(0.001 * grads[k] ** 2) + eps)
+                    unclipped = max(unclipped, float(np.abs(want - alt).max()))
+                cur[k] = r["params"][k].astype(np.float64)
+            if step == 1:
+                assert (unclipped > 0.05 * lr_t) if regime == "active" else (unclipped < 1e-6 * lr_t), (regime, unclipped)
+            for k in params:
+                if k not in names:
+                    np.testing.assert_array_equal(r["params"][k], params[k])        # unused biases never move
+
+
+def test_decoder_batch_bound_is_refused_up_front(native):
+    """RGCN_MAX_DECODER_TRIPLES (include/rgcn.h): one triple more is refused by rgcn_decoder_reserve and by the device
+    negative sampler (n * (rate + 1) = bound + 1 with rate 2) before anything is allocated or launched, and the context
+    goes on working.  (Never called AT the bound: that reserve would take tens of GB.)"""
+    bound = dg.MAX_DECODER_TRIPLES
+    assert (bound + 1) % 3 == 0
+    eng = native.Engine(40, 5, 8, 1, "block", 2, max_edges=16)
+    bufs = []
+    try:
+        with pytest.raises(native.RgcnError) as err:
+            eng.decoder_reserve(bound + 1)
+        assert "max_triples out of range" in str(err.value)
+        batch = np.array([[1, 2, 3], [4, 0, 5], [6, 1, 7], [8, 4, 9]], np.int32)
+        bd, xd, yd = eng.to_device(batch), eng.alloc(12 * 12), eng.alloc(4 * 12)
+        bufs += [bd, xd, yd]
+        with pytest.raises(native.RgcnError) as err:
+            eng.negative_sample_device(bd, (bound + 1) // 3, 2, 1, xd, yd)
+        assert "batch too large" in str(err.value)
+        eng.negative_sample_device(bd, 4, 2, 1, xd, yd)
+        X = xd.download(np.int32, (12, 3))
+        assert np.array_equal(X[:4], batch) and np.array_equal(X[:, 1], np.tile(batch[:, 1], 3))
+        eng.decoder_reserve(12)
+    finally:
+        for b in bufs:
+            b.free()
         eng.close()

@@ -79,8 +79,9 @@ enum {
    * directed relation r (m < E) or R + r */
   RGCN_BUF_PERM_VERTEX = 8,     /* int32 [2E] incidence ids in incidence-CSR order (by vertex, ties by id) */
   RGCN_BUF_PERM_RELATION = 9,   /* int32 [2E] message ids in message-list order (by directed relation, ties by id) */
-  RGCN_BUF_RANK_ENERGIES = 10   /* float [reserved queries, V] energies of the last chunk rgcn_rank_device scored (the
-                                   float half of the ranking; the counts are integer work on exactly these values) */
+  RGCN_BUF_RANK_ENERGIES = 10   /* float [reserved queries, V] energies of the last chunk rgcn_rank_device or
+                                   rgcn_topk_device scored (the float half of the ranking; the counts and the selection
+                                   are integer work on exactly these values) */
 };
 
 /*
@@ -267,6 +268,35 @@ rgcn_status rgcn_rank_reserve(rgcn_ctx* ctx, int64_t max_queries);
 rgcn_status rgcn_rank_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t num_queries, int32_t predict_object,
                              const int64_t* filter_ptr_dev, const int32_t* filter_idx_dev, int32_t* raw_rank_dev,
                              int32_t* filtered_rank_dev);
+
+/* ---- prediction: the k most plausible entities of a query, best first ------------------------------------
+ * What a trained link predictor is asked: given (s, r, ?) or (?, r, o), which entities complete it.  Selects from the
+ * scores of BilinearDiag.predict_all_object_scores / predict_all_subject_scores (code/decoders/bilinear_diag.py:51-61;
+ * the reference has no top-k call: its users sort the [queries, V] score matrix on the host).
+ * x = int32 [N,3] rows (s, r, o).  predict_object = 1: the candidates are objects, s and r are read, the o column is
+ * NOT read and may hold anything (e.g. -1); predict_object = 0: candidates are subjects, r and o are read, s is not.
+ * The two ids that are read are validated on the device as rgcn_rank_device does it (RGCN_ERR_INVALID, no result).
+ * The energies are the ones rgcn_rank_device scores -- same query kernel, same GEMM, same buffers sized by
+ * rgcn_rank_reserve, longer inputs chunked alike -- and RGCN_BUF_RANK_ENERGIES holds the last chunk's afterwards,
+ * unmodified (exclusion is a bit mask beside them, never a write into them).
+ * exclude_ptr int64 [N+1] / exclude_idx int32: CSR of the entity ids that may not appear in row i's answer (the known
+ * completions of the pair); both NULL = exclude nothing.  Validated like the filter lists of rgcn_rank_device (ranges
+ * monotone and within exclude_ptr[N], entries in [0, V), duplicates allowed).
+ * Row i of the result holds the min(k, V - #distinct excluded) best remaining entities ordered by (energy descending,
+ * entity id ascending), energies compared as floats in their numeric order with -0.0 below +0.0 -- a total order, so
+ * the answer is a function of the energies alone, ties included, and two calls on the same energies return the same
+ * bytes.  The sigmoid is monotone: this order refines the reference's order by score.  topk_idx int32 [N,k],
+ * topk_energy float [N,k] (the buffer's values, bit for bit; sigmoid is left to the caller); slots a row cannot fill
+ * hold id -1 and energy -INFINITY.
+ * 1 <= k <= min(V, RGCN_MAX_TOPK), else RGCN_ERR_INVALID.  Needs a completed rgcn_forward and rgcn_rank_reserve
+ * (RGCN_ERR_STATE).  EntityCount above RGCN_MAX_TOPK_ENTITIES is RGCN_ERR_UNSUPPORTED: a row's exclusion mask (one bit
+ * per entity, 64 KB at the limit) lives in LDS.  Relation-sharded contexts: as rgcn_rank_device, every rank answers
+ * its own queries, no collective.  Synchronises at the end (it reads the validation verdict): not capturable. */
+#define RGCN_MAX_TOPK 1024
+#define RGCN_MAX_TOPK_ENTITIES 524288
+rgcn_status rgcn_topk_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t num_queries, int32_t predict_object,
+                             int32_t k, const int64_t* exclude_ptr_dev, const int32_t* exclude_idx_dev,
+                             int32_t* topk_idx_dev, float* topk_energy_dev);
 
 /* GradientClipping(max_norm) + Adam(lr) of the Converge chain (optimization/tensorflow_backend/
  * algorithms.py:27-42,58-68).  max_grad_norm = 0 disables clipping. */

@@ -82,6 +82,7 @@ _SIGS = {
     "rgcn_negative_sample_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, _P, _P]),
     "rgcn_rank_reserve": (C.c_int32, [_P, C.c_int64]),
     "rgcn_rank_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
+    "rgcn_topk_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rgcn_optimizer_step": (C.c_int32, [_P]),
     "rgcn_optimizer_norm_partial": (C.c_int32, [_P]),
     "rgcn_optimizer_apply": (C.c_int32, [_P]),
@@ -529,6 +530,50 @@ class Engine:
         out = np.empty(2 * n, dtype=np.int32)
         self._check(self.lib.rgcn_copy_to_host(self.ctx, _ptr(out), C.c_void_p(base + off_out), 8 * n))
         return out[:n].copy(), out[n:].copy()
+
+    def topk(self, queries, predict_object, k, exclude_ptr=None, exclude_idx=None):
+        """The k best completions of every query on the codes of the last forward, best first (include/rgcn.h
+        rgcn_topk_device): (idx int32 [N,k], energy float32 [N,k]), rows short of k answers padded with (-1, -inf).
+        queries [N,3] rows (s, r, o) of which the column being predicted is not read; exclude_ptr int64 [N+1] /
+        exclude_idx int32 [nnz]: per-row ids that may not be answered (both None: none)."""
+        x = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1, 3)
+        n, k = len(x), int(k)
+        if (exclude_ptr is None) != (exclude_idx is None):
+            raise ValueError("exclude_ptr and exclude_idx come together")
+        if n == 0:
+            return np.zeros((0, max(k, 0)), np.int32), np.zeros((0, max(k, 0)), np.float32)
+        has = exclude_ptr is not None
+        fp = np.ascontiguousarray(exclude_ptr if has else np.zeros(n + 1), dtype=np.int64)
+        fi = np.ascontiguousarray(exclude_idx if has else np.zeros(0), dtype=np.int32)
+        assert fp.shape == (n + 1,) and fp[-1] == len(fi)
+        # one staging buffer as in ranks(): exclusion pointers | queries | exclusion list | ids out | energies out
+        nnz = max(len(fi), 1)
+        off_x, off_fi = 8 * (n + 1), 8 * (n + 1) + 12 * n
+        off_out = (off_fi + 4 * nnz + 7) // 8 * 8
+        room = min(max(k, 0), 1024)        # (a k outside [1, RGCN_MAX_TOPK] is the library's to refuse: it writes nothing)
+        total = off_out + 8 * n * room
+        if getattr(self, "_rank_buf", None) is None or self._rank_buf.nbytes < total:
+            if getattr(self, "_rank_buf", None) is not None:
+                self._rank_buf.free()
+            self._rank_buf = DeviceBuffer(self, max(total, 1 << 20))
+        base = self._rank_buf.ptr.value if hasattr(self._rank_buf.ptr, "value") else int(self._rank_buf.ptr)
+        head = np.empty(off_fi, dtype=np.uint8)
+        head[:off_x] = fp.view(np.uint8)
+        head[off_x:] = x.reshape(-1).view(np.uint8)
+        for lo in range(0, off_fi, 1 << 20):
+            part = head[lo:lo + (1 << 20)]
+            self._check(self.lib.rgcn_copy_to_device_async(self.ctx, C.c_void_p(base + lo), _ptr(part), len(part), 0))
+        fb = fi.view(np.uint8)
+        for lo in range(0, len(fb), 1 << 20):
+            part = fb[lo:lo + (1 << 20)]
+            self._check(self.lib.rgcn_copy_to_device_async(self.ctx, C.c_void_p(base + off_fi + lo), _ptr(part), len(part), 0))
+        self._check(self.lib.rgcn_topk_device(self.ctx, C.c_void_p(base + off_x), n, 1 if predict_object else 0, k,
+                                              C.c_void_p(base) if has else None,
+                                              C.c_void_p(base + off_fi) if has else None, C.c_void_p(base + off_out),
+                                              C.c_void_p(base + off_out + 4 * n * k)))
+        out = np.empty(2 * n * k, dtype=np.int32)
+        self._check(self.lib.rgcn_copy_to_host(self.ctx, _ptr(out), C.c_void_p(base + off_out), 8 * n * k))
+        return out[:n * k].reshape(n, k).copy(), out[n * k:].view(np.float32).reshape(n, k).copy()
 
     def optimizer_config(self, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, max_grad_norm=1.0):
         self._check(self.lib.rgcn_optimizer_config(self.ctx, lr, beta1, beta2, eps, max_grad_norm))

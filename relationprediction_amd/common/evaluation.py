@@ -161,6 +161,19 @@ class AccuracyScore(object):
         return AccuracySummary(self.predictions)
 
 
+def known_completions_csr(pairs, known):
+    """Exclusion lists for a batch of prediction queries (rgcn_topk_device, BilinearDiag.device_topk).
+    pairs: [N,2] rows (entity, relation): the fixed entity of the query -- the subject when objects are predicted, the
+    object when subjects are -- and its relation.  known: the matching dictionary of a Scorer after register_data
+    (known_object_triples / known_subject_triples), {(entity, relation): [completing entity ids]}.
+    Returns (ptr int64 [N+1], idx int32 [nnz]); a pair with no known completion gets an empty range."""
+    ptr, idx = np.zeros(len(pairs) + 1, dtype=np.int64), []
+    for i, (e, r) in enumerate(pairs):
+        idx.extend(known.get((int(e), int(r)), ()))
+        ptr[i + 1] = len(idx)
+    return ptr, np.asarray(idx, dtype=np.int32)
+
+
 class Scorer(object):
     chunk_size = 1000
 

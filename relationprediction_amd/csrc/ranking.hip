@@ -18,6 +18,9 @@
 // SMALLEST float whose score reaches the gold score; t is found once per query by bisection over the ordered float
 // bit patterns (32 sigmoids per query) and the [queries, V] pass compares energies -- 64 thousand double-precision
 // exponentials per 2,000 queries instead of 58 million, the same counts bit for bit.
+//
+// Top-k prediction (rgcn_topk_device) selects from the same energies: same query kernel, same GEMM, same buffers; one
+// workgroup per query picks and orders the k best entities that its exclusion list leaves (k_topk_rows below).
 #include "rgcn_internal.h"
 
 namespace rgcn {
@@ -125,6 +128,232 @@ __global__ void k_rank_check(const int32_t* __restrict__ X, int n, int V, int R,
   if (!ok) atomicAdd(bad, 1);
 }
 
+// ---------------------------------------------------------------- top-k selection (rgcn_topk_device)
+// One workgroup of four wave64s per query row.  The row's answer is a function of its energies alone:
+//   1. the exclusion list becomes a bit mask of V bits in LDS (the energies are never touched);
+//   2. a radix select over float_key -- four 8-bit passes, most significant first, each a 256-bin LDS histogram of
+//      the non-excluded entries that match the digits found so far -- yields the key T of the kk-th best entry, how
+//      many entries lie above it and how many equal it;
+//   3. everything above T is gathered in any order (the sort below fixes the order); the entries EQUAL to T are all
+//      taken when they all fit, else the lowest ids among them: a scan in id order, 256 ids per step, whose slot
+//      is the entry's rank among the equals -- no counter is raced for, so the choice does not depend on timing;
+//   4. the <= 1024 gathered (key, ~id) pairs are sorted in LDS (bitonic, descending: key descending, id ascending).
+// The row is read five times (six where a tie straddles position k), after the first time from L2.
+constexpr int TOPK_THREADS = 256;
+constexpr int TOPK_WAVES = TOPK_THREADS / 64;
+constexpr int TOPK_UNROLL = 4;
+static_assert(RGCN_MAX_TOPK == 1024, "the sort buffer of k_topk_rows holds 1024 pairs");
+
+__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
+__device__ __forceinline__ uint64_t lanes_below() { return (1ull << lane_id()) - 1ull; }
+
+// hist[digit] += 1 for every active lane, one LDS atomic per distinct digit of the wave: the lanes that hold the same
+// digit find each other with eight ballots and the lowest of them adds their number.  (Energies of one row share their
+// exponent: left to themselves, 64 lanes would queue on one or two bins.)  Every lane of the wave must call this.
+__device__ __forceinline__ void hist_add(uint32_t* hist, uint32_t digit, bool active) {
+  uint64_t peers = __ballot(active);
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    const uint64_t set = __ballot((digit >> b) & 1u);
+    peers &= ((digit >> b) & 1u) ? set : ~set;
+  }
+  if (active && (peers & lanes_below()) == 0) atomicAdd(&hist[digit], (uint32_t)__popcll(peers));
+}
+
+__global__ void __launch_bounds__(TOPK_THREADS)
+k_topk_rows(const float* __restrict__ S, int V, int n, int k, const int64_t* __restrict__ excl_ptr,
+            const int32_t* __restrict__ excl_idx, const int64_t* __restrict__ excl_end, int32_t* __restrict__ out_idx,
+            float* __restrict__ out_energy, int32_t* __restrict__ bad) {
+  extern __shared__ uint32_t excl_mask[];               // V bits, rounded up to whole words
+  __shared__ uint32_t hist[256];
+  __shared__ unsigned long long pairs[RGCN_MAX_TOPK];   // key << 32 | ~id
+  __shared__ uint32_t wave_cnt[2][TOPK_WAVES];
+  __shared__ uint32_t sh_bucket, sh_rank, sh_eq, sh_fill;
+  __shared__ int red[TOPK_THREADS];
+  const int row = blockIdx.x;
+  if (row >= n) return;
+  const int tid = (int)threadIdx.x, wave = tid >> 6;
+  const float* s = S + (size_t)row * V;
+  int32_t* oi = out_idx + (size_t)row * k;
+  float* oe = out_energy + (size_t)row * k;
+  const int words = (V + 31) >> 5;
+
+  // 1. exclusion mask
+  for (int w = tid; w < words; w += TOPK_THREADS) excl_mask[w] = 0u;
+  __syncthreads();
+  if (excl_ptr) {
+    int64_t fb = excl_ptr[row], fe = excl_ptr[row + 1];
+    // (a negative, decreasing or overlong range has been flagged by k_topk_check: it is not walked at all)
+    if (fb < 0 || fe < fb || fe > *excl_end) fb = fe = 0;
+    bool oob = false;
+    for (int64_t j = fb + tid; j < fe; j += TOPK_THREADS) {
+      const int e = excl_idx[j];
+      if ((unsigned)e < (unsigned)V) atomicOr(&excl_mask[e >> 5], 1u << (e & 31));
+      else oob = true;
+    }
+    if (oob) atomicAdd(bad, 1);
+  }
+  __syncthreads();
+  int gone = 0;
+  for (int w = tid; w < words; w += TOPK_THREADS) gone += __popc(excl_mask[w]);
+  red[tid] = gone;
+  __syncthreads();
+  for (int w = TOPK_THREADS / 2; w > 0; w >>= 1) {
+    if (tid < w) red[tid] += red[tid + w];
+    __syncthreads();
+  }
+  const int kk = min(k, V - red[0]);                    // answers this row has
+  for (int j = kk + tid; j < k; j += TOPK_THREADS) {
+    oi[j] = -1;
+    oe[j] = -INFINITY;
+  }
+  if (kk <= 0) return;
+
+  // 2. radix select: after pass p the top 8 (p + 1) bits of T are known; `rank` counts from the best of the entries
+  // that share them
+  uint32_t prefix = 0u, rank = (uint32_t)kk, n_eq = 0u;
+  const int span = TOPK_THREADS * TOPK_UNROLL;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    const uint32_t known = shift == 24 ? 0u : 0xffffffffu << (shift + 8);
+    hist[tid] = 0u;
+    __syncthreads();
+    for (int base = 0; base < V; base += span) {
+      uint32_t key[TOPK_UNROLL];
+#pragma unroll
+      for (int u = 0; u < TOPK_UNROLL; ++u) {
+        const int e = base + u * TOPK_THREADS + tid;
+        key[u] = e < V ? float_key(s[e]) : 0u;
+      }
+#pragma unroll
+      for (int u = 0; u < TOPK_UNROLL; ++u) {
+        const int e = base + u * TOPK_THREADS + tid;
+        const bool in = e < V && !((excl_mask[e >> 5] >> (e & 31)) & 1u) && (key[u] & known) == prefix;
+        hist_add(hist, (key[u] >> shift) & 255u, in);
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {
+      // lane l owns bins 255 - 4 l ... 252 - 4 l; `above` = entries in better bins than its own
+      uint32_t h[4], mine = 0u;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        h[j] = hist[255 - 4 * tid - j];
+        mine += h[j];
+      }
+      uint32_t incl = mine;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t up = __shfl_up(incl, off);
+        if (tid >= off) incl += up;
+      }
+      uint32_t above = incl - mine;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (above < rank && rank <= above + h[j]) {      // true for exactly one bin: rank <= the pass's total
+          sh_bucket = (uint32_t)(255 - 4 * tid - j);
+          sh_rank = rank - above;
+          sh_eq = h[j];
+        }
+        above += h[j];
+      }
+    }
+    __syncthreads();
+    prefix |= sh_bucket << shift;
+    rank = sh_rank;
+    n_eq = sh_eq;
+    __syncthreads();                                     // (hist and the three words are rewritten by the next pass)
+  }
+  const uint32_t T = prefix;                             // the kk-th best key
+  const uint32_t need = rank;                            // entries equal to T that belong to the answer (>= 1)
+  const uint32_t n_gt = (uint32_t)kk - need;             // entries above T: all of them belong to it
+  const bool all_eq = need == n_eq;
+
+  // 3. gather
+  int n2 = 1;
+  while (n2 < kk) n2 <<= 1;
+  for (int j = kk + tid; j < n2; j += TOPK_THREADS) pairs[j] = 0ull;     // below every real pair (~id has bit 31 set)
+  if (tid == 0) sh_fill = 0u;
+  __syncthreads();
+  for (int base = 0; base < V; base += span) {
+    uint32_t key[TOPK_UNROLL];
+#pragma unroll
+    for (int u = 0; u < TOPK_UNROLL; ++u) {
+      const int e = base + u * TOPK_THREADS + tid;
+      key[u] = e < V ? float_key(s[e]) : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < TOPK_UNROLL; ++u) {
+      const int e = base + u * TOPK_THREADS + tid;
+      const bool in = e < V && !((excl_mask[e >> 5] >> (e & 31)) & 1u);
+      const bool take = in && (key[u] > T || (all_eq && key[u] == T));
+      const uint64_t takers = __ballot(take);
+      if (takers) {
+        uint32_t slot = 0u;
+        if (lane_id() == __ffsll((unsigned long long)takers) - 1) slot = atomicAdd(&sh_fill, (uint32_t)__popcll(takers));
+        slot = __shfl(slot, __ffsll((unsigned long long)takers) - 1) + (uint32_t)__popcll(takers & lanes_below());
+        // (the select counted exactly kk takers, so slot < kk; the test only guards the buffer should the energies be
+        // rewritten by someone else between the select passes and this one)
+        if (take && slot < (uint32_t)kk) pairs[slot] = ((unsigned long long)key[u] << 32) | (uint32_t)~e;
+      }
+    }
+  }
+  if (!all_eq) {
+    // the `need` lowest ids among the entries equal to T, in id order: slot n_gt + (rank among the equals)
+    uint32_t before = 0u;                                // equals in the ids already passed (the same in every thread)
+    int flip = 0;
+    for (int base = 0; base < V && before < need; base += TOPK_THREADS, flip ^= 1) {
+      const int e = base + tid;
+      const bool eq = e < V && !((excl_mask[e >> 5] >> (e & 31)) & 1u) && float_key(s[e]) == T;
+      const uint64_t eqs = __ballot(eq);
+      if (lane_id() == 0) wave_cnt[flip][wave] = (uint32_t)__popcll(eqs);
+      __syncthreads();
+      uint32_t r = before + (uint32_t)__popcll(eqs & lanes_below()), total = 0u;
+#pragma unroll
+      for (int w = 0; w < TOPK_WAVES; ++w) {
+        const uint32_t cw = wave_cnt[flip][w];
+        if (w < wave) r += cw;
+        total += cw;
+      }
+      if (eq && r < need) pairs[n_gt + r] = ((unsigned long long)T << 32) | (uint32_t)~e;
+      before += total;
+    }
+  }
+  __syncthreads();
+
+  // 4. bitonic sort of n2 pairs, descending
+  for (int size = 2; size <= n2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = tid; t < (n2 >> 1); t += TOPK_THREADS) {
+        const int lo = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), hi = lo + stride;
+        const unsigned long long a = pairs[lo], b = pairs[hi];
+        const bool descending = (lo & size) == 0;
+        if ((a < b) == descending) {
+          pairs[lo] = b;
+          pairs[hi] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int j = tid; j < kk; j += TOPK_THREADS) {
+    const unsigned long long p = pairs[j];
+    oi[j] = (int32_t)~(uint32_t)p;
+    oe[j] = key_float((uint32_t)(p >> 32));
+  }
+}
+
+// the two ids of a query that are read, and the exclusion ranges (their entries are checked where they are read)
+__global__ void k_topk_check(const int32_t* __restrict__ X, int n, int V, int R, int predict_object,
+                             const int64_t* __restrict__ excl_ptr, int32_t* __restrict__ bad) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n) return;
+  const int ent = X[3 * row + (predict_object ? 0 : 2)], rel = X[3 * row + 1];
+  bool ok = ent >= 0 && ent < V && rel >= 0 && rel < R;
+  if (excl_ptr)
+    ok = ok && excl_ptr[row] >= 0 && excl_ptr[row] <= excl_ptr[row + 1] && excl_ptr[row + 1] <= excl_ptr[n];
+  if (!ok) atomicAdd(bad, 1);
+}
+
 }  // namespace
 
 void rank_free(rgcn_ctx* c) {
@@ -183,6 +412,52 @@ rgcn_status rank_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predi
   RGCN_HIP(c, hipMemcpyAsync(&bad, c->rank_bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   RGCN_HIP(c, hipStreamSynchronize(c->stream));
   if (bad) RGCN_FAIL(c, RGCN_ERR_INVALID, "rank: entity / relation / filter index out of range");
+  return RGCN_OK;
+}
+
+rgcn_status topk_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, int k,
+                         const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out, float* energy_out) {
+  const float* codes = c->H[c->L];
+  const size_t mask_bytes = (size_t)((c->V + 31) / 32) * sizeof(uint32_t);
+  // the mask is dynamic LDS, above the default limit for large V: raise the kernel's limit on the context's device (every
+  // API entry selects it) the first time it launches there.  One bit per device id, per process and unguarded like the
+  // GEMM launchers' (a context is single-threaded); past 64 devices the attribute is set on every call.
+  static uint64_t lds_configured = 0;
+  const uint64_t device_bit = c->cfg.device < 64 ? 1ull << c->cfg.device : 0;
+  if (!(lds_configured & device_bit)) {
+    RGCN_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_topk_rows), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)((size_t)((RGCN_MAX_TOPK_ENTITIES + 31) / 32) * sizeof(uint32_t))));
+    lds_configured |= device_bit;
+  }
+  // as rank_compute: ids are validated on the device, id 0 stands in for a bad one until the verdict is read back at the
+  // end of the call, and the (meaningless) answers of a rejected call are not to be used
+  RGCN_HIP(c, hipMemsetAsync(c->rank_bad, 0, sizeof(int32_t), c->stream));
+  hipLaunchKernelGGL(k_topk_check, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, X_dev, (int)N, c->V, c->R,
+                     predict_object, excl_ptr, c->rank_bad);
+  RGCN_HIP(c, hipGetLastError());
+  for (int64_t b = 0; b < N; b += c->rank_max) {
+    const int n = (int)std::min<int64_t>(c->rank_max, N - b);
+    const int32_t* X = X_dev + 3 * b;
+    {
+      ProfScope ps(c, "rank_query", 4.0 * 3 * n * c->d, 0);
+      hipLaunchKernelGGL(k_rank_query, dim3((unsigned)n), dim3(128), 0, c->stream, codes, c->w_rel, X, n, c->d,
+                         predict_object, c->rank_q, c->V, c->R);
+      RGCN_HIP(c, hipGetLastError());
+    }
+    RGCN_TRY(gemm_f32(c, "rank_scores", true, true, n, c->V, c->d, c->rank_q, c->d, codes, c->d, c->rank_s, c->V, 1));
+    {
+      // design bytes: four select passes and the gather read the row (from L2 after the first)
+      ProfScope ps(c, "topk_rows", 5.0 * 4.0 * n * c->V + 8.0 * n * k, 0, 4.0 * n * c->V + 8.0 * n * k);
+      hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)n), dim3(TOPK_THREADS), mask_bytes, c->stream, c->rank_s, c->V, n, k,
+                         excl_ptr ? excl_ptr + b : nullptr, excl_idx, excl_ptr ? excl_ptr + N : nullptr,
+                         idx_out + (size_t)b * k, energy_out + (size_t)b * k, c->rank_bad);
+      RGCN_HIP(c, hipGetLastError());
+    }
+  }
+  int32_t bad = 0;
+  RGCN_HIP(c, hipMemcpyAsync(&bad, c->rank_bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  RGCN_HIP(c, hipStreamSynchronize(c->stream));
+  if (bad) RGCN_FAIL(c, RGCN_ERR_INVALID, "topk: entity / relation / exclusion index out of range");
   return RGCN_OK;
 }
 

@@ -783,6 +783,25 @@ rgcn_status rgcn_rank_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32
   return rank_compute(c, x_dev, n, predict_object ? 1 : 0, filter_ptr_dev, filter_idx_dev, raw_rank_dev, filtered_rank_dev);
 }
 
+rgcn_status rgcn_topk_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32_t predict_object, int32_t k,
+                             const int64_t* exclude_ptr_dev, const int32_t* exclude_idx_dev, int32_t* topk_idx_dev,
+                             float* topk_energy_dev) {
+  RGCN_NEED(c);
+  if (n < 0 || (n > 0 && (!x_dev || !topk_idx_dev || !topk_energy_dev)) || (!exclude_ptr_dev != !exclude_idx_dev))
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
+  if (k < 1 || k > c->V || k > RGCN_MAX_TOPK)
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_topk_device: k must be in [1, min(EntityCount, " + std::to_string(RGCN_MAX_TOPK) + ")]");
+  if (c->V > RGCN_MAX_TOPK_ENTITIES)
+    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "rgcn_topk_device: EntityCount above " + std::to_string(RGCN_MAX_TOPK_ENTITIES) +
+                                           " (a row's exclusion mask must fit in LDS)");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "this call synchronises with the device: not allowed between rgcn_capture_begin and rgcn_capture_end");
+  if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_topk_device needs a completed rgcn_forward (test mode on the full graph)");
+  // world > 1: as rgcn_rank_device -- the codes are replicated after the last exchange, every rank answers its own queries
+  if (c->rank_max <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_rank_reserve first");
+  if (n == 0) return RGCN_OK;
+  return topk_compute(c, x_dev, n, predict_object ? 1 : 0, k, exclude_ptr_dev, exclude_idx_dev, topk_idx_dev, topk_energy_dev);
+}
+
 rgcn_status rgcn_optimizer_config(rgcn_ctx* c, float lr, float beta1, float beta2, float eps, float max_grad_norm) {
   RGCN_NEED(c);
   if (!(lr > 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps > 0.f) ||

@@ -631,6 +631,8 @@ rgcn_status rank_reserve(rgcn_ctx* c, int64_t max_queries);
 void rank_free(rgcn_ctx* c);
 rgcn_status rank_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, const int64_t* filt_ptr,
                          const int32_t* filt_idx, int32_t* raw_out, int32_t* filt_out);
+rgcn_status topk_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, int k,
+                         const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out, float* energy_out);
 void optimizer_free(rgcn_ctx* c);
 
 // ---- comm.cpp (RCCL via dlopen)

@@ -110,6 +110,36 @@ class BilinearDiag(Model):
             self._ranks_graph = graph
         return self.next_component.get_runtime().ranks(triplets, predict_object, filter_ptr, filter_idx)
 
+    def device_topk(self, graph, queries, predict_object, k, exclude_ptr=None, exclude_idx=None):
+        """The k most plausible objects of (s, r, ?) (predict_object) or subjects of (?, r, o) for every row of
+        `queries`, best first, leaving out row i's exclude_idx[exclude_ptr[i]:exclude_ptr[i + 1]]; codes from a
+        test-mode pass over `graph`.  Returns (entity ids int32 [N,k], energies float32 [N,k]); the column being
+        predicted is not read; rows short of k answers end in (-1, -inf).  Scores are _sigmoid(energies)."""
+        variables = self.get_test_input_variables()
+        if getattr(self, '_ranks_graph', None) is not graph or variables[0].value is None:
+            variables[0].feed(graph)          # re-encoded only when the graph or the weights changed
+            self._ranks_graph = graph
+        return self.next_component.get_runtime().topk(queries, predict_object, k, exclude_ptr, exclude_idx)
+
+    def predict_top(self, predict_object, k, exclude_ptr=None, exclude_idx=None):
+        """device_topk restated eagerly on predict_all_object_scores / predict_all_subject_scores of the triples fed
+        to X (all three columns valid ids): (entity ids int32 [N,k], scores float32 [N,k]) ordered by (score
+        descending, id ascending).  Scores saturate where energies do not, so this order is coarser than the
+        device's; the small-size cross-check of the device path, like the other eager methods."""
+        scores = self.predict_all_object_scores() if predict_object else self.predict_all_subject_scores()
+        n, V = scores.shape
+        idx = np.full((n, int(k)), -1, dtype=np.int32)
+        top = np.zeros((n, int(k)), dtype=np.float32)
+        for i in range(n):
+            keep = np.ones(V, dtype=bool)
+            if exclude_ptr is not None:
+                keep[np.asarray(exclude_idx[exclude_ptr[i]:exclude_ptr[i + 1]], dtype=np.int64)] = False
+            ids = np.flatnonzero(keep)
+            order = ids[np.lexsort((ids, -scores[i, ids].astype(np.float64)))][:int(k)]
+            idx[i, :len(order)] = order
+            top[i, :len(order)] = scores[i, order]
+        return idx, top
+
     def backward(self, upstream=None):
         """d(loss + regularisation)/d(codes, W_relation), then down the chain."""
         subject_codes, relation_codes, object_codes = self.next_component.get_all_codes(mode='train')

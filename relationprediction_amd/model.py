@@ -210,6 +210,12 @@ class Model(object):
     def device_ranks(self, *args):
         return self.__delegate__('device_ranks', *args)
 
+    def device_topk(self, *args, **kwargs):
+        return self.__delegate__('device_topk', *args, **kwargs)
+
+    def predict_top(self, *args, **kwargs):
+        return self.__delegate__('predict_top', *args, **kwargs)
+
     def get_runtime(self):
         """The EncoderRuntime (one HIP engine context) the chain's graph-convolution stack runs on."""
         return self.__delegate__('get_runtime')

@@ -1,0 +1,118 @@
+"""Ask a trained model: the k most plausible completions of (entity, relation, ?) or (?, relation, entity).
+
+    python -m relationprediction_amd.predict --settings settings/gcn_block.exp --dataset data/FB-Toutanova \
+        --model models/GcnBlock-3.npz --queries queries.txt --k 10 [--side object|subject] [--keep-known] [--out FILE]
+
+The model is built exactly as train.py builds it (same settings merge, same chain), the checkpoint is one written by
+Model.save, the training graph is encoded once in test mode and the selection runs on the device (rgcn_topk_device:
+energies of every entity from one GEMM per chunk of queries, the k best per query picked and ordered there; nothing of
+size [queries, entities] crosses to the host).  The reference has no such command: its checkpoints can only be ranked
+against a test set (code/train.py:99-128).
+
+--queries: one `entity<TAB>relation` per line, names as in entities.dict / relations.dict.  --side object (default)
+reads the entity as the subject and answers objects; --side subject reads it as the object and answers subjects.
+Completions already known from train / valid / test are left out unless --keep-known.  Output, one line per answer:
+
+    query_entity<TAB>relation<TAB>answer_entity<TAB>position<TAB>score
+
+position counts from 1 (best); score = sigmoid(energy), evaluated in double and rounded once to float32 as everywhere
+else (csrc/ranking.hip).  Answers are ordered by (energy descending, entity id ascending)."""
+import argparse
+import sys
+
+import numpy as np
+
+from .common import settings_reader, evaluation
+
+MAX_K = 1024          # RGCN_MAX_TOPK (include/rgcn.h)
+
+
+def read_queries(path, entity_ids, relation_ids):
+    """[(entity id, relation id)] of a query file; an unknown name or a malformed line is a ValueError naming the line"""
+    pairs = []
+    with open(path, "r") as f:
+        for number, line in enumerate(f, start=1):
+            if not line.strip():
+                continue
+            fields = line.rstrip("\r\n").split("\t")
+            if len(fields) != 2:
+                raise ValueError("%s line %d: expected entity<TAB>relation, got %d field(s)" % (path, number, len(fields)))
+            entity, relation = fields
+            if entity not in entity_ids:
+                raise ValueError("%s line %d: unknown entity %r" % (path, number, entity))
+            if relation not in relation_ids:
+                raise ValueError("%s line %d: unknown relation %r" % (path, number, relation))
+            pairs.append((entity_ids[entity], relation_ids[relation]))
+    return pairs
+
+
+def build_model(settings, splits, n_entities, n_relations):
+    """The training driver's own chain (train.build_model, train.initialize_model), ready for test-mode calls."""
+    from . import train
+    _, model = train.build_model(settings, splits['train'], n_entities, n_relations)
+    train.initialize_model(model, splits['train'])
+    return model
+
+
+def sigmoid_f32(energies):
+    with np.errstate(over='ignore'):
+        return (1.0 / (1.0 + np.exp(-np.asarray(energies, dtype=np.float64)))).astype(np.float32)
+
+
+def main(argv=None, out=None):
+    parser = argparse.ArgumentParser(description="Top-k link prediction with a trained model.")
+    parser.add_argument("--settings", help="Filepath for settings file.", required=True)
+    parser.add_argument("--dataset", help="Filepath for dataset.", required=True)
+    parser.add_argument("--model", help="checkpoint written by Model.save (.npz)", required=True)
+    parser.add_argument("--queries", help="file of entity<TAB>relation lines (names)", required=True)
+    parser.add_argument("--k", type=int, default=10, help="answers per query (at most %d)" % MAX_K)
+    parser.add_argument("--side", choices=("object", "subject"), default="object",
+                        help="what is predicted: the object of (entity, relation, ?) or the subject of (?, relation, entity)")
+    parser.add_argument("--keep-known", action="store_true",
+                        help="do not leave out the completions known from train / valid / test")
+    parser.add_argument("--out", default=None, help="write the answers here instead of standard output")
+    args = parser.parse_args(argv)
+
+    settings = settings_reader.read(args.settings)
+    from .train import load_dataset
+    splits, entities, relations = load_dataset(args.dataset, settings['Evaluation']['Metric'])
+    if not 1 <= args.k <= min(len(entities), MAX_K):
+        raise ValueError("--k %d: must be between 1 and min(number of entities = %d, %d)"
+                         % (args.k, len(entities), MAX_K))
+    entity_ids = {name: i for i, name in entities.items()}
+    relation_ids = {name: i for i, name in relations.items()}
+    pairs = read_queries(args.queries, entity_ids, relation_ids)
+    predict_object = args.side == "object"
+
+    ptr = idx = None
+    if not args.keep_known:
+        known = {}
+        for part in ('train', 'valid', 'test'):
+            evaluation.Scorer.extend_triple_dict(known, splits[part], object_list=predict_object)
+        ptr, idx = evaluation.known_completions_csr(pairs, known)
+
+    model = build_model(settings, splits, len(entities), len(relations))
+    model.load(args.model)
+    queries = np.full((len(pairs), 3), -1, dtype=np.int32)         # the predicted column is not read
+    if pairs:
+        queries[:, 0 if predict_object else 2] = [p[0] for p in pairs]
+        queries[:, 1] = [p[1] for p in pairs]
+    top, energies = model.device_topk(model.test_graph, queries, predict_object, args.k, ptr, idx)
+    scores = sigmoid_f32(energies)
+
+    sink = open(args.out, "w") if args.out else (out or sys.stdout)
+    try:
+        for (entity, relation), ids, row in zip(pairs, top, scores):
+            for position, (answer, score) in enumerate(zip(ids, row), start=1):
+                if answer < 0:
+                    break                                            # fewer than k entities were left to answer
+                sink.write("%s\t%s\t%s\t%d\t%.9g\n" % (entities[entity], relations[relation], entities[int(answer)],
+                                                       position, score))
+    finally:
+        if args.out:
+            sink.close()
+    return top, scores
+
+
+if __name__ == '__main__':
+    main()

@@ -282,6 +282,15 @@ class EncoderRuntime(object):
             self._rank_reserved = chunk
         return self.engine.ranks(triples, predict_object, filter_ptr, filter_idx)
 
+    def topk(self, queries, predict_object, k, exclude_ptr=None, exclude_idx=None, chunk=2048):
+        """The k best completions of every query, best first, on the codes of a test-mode forward over the fed graph
+        (rgcn_topk_device): (entity ids int32 [N,k], energies float32 [N,k])."""
+        self.forward('test')
+        if self._rank_reserved < chunk:
+            self.engine.rank_reserve(chunk)
+            self._rank_reserved = chunk
+        return self.engine.topk(queries, predict_object, k, exclude_ptr, exclude_idx)
+
     def backward(self, dcodes):
         if self._state is None or self._state[1] != 'train':
             raise RuntimeError("backward() needs a train-mode forward pass on the current graph")

@@ -92,6 +92,31 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
     return t_func
 
 
+def build_model(settings, train_triplets, entity_count, relation_count):
+    """code/train.py:76-93: the dataset's counts into General, the section merges, the encoder / decoder chain.
+    Returns (encoder, model).  The training driver and relationprediction_amd.predict both build their model here."""
+    encoder_settings, decoder_settings = settings['Encoder'], settings['Decoder']
+    shared_settings, general_settings = settings['Shared'], settings['General']
+    general_settings.put('EntityCount', entity_count)
+    general_settings.put('RelationCount', relation_count)
+    general_settings.put('EdgeCount', len(train_triplets))
+    encoder_settings.merge(shared_settings)
+    encoder_settings.merge(general_settings)
+    decoder_settings.merge(shared_settings)
+    decoder_settings.merge(general_settings)
+    settings['Optimizer'].merge(general_settings)
+    settings['Evaluation'].merge(general_settings)
+    encoder = model_builder.build_encoder(encoder_settings, train_triplets)
+    return encoder, model_builder.build_decoder(encoder, decoder_settings)
+
+
+def initialize_model(model, train_triplets):
+    """code/train.py:249-251: the training graph is what test-mode calls encode; the weights are drawn"""
+    model.preprocess(train_triplets)
+    model.register_for_test(train_triplets)
+    model.initialize_train()
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description="Train a model on a given dataset.")
     parser.add_argument("--settings", help="Filepath for settings file.", required=True)
@@ -123,20 +148,9 @@ def main(argv=None):
     splits, entities, relations = load_dataset(args.dataset, evaluation_settings['Metric'])
     train_triplets, valid_triplets, test_triplets = splits['train'], splits['valid'], splits['test']
 
-    general_settings.put('EntityCount', len(entities))
-    general_settings.put('RelationCount', len(relations))
-    general_settings.put('EdgeCount', len(train_triplets))
-    encoder_settings.merge(shared_settings)
-    encoder_settings.merge(general_settings)
-    decoder_settings.merge(shared_settings)
-    decoder_settings.merge(general_settings)
-    optimizer_settings.merge(general_settings)
-    evaluation_settings.merge(general_settings)
+    encoder, model = build_model(settings, train_triplets, len(entities), len(relations))
     if args.max_iterations is not None:
         optimizer_settings.put('MaxIterations', args.max_iterations)
-
-    encoder = model_builder.build_encoder(encoder_settings, train_triplets)
-    model = model_builder.build_decoder(encoder, decoder_settings)
 
     opp = optimizer_parameter_parser.Parser(optimizer_settings)
     opp.set_save_function(model.save)
@@ -168,9 +182,7 @@ def main(argv=None):
                                                                              args.host_edge_dropout),
                                                          device_sampler=not args.host_sampler))
 
-    model.preprocess(train_triplets)
-    model.register_for_test(train_triplets)
-    model.initialize_train()
+    initialize_model(model, train_triplets)
     print(model.get_train_input_variables())
 
     optimizer = build_hip(model, opp.get_parametrization(), batch_workers=args.batch_workers)

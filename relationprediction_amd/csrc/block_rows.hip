@@ -683,7 +683,7 @@ rgcn_status block_rows(rgcn_ctx* c, const char* tag, int layer, bool backward, c
   const int giant_parts = giant ? c->g.giant_cap : 0;
   if (backward && ca.colsum && c->colsum_part != nullptr &&
       (size_t)(grid / 8 + giant_parts) * c->d <= c->colsum_part_floats) {
-    a.colpart = c->colsum_part;
+    a.colpart = colsum_scratch(c);
     c->colsum_parts = grid / 8 + giant_parts;
   }
   const double M = 2.0 * c->g.E, P = 4.0 * c->V * c->d;

@@ -563,13 +563,13 @@ rgcn_status column_sum_giant_rows(rgcn_ctx* c, const float* out, float* part) {
 
 rgcn_status column_sum_finish(rgcn_ctx* c, float* out, int nparts, int cols) {
   ProfScope ps(c, "bias_grad_colsum", 4.0 * nparts * cols, 0);
-  hipLaunchKernelGGL(k_colsum_final, dim3((cols + 63) / 64), dim3(1024), 0, c->stream, c->colsum_part, out, nparts, cols);
+  hipLaunchKernelGGL(k_colsum_final, dim3((cols + 63) / 64), dim3(1024), 0, c->stream, colsum_scratch(c), out, nparts, cols);
   RGCN_HIP(c, hipGetLastError());
   return RGCN_OK;
 }
 
 rgcn_status column_sum(rgcn_ctx* c, const float* in, float* out, int rows, int cols) {
-  float* part = c->colsum_part;
+  float* part = colsum_scratch(c);
   const int nparts = (rows + kColRowsPerBlock - 1) / kColRowsPerBlock;
   if ((size_t)nparts * cols > c->colsum_part_floats) RGCN_FAIL(c, RGCN_ERR_STATE, "internal: column-sum scratch too small");
   ProfScope ps(c, "bias_grad_colsum", 4.0 * rows * cols, 0);

@@ -60,6 +60,7 @@ rgcn_status stream_join(rgcn_ctx* c, int k) {
   // nothing went to that stream since its last join (side streams switched off, or no fork taken)
   if (!c->aux_dirty[k]) return RGCN_OK;
   c->aux_dirty[k] = false;
+  if (k < 2) c->side_state = rgcn_ctx::SIDE_NONE;      // (ev_join[k] is re-recorded: back to what the dirty flags say)
   RGCN_HIP(c, hipEventRecord(c->ev_join[k], c->aux[k]));
   RGCN_HIP(c, hipStreamWaitEvent(c->main_stream, c->ev_join[k], 0));
   return RGCN_OK;
@@ -70,6 +71,7 @@ rgcn_status stream_join(rgcn_ctx* c, int k) {
 rgcn_status stream_join_both(rgcn_ctx* c) {
   if (c->stream != c->main_stream) return RGCN_OK;
   if (c->aux_dirty[0] && c->aux_dirty[1]) {
+    c->side_state = rgcn_ctx::SIDE_NONE;
     RGCN_HIP(c, hipEventRecord(c->ev_join[1], c->aux[1]));
     RGCN_HIP(c, hipStreamWaitEvent(c->aux[0], c->ev_join[1], 0));
     c->aux_dirty[1] = false;
@@ -78,14 +80,52 @@ rgcn_status stream_join_both(rgcn_ctx* c) {
   return stream_join(c, 1);
 }
 
-// A backward pass driven layer by layer (phase API) and abandoned between layers 2 and 1 leaves layer 2's side kernels
-// unjoined (bwd_layer_partial defers their joins to layer 1).  They read D / dS / the activations and the graph's message
-// lists: whoever is about to rewrite any of those -- the next forward pass, the next backward pass, a graph build on the
-// main stream -- joins them first.  Nothing is queued (and nothing is paid) in the usual case, where every pass ended joined.
+// Side kernels the main stream has not waited for.  Two ways to get there: a backward pass driven layer by layer (phase
+// API) and abandoned between layers 2 and 1 (bwd_layer_partial defers layer 2's joins to layer 1), and the backward pass
+// of rgcn_step_device, which ends unjoined on purpose (rgcn_ctx::side_state).  The side kernels read D / dS / the
+// activations and the graph's message lists and write the weight gradients, their slabs and the bias gradient: whoever
+// is about to rewrite what they read or to touch what they write -- a backward pass, a graph build on the main stream,
+// the optimizer, a replayed graph, a copy into a caller's buffer -- joins them first (the calls that wait on the host
+// synchronise the side streams themselves: sync_all, check_dev_flag).  Nothing is queued, and nothing is paid, where
+// every pass ended joined.
 rgcn_status join_abandoned_side_work(rgcn_ctx* c) {
   if (c->stream != c->main_stream) return RGCN_OK;
   RGCN_TRY(stream_join(c, 0));
-  return stream_join(c, 1);
+  RGCN_TRY(stream_join(c, 1));
+  c->side_state = rgcn_ctx::SIDE_NONE;
+  return RGCN_OK;
+}
+
+// The end of a backward pass that leaves its side kernels unjoined: one event, on side stream 0, behind all of them.
+rgcn_status record_side_done(rgcn_ctx* c) {
+  RGCN_HIP(c, hipEventRecord(c->ev_join[1], c->aux[1]));
+  RGCN_HIP(c, hipStreamWaitEvent(c->aux[0], c->ev_join[1], 0));
+  RGCN_HIP(c, hipEventRecord(c->ev_join[0], c->aux[0]));
+  c->aux_dirty[0] = c->aux_dirty[1] = true;
+  c->side_state = rgcn_ctx::SIDE_RECORDED;
+  return RGCN_OK;
+}
+
+// What a forward pass needs of unjoined side work: that it has finished READING (the pass overwrites the activations; it
+// touches neither the gradients nor the slabs).  After a deferred end of step that is one wait for the event
+// record_side_done left -- which fired before the main chain ended, the column sums behind it excluded -- and the gradients
+// stay pending; in every other state, the full join.  also: an event of another stream (a prefetched graph's ev_ready) the
+// main stream has to wait for at the same point; side stream 0, idle by then, takes that wait and the main stream still
+// pays ONE wait packet.
+rgcn_status join_side_reads(rgcn_ctx* c, hipEvent_t also) {
+  if (c->stream != c->main_stream) return RGCN_OK;
+  if (c->side_state == rgcn_ctx::SIDE_RECORDED) {
+    if (also) {
+      RGCN_HIP(c, hipStreamWaitEvent(c->aux[0], also, 0));
+      RGCN_HIP(c, hipEventRecord(c->ev_join[0], c->aux[0]));
+    }
+    RGCN_HIP(c, hipStreamWaitEvent(c->main_stream, c->ev_join[0], 0));
+    c->side_state = rgcn_ctx::SIDE_READS_JOINED;
+    return RGCN_OK;
+  }
+  if (c->side_state != rgcn_ctx::SIDE_READS_JOINED) RGCN_TRY(join_abandoned_side_work(c));
+  if (also) RGCN_HIP(c, hipStreamWaitEvent(c->main_stream, also, 0));
+  return RGCN_OK;
 }
 
 static rgcn_status sync_all(rgcn_ctx* c) {
@@ -95,6 +135,7 @@ static rgcn_status sync_all(rgcn_ctx* c) {
     if (c->aux[k]) RGCN_HIP(c, hipStreamSynchronize(c->aux[k]));
   RGCN_HIP(c, hipStreamSynchronize(c->main_stream));
   for (int k = 0; k < kAuxStreams; ++k) c->aux_dirty[k] = false;     // nothing left to join
+  c->side_state = rgcn_ctx::SIDE_NONE;
   return RGCN_OK;
 }
 
@@ -489,7 +530,7 @@ static rgcn_status create_impl(rgcn_ctx* c) {
   RGCN_TRY(dmalloc(c, &c->stage, stage, false));
   // one partial row per combine workgroup (4 rows each at worst) + the second-level partials of their sum
   c->colsum_part_floats = ((V + 3) / 4 + 1024 + 2 + ((V + 3) / 4 + 1024) / 32 + 2) * d;
-  RGCN_TRY(dmalloc(c, &c->colsum_part, c->colsum_part_floats));
+  RGCN_TRY(dmalloc(c, &c->colsum_part, 2 * c->colsum_part_floats));      // two halves: rgcn_ctx::colsum_half
   RGCN_TRY(dmalloc(c, &c->zeros, 1024));
   RGCN_TRY(graph_alloc(c, nullptr));
   std::swap(c->g, c->g_alt);
@@ -665,6 +706,7 @@ rgcn_status rgcn_backward(rgcn_ctx* c, const float* dcodes_host, int64_t count) 
   RGCN_NEED(c);
   if (!dcodes_host || count != (int64_t)c->V * c->d) RGCN_FAIL(c, RGCN_ERR_INVALID, "dcodes must be [V,d]");
   if (!c->dcodes_own) RGCN_TRY(dmalloc(c, &c->dcodes_own, (size_t)count, false));
+  RGCN_TRY(join_abandoned_side_work(c));      // (unjoined side kernels may read the previous dcodes)
   RGCN_TRY(to_dev(c, c->dcodes_own, dcodes_host, sizeof(float) * (size_t)count));
   return backward_all(c, c->dcodes_own);
 }
@@ -675,24 +717,37 @@ rgcn_status rgcn_backward(rgcn_ctx* c, const float* dcodes_host, int64_t count) 
 // keep >= 0: the graph is the edge-dropout subset (keep of the E batch edges, generator key eseed) of tri_dev.
 // fork_point: something of this step forks from its start (the decoder's batch preparation; inside a capture, the prefetch):
 // an encoder step outside a capture has no such fork and saves the main stream the packet.
+// Ordering against the step before: every packet between two kernels of the main stream -- record or
+// wait, fired or not -- costs the chain ~6 us (profiles/r07_deferred_joins.md), so an encoder step ends unjoined and this
+// one starts with ONE wait: for the prefetched set's ev_ready and, through side stream 0, for the side kernels that read
+// what the forward pass overwrites.  A graph built in line takes the full join first: the build rewrites the message lists.
 static rgcn_status step_begin(rgcn_ctx* c, const int32_t* tri_dev, int64_t E, bool fork_point, int64_t keep = -1,
                               uint64_t eseed = 0) {
-  RGCN_TRY(join_abandoned_side_work(c));
+  const bool adopt = c->g_alt.pf_valid && c->g_alt.pf_tri == tri_dev && c->g_alt.pf_E == E && c->g_alt.pf_keep == keep &&
+                     (keep < 0 || c->g_alt.pf_eseed == eseed);
+  // a build in line rewrites the message lists unjoined side kernels may still read; a prefetched set was built behind
+  // its own ev_free, which covers them (step_end), and the forward pass takes the join it needs (join_side_reads)
+  if (!adopt) RGCN_TRY(join_abandoned_side_work(c));
   if (fork_point || c->capturing) RGCN_HIP(c, hipEventRecord(c->ev_step_begin, c->main_stream));
   c->step_begin_in_capture = c->capturing;
-  if (c->g_alt.pf_valid && c->g_alt.pf_tri == tri_dev && c->g_alt.pf_E == E && c->g_alt.pf_keep == keep &&
-      (keep < 0 || c->g_alt.pf_eseed == eseed)) {
+  if (adopt) {
     // the structures for this graph were prepared beside the previous step: swap them in
     std::swap(c->g, c->g_alt);
     c->g.pf_valid = false;
     c->fwd_done = false;
-    if (!c->capturing || c->g.ready_in_capture) RGCN_HIP(c, hipStreamWaitEvent(c->main_stream, c->g.ev_ready, 0));
-    return RGCN_OK;
+    if (c->capturing) {
+      if (c->g.ready_in_capture) RGCN_HIP(c, hipStreamWaitEvent(c->main_stream, c->g.ev_ready, 0));
+      return RGCN_OK;
+    }
+    return join_side_reads(c, c->g.ev_ready);
   }
   return keep < 0 ? graph_build(c, tri_dev, E) : graph_build_dropout(c, tri_dev, E, keep, eseed, nullptr);
 }
+// ev_free: the graph set may be rebuilt.  After a deferred end of step the side kernels still read it: side stream 1, which
+// bwd_end put behind the main stream's last kernel and behind side stream 0, takes the record -- the prefetch stream waits
+// for all three, the main stream for nothing.
 static rgcn_status step_end(rgcn_ctx* c) {
-  RGCN_HIP(c, hipEventRecord(c->g.ev_free, c->main_stream));
+  RGCN_HIP(c, hipEventRecord(c->g.ev_free, c->side_state == rgcn_ctx::SIDE_RECORDED ? c->aux[1] : c->main_stream));
   c->g.free_in_capture = c->capturing;
   return RGCN_OK;
 }
@@ -706,7 +761,11 @@ rgcn_status rgcn_step_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t E, int
   // only -- on a side stream beside the forward pass: 0.567 ms per step against 0.559 on the same box.  A fork + join costs
   // the main stream more than the 13 us pass it hides.)
   RGCN_TRY(forward_all(c, train, seed, nullptr));
-  RGCN_TRY(backward_all(c, dcodes_dev));
+  // The step ends without a join (bwd_layer_partial, bwd_end): its caller gets the gradients through calls that join.
+  c->defer_end_joins = true;
+  const rgcn_status bs = backward_all(c, dcodes_dev);
+  c->defer_end_joins = false;
+  RGCN_TRY(bs);
   return step_end(c);
 }
 
@@ -816,9 +875,14 @@ rgcn_status rgcn_optimizer_step(rgcn_ctx* c) {
   RGCN_NEED(c);
   if (c->world > 1 && !c->comm)
     RGCN_FAIL(c, RGCN_ERR_STATE, "world > 1: call rgcn_comm_init first (or drive rgcn_optimizer_norm_partial / _apply yourself)");
+  RGCN_TRY(join_abandoned_side_work(c));      // (the gradients of a step that ended unjoined)
   return optimizer_step(c);
 }
-rgcn_status rgcn_optimizer_norm_partial(rgcn_ctx* c) { RGCN_NEED(c); return optimizer_norm_partial(c); }
+rgcn_status rgcn_optimizer_norm_partial(rgcn_ctx* c) {
+  RGCN_NEED(c);
+  RGCN_TRY(join_abandoned_side_work(c));
+  return optimizer_norm_partial(c);
+}
 rgcn_status rgcn_optimizer_apply(rgcn_ctx* c) { RGCN_NEED(c); return optimizer_apply(c); }
 
 // everything of a train step behind the graph preparation: encoder forward, decoder loss + gradients, encoder
@@ -937,6 +1001,7 @@ rgcn_status rgcn_set_graph_dropout_device(rgcn_ctx* c, const int32_t* batch_dev,
   if (keep < 0 || keep > n) RGCN_FAIL(c, RGCN_ERR_INVALID, "edge dropout: keep outside [0, num_edges]");
   if (n >= ((int64_t)1 << 24)) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "edge dropout: more than 2^24 batch edges");
   if (n > 0 && !batch_dev) RGCN_FAIL(c, RGCN_ERR_INVALID, "NULL triples");
+  RGCN_TRY(join_abandoned_side_work(c));
   return graph_build_dropout(c, batch_dev, n, keep, seed, keep_mask_dev);
 }
 
@@ -1097,6 +1162,7 @@ rgcn_status rgcn_graph_launch(rgcn_ctx* c, int32_t graph_id) {
   if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "a capture is running");
   if (graph_id < 0 || graph_id >= (int32_t)c->graphs.size() || !c->graphs[graph_id])
     RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown graph id");
+  RGCN_TRY(join_abandoned_side_work(c));      // (the replayed steps rewrite everything unjoined side kernels touch)
   RGCN_HIP(c, hipGraphLaunch(c->graphs[graph_id], c->main_stream));
   c->fwd_done = true;       // the replayed steps leave activations / gradients of their last step behind
   c->weights_version += 1;  // a replayed train step moved the weights behind the host's back: derived weight tables
@@ -1238,6 +1304,8 @@ rgcn_status rgcn_device_free(rgcn_ctx* c, void* dev) {
   if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "this call synchronises with the device: not allowed between rgcn_capture_begin and rgcn_capture_end");
   RGCN_HIP(c, hipStreamSynchronize(c->stream));
   if (dev) {
+    for (int k = 0; k < 2; ++k)      // unjoined side kernels may still be reading it (the dcodes of rgcn_step_device)
+      if (c->aux_dirty[k] && c->aux[k]) RGCN_HIP(c, hipStreamSynchronize(c->aux[k]));
     invalidate_prefetch_of(c, dev, 1);
     if (c->pf_stream) RGCN_HIP(c, hipStreamSynchronize(c->pf_stream));   // a prefetch may still be reading it
     RGCN_HIP(c, hipFree(dev));
@@ -1248,6 +1316,7 @@ rgcn_status rgcn_copy_to_device(rgcn_ctx* c, void* dev, const void* host, int64_
   RGCN_NEED(c);
   if (!dev || !host || bytes < 0) RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
   invalidate_prefetch_of(c, dev, (size_t)bytes);
+  RGCN_TRY(join_abandoned_side_work(c));      // (dev may be the dcodes unjoined side kernels still read)
   return to_dev(c, dev, host, (size_t)bytes);
 }
 rgcn_status rgcn_copy_to_device_async(rgcn_ctx* c, void* dev, const void* host, int64_t bytes,
@@ -1258,6 +1327,14 @@ rgcn_status rgcn_copy_to_device_async(rgcn_ctx* c, void* dev, const void* host, 
   if (bytes == 0) return RGCN_OK;
   invalidate_prefetch_of(c, dev, (size_t)bytes);
   hipStream_t st = on_prefetch_stream ? c->pf_stream : c->main_stream;
+  if (!on_prefetch_stream) {
+    RGCN_TRY(join_abandoned_side_work(c));    // as rgcn_copy_to_device
+  } else if (c->side_state != rgcn_ctx::SIDE_NONE) {
+    RGCN_HIP(c, hipStreamWaitEvent(st, c->ev_join[0], 0));      // (behind every side kernel that reads; the main stream pays nothing)
+  } else {
+    for (int k = 0; k < 2; ++k)
+      if (c->aux_dirty[k] && c->aux[k]) RGCN_HIP(c, hipStreamSynchronize(c->aux[k]));
+  }
   if ((size_t)bytes > rgcn_ctx::kStageBytes) {      // too large for a staging slot: ordered on `st`, host waits
     RGCN_HIP(c, hipMemcpyAsync(dev, host, (size_t)bytes, hipMemcpyHostToDevice, st));
     RGCN_HIP(c, hipStreamSynchronize(st));

@@ -22,6 +22,8 @@ namespace rgcn {
 // ---- rgcn_api.hip
 rgcn_status stream_join_both(rgcn_ctx* c);
 rgcn_status join_abandoned_side_work(rgcn_ctx* c);
+rgcn_status record_side_done(rgcn_ctx* c);
+rgcn_status join_side_reads(rgcn_ctx* c, hipEvent_t also = nullptr);
 int auto_split_k(int M, int N, int K, bool narrow = false);
 rgcn_status to_host(rgcn_ctx* c, void* host, const void* dev, size_t bytes);
 rgcn_status to_dev(rgcn_ctx* c, void* dev, const void* host, size_t bytes);

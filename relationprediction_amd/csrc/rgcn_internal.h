@@ -341,6 +341,17 @@ struct rgcn_ctx {
   int fuse = 1;
   uint64_t weights_version = 1;           // bumped whenever a parameter value changes (set_param, Adam)
   bool dw_pending = false;                // a dW-only message-gradient kernel of the previous backward layer is still on side stream 0
+  // Deferred end-of-step joins (rgcn_step_device at minibatch scale).  The backward pass of such a step
+  // ends WITHOUT making the main stream wait for its side kernels: aux_dirty[0 / 1] stay set ("gradients pending") and
+  //   SIDE_RECORDED: ev_join[0] (side stream 0, behind a wait for side stream 1) marks the end of every side kernel of the
+  //                  backward layers -- all that reads activations, D / dS and the graph -- but not of the bias gradient's
+  //                  column sums, which trail on side stream 1;
+  //   SIDE_READS_JOINED: the main stream has waited for that event (the next forward pass may overwrite the activations);
+  //                  the gradients themselves are still unjoined.
+  // A full join (join_abandoned_side_work, sync_all) returns to SIDE_NONE.
+  enum { SIDE_NONE = 0, SIDE_RECORDED = 1, SIDE_READS_JOINED = 2 };
+  int side_state = SIDE_NONE;
+  bool defer_end_joins = false;           // the backward pass in flight may end unjoined (set by rgcn_step_device)
   std::string err;
 
   std::vector<rgcn::Param> params;
@@ -367,8 +378,9 @@ struct rgcn_ctx {
   float* stage = nullptr;                // host<->device staging for layout conversion
   size_t stage_floats = 0;
   uint8_t* masks = nullptr;              // [L,V,d] explicit dropout masks
-  float* colsum_part = nullptr;
-  size_t colsum_part_floats = 0;
+  float* colsum_part = nullptr;           // two halves of colsum_part_floats each: a pass whose column sums finish on a side
+  size_t colsum_part_floats = 0;          // stream (deferred joins) leaves its half to them and hands the next pass the other
+  int colsum_half = 0;
   int32_t colsum_parts = 0;    // > 0: the last block_rows backward launch left that many [d] partial rows in colsum_part
   float* zeros = nullptr;                // 1024 zero floats (masked-lane load target of the GEMMs; 3 KB for a masked LDS-DMA)
 
@@ -453,6 +465,8 @@ struct StreamScope {
   ~StreamScope();
 };
 rgcn_status stream_join(rgcn_ctx* c, int k);
+// the column-sum scratch of the pass in flight (rgcn_ctx::colsum_part, the current half)
+inline float* colsum_scratch(const rgcn_ctx* c) { return c->colsum_part + (size_t)c->colsum_half * c->colsum_part_floats; }
 
 // Brackets a launch with events when profiling is on.
 struct ProfScope {

@@ -11,9 +11,10 @@ namespace rgcn {
 // ---------------------------------------------------------------- forward
 rgcn_status fwd_begin(rgcn_ctx* c, int train, uint64_t seed, const uint8_t* masks_host) {
   if (!c->g.ready) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_forward before rgcn_set_graph");
-  // (a backward pass that was driven layer by layer and abandoned between layers 2 and 1 left its side kernels unjoined:
-  // they read the activations this pass overwrites.  Nothing is queued in the usual case, where every pass ended joined.)
-  RGCN_TRY(join_abandoned_side_work(c));
+  // (side kernels the main stream has not joined -- a step that ended unjoined, rgcn_step_device; a backward pass driven
+  // layer by layer and abandoned between layers 2 and 1 -- read the activations this pass overwrites.  Nothing is queued
+  // where the last pass ended joined, or where step_begin took this wait together with the prefetched graph's.)
+  RGCN_TRY(join_side_reads(c));
   c->fwd_done = false;
   c->frag_fresh = false;
   c->wtile_fresh = false;
@@ -193,12 +194,26 @@ rgcn_status fwd_layer_finish(rgcn_ctx* c, int l) {
 }
 
 // ---------------------------------------------------------------- backward
+// The schedule whose end-of-pass joins may be deferred (rgcn_ctx::defer_end_joins): the single-pass block layer at
+// minibatch scale on one GPU with the side streams on, outside a capture, two layers or more (bwd_layer_partial's first
+// branch).  In that schedule dW_self always runs on side stream 1 and the relation-weight kernels on side stream 0, so a
+// pass that starts while the previous one's side kernels are unjoined queues its own behind them IN STREAM ORDER: the
+// slabs and the gradients they share need no event.
+static bool deferred_schedule(const rgcn_ctx* c) {
+  return c->defer_end_joins && c->kind == RGCN_KIND_BLOCK && c->fuse == 1 && block_rows_available(c) && c->world == 1 &&
+         c->g.E <= 65536 && c->use_aux && !c->capturing && c->L >= 2 && c->stream == c->main_stream;
+}
+
 // ds_ready: dcodes * dropout of the top layer, already written by the producer of dcodes (the device decoder does,
 // inside a train step): the scale-and-copy pass over [V,d] is skipped
 rgcn_status bwd_begin(rgcn_ctx* c, const float* dcodes_dev, const float* ds_ready) {
   if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_backward needs a completed rgcn_forward on the current graph");
   if (!dcodes_dev) RGCN_FAIL(c, RGCN_ERR_INVALID, "dcodes is NULL");
-  RGCN_TRY(join_abandoned_side_work(c));      // (an abandoned pass's side kernels read the dS / D buffers this one rewrites)
+  // Unjoined side kernels read the dS / D buffers this pass rewrites and write the gradients, slabs and column-sum partials
+  // it writes: the full join -- except from one deferred step to the next.  There the forward pass has waited for every side
+  // kernel that reads (SIDE_READS_JOINED), this pass's side kernels follow the pending ones in stream order, and its
+  // column-sum partials go to the other half of the scratch (bwd_end): the main stream waits for nothing.
+  if (!(c->side_state == rgcn_ctx::SIDE_READS_JOINED && deferred_schedule(c))) RGCN_TRY(join_abandoned_side_work(c));
   c->bwd_layer = c->L;
   c->bwd_D = dcodes_dev;
   DropSpec ds = make_drop(c, c->L, true);
@@ -286,6 +301,14 @@ rgcn_status bwd_layer_partial(rgcn_ctx* c, int l) {
       // none of those (its rows go to g_emb) and queues its side kernels behind them in stream order: its joins cover
       // both layers, and the main stream saves two waits between the layers.
       defer_joins = l == 2;
+      // Layer 1 of a step that may end unjoined (rgcn_step_device): nothing on the main stream behind this layer touches
+      // what the side kernels read or write, so the main stream does not wait for them either.  One event marks their end
+      // (record_side_done); the next forward pass, the prefetch stream and whoever wants the gradients wait for it --
+      // DESIGN.md section 5.1 lists who.
+      if (l == 1 && deferred_schedule(c)) {
+        RGCN_TRY(record_side_done(c));
+        defer_joins = true;
+      }
       if (!defer_joins) RGCN_TRY(stream_join_both(c));
     } else if (minibatch) {
       RGCN_TRY(block_msg_backward(c, l, Hin, c->bwd_D, nullptr));
@@ -391,6 +414,23 @@ rgcn_status bwd_end(rgcn_ctx* c) {
   if (c->bwd_layer != 0) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_backward_end before all layers ran");
   // AffineTransform: dW_emb = dH0 * (H0 > 0) is already in g_emb; db_emb = column sums
   // (single-pass block layer on one GPU: the bottom layer's row-gradient kernel left the column sums of its rows as partials)
+  if (c->defer_end_joins && c->side_state == rgcn_ctx::SIDE_RECORDED && c->stream == c->main_stream && c->colsum_parts > 0) {
+    // Deferred end (bwd_layer_partial, layer 1): the sum of the partials is 4 us of work nothing in the step waits for.  It
+    // trails on side stream 1, behind the row kernel that left the partials; side stream 1 then waits for side stream 0, so
+    // that its end is the end of everything the step launched (step_end records the graph set's ev_free there).  The next
+    // pass writes its partials to the other half of the scratch: ordered behind this sum by the events of the pass between.
+    {
+      StreamScope side(c, 1);
+      if (!side.active) RGCN_FAIL(c, RGCN_ERR_HIP, "internal: fork onto side stream 1 failed");
+      RGCN_TRY(column_sum_finish(c, c->gb_emb, c->colsum_parts, c->d));
+    }
+    RGCN_HIP(c, hipStreamWaitEvent(c->aux[1], c->ev_join[0], 0));
+    c->colsum_half ^= 1;
+    c->colsum_parts = 0;
+    c->dw_pending = false;
+    return RGCN_OK;
+  }
+  if (c->side_state != rgcn_ctx::SIDE_NONE) RGCN_TRY(join_abandoned_side_work(c));      // (no partials were left, or a second rgcn_backward_end: gb_emb)
   if (c->colsum_parts > 0) RGCN_TRY(column_sum_finish(c, c->gb_emb, c->colsum_parts, c->d));
   else RGCN_TRY(column_sum(c, c->g_emb, c->gb_emb, c->V, c->d));
   c->colsum_parts = 0;

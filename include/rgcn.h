@@ -63,6 +63,17 @@ enum { RGCN_KIND_BLOCK = 0, RGCN_KIND_BASIS = 1 };
  * values in sorted-row order); NONE = the 'none' branch (:70-81). */
 enum { RGCN_NORM_INTENDED = 0, RGCN_NORM_TF_AS_EXECUTED = 1, RGCN_NORM_NONE = 2 };
 
+/* What lies under the first graph convolution (code/common/model_builder.py:140-165,277-283).
+ * EMBEDDING = UseInputTransform=Yes: AffineTransform H_0 = relu(W_emb + b_emb), every layer dense.
+ * ONEHOT    = UseInputTransform=No (RandomInput=No, PartiallyRandomInput=No): no input layer; the first BasisGcn has
+ *             onehot_input=True and looks its messages up in per-entity tables (gcn_basis.py:16-24,60-71,
+ *             message_gcn.py:28-79, shared_functions.py:5-9).  Basis kind on one GPU only: with RGCN_KIND_BLOCK (the
+ *             reference's one-hot branch of ConcatGcn cannot execute, gcn_basis_concat.py:18-19,42-46), with world > 1
+ *             or with EntityCount * NumberOfBasisFunctions * dim >= 2^31 rgcn_create returns RGCN_ERR_UNSUPPORTED.
+ *             rgcn_capture_begin returns RGCN_ERR_UNSUPPORTED on such a context (a captured one-hot step has not
+ *             been tested).  Any other value of the field: RGCN_ERR_INVALID. */
+enum { RGCN_INPUT_EMBEDDING = 0, RGCN_INPUT_ONEHOT = 1 };
+
 /* Buffers readable through rgcn_read_buffer (tests / the sharding exchange). */
 enum {
   RGCN_BUF_EXCHANGE = 0,   /* [V,d] buffer a multi-GPU run all-reduces (partial pre-activation / partial dH) */
@@ -104,7 +115,7 @@ typedef struct rgcn_config {
   int64_t max_edges;      /* capacity: largest E ever passed to rgcn_set_graph* */
   int32_t rank;           /* relation-sharding rank in [0, world) */
   int32_t world;          /* number of relation shards (1 = single GPU) */
-  int32_t reserved;       /* must be 0 */
+  int32_t input_mode;     /* RGCN_INPUT_* (0 = embedding input, what every earlier caller passed here) */
 } rgcn_config;
 
 /* ---- lifecycle ------------------------------------------------------------------------------ */
@@ -131,6 +142,9 @@ rgcn_status rgcn_sync(rgcn_ctx* ctx);
  *                                                           (gcn_basis_concat.py:30-33)
  *                      BASIS: W_f [d,B,d], W_b [d,B,d], C_f [R,B], C_b [R,B], W_self [d,d], b [d]
  *                                                           (gcn_basis.py:33-37)
+ * RGCN_INPUT_ONEHOT (basis kind; model_builder.py:140-165,277-283, gcn_basis.py:16-24): no W_emb / b_emb, and layer 1 is
+ *                      W_f [V,B,d], W_b [V,B,d], C_f [R,B], C_b [R,B], W_self [V,d], b [d]; layers 2..L as above.
+ *                      rgcn_param_count / _info / rgcn_set_param / rgcn_get_param / rgcn_get_grad all follow that list.
  * Host layouts are the reference's (row-major, shapes above); the device layout is private.
  * `b` is created but never used by the reference layers: it is stored, never read,
  * and its gradient is all zeros.  The LAST parameter is the decoder's W_relation [EntityCount, d]
@@ -179,6 +193,7 @@ rgcn_status rgcn_get_graph_edges(rgcn_ctx* ctx, int32_t* host, int64_t count);
 rgcn_status rgcn_forward(rgcn_ctx* ctx, int32_t train, uint64_t dropout_seed,
                          const uint8_t* dropout_masks_host);
 rgcn_status rgcn_get_codes(rgcn_ctx* ctx, float* host, int64_t count);              /* H_L  */
+/* RGCN_INPUT_ONEHOT: there is no H_0 (message_gcn.py:28-36 hands the layer the vertex ids); layer 0 is RGCN_ERR_INVALID */
 rgcn_status rgcn_get_activation(rgcn_ctx* ctx, int32_t layer, float* host, int64_t count); /* H_0..H_L */
 rgcn_status rgcn_get_dropout_mask(rgcn_ctx* ctx, int32_t layer /*1..L*/, uint8_t* host, int64_t count);
 const float* rgcn_codes_device(rgcn_ctx* ctx);                                      /* device H_L */

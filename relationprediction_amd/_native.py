@@ -23,6 +23,8 @@ BUF_EXCHANGE, BUF_SELF, BUF_DSELF_EXCHANGE, BUF_INDEG, BUF_OUTDEG, BUF_ROWPTR, B
 
 KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS}
 NORMS = {"intended": NORM_INTENDED, "tf_as_executed": NORM_TF_AS_EXECUTED, "none": NORM_NONE}
+INPUT_EMBEDDING, INPUT_ONEHOT = 0, 1
+INPUT_MODES = {"embedding": INPUT_EMBEDDING, "onehot": INPUT_ONEHOT}
 
 
 class RgcnError(RuntimeError):
@@ -37,7 +39,7 @@ class RgcnConfig(C.Structure):
         ("num_relations", C.c_int32), ("dim", C.c_int32), ("num_layers", C.c_int32),
         ("kind", C.c_int32), ("num_bases", C.c_int32), ("keep_prob", C.c_float),
         ("norm_mode", C.c_int32), ("max_edges", C.c_int64), ("rank", C.c_int32),
-        ("world", C.c_int32), ("reserved", C.c_int32),
+        ("world", C.c_int32), ("input_mode", C.c_int32),
     ]
 
 
@@ -249,10 +251,12 @@ class NeighborhoodSampler:
 
 
 class Engine:
-    """One rgcn_ctx: the encoder (input layer + L relational graph-convolution layers) on one GPU."""
+    """One rgcn_ctx: the encoder (input layer + L relational graph-convolution layers) on one GPU.
+    input_mode "embedding": AffineTransform under the layers (UseInputTransform=Yes); "onehot": no input layer, the
+    first basis layer reads per-entity tables (UseInputTransform=No; include/rgcn.h RGCN_INPUT_ONEHOT)."""
 
     def __init__(self, num_entities, num_relations, dim, num_layers, kind, num_bases, keep_prob=0.8,
-                 norm_mode="intended", max_edges=0, device=0, rank=0, world=1, devtools=False):
+                 norm_mode="intended", max_edges=0, device=0, rank=0, world=1, devtools=False, input_mode="embedding"):
         self.lib = load_library(devtools=devtools)
         self.ctx = None
         cfg = RgcnConfig()
@@ -269,7 +273,7 @@ class Engine:
         cfg.max_edges = int(max_edges)
         cfg.rank = int(rank)
         cfg.world = int(world)
-        cfg.reserved = 0
+        cfg.input_mode = INPUT_MODES[input_mode] if isinstance(input_mode, str) else int(input_mode)
         self.cfg = cfg
         ctx = C.c_void_p()
         st = self.lib.rgcn_create(C.byref(cfg), C.byref(ctx))

@@ -1,7 +1,8 @@
 """Plugin registry (reference: code/common/model_builder.py): maps `Encoder.Name` and its flags to a
-chain of components.  Only the hot-path family is built: `Name=gcn_basis` with UseInputTransform=Yes,
-UseOutputTransform=No and none of the experimental layer flags (exactly settings/gcn_block.exp and
-settings/gcn_basis.exp); everything else raises NotImplementedError naming SURVEY.md section 2's
+chain of components.  Only the hot-path family is built: `Name=gcn_basis` with UseOutputTransform=No and none of the
+experimental layer flags -- UseInputTransform=Yes (exactly settings/gcn_block.exp and settings/gcn_basis.exp) or, for
+the basis kind, UseInputTransform=No: the featureless encoder whose first layer reads one-hot entity ids
+(:140-165,277-283); everything else raises NotImplementedError naming SURVEY.md section 2's
 out-of-scope row instead of silently building something different."""
 from ..decoders.bilinear_diag import BilinearDiag
 from ..encoders.affine_transform import AffineTransform
@@ -20,8 +21,14 @@ def build_encoder(encoder_settings, triples):
     if name != "gcn_basis":
         raise NotImplementedError("encoder '%s' is outside the accelerated path (SURVEY.md section 2); "
                                   "only 'gcn_basis' (ConcatGcn / BasisGcn stacks) is built" % name)
-    if _flag(encoder_settings, 'UseInputTransform') != "Yes":
-        raise NotImplementedError("UseInputTransform=No (one-hot first layer / RandomInput variants)")
+    input_transform = _flag(encoder_settings, 'UseInputTransform', None)
+    if input_transform not in ("Yes", "No"):
+        raise NotImplementedError("UseInputTransform must be Yes or No (the reference reads it unconditionally, "
+                                  "model_builder.py:140), got %r" % (input_transform,))
+    concat = _flag(encoder_settings, 'Concatenation') == "Yes"
+    if input_transform == "No" and concat:
+        raise NotImplementedError("UseInputTransform=No with Concatenation=Yes: the reference's one-hot branch of "
+                                  "ConcatGcn cannot execute (gcn_basis_concat.py:18-19,42-46)")
     for key in ('UseOutputTransform', 'AddDiagonal', 'DiagonalCoefficients', 'StoreEdgeData', 'RandomInput',
                 'PartiallyRandomInput'):
         if _flag(encoder_settings, key) == "Yes":
@@ -38,18 +45,22 @@ def build_encoder(encoder_settings, triples):
         raise NotImplementedError("CodeDimension != InternalEncoderDimension needs UseOutputTransform=Yes")
     layers = int(encoder_settings['NumberOfLayers'])
 
-    encoding = AffineTransform(input_shape, encoder_settings, next_component=graph, onehot_input=True,
-                               use_bias=True, use_nonlinearity=True)
-    encoding = apply_basis_gcn(encoder_settings, encoding, internal_shape, layers)
+    if input_transform == "Yes":
+        encoding = AffineTransform(input_shape, encoder_settings, next_component=graph, onehot_input=True,
+                                   use_bias=True, use_nonlinearity=True)
+    else:
+        encoding = graph      # RandomInput / PartiallyRandomInput are refused above: the layers sit on the graph itself
+    encoding = apply_basis_gcn(encoder_settings, encoding, internal_shape, layers,
+                               onehot_first=input_transform == "No")
     return RelationEmbedding(relation_shape, encoder_settings, next_component=encoding)
 
 
-def apply_basis_gcn(encoder_settings, encoding, internal_shape, layers):
+def apply_basis_gcn(encoder_settings, encoding, internal_shape, layers, onehot_first=False):
     concat = 'Concatenation' in encoder_settings and encoder_settings['Concatenation'] == "Yes"
     layer_class = ConcatGcn if concat else BasisGcn
     for layer in range(layers):
-        encoding = layer_class(internal_shape, encoder_settings, next_component=encoding, onehot_input=False,
-                               use_nonlinearity=layer < layers - 1)
+        encoding = layer_class(internal_shape, encoder_settings, next_component=encoding,
+                               onehot_input=onehot_first and layer == 0, use_nonlinearity=layer < layers - 1)
     return encoding
 
 

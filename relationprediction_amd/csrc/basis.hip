@@ -543,13 +543,17 @@ rgcn_status basis_dcoef(rgcn_ctx* c, int layer, const float* Hin, const float* d
       hipLaunchKernelGGL((k_basis_dcoef<1>), dim3(nchunks), dim3(256), 0, c->stream, a);
     RGCN_HIP(c, hipGetLastError());
   }
-  {
-    const int n = R2 * c->B;
-    ProfScope ps(c, "basis_dcoef_reduce", 8.0 * n, 0);
-    hipLaunchKernelGGL(k_basis_dcoef_reduce, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->slab_dw,
-                       c->g.chunk_ptr, c->layers[layer].gcoef, R2, c->B);
-    RGCN_HIP(c, hipGetLastError());
-  }
+  return basis_dcoef_reduce(c, layer);
+}
+
+// gcoef of `layer` = the chunk partials in rgcn_ctx::slab_dw ([chunks][B]) summed per directed relation, in chunk order
+rgcn_status basis_dcoef_reduce(rgcn_ctx* c, int layer) {
+  const int R2 = 2 * c->R;
+  const int n = R2 * c->B;
+  ProfScope ps(c, "basis_dcoef_reduce", 8.0 * n, 0);
+  hipLaunchKernelGGL(k_basis_dcoef_reduce, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->slab_dw,
+                     c->g.chunk_ptr, c->layers[layer].gcoef, R2, c->B);
+  RGCN_HIP(c, hipGetLastError());
   return RGCN_OK;
 }
 

@@ -367,9 +367,21 @@ static rgcn_status create_impl(rgcn_ctx* c) {
   if (f.norm_mode < 0 || f.norm_mode > 2) RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown norm_mode");
   if (f.world < 1 || f.rank < 0 || f.rank >= f.world) RGCN_FAIL(c, RGCN_ERR_INVALID, "need 0 <= rank < world");
   if (f.max_edges < 0 || f.max_edges > (int64_t)500 * 1000 * 1000) RGCN_FAIL(c, RGCN_ERR_INVALID, "max_edges out of range");
-  if (f.reserved != 0) RGCN_FAIL(c, RGCN_ERR_INVALID, "reserved must be 0");
+  if (f.input_mode != RGCN_INPUT_EMBEDDING && f.input_mode != RGCN_INPUT_ONEHOT)
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown input_mode (0: embedding input, 1: RGCN_INPUT_ONEHOT)");
   c->V = f.num_entities; c->R = f.num_relations; c->d = f.dim; c->L = f.num_layers; c->kind = f.kind;
   c->rank = f.rank; c->world = f.world;
+  c->onehot = f.input_mode == RGCN_INPUT_ONEHOT;
+  if (c->onehot) {
+    // the featureless first layer (model_builder.py:277-283): BasisGcn only, per-entity tables on one GPU
+    if (f.kind != RGCN_KIND_BASIS)
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_INPUT_ONEHOT with the block kind: the reference's one-hot branch of ConcatGcn "
+                                         "cannot execute (gcn_basis_concat.py:18-19,42-46)");
+    if (f.world > 1)
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_INPUT_ONEHOT on a sharded context (the [V,B,d] tables are not sharded)");
+    if ((int64_t)f.num_entities * f.num_bases * (int64_t)f.dim >= ((int64_t)1 << 31))
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_INPUT_ONEHOT: EntityCount x NumberOfBasisFunctions x dimension must be below 2^31");
+  }
   // the library's radix sort takes keys below 2^24 (csr_sort.hip): vertex ids and directed-relation ids
   if (c->V >= (1 << 24) || 2 * (int64_t)c->R >= (1 << 24))
     RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "EntityCount and 2 x RelationCount must be below 2^24 (sort key range of this build)");
@@ -433,12 +445,14 @@ static rgcn_status create_impl(rgcn_ctx* c) {
   // padding rows stay zero
   const size_t V = c->V, d = c->d, R = c->R, Vd = (size_t)c->V_pad * d;
   RGCN_HIP(c, hipEventCreateWithFlags(&c->ev_gather, hipEventDisableTiming));
-  RGCN_TRY(dmalloc(c, &c->w_emb, Vd));
-  RGCN_TRY(dmalloc(c, &c->g_emb, Vd));
-  RGCN_TRY(dmalloc(c, &c->b_emb, d));
-  RGCN_TRY(dmalloc(c, &c->gb_emb, d));
-  add_param(c, "W_emb", {(int64_t)V, (int64_t)d}, c->w_emb, c->g_emb, LAYOUT_PLAIN);
-  add_param(c, "b_emb", {(int64_t)d}, c->b_emb, c->gb_emb, LAYOUT_PLAIN);
+  if (!c->onehot) {      // (one-hot input: no AffineTransform under the layers, model_builder.py:140-165)
+    RGCN_TRY(dmalloc(c, &c->w_emb, Vd));
+    RGCN_TRY(dmalloc(c, &c->g_emb, Vd));
+    RGCN_TRY(dmalloc(c, &c->b_emb, d));
+    RGCN_TRY(dmalloc(c, &c->gb_emb, d));
+    add_param(c, "W_emb", {(int64_t)V, (int64_t)d}, c->w_emb, c->g_emb, LAYOUT_PLAIN);
+    add_param(c, "b_emb", {(int64_t)d}, c->b_emb, c->gb_emb, LAYOUT_PLAIN);
+  }
   c->layers.resize(c->L + 1);
   // world > 1: the gradients every rank holds a partial sum of -- W_self, and the basis tensors -- sit in ONE
   // allocation, layer after layer, so that the backward pass ends with one all-reduce instead of 2-3 per layer
@@ -451,6 +465,27 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     LayerBufs& lb = c->layers[l];
     const std::string sl = std::to_string(l);
     float* repl = c->repl_grads ? c->repl_grads + repl_per_layer * (l - 1) : nullptr;
+    if (c->onehot && l == 1) {
+      // BasisGcn with onehot_input=True (gcn_basis.py:16-24): vertex_feature_dimension = EntityCount -- W_forward,
+      // W_backward [V,B,d] and W_self [V,d] are lookup tables, kept in the host layout; no GEMM, no fragment tables
+      const size_t per_dir = V * (size_t)c->B * d;
+      RGCN_TRY(dmalloc(c, &lb.wrel, 2 * per_dir));
+      RGCN_TRY(dmalloc(c, &lb.grel, 2 * per_dir));
+      RGCN_TRY(dmalloc(c, &lb.coef, 2 * R * c->B));
+      RGCN_TRY(dmalloc(c, &lb.gcoef, 2 * R * c->B));
+      add_param(c, "W_f1", {(int64_t)V, c->B, (int64_t)d}, lb.wrel, lb.grel, LAYOUT_PLAIN);
+      add_param(c, "W_b1", {(int64_t)V, c->B, (int64_t)d}, lb.wrel + per_dir, lb.grel + per_dir, LAYOUT_PLAIN);
+      add_param(c, "C_f1", {(int64_t)R, c->B}, lb.coef, lb.gcoef, LAYOUT_PLAIN);
+      add_param(c, "C_b1", {(int64_t)R, c->B}, lb.coef + R * c->B, lb.gcoef + R * c->B, LAYOUT_PLAIN);
+      RGCN_TRY(dmalloc(c, &lb.wself, V * d));
+      RGCN_TRY(dmalloc(c, &lb.gwself, V * d));
+      RGCN_TRY(dmalloc(c, &lb.bias, d));
+      RGCN_TRY(dmalloc(c, &lb.gbias, d));
+      add_param(c, "W_self1", {(int64_t)V, (int64_t)d}, lb.wself, lb.gwself, LAYOUT_PLAIN);
+      add_param(c, "b1", {(int64_t)d}, lb.bias, lb.gbias, LAYOUT_PLAIN);
+      c->params.back().no_grad = true;
+      continue;
+    }
     if (c->kind == RGCN_KIND_BLOCK) {
       const size_t per_dir = R * c->nb * c->sd * c->sd;
       RGCN_TRY(dmalloc(c, &lb.wrel, 2 * per_dir));
@@ -493,7 +528,7 @@ static rgcn_status create_impl(rgcn_ctx* c) {
   RGCN_TRY(dmalloc(c, &c->g_rel, Vd));
   add_param(c, "W_relation", {(int64_t)V, (int64_t)d}, c->w_rel, c->g_rel, LAYOUT_PLAIN);
   c->H.assign(c->L + 1, nullptr);
-  for (int l = 0; l <= c->L; ++l) RGCN_TRY(dmalloc(c, &c->H[l], Vd));
+  for (int l = c->onehot ? 1 : 0; l <= c->L; ++l) RGCN_TRY(dmalloc(c, &c->H[l], Vd));      // (one-hot input: no H_0)
   RGCN_TRY(dmalloc(c, &c->self_buf, Vd));
   if (c->world > 1) RGCN_TRY(dmalloc(c, &c->exch, Vd));
   for (int k = 0; k < 2; ++k) {
@@ -515,7 +550,7 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     RGCN_TRY(dmalloc(c, &c->msgbuf2, V * zc));
     RGCN_TRY(dmalloc(c, &c->aggbuf, 2 * V * d));     // [2][V][d]: unit products (forward), gathered upstream rows (backward)
     c->zsave.assign(c->L + 1, nullptr);
-    for (int l = 1; l <= c->L; ++l) RGCN_TRY(dmalloc(c, &c->zsave[l], V * zc));
+    for (int l = c->onehot ? 2 : 1; l <= c->L; ++l) RGCN_TRY(dmalloc(c, &c->zsave[l], V * zc));   // (a one-hot layer 1 has no Z)
     const size_t s2 = 16 * zc * d;
     if (s2 > slab) slab = s2;
     c->slab_dw_floats = max_rel_chunks * (size_t)c->B;
@@ -677,6 +712,7 @@ rgcn_status rgcn_forward(rgcn_ctx* c, int32_t train, uint64_t seed, const uint8_
 rgcn_status rgcn_get_activation(rgcn_ctx* c, int32_t layer, float* host, int64_t count) {
   RGCN_NEED(c);
   if (layer < 0 || layer > c->L) RGCN_FAIL(c, RGCN_ERR_INVALID, "layer out of range");
+  if (c->onehot && layer == 0) RGCN_FAIL(c, RGCN_ERR_INVALID, "RGCN_INPUT_ONEHOT: there is no H_0 (the first layer reads entity ids)");
   if (!host || count != (int64_t)c->V * c->d) RGCN_FAIL(c, RGCN_ERR_INVALID, "need a [V,d] host buffer");
   if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "no completed forward pass");
   RGCN_TRY(check_dev_flag(c));
@@ -1075,6 +1111,9 @@ rgcn_status rgcn_capture_begin(rgcn_ctx* c) {
   RGCN_NEED(c);
   if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "a capture is already running");
   if (c->prof_on) RGCN_FAIL(c, RGCN_ERR_STATE, "switch the per-kernel profile off before capturing");
+  if (c->onehot)
+    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "rgcn_capture_begin: capture on an RGCN_INPUT_ONEHOT context is not supported (a captured "
+                                       "one-hot step has never been replayed against a reference)");
   // Sharded contexts: the step contains RCCL collectives, which a stream capture records like any other launch.  That
   // path is exercised with device-side stand-in collectives of several ranks on ONE GPU only
   // (tests/test_gpu_multiprocess.py::test_captured_sharded_train_step); real librccl kernels inside a capture have never

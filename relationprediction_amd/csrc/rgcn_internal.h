@@ -154,6 +154,7 @@ struct Param {
 struct LayerBufs {
   // BLOCK: wrel = [2R][sd*sd][nb] (first R = W_forward, last R = W_backward), same for grel.
   // BASIS: wrel = [2][B][d][d]  (GEMM operand [2B*d, d]); coef = [2R][B] (first R = C_forward).
+  // BASIS, layer 1 of a one-hot context: wrel = [2][V][B][d] (the host layout), wself = [V][d], no fragment tables.
   float* wrel = nullptr;
   float* grel = nullptr;
   float* coef = nullptr;
@@ -322,6 +323,7 @@ struct rgcn_ctx {
   rgcn_config cfg;
   int V = 0, R = 0, d = 0, L = 0, nb = 0, sd = 0, kind = 0, B = 0;
   int rank = 0, world = 1;
+  bool onehot = false;          // featureless first layer (RGCN_INPUT_ONEHOT): no W_emb / b_emb / H_0, layer 1 is basis_onehot.hip
   int row_lo = 0, row_hi = 0;   // row shard of this rank: [rank * shard_rows, +shard_rows) cut at V
   int shard_rows = 0;           // ceil(V / world): equal chunks for the reduce-scatter / all-gather
   int V_pad = 0;                // world * shard_rows: rows every exchanged [V,d] buffer is allocated with
@@ -569,11 +571,18 @@ struct CombineArgs;
 rgcn_status basis_backward_gather(rgcn_ctx* c, int layer, const float* dZ, const CombineArgs& ca,
                                   bool with_messages);
 rgcn_status basis_dcoef(rgcn_ctx* c, int layer, const float* Hin, const float* dZ);
+rgcn_status basis_dcoef_reduce(rgcn_ctx* c, int layer);   // the chunk partials in slab_dw -> gcoef of `layer`
 double basis_units(rgcn_ctx* c);      // (row, direction) units of the current graph (profile accounting)
 // Dc[dir][i][:] = D[row of unit i of direction dir][:]  (the compacted upstream rows, [2][V][d])
 rgcn_status basis_gather_units(rgcn_ctx* c, const float* D, float* Dc);
 rgcn_status basis_to_device_layout(rgcn_ctx* c, const float* host_layout_dev, float* dst);
 rgcn_status basis_from_device_layout(rgcn_ctx* c, const float* src, float* host_layout_dev);
+
+// ---- basis_onehot.hip: the featureless first layer (rgcn_config::input_mode == RGCN_INPUT_ONEHOT, basis kind): layer 1's
+// weights are per-entity tables [2][V][B][d] (LayerBufs::wrel) and W_self [V,d], messages are table rows
+rgcn_status onehot_forward(rgcn_ctx* c, float* out);                 // H_1 = act(dropout(W_self) + gathered table rows)
+rgcn_status onehot_backward_tables(rgcn_ctx* c, const float* D);     // dW_forward, dW_backward from D = dL/dpre1
+rgcn_status onehot_dcoef(rgcn_ctx* c, const float* D);               // dC_forward, dC_backward
 
 // ---- elementwise.hip
 struct CombineArgs {

@@ -27,6 +27,7 @@ rgcn_status fwd_begin(rgcn_ctx* c, int train, uint64_t seed, const uint8_t* mask
     RGCN_TRY(to_dev(c, c->masks, masks_host, n));
     c->explicit_masks = true;
   }
+  if (c->onehot) return RGCN_OK;      // no AffineTransform under the layers: layer 1 reads entity ids (basis_onehot.hip)
   return input_forward(c);
 }
 
@@ -105,6 +106,9 @@ static double basis_unit_share(rgcn_ctx* c) { return basis_units(c) / (2.0 * c->
 
 rgcn_status fwd_layer_partial(rgcn_ctx* c, int l) {
   if (l < 1 || l > c->L) RGCN_FAIL(c, RGCN_ERR_INVALID, "layer out of range");
+  // featureless first layer (world == 1): one destination-major kernel, messages looked up in the [V,B,d] tables, the
+  // combine -- W_self row, dropout, relu -- as its epilogue; no GEMM
+  if (c->onehot && l == 1) return onehot_forward(c, c->H[1]);
   const float* Hin = c->H[l - 1];
   const int d = c->d, V = c->V;
   const int lo = c->world > 1 ? c->row_lo : 0, hi = c->world > 1 ? c->row_hi : V;
@@ -230,6 +234,20 @@ rgcn_status bwd_begin(rgcn_ctx* c, const float* dcodes_dev, const float* ds_read
 
 rgcn_status bwd_layer_partial(rgcn_ctx* c, int l) {
   if (l != c->bwd_layer || l < 1) RGCN_FAIL(c, RGCN_ERR_STATE, "backward layers must run L..1 in order");
+  if (c->onehot && l == 1) {
+    // Featureless first layer: D = dL/dpre1 (the layer above applied relu'(H_1); L = 1: the codes' gradient), dS = D *
+    // dropout_1.  Nothing lies below, so there is no dH -- no self-loop GEMMs, no relu' of an H_0, no column sums:
+    //   dW_self = dS (a copy), the tables' gradient source-major, the coefficients' per relation chunk.
+    // The coefficient kernel reads the tables and D, the table kernel writes the tables' gradient: independent, the former
+    // on side stream 0 beside the latter (which is bound by its 2 V B d writes).
+    {
+      StreamScope side(c, 0);
+      RGCN_TRY(onehot_dcoef(c, c->bwd_D));
+    }
+    RGCN_TRY(relu_copy(c, c->bwd_dS, c->layers[1].gwself, (int64_t)c->V * c->d, 0));
+    RGCN_TRY(onehot_backward_tables(c, c->bwd_D));
+    return stream_join(c, 0);
+  }
   const float* Hin = c->H[l - 1];
   const int d = c->d, V = c->V;
   const int lo = c->world > 1 ? c->row_lo : 0, hi = c->world > 1 ? c->row_hi : V;
@@ -412,6 +430,11 @@ rgcn_status bwd_layer_finish(rgcn_ctx* c, int l) {
 
 rgcn_status bwd_end(rgcn_ctx* c) {
   if (c->bwd_layer != 0) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_backward_end before all layers ran");
+  if (c->onehot) {      // no W_emb / b_emb: nothing of the bottom-layer work exists (no relu' of H_0, no column sums)
+    if (c->side_state != rgcn_ctx::SIDE_NONE) RGCN_TRY(join_abandoned_side_work(c));
+    c->dw_pending = false;
+    return stream_join(c, 0);
+  }
   // AffineTransform: dW_emb = dH0 * (H0 > 0) is already in g_emb; db_emb = column sums
   // (single-pass block layer on one GPU: the bottom layer's row-gradient kernel left the column sums of its rows as partials)
   if (c->defer_end_joins && c->side_state == rgcn_ctx::SIDE_RECORDED && c->stream == c->main_stream && c->colsum_parts > 0) {

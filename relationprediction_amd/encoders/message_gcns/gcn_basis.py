@@ -6,6 +6,10 @@ W_r = sum_b C[r, b] W_b: message = sum_b C[r,b] (x . W[:, b, :]) (:39-68).  Weig
 order (:15-30): W_forward, W_backward `[d, B, d]` (in, basis, out), W_self `[d, d]`, all
 N(0, glorot_variance([d, d])); C_forward, C_backward `[R, B]` ~ N(0, 1); b = 0, never added.
 `get_weights()` order (:33-37): W_forward, W_backward, C_forward, C_backward, W_self, b.
+
+`onehot_input=True` (the first layer under UseInputTransform=No, model_builder.py:277-283): the vertex feature
+dimension is EntityCount (:16), so W_forward, W_backward are `[V, B, d]` and W_self `[V, d]` lookup tables, all
+N(0, glorot_variance([V, d])), same creation order (engine: csrc/basis_onehot.hip).
 """
 from ...common.shared_functions import glorot_variance, make_variable, make_bias
 from ...model import Variable
@@ -20,7 +24,7 @@ class BasisGcn(MessageGcn):
         self.n_coefficients = int(self.settings['NumberOfBasisFunctions'])
 
     def create_variables(self):
-        d_in, d_out = self.shape[0], self.shape[1]
+        d_in, d_out = (self.entity_count if self.onehot_input else self.shape[0]), self.shape[1]
         type_matrix_shape = (self.relation_count, self.n_coefficients)
         vertex_matrix_shape = (d_in, self.n_coefficients, d_out)
         self_matrix_shape = (d_in, d_out)

@@ -6,6 +6,7 @@ forward / backward messages, compute the self-loop term, drop out ONLY the self-
 mode (:60-64), combine.  All of it runs inside the engine (rgcn_forward); a layer object here
 contributes its hyper-parameters and weights and reads back its own activation.
 """
+from ...extras.graph_representations import Representation
 from ...model import Model
 from ...runtime import EncoderRuntime
 
@@ -36,8 +37,8 @@ class MessageGcn(Model):
         while isinstance(comp, MessageGcn):
             below.append(comp)
             comp = comp.next_component
-        affine = comp
-        rep = affine.next_component
+        # under the stack: the input layer and the graph, or (UseInputTransform=No) the graph itself
+        affine, rep = (None, comp) if isinstance(comp, Representation) else (comp, comp.next_component)
         if rep.runtime is None:
             # `self` may be an inner layer asked directly; the stack always starts at the top layer,
             # which registered itself on the representation when the chain was initialised
@@ -55,7 +56,7 @@ class MessageGcn(Model):
         comp = self.next_component
         while isinstance(comp, MessageGcn):
             comp = comp.next_component
-        rep = comp.next_component
+        rep = comp if isinstance(comp, Representation) else comp.next_component
         if not hasattr(rep, '_top_gcn'):
             rep._top_gcn = self
 

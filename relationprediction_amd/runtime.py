@@ -12,7 +12,8 @@ from . import _native
 
 class EncoderRuntime(object):
     def __init__(self, layers, affine, representation):
-        """layers: MessageGcn components bottom -> top."""
+        """layers: MessageGcn components bottom -> top.  affine: the input layer under them, or None when the bottom
+        layer is featureless (onehot_input=True, UseInputTransform=No: it reads entity ids, there is no H_0)."""
         self.layers = layers
         self.affine = affine
         self.representation = representation
@@ -25,8 +26,12 @@ class EncoderRuntime(object):
             if l.use_nonlinearity != (i < len(layers) - 1):
                 raise NotImplementedError("only 'relu on all but the last layer' stacks are supported "
                                           "(model_builder.py:275)")
-            if l.onehot_input:
-                raise NotImplementedError("onehot_input graph-convolution layers (UseInputTransform=No)")
+            if l.onehot_input != (i == 0 and affine is None):
+                raise NotImplementedError("onehot_input belongs to the bottom layer of a stack without an input "
+                                          "transform, and to no other (model_builder.py:277-283)")
+        if affine is None and self.kind != "basis":
+            raise NotImplementedError("UseInputTransform=No with Concatenation=Yes: the reference's one-hot branch of "
+                                      "ConcatGcn cannot execute (gcn_basis_concat.py:18-19,42-46)")
         s = top.settings
         self.V, self.R = top.entity_count, top.relation_count
         self.d = int(top.shape[1])
@@ -37,7 +42,8 @@ class EncoderRuntime(object):
             max_edges = max(max_edges, int(s['GraphBatchSize']))
         self.engine = _native.Engine(self.V, self.R, self.d, len(layers), self.kind, top.n_coefficients,
                                      keep_prob=top.dropout_keep_probability, norm_mode=norm,
-                                     max_edges=max_edges, device=device)
+                                     max_edges=max_edges, device=device,
+                                     input_mode="embedding" if affine is not None else "onehot")
         self._state = None        # (graph version, mode) of the activations held by the engine
         self._dev = {}            # persistent device buffers of the fused train step (name -> DeviceBuffer)
         self._dec_reserved = 0
@@ -46,8 +52,9 @@ class EncoderRuntime(object):
         self.weights_version = 0
         self._fwd_weights_version = -1
         # move the weights into the engine (names follow rgcn_param_info)
-        affine.W.bind(*self._accessors("W_emb"))
-        affine.b.bind(*self._accessors("b_emb"))
+        if affine is not None:
+            affine.W.bind(*self._accessors("W_emb"))
+            affine.b.bind(*self._accessors("b_emb"))
         for i, l in enumerate(layers, start=1):
             l.layer_index = i
             for var, base in l.engine_variables():

@@ -60,8 +60,16 @@ enum { RGCN_KIND_BLOCK = 0, RGCN_KIND_BASIS = 1 };
 /* Neighbour normalisation of the incidence matrices, normalization=('global', ...)
  * (code/extras/graph_representations.py:82-93,122-133).  INTENDED = 1/deg(row of this edge);
  * TF_AS_EXECUTED = SURVEY.md section 9 H1 (tf.sparse_softmax on non-canonical indices returns the
- * values in sorted-row order); NONE = the 'none' branch (:70-81). */
-enum { RGCN_NORM_INTENDED = 0, RGCN_NORM_TF_AS_EXECUTED = 1, RGCN_NORM_NONE = 2 };
+ * values in sorted-row order); NONE = the 'none' branch (:70-81).
+ * LOCAL = normalization=('local', ...) (code/extras/graph_representations.py:94-107,134-147: softmax of ones over the
+ * entries that share (relation, row), summed over the relation axis), the paper's c_{i,r} = |N_i^r|: of a fed triple
+ * (s, r, o) the forward message (directed relation r, destination o) gets 1 / |{fed (s', r, o)}| and the backward
+ * message (directed relation R + r, destination s) gets 1 / |{fed (s, r, o')}|.  Counts run over the triples actually
+ * fed (after edge dropout: the kept ones); duplicates count once each; a self-edge counts in both directions.  As
+ * written only: there is no as-executed reading of 'local' (the H1 hazard would apply to the reference's 3-D softmax
+ * as it does to the 2-D one).  Under relation sharding the counts need no exchange: a relation's owner holds every
+ * message of it.  Any other value of the field: RGCN_ERR_INVALID. */
+enum { RGCN_NORM_INTENDED = 0, RGCN_NORM_TF_AS_EXECUTED = 1, RGCN_NORM_NONE = 2, RGCN_NORM_LOCAL = 3 };
 
 /* What lies under the first graph convolution (code/common/model_builder.py:140-165,277-283).
  * EMBEDDING = UseInputTransform=Yes: AffineTransform H_0 = relu(W_emb + b_emb), every layer dense.
@@ -90,9 +98,12 @@ enum {
    * directed relation r (m < E) or R + r */
   RGCN_BUF_PERM_VERTEX = 8,     /* int32 [2E] incidence ids in incidence-CSR order (by vertex, ties by id) */
   RGCN_BUF_PERM_RELATION = 9,   /* int32 [2E] message ids in message-list order (by directed relation, ties by id) */
-  RGCN_BUF_RANK_ENERGIES = 10   /* float [reserved queries, V] energies of the last chunk rgcn_rank_device or
+  RGCN_BUF_RANK_ENERGIES = 10,  /* float [reserved queries, V] energies of the last chunk rgcn_rank_device or
                                    rgcn_topk_device scored (the float half of the ranking; the counts and the selection
                                    are integer work on exactly these values) */
+  RGCN_BUF_MSG_NORM = 11        /* float [2E] normalisation of every message, in message-list order: entry j belongs to
+                                   message RGCN_BUF_PERM_RELATION[j] (every RGCN_NORM_* mode).  Sharded context: only
+                                   this rank's messages, which come first in the list; the rest is undefined */
 };
 
 /*

@@ -17,14 +17,25 @@ LIB_PATH = os.path.join(_HERE, "lib", "librgcn.so")
 
 ABI_VERSION = 1
 KIND_BLOCK, KIND_BASIS = 0, 1
-NORM_INTENDED, NORM_TF_AS_EXECUTED, NORM_NONE = 0, 1, 2
+NORM_INTENDED, NORM_TF_AS_EXECUTED, NORM_NONE, NORM_LOCAL = 0, 1, 2, 3
 BUF_EXCHANGE, BUF_SELF, BUF_DSELF_EXCHANGE, BUF_INDEG, BUF_OUTDEG, BUF_ROWPTR, BUF_NORM_EXCHANGE, \
-    BUF_DBASIS_EXCHANGE, BUF_PERM_VERTEX, BUF_PERM_RELATION, BUF_RANK_ENERGIES = range(11)
+    BUF_DBASIS_EXCHANGE, BUF_PERM_VERTEX, BUF_PERM_RELATION, BUF_RANK_ENERGIES, BUF_MSG_NORM = range(12)
 
 KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS}
-NORMS = {"intended": NORM_INTENDED, "tf_as_executed": NORM_TF_AS_EXECUTED, "none": NORM_NONE}
+NORMS = {"intended": NORM_INTENDED, "tf_as_executed": NORM_TF_AS_EXECUTED, "none": NORM_NONE, "local": NORM_LOCAL}
+
 INPUT_EMBEDDING, INPUT_ONEHOT = 0, 1
 INPUT_MODES = {"embedding": INPUT_EMBEDDING, "onehot": INPUT_ONEHOT}
+
+
+def norm_mode_value(norm_mode):
+    """RGCN_NORM_* value of a name (the `IncidenceNormalization` settings key) or of a number"""
+    if isinstance(norm_mode, str):
+        if norm_mode not in NORMS:
+            raise ValueError("IncidenceNormalization / norm_mode must be one of %s, not %r"
+                             % (", ".join(sorted(NORMS, key=NORMS.get)), norm_mode))
+        return NORMS[norm_mode]
+    return int(norm_mode)
 
 
 class RgcnError(RuntimeError):
@@ -269,7 +280,7 @@ class Engine:
         cfg.kind = KINDS[kind] if isinstance(kind, str) else int(kind)
         cfg.num_bases = int(num_bases)
         cfg.keep_prob = float(keep_prob)
-        cfg.norm_mode = NORMS[norm_mode] if isinstance(norm_mode, str) else int(norm_mode)
+        cfg.norm_mode = norm_mode_value(norm_mode)
         cfg.max_edges = int(max_edges)
         cfg.rank = int(rank)
         cfg.world = int(world)
@@ -438,6 +449,7 @@ class Engine:
     def step_device(self, triples_dev, num_edges, dcodes_dev, train=True, seed=0):
         self._check(self.lib.rgcn_step_device(self.ctx, triples_dev.ptr, int(num_edges), 1 if train else 0,
                                               C.c_uint64(seed), dcodes_dev.ptr))
+        self.num_edges = int(num_edges)
 
     # -- decoder / optimizer / whole train step on the device
     def decoder_reserve(self, max_triples):
@@ -594,6 +606,7 @@ class Engine:
     def train_step_device(self, triples_dev, num_edges, x_dev, y_dev, num_triples, seed=0, reg_param=0.01):
         self._check(self.lib.rgcn_train_step_device(self.ctx, triples_dev.ptr, int(num_edges), x_dev.ptr, y_dev.ptr,
                                                     int(num_triples), C.c_uint64(seed), C.c_float(reg_param)))
+        self.num_edges = int(num_edges)
 
     def prefetch_graph_device(self, triples_dev, num_edges):
         self._check(self.lib.rgcn_prefetch_graph_device(self.ctx, triples_dev.ptr, int(num_edges)))
@@ -630,6 +643,8 @@ class Engine:
             out = np.empty(self.V + 1, dtype=np.int32)
         elif which in (BUF_PERM_VERTEX, BUF_PERM_RELATION):
             out = np.empty(2 * self.num_edges, dtype=np.int32)
+        elif which == BUF_MSG_NORM:
+            out = np.empty(2 * self.num_edges, dtype=np.float32)
         elif which == BUF_RANK_ENERGIES:
             out = np.empty((getattr(self, "_rank_reserved", 0), self.V), dtype=np.float32)
         elif which == BUF_DSELF_EXCHANGE:

@@ -15,6 +15,18 @@
 //     the forward pass (rows = destinations) and to slot pos[(m+E) mod 2E] in the backward pass
 //     (rows = sources): one sort serves both directions.
 //
+// RGCN_NORM_LOCAL (code/extras/graph_representations.py:94-107,134-147, the 'local' branch: softmax of ones over the
+// entries that share (relation, row), summed over the relation axis): norm = 1 / |{fed messages with this message's
+// directed relation AND destination}| -- the paper's c_{i,r} = |N_i^r|.  Only the as-written meaning exists: the
+// tf.sparse_softmax ordering hazard would hit the reference's 3-D call like its 2-D one, and no as-executed
+// variant of 'local' is built.  The count needs no kernel of its own: the incidence CSR is sorted by (vertex, directed
+// relation), so the messages that share both are one run of equal keys in keyv_s and k_build_msgs measures the run with
+// two binary searches (integer work: no atomics, independent of launch geometry and of the row's length).  Where the
+// key cannot carry the relation (vmul == 1, (V+1) 2R >= 2^31) one more job of the radix sort orders the relation-sorted
+// message list by destination -- stable, so (destination, relation) pairs sit in runs -- and the search runs over that.
+// Under relation sharding a relation's owner holds ALL messages of that relation: the counts are complete with no
+// exchange, where the global modes need the all-edges degrees.
+//
 // All of it is stream-ordered with no host synchronisation, so a step can be graph-captured.
 // The two sorts are ONE call of the library's own stable LSD radix sort (csr_sort.hip: both sorts share its
 // launches; deterministic order => deterministic fp32 sums), whose last pass also writes the slot of every incidence.
@@ -235,6 +247,35 @@ __device__ __forceinline__ int upper_bound_dev(const int32_t* a, int n, int x) {
   return lo;
 }
 
+// RGCN_NORM_LOCAL without the relation in the vertex key: sort key of entry j of the relation-sorted message list = its
+// destination (V: beyond the owned messages)
+__global__ void k_dst_keys(const int32_t* __restrict__ tri, int E, int V, int R, const int32_t* __restrict__ permr,
+                           const uint32_t* __restrict__ keyr_s, uint32_t* keyd) {
+  int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= 2 * E) return;
+  const int m = permr[j];
+  keyd[j] = keyr_s[j] < (uint32_t)(2 * R) ? (uint32_t)(m < E ? tri[3 * m + 2] : tri[3 * (m - E)]) : (uint32_t)V;
+}
+
+// number of entries of a sequence sorted by (a, b) that equal (x, y); b is read through `via` (nullptr: a alone, y unused)
+__device__ __forceinline__ int run_length(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                          const int32_t* __restrict__ via, int n, uint32_t x, uint32_t y) {
+  int lo = 0, hi = n;     // first entry >= (x, y)
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    const uint32_t am = a[mid];
+    if (am < x || (am == x && via != nullptr && b[via[mid]] < y)) lo = mid + 1; else hi = mid;
+  }
+  const int first = lo;
+  hi = n;                 // first entry > (x, y)
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    const uint32_t am = a[mid];
+    if (am < x || (am == x && (via == nullptr || b[via[mid]] <= y))) lo = mid + 1; else hi = mid;
+  }
+  return lo - first;
+}
+
 __global__ void k_build_msgs(const int32_t* __restrict__ tri, int E, int V, int R, int norm_mode,
                              const int32_t* __restrict__ permr, const int32_t* __restrict__ rel_ptr,
                              const int32_t* __restrict__ pos, const int32_t* __restrict__ indeg,
@@ -242,7 +283,9 @@ __global__ void k_build_msgs(const int32_t* __restrict__ tri, int E, int V, int 
                              const int32_t* __restrict__ cum_out, int32_t* m_src, int32_t* m_dst,
                              int32_t* m_dslot, int32_t* m_sslot, float* m_norm,
                              const uint32_t* __restrict__ keyr_s, int slot_arrays, int32_t* d_src,
-                             int32_t* d_rel, float* d_norm, int32_t* s_dst, int32_t* s_rel, float* s_norm) {
+                             int32_t* d_rel, float* d_norm, int32_t* s_dst, int32_t* s_rel, float* s_norm,
+                             const uint32_t* __restrict__ keyv_s, uint32_t vmul, const uint32_t* __restrict__ keyd_s,
+                             const int32_t* __restrict__ permd) {
   int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= 2 * E) return;
   if (j >= rel_ptr[2 * R]) return;    // beyond the owned messages
@@ -256,6 +299,13 @@ __global__ void k_build_msgs(const int32_t* __restrict__ tri, int E, int V, int 
     norm = 1.0f;
   } else if (norm_mode == RGCN_NORM_INTENDED) {
     norm = 1.0f / (float)(fwd ? indeg[o] : outdeg[s]);
+  } else if (norm_mode == RGCN_NORM_LOCAL) {
+    // messages of this directed relation landing on this destination: a run of equal (vertex, relation) keys -- of the
+    // incidence CSR's sorted keys, or (vmul == 1) of the destination-sorted message list
+    const uint32_t rel2 = keyr_s[j];
+    const int cnt = keyd_s == nullptr ? run_length(keyv_s, nullptr, nullptr, 2 * E, (uint32_t)dst * vmul + rel2, 0u)
+                                      : run_length(keyd_s, keyr_s, permd, 2 * E, (uint32_t)dst, rel2);
+    norm = 1.0f / (float)cnt;
   } else {
     // tf_as_executed: value k of the sorted-row softmax is attached to edge k:
     // the k-th smallest row index is the vertex v with cum[v] <= k < cum[v+1].
@@ -439,6 +489,12 @@ int bits_for(uint32_t max_value) {
   return b;
 }
 
+// the vertex key carries the directed relation when (V + 1) 2R fits the sort's key range (every dataset of the reference;
+// otherwise rows keep incidence order: the layer kernels find fewer runs, nothing else changes)
+uint32_t vertex_key_mul(int V, int R) {
+  return (uint64_t)(V + 1) * (2 * (uint64_t)R) < (1ull << 31) ? (uint32_t)(2 * R) : 1u;
+}
+
 template <class T>
 rgcn_status dalloc(rgcn_ctx* c, T** p, size_t n) {
   RGCN_HIP(c, hipMalloc((void**)p, (n ? n : 1) * sizeof(T)));
@@ -525,6 +581,15 @@ rgcn_status graph_alloc(rgcn_ctx* c, const GraphBufs* share) {
   RGCN_TRY(dalloc(c, &g.keyr_t, M));
   RGCN_TRY(dalloc(c, &g.tablev, sort_table_elems(M)));
   RGCN_TRY(dalloc(c, &g.tabler, sort_table_elems(M)));
+  if (c->cfg.norm_mode == RGCN_NORM_LOCAL && vertex_key_mul(c->V, c->R) == 1u) {
+    // the message list by destination (see the header comment): only this mode, only where the vertex key is bare
+    RGCN_TRY(dalloc(c, &g.keyd, M));
+    RGCN_TRY(dalloc(c, &g.keyd_s, M));
+    RGCN_TRY(dalloc(c, &g.keyd_t, M));
+    RGCN_TRY(dalloc(c, &g.vald, M));
+    RGCN_TRY(dalloc(c, &g.permd, M));
+    RGCN_TRY(dalloc(c, &g.tabled, sort_table_elems(M)));
+  }
   return RGCN_OK;
 }
 
@@ -536,7 +601,7 @@ static void graph_free_one(GraphBufs& g, bool owns_shared) {
                   g.keyv, g.keyv_s, g.keyr, g.keyr_s, g.valv, g.permv, g.valr, g.permr, g.pos,
                   g.m_src, g.m_dst, g.m_dslot, g.m_sslot, g.m_norm, g.d_src, g.d_rel, g.d_norm, g.s_dst, g.s_rel,
                   g.s_norm, g.owner, g.errflag, g.keyv_t, g.keyr_t, g.tablev, g.tabler, g.row_key, g.row_key_s, g.row_order,
-                  g.row_tab, g.has_dir, g.unit_ptr, g.unit_rows};
+                  g.row_tab, g.has_dir, g.unit_ptr, g.unit_rows, g.keyd, g.keyd_s, g.keyd_t, g.vald, g.permd, g.tabled};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   g = GraphBufs();
@@ -564,9 +629,7 @@ rgcn_status graph_build(rgcn_ctx* c, const int32_t* tri, int64_t E64) {
   g.pf_valid = false;
   g.units_host = -1;
   c->fwd_done = false;
-  // the vertex key carries the directed relation when (V + 1) 2R fits the sort's key range (every dataset of the reference;
-  // otherwise rows keep incidence order: the layer kernels find fewer runs, nothing else changes)
-  const uint32_t vmul = (uint64_t)(V + 1) * (2 * (uint64_t)R) < (1ull << 31) ? (uint32_t)(2 * R) : 1u;
+  const uint32_t vmul = vertex_key_mul(V, R);
   const bool zero_in_keys = c->world == 1 && E > 0;      // (sharded: the degree counters are atomically added to)
   if (!zero_in_keys) RGCN_HIP(c, hipMemsetAsync(g.counters, 0, g.counters_bytes, c->stream));
   const int T = 256;
@@ -616,12 +679,21 @@ rgcn_status graph_build(rgcn_ctx* c, const int32_t* tri, int64_t E64) {
       hipLaunchKernelGGL(k_exscan, dim3(nj), dim3(kScanThreads), 0, c->stream, jobs);
     }
   }
+  if (E > 0 && g.keyd != nullptr) {
+    {
+      ProfScope ps(c, "prep_dst_keys", 12.0 * M, 0);
+      hipLaunchKernelGGL(k_dst_keys, dim3((M + T - 1) / T), dim3(T), 0, c->stream, tri, E, V, R, g.permr, g.keyr_s, g.keyd);
+    }
+    SortSpec sp{g.keyd, g.keyd_s, g.permd, g.keyd_t, g.vald, nullptr, g.tabled, (int64_t)M, (uint32_t)V};
+    RGCN_TRY(sort_pairs(c, "prep_sort_dst", 1, &sp));
+  }
   if (E > 0) {
     ProfScope ps(c, "prep_build_msgs", 12.0 * E + 36.0 * M, 0);
     hipLaunchKernelGGL(k_build_msgs, dim3((M + T - 1) / T), dim3(T), 0, c->stream, tri, E, V, R,
                        c->cfg.norm_mode, g.permr, g.rel_ptr, g.pos, g.indeg, g.outdeg, g.cum_in,
                        g.cum_out, g.m_src, g.m_dst, g.m_dslot, g.m_sslot, g.m_norm, g.keyr_s,
-                       g.d_src != nullptr ? 1 : 0, g.d_src, g.d_rel, g.d_norm, g.s_dst, g.s_rel, g.s_norm);
+                       g.d_src != nullptr ? 1 : 0, g.d_src, g.d_rel, g.d_norm, g.s_dst, g.s_rel, g.s_norm, g.keyv_s, vmul,
+                       g.keyd_s, g.permd);
   }
   RGCN_HIP(c, hipGetLastError());
   g.ready = true;

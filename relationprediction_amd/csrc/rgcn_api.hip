@@ -364,7 +364,7 @@ static rgcn_status create_impl(rgcn_ctx* c) {
                                    "NumberOfBasisFunctions must be positive");
   if (!(f.keep_prob > 0.0f && f.keep_prob <= 1.0f)) RGCN_FAIL(c, RGCN_ERR_INVALID, "DropoutKeepProbability must be in (0,1]");
   if (f.kind != RGCN_KIND_BLOCK && f.kind != RGCN_KIND_BASIS) RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown kind");
-  if (f.norm_mode < 0 || f.norm_mode > 2) RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown norm_mode");
+  if (f.norm_mode < 0 || f.norm_mode > RGCN_NORM_LOCAL) RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown norm_mode");
   if (f.world < 1 || f.rank < 0 || f.rank >= f.world) RGCN_FAIL(c, RGCN_ERR_INVALID, "need 0 <= rank < world");
   if (f.max_edges < 0 || f.max_edges > (int64_t)500 * 1000 * 1000) RGCN_FAIL(c, RGCN_ERR_INVALID, "max_edges out of range");
   if (f.input_mode != RGCN_INPUT_EMBEDDING && f.input_mode != RGCN_INPUT_ONEHOT)
@@ -1308,6 +1308,7 @@ static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* byte
     case RGCN_BUF_ROWPTR: *p = c->g.row_ptr; *bytes = (int64_t)(c->V + 1) * 4; return RGCN_OK;
     case RGCN_BUF_PERM_VERTEX: *p = c->g.permv; *bytes = (int64_t)2 * c->g.E * 4; return RGCN_OK;
     case RGCN_BUF_PERM_RELATION: *p = c->g.permr; *bytes = (int64_t)2 * c->g.E * 4; return RGCN_OK;
+    case RGCN_BUF_MSG_NORM: *p = c->g.m_norm; *bytes = (int64_t)2 * c->g.E * 4; return RGCN_OK;
     case RGCN_BUF_RANK_ENERGIES:
       if (!c->rank_s) RGCN_FAIL(c, RGCN_ERR_STATE, "no score buffer (rgcn_rank_reserve first)");
       *p = c->rank_s; *bytes = (int64_t)c->rank_max * c->V * 4; return RGCN_OK;

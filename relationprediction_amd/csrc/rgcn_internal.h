@@ -220,6 +220,11 @@ struct GraphBufs {
   int64_t units_host = -1;      // number of units, once somebody has read it back (profile accounting); -1: unknown
   uint32_t *keyv_t = nullptr, *keyr_t = nullptr;   // sort scratch (csr_sort.hip)
   uint16_t *tablev = nullptr, *tabler = nullptr;
+  // RGCN_NORM_LOCAL where the vertex key cannot carry the relation: the relation-sorted message list stably sorted by
+  // destination (keyd_s = destinations, permd = positions in the message list), and that sort's scratch
+  uint32_t *keyd = nullptr, *keyd_s = nullptr, *keyd_t = nullptr;
+  int32_t *vald = nullptr, *permd = nullptr;
+  uint16_t* tabled = nullptr;
   // prefetch bookkeeping (rgcn_prefetch_graph_device): which graph this set was prepared for
   const int32_t* pf_tri = nullptr;
   int64_t pf_E = -1;
@@ -268,6 +273,11 @@ struct DecoderBufs {
   double* loss = nullptr;
   uint32_t *keyv_t = nullptr, *keyr_t = nullptr;   // sort scratch (csr_sort.hip)
   uint16_t *tablev = nullptr, *tabler = nullptr;
+  // RGCN_NORM_LOCAL where the vertex key cannot carry the relation: the relation-sorted message list stably sorted by
+  // destination (keyd_s = destinations, permd = positions in the message list), and that sort's scratch
+  uint32_t *keyd = nullptr, *keyd_s = nullptr, *keyd_t = nullptr;
+  int32_t *vald = nullptr, *permd = nullptr;
+  uint16_t* tabled = nullptr;
   hipEvent_t ev_ready = nullptr;
   bool loss_valid = false;
 };

@@ -36,6 +36,7 @@ class EncoderRuntime(object):
         self.V, self.R = top.entity_count, top.relation_count
         self.d = int(top.shape[1])
         norm = s['IncidenceNormalization'] if 'IncidenceNormalization' in s else 'intended'
+        _native.norm_mode_value(norm)        # an unknown name: ValueError naming the accepted ones, before any engine exists
         device = int(s['Device']) if 'Device' in s else 0
         max_edges = max(int(top.edge_count), 1)
         if 'GraphBatchSize' in s:

@@ -37,6 +37,17 @@ rgcn_status rgcn_debug_gemm_time(rgcn_ctx* ctx, int32_t trans_a, int32_t trans_b
 rgcn_status rgcn_debug_gemm_presplit(rgcn_ctx* ctx, int32_t trans_b, int32_t M, int32_t N, int32_t K, int32_t iters,
                                      const float* a_host, const float* b_host, float* c_host, float* avg_ms);
 
+/* One product C[M,N] = relu(A + bias) . B through the A-operand prologue of the pre-split-weight NN kernels (GemmBatch::
+ * a_bias / a_out; csrc/gemm_bf16x3_w8.hip, csrc/gemm_bf16x3.hip APRO; modes 6 / 9), or -- prologue == 0 -- the plain product
+ * A . B on the same kernel.  A is [M,K] with leading dimension lda >= K, B is [K,N], bias is [K].  a_out_host ([M,lda], in
+ * and out) is copied to the device before the launch and back after it: what the kernel leaves untouched keeps the caller's
+ * values.  wide != 0: the 128 x 256 / eight-wavefront kernel, else the 128 x 128 one (the RGCN_GEMM_W8 knob is overridden
+ * for the call).  row_limit >= 0: the row extent is read on the device (GemmBatch::limit, the round-robin XCD swizzle) and
+ * rows >= row_limit do not exist; < 0: no limit (the contiguous XCD swizzle). */
+rgcn_status rgcn_debug_gemm_prologue(rgcn_ctx* ctx, int32_t wide, int32_t prologue, int32_t M, int32_t N, int32_t K,
+                                     int32_t lda, int32_t row_limit, const float* a_host, const float* bias_host,
+                                     const float* b_host, float* a_out_host, float* c_host);
+
 /* ---- placement self-check ---- */
 /* out_host[b] = the XCD (HW_REG_XCC_ID) workgroup b of a plain 1-D launch of n_blocks workgroups ran on.  The
  * destination-major block layer (csrc/block_rows.hip) and the decoder's line kernel give column band x to the workgroups

@@ -146,6 +146,8 @@ _DEVTOOLS_SIGS = {
                                              C.POINTER(C.c_float)]),
     "rgcn_debug_gemm_time": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_int32, _P, _P, C.POINTER(C.c_float)]),
+    "rgcn_debug_gemm_prologue": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, _P, _P, _P, _P, _P]),
 }
 _lib_devtools = None
 
@@ -770,6 +772,22 @@ class Engine:
         self._check(self.lib.rgcn_debug_gemm_presplit(self.ctx, int(trans_b), M, N, K, int(iters), _ptr(a), _ptr(b),
                                                       _ptr(out), C.byref(ms)))
         return (out, float(ms.value)) if iters else out
+
+    def debug_gemm_prologue(self, a, bias, b, a_out, wide=True, prologue=True, row_limit=-1):
+        """relu(a + bias) . b through the A-operand prologue of a pre-split-weight kernel (devtools build; prologue=False:
+        a . b on the same kernel).  a [M,lda] holds the operand in its first K = len(bias) columns; a_out [M,lda] is the
+        write-back target's content before the launch.  Returns (C, a_out after the launch)."""
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        bias = np.ascontiguousarray(bias, dtype=np.float32)
+        out_a = np.array(a_out, dtype=np.float32, order="C", copy=True)
+        M, lda = a.shape
+        K, N = b.shape
+        assert bias.shape == (K,) and out_a.shape == (M, lda)
+        out = np.empty((M, N), dtype=np.float32)
+        self._check(self.lib.rgcn_debug_gemm_prologue(self.ctx, int(bool(wide)), int(bool(prologue)), M, N, K, lda,
+                                                      int(row_limit), _ptr(a), _ptr(bias), _ptr(b), _ptr(out_a), _ptr(out)))
+        return out, out_a
 
     def debug_xcd_map(self, n_blocks):
         """XCD of every workgroup of a plain 1-D launch (devtools build)"""

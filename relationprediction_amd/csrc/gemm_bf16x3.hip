@@ -171,8 +171,18 @@ __device__ __forceinline__ bf16x8 load_frag(const uint32_t* __restrict__ plane, 
 // A (the activations) keeps the staged path.  Same products in the same order: bitwise the plain kernel's result.
 // (Measured, profiles/r05_gemm_presplit.md: 5-12 % on the NN form, 0-6 % on NT; letting the two waves that own the same 64
 // columns fetch half of the fragments each and swap them through LDS -- half the L1 requests -- changed nothing.)
-template <bool A_KC, bool B_KC, bool VEC, int TERMS, bool B_PRE = false>
+//
+// APRO (with B_PRE, k-contiguous A, 16-byte loads; GemmBatch::a_bias / a_out): the A-operand prologue with write-back, as in
+// k_gemm_w8 (gemm_bf16x3_w8.hip has the description).  A staged tile becomes fmaxf(a + a_bias[k], 0.f) at the top of the step
+// that splits it; the bias comes from an LDS copy behind the tile buffers whose entries k >= K are -inf, so that the zeros a
+// tile loads past the end of K stay exact zeros; the workgroups of column tile n0 == 0 store the transformed float4s of the
+// rows below Mlim and the k below K to a_out.  (Rows past Mlim load zeros here and become relu(bias): finite, and their
+// products are never stored.)  All loads and stores of this kernel are the compiler's to count.
+constexpr int PRO_OFF = 2 * 3 * KC_PLANE;                       // dwords: the bias copy starts behind B_PRE's two A tiles
+constexpr int PRO_BYTES = (PRO_MAX_KT + 1) * BK * 4;
+template <bool A_KC, bool B_KC, bool VEC, int TERMS, bool B_PRE = false, bool APRO = false>
 __global__ void __launch_bounds__(NTH, 2) k_gemm_bf16x3(XArgs g) {
+  static_assert(!APRO || (B_PRE && A_KC && VEC), "the prologue exists for the pre-split-weight NN form");
   constexpr int PA = A_KC ? KC_PLANE : RC_PLANE, PB = B_KC ? KC_PLANE : RC_PLANE;
   constexpr int TA = 3 * PA, TB = B_PRE ? 0 : 3 * PB;
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -288,6 +298,28 @@ __global__ void __launch_bounds__(NTH, 2) k_gemm_bf16x3(XArgs g) {
       }
     }
   };
+  // APRO: tile `tile` (relative to ks = 0: the form has no split over K) in xa -> transformed, written back
+  float* const lbias = reinterpret_cast<float*>(lds) + PRO_OFF;
+  const bool writes_a = APRO && n0 == 0 && g.batch.a_out != nullptr;
+  auto apro = [&](int tile, f32x4 (&xa)[2]) {
+    if constexpr (APRO) {
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        const int f = threadIdx.x + NTH * p;
+        const int row = m0 + (f >> 2), kq = (f & 3) * 4;
+        const f32x4 b = *reinterpret_cast<const f32x4*>(lbias + min(tile, nkt) * BK + kq);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xa[p][e] = fmaxf(xa[p][e] + b[e], 0.f);
+        const int k = tile * BK + kq;
+        if (writes_a && row < Mlim && k < ke)
+          *reinterpret_cast<f32x4*>(g.batch.a_out + (size_t)grp * g.batch.strideA + (size_t)row * g.lda + k) = xa[p];
+      }
+    }
+  };
+  if constexpr (APRO) {
+    for (int i = threadIdx.x; i < (nkt + 1) * BK; i += NTH) lbias[i] = i < ke ? g.batch.a_bias[i] : -__builtin_inff();
+    __syncthreads();
+  }
   auto sstore = [&](uint32_t* buf, f32x4 (&xa)[2], f32x4 (&xb)[2]) {
     SplitRegs st;
     split_chunks<A_KC, PA, 0, 12>(xa, st, buf);
@@ -339,6 +371,7 @@ __global__ void __launch_bounds__(NTH, 2) k_gemm_bf16x3(XArgs g) {
     const uint32_t negmask = (sign_group(kt + 1) & 1) ? 0x80000000u : 0u;   // sign of the tile this step stages
     if constexpr (WALK) gwalk(ra[P], rb[P]); else gload(ks + (kt + 2) * BK, ra[P], rb[P]);
     if constexpr (B_PRE) bfetch(kt + 1, fbp[1 - P]);
+    apro(kt + 1, ra[1 - P]);
     const uint32_t* a_lds = lds + P * (TA + TB);
     const uint32_t* b_lds = a_lds + TA;
     uint32_t* nxt = lds + (1 - P) * (TA + TB);
@@ -383,6 +416,7 @@ __global__ void __launch_bounds__(NTH, 2) k_gemm_bf16x3(XArgs g) {
   if (nkt > 0) {
     gload(ks, ra[0], rb[0]);
     if constexpr (B_PRE) bfetch(0, fbp[0]);
+    apro(0, ra[0]);
     sstore(lds, ra[0], rb[0]);
     gload(ks + BK, ra[1], rb[1]);
   }
@@ -458,10 +492,11 @@ constexpr size_t lds_bytes(bool a_kc, bool b_kc, bool b_pre = false) {
   return tiles > epi ? tiles : epi;
 }
 
-template <bool A_KC, bool B_KC, bool VEC, int TERMS, bool B_PRE = false>
+template <bool A_KC, bool B_KC, bool VEC, int TERMS, bool B_PRE = false, bool APRO = false>
 hipError_t launch_one(rgcn_ctx* c, const XArgs& g) {
-  constexpr size_t bytes = lds_bytes(A_KC, B_KC, B_PRE);
-  auto kern = k_gemm_bf16x3<A_KC, B_KC, VEC, TERMS, B_PRE>;
+  static_assert(!APRO || lds_bytes(A_KC, B_KC, B_PRE) == PRO_OFF * 4, "the bias copy starts where the tile buffers end");
+  constexpr size_t bytes = lds_bytes(A_KC, B_KC, B_PRE) + (APRO ? PRO_BYTES : 0);
+  auto kern = k_gemm_bf16x3<A_KC, B_KC, VEC, TERMS, B_PRE, APRO>;
   static uint64_t configured = 0;
   const hipError_t e = set_dynamic_lds(reinterpret_cast<const void*>(kern), (int)bytes, c->cfg.device, configured);
   if (e != hipSuccess) return e;
@@ -473,6 +508,9 @@ hipError_t launch_one(rgcn_ctx* c, const XArgs& g) {
 template <bool VEC, int TERMS>
 hipError_t launch_form(rgcn_ctx* c, bool a_kc, bool b_kc, const XArgs& g) {
   if constexpr (VEC) {      // pre-split B: k-contiguous A with 16-byte rows, no split over K (the caller checks)
+    if constexpr (TERMS != 3) {
+      if (g.bfrag != nullptr && a_kc && g.batch.a_bias != nullptr) return launch_one<true, true, true, TERMS, true, true>(c, g);
+    }
     if (g.bfrag != nullptr && a_kc) return launch_one<true, true, true, TERMS, true>(c, g);
   }
   if (a_kc && !b_kc) return launch_one<true, false, VEC, TERMS>(c, g);
@@ -523,6 +561,14 @@ __global__ void __launch_bounds__(256) k_presplit_b(PresplitJobs jobs) {
 
 }  // namespace
 
+bool gemm_a_prologue_ok(const rgcn_ctx* c, int N, int K, const float* A, int lda, const float* B, int ldb, const void* bfrag) {
+  auto vec = [](const float* p, int ld, int extent) {      // gemm_f32's condition for 16-byte loads
+    return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && ld % 4 == 0 && extent % 4 == 0 && extent >= 4;
+  };
+  (void)B; (void)ldb; (void)N;      // (B comes from its fragment table: any width, any alignment)
+  return (c->gemm_mode == 6 || c->gemm_mode == 9) && bfrag != nullptr && vec(A, lda, K) && (K + BK - 1) / BK <= PRO_MAX_KT;
+}
+
 size_t gemm_bfrag_words(int K, int N) {      // 16-byte words of one operand's fragment table
   return (size_t)((K + BK - 1) / BK) * bfrag_nt32(N) * 192;
 }
@@ -561,6 +607,10 @@ hipError_t gemm_bf16x3_launch(rgcn_ctx* c, int terms, bool a_kc, bool b_kc, bool
   g.tiles_m = (M + BM - 1) / BM;
   g.tiles_n = (N + BN - 1) / BN;
   g.nt32 = bfrag_nt32(N);
+  // the A-operand prologue exists in the two pre-split-weight NN kernels only: anything else is the caller's error
+  if (g.batch.a_bias != nullptr &&
+      !(g.bfrag != nullptr && !b_kc && g.batch.limit_on_k == 0 && (terms == 6 || terms == 9) && (K + BK - 1) / BK <= PRO_MAX_KT))
+    return hipErrorInvalidValue;
   // a weight on the B side: the eight-wavefront kernel (gemm_bf16x3_w8.hip), bitwise the same product
   // (devtools knob RGCN_GEMM_W8: 0 never, 1 where the call site asks for it, 2 / 3 everywhere).  The kernel reads
   // batch.limit as a row limit only.

@@ -40,6 +40,8 @@ constexpr int B_SZ = 24 * 1024;           // 8 column tiles x 3 planes x 1 KB, t
 constexpr int ST_SZ = A_SZ + B_SZ;        // one stage: 37376 B
 constexpr int W_LDS_BYTES = 4 * ST_SZ;    // 149504 B
 constexpr int WEPI_LD = WBN + 4;          // floats per staged row of the product
+// A-operand prologue (APRO): the bias vector's copy behind the ring, one 64-byte row per k-tile + one row of -inf
+constexpr int PRO_LDS_BYTES = (PRO_MAX_KT + 1) * BK * 4;      // 8 KB: 154 KB with the ring, of the CU's 160
 
 // loads the compiler must not count (it would drain them at the next ordinary use): destination registers are named by
 // the wait statement that retires them
@@ -49,6 +51,13 @@ __device__ __forceinline__ void aload(f32x4& dst, const float* p) {
 // the same from a wave-uniform base + a per-lane byte offset: the base walks on the scalar unit, no VALU per stage
 __device__ __forceinline__ void aload_s(f32x4& dst, uint32_t voff, const float* sbase) {
   asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(sbase) : "memory");
+}
+// the prologue's write-back of a transformed float4 (APRO): plain store (the row kernel's gathers read it next; `nt` stores of
+// the product cost their consumer more than they saved, profiles/r06_gemm_w8.md section 3).  The data register is an input
+// of the statement, so it is live -- and holds the transformed value -- until the store has issued; the hardware reads a
+// store's data before a later VALU write of the same register lands.
+__device__ __forceinline__ void astore_s(uint32_t voff, const f32x4& v, float* sbase) {
+  asm volatile("global_store_dwordx4 %0, %1, %2" : : "v"(voff), "v"(v), "s"(sbase) : "memory");
 }
 // one 1 KB piece (PIECE = 0, 1, 2: the immediate offset moves the source and the destination alike)
 template <int PIECE>
@@ -67,7 +76,22 @@ __device__ __forceinline__ void dma1(uint32_t voff, const u32x4* sbase, uint32_t
 
 // (192 registers, not the 193 the allocator would take: two wavefronts of this kernel then leave a SIMD 128 registers, one
 // wavefront of the 126-128-register layer kernels)
-template <int TERMS>
+//
+// APRO (A-operand prologue with write-back, GemmBatch::a_bias / a_out): every A element becomes fmaxf(a + a_bias[k], 0.f)
+// -- k_input_fwd's fp32 expression -- between the wait that retires its load and the split, and the workgroups of column
+// tile n0 == 0 (every row tile loads all of K: one column tile covers the operand) store the transformed float4 to a_out.
+//   * the bias comes from LDS: a copy made before the ring starts, behind the ring (PRO_LDS_BYTES), one ds_read_b128 per
+//     thread and stage -- no VMEM operation joins the ones the waits count;
+//   * k >= K of the copy is -inf: a stage past the end, or the missing part of a partial last tile, loads zeros, and
+//     fmaxf(0 + -inf, 0) = +0 -- padding still contributes exact zeros, with no select on the data.  Nothing is stored there
+//     (the lanes are masked), nor for the rows past Mlim, which re-read the last row;
+//   * vmcnt: gfx950 counts stores with the loads.  The store of stage t + 2 is issued behind step t's wait, i.e. between the
+//     loads of stages t + 4 and t + 5; at step t + 1's wait the operations younger than stage t + 3's loads are then 4 + 1
+//     + 4.  The wait stays `vmcnt(8)`: it retires one operation more than it must (the first 1 KB piece of stage t + 4, a
+//     whole step old), and it is right whether or not a wavefront's lanes store at all (masked rows, column tiles != 0);
+//   * registers: the bias float4 is live where everything else is, and the prologue instantiations take 196 (TERMS 6) / 198
+//     (9) registers, no scratch, still two wavefronts per SIMD (profiles/r08_input_prologue.md); the plain ones keep 192.
+template <int TERMS, bool APRO = false>
 __global__ void __launch_bounds__(WNTH, 2) __attribute__((amdgpu_num_vgpr(192))) k_gemm_w8(XArgs g) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
 
@@ -117,6 +141,19 @@ __global__ void __launch_bounds__(WNTH, 2) __attribute__((amdgpu_num_vgpr(192)))
   const float* sa = gA + (size_t)m0 * g.lda;            // wave-uniform, + BK floats per stage
   const uint32_t a_off = ((uint32_t)min(arow, Mlim - 1 - m0) * (uint32_t)g.lda + 4u * aq) * 4u;
   const bool atail_ok = 4 * aq < (g.K & (BK - 1));      // this thread's float4 exists in a partial last tile
+  // APRO: the bias copy; the rows of a_out this workgroup writes (for those a_off is the unclamped offset, and a_out has A's
+  // leading dimension: the store takes the load's offset)
+  float* const lbias = reinterpret_cast<float*>(lds) + W_LDS_BYTES / 4;
+  float* so = nullptr;
+  bool st_ok = false;
+  if constexpr (APRO) {
+    for (int i = threadIdx.x; i < (nkt + 1) * BK; i += WNTH) lbias[i] = i < g.K ? g.batch.a_bias[i] : -__builtin_inff();
+    if (n0 == 0 && g.batch.a_out != nullptr) {
+      so = g.batch.a_out + (size_t)grp * g.batch.strideA + (size_t)m0 * g.lda;
+      st_ok = arow < Mlim - m0;
+    }
+    __syncthreads();
+  }
   f32x4 ra[4];
   // its place in a stage: plane p at p * A_PL
   const uint32_t a_wr = (aq >> 1) * A_HS + arow * 16 + (aq & 1) * 8;
@@ -222,6 +259,14 @@ __global__ void __launch_bounds__(WNTH, 2) __attribute__((amdgpu_num_vgpr(192)))
       if constexpr (m < 12) read_frag(mi, st_rd, fn);
       // two steps' loads stay in flight: 2 x (3 DMA + 1 A)
       if constexpr (m == M_WAIT) asm volatile("s_waitcnt vmcnt(8)" : "+v"(rs) : : "memory");
+      if constexpr (APRO && m == M_WAIT) {      // stage t + 2: transform, write back (see the kernel's head comment)
+        const int s = t + 2;
+        const f32x4 b = *reinterpret_cast<const f32x4*>(lbias + min(s, nkt) * BK + 4 * aq);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) rs[e] = fmaxf(rs[e] + b[e], 0.f);
+        if (st_ok && (s < nfull || (s < nkt && atail_ok))) astore_s(a_off, rs, so);
+        so += BK;
+      }
       if constexpr (m > M_WAIT && (m - M_WAIT) % 2 == 1 && (m - M_WAIT) / 2 < 5)
         split_piece(std::integral_constant<int, (m - M_WAIT) / 2>{}, rs, st_wr, negmask);
       __builtin_amdgcn_sched_barrier(0);
@@ -295,14 +340,15 @@ __global__ void __launch_bounds__(WNTH, 2) __attribute__((amdgpu_num_vgpr(192)))
   }
 }
 
-template <int TERMS>
+template <int TERMS, bool APRO = false>
 hipError_t launch_w8(rgcn_ctx* c, const XArgs& g) {
-  auto kern = k_gemm_w8<TERMS>;
+  auto kern = k_gemm_w8<TERMS, APRO>;
+  constexpr int bytes = W_LDS_BYTES + (APRO ? PRO_LDS_BYTES : 0);
   static uint64_t configured = 0;
-  const hipError_t e = set_dynamic_lds(reinterpret_cast<const void*>(kern), W_LDS_BYTES, c->cfg.device, configured);
+  const hipError_t e = set_dynamic_lds(reinterpret_cast<const void*>(kern), bytes, c->cfg.device, configured);
   if (e != hipSuccess) return e;
   const int gx = g.swizzle == 2 ? ((g.tiles_m + 7) / 8) * 8 * g.tiles_n : g.tiles_m * g.tiles_n;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)g.batch.groups), dim3(WNTH), W_LDS_BYTES, c->stream, g);
+  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)g.batch.groups), dim3(WNTH), bytes, c->stream, g);
   return hipGetLastError();
 }
 
@@ -321,6 +367,10 @@ hipError_t gemm_bf16x3_w8_launch(rgcn_ctx* c, int terms, int M, int N, int K, co
   g.tiles_m = (M + WBM - 1) / WBM;
   g.tiles_n = (N + WBN - 1) / WBN;
   g.nt32 = bfrag_nt32(N);
+  if (batch.a_bias != nullptr) {      // the caller (gemm_bf16x3_launch) checked K against the bias copy's room
+    if (terms == 9) return launch_w8<9, true>(c, g);
+    return launch_w8<6, true>(c, g);
+  }
   if (terms == 9) return launch_w8<9>(c, g);
   return launch_w8<6>(c, g);
 }

@@ -354,11 +354,16 @@ rgcn_status gemm_f32(rgcn_ctx* c, const char* tag, bool a_kc, bool b_kc, int M, 
   if (M <= 0 || N <= 0) return RGCN_OK;
   const int groups = batch ? batch->groups : 1;
   if (a_kc == false && b_kc == true) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "gemm TT form not instantiated");
+  if (batch && batch->a_bias != nullptr && (c->gemm_mode == 0 || !a_kc || b_kc || split_k > 1))
+    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "gemm: the A-operand prologue exists in the pre-split-weight NN kernels only");
   const int bk = 16;
   GemmArgs g;
   g.A = A; g.B = B; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb;
-  const bool vec = vec_ok(A, lda, a_kc ? K : M) && vec_ok(B, ldb, b_kc ? K : N) &&
-                   (!batch || (batch->strideA % 4 == 0 && batch->strideB % 4 == 0));
+  // (the NN product with a pre-split weight fetches B from its fragment table and never loads B itself: B's own alignment
+  // and width do not matter there -- a weight of any width reaches the pre-split kernels, with or without the prologue)
+  const bool b_unread = batch && batch->bfrag != nullptr && a_kc && !b_kc && c->gemm_mode != 0 && split_k <= 1;
+  const bool vec = vec_ok(A, lda, a_kc ? K : M) && (b_unread || vec_ok(B, ldb, b_kc ? K : N)) &&
+                   (!batch || (batch->strideA % 4 == 0 && (b_unread || batch->strideB % 4 == 0)));
   g.swizzle = 1;
   g.zeros = c->zeros;
   if (batch) g.batch = *batch;
@@ -381,7 +386,9 @@ rgcn_status gemm_f32(rgcn_ctx* c, const char* tag, bool a_kc, bool b_kc, int M, 
   g.vecC = ((reinterpret_cast<uintptr_t>(g.C) & 15u) == 0 && g.ldc % 4 == 0 && N % 4 == 0) ? 1 : 0;
   {
     // (prof_scale: the share of the launch's M x K extent that exists on the device side -- compacted groups)
-    ProfScope ps(c, tag, prof_scale * groups * 4.0 * ((double)M * K + (double)K * N + (double)M * N),
+    // (the prologue's write-back of the transformed A operand: M x K floats more, design and compulsory alike)
+    const double a_out_elems = batch && batch->a_bias && batch->a_out ? (double)M * K : 0.0;
+    ProfScope ps(c, tag, prof_scale * groups * 4.0 * ((double)M * K + (double)K * N + (double)M * N + a_out_elems),
                  prof_scale * groups * 2.0 * M * N * K);
     if (c->gemm_mode != 0) {
       RGCN_HIP(c, gemm_bf16x3_launch(c, c->gemm_mode, a_kc, b_kc, vec, M, N, K, A, lda, B, ldb, g.C, g.ldc,

@@ -45,6 +45,8 @@ inline hipError_t set_dynamic_lds(const void* kern, int bytes, int device, uint6
 }
 
 constexpr int BM = 128, BN = 128, BK = 16, NTH = 256;
+// A-operand prologue (GemmBatch::a_bias): the kernels keep the bias vector in LDS, one row per k-tile of the contraction
+constexpr int PRO_MAX_KT = 127;
 constexpr int KC_LD = 12;                 // dwords per row of a k-contiguous plane (8 + 4 pad)
 constexpr int RC_LD = 136;                // dwords per k-pair row of a row-contiguous plane (128 + 8 pad)
 constexpr int KC_PLANE = 128 * KC_LD;     // 1536 dwords

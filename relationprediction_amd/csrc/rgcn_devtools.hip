@@ -93,6 +93,59 @@ rgcn_status rgcn_debug_gemm_presplit(rgcn_ctx* c, int32_t tb, int32_t M, int32_t
   return s;
 }
 
+rgcn_status rgcn_debug_gemm_prologue(rgcn_ctx* c, int32_t wide, int32_t prologue, int32_t M, int32_t N, int32_t K,
+                                     int32_t lda, int32_t row_limit, const float* a_host, const float* bias_host,
+                                     const float* b_host, float* a_out_host, float* c_host) {
+  RGCN_NEED(c);
+  if (M <= 0 || N <= 0 || K <= 0 || lda < K || row_limit > M || !a_host || !bias_host || !b_host || !a_out_host || !c_host)
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
+  float *A = nullptr, *B = nullptr, *C = nullptr, *bias = nullptr, *Aout = nullptr;
+  int32_t* lim = nullptr;
+  void* F = nullptr;
+  rgcn_status s = RGCN_OK;
+  // the kernel under test is chosen here, not by the tile-count heuristic (RGCN_GEMM_W8: 3 = wide everywhere, 0 = never)
+  const char* prev = getenv("RGCN_GEMM_W8");
+  const std::string saved = prev ? prev : "";
+  setenv("RGCN_GEMM_W8", wide ? "3" : "0", 1);
+  do {
+    if ((s = dmalloc(c, &A, (size_t)M * lda, false)) != RGCN_OK) break;
+    if ((s = dmalloc(c, &Aout, (size_t)M * lda, false)) != RGCN_OK) break;
+    if ((s = dmalloc(c, &B, (size_t)K * N, false)) != RGCN_OK) break;
+    if ((s = dmalloc(c, &bias, (size_t)K, false)) != RGCN_OK) break;
+    if ((s = dmalloc(c, &C, (size_t)M * N)) != RGCN_OK) break;
+    if ((s = dmalloc(c, &lim, 1)) != RGCN_OK) break;
+    if (hipMalloc(&F, 16 * gemm_bfrag_words(K, N)) != hipSuccess) { s = RGCN_ERR_NOMEM; break; }
+    if ((s = to_dev(c, A, a_host, sizeof(float) * (size_t)M * lda)) != RGCN_OK) break;
+    if ((s = to_dev(c, Aout, a_out_host, sizeof(float) * (size_t)M * lda)) != RGCN_OK) break;
+    if ((s = to_dev(c, B, b_host, sizeof(float) * (size_t)K * N)) != RGCN_OK) break;
+    if ((s = to_dev(c, bias, bias_host, sizeof(float) * (size_t)K)) != RGCN_OK) break;
+    if (row_limit >= 0 && (s = to_dev(c, lim, &row_limit, sizeof(int32_t))) != RGCN_OK) break;
+    const PresplitJob pj{B, F, N, K, N, 0};
+    if ((s = gemm_presplit_b(c, &pj, 1)) != RGCN_OK) break;
+    GemmBatch gb;
+    gb.bfrag = F;
+    gb.wide = wide ? 1 : 0;
+    if (row_limit >= 0) gb.limit = lim;
+    if (prologue) {
+      if (!gemm_a_prologue_ok(c, N, K, A, lda, B, N, F)) { c->err = "no prologue kernel takes this product"; s = RGCN_ERR_UNSUPPORTED; break; }
+      gb.a_bias = bias;
+      gb.a_out = Aout;
+    }
+    if ((s = gemm_f32(c, "debug_gemm", true, false, M, N, K, A, lda, B, N, C, N, 1, &gb)) != RGCN_OK) break;
+    if ((s = to_host(c, c_host, C, sizeof(float) * (size_t)M * N)) != RGCN_OK) break;
+    s = to_host(c, a_out_host, Aout, sizeof(float) * (size_t)M * lda);
+  } while (0);
+  if (prev) setenv("RGCN_GEMM_W8", saved.c_str(), 1); else unsetenv("RGCN_GEMM_W8");
+  if (A) (void)hipFree(A);
+  if (Aout) (void)hipFree(Aout);
+  if (B) (void)hipFree(B);
+  if (bias) (void)hipFree(bias);
+  if (C) (void)hipFree(C);
+  if (lim) (void)hipFree(lim);
+  if (F) (void)hipFree(F);
+  return s;
+}
+
 rgcn_status rgcn_debug_gemm_time(rgcn_ctx* c, int32_t ta, int32_t tb, int32_t M, int32_t N, int32_t K,
                                  int32_t split_k, int32_t iters, const float* a_host,
                                  const float* b_host, float* avg_ms) {

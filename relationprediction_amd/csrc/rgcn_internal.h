@@ -417,6 +417,7 @@ struct rgcn_ctx {
   bool frag_fresh = false;               // ... built since the last rgcn_forward_begin (captured steps rebuild once per step)
   bool wtile_fresh = false;              // the same for the band-tiled block weights (LayerBufs::wtile)
   bool fwd_done = false;
+  bool h0_in_gemm = false;               // fwd_begin left H0 = relu(W_emb + b_emb) to layer 1's self-loop product (rgcn_schedule.hip)
   int fwd_train = 0;
   uint64_t seed = 0;
   bool explicit_masks = false;
@@ -535,8 +536,17 @@ struct GemmBatch {
   // bit; which is faster in the step depends on what runs beside the product: the forward products
   // run alone on the main stream (wide), the backward ones beside dW_self and the relation-weight kernels (not wide).
   int wide = 0;
+  // optional A-operand prologue with write-back (the pre-split-weight NN kernels only: gemm_a_prologue_ok): every A element
+  // enters the product as fmaxf(a + a_bias[k], 0.f), and -- a_out != nullptr -- the transformed operand is also written to
+  // a_out, which has A's leading dimension and group stride.  Layer 1's self-loop product forms H0 = relu(W_emb + b_emb)
+  // this way, in k_input_fwd's arithmetic, from the operand it has in registers anyway.
+  const float* a_bias = nullptr;    // [K]
+  float* a_out = nullptr;
 };
 size_t gemm_bfrag_words(int K, int N);
+// whether gemm_f32 can take GemmBatch::a_bias for the NN product A[.,K] (lda) . B[K,N] (ldb) with B's fragment table given:
+// split arithmetic with six or nine products, 16-byte-loadable operands, K within the kernels' bias copy
+bool gemm_a_prologue_ok(const rgcn_ctx* c, int N, int K, const float* A, int lda, const float* B, int ldb, const void* bfrag);
 struct PresplitJob {
   const float* B;      // the operand B (k, n): stored [n][k] (b_kc) or [k][n], leading dimension ldb
   void* F;             // its fragment table, gemm_bfrag_words(K, N) 16-byte words

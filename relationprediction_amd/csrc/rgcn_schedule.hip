@@ -1,6 +1,9 @@
 // The per-layer orchestration of the encoder: which kernel goes to which stream, in which order.
 //   forward  (MessageGcn.compute_vertex_embeddings, code/encoders/message_gcns/message_gcn.py:49-79)
 //   backward (tf.gradients(loss, weights), code/optimization/abstract.py:117-118; formulas SURVEY 8a a15)
+// The forward pass of a block step is one chain on the main stream: [self-loop GEMM -> row kernel] x L.  H0 = relu(W_emb +
+// b_emb) is formed by layer 1's self-loop GEMM on load and written back by it where that GEMM has the A-operand prologue
+// (h0_by_self_loop_gemm below); everywhere else k_input_fwd opens the chain.
 // One schedule per situation: minibatch scale on one GPU with side streams, the chain a captured
 // step records, full-graph scale / a relation-sharded run (the exchange points of DESIGN.md section 7).  The C ABI that
 // drives these functions is rgcn_api.hip.
@@ -9,6 +12,8 @@
 namespace rgcn {
 
 // ---------------------------------------------------------------- forward
+static bool h0_by_self_loop_gemm(const rgcn_ctx* c);
+
 rgcn_status fwd_begin(rgcn_ctx* c, int train, uint64_t seed, const uint8_t* masks_host) {
   if (!c->g.ready) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_forward before rgcn_set_graph");
   // (side kernels the main stream has not joined -- a step that ended unjoined, rgcn_step_device; a backward pass driven
@@ -28,6 +33,11 @@ rgcn_status fwd_begin(rgcn_ctx* c, int train, uint64_t seed, const uint8_t* mask
     c->explicit_masks = true;
   }
   if (c->onehot) return RGCN_OK;      // no AffineTransform under the layers: layer 1 reads entity ids (basis_onehot.hip)
+  // H0 = relu(W_emb + b_emb): a pass of its own (k_input_fwd), or -- where layer 1's self-loop product runs on a kernel with
+  // the A-operand prologue and nothing reads H0 before the row kernel behind that product -- formed by that product on load
+  // and written back by it (fwd_layer_partial).  The wait above precedes either: both overwrite H0.
+  c->h0_in_gemm = h0_by_self_loop_gemm(c);
+  if (c->h0_in_gemm) return RGCN_OK;
   return input_forward(c);
 }
 
@@ -55,6 +65,18 @@ static rgcn_status gather_rows(rgcn_ctx* c, float* buf) {
 // (block_rows.hip): block kind, any world.  Otherwise (rgcn_set_fusion 0, or more blocks than the kernel's lane groups
 // cover) the two-kernel form: relation-major message kernel + k_combine.
 static bool rows_layer(const rgcn_ctx* c) { return c->fuse == 1 && block_rows_available(c); }
+
+// Layer 1's self-loop product takes W_emb as its A operand and forms H0 itself (GemmBatch::a_bias / a_out): the single-pass
+// block layer on one GPU with the split arithmetic, where the GEMM is the first reader of H0 and the row kernel behind it
+// the second.  Everywhere else -- the basis kind (the aggregation reads H0 beside the GEMM), the two-kernel block form (so
+// does the message kernel), a sharded run, the fp32-MFMA mode, a shape the pre-split-weight kernels do not take -- H0 stays
+// k_input_fwd's.  Devtools knob RGCN_H0_IN_GEMM = 0: the separate pass everywhere (the A/B, the bitwise tests).
+constexpr int kH0InGemmDefault = 1;
+static bool h0_by_self_loop_gemm(const rgcn_ctx* c) {
+  if (knob("RGCN_H0_IN_GEMM", kH0InGemmDefault) == 0) return false;
+  if (c->onehot || c->world != 1 || c->kind != RGCN_KIND_BLOCK || !rows_layer(c) || c->L < 1) return false;
+  return gemm_a_prologue_ok(c, c->d, c->d, c->w_emb, c->d, c->layers[1].wself, c->d, c->layers[1].wself_nn);
+}
 
 // Fragment tables of the weights that are the B operand of a contraction (W_self of every layer in both orientations, the
 // basis tensors), rebuilt -- all of them, one launch -- when the weights changed (set_param, Adam) and once inside every
@@ -109,13 +131,25 @@ rgcn_status fwd_layer_partial(rgcn_ctx* c, int l) {
   // featureless first layer (world == 1): one destination-major kernel, messages looked up in the [V,B,d] tables, the
   // combine -- W_self row, dropout, relu -- as its epilogue; no GEMM
   if (c->onehot && l == 1) return onehot_forward(c, c->H[1]);
-  const float* Hin = c->H[l - 1];
+  const float* Hin = c->H[l - 1];      // (the self-loop product's A operand; W_emb where that product forms H0 itself)
   const int d = c->d, V = c->V;
   const int lo = c->world > 1 ? c->row_lo : 0, hi = c->world > 1 ? c->row_hi : V;
   float* dst = c->world > 1 ? c->exch : c->H[l];
   const double Mmsg = 2.0 * c->g.E / c->world;
   GemmBatch sb;
   RGCN_TRY(self_loop_batch(c, l, false, &sb));
+  if (l == 1 && c->h0_in_gemm) {
+    // fwd_begin left H0 to this layer's self-loop product.  If the product can still form it (nothing switched the layer's
+    // form or the arithmetic since), it reads W_emb and writes H0 = relu(W_emb + b_emb) on the way; otherwise the pass runs now.
+    c->h0_in_gemm = false;
+    if (h0_by_self_loop_gemm(c)) {
+      Hin = c->w_emb;
+      sb.a_bias = c->b_emb;
+      sb.a_out = c->H[0];
+    } else {
+      RGCN_TRY(input_forward(c));
+    }
+  }
   if (c->kind == RGCN_KIND_BLOCK && rows_layer(c)) {
     // S = H . W_self, then ONE kernel: H' = relu(dropout(S) + sum over the row's messages of n W_r H[src]) straight from
     // the incidence CSR (no message buffer)
@@ -132,7 +166,7 @@ rgcn_status fwd_layer_partial(rgcn_ctx* c, int l) {
     a.row_lo = lo; a.row_hi = hi;
     a.drop = make_drop(c, l, true);
     a.drop2 = make_drop(c, l, false);
-    RGCN_TRY(block_rows(c, "block_rows_fwd", l, false, Hin, a));
+    RGCN_TRY(block_rows(c, "block_rows_fwd", l, false, c->H[l - 1], a));
   } else if (c->kind == RGCN_KIND_BLOCK) {
     // Two-kernel form.  The relational messages (HBM-bound) run beside the self-loop GEMM.  A stream that blocks on
     // another stream's event resumes ~10 us after the event fires, so the chain that continues (the combine) stays on

@@ -3,7 +3,9 @@
 
     python tools/step_gap_table.py <kernel_trace.csv> [steps-to-average]
 
-A step is cut at the starts of two consecutive k_input_fwd launches; the main stream is k_input_fwd's queue.  For the
+A step is cut at the starts of two consecutive launches of its first kernel: k_input_fwd where the step has one, else the
+self-loop GEMM that forms H0 on load (the prologue instantiation, k_gemm_w8<.., true>); the main stream is that kernel's
+queue.  For the
 last complete steps (default 8) prints: the timeline of the last one, and a table -- mean over the steps -- of the gap
 in front of every main-stream kernel (end of the previous main-stream kernel to its start), the sum of those gaps, and
 the time no kernel runs on any queue."""
@@ -21,6 +23,8 @@ def short(n):
 ks = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r.get("Queue_Id", r.get("Stream_Id", "?")),
              short(r["Kernel_Name"])) for r in rows)
 starts = [i for i, k in enumerate(ks) if k[3].startswith("k_input_fwd")]
+if not starts:
+    starts = [i for i, k in enumerate(ks) if k[3].startswith("k_gemm") and k[3].rstrip().endswith("true>")]
 if len(starts) < nsteps + 2:
     sys.exit("too few steps in the trace")
 mainq = ks[starts[-1]][2]

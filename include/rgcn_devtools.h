@@ -41,8 +41,8 @@ rgcn_status rgcn_debug_gemm_presplit(rgcn_ctx* ctx, int32_t trans_b, int32_t M, 
  * a_bias / a_out; csrc/gemm_bf16x3_w8.hip, csrc/gemm_bf16x3.hip APRO; modes 6 / 9), or -- prologue == 0 -- the plain product
  * A . B on the same kernel.  A is [M,K] with leading dimension lda >= K, B is [K,N], bias is [K].  a_out_host ([M,lda], in
  * and out) is copied to the device before the launch and back after it: what the kernel leaves untouched keeps the caller's
- * values.  wide != 0: the 128 x 256 / eight-wavefront kernel, else the 128 x 128 one (the RGCN_GEMM_W8 knob is overridden
- * for the call).  row_limit >= 0: the row extent is read on the device (GemmBatch::limit, the round-robin XCD swizzle) and
+ * values.  wide != 0: the 128 x 256 / eight-wavefront kernel, else the 128 x 128 one (whatever RGCN_GEMM_W8 says:
+ * the choice goes straight into the call's plan).  row_limit >= 0: the row extent is read on the device (GemmBatch::limit, the round-robin XCD swizzle) and
  * rows >= row_limit do not exist; < 0: no limit (the contiguous XCD swizzle). */
 rgcn_status rgcn_debug_gemm_prologue(rgcn_ctx* ctx, int32_t wide, int32_t prologue, int32_t M, int32_t N, int32_t K,
                                      int32_t lda, int32_t row_limit, const float* a_host, const float* bias_host,

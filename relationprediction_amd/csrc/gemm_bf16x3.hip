@@ -493,29 +493,28 @@ constexpr size_t lds_bytes(bool a_kc, bool b_kc, bool b_pre = false) {
 }
 
 template <bool A_KC, bool B_KC, bool VEC, int TERMS, bool B_PRE = false, bool APRO = false>
-hipError_t launch_one(rgcn_ctx* c, const XArgs& g) {
+hipError_t launch_one(rgcn_ctx* c, const GemmPlan& p, const XArgs& g) {
   static_assert(!APRO || lds_bytes(A_KC, B_KC, B_PRE) == PRO_OFF * 4, "the bias copy starts where the tile buffers end");
   constexpr size_t bytes = lds_bytes(A_KC, B_KC, B_PRE) + (APRO ? PRO_BYTES : 0);
   auto kern = k_gemm_bf16x3<A_KC, B_KC, VEC, TERMS, B_PRE, APRO>;
   static uint64_t configured = 0;
   const hipError_t e = set_dynamic_lds(reinterpret_cast<const void*>(kern), (int)bytes, c->cfg.device, configured);
   if (e != hipSuccess) return e;
-  const int gx = g.swizzle == 2 ? ((g.tiles_m + 7) / 8) * 8 * g.tiles_n : g.tiles_m * g.tiles_n * g.splits;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)g.batch.groups), dim3(NTH), bytes, c->stream, g);
+  hipLaunchKernelGGL(kern, dim3((unsigned)p.grid_x, (unsigned)g.batch.groups), dim3(NTH), bytes, c->stream, g);
   return hipGetLastError();
 }
 
 template <bool VEC, int TERMS>
-hipError_t launch_form(rgcn_ctx* c, bool a_kc, bool b_kc, const XArgs& g) {
-  if constexpr (VEC) {      // pre-split B: k-contiguous A with 16-byte rows, no split over K (the caller checks)
+hipError_t launch_plan(rgcn_ctx* c, const GemmPlan& p, const XArgs& g) {
+  if constexpr (VEC) {      // pre-split B: k-contiguous A with 16-byte rows, no split over K (GemmPlan::table)
     if constexpr (TERMS != 3) {
-      if (g.bfrag != nullptr && a_kc && g.batch.a_bias != nullptr) return launch_one<true, true, true, TERMS, true, true>(c, g);
+      if (p.kernel == GEMM_PRESPLIT && p.prologue) return launch_one<true, true, true, TERMS, true, true>(c, p, g);
     }
-    if (g.bfrag != nullptr && a_kc) return launch_one<true, true, true, TERMS, true>(c, g);
+    if (p.kernel == GEMM_PRESPLIT) return launch_one<true, true, true, TERMS, true>(c, p, g);
   }
-  if (a_kc && !b_kc) return launch_one<true, false, VEC, TERMS>(c, g);
-  if (a_kc && b_kc) return launch_one<true, true, VEC, TERMS>(c, g);
-  return launch_one<false, false, VEC, TERMS>(c, g);
+  if (p.a_kc && !p.b_kc) return launch_one<true, false, VEC, TERMS>(c, p, g);
+  if (p.a_kc && p.b_kc) return launch_one<true, true, VEC, TERMS>(c, p, g);
+  return launch_one<false, false, VEC, TERMS>(c, p, g);
 }
 
 // B (k, n) of a contraction -- stored [n][k] (b_kc) or [k][n] -- split ONCE into the three bf16 planes, laid out so that
@@ -561,14 +560,6 @@ __global__ void __launch_bounds__(256) k_presplit_b(PresplitJobs jobs) {
 
 }  // namespace
 
-bool gemm_a_prologue_ok(const rgcn_ctx* c, int N, int K, const float* A, int lda, const float* B, int ldb, const void* bfrag) {
-  auto vec = [](const float* p, int ld, int extent) {      // gemm_f32's condition for 16-byte loads
-    return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && ld % 4 == 0 && extent % 4 == 0 && extent >= 4;
-  };
-  (void)B; (void)ldb; (void)N;      // (B comes from its fragment table: any width, any alignment)
-  return (c->gemm_mode == 6 || c->gemm_mode == 9) && bfrag != nullptr && vec(A, lda, K) && (K + BK - 1) / BK <= PRO_MAX_KT;
-}
-
 size_t gemm_bfrag_words(int K, int N) {      // 16-byte words of one operand's fragment table
   return (size_t)((K + BK - 1) / BK) * bfrag_nt32(N) * 192;
 }
@@ -594,40 +585,11 @@ rgcn_status gemm_presplit_b(rgcn_ctx* c, const PresplitJob* jobs, int n) {
   return RGCN_OK;
 }
 
-// Called by gemm_f32() when the context's gemm mode asks for the split evaluation; same contract.
-hipError_t gemm_bf16x3_launch(rgcn_ctx* c, int terms, bool a_kc, bool b_kc, bool vec, int M, int N, int K,
-                              const float* A, int lda, const float* B, int ldb, float* C, int ldc,
-                              int k_per_split, int splits, int swizzle, int vecC, const GemmBatch* batch) {
-  XArgs g;
-  if (batch) g.batch = *batch;
-  g.bfrag = (batch && batch->bfrag && splits == 1 && a_kc && vec) ? reinterpret_cast<const u32x4*>(batch->bfrag) : nullptr;
-  g.A = A; g.B = B; g.C = C; g.zeros = c->zeros;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.k_per_split = k_per_split; g.splits = splits; g.swizzle = swizzle; g.vecC = vecC;
-  g.tiles_m = (M + BM - 1) / BM;
-  g.tiles_n = (N + BN - 1) / BN;
-  g.nt32 = bfrag_nt32(N);
-  // the A-operand prologue exists in the two pre-split-weight NN kernels only: anything else is the caller's error
-  if (g.batch.a_bias != nullptr &&
-      !(g.bfrag != nullptr && !b_kc && g.batch.limit_on_k == 0 && (terms == 6 || terms == 9) && (K + BK - 1) / BK <= PRO_MAX_KT))
-    return hipErrorInvalidValue;
-  // a weight on the B side: the eight-wavefront kernel (gemm_bf16x3_w8.hip), bitwise the same product
-  // (devtools knob RGCN_GEMM_W8: 0 never, 1 where the call site asks for it, 2 / 3 everywhere).  The kernel reads
-  // batch.limit as a row limit only.
-  const int w8 = knob("RGCN_GEMM_W8", 1);
-  bool wide = g.batch.wide != 0;
-  if (wide && g.batch.limit == nullptr) {
-    // one workgroup per CU and nothing to hide a tile's fill and its stores behind: the wide kernel wins when the launch is ONE
-    // round of tiles that fills most of the chip (FB15k-237: 228 tiles, 45.8 against 48.8 us), and loses to the two-per-CU
-    // kernel over several rounds (WN18, 640 tiles: 125 against 114 us) -- profiles/r06_gemm_w8.md
-    const long t = (long)((M + 127) / 128) * ((N + 255) / 256) * g.batch.groups;
-    wide = t <= 256 && t >= 160;
-  }
-  if (g.bfrag != nullptr && !g.batch.limit_on_k && (terms == 6 || terms == 9) && (w8 >= 2 || (w8 == 1 && wide)))
-    return gemm_bf16x3_w8_launch(c, terms, M, N, K, A, lda, C, ldc, swizzle, vecC, g.batch);
-  if (terms == 9) return vec ? launch_form<true, 9>(c, a_kc, b_kc, g) : launch_form<false, 9>(c, a_kc, b_kc, g);
-  if (terms == 3) return vec ? launch_form<true, 3>(c, a_kc, b_kc, g) : launch_form<false, 3>(c, a_kc, b_kc, g);
-  return vec ? launch_form<true, 6>(c, a_kc, b_kc, g) : launch_form<false, 6>(c, a_kc, b_kc, g);
+hipError_t gemm_bf16x3_launch(rgcn_ctx* c, const GemmPlan& p, const XArgs& g) {
+  static_assert(BM == kGemmBM && BN == kGemmBN && BK == kGemmBK && PRO_MAX_KT == kGemmPrologueMaxKT, "the plan's tile is this kernel's");
+  if (p.terms == 9) return p.vec ? launch_plan<true, 9>(c, p, g) : launch_plan<false, 9>(c, p, g);
+  if (p.terms == 3) return p.vec ? launch_plan<true, 3>(c, p, g) : launch_plan<false, 3>(c, p, g);
+  return p.vec ? launch_plan<true, 6>(c, p, g) : launch_plan<false, 6>(c, p, g);
 }
 
 }  // namespace rgcn

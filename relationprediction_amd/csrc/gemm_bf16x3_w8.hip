@@ -341,38 +341,22 @@ __global__ void __launch_bounds__(WNTH, 2) __attribute__((amdgpu_num_vgpr(192)))
 }
 
 template <int TERMS, bool APRO = false>
-hipError_t launch_w8(rgcn_ctx* c, const XArgs& g) {
+hipError_t launch_w8(rgcn_ctx* c, const GemmPlan& p, const XArgs& g) {
   auto kern = k_gemm_w8<TERMS, APRO>;
   constexpr int bytes = W_LDS_BYTES + (APRO ? PRO_LDS_BYTES : 0);
   static uint64_t configured = 0;
   const hipError_t e = set_dynamic_lds(reinterpret_cast<const void*>(kern), bytes, c->cfg.device, configured);
   if (e != hipSuccess) return e;
-  const int gx = g.swizzle == 2 ? ((g.tiles_m + 7) / 8) * 8 * g.tiles_n : g.tiles_m * g.tiles_n;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)g.batch.groups), dim3(WNTH), bytes, c->stream, g);
+  hipLaunchKernelGGL(kern, dim3((unsigned)p.grid_x, (unsigned)g.batch.groups), dim3(WNTH), bytes, c->stream, g);
   return hipGetLastError();
 }
 
 }  // namespace
 
-// A k-contiguous with 16-byte rows, B pre-split (batch->bfrag), no split over K, batch.limit on the rows: the caller
-// (gemm_bf16x3_launch) checks.
-hipError_t gemm_bf16x3_w8_launch(rgcn_ctx* c, int terms, int M, int N, int K, const float* A, int lda, float* C, int ldc,
-                                 int swizzle, int vecC, const GemmBatch& batch) {
-  XArgs g;
-  g.batch = batch;
-  g.bfrag = reinterpret_cast<const u32x4*>(batch.bfrag);
-  g.A = A; g.B = nullptr; g.C = C; g.zeros = c->zeros;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = 0; g.ldc = ldc;
-  g.k_per_split = K; g.splits = 1; g.swizzle = swizzle; g.vecC = vecC;
-  g.tiles_m = (M + WBM - 1) / WBM;
-  g.tiles_n = (N + WBN - 1) / WBN;
-  g.nt32 = bfrag_nt32(N);
-  if (batch.a_bias != nullptr) {      // the caller (gemm_bf16x3_launch) checked K against the bias copy's room
-    if (terms == 9) return launch_w8<9, true>(c, g);
-    return launch_w8<6, true>(c, g);
-  }
-  if (terms == 9) return launch_w8<9>(c, g);
-  return launch_w8<6>(c, g);
+hipError_t gemm_bf16x3_w8_launch(rgcn_ctx* c, const GemmPlan& p, const XArgs& g) {
+  static_assert(WBM == kGemmBM && WBN == kGemmWideBN && PRO_MAX_KT == kGemmPrologueMaxKT, "the plan's tile is this kernel's");
+  if (p.prologue) return p.terms == 9 ? launch_w8<9, true>(c, p, g) : launch_w8<6, true>(c, p, g);
+  return p.terms == 9 ? launch_w8<9>(c, p, g) : launch_w8<6>(c, p, g);
 }
 
 }  // namespace rgcn

@@ -23,7 +23,7 @@
 // of one K slab) run on the same XCD and hit its L2 instead of re-fetching the panel over the fabric.
 #include <cstdlib>
 
-#include "rgcn_internal.h"
+#include "gemm_split.h"
 
 namespace rgcn {
 
@@ -323,27 +323,15 @@ __global__ void k_splitk_reduce(const float* __restrict__ slab, float* __restric
   }
 }
 
-// 16-byte loads legal and float4 validity all-or-nothing: aligned base, ld % 4 == 0, and the
-// contiguous extent (K for a k-contiguous operand, the row count for a row-contiguous one) % 4 == 0.
-bool vec_ok(const float* p, int ld, int contiguous_extent) {
-  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && (ld % 4) == 0 && (contiguous_extent % 4) == 0 &&
-         contiguous_extent >= 4;
-}
-
-template <class CF, bool VEC>
-void launch_v(rgcn_ctx* c, bool a_kc, bool b_kc, GemmArgs& g) {
-  g.tiles_m = (g.M + CF::BM - 1) / CF::BM;
-  g.tiles_n = (g.N + CF::BN - 1) / CF::BN;
-  const int gx = g.swizzle == 2 ? ((g.tiles_m + 7) / 8) * 8 * g.tiles_n : g.tiles_m * g.tiles_n * g.splits;
-  dim3 grid((unsigned)gx, (unsigned)g.batch.groups), block(CF::NT);
+template <bool VEC>
+void launch(rgcn_ctx* c, const GemmPlan& p, const GemmArgs& g) {
+  using CF = Cfg<128, 128, 16, 4, 2>;
+  static_assert(CF::BM == kGemmBM && CF::BN == kGemmBN && CF::BK == kGemmBK, "the plan's tile is this kernel's");
   static_assert((64 * CF::BN / 4) % CF::NT == 0 && CF::TM * 32 <= 64, "epilogue staging geometry");
-  if (a_kc && !b_kc) hipLaunchKernelGGL((k_gemm_f32<true, false, VEC, CF>), grid, block, 0, c->stream, g);
-  else if (a_kc && b_kc) hipLaunchKernelGGL((k_gemm_f32<true, true, VEC, CF>), grid, block, 0, c->stream, g);
+  dim3 grid((unsigned)p.grid_x, (unsigned)g.batch.groups), block(CF::NT);
+  if (p.a_kc && !p.b_kc) hipLaunchKernelGGL((k_gemm_f32<true, false, VEC, CF>), grid, block, 0, c->stream, g);
+  else if (p.a_kc && p.b_kc) hipLaunchKernelGGL((k_gemm_f32<true, true, VEC, CF>), grid, block, 0, c->stream, g);
   else hipLaunchKernelGGL((k_gemm_f32<false, false, VEC, CF>), grid, block, 0, c->stream, g);
-}
-template <class CF>
-void launch(rgcn_ctx* c, bool a_kc, bool b_kc, GemmArgs& g, bool vec) {
-  if (vec) launch_v<CF, true>(c, a_kc, b_kc, g); else launch_v<CF, false>(c, a_kc, b_kc, g);
 }
 
 }  // namespace
@@ -351,63 +339,58 @@ void launch(rgcn_ctx* c, bool a_kc, bool b_kc, GemmArgs& g, bool vec) {
 rgcn_status gemm_f32(rgcn_ctx* c, const char* tag, bool a_kc, bool b_kc, int M, int N, int K,
                      const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                      int split_k, const GemmBatch* batch, double prof_scale) {
-  if (M <= 0 || N <= 0) return RGCN_OK;
-  const int groups = batch ? batch->groups : 1;
-  if (a_kc == false && b_kc == true) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "gemm TT form not instantiated");
-  if (batch && batch->a_bias != nullptr && (c->gemm_mode == 0 || !a_kc || b_kc || split_k > 1))
-    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "gemm: the A-operand prologue exists in the pre-split-weight NN kernels only");
-  const int bk = 16;
-  GemmArgs g;
-  g.A = A; g.B = B; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb;
-  // (the NN product with a pre-split weight fetches B from its fragment table and never loads B itself: B's own alignment
-  // and width do not matter there -- a weight of any width reaches the pre-split kernels, with or without the prologue)
-  const bool b_unread = batch && batch->bfrag != nullptr && a_kc && !b_kc && c->gemm_mode != 0 && split_k <= 1;
-  const bool vec = vec_ok(A, lda, a_kc ? K : M) && (b_unread || vec_ok(B, ldb, b_kc ? K : N)) &&
-                   (!batch || (batch->strideA % 4 == 0 && (b_unread || batch->strideB % 4 == 0)));
-  g.swizzle = 1;
-  g.zeros = c->zeros;
-  if (batch) g.batch = *batch;
-  if (batch && batch->limit != nullptr && !batch->limit_on_k && split_k <= 1) g.swizzle = 2;
-  if (split_k < 1) split_k = 1;
-  int kps = (K + split_k - 1) / split_k;
-  kps = ((kps + bk - 1) / bk) * bk;
-  if (kps < bk) kps = bk;
-  split_k = K > 0 ? (K + kps - 1) / kps : 1;
-  g.k_per_split = kps;
-  g.splits = split_k;
-  const bool slabs = split_k > 1;
-  if (slabs) {
-    if ((size_t)groups * split_k * M * N > c->slab_floats) RGCN_FAIL(c, RGCN_ERR_STATE, "internal: split-K slab too small");
-    g.C = c->slab; g.ldc = N;
-    g.batch.strideC = (size_t)split_k * M * N;
-  } else {
-    g.C = C; g.ldc = ldc;
-  }
-  g.vecC = ((reinterpret_cast<uintptr_t>(g.C) & 15u) == 0 && g.ldc % 4 == 0 && N % 4 == 0) ? 1 : 0;
+  return gemm_f32(c, tag, GemmCall{a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, split_k, c->slab, batch ? *batch : GemmBatch()},
+                  prof_scale);
+}
+rgcn_status gemm_f32(rgcn_ctx* c, const char* tag, const GemmCall& call, double prof_scale) {
+  // (devtools knob RGCN_GEMM_W8: which pre-split-weight kernel -- gemm_plan.h; read here and nowhere else)
+  return gemm_run(c, tag, call, gemm_plan(call, c->gemm_mode, knob("RGCN_GEMM_W8", 1)), prof_scale);
+}
+
+rgcn_status gemm_run(rgcn_ctx* c, const char* tag, const GemmCall& q, const GemmPlan& p, double prof_scale) {
+  if (p.refused) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, p.refused);
+  if (p.kernel == GEMM_NONE) return RGCN_OK;
+  const int M = q.M, N = q.N, K = q.K, groups = q.batch.groups;
+  if (p.slabs && (size_t)groups * p.splits * M * N > c->slab_floats) RGCN_FAIL(c, RGCN_ERR_STATE, "internal: split-K slab too small");
+  gx::XArgs g;
+  g.A = q.A; g.B = q.B; g.zeros = c->zeros;
+  g.M = M; g.N = N; g.K = K; g.lda = q.lda; g.ldb = q.ldb;
+  g.C = p.slabs ? q.slab : q.C;
+  g.ldc = p.ldc;
+  g.k_per_split = p.k_per_split; g.splits = p.splits; g.swizzle = p.swizzle; g.vecC = p.vecC;
+  g.tiles_m = p.tiles_m; g.tiles_n = p.tiles_n;
+  g.batch = q.batch;
+  if (p.slabs) g.batch.strideC = (size_t)p.splits * M * N;
+  g.bfrag = p.table ? reinterpret_cast<const gx::u32x4*>(q.batch.bfrag) : nullptr;
+  g.nt32 = gx::bfrag_nt32(N);
   {
     // (prof_scale: the share of the launch's M x K extent that exists on the device side -- compacted groups)
     // (the prologue's write-back of the transformed A operand: M x K floats more, design and compulsory alike)
-    const double a_out_elems = batch && batch->a_bias && batch->a_out ? (double)M * K : 0.0;
+    const double a_out_elems = q.batch.a_bias && q.batch.a_out ? (double)M * K : 0.0;
     ProfScope ps(c, tag, prof_scale * groups * 4.0 * ((double)M * K + (double)K * N + (double)M * N + a_out_elems),
                  prof_scale * groups * 2.0 * M * N * K);
-    if (c->gemm_mode != 0) {
-      RGCN_HIP(c, gemm_bf16x3_launch(c, c->gemm_mode, a_kc, b_kc, vec, M, N, K, A, lda, B, ldb, g.C, g.ldc,
-                                     g.k_per_split, g.splits, g.swizzle, g.vecC, &g.batch));
-    } else {
-      launch<Cfg<128, 128, 16, 4, 2>>(c, a_kc, b_kc, g, vec);
+    switch (p.kernel) {
+      case GEMM_F32: {
+        const GemmArgs f{g.A, g.B, g.C, g.zeros, M, N, K, g.lda, g.ldb, g.ldc, g.k_per_split,
+                         g.tiles_m, g.tiles_n, g.splits, g.swizzle, g.vecC, g.batch};
+        if (p.vec) launch<true>(c, p, f); else launch<false>(c, p, f);
+        break;
+      }
+      case GEMM_W8: RGCN_HIP(c, gemm_bf16x3_w8_launch(c, p, g)); break;
+      default: RGCN_HIP(c, gemm_bf16x3_launch(c, p, g)); break;
     }
     RGCN_HIP(c, hipGetLastError());
   }
-  if (slabs) {
+  if (p.slabs) {
     const int64_t mn = (int64_t)M * N;
-    ProfScope ps(c, "splitk_reduce", 4.0 * groups * mn * (split_k + 1), 0);
-    const size_t gsc = batch ? batch->strideC : 0;
-    if (N % 4 == 0 && ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(C) & 15u) == 0 && gsc % 4 == 0)
+    ProfScope ps(c, "splitk_reduce", 4.0 * groups * mn * (p.splits + 1), 0);
+    const size_t gsc = q.batch.strideC;
+    if (N % 4 == 0 && q.ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(q.C) & 15u) == 0 && gsc % 4 == 0)
       hipLaunchKernelGGL((k_splitk_reduce<4>), dim3((unsigned)((mn / 4 + 255) / 256), (unsigned)groups), dim3(256), 0,
-                         c->stream, c->slab, C, M, N, ldc, split_k, gsc);
+                         c->stream, q.slab, q.C, M, N, q.ldc, p.splits, gsc);
     else
       hipLaunchKernelGGL((k_splitk_reduce<1>), dim3((unsigned)((mn + 255) / 256), (unsigned)groups), dim3(256), 0,
-                         c->stream, c->slab, C, M, N, ldc, split_k, gsc);
+                         c->stream, q.slab, q.C, M, N, q.ldc, p.splits, gsc);
     RGCN_HIP(c, hipGetLastError());
   }
   return RGCN_OK;

@@ -1,6 +1,6 @@
 // Shared pieces of the split-arithmetic GEMM kernels (gemm_bf16x3.hip: 128x128 tiles, operands staged through registers;
 // gemm_bf16x3_w8.hip: 128x256 tiles, 8 wavefronts, pre-split B by LDS-DMA): vector types, the launch arguments and the
-// exact bf16 split of an fp32 pair.  Device code only.
+// exact bf16 split of an fp32 pair.
 #ifndef RGCN_GEMM_SPLIT_H_
 #define RGCN_GEMM_SPLIT_H_
 
@@ -97,5 +97,10 @@ __device__ __forceinline__ void static_for(F& f) {
 __host__ __device__ constexpr int bfrag_nt32(int N) { return 8 * ((N + 255) / 256); }
 
 }  // namespace gx
+
+// The two launchers obey the plan (gemm_plan.h; gemm_run fills XArgs): the template switch, the LDS limit, the launch.
+hipError_t gemm_bf16x3_launch(rgcn_ctx* c, const GemmPlan& p, const gx::XArgs& g);       // GEMM_STAGED, GEMM_PRESPLIT
+hipError_t gemm_bf16x3_w8_launch(rgcn_ctx* c, const GemmPlan& p, const gx::XArgs& g);    // GEMM_W8
+
 }  // namespace rgcn
 #endif  // RGCN_GEMM_SPLIT_H_

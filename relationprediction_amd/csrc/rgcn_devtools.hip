@@ -103,10 +103,6 @@ rgcn_status rgcn_debug_gemm_prologue(rgcn_ctx* c, int32_t wide, int32_t prologue
   int32_t* lim = nullptr;
   void* F = nullptr;
   rgcn_status s = RGCN_OK;
-  // the kernel under test is chosen here, not by the tile-count heuristic (RGCN_GEMM_W8: 3 = wide everywhere, 0 = never)
-  const char* prev = getenv("RGCN_GEMM_W8");
-  const std::string saved = prev ? prev : "";
-  setenv("RGCN_GEMM_W8", wide ? "3" : "0", 1);
   do {
     if ((s = dmalloc(c, &A, (size_t)M * lda, false)) != RGCN_OK) break;
     if ((s = dmalloc(c, &Aout, (size_t)M * lda, false)) != RGCN_OK) break;
@@ -122,20 +118,21 @@ rgcn_status rgcn_debug_gemm_prologue(rgcn_ctx* c, int32_t wide, int32_t prologue
     if (row_limit >= 0 && (s = to_dev(c, lim, &row_limit, sizeof(int32_t))) != RGCN_OK) break;
     const PresplitJob pj{B, F, N, K, N, 0};
     if ((s = gemm_presplit_b(c, &pj, 1)) != RGCN_OK) break;
-    GemmBatch gb;
-    gb.bfrag = F;
-    gb.wide = wide ? 1 : 0;
-    if (row_limit >= 0) gb.limit = lim;
+    GemmCall q{true, false, M, N, K, A, lda, B, N, C, N, 1, c->slab, GemmBatch()};
+    q.batch.bfrag = F;
+    q.batch.wide = wide ? 1 : 0;
+    if (row_limit >= 0) q.batch.limit = lim;
     if (prologue) {
-      if (!gemm_a_prologue_ok(c, N, K, A, lda, B, N, F)) { c->err = "no prologue kernel takes this product"; s = RGCN_ERR_UNSUPPORTED; break; }
-      gb.a_bias = bias;
-      gb.a_out = Aout;
+      q.batch.a_bias = bias;
+      q.batch.a_out = Aout;
     }
-    if ((s = gemm_f32(c, "debug_gemm", true, false, M, N, K, A, lda, B, N, C, N, 1, &gb)) != RGCN_OK) break;
+    // the kernel under test is chosen here, not by the tile-count heuristic (gemm_plan's knob: 3 = wide everywhere, 0 = never)
+    const GemmPlan plan = gemm_plan(q, c->gemm_mode, wide ? 3 : 0);
+    if (prologue && !plan.prologue) { c->err = "no prologue kernel takes this product"; s = RGCN_ERR_UNSUPPORTED; break; }
+    if ((s = gemm_run(c, "debug_gemm", q, plan)) != RGCN_OK) break;
     if ((s = to_host(c, c_host, C, sizeof(float) * (size_t)M * N)) != RGCN_OK) break;
     s = to_host(c, a_out_host, Aout, sizeof(float) * (size_t)M * lda);
   } while (0);
-  if (prev) setenv("RGCN_GEMM_W8", saved.c_str(), 1); else unsetenv("RGCN_GEMM_W8");
   if (A) (void)hipFree(A);
   if (Aout) (void)hipFree(Aout);
   if (B) (void)hipFree(B);

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/rgcn.h"
+#include "gemm_plan.h"
 
 namespace rgcn {
 
@@ -514,39 +515,8 @@ struct SortSpec {
 size_t sort_table_elems(size_t n);
 rgcn_status sort_pairs(rgcn_ctx* c, const char* tag, int njobs, const SortSpec* specs);
 
-// ---- gemm_f32.hip
-// Several contractions of one shape in ONE launch (blockIdx.y = group), each with its own operands and -- read on the
-// device, so that nothing about the graph has to come back to the host -- its own extent along M (rows of A and C that
-// exist; workgroups of tiles beyond it leave at once and write nothing) or along K (the depth of the contraction; the
-// split-K slices divide the ACTUAL depth evenly).  The row-compacted basis contraction (basis.hip) is two groups, one
-// per message direction, whose row counts the graph preparation leaves in GraphBufs::unit_ptr.
-struct GemmBatch {
-  int groups = 1;
-  size_t strideA = 0, strideB = 0, strideC = 0;   // floats between consecutive groups' operands
-  const int32_t* limit = nullptr;                 // device, limit[g * limit_stride]: extent of group g (<= M resp. K)
-  int limit_stride = 1;
-  int limit_on_k = 0;                             // 0: rows of A / C; 1: depth K
-  // optional: B already split into bf16 planes in MFMA fragment order (gemm_presplit_b; a weight, split once per weight
-  // update instead of once per tile and step).  Used by the split-arithmetic kernel when A is k-contiguous and there is no
-  // split over K; ignored otherwise (B itself must still be passed).  strideBfrag: 16-byte words between groups.
-  const void* bfrag = nullptr;
-  size_t strideBfrag = 0;
-  // with bfrag: take the 128 x 256 / eight-wavefront kernel (gemm_bf16x3_w8.hip; one workgroup holds a whole CU) instead of
-  // the 128 x 128 / four-wavefront one (two per CU, room for another kernel's workgroups beside them).  Same result bit for
-  // bit; which is faster in the step depends on what runs beside the product: the forward products
-  // run alone on the main stream (wide), the backward ones beside dW_self and the relation-weight kernels (not wide).
-  int wide = 0;
-  // optional A-operand prologue with write-back (the pre-split-weight NN kernels only: gemm_a_prologue_ok): every A element
-  // enters the product as fmaxf(a + a_bias[k], 0.f), and -- a_out != nullptr -- the transformed operand is also written to
-  // a_out, which has A's leading dimension and group stride.  Layer 1's self-loop product forms H0 = relu(W_emb + b_emb)
-  // this way, in k_input_fwd's arithmetic, from the operand it has in registers anyway.
-  const float* a_bias = nullptr;    // [K]
-  float* a_out = nullptr;
-};
+// ---- gemm_f32.hip (GemmBatch, GemmCall, GemmPlan and the decision itself: gemm_plan.h)
 size_t gemm_bfrag_words(int K, int N);
-// whether gemm_f32 can take GemmBatch::a_bias for the NN product A[.,K] (lda) . B[K,N] (ldb) with B's fragment table given:
-// split arithmetic with six or nine products, 16-byte-loadable operands, K within the kernels' bias copy
-bool gemm_a_prologue_ok(const rgcn_ctx* c, int N, int K, const float* A, int lda, const float* B, int ldb, const void* bfrag);
 struct PresplitJob {
   const float* B;      // the operand B (k, n): stored [n][k] (b_kc) or [k][n], leading dimension ldb
   void* F;             // its fragment table, gemm_bfrag_words(K, N) 16-byte words
@@ -554,20 +524,14 @@ struct PresplitJob {
 };
 rgcn_status gemm_presplit_b(rgcn_ctx* c, const PresplitJob* jobs, int n);
 
-// C[M,N] (ldc) = A(m,k) . B(k,n).  a_kc: A stored [m][k] (k contiguous, lda) else [k][m];
-// b_kc: B stored [n][k] (k contiguous, ldb) else [k][n].  split_k > 1 writes partial slabs to
-// `slab` ([group][split_k][M][N]) and reduces them into C deterministically.
+// C = A . B as GemmCall describes it: gemm_plan(call, c->gemm_mode, the RGCN_GEMM_W8 knob) followed by gemm_run
+rgcn_status gemm_f32(rgcn_ctx* c, const char* tag, const GemmCall& call, double prof_scale = 1.0);
+// the same, the call spelled out (GemmCall's fields; the slabs are the context's)
 rgcn_status gemm_f32(rgcn_ctx* c, const char* tag, bool a_kc, bool b_kc, int M, int N, int K,
                      const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                      int split_k, const GemmBatch* batch = nullptr, double prof_scale = 1.0);
-
-// gemm_bf16x3.hip: the same contraction on the bf16 matrix cores (exact 3-way operand split)
-hipError_t gemm_bf16x3_launch(rgcn_ctx* c, int terms, bool a_kc, bool b_kc, bool vec, int M, int N, int K,
-                              const float* A, int lda, const float* B, int ldb, float* C, int ldc,
-                              int k_per_split, int splits, int swizzle, int vecC, const GemmBatch* batch = nullptr);
-// gemm_bf16x3_w8.hip: the form for a pre-split weight on the B side (A k-contiguous with 16-byte rows, no split over K)
-hipError_t gemm_bf16x3_w8_launch(rgcn_ctx* c, int terms, int M, int N, int K, const float* A, int lda, float* C, int ldc,
-                                 int swizzle, int vecC, const GemmBatch& batch);
+// launches what the plan says (a refused plan: RGCN_ERR_UNSUPPORTED with the plan's reason), then the split-K reduce
+rgcn_status gemm_run(rgcn_ctx* c, const char* tag, const GemmCall& call, const GemmPlan& plan, double prof_scale = 1.0);
 
 // ---- block_msgs.hip
 rgcn_status block_geometry(rgcn_ctx* c);

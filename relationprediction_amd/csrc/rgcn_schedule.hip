@@ -3,7 +3,7 @@
 //   backward (tf.gradients(loss, weights), code/optimization/abstract.py:117-118; formulas SURVEY 8a a15)
 // The forward pass of a block step is one chain on the main stream: [self-loop GEMM -> row kernel] x L.  H0 = relu(W_emb +
 // b_emb) is formed by layer 1's self-loop GEMM on load and written back by it where that GEMM has the A-operand prologue
-// (h0_by_self_loop_gemm below); everywhere else k_input_fwd opens the chain.
+// (h0_by_self_loop_gemm below: the GEMM's plan says so); everywhere else k_input_fwd opens the chain.
 // One schedule per situation: minibatch scale on one GPU with side streams, the chain a captured
 // step records, full-graph scale / a relation-sharded run (the exchange points of DESIGN.md section 7).  The C ABI that
 // drives these functions is rgcn_api.hip.
@@ -66,18 +66,6 @@ static rgcn_status gather_rows(rgcn_ctx* c, float* buf) {
 // cover) the two-kernel form: relation-major message kernel + k_combine.
 static bool rows_layer(const rgcn_ctx* c) { return c->fuse == 1 && block_rows_available(c); }
 
-// Layer 1's self-loop product takes W_emb as its A operand and forms H0 itself (GemmBatch::a_bias / a_out): the single-pass
-// block layer on one GPU with the split arithmetic, where the GEMM is the first reader of H0 and the row kernel behind it
-// the second.  Everywhere else -- the basis kind (the aggregation reads H0 beside the GEMM), the two-kernel block form (so
-// does the message kernel), a sharded run, the fp32-MFMA mode, a shape the pre-split-weight kernels do not take -- H0 stays
-// k_input_fwd's.  Devtools knob RGCN_H0_IN_GEMM = 0: the separate pass everywhere (the A/B, the bitwise tests).
-constexpr int kH0InGemmDefault = 1;
-static bool h0_by_self_loop_gemm(const rgcn_ctx* c) {
-  if (knob("RGCN_H0_IN_GEMM", kH0InGemmDefault) == 0) return false;
-  if (c->onehot || c->world != 1 || c->kind != RGCN_KIND_BLOCK || !rows_layer(c) || c->L < 1) return false;
-  return gemm_a_prologue_ok(c, c->d, c->d, c->w_emb, c->d, c->layers[1].wself, c->d, c->layers[1].wself_nn);
-}
-
 // Fragment tables of the weights that are the B operand of a contraction (W_self of every layer in both orientations, the
 // basis tensors), rebuilt -- all of them, one launch -- when the weights changed (set_param, Adam) and once inside every
 // captured step, whose replays follow weights the host does not see.  Nothing to do when the dense contractions run on
@@ -104,13 +92,36 @@ static rgcn_status refresh_weight_fragments(rgcn_ctx* c) {
   c->frag_version = c->capturing ? ~0ull : c->weights_version;
   return RGCN_OK;
 }
-// the self-loop products: one group, W_self as the pre-split B operand (forward: [k][n]; dH: used transposed, [n][k])
-static rgcn_status self_loop_batch(rgcn_ctx* c, int l, bool transposed, GemmBatch* b) {
-  *b = GemmBatch();
-  RGCN_TRY(refresh_weight_fragments(c));
-  if (c->gemm_mode != 0) b->bfrag = transposed ? c->layers[l].wself_nt : c->layers[l].wself_nn;
-  b->wide = transposed ? 0 : 1;
-  return RGCN_OK;
+// the self-loop products: one group, W_self as the pre-split B operand (forward: [k][n]; dH: used transposed, [n][k]);
+// whoever launches one refreshes the fragment tables first
+static GemmBatch self_loop_batch(const rgcn_ctx* c, int l, bool transposed) {
+  GemmBatch b;
+  if (c->gemm_mode != 0) b.bfrag = transposed ? c->layers[l].wself_nt : c->layers[l].wself_nn;
+  b.wide = transposed ? 0 : 1;
+  return b;
+}
+// S = H_{l-1} . W_self of layer l over this rank's row shard; form_h0 (layer 1): W_emb is the A operand and the product
+// forms H0 = relu(W_emb + b_emb) on load and writes it back (GemmBatch::a_bias / a_out)
+static GemmCall self_fwd_call(const rgcn_ctx* c, int l, bool form_h0) {
+  const int d = c->d, lo = c->world > 1 ? c->row_lo : 0, hi = c->world > 1 ? c->row_hi : c->V;
+  GemmCall q{true, false, hi - lo, d, d, (form_h0 ? c->w_emb : c->H[l - 1]) + (size_t)lo * d, d, c->layers[l].wself, d,
+             c->self_buf + (size_t)lo * d, d, 1, c->slab, self_loop_batch(c, l, false)};
+  if (form_h0) {
+    q.batch.a_bias = c->b_emb;
+    q.batch.a_out = c->H[0];
+  }
+  return q;
+}
+// Layer 1's self-loop product takes W_emb as its A operand and forms H0 itself (GemmBatch::a_bias / a_out): the single-pass
+// block layer on one GPU with the split arithmetic, where the GEMM is the first reader of H0 and the row kernel behind it
+// the second.  Everywhere else -- the basis kind (the aggregation reads H0 beside the GEMM), the two-kernel block form (so
+// does the message kernel), a sharded run, the fp32-MFMA mode, a shape the pre-split-weight kernels do not take -- H0 stays
+// k_input_fwd's.  Devtools knob RGCN_H0_IN_GEMM = 0: the separate pass everywhere (the A/B, the bitwise tests).
+constexpr int kH0InGemmDefault = 1;
+static bool h0_by_self_loop_gemm(const rgcn_ctx* c) {
+  if (knob("RGCN_H0_IN_GEMM", kH0InGemmDefault) == 0) return false;
+  if (c->onehot || c->world != 1 || c->kind != RGCN_KIND_BLOCK || !rows_layer(c) || c->L < 1) return false;
+  return gemm_plan(self_fwd_call(c, 1, true), c->gemm_mode, 1).prologue;      // (both pre-split kernels have it: any knob)
 }
 
 // Basis kind: the two direction groups of a batched GEMM over the (row, direction) units of the current graph; the
@@ -131,33 +142,28 @@ rgcn_status fwd_layer_partial(rgcn_ctx* c, int l) {
   // featureless first layer (world == 1): one destination-major kernel, messages looked up in the [V,B,d] tables, the
   // combine -- W_self row, dropout, relu -- as its epilogue; no GEMM
   if (c->onehot && l == 1) return onehot_forward(c, c->H[1]);
-  const float* Hin = c->H[l - 1];      // (the self-loop product's A operand; W_emb where that product forms H0 itself)
+  const float* Hin = c->H[l - 1];
   const int d = c->d, V = c->V;
   const int lo = c->world > 1 ? c->row_lo : 0, hi = c->world > 1 ? c->row_hi : V;
   float* dst = c->world > 1 ? c->exch : c->H[l];
   const double Mmsg = 2.0 * c->g.E / c->world;
-  GemmBatch sb;
-  RGCN_TRY(self_loop_batch(c, l, false, &sb));
+  RGCN_TRY(refresh_weight_fragments(c));
+  bool form_h0 = false;
   if (l == 1 && c->h0_in_gemm) {
     // fwd_begin left H0 to this layer's self-loop product.  If the product can still form it (nothing switched the layer's
     // form or the arithmetic since), it reads W_emb and writes H0 = relu(W_emb + b_emb) on the way; otherwise the pass runs now.
     c->h0_in_gemm = false;
-    if (h0_by_self_loop_gemm(c)) {
-      Hin = c->w_emb;
-      sb.a_bias = c->b_emb;
-      sb.a_out = c->H[0];
-    } else {
-      RGCN_TRY(input_forward(c));
-    }
+    form_h0 = h0_by_self_loop_gemm(c);
+    if (!form_h0) RGCN_TRY(input_forward(c));
   }
+  const GemmCall self = self_fwd_call(c, l, form_h0);      // S = H . W_self  (rows of this rank's shard)
   if (c->kind == RGCN_KIND_BLOCK && rows_layer(c)) {
     // S = H . W_self, then ONE kernel: H' = relu(dropout(S) + sum over the row's messages of n W_r H[src]) straight from
     // the incidence CSR (no message buffer)
     // (sharded run: the self-loop GEMM covers this rank's row shard, the kernel walks the rank's own messages and writes
     // the PARTIAL pre-activations -- the self-loop term inside the shard only, no relu -- for the reduce-scatter that
     // follows)
-    RGCN_TRY(gemm_f32(c, "gemm_self_fwd", true, false, hi - lo, d, d, Hin + (size_t)lo * d, d, c->layers[l].wself, d,
-                      c->self_buf + (size_t)lo * d, d, 1, &sb));
+    RGCN_TRY(gemm_f32(c, "gemm_self_fwd", self));
     RGCN_TRY(wait_gather(c));
     CombineArgs a;
     a.add = nullptr; a.msg = nullptr; a.row_ptr = nullptr; a.long_rows = nullptr; a.nlong = nullptr;
@@ -171,10 +177,9 @@ rgcn_status fwd_layer_partial(rgcn_ctx* c, int l) {
     // Two-kernel form.  The relational messages (HBM-bound) run beside the self-loop GEMM.  A stream that blocks on
     // another stream's event resumes ~10 us after the event fires, so the chain that continues (the combine) stays on
     // the stream of the kernel that finishes LAST: the messages on the main stream, the (shorter) GEMM forked.
-    {   // self-loop: S = H . W_self  (rows of this rank's shard)
+    {
       StreamScope side(c, 0);
-      RGCN_TRY(gemm_f32(c, "gemm_self_fwd", true, false, hi - lo, d, d, Hin + (size_t)lo * d, d,
-                        c->layers[l].wself, d, c->self_buf + (size_t)lo * d, d, 1, &sb));
+      RGCN_TRY(gemm_f32(c, "gemm_self_fwd", self));
     }
     RGCN_TRY(wait_gather(c));
     RGCN_TRY(block_msg_forward(c, l, Hin, c->msgbuf));
@@ -196,8 +201,7 @@ rgcn_status fwd_layer_partial(rgcn_ctx* c, int l) {
     // then beside the basis GEMM
     {
       StreamScope side(c, 1);
-      RGCN_TRY(gemm_f32(c, "gemm_self_fwd", true, false, hi - lo, d, d, Hin + (size_t)lo * d, d,
-                        c->layers[l].wself, d, c->self_buf + (size_t)lo * d, d, 1, &sb));
+      RGCN_TRY(gemm_f32(c, "gemm_self_fwd", self));
     }
     RGCN_TRY(wait_gather(c));
     RGCN_TRY(basis_aggregate_forward(c, l, Hin, c->zsave[l]));
@@ -315,8 +319,8 @@ rgcn_status bwd_layer_partial(rgcn_ctx* c, int l) {
     return gemm_f32(c, "gemm_self_dw", false, false, d, d, rows, Hin + (size_t)lo * d, d, c->bwd_dS + (size_t)lo * d, d,
                     lb.gwself, d, auto_split_k(d, d, rows, narrow_dw));
   };
-  GemmBatch sbt;
-  RGCN_TRY(self_loop_batch(c, l, true, &sbt));
+  RGCN_TRY(refresh_weight_fragments(c));
+  const GemmBatch sbt = self_loop_batch(c, l, true);
   auto self_dh = [&]() {      // G = dS . W_self^T
     return gemm_f32(c, "gemm_self_dh", true, true, rows, d, d, c->bwd_dS + (size_t)lo * d, d, lb.wself, d,
                     c->self_buf + (size_t)lo * d, d, 1, &sbt);

@@ -123,7 +123,7 @@ def test_gemm_with_presplit_weights_is_bitwise_the_staged_kernel(native, M, N, K
     A = rng.randn(M, K).astype(np.float32)
     B = (rng.randn(K, N) * np.exp(rng.uniform(-6, 6, (K, N)))).astype(np.float32)
     Bop = np.ascontiguousarray(B.T) if trans_b else B
-    # two kernels take a pre-split weight (csrc/gemm_bf16x3.hip picks by call site and tile count): the 128 x 128 /
+    # two kernels take a pre-split weight (csrc/gemm_plan.h picks by call site and tile count): the 128 x 128 /
     # four-wavefront one whose fragments go straight to registers (B_PRE), and the 128 x 256 / eight-wavefront one that
     # brings them in by LDS-DMA (gemm_bf16x3_w8.hip, round 6).  The devtools knob forces each in turn.
     prev = os.environ.get("RGCN_GEMM_W8")

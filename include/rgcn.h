@@ -50,7 +50,7 @@ enum {
   RGCN_ERR_RCCL = 3,        /* an RCCL call failed / librccl not loadable */
   RGCN_ERR_STATE = 4,       /* call order violated (e.g. backward before forward) */
   RGCN_ERR_UNSUPPORTED = 5, /* configuration outside what the kernels implement */
-  RGCN_ERR_NOMEM = 6
+  RGCN_ERR_NOMEM = 6        /* the device is out of memory: any allocation the library makes, at create or later */
 };
 
 /* Encoder.Concatenation=Yes -> ConcatGcn (block-diagonal), else BasisGcn:

@@ -56,6 +56,12 @@ rgcn_status rgcn_debug_gemm_prologue(rgcn_ctx* ctx, int32_t wide, int32_t prolog
  * test_workgroups_of_a_band_share_an_xcd re-checks it on the box the suite runs on. */
 rgcn_status rgcn_debug_xcd_map(rgcn_ctx* ctx, int32_t n_blocks, int32_t* out_host);
 
+/* ---- device-memory ownership ---- */
+/* The device allocations the context owns right now, summed over all its owners (the context itself, both graph sets, the
+ * decoder batch, the sampler, the optimizer, the ranking scratch): live blocks and their bytes as allocated.  Caller-owned
+ * memory (rgcn_device_alloc) and the pinned host buffers are not counted.  tests/test_gpu_memory_ownership.py. */
+rgcn_status rgcn_debug_device_memory(rgcn_ctx* ctx, int64_t* blocks, int64_t* bytes);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -142,6 +142,7 @@ _SIGS = {
 _DEVTOOLS_SIGS = {
     "rgcn_debug_gemm": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "rgcn_debug_xcd_map": (C.c_int32, [_P, C.c_int32, _P]),
+    "rgcn_debug_device_memory": (C.c_int32, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "rgcn_debug_gemm_presplit": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
                                              C.POINTER(C.c_float)]),
     "rgcn_debug_gemm_time": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -794,6 +795,12 @@ class Engine:
         out = np.zeros(int(n_blocks), dtype=np.int32)
         self._check(self.lib.rgcn_debug_xcd_map(self.ctx, int(n_blocks), _ptr(out)))
         return out
+
+    def device_memory(self):
+        """(blocks, bytes) of the device allocations the context owns right now, over all its owners (devtools build)"""
+        blocks, nbytes = C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.rgcn_debug_device_memory(self.ctx, C.byref(blocks), C.byref(nbytes)))
+        return int(blocks.value), int(nbytes.value)
 
     def debug_gemm_time(self, a, b, trans_a=False, trans_b=False, split_k=0, iters=20):
         a = np.ascontiguousarray(a, dtype=np.float32)

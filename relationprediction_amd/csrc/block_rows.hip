@@ -617,10 +617,7 @@ static rgcn_status block_rows_refresh_weights(rgcn_ctx* c, int layer) {
   const int gw = rows_group_width(c), nt = nt_of(c->sd);
   const int64_t n4 = (int64_t)2 * c->R * 8 * nt * gw;
   LayerBufs& mine = c->layers[layer];
-  if (!mine.wtile) {
-    if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "internal: the band-tiled weight copy must exist before a capture");
-    RGCN_HIP(c, hipMalloc((void**)&mine.wtile, sizeof(float) * 4 * (size_t)n4));
-  }
+  if (!mine.wtile) RGCN_FAIL(c, RGCN_ERR_STATE, "internal: the band-tiled weight copy is allocated at create");
   if (c->capturing ? c->wtile_fresh : mine.wtile_version == c->weights_version) return RGCN_OK;
   c->wtile_fresh = true;
   for (int l0 = 1; l0 <= c->L; l0 += 8) {
@@ -656,8 +653,7 @@ rgcn_status block_rows(rgcn_ctx* c, const char* tag, int layer, bool backward, c
   a.long_rows = c->g.long_rows;
   a.nlong = c->g.nlong;
   const bool giant = c->g.giant_on;
-  if (giant && !c->giant_slab)
-    RGCN_HIP(c, hipMalloc((void**)&c->giant_slab, sizeof(float) * (size_t)c->g.piece_cap * c->d));
+  if (giant) RGCN_TRY(giant_slab_ensure(c));
   a.piece_row = giant ? c->g.piece_row : nullptr;
   a.piece_k = giant ? c->g.piece_k : nullptr;
   a.ngiant = giant ? c->g.ngiant : nullptr;

@@ -815,12 +815,6 @@ int bits_for(uint32_t max_value) {
   return b;
 }
 
-template <class T>
-rgcn_status dalloc(rgcn_ctx* c, T** p, size_t n) {
-  RGCN_HIP(c, hipMalloc((void**)p, (n ? n : 1) * sizeof(T)));
-  return RGCN_OK;
-}
-
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
@@ -844,22 +838,31 @@ rgcn_status decoder_reserve(rgcn_ctx* c, int64_t maxN) {
   if (q.maxN >= maxN && q.maxN > 0) return RGCN_OK;
   decoder_free(c);
   const size_t N = (size_t)maxN, V = c->V, R = c->R, d = c->d;
-  RGCN_TRY(dalloc(c, &q.keyv, 2 * N)); RGCN_TRY(dalloc(c, &q.keyv_s, 2 * N));
-  RGCN_TRY(dalloc(c, &q.valv, 2 * N)); RGCN_TRY(dalloc(c, &q.permv, 2 * N));
-  RGCN_TRY(dalloc(c, &q.keyr, N)); RGCN_TRY(dalloc(c, &q.keyr_s, N));
-  RGCN_TRY(dalloc(c, &q.valr, N)); RGCN_TRY(dalloc(c, &q.permr, N)); RGCN_TRY(dalloc(c, &q.perm_pos, N));
-  RGCN_TRY(dalloc(c, &q.row_ptr, V + 1)); RGCN_TRY(dalloc(c, &q.rel_ptr, R + 1)); RGCN_TRY(dalloc(c, &q.chunk_ptr, R + 1));
-  RGCN_TRY(dalloc(c, &q.e_other, 2 * N)); RGCN_TRY(dalloc(c, &q.e_rel, 2 * N)); RGCN_TRY(dalloc(c, &q.e_trip, 2 * N));
+  RGCN_TRY(dmalloc(c, q.pool, &q.keyv, 2 * N, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.keyv_s, 2 * N, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.valv, 2 * N, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.permv, 2 * N, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.keyr, N, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.keyr_s, N, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.valr, N, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.permr, N, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.perm_pos, N, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.row_ptr, V + 1, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.rel_ptr, R + 1, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.chunk_ptr, R + 1, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.e_other, 2 * N, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.e_rel, 2 * N, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.e_trip, 2 * N, false));
   q.long_cap = (int32_t)(2 * N / kDecLongRow + 1);
-  RGCN_TRY(dalloc(c, &q.long_rows, (size_t)q.long_cap));
-  RGCN_TRY(dalloc(c, &q.long_first, (size_t)q.long_cap));
-  RGCN_TRY(dalloc(c, &q.long_cnt, (size_t)q.long_cap));
+  RGCN_TRY(dmalloc(c, q.pool, &q.long_rows, (size_t)q.long_cap, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.long_first, (size_t)q.long_cap, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.long_cnt, (size_t)q.long_cap, false));
   q.piece_cap = (int32_t)(2 * N / kDecPiece + q.long_cap + 1);     // sum of ceil(len / piece) over the long rows
-  RGCN_TRY(dalloc(c, &q.piece_row, (size_t)q.piece_cap));
-  RGCN_TRY(dalloc(c, &q.piece_k, (size_t)q.piece_cap));
-  RGCN_TRY(dalloc(c, &q.piece_slab, (size_t)q.piece_cap * d));
-  RGCN_TRY(dalloc(c, &q.nlong, 2));
-  RGCN_TRY(dalloc(c, &q.dx, N));
+  RGCN_TRY(dmalloc(c, q.pool, &q.piece_row, (size_t)q.piece_cap, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.piece_k, (size_t)q.piece_cap, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.piece_slab, (size_t)q.piece_cap * d, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.nlong, 2, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.dx, N, false));
   q.nbands = (int32_t)((d + kLine - 1) / kLine);
   {
     int dev = 0, cus = 0;
@@ -867,32 +870,31 @@ rgcn_status decoder_reserve(rgcn_ctx* c, int64_t maxN) {
     RGCN_HIP(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     q.cus = cus > 0 ? cus : 256;
   }
-  RGCN_TRY(dalloc(c, &q.cb, (size_t)q.nbands * V * kLine));
-  RGCN_TRY(dalloc(c, &q.rb, (size_t)q.nbands * R * kLine));
-  RGCN_TRY(dalloc(c, &q.e_g, 2 * N));
-  RGCN_TRY(dalloc(c, &q.row_key, V)); RGCN_TRY(dalloc(c, &q.row_key_s, V)); RGCN_TRY(dalloc(c, &q.row_order, V));
-  RGCN_TRY(dalloc(c, &q.row_tab, sort_table_elems(V)));
+  RGCN_TRY(dmalloc(c, q.pool, &q.cb, (size_t)q.nbands * V * kLine, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.rb, (size_t)q.nbands * R * kLine, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.e_g, 2 * N, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.row_key, V, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.row_key_s, V, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.row_order, V, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.row_tab, sort_table_elems(V), false));
   q.energy_blocks = 2048;
   q.max_chunks = (int32_t)(N / kDecChunk + R + 1);
-  RGCN_TRY(dalloc(c, &q.loss_part, 2 * (size_t)(q.energy_blocks > q.max_chunks ? q.energy_blocks : q.max_chunks)));
-  RGCN_TRY(dalloc(c, &q.loss, 1));
-  RGCN_TRY(dalloc(c, &q.slab, (size_t)q.max_chunks * d));
-  RGCN_TRY(dalloc(c, &q.keyv_t, 2 * N)); RGCN_TRY(dalloc(c, &q.keyr_t, N));
-  RGCN_TRY(dalloc(c, &q.tablev, sort_table_elems(2 * N))); RGCN_TRY(dalloc(c, &q.tabler, sort_table_elems(N)));
+  RGCN_TRY(dmalloc(c, q.pool, &q.loss_part, 2 * (size_t)std::max(q.energy_blocks, q.max_chunks), false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.loss, 1, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.slab, (size_t)q.max_chunks * d, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.keyv_t, 2 * N, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.keyr_t, N, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.tablev, sort_table_elems(2 * N), false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.tabler, sort_table_elems(N), false));
   RGCN_HIP(c, hipEventCreateWithFlags(&q.ev_ready, order_event_flags(c)));
-  if (!c->dcodes_own) RGCN_HIP(c, hipMalloc((void**)&c->dcodes_own, sizeof(float) * V * d));
+  if (!c->dcodes_own) RGCN_TRY(dmalloc(c, c->pool, &c->dcodes_own, V * d, false));
   q.maxN = maxN;
   return RGCN_OK;
 }
 
 void decoder_free(rgcn_ctx* c) {
   DecoderBufs& q = c->dec;
-  void* ptrs[] = {q.keyv, q.keyv_s, q.valv, q.permv, q.keyr, q.keyr_s, q.valr, q.permr, q.row_ptr, q.rel_ptr,
-                  q.chunk_ptr, q.e_other, q.e_rel, q.e_trip, q.long_rows, q.nlong, q.dx, q.loss_part, q.loss,
-                  q.slab, q.keyv_t, q.keyr_t, q.tablev, q.tabler, q.long_first, q.long_cnt, q.piece_row, q.piece_k,
-                  q.piece_slab, q.perm_pos, q.cb, q.rb, q.e_g, q.row_key, q.row_key_s, q.row_order, q.row_tab};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
+  q.pool.release();
   if (q.ev_ready) (void)hipEventDestroy(q.ev_ready);
   q = DecoderBufs();
 }

@@ -443,7 +443,7 @@ rgcn_status combine(rgcn_ctx* c, const char* tag, const CombineArgs& a_in, doubl
   CombineArgs a = a_in;
   const bool giant = a.msg != nullptr && a.row_ptr == c->g.row_ptr && c->g.giant_on;
   if (giant) {
-    if (!c->giant_slab) RGCN_HIP(c, hipMalloc((void**)&c->giant_slab, sizeof(float) * (size_t)c->g.piece_cap * c->d));
+    RGCN_TRY(giant_slab_ensure(c));
     a.giant_rows = c->g.giant_rows; a.giant_first = c->g.giant_first; a.giant_cnt = c->g.giant_cnt;
     a.piece_row = c->g.piece_row; a.piece_k = c->g.piece_k; a.ngiant = c->g.ngiant; a.giant_slab = c->giant_slab;
   }

@@ -495,121 +495,95 @@ uint32_t vertex_key_mul(int V, int R) {
   return (uint64_t)(V + 1) * (2 * (uint64_t)R) < (1ull << 31) ? (uint32_t)(2 * R) : 1u;
 }
 
-template <class T>
-rgcn_status dalloc(rgcn_ctx* c, T** p, size_t n) {
-  RGCN_HIP(c, hipMalloc((void**)p, (n ? n : 1) * sizeof(T)));
-  return RGCN_OK;
-}
-
 }  // namespace
 
-// `share`: a previously allocated set whose read-only / OR-only members (relation owner, error flag)
-// this set aliases.
-rgcn_status graph_alloc(rgcn_ctx* c, const GraphBufs* share) {
-  GraphBufs& g = c->g;
+// Everything the set owns.  The relation owner table and the error flag (read-only / OR-only) are the context's: the
+// caller points both sets at them.
+rgcn_status graph_alloc(rgcn_ctx* c, GraphBufs& g) {
   const size_t V = c->V, R2 = 2 * (size_t)c->R, M = 2 * (size_t)c->cfg.max_edges;
-  RGCN_TRY(dalloc(c, &g.triples, 3 * (size_t)c->cfg.max_edges));
+  RGCN_TRY(dmalloc(c, g.pool, &g.triples, 3 * (size_t)c->cfg.max_edges, false));
   g.counters_bytes = (2 * V + 3) * sizeof(int32_t);
-  RGCN_TRY(dalloc(c, &g.counters, 2 * V + 3));
+  RGCN_TRY(dmalloc(c, g.pool, &g.counters, 2 * V + 3, false));
   g.indeg = g.counters;
   g.outdeg = g.counters + V;
   g.nlong = g.counters + 2 * V;
   g.ngiant = g.counters + 2 * V + 1;
   g.giant_cap = (int32_t)(M / kGiantRow + 1);
   g.piece_cap = (int32_t)(2 * (M / kGiantRow) + 2);
-  RGCN_TRY(dalloc(c, &g.giant_rows, (size_t)g.giant_cap));
-  RGCN_TRY(dalloc(c, &g.giant_first, (size_t)g.giant_cap));
-  RGCN_TRY(dalloc(c, &g.giant_cnt, (size_t)g.giant_cap));
-  RGCN_TRY(dalloc(c, &g.piece_row, (size_t)g.piece_cap));
-  RGCN_TRY(dalloc(c, &g.piece_k, (size_t)g.piece_cap));
+  RGCN_TRY(dmalloc(c, g.pool, &g.giant_rows, (size_t)g.giant_cap, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.giant_first, (size_t)g.giant_cap, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.giant_cnt, (size_t)g.giant_cap, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.piece_row, (size_t)g.piece_cap, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.piece_k, (size_t)g.piece_cap, false));
   g.long_cap = (int32_t)(M / kLongRow + 1);
-  RGCN_TRY(dalloc(c, &g.long_rows, (size_t)g.long_cap));
-  RGCN_TRY(dalloc(c, &g.row_ptr, V + 1));
-  RGCN_TRY(dalloc(c, &g.rel_ptr, R2 + 1));
-  RGCN_TRY(dalloc(c, &g.chunk_ptr, R2 + 1));
-  RGCN_TRY(dalloc(c, &g.cum_in, V + 1));
-  RGCN_TRY(dalloc(c, &g.cum_out, V + 1));
-  RGCN_TRY(dalloc(c, &g.keyv, M));
-  RGCN_TRY(dalloc(c, &g.keyv_s, M));
-  RGCN_TRY(dalloc(c, &g.keyr, M));
-  RGCN_TRY(dalloc(c, &g.keyr_s, M));
-  RGCN_TRY(dalloc(c, &g.valv, M));
-  RGCN_TRY(dalloc(c, &g.permv, M));
-  RGCN_TRY(dalloc(c, &g.valr, M));
-  RGCN_TRY(dalloc(c, &g.permr, M));
-  RGCN_TRY(dalloc(c, &g.pos, M));
-  RGCN_TRY(dalloc(c, &g.m_src, M));
-  RGCN_TRY(dalloc(c, &g.m_dst, M));
-  RGCN_TRY(dalloc(c, &g.m_dslot, M));
-  RGCN_TRY(dalloc(c, &g.m_sslot, M));
-  RGCN_TRY(dalloc(c, &g.m_norm, M));
+  RGCN_TRY(dmalloc(c, g.pool, &g.long_rows, (size_t)g.long_cap, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.row_ptr, V + 1, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.rel_ptr, R2 + 1, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.chunk_ptr, R2 + 1, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.cum_in, V + 1, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.cum_out, V + 1, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.keyv, M, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.keyv_s, M, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.keyr, M, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.keyr_s, M, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.valv, M, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.permv, M, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.valr, M, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.permr, M, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.pos, M, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.m_src, M, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.m_dst, M, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.m_dslot, M, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.m_sslot, M, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.m_norm, M, false));
   {      // slot-ordered message lists (row-major gathers): the basis kind and the destination-major block layer
-    RGCN_TRY(dalloc(c, &g.d_src, M));
-    RGCN_TRY(dalloc(c, &g.d_rel, M));
-    RGCN_TRY(dalloc(c, &g.d_norm, M));
-    RGCN_TRY(dalloc(c, &g.s_dst, M));
-    RGCN_TRY(dalloc(c, &g.s_rel, M));
-    RGCN_TRY(dalloc(c, &g.s_norm, M));
+    RGCN_TRY(dmalloc(c, g.pool, &g.d_src, M, false));
+    RGCN_TRY(dmalloc(c, g.pool, &g.d_rel, M, false));
+    RGCN_TRY(dmalloc(c, g.pool, &g.d_norm, M, false));
+    RGCN_TRY(dmalloc(c, g.pool, &g.s_dst, M, false));
+    RGCN_TRY(dmalloc(c, g.pool, &g.s_rel, M, false));
+    RGCN_TRY(dmalloc(c, g.pool, &g.s_norm, M, false));
   }
   if (c->kind == RGCN_KIND_BASIS) {
-    RGCN_TRY(dalloc(c, &g.has_dir, 2 * V));
-    RGCN_TRY(dalloc(c, &g.unit_ptr, 2 * (V + 1)));
-    RGCN_TRY(dalloc(c, &g.unit_rows, 2 * V));
+    RGCN_TRY(dmalloc(c, g.pool, &g.has_dir, 2 * V, false));
+    RGCN_TRY(dmalloc(c, g.pool, &g.unit_ptr, 2 * (V + 1), false));
+    RGCN_TRY(dmalloc(c, g.pool, &g.unit_rows, 2 * V, false));
     RGCN_HIP(c, hipMemsetAsync(g.unit_ptr, 0, sizeof(int32_t) * 2 * (V + 1), c->stream));
   }
   if (c->kind == RGCN_KIND_BLOCK) {
-    RGCN_TRY(dalloc(c, &g.row_key, V));
-    RGCN_TRY(dalloc(c, &g.row_key_s, V));
-    RGCN_TRY(dalloc(c, &g.row_order, V));
-    RGCN_TRY(dalloc(c, &g.row_tab, sort_table_elems(V)));
-  }
-  if (share) {
-    g.owner = share->owner;
-    g.errflag = share->errflag;
-  } else {
-    RGCN_TRY(dalloc(c, &g.owner, (size_t)c->R));
-    RGCN_TRY(dalloc(c, &g.errflag, 1));
-    RGCN_HIP(c, hipMemsetAsync(g.owner, 0, sizeof(int32_t) * (size_t)(c->R ? c->R : 1), c->stream));
-    RGCN_HIP(c, hipMemsetAsync(g.errflag, 0, sizeof(int32_t), c->stream));
+    RGCN_TRY(dmalloc(c, g.pool, &g.row_key, V, false));
+    RGCN_TRY(dmalloc(c, g.pool, &g.row_key_s, V, false));
+    RGCN_TRY(dmalloc(c, g.pool, &g.row_order, V, false));
+    RGCN_TRY(dmalloc(c, g.pool, &g.row_tab, sort_table_elems(V), false));
   }
   RGCN_HIP(c, hipEventCreateWithFlags(&g.ev_ready, order_event_flags(c)));
   RGCN_HIP(c, hipEventCreateWithFlags(&g.ev_free, order_event_flags(c)));
   RGCN_HIP(c, hipMemsetAsync(g.row_ptr, 0, sizeof(int32_t) * (V + 1), c->stream));
   RGCN_HIP(c, hipMemsetAsync(g.rel_ptr, 0, sizeof(int32_t) * (R2 + 1), c->stream));
   RGCN_HIP(c, hipMemsetAsync(g.chunk_ptr, 0, sizeof(int32_t) * (R2 + 1), c->stream));
-  RGCN_TRY(dalloc(c, &g.keyv_t, M));
-  RGCN_TRY(dalloc(c, &g.keyr_t, M));
-  RGCN_TRY(dalloc(c, &g.tablev, sort_table_elems(M)));
-  RGCN_TRY(dalloc(c, &g.tabler, sort_table_elems(M)));
+  RGCN_TRY(dmalloc(c, g.pool, &g.keyv_t, M, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.keyr_t, M, false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.tablev, sort_table_elems(M), false));
+  RGCN_TRY(dmalloc(c, g.pool, &g.tabler, sort_table_elems(M), false));
   if (c->cfg.norm_mode == RGCN_NORM_LOCAL && vertex_key_mul(c->V, c->R) == 1u) {
     // the message list by destination (see the header comment): only this mode, only where the vertex key is bare
-    RGCN_TRY(dalloc(c, &g.keyd, M));
-    RGCN_TRY(dalloc(c, &g.keyd_s, M));
-    RGCN_TRY(dalloc(c, &g.keyd_t, M));
-    RGCN_TRY(dalloc(c, &g.vald, M));
-    RGCN_TRY(dalloc(c, &g.permd, M));
-    RGCN_TRY(dalloc(c, &g.tabled, sort_table_elems(M)));
+    RGCN_TRY(dmalloc(c, g.pool, &g.keyd, M, false));
+    RGCN_TRY(dmalloc(c, g.pool, &g.keyd_s, M, false));
+    RGCN_TRY(dmalloc(c, g.pool, &g.keyd_t, M, false));
+    RGCN_TRY(dmalloc(c, g.pool, &g.vald, M, false));
+    RGCN_TRY(dmalloc(c, g.pool, &g.permd, M, false));
+    RGCN_TRY(dmalloc(c, g.pool, &g.tabled, sort_table_elems(M), false));
   }
   return RGCN_OK;
 }
 
-static void graph_free_one(GraphBufs& g, bool owns_shared) {
-  if (!owns_shared) { g.owner = nullptr; g.errflag = nullptr; }
-  if (g.ev_ready) (void)hipEventDestroy(g.ev_ready);
-  if (g.ev_free) (void)hipEventDestroy(g.ev_free);
-  void* ptrs[] = {g.giant_rows, g.giant_first, g.giant_cnt, g.piece_row, g.piece_k, g.long_rows, g.triples, g.counters, g.row_ptr, g.rel_ptr, g.chunk_ptr, g.cum_in, g.cum_out,
-                  g.keyv, g.keyv_s, g.keyr, g.keyr_s, g.valv, g.permv, g.valr, g.permr, g.pos,
-                  g.m_src, g.m_dst, g.m_dslot, g.m_sslot, g.m_norm, g.d_src, g.d_rel, g.d_norm, g.s_dst, g.s_rel,
-                  g.s_norm, g.owner, g.errflag, g.keyv_t, g.keyr_t, g.tablev, g.tabler, g.row_key, g.row_key_s, g.row_order,
-                  g.row_tab, g.has_dir, g.unit_ptr, g.unit_rows, g.keyd, g.keyd_s, g.keyd_t, g.vald, g.permd, g.tabled};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  g = GraphBufs();
-}
-
 void graph_free(rgcn_ctx* c) {
-  graph_free_one(c->g_alt, false);
-  graph_free_one(c->g, true);
+  for (GraphBufs* g : {&c->g_alt, &c->g}) {
+    g->pool.release();
+    if (g->ev_ready) (void)hipEventDestroy(g->ev_ready);
+    if (g->ev_free) (void)hipEventDestroy(g->ev_free);
+    *g = GraphBufs();
+  }
 }
 
 rgcn_status graph_build(rgcn_ctx* c, const int32_t* tri, int64_t E64) {

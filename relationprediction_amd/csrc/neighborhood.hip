@@ -327,12 +327,6 @@ __global__ void __launch_bounds__(kCompactBlock) k_nbr_write(const DrawParams* _
   out[3 * slot + 2] = tri[3 * e + 2];
 }
 
-template <class T>
-rgcn_status dalloc(rgcn_ctx* c, T** p, size_t n) {
-  RGCN_HIP(c, hipMalloc((void**)p, (n ? n : 1) * sizeof(T)));
-  return RGCN_OK;
-}
-
 int find_root(std::vector<int32_t>& parent, int x) {
   while (parent[x] != x) {
     parent[x] = parent[parent[x]];
@@ -345,10 +339,7 @@ int find_root(std::vector<int32_t>& parent, int x) {
 
 void neighborhood_free(rgcn_ctx* c) {
   NeighborhoodBufs& q = c->nbr;
-  void* ptrs[] = {q.triples, q.seg_v, q.seg_beg, q.seg_end, q.adj_other, q.adj_end, q.comp, q.comp_state, q.dist, q.tkey, q.hist, q.state,
-                  q.changed, q.bcnt, q.params};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
+  q.pool.release();
   if (q.draw_exec) (void)hipGraphExecDestroy(q.draw_exec);
   if (q.draw_graph) (void)hipGraphDestroy(q.draw_graph);
   if (q.capture_stream) (void)hipStreamDestroy(q.capture_stream);
@@ -440,21 +431,21 @@ rgcn_status neighborhood_reserve(rgcn_ctx* c, const int32_t* tri, int64_t n64) {
     q.launches = launches;
   }
   const size_t nb = (size_t)((n + kCompactBlock - 1) / kCompactBlock) + 1;
-  RGCN_TRY(dalloc(c, &q.triples, 3 * (size_t)n));
-  RGCN_TRY(dalloc(c, &q.seg_v, seg_v.size()));
-  RGCN_TRY(dalloc(c, &q.seg_beg, seg_v.size()));
-  RGCN_TRY(dalloc(c, &q.seg_end, seg_v.size()));
-  RGCN_TRY(dalloc(c, &q.adj_other, other.size()));
-  RGCN_TRY(dalloc(c, &q.adj_end, endid.size()));
-  RGCN_TRY(dalloc(c, &q.comp, (size_t)V));
-  RGCN_TRY(dalloc(c, &q.comp_state, (size_t)q.ncomp));
-  RGCN_TRY(dalloc(c, &q.dist, (size_t)V));
-  RGCN_TRY(dalloc(c, &q.tkey, (size_t)n));
-  RGCN_TRY(dalloc(c, &q.hist, (size_t)kBins));
-  RGCN_TRY(dalloc(c, &q.state, (size_t)2));
-  RGCN_TRY(dalloc(c, &q.changed, (size_t)q.launches * kFlagSlots * kFlagStride));
-  RGCN_TRY(dalloc(c, &q.bcnt, nb));
-  RGCN_HIP(c, hipMalloc(&q.params, sizeof(DrawParams)));
+  RGCN_TRY(dmalloc(c, q.pool, &q.triples, 3 * (size_t)n, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.seg_v, seg_v.size(), false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.seg_beg, seg_v.size(), false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.seg_end, seg_v.size(), false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.adj_other, other.size(), false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.adj_end, endid.size(), false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.comp, (size_t)V, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.comp_state, (size_t)q.ncomp, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.dist, (size_t)V, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.tkey, (size_t)n, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.hist, (size_t)kBins, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.state, (size_t)2, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.changed, (size_t)q.launches * kFlagSlots * kFlagStride, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.bcnt, nb, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.params, sizeof(DrawParams), false));
   hipStream_t st = c->stream;
   RGCN_HIP(c, hipMemcpyAsync(q.triples, tri, sizeof(int32_t) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
   if (!other.empty()) {

@@ -182,10 +182,8 @@ rgcn_status build_table(rgcn_ctx* c, OptTable& tab, int* nrep, double* total) {
       int64_t n = p.count;
       if (p.name == "W_relation") n = (int64_t)c->R * c->d;     // rows >= RelationCount never get a gradient
       if (!o.m[i]) {
-        RGCN_HIP(c, hipMalloc((void**)&o.m[i], sizeof(float) * (size_t)n));
-        RGCN_HIP(c, hipMalloc((void**)&o.v[i], sizeof(float) * (size_t)n));
-        RGCN_HIP(c, hipMemsetAsync(o.m[i], 0, sizeof(float) * (size_t)n, c->stream));
-        RGCN_HIP(c, hipMemsetAsync(o.v[i], 0, sizeof(float) * (size_t)n, c->stream));
+        RGCN_TRY(dmalloc(c, o.pool, &o.m[i], (size_t)n, true));
+        RGCN_TRY(dmalloc(c, o.pool, &o.v[i], (size_t)n, true));
       }
       if (tab.count >= kOptMaxTensors) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "too many tensors for one optimizer launch");
       OptTensor& t = tab.t[tab.count++];
@@ -197,18 +195,13 @@ rgcn_status build_table(rgcn_ctx* c, OptTable& tab, int* nrep, double* total) {
   }
   tab.nblocks = nblocks;
   if ((size_t)nblocks > o.part_cap) {
-    if (o.part) (void)hipFree(o.part);
-    RGCN_HIP(c, hipMalloc((void**)&o.part, sizeof(float) * (size_t)nblocks));
+    o.part_pool.release();
+    o.part_cap = 0;
+    RGCN_TRY(dmalloc(c, o.part_pool, &o.part, (size_t)nblocks, false));
     o.part_cap = (size_t)nblocks;
   }
-  if (!o.state) {
-    RGCN_HIP(c, hipMalloc((void**)&o.state, 4 * sizeof(float)));
-    RGCN_HIP(c, hipMemsetAsync(o.state, 0, 4 * sizeof(float), c->stream));
-  }
-  if (c->world > 1 && !o.shard_sq) {
-    RGCN_HIP(c, hipMalloc((void**)&o.shard_sq, sizeof(float)));
-    RGCN_HIP(c, hipMemsetAsync(o.shard_sq, 0, sizeof(float), c->stream));
-  }
+  if (!o.state) RGCN_TRY(dmalloc(c, o.pool, &o.state, 4, true));
+  if (c->world > 1 && !o.shard_sq) RGCN_TRY(dmalloc(c, o.pool, &o.shard_sq, 1, true));
   return RGCN_OK;
 }
 
@@ -267,13 +260,9 @@ rgcn_status optimizer_step(rgcn_ctx* c) {
 }
 
 void optimizer_free(rgcn_ctx* c) {
-  OptimizerState& o = c->opt;
-  for (float* p : o.m) if (p) (void)hipFree(p);
-  for (float* p : o.v) if (p) (void)hipFree(p);
-  if (o.part) (void)hipFree(o.part);
-  if (o.state) (void)hipFree(o.state);
-  if (o.shard_sq) (void)hipFree(o.shard_sq);
-  o = OptimizerState();
+  c->opt.pool.release();
+  c->opt.part_pool.release();
+  c->opt = OptimizerState();
 }
 
 }  // namespace rgcn

@@ -357,24 +357,19 @@ __global__ void k_topk_check(const int32_t* __restrict__ X, int n, int V, int R,
 }  // namespace
 
 void rank_free(rgcn_ctx* c) {
-  if (c->rank_q) (void)hipFree(c->rank_q);
-  if (c->rank_s) (void)hipFree(c->rank_s);
-  if (c->rank_bad) (void)hipFree(c->rank_bad);
-  if (c->rank_thr) (void)hipFree(c->rank_thr);
-  c->rank_thr = nullptr;
-  c->rank_q = c->rank_s = nullptr;
-  c->rank_bad = nullptr;
-  c->rank_max = 0;
+  c->ranking.pool.release();
+  c->ranking = RankBufs();
 }
 
 rgcn_status rank_reserve(rgcn_ctx* c, int64_t max_queries) {
-  if (max_queries <= c->rank_max) return RGCN_OK;
+  RankBufs& q = c->ranking;
+  if (max_queries <= q.max) return RGCN_OK;
   rank_free(c);
-  RGCN_HIP(c, hipMalloc((void**)&c->rank_q, sizeof(float) * (size_t)max_queries * c->d));
-  RGCN_HIP(c, hipMalloc((void**)&c->rank_s, sizeof(float) * (size_t)max_queries * c->V));
-  RGCN_HIP(c, hipMalloc((void**)&c->rank_bad, sizeof(int32_t)));
-  RGCN_HIP(c, hipMalloc((void**)&c->rank_thr, sizeof(float) * (size_t)max_queries));
-  c->rank_max = max_queries;
+  RGCN_TRY(dmalloc(c, q.pool, &q.q, (size_t)max_queries * c->d, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.s, (size_t)max_queries * c->V, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.bad, 1, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.thr, (size_t)max_queries, false));
+  q.max = max_queries;
   return RGCN_OK;
 }
 
@@ -384,32 +379,32 @@ rgcn_status rank_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predi
   // ids are validated on the device (out-of-range ids are rejected, never clamped): the verdict is read back at the END
   // of the call, with no host wait in the middle -- until then the kernels below substitute id 0 for a bad id so that
   // nothing faults, and the (meaningless) ranks of a rejected call are never returned
-  RGCN_HIP(c, hipMemsetAsync(c->rank_bad, 0, sizeof(int32_t), c->stream));
+  RGCN_HIP(c, hipMemsetAsync(c->ranking.bad, 0, sizeof(int32_t), c->stream));
   hipLaunchKernelGGL(k_rank_check, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, X_dev, (int)N, c->V,
-                     c->R, filt_ptr, filt_idx, c->rank_bad);
+                     c->R, filt_ptr, filt_idx, c->ranking.bad);
   RGCN_HIP(c, hipGetLastError());
-  for (int64_t b = 0; b < N; b += c->rank_max) {
-    const int n = (int)std::min<int64_t>(c->rank_max, N - b);
+  for (int64_t b = 0; b < N; b += c->ranking.max) {
+    const int n = (int)std::min<int64_t>(c->ranking.max, N - b);
     const int32_t* X = X_dev + 3 * b;
     {
       ProfScope ps(c, "rank_query", 4.0 * 3 * n * c->d, 0);
       hipLaunchKernelGGL(k_rank_query, dim3((unsigned)n), dim3(128), 0, c->stream, codes, c->w_rel, X, n, c->d,
-                         predict_object, c->rank_q, c->V, c->R);
+                         predict_object, c->ranking.q, c->V, c->R);
       RGCN_HIP(c, hipGetLastError());
     }
-    RGCN_TRY(gemm_f32(c, "rank_scores", true, true, n, c->V, c->d, c->rank_q, c->d, codes, c->d, c->rank_s, c->V, 1));
+    RGCN_TRY(gemm_f32(c, "rank_scores", true, true, n, c->V, c->d, c->ranking.q, c->d, codes, c->d, c->ranking.s, c->V, 1));
     {
       ProfScope ps(c, "rank_rows", 4.0 * n * c->V, 0);
-      hipLaunchKernelGGL(k_rank_threshold, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, c->rank_s, c->V, X, n,
-                         predict_object, c->rank_thr);
-      hipLaunchKernelGGL(k_rank_rows, dim3((unsigned)n), dim3(256), 0, c->stream, c->rank_s, c->V, X, n,
-                         predict_object, filt_ptr + b, filt_idx, c->rank_thr, raw_out + b, filt_out + b, c->rank_bad,
+      hipLaunchKernelGGL(k_rank_threshold, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, c->ranking.s, c->V, X, n,
+                         predict_object, c->ranking.thr);
+      hipLaunchKernelGGL(k_rank_rows, dim3((unsigned)n), dim3(256), 0, c->stream, c->ranking.s, c->V, X, n,
+                         predict_object, filt_ptr + b, filt_idx, c->ranking.thr, raw_out + b, filt_out + b, c->ranking.bad,
                          filt_ptr + N);
       RGCN_HIP(c, hipGetLastError());
     }
   }
   int32_t bad = 0;
-  RGCN_HIP(c, hipMemcpyAsync(&bad, c->rank_bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  RGCN_HIP(c, hipMemcpyAsync(&bad, c->ranking.bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   RGCN_HIP(c, hipStreamSynchronize(c->stream));
   if (bad) RGCN_FAIL(c, RGCN_ERR_INVALID, "rank: entity / relation / filter index out of range");
   return RGCN_OK;
@@ -431,31 +426,31 @@ rgcn_status topk_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predi
   }
   // as rank_compute: ids are validated on the device, id 0 stands in for a bad one until the verdict is read back at the
   // end of the call, and the (meaningless) answers of a rejected call are not to be used
-  RGCN_HIP(c, hipMemsetAsync(c->rank_bad, 0, sizeof(int32_t), c->stream));
+  RGCN_HIP(c, hipMemsetAsync(c->ranking.bad, 0, sizeof(int32_t), c->stream));
   hipLaunchKernelGGL(k_topk_check, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, X_dev, (int)N, c->V, c->R,
-                     predict_object, excl_ptr, c->rank_bad);
+                     predict_object, excl_ptr, c->ranking.bad);
   RGCN_HIP(c, hipGetLastError());
-  for (int64_t b = 0; b < N; b += c->rank_max) {
-    const int n = (int)std::min<int64_t>(c->rank_max, N - b);
+  for (int64_t b = 0; b < N; b += c->ranking.max) {
+    const int n = (int)std::min<int64_t>(c->ranking.max, N - b);
     const int32_t* X = X_dev + 3 * b;
     {
       ProfScope ps(c, "rank_query", 4.0 * 3 * n * c->d, 0);
       hipLaunchKernelGGL(k_rank_query, dim3((unsigned)n), dim3(128), 0, c->stream, codes, c->w_rel, X, n, c->d,
-                         predict_object, c->rank_q, c->V, c->R);
+                         predict_object, c->ranking.q, c->V, c->R);
       RGCN_HIP(c, hipGetLastError());
     }
-    RGCN_TRY(gemm_f32(c, "rank_scores", true, true, n, c->V, c->d, c->rank_q, c->d, codes, c->d, c->rank_s, c->V, 1));
+    RGCN_TRY(gemm_f32(c, "rank_scores", true, true, n, c->V, c->d, c->ranking.q, c->d, codes, c->d, c->ranking.s, c->V, 1));
     {
       // design bytes: four select passes and the gather read the row (from L2 after the first)
       ProfScope ps(c, "topk_rows", 5.0 * 4.0 * n * c->V + 8.0 * n * k, 0, 4.0 * n * c->V + 8.0 * n * k);
-      hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)n), dim3(TOPK_THREADS), mask_bytes, c->stream, c->rank_s, c->V, n, k,
+      hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)n), dim3(TOPK_THREADS), mask_bytes, c->stream, c->ranking.s, c->V, n, k,
                          excl_ptr ? excl_ptr + b : nullptr, excl_idx, excl_ptr ? excl_ptr + N : nullptr,
-                         idx_out + (size_t)b * k, energy_out + (size_t)b * k, c->rank_bad);
+                         idx_out + (size_t)b * k, energy_out + (size_t)b * k, c->ranking.bad);
       RGCN_HIP(c, hipGetLastError());
     }
   }
   int32_t bad = 0;
-  RGCN_HIP(c, hipMemcpyAsync(&bad, c->rank_bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  RGCN_HIP(c, hipMemcpyAsync(&bad, c->ranking.bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   RGCN_HIP(c, hipStreamSynchronize(c->stream));
   if (bad) RGCN_FAIL(c, RGCN_ERR_INVALID, "topk: entity / relation / exclusion index out of range");
   return RGCN_OK;

@@ -312,25 +312,11 @@ static void free_all(rgcn_ctx* c) {
   if (c->main_stream) (void)hipStreamSynchronize(c->main_stream);
   comm_destroy(c);
   graph_free(c);
-  auto F = [](void* p) { if (p) (void)hipFree(p); };
   decoder_free(c);
   neighborhood_free(c);
   optimizer_free(c);
   rank_free(c);
-  if (c->giant_slab) (void)hipFree(c->giant_slab);
-  F(c->w_emb); F(c->g_emb); F(c->b_emb); F(c->gb_emb); F(c->w_rel); F(c->g_rel);
-  for (LayerBufs& lb : c->layers) {
-    if (c->repl_grads) {      // views into repl_grads
-      lb.gwself = nullptr;
-      if (c->kind == RGCN_KIND_BASIS) lb.grel = nullptr;
-    }
-    F(lb.wrel); F(lb.grel); F(lb.coef); F(lb.gcoef); F(lb.wself); F(lb.gwself); F(lb.bias); F(lb.gbias); F(lb.wtile);
-    F(lb.wself_nn); F(lb.wself_nt); F(lb.wrel_nn); F(lb.wrel_nt);
-  }
-  for (float* h : c->H) F(h);
-  F(c->self_buf); F(c->exch); F(c->dbuf[0]); F(c->dbuf[1]); F(c->dsbuf[0]); F(c->dsbuf[1]);
-  F(c->msgbuf); F(c->msgbuf2); F(c->slab); F(c->slab_dw); F(c->aggbuf);
-  for (float* z : c->zsave) F(z); F(c->stage); F(c->masks); F(c->colsum_part); F(c->dcodes_own); F(c->zeros);
+  c->pool.release();
   for (ProfRec& r : c->prof) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
   for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
   if (c->t0) (void)hipEventDestroy(c->t0);
@@ -341,11 +327,9 @@ static void free_all(rgcn_ctx* c) {
   }
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_gather) (void)hipEventDestroy(c->ev_gather);
-  F(c->repl_grads);
   if (c->ev_step_begin) (void)hipEventDestroy(c->ev_step_begin);
   for (hipGraphExec_t g : c->graphs) if (g) (void)hipGraphExecDestroy(g);
   for (hipGraph_t g : c->graph_defs) if (g) (void)hipGraphDestroy(g);
-  if (c->replay_counter) (void)hipFree(c->replay_counter);
   if (c->readback_host) (void)hipHostFree(c->readback_host);
   if (c->stage_host) {
     (void)hipHostFree(c->stage_host);
@@ -446,10 +430,10 @@ static rgcn_status create_impl(rgcn_ctx* c) {
   const size_t V = c->V, d = c->d, R = c->R, Vd = (size_t)c->V_pad * d;
   RGCN_HIP(c, hipEventCreateWithFlags(&c->ev_gather, hipEventDisableTiming));
   if (!c->onehot) {      // (one-hot input: no AffineTransform under the layers, model_builder.py:140-165)
-    RGCN_TRY(dmalloc(c, &c->w_emb, Vd));
-    RGCN_TRY(dmalloc(c, &c->g_emb, Vd));
-    RGCN_TRY(dmalloc(c, &c->b_emb, d));
-    RGCN_TRY(dmalloc(c, &c->gb_emb, d));
+    RGCN_TRY(dmalloc(c, c->pool, &c->w_emb, Vd, true));
+    RGCN_TRY(dmalloc(c, c->pool, &c->g_emb, Vd, true));
+    RGCN_TRY(dmalloc(c, c->pool, &c->b_emb, d, true));
+    RGCN_TRY(dmalloc(c, c->pool, &c->gb_emb, d, true));
     add_param(c, "W_emb", {(int64_t)V, (int64_t)d}, c->w_emb, c->g_emb, LAYOUT_PLAIN);
     add_param(c, "b_emb", {(int64_t)d}, c->b_emb, c->gb_emb, LAYOUT_PLAIN);
   }
@@ -459,7 +443,7 @@ static rgcn_status create_impl(rgcn_ctx* c) {
   const size_t repl_per_layer = d * d + (c->kind == RGCN_KIND_BASIS ? 2 * (size_t)f.num_bases * d * d : 0);
   if (c->world > 1) {
     c->repl_grads_floats = repl_per_layer * c->L;
-    RGCN_TRY(dmalloc(c, &c->repl_grads, c->repl_grads_floats));
+    RGCN_TRY(dmalloc(c, c->pool, &c->repl_grads, c->repl_grads_floats, true));
   }
   for (int l = 1; l <= c->L; ++l) {
     LayerBufs& lb = c->layers[l];
@@ -469,18 +453,18 @@ static rgcn_status create_impl(rgcn_ctx* c) {
       // BasisGcn with onehot_input=True (gcn_basis.py:16-24): vertex_feature_dimension = EntityCount -- W_forward,
       // W_backward [V,B,d] and W_self [V,d] are lookup tables, kept in the host layout; no GEMM, no fragment tables
       const size_t per_dir = V * (size_t)c->B * d;
-      RGCN_TRY(dmalloc(c, &lb.wrel, 2 * per_dir));
-      RGCN_TRY(dmalloc(c, &lb.grel, 2 * per_dir));
-      RGCN_TRY(dmalloc(c, &lb.coef, 2 * R * c->B));
-      RGCN_TRY(dmalloc(c, &lb.gcoef, 2 * R * c->B));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.wrel, 2 * per_dir, true));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.grel, 2 * per_dir, true));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.coef, 2 * R * c->B, true));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.gcoef, 2 * R * c->B, true));
       add_param(c, "W_f1", {(int64_t)V, c->B, (int64_t)d}, lb.wrel, lb.grel, LAYOUT_PLAIN);
       add_param(c, "W_b1", {(int64_t)V, c->B, (int64_t)d}, lb.wrel + per_dir, lb.grel + per_dir, LAYOUT_PLAIN);
       add_param(c, "C_f1", {(int64_t)R, c->B}, lb.coef, lb.gcoef, LAYOUT_PLAIN);
       add_param(c, "C_b1", {(int64_t)R, c->B}, lb.coef + R * c->B, lb.gcoef + R * c->B, LAYOUT_PLAIN);
-      RGCN_TRY(dmalloc(c, &lb.wself, V * d));
-      RGCN_TRY(dmalloc(c, &lb.gwself, V * d));
-      RGCN_TRY(dmalloc(c, &lb.bias, d));
-      RGCN_TRY(dmalloc(c, &lb.gbias, d));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.wself, V * d, true));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.gwself, V * d, true));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.bias, d, true));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.gbias, d, true));
       add_param(c, "W_self1", {(int64_t)V, (int64_t)d}, lb.wself, lb.gwself, LAYOUT_PLAIN);
       add_param(c, "b1", {(int64_t)d}, lb.bias, lb.gbias, LAYOUT_PLAIN);
       c->params.back().no_grad = true;
@@ -488,52 +472,52 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     }
     if (c->kind == RGCN_KIND_BLOCK) {
       const size_t per_dir = R * c->nb * c->sd * c->sd;
-      RGCN_TRY(dmalloc(c, &lb.wrel, 2 * per_dir));
-      RGCN_TRY(dmalloc(c, &lb.grel, 2 * per_dir));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.wrel, 2 * per_dir, true));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.grel, 2 * per_dir, true));
       add_param(c, "W_f" + sl, {(int64_t)R, c->nb, c->sd, c->sd}, lb.wrel, lb.grel, LAYOUT_BLOCK_T);
       add_param(c, "W_b" + sl, {(int64_t)R, c->nb, c->sd, c->sd}, lb.wrel + per_dir, lb.grel + per_dir, LAYOUT_BLOCK_T);
-      if (c->nb <= 512) RGCN_TRY(dmalloc(c, &lb.wtile, block_rows_weight_floats(c)));
+      if (c->nb <= 512) RGCN_TRY(dmalloc(c, c->pool, &lb.wtile, block_rows_weight_floats(c), true));
     } else {
       const size_t per_dir = (size_t)c->B * d * d;
-      RGCN_TRY(dmalloc(c, &lb.wrel, 2 * per_dir));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.wrel, 2 * per_dir, true));
       if (repl) lb.grel = repl + d * d;
-      else RGCN_TRY(dmalloc(c, &lb.grel, 2 * per_dir));
-      RGCN_TRY(dmalloc(c, &lb.coef, 2 * R * c->B));
-      RGCN_TRY(dmalloc(c, &lb.gcoef, 2 * R * c->B));
+      else RGCN_TRY(dmalloc(c, c->pool, &lb.grel, 2 * per_dir, true));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.coef, 2 * R * c->B, true));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.gcoef, 2 * R * c->B, true));
       add_param(c, "W_f" + sl, {(int64_t)d, c->B, (int64_t)d}, lb.wrel, lb.grel, LAYOUT_BASIS_T);
       add_param(c, "W_b" + sl, {(int64_t)d, c->B, (int64_t)d}, lb.wrel + per_dir, lb.grel + per_dir, LAYOUT_BASIS_T);
       add_param(c, "C_f" + sl, {(int64_t)R, c->B}, lb.coef, lb.gcoef, LAYOUT_PLAIN);
       add_param(c, "C_b" + sl, {(int64_t)R, c->B}, lb.coef + R * c->B, lb.gcoef + R * c->B, LAYOUT_PLAIN);
     }
-    RGCN_TRY(dmalloc(c, &lb.wself, d * d));
+    RGCN_TRY(dmalloc(c, c->pool, &lb.wself, d * d, true));
     {      // fragment tables (allocated here: a capture may be the first call that needs them)
       const size_t ws = 16 * gemm_bfrag_words((int)d, (int)d);
-      RGCN_HIP(c, hipMalloc(&lb.wself_nn, ws));
-      RGCN_HIP(c, hipMalloc(&lb.wself_nt, ws));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.wself_nn, ws, false));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.wself_nt, ws, false));
       if (c->kind == RGCN_KIND_BASIS) {
         const int Bd = c->B * (int)d;
-        RGCN_HIP(c, hipMalloc(&lb.wrel_nn, 2 * 16 * gemm_bfrag_words(Bd, (int)d)));
-        RGCN_HIP(c, hipMalloc(&lb.wrel_nt, 2 * 16 * gemm_bfrag_words((int)d, Bd)));
+        RGCN_TRY(dmalloc(c, c->pool, &lb.wrel_nn, 2 * 16 * gemm_bfrag_words(Bd, (int)d), false));
+        RGCN_TRY(dmalloc(c, c->pool, &lb.wrel_nt, 2 * 16 * gemm_bfrag_words((int)d, Bd), false));
       }
     }
     if (repl) lb.gwself = repl;
-    else RGCN_TRY(dmalloc(c, &lb.gwself, d * d));
-    RGCN_TRY(dmalloc(c, &lb.bias, d));
-    RGCN_TRY(dmalloc(c, &lb.gbias, d));
+    else RGCN_TRY(dmalloc(c, c->pool, &lb.gwself, d * d, true));
+    RGCN_TRY(dmalloc(c, c->pool, &lb.bias, d, true));
+    RGCN_TRY(dmalloc(c, c->pool, &lb.gbias, d, true));
     add_param(c, "W_self" + sl, {(int64_t)d, (int64_t)d}, lb.wself, lb.gwself, LAYOUT_PLAIN);
     add_param(c, "b" + sl, {(int64_t)d}, lb.bias, lb.gbias, LAYOUT_PLAIN);
     c->params.back().no_grad = true;
   }
-  RGCN_TRY(dmalloc(c, &c->w_rel, Vd));
-  RGCN_TRY(dmalloc(c, &c->g_rel, Vd));
+  RGCN_TRY(dmalloc(c, c->pool, &c->w_rel, Vd, true));
+  RGCN_TRY(dmalloc(c, c->pool, &c->g_rel, Vd, true));
   add_param(c, "W_relation", {(int64_t)V, (int64_t)d}, c->w_rel, c->g_rel, LAYOUT_PLAIN);
   c->H.assign(c->L + 1, nullptr);
-  for (int l = c->onehot ? 1 : 0; l <= c->L; ++l) RGCN_TRY(dmalloc(c, &c->H[l], Vd));      // (one-hot input: no H_0)
-  RGCN_TRY(dmalloc(c, &c->self_buf, Vd));
-  if (c->world > 1) RGCN_TRY(dmalloc(c, &c->exch, Vd));
+  for (int l = c->onehot ? 1 : 0; l <= c->L; ++l) RGCN_TRY(dmalloc(c, c->pool, &c->H[l], Vd, true));   // (one-hot input: no H_0)
+  RGCN_TRY(dmalloc(c, c->pool, &c->self_buf, Vd, true));
+  if (c->world > 1) RGCN_TRY(dmalloc(c, c->pool, &c->exch, Vd, true));
   for (int k = 0; k < 2; ++k) {
-    RGCN_TRY(dmalloc(c, &c->dbuf[k], Vd));
-    RGCN_TRY(dmalloc(c, &c->dsbuf[k], Vd));
+    RGCN_TRY(dmalloc(c, c->pool, &c->dbuf[k], Vd, true));
+    RGCN_TRY(dmalloc(c, c->pool, &c->dsbuf[k], Vd, true));
   }
   const size_t M = 2 * (size_t)f.max_edges;
   size_t slab = 64 * d * d;   // split-K slabs of the dW_self GEMM
@@ -541,37 +525,40 @@ static rgcn_status create_impl(rgcn_ctx* c) {
   // (graph_build), so a graph of 65536 messages cut at 48 can have more chunks than the largest graph cut coarser
   const size_t max_rel_chunks = std::max((M + c->chunk - 1) / c->chunk, (std::min<size_t>(M, 65536) + 47) / 48) + 2 * R;
   if (c->kind == RGCN_KIND_BLOCK) {
-    RGCN_TRY(dmalloc(c, &c->msgbuf, (M ? M : 1) * d, false));
+    RGCN_TRY(dmalloc(c, c->pool, &c->msgbuf, (M ? M : 1) * d, false));
     const size_t per_rel = (size_t)c->sd * c->sd * c->nb;
     c->slab_dw_floats = max_rel_chunks * per_rel;
-    RGCN_TRY(dmalloc(c, &c->slab_dw, c->slab_dw_floats, false));
+    RGCN_TRY(dmalloc(c, c->pool, &c->slab_dw, c->slab_dw_floats, false));
   } else {
     const size_t zc = 2 * (size_t)c->B * d;
-    RGCN_TRY(dmalloc(c, &c->msgbuf2, V * zc));
-    RGCN_TRY(dmalloc(c, &c->aggbuf, 2 * V * d));     // [2][V][d]: unit products (forward), gathered upstream rows (backward)
+    RGCN_TRY(dmalloc(c, c->pool, &c->msgbuf2, V * zc, true));
+    // aggbuf [2][V][d]: unit products (forward), gathered upstream rows (backward)
+    RGCN_TRY(dmalloc(c, c->pool, &c->aggbuf, 2 * V * d, true));
     c->zsave.assign(c->L + 1, nullptr);
-    for (int l = c->onehot ? 2 : 1; l <= c->L; ++l) RGCN_TRY(dmalloc(c, &c->zsave[l], V * zc));   // (a one-hot layer 1 has no Z)
+    // (a one-hot layer 1 has no Z)
+    for (int l = c->onehot ? 2 : 1; l <= c->L; ++l) RGCN_TRY(dmalloc(c, c->pool, &c->zsave[l], V * zc, true));
     const size_t s2 = 16 * zc * d;
     if (s2 > slab) slab = s2;
     c->slab_dw_floats = max_rel_chunks * (size_t)c->B;
-    RGCN_TRY(dmalloc(c, &c->slab_dw, c->slab_dw_floats, false));
+    RGCN_TRY(dmalloc(c, c->pool, &c->slab_dw, c->slab_dw_floats, false));
   }
   c->slab_floats = slab;
-  RGCN_TRY(dmalloc(c, &c->slab, slab));
+  RGCN_TRY(dmalloc(c, c->pool, &c->slab, slab, true));
   size_t stage = Vd;
   for (const Param& p : c->params)
     if ((size_t)p.count > stage) stage = (size_t)p.count;
   c->stage_floats = stage;
-  RGCN_TRY(dmalloc(c, &c->stage, stage, false));
+  RGCN_TRY(dmalloc(c, c->pool, &c->stage, stage, false));
   // one partial row per combine workgroup (4 rows each at worst) + the second-level partials of their sum
   c->colsum_part_floats = ((V + 3) / 4 + 1024 + 2 + ((V + 3) / 4 + 1024) / 32 + 2) * d;
-  RGCN_TRY(dmalloc(c, &c->colsum_part, 2 * c->colsum_part_floats));      // two halves: rgcn_ctx::colsum_half
-  RGCN_TRY(dmalloc(c, &c->zeros, 1024));
-  RGCN_TRY(graph_alloc(c, nullptr));
-  std::swap(c->g, c->g_alt);
-  RGCN_TRY(graph_alloc(c, &c->g_alt));
-  std::swap(c->g, c->g_alt);
-  {
+  RGCN_TRY(dmalloc(c, c->pool, &c->colsum_part, 2 * c->colsum_part_floats, true));      // two halves: rgcn_ctx::colsum_half
+  RGCN_TRY(dmalloc(c, c->pool, &c->zeros, 1024, true));
+  for (GraphBufs* g : {&c->g, &c->g_alt}) RGCN_TRY(graph_alloc(c, *g));
+  {      // the relation owner table and the error flag: one copy, both graph sets point at it
+    RGCN_TRY(dmalloc(c, c->pool, &c->g.owner, R, true));
+    RGCN_TRY(dmalloc(c, c->pool, &c->g.errflag, 1, true));
+    c->g_alt.owner = c->g.owner;
+    c->g_alt.errflag = c->g.errflag;
     std::vector<int32_t> owner(c->R);
     for (int r = 0; r < c->R; ++r) owner[r] = r % c->world;
     RGCN_TRY(to_dev(c, c->g.owner, owner.data(), sizeof(int32_t) * owner.size()));
@@ -741,7 +728,7 @@ rgcn_status rgcn_backward_device(rgcn_ctx* c, const float* dcodes_dev) {
 rgcn_status rgcn_backward(rgcn_ctx* c, const float* dcodes_host, int64_t count) {
   RGCN_NEED(c);
   if (!dcodes_host || count != (int64_t)c->V * c->d) RGCN_FAIL(c, RGCN_ERR_INVALID, "dcodes must be [V,d]");
-  if (!c->dcodes_own) RGCN_TRY(dmalloc(c, &c->dcodes_own, (size_t)count, false));
+  if (!c->dcodes_own) RGCN_TRY(dmalloc(c, c->pool, &c->dcodes_own, (size_t)count, false));
   RGCN_TRY(join_abandoned_side_work(c));      // (unjoined side kernels may read the previous dcodes)
   RGCN_TRY(to_dev(c, c->dcodes_own, dcodes_host, sizeof(float) * (size_t)count));
   return backward_all(c, c->dcodes_own);
@@ -873,7 +860,7 @@ rgcn_status rgcn_rank_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32
   if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_rank_device needs a completed rgcn_forward (test mode on the full graph)");
   // world > 1: the codes are replicated after the last exchange, so ranking needs no collective -- each rank
   // passes its own slice of the queries and the caller concatenates
-  if (c->rank_max <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_rank_reserve first");
+  if (c->ranking.max <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_rank_reserve first");
   if (n == 0) return RGCN_OK;
   return rank_compute(c, x_dev, n, predict_object ? 1 : 0, filter_ptr_dev, filter_idx_dev, raw_rank_dev, filtered_rank_dev);
 }
@@ -892,7 +879,7 @@ rgcn_status rgcn_topk_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32
   if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "this call synchronises with the device: not allowed between rgcn_capture_begin and rgcn_capture_end");
   if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_topk_device needs a completed rgcn_forward (test mode on the full graph)");
   // world > 1: as rgcn_rank_device -- the codes are replicated after the last exchange, every rank answers its own queries
-  if (c->rank_max <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_rank_reserve first");
+  if (c->ranking.max <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_rank_reserve first");
   if (n == 0) return RGCN_OK;
   return topk_compute(c, x_dev, n, predict_object ? 1 : 0, k, exclude_ptr_dev, exclude_idx_dev, topk_idx_dev, topk_energy_dev);
 }
@@ -1123,7 +1110,7 @@ rgcn_status rgcn_capture_begin(rgcn_ctx* c) {
                                        "several GPUs): the devtools build enables it with RGCN_CAPTURE_SHARDED=1");
   RGCN_TRY(sync_all(c));
   if (!c->replay_counter) {
-    RGCN_HIP(c, hipMalloc((void**)&c->replay_counter, sizeof(uint64_t)));
+    RGCN_TRY(dmalloc(c, c->pool, &c->replay_counter, 1, false));
     RGCN_HIP(c, hipMemset(c->replay_counter, 0, sizeof(uint64_t)));
   }
   c->g.ready_in_capture = c->g.free_in_capture = false;
@@ -1310,8 +1297,8 @@ static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* byte
     case RGCN_BUF_PERM_RELATION: *p = c->g.permr; *bytes = (int64_t)2 * c->g.E * 4; return RGCN_OK;
     case RGCN_BUF_MSG_NORM: *p = c->g.m_norm; *bytes = (int64_t)2 * c->g.E * 4; return RGCN_OK;
     case RGCN_BUF_RANK_ENERGIES:
-      if (!c->rank_s) RGCN_FAIL(c, RGCN_ERR_STATE, "no score buffer (rgcn_rank_reserve first)");
-      *p = c->rank_s; *bytes = (int64_t)c->rank_max * c->V * 4; return RGCN_OK;
+      if (!c->ranking.s) RGCN_FAIL(c, RGCN_ERR_STATE, "no score buffer (rgcn_rank_reserve first)");
+      *p = c->ranking.s; *bytes = (int64_t)c->ranking.max * c->V * 4; return RGCN_OK;
     default: RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown buffer id");
   }
 }

@@ -28,18 +28,6 @@ int auto_split_k(int M, int N, int K, bool narrow = false);
 rgcn_status to_host(rgcn_ctx* c, void* host, const void* dev, size_t bytes);
 rgcn_status to_dev(rgcn_ctx* c, void* dev, const void* host, size_t bytes);
 
-template <class T>
-inline rgcn_status dmalloc(rgcn_ctx* c, T** p, size_t n, bool zero = true) {
-  *p = nullptr;
-  hipError_t e = hipMalloc((void**)p, (n ? n : 1) * sizeof(T));
-  if (e != hipSuccess) {
-    c->err = std::string("hipMalloc of ") + std::to_string(n * sizeof(T)) + " bytes: " + hipGetErrorString(e);
-    return e == hipErrorOutOfMemory ? RGCN_ERR_NOMEM : RGCN_ERR_HIP;
-  }
-  if (zero) RGCN_HIP(c, hipMemsetAsync(*p, 0, (n ? n : 1) * sizeof(T), c->stream));
-  return RGCN_OK;
-}
-
 // ---- rgcn_schedule.hip
 rgcn_status fwd_begin(rgcn_ctx* c, int train, uint64_t seed, const uint8_t* masks_host);
 rgcn_status fwd_layer_partial(rgcn_ctx* c, int l);

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/rgcn.h"
+#include "dev_pool.h"
 #include "gemm_plan.h"
 
 namespace rgcn {
@@ -169,12 +170,13 @@ struct LayerBufs {
   // basis kind: W'_dir for Zc.W' (nn) and Dc.W'^T (nt), two groups each.  Split arithmetic only (rgcn_set_gemm_mode 6 / 9).
   void *wself_nn = nullptr, *wself_nt = nullptr, *wrel_nn = nullptr, *wrel_nt = nullptr;
   // BLOCK, destination-major banded layer kernel (block_rows.hip): band-tiled copy of wrel,
-  // [2R][8 bands][ceil(sd*sd/4)][GW lanes][4], allocated at first use
+  // [2R][8 bands][ceil(sd*sd/4)][GW lanes][4], allocated at create wherever block_rows_available() can hold
   float* wtile = nullptr;
   uint64_t wtile_version = ~0ull;
 };
 
 struct GraphBufs {
+  DevPool pool;                 // owns every device buffer of the set (owner / errflag are the context's)
   int32_t* triples = nullptr;   // [maxE,3] (only when the host variant of set_graph is used)
   const int32_t* cur = nullptr; // triples of the current graph (ours or the caller's)
   int64_t E = 0;
@@ -235,6 +237,7 @@ struct GraphBufs {
   hipEvent_t ev_ready = nullptr;   // recorded on the prefetch stream when the set is complete
   hipEvent_t ev_free = nullptr;    // recorded on the main stream when the last step using the set ended
   bool ready_in_capture = false, free_in_capture = false;   // those records belong to the running capture
+  // both sets point at the context's one copy of these (rgcn_ctx::pool)
   int32_t* owner = nullptr;     // [R]
   int32_t* errflag = nullptr;   // device int: nonzero = bad id seen
   bool ready = false;
@@ -242,6 +245,7 @@ struct GraphBufs {
 
 // decoder batch structures (csrc/decoder.hip)
 struct DecoderBufs {
+  DevPool pool;
   int64_t maxN = 0;
   int32_t N = 0;
   int64_t N_total = 0;         // triples of the whole batch when N is one rank's slice of it (denominator of the means)
@@ -274,17 +278,13 @@ struct DecoderBufs {
   double* loss = nullptr;
   uint32_t *keyv_t = nullptr, *keyr_t = nullptr;   // sort scratch (csr_sort.hip)
   uint16_t *tablev = nullptr, *tabler = nullptr;
-  // RGCN_NORM_LOCAL where the vertex key cannot carry the relation: the relation-sorted message list stably sorted by
-  // destination (keyd_s = destinations, permd = positions in the message list), and that sort's scratch
-  uint32_t *keyd = nullptr, *keyd_s = nullptr, *keyd_t = nullptr;
-  int32_t *vald = nullptr, *permd = nullptr;
-  uint16_t* tabled = nullptr;
   hipEvent_t ev_ready = nullptr;
   bool loss_valid = false;
 };
 
 // device neighbourhood sampler (csrc/neighborhood.hip): the training graph and the scratch of one draw
 struct NeighborhoodBufs {
+  DevPool pool;
   int64_t n = 0;                         // training triples
   int32_t* triples = nullptr;            // [n,3]
   // adjacency CSR by vertex, self loops left out: the other endpoint, and the id 2 e + side of the edge END AT THAT
@@ -317,6 +317,8 @@ struct NeighborhoodBufs {
 };
 
 struct OptimizerState {
+  DevPool pool;              // moments, state, shard_sq
+  DevPool part_pool;         // `part` alone: it is the one buffer that grows
   bool configured = false;
   float lr = 0.01f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f, max_norm = 0.f;
   int64_t t = 0;
@@ -328,10 +330,23 @@ struct OptimizerState {
   bool norm_pending = false; // optimizer_norm_partial ran, optimizer_apply has not
 };
 
+// ranking scratch (csrc/ranking.hip)
+struct RankBufs {
+  DevPool pool;
+  float *q = nullptr, *s = nullptr;      // query rows [max,d], energies [max,V]
+  int32_t* bad = nullptr;
+  float* thr = nullptr;                  // per query: the smallest energy whose fp32 sigmoid reaches the gold entity's
+  int64_t max = 0;
+};
+
 }  // namespace rgcn
 
 struct rgcn_ctx {
   rgcn_config cfg;
+  // Owns every device buffer that lives as long as the context: parameters, gradients, activations, slabs, the lazily
+  // allocated masks / giant_slab / dcodes_own / replay_counter, the relation owner table and the error flag.  The graph
+  // sets, the decoder batch, the sampler, the optimizer and the ranking scratch own theirs (their structs' pools).
+  rgcn::DevPool pool;
   int V = 0, R = 0, d = 0, L = 0, nb = 0, sd = 0, kind = 0, B = 0;
   int rank = 0, world = 1;
   bool onehot = false;          // featureless first layer (RGCN_INPUT_ONEHOT): no W_emb / b_emb / H_0, layer 1 is basis_onehot.hip
@@ -435,10 +450,7 @@ struct rgcn_ctx {
   std::vector<hipGraphExec_t> graphs;
   std::vector<hipGraph_t> graph_defs;
   float* giant_slab = nullptr;           // [piece_cap][d] partial sums of giant-row pieces (scratch of one combine launch)
-  float *rank_q = nullptr, *rank_s = nullptr;   // ranking: query rows [max,d], energies [max,V]
-  int32_t* rank_bad = nullptr;
-  float* rank_thr = nullptr;             // per query: the smallest energy whose fp32 sigmoid reaches the gold entity's
-  int64_t rank_max = 0;
+  rgcn::RankBufs ranking;
   float* dcodes_own = nullptr;           // [V,d] staging for the host variant of backward
 
   // comm
@@ -465,6 +477,19 @@ namespace rgcn {
 // ready event, the step-begin marker -- keep the default fence: HIP documents no agent-scope release for SDMA operations.
 inline unsigned order_event_flags(const rgcn_ctx* c, bool kernel_only = false) {
   return hipEventDisableTiming | (kernel_only && c->world == 1 ? hipEventDisableSystemFence : 0u);
+}
+
+// The one way the library allocates device memory: `pool` owns the block (n elements of T, or n bytes through a void**);
+// zero queues a memset of it on the context's current stream.  Out of memory is RGCN_ERR_NOMEM.
+template <class T>
+inline rgcn_status dmalloc(rgcn_ctx* c, DevPool& pool, T** p, size_t n, bool zero) {
+  return pool.alloc(p, n, zero, c->stream, &c->err);
+}
+
+// the partial sums of the giant-row pieces (rgcn_ctx::giant_slab), allocated when a graph with the cut on first meets a layer
+inline rgcn_status giant_slab_ensure(rgcn_ctx* c) {
+  if (c->giant_slab) return RGCN_OK;
+  return dmalloc(c, c->pool, &c->giant_slab, (size_t)c->g.piece_cap * c->d, false);
 }
 
 // Runs the launches inside its scope on side stream k, ordered after everything already queued on
@@ -494,7 +519,7 @@ struct ProfScope {
 };
 
 // ---- graph_prep.hip
-rgcn_status graph_alloc(rgcn_ctx* c, const GraphBufs* share);
+rgcn_status graph_alloc(rgcn_ctx* c, GraphBufs& g);   // fills the set it is handed (owner / errflag: the caller)
 void graph_free(rgcn_ctx* c);
 rgcn_status graph_build(rgcn_ctx* c, const int32_t* triples_dev, int64_t E);
 rgcn_status graph_build_dropout(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int64_t keep, uint64_t seed,

@@ -28,7 +28,7 @@ rgcn_status fwd_begin(rgcn_ctx* c, int train, uint64_t seed, const uint8_t* mask
   c->explicit_masks = false;
   if (train && masks_host) {
     const size_t n = (size_t)c->L * c->V * c->d;
-    if (!c->masks) RGCN_TRY(dmalloc(c, &c->masks, n, false));
+    if (!c->masks) RGCN_TRY(dmalloc(c, c->pool, &c->masks, n, false));
     RGCN_TRY(to_dev(c, c->masks, masks_host, n));
     c->explicit_masks = true;
   }

@@ -82,6 +82,20 @@ enum { RGCN_NORM_INTENDED = 0, RGCN_NORM_TF_AS_EXECUTED = 1, RGCN_NORM_NONE = 2,
  *             been tested).  Any other value of the field: RGCN_ERR_INVALID. */
 enum { RGCN_INPUT_EMBEDDING = 0, RGCN_INPUT_ONEHOT = 1 };
 
+/* Skip connections around the graph-convolution layers (SkipConnections, code/common/model_builder.py:273-309).
+ * NONE    = every layer's result is the next layer's input, what rgcn_create builds.
+ * HIGHWAY = every layer l = 1..L is wrapped in a HighwayLayer (code/extras/highway_layer.py):
+ *               T_l = sigmoid(H_{l-1} . W_highway_l + b_highway_l)
+ *               H_l = T_l * N_l + (1 - T_l) * H_{l-1}        N_l = what layer l returns under RGCN_SKIP_NONE
+ *           (N_l with the layer's relu for l < L, without for l = L; the self-loop dropout stays inside N_l, the highway
+ *           layer applies none).  rgcn_get_codes / rgcn_get_activation(l) / rgcn_codes_device return the post-highway H_l.
+ *           One GPU with embedding input only: with world > 1 or with RGCN_INPUT_ONEHOT rgcn_create_ex returns
+ *           RGCN_ERR_UNSUPPORTED (the reference's one-hot first layer gets no highway layer while layers >= 2 do: not
+ *           built), and rgcn_capture_begin returns RGCN_ERR_UNSUPPORTED on such a context.  Both block forms
+ *           (rgcn_set_fusion), the basis kind, every RGCN_NORM_* and every rgcn_set_gemm_mode work.
+ * Any other value: RGCN_ERR_INVALID. */
+enum { RGCN_SKIP_NONE = 0, RGCN_SKIP_HIGHWAY = 1 };
+
 /* Buffers readable through rgcn_read_buffer (tests / the sharding exchange). */
 enum {
   RGCN_BUF_EXCHANGE = 0,   /* [V,d] buffer a multi-GPU run all-reduces (partial pre-activation / partial dH) */
@@ -101,9 +115,12 @@ enum {
   RGCN_BUF_RANK_ENERGIES = 10,  /* float [reserved queries, V] energies of the last chunk rgcn_rank_device or
                                    rgcn_topk_device scored (the float half of the ranking; the counts and the selection
                                    are integer work on exactly these values) */
-  RGCN_BUF_MSG_NORM = 11        /* float [2E] normalisation of every message, in message-list order: entry j belongs to
+  RGCN_BUF_MSG_NORM = 11,       /* float [2E] normalisation of every message, in message-list order: entry j belongs to
                                    message RGCN_BUF_PERM_RELATION[j] (every RGCN_NORM_* mode).  Sharded context: only
                                    this rank's messages, which come first in the list; the rest is undefined */
+  /* RGCN_SKIP_HIGHWAY contexts, of the layer the last rgcn_forward_layer_finish (or rgcn_forward: layer L) ran: */
+  RGCN_BUF_HIGHWAY_INNER = 12,  /* float [V,d] N_l, the wrapped layer's result */
+  RGCN_BUF_HIGHWAY_GATE = 13    /* float [V,d] T_l, the transform gate */
 };
 
 /*
@@ -129,6 +146,13 @@ typedef struct rgcn_config {
   int32_t input_mode;     /* RGCN_INPUT_* (0 = embedding input, what every earlier caller passed here) */
 } rgcn_config;
 
+/* rgcn_config is full (64 bytes, pinned): what came later is passed beside it.  struct_size must be
+ * sizeof(rgcn_config_ext), else RGCN_ERR_INVALID. */
+typedef struct rgcn_config_ext {
+  int32_t struct_size;
+  int32_t skip_mode;      /* RGCN_SKIP_* */
+} rgcn_config_ext;
+
 /* ---- lifecycle ------------------------------------------------------------------------------ */
 
 int32_t rgcn_abi_version(void);
@@ -137,6 +161,10 @@ int32_t rgcn_abi_version(void);
  * (code/train.py:258,278; code/model.py:93-94).  Weights start as zeros: the host plugin chain
  * draws the reference's numpy initialisers (shared_functions.py:16-29) and pushes them. */
 rgcn_status rgcn_create(const rgcn_config* cfg, rgcn_ctx** out);
+/* The same with the extended settings; ext == NULL: their defaults (RGCN_SKIP_NONE) -- rgcn_create(cfg, out) is
+ * rgcn_create_ex(cfg, NULL, out).  A wrong struct_size or an unknown skip_mode: RGCN_ERR_INVALID; RGCN_SKIP_HIGHWAY
+ * with world > 1 or with RGCN_INPUT_ONEHOT: RGCN_ERR_UNSUPPORTED. */
+rgcn_status rgcn_create_ex(const rgcn_config* cfg, const rgcn_config_ext* ext, rgcn_ctx** out);
 rgcn_status rgcn_destroy(rgcn_ctx* ctx);
 
 /* Text of the last error on this context (ctx == NULL: last error of a failed rgcn_create). */
@@ -156,6 +184,8 @@ rgcn_status rgcn_sync(rgcn_ctx* ctx);
  * RGCN_INPUT_ONEHOT (basis kind; model_builder.py:140-165,277-283, gcn_basis.py:16-24): no W_emb / b_emb, and layer 1 is
  *                      W_f [V,B,d], W_b [V,B,d], C_f [R,B], C_b [R,B], W_self [V,d], b [d]; layers 2..L as above.
  *                      rgcn_param_count / _info / rgcn_set_param / rgcn_get_param / rgcn_get_grad all follow that list.
+ * RGCN_SKIP_HIGHWAY:   behind every layer's b come W_highway<l> [d,d] and b_highway<l> [d] (highway_layer.py; the
+ *                      order Model.get_weights() returns).  The same calls, the optimizer's clip norm and Adam follow.
  * Host layouts are the reference's (row-major, shapes above); the device layout is private.
  * `b` is created but never used by the reference layers: it is stored, never read,
  * and its gradient is all zeros.  The LAST parameter is the decoder's W_relation [EntityCount, d]

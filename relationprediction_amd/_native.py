@@ -19,13 +19,17 @@ ABI_VERSION = 1
 KIND_BLOCK, KIND_BASIS = 0, 1
 NORM_INTENDED, NORM_TF_AS_EXECUTED, NORM_NONE, NORM_LOCAL = 0, 1, 2, 3
 BUF_EXCHANGE, BUF_SELF, BUF_DSELF_EXCHANGE, BUF_INDEG, BUF_OUTDEG, BUF_ROWPTR, BUF_NORM_EXCHANGE, \
-    BUF_DBASIS_EXCHANGE, BUF_PERM_VERTEX, BUF_PERM_RELATION, BUF_RANK_ENERGIES, BUF_MSG_NORM = range(12)
+    BUF_DBASIS_EXCHANGE, BUF_PERM_VERTEX, BUF_PERM_RELATION, BUF_RANK_ENERGIES, BUF_MSG_NORM, BUF_HIGHWAY_INNER, \
+    BUF_HIGHWAY_GATE = range(14)
 
 KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS}
 NORMS = {"intended": NORM_INTENDED, "tf_as_executed": NORM_TF_AS_EXECUTED, "none": NORM_NONE, "local": NORM_LOCAL}
 
 INPUT_EMBEDDING, INPUT_ONEHOT = 0, 1
 INPUT_MODES = {"embedding": INPUT_EMBEDDING, "onehot": INPUT_ONEHOT}
+
+SKIP_NONE, SKIP_HIGHWAY = 0, 1
+SKIP_MODES = {"none": SKIP_NONE, "highway": SKIP_HIGHWAY}
 
 
 def norm_mode_value(norm_mode):
@@ -54,12 +58,17 @@ class RgcnConfig(C.Structure):
     ]
 
 
+class RgcnConfigExt(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("skip_mode", C.c_int32)]
+
+
 _lib = None
 
 _P = C.c_void_p
 _SIGS = {
     "rgcn_abi_version": (C.c_int32, []),
     "rgcn_create": (C.c_int32, [C.POINTER(RgcnConfig), C.POINTER(_P)]),
+    "rgcn_create_ex": (C.c_int32, [C.POINTER(RgcnConfig), C.POINTER(RgcnConfigExt), C.POINTER(_P)]),
     "rgcn_destroy": (C.c_int32, [_P]),
     "rgcn_last_error": (C.c_char_p, [_P]),
     "rgcn_sync": (C.c_int32, [_P]),
@@ -267,10 +276,14 @@ class NeighborhoodSampler:
 class Engine:
     """One rgcn_ctx: the encoder (input layer + L relational graph-convolution layers) on one GPU.
     input_mode "embedding": AffineTransform under the layers (UseInputTransform=Yes); "onehot": no input layer, the
-    first basis layer reads per-entity tables (UseInputTransform=No; include/rgcn.h RGCN_INPUT_ONEHOT)."""
+    first basis layer reads per-entity tables (UseInputTransform=No; include/rgcn.h RGCN_INPUT_ONEHOT).
+    skip "highway": every layer wrapped in a highway layer (SkipConnections=Highway; RGCN_SKIP_HIGHWAY), created through
+    rgcn_create_ex; skip "none" goes through rgcn_create.  create_ex (tests): True = rgcn_create_ex with the extension
+    struct whatever `skip` is, "null" = rgcn_create_ex with a NULL extension."""
 
     def __init__(self, num_entities, num_relations, dim, num_layers, kind, num_bases, keep_prob=0.8,
-                 norm_mode="intended", max_edges=0, device=0, rank=0, world=1, devtools=False, input_mode="embedding"):
+                 norm_mode="intended", max_edges=0, device=0, rank=0, world=1, devtools=False, input_mode="embedding",
+                 skip="none", create_ex=None):
         self.lib = load_library(devtools=devtools)
         self.ctx = None
         cfg = RgcnConfig()
@@ -290,7 +303,14 @@ class Engine:
         cfg.input_mode = INPUT_MODES[input_mode] if isinstance(input_mode, str) else int(input_mode)
         self.cfg = cfg
         ctx = C.c_void_p()
-        st = self.lib.rgcn_create(C.byref(cfg), C.byref(ctx))
+        skip_mode = SKIP_MODES[skip] if isinstance(skip, str) else int(skip)
+        if create_ex == "null":
+            st = self.lib.rgcn_create_ex(C.byref(cfg), None, C.byref(ctx))
+        elif skip_mode == SKIP_NONE and not create_ex:
+            st = self.lib.rgcn_create(C.byref(cfg), C.byref(ctx))
+        else:
+            ext = RgcnConfigExt(C.sizeof(RgcnConfigExt), skip_mode)
+            st = self.lib.rgcn_create_ex(C.byref(cfg), C.byref(ext), C.byref(ctx))
         if st != 0:
             raise RgcnError(st, (self.lib.rgcn_last_error(None) or b"").decode())
         self.ctx = ctx

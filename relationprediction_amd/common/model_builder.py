@@ -1,5 +1,6 @@
 """Plugin registry (reference: code/common/model_builder.py): maps `Encoder.Name` and its flags to a
-chain of components.  Only the hot-path family is built: `Name=gcn_basis` with UseOutputTransform=No and none of the
+chain of components.  Only the hot-path family is built: `Name=gcn_basis` with UseOutputTransform=No, SkipConnections
+None or Highway (every layer wrapped in extras/highway_layer.py; UseInputTransform=Yes only) and none of the
 experimental layer flags -- UseInputTransform=Yes (exactly settings/gcn_block.exp and settings/gcn_basis.exp) or, for
 the basis kind, UseInputTransform=No: the featureless encoder whose first layer reads one-hot entity ids
 (:140-165,277-283); everything else raises NotImplementedError naming SURVEY.md section 2's
@@ -10,6 +11,7 @@ from ..encoders.message_gcns.gcn_basis import BasisGcn
 from ..encoders.message_gcns.gcn_basis_concat import ConcatGcn
 from ..encoders.relation_embedding import RelationEmbedding
 from ..extras.graph_representations import Representation
+from ..extras.highway_layer import HighwayLayer
 
 
 def _flag(settings, key, default="No"):
@@ -33,8 +35,13 @@ def build_encoder(encoder_settings, triples):
                 'PartiallyRandomInput'):
         if _flag(encoder_settings, key) == "Yes":
             raise NotImplementedError("%s=Yes selects a reference variant outside the hot path" % key)
-    if _flag(encoder_settings, 'SkipConnections', 'None') != 'None':
+    skip = _flag(encoder_settings, 'SkipConnections', 'None')
+    if skip not in ('None', 'Highway'):
         raise NotImplementedError("SkipConnections other than None")
+    if skip == 'Highway' and input_transform == "No":
+        raise NotImplementedError("SkipConnections=Highway with UseInputTransform=No is the one-hot follow-up: the "
+                                  "reference gives the one-hot first layer no highway layer while the layers above it "
+                                  "get one (model_builder.py:304-305), which the engine does not build")
 
     graph = Representation(triples, encoder_settings)
     input_shape = [int(encoder_settings['EntityCount']), int(encoder_settings['InternalEncoderDimension'])]
@@ -58,9 +65,15 @@ def build_encoder(encoder_settings, triples):
 def apply_basis_gcn(encoder_settings, encoding, internal_shape, layers, onehot_first=False):
     concat = 'Concatenation' in encoder_settings and encoder_settings['Concatenation'] == "Yes"
     layer_class = ConcatGcn if concat else BasisGcn
+    highway = _flag(encoder_settings, 'SkipConnections', 'None') == 'Highway'
     for layer in range(layers):
-        encoding = layer_class(internal_shape, encoder_settings, next_component=encoding,
-                               onehot_input=onehot_first and layer == 0, use_nonlinearity=layer < layers - 1)
+        onehot_input = onehot_first and layer == 0
+        new_encoding = layer_class(internal_shape, encoder_settings, next_component=encoding,
+                                   onehot_input=onehot_input, use_nonlinearity=layer < layers - 1)
+        if highway and not onehot_input:       # (model_builder.py:304-305)
+            encoding = HighwayLayer(internal_shape, next_component=new_encoding, next_component_2=encoding)
+        else:
+            encoding = new_encoding
     return encoding
 
 

@@ -366,6 +366,13 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     if ((int64_t)f.num_entities * f.num_bases * (int64_t)f.dim >= ((int64_t)1 << 31))
       RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_INPUT_ONEHOT: EntityCount x NumberOfBasisFunctions x dimension must be below 2^31");
   }
+  if (c->highway) {
+    if (f.world > 1)
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_SKIP_HIGHWAY on a sharded context (the highway passes have no exchange points)");
+    if (c->onehot)
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_SKIP_HIGHWAY with RGCN_INPUT_ONEHOT (in the reference the one-hot first layer "
+                                         "gets no highway layer while the layers above it do: not built)");
+  }
   // the library's radix sort takes keys below 2^24 (csr_sort.hip): vertex ids and directed-relation ids
   if (c->V >= (1 << 24) || 2 * (int64_t)c->R >= (1 << 24))
     RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "EntityCount and 2 x RelationCount must be below 2^24 (sort key range of this build)");
@@ -507,6 +514,14 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     add_param(c, "W_self" + sl, {(int64_t)d, (int64_t)d}, lb.wself, lb.gwself, LAYOUT_PLAIN);
     add_param(c, "b" + sl, {(int64_t)d}, lb.bias, lb.gbias, LAYOUT_PLAIN);
     c->params.back().no_grad = true;
+    if (c->highway) {      // HighwayLayer.local_get_weights (highway_layer.py): [W, b], behind the layer it wraps
+      RGCN_TRY(dmalloc(c, c->pool, &lb.whw, d * d, true));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.gwhw, d * d, true));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.bhw, d, true));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.gbhw, d, true));
+      add_param(c, "W_highway" + sl, {(int64_t)d, (int64_t)d}, lb.whw, lb.gwhw, LAYOUT_PLAIN);
+      add_param(c, "b_highway" + sl, {(int64_t)d}, lb.bhw, lb.gbhw, LAYOUT_PLAIN);
+    }
   }
   RGCN_TRY(dmalloc(c, c->pool, &c->w_rel, Vd, true));
   RGCN_TRY(dmalloc(c, c->pool, &c->g_rel, Vd, true));
@@ -514,6 +529,16 @@ static rgcn_status create_impl(rgcn_ctx* c) {
   c->H.assign(c->L + 1, nullptr);
   for (int l = c->onehot ? 1 : 0; l <= c->L; ++l) RGCN_TRY(dmalloc(c, c->pool, &c->H[l], Vd, true));   // (one-hot input: no H_0)
   RGCN_TRY(dmalloc(c, c->pool, &c->self_buf, Vd, true));
+  if (c->highway) {
+    c->hw_N.assign(c->L + 1, nullptr);
+    c->hw_T.assign(c->L + 1, nullptr);
+    for (int l = 1; l <= c->L; ++l) {
+      RGCN_TRY(dmalloc(c, c->pool, &c->hw_N[l], Vd, true));
+      RGCN_TRY(dmalloc(c, c->pool, &c->hw_T[l], Vd, true));
+    }
+    for (int k = 0; k < 2; ++k) RGCN_TRY(dmalloc(c, c->pool, &c->hw_dz[k], Vd, true));
+    RGCN_TRY(dmalloc(c, c->pool, &c->hw_carry, Vd, true));
+  }
   if (c->world > 1) RGCN_TRY(dmalloc(c, c->pool, &c->exch, Vd, true));
   for (int k = 0; k < 2; ++k) {
     RGCN_TRY(dmalloc(c, c->pool, &c->dbuf[k], Vd, true));
@@ -594,12 +619,23 @@ extern "C" {
 
 int32_t rgcn_abi_version(void) { return RGCN_ABI_VERSION; }
 
-rgcn_status rgcn_create(const rgcn_config* cfg, rgcn_ctx** out) {
+rgcn_status rgcn_create(const rgcn_config* cfg, rgcn_ctx** out) { return rgcn_create_ex(cfg, nullptr, out); }
+
+rgcn_status rgcn_create_ex(const rgcn_config* cfg, const rgcn_config_ext* ext, rgcn_ctx** out) {
   if (!cfg || !out) { set_global_error("rgcn_create: NULL argument"); return RGCN_ERR_INVALID; }
   *out = nullptr;
+  if (ext && ext->struct_size != (int32_t)sizeof(rgcn_config_ext)) {
+    set_global_error("rgcn_create_ex: rgcn_config_ext::struct_size is not sizeof(rgcn_config_ext)");
+    return RGCN_ERR_INVALID;
+  }
+  if (ext && ext->skip_mode != RGCN_SKIP_NONE && ext->skip_mode != RGCN_SKIP_HIGHWAY) {
+    set_global_error("rgcn_create_ex: unknown skip_mode (0: RGCN_SKIP_NONE, 1: RGCN_SKIP_HIGHWAY)");
+    return RGCN_ERR_INVALID;
+  }
   rgcn_ctx* c = new (std::nothrow) rgcn_ctx();
   if (!c) { set_global_error("out of host memory"); return RGCN_ERR_NOMEM; }
   c->cfg = *cfg;
+  c->highway = ext && ext->skip_mode == RGCN_SKIP_HIGHWAY;
   rgcn_status s = create_impl(c);
   if (s != RGCN_OK) {
     set_global_error(c->err);
@@ -943,7 +979,8 @@ static rgcn_status train_step_tail(rgcn_ctx* c, const int32_t* X_dev, const floa
   // one GPU: the decoder's entity-gradient kernel also writes dL/dcodes * dropout_L, the operand of the top layer's
   // self-loop GEMMs (a sharded run scales after the all-reduce of the partial dL/dcodes, in bwd_begin)
   const DropSpec top_drop = make_drop(c, c->L, true);
-  float* ds_ready = (c->world == 1 && top_drop.mode != DROP_NONE) ? c->dsbuf[c->L & 1] : nullptr;
+  // (a highway context forms dS_L itself, from G_L T_L: bwd_layer_partial)
+  float* ds_ready = (c->world == 1 && !c->highway && top_drop.mode != DROP_NONE) ? c->dsbuf[c->L & 1] : nullptr;
   RGCN_TRY(decoder_compute(c, c->H[c->L], Y_loc, reg_param, ds_ready, &top_drop));
   if (c->world > 1) {
     RGCN_TRY(stream_join(c, 2));    // the relation gradient's reduce ran on its own side stream: it is all-reduced too
@@ -1105,6 +1142,9 @@ rgcn_status rgcn_capture_begin(rgcn_ctx* c) {
   // path is exercised with device-side stand-in collectives of several ranks on ONE GPU only
   // (tests/test_gpu_multiprocess.py::test_captured_sharded_train_step); real librccl kernels inside a capture have never
   // run here (no multi-GPU box), so it stays EXPERIMENTAL and opt-in: RGCN_CAPTURE_SHARDED=1.
+  if (c->highway)
+    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "rgcn_capture_begin: capture on an RGCN_SKIP_HIGHWAY context is not supported (a captured "
+                                       "highway step has never been replayed against a reference)");
   if (c->world > 1 && knob("RGCN_CAPTURE_SHARDED", 0) != 1)
     RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "capture on a sharded context is experimental (never run against real RCCL on "
                                        "several GPUs): the devtools build enables it with RGCN_CAPTURE_SHARDED=1");
@@ -1299,6 +1339,11 @@ static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* byte
     case RGCN_BUF_RANK_ENERGIES:
       if (!c->ranking.s) RGCN_FAIL(c, RGCN_ERR_STATE, "no score buffer (rgcn_rank_reserve first)");
       *p = c->ranking.s; *bytes = (int64_t)c->ranking.max * c->V * 4; return RGCN_OK;
+    case RGCN_BUF_HIGHWAY_INNER:
+    case RGCN_BUF_HIGHWAY_GATE:
+      if (!c->highway) RGCN_FAIL(c, RGCN_ERR_STATE, "not an RGCN_SKIP_HIGHWAY context");
+      if (c->hw_last < 1) RGCN_FAIL(c, RGCN_ERR_STATE, "no rgcn_forward_layer_finish has run");
+      *p = which == RGCN_BUF_HIGHWAY_INNER ? c->hw_N[c->hw_last] : c->hw_T[c->hw_last]; *bytes = Vd; return RGCN_OK;
     default: RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown buffer id");
   }
 }

@@ -173,6 +173,8 @@ struct LayerBufs {
   // [2R][8 bands][ceil(sd*sd/4)][GW lanes][4], allocated at create wherever block_rows_available() can hold
   float* wtile = nullptr;
   uint64_t wtile_version = ~0ull;
+  // highway context (RGCN_SKIP_HIGHWAY): the gate's weight [d,d] and bias [d] (highway_layer.py) and their gradients
+  float *whw = nullptr, *gwhw = nullptr, *bhw = nullptr, *gbhw = nullptr;
 };
 
 struct GraphBufs {
@@ -349,6 +351,13 @@ struct rgcn_ctx {
   rgcn::DevPool pool;
   int V = 0, R = 0, d = 0, L = 0, nb = 0, sd = 0, kind = 0, B = 0;
   int rank = 0, world = 1;
+  // highway skip connections around every layer (rgcn_config_ext::skip_mode == RGCN_SKIP_HIGHWAY; highway.hip; one GPU,
+  // embedding input): the layers write N_l, the highway pass T_l and H_l; all four buffers exist on such a context only
+  bool highway = false;
+  std::vector<float*> hw_N, hw_T;         // [1..L] N_l and T_l, [V,d] each, kept for the backward pass
+  float* hw_dz[2] = {nullptr, nullptr};   // dZ_l, ping-pong like D / dS (layer 2's dW_hw GEMM may trail beside layer 1)
+  float* hw_carry = nullptr;              // G_l * (1 - T_l)
+  int hw_last = 0;                        // the layer the last fwd_layer_finish ran (RGCN_BUF_HIGHWAY_INNER / _GATE)
   bool onehot = false;          // featureless first layer (RGCN_INPUT_ONEHOT): no W_emb / b_emb / H_0, layer 1 is basis_onehot.hip
   int row_lo = 0, row_hi = 0;   // row shard of this rank: [rank * shard_rows, +shard_rows) cut at V
   int shard_rows = 0;           // ceil(V / world): equal chunks for the reduce-scatter / all-gather
@@ -638,6 +647,16 @@ rgcn_status relu_copy(rgcn_ctx* c, const float* in, float* out, int64_t n, int r
 rgcn_status materialize_mask(rgcn_ctx* c, const DropSpec& ds, uint8_t* out_dev, int64_t n);
 
 DropSpec make_drop(const rgcn_ctx* c, int layer, bool active);
+
+// ---- highway.hip: the [V,d] passes of a highway context (the gate's three GEMMs are gemm_f32 calls of the schedule)
+// T holds Z = H_in . W_hw on entry: T = sigmoid(Z + b), H = T * N + (1 - T) * H_in
+rgcn_status highway_forward(rgcn_ctx* c, float* T, const float* b, const float* N, const float* Hin, float* H);
+// D = G T relu'(N) (relu != 0), dS = D * dropout (dS != nullptr), dZ = G (N - H_in) T (1 - T), carry = G (1 - T); leaves
+// *nparts column partials of dZ in colsum_scratch(c) (column_sum_finish adds them).  D may be G.
+rgcn_status highway_backward(rgcn_ctx* c, const float* G, const float* T, const float* N, const float* Hin, float* D,
+                             float* dS, float* dZ, float* carry, int relu, const DropSpec& drop, int* nparts);
+// out += gz + carry; gate != nullptr: out *= (gate > 0) and *nparts column partials of out in colsum_scratch(c)
+rgcn_status highway_join(rgcn_ctx* c, float* out, const float* gz, const float* carry, const float* gate, int* nparts);
 
 // ---- decoder.hip / optimizer.hip
 rgcn_status negative_sample(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int rate, uint64_t seed, int32_t* X,

@@ -145,7 +145,8 @@ rgcn_status fwd_layer_partial(rgcn_ctx* c, int l) {
   const float* Hin = c->H[l - 1];
   const int d = c->d, V = c->V;
   const int lo = c->world > 1 ? c->row_lo : 0, hi = c->world > 1 ? c->row_hi : V;
-  float* dst = c->world > 1 ? c->exch : c->H[l];
+  // highway context: the layer's result is N_l; fwd_layer_finish forms H_l from it
+  float* dst = c->world > 1 ? c->exch : c->highway ? c->hw_N[l] : c->H[l];
   const double Mmsg = 2.0 * c->g.E / c->world;
   RGCN_TRY(refresh_weight_fragments(c));
   bool form_h0 = false;
@@ -231,6 +232,14 @@ rgcn_status fwd_layer_finish(rgcn_ctx* c, int l) {
   if (l < 1 || l > c->L) RGCN_FAIL(c, RGCN_ERR_INVALID, "layer out of range");
   if (c->world > 1)
     RGCN_TRY(relu_copy(c, c->exch, c->H[l], (int64_t)c->V * c->d, l < c->L ? 1 : 0));
+  if (c->highway) {
+    // T_l = sigmoid(H_{l-1} . W_hw + b_hw), H_l = T_l N_l + (1 - T_l) H_{l-1}: the gate product lands in T_l's buffer and
+    // the pass turns it into T_l in place.  W_hw has no fragment table: the plan picks a kernel that splits it per tile.
+    const int d = c->d;
+    RGCN_TRY(gemm_f32(c, "gemm_highway_fwd", true, false, c->V, d, d, c->H[l - 1], d, c->layers[l].whw, d, c->hw_T[l], d, 1));
+    RGCN_TRY(highway_forward(c, c->hw_T[l], c->layers[l].bhw, c->hw_N[l], c->H[l - 1], c->H[l]));
+    c->hw_last = l;
+  }
   if (l == c->L) c->fwd_done = true;
   return RGCN_OK;
 }
@@ -242,7 +251,7 @@ rgcn_status fwd_layer_finish(rgcn_ctx* c, int l) {
 // pass that starts while the previous one's side kernels are unjoined queues its own behind them IN STREAM ORDER: the
 // slabs and the gradients they share need no event.
 static bool deferred_schedule(const rgcn_ctx* c) {
-  return c->defer_end_joins && c->kind == RGCN_KIND_BLOCK && c->fuse == 1 && block_rows_available(c) && c->world == 1 &&
+  return !c->highway && c->defer_end_joins && c->kind == RGCN_KIND_BLOCK && c->fuse == 1 && block_rows_available(c) && c->world == 1 &&
          c->g.E <= 65536 && c->use_aux && !c->capturing && c->L >= 2 && c->stream == c->main_stream;
 }
 
@@ -258,6 +267,10 @@ rgcn_status bwd_begin(rgcn_ctx* c, const float* dcodes_dev, const float* ds_read
   if (!(c->side_state == rgcn_ctx::SIDE_READS_JOINED && deferred_schedule(c))) RGCN_TRY(join_abandoned_side_work(c));
   c->bwd_layer = c->L;
   c->bwd_D = dcodes_dev;
+  if (c->highway) {      // dcodes is G_L; D_L and dS_L are the highway pass's (bwd_layer_partial), a ready-made dS is of no use
+    c->bwd_dS = nullptr;
+    return RGCN_OK;
+  }
   DropSpec ds = make_drop(c, c->L, true);
   if (ds.mode != DROP_NONE && ds_ready != nullptr) {
     c->bwd_dS = ds_ready;
@@ -300,7 +313,26 @@ rgcn_status bwd_layer_partial(rgcn_ctx* c, int l) {
   a.base = c->self_buf; a.msg = nullptr; a.row_ptr = nullptr; a.long_rows = nullptr; a.nlong = nullptr;
   a.V = V; a.d = d; a.relu = 0; a.row_lo = lo; a.row_hi = hi;
   a.drop = make_drop(c, l, false);
-  if (c->world == 1) {
+  if (c->highway) {
+    // The epilogue leaves the RAW dH_{l-1}: relu' belongs to N_{l-1}, not to H_{l-1}, and applies to the sum with the
+    // highway terms -- the gate, the dropout copy and (l = 1) relu'(H_0) with db_emb's column sums are highway.hip's.
+    a.out = (l - 1 == 0) ? c->g_emb : c->dbuf[(l - 1) & 1];
+    a.out2 = nullptr; a.gate = nullptr; a.drop2 = make_drop(c, l - 1, false);
+    // G_l (bwd_D; l < L: in dbuf[l & 1], turned into D_l in place) -> D_l, dS_l, dZ_l, the carry, db_hw's partials
+    const DropSpec dl = make_drop(c, l, true);
+    float* dS = dl.mode != DROP_NONE ? c->dsbuf[l & 1] : nullptr;
+    int nparts = 0;
+    RGCN_TRY(highway_backward(c, c->bwd_D, c->hw_T[l], c->hw_N[l], Hin, c->dbuf[l & 1], dS, c->hw_dz[l & 1], c->hw_carry,
+                              l < c->L ? 1 : 0, dl, &nparts));
+    RGCN_TRY(column_sum_finish(c, lb.gbhw, nparts, d));
+    c->bwd_D = c->dbuf[l & 1];
+    c->bwd_dS = dS ? dS : c->dbuf[l & 1];
+    {   // dW_hw = H_{l-1}^T . dZ (split-K): side stream 1, AHEAD of the layer's dW_self there -- the two share the slabs
+      StreamScope side(c, 1);
+      RGCN_TRY(gemm_f32(c, "gemm_highway_dw", false, false, d, d, V, Hin, d, c->hw_dz[l & 1], d, lb.gwhw, d,
+                        auto_split_k(d, d, V, narrow_dw)));
+    }
+  } else if (c->world == 1) {
     a.out = (l - 1 == 0) ? c->g_emb : c->dbuf[(l - 1) & 1];
     a.colsum = (l - 1 == 0) ? 1 : 0;       // db_emb = the column sums of dL/dH0 * relu'(H0): partials from the kernel that writes it
     a.drop2 = make_drop(c, l - 1, l - 1 >= 1);
@@ -439,6 +471,14 @@ rgcn_status bwd_layer_partial(rgcn_ctx* c, int l) {
                       basis_unit_share(c)));
     RGCN_TRY(basis_dcoef(c, l, Hin, c->msgbuf2));
     RGCN_TRY(basis_backward_gather(c, l, c->msgbuf2, a, true));
+  }
+  if (c->highway) {
+    // G_{l-1} = raw dH_{l-1} + dZ_l . W_hw^T + G_l (1 - T_l), in place over the raw rows; the product goes through the
+    // self-loop buffer, free since the epilogue above read it
+    RGCN_TRY(gemm_f32(c, "gemm_highway_dh", true, true, V, d, d, c->hw_dz[l & 1], d, lb.whw, d, c->self_buf, d, 1));
+    int nparts = 0;
+    RGCN_TRY(highway_join(c, a.out, c->self_buf, c->hw_carry, l == 1 ? Hin : nullptr, &nparts));
+    if (l == 1) c->colsum_parts = nparts;      // db_emb: bwd_end adds them
   }
   // the dW_self GEMM must be done before the next layer overwrites its dS operand / the caller
   // all-reduces gwself

@@ -7,8 +7,16 @@ mode (:60-64), combine.  All of it runs inside the engine (rgcn_forward); a laye
 contributes its hyper-parameters and weights and reads back its own activation.
 """
 from ...extras.graph_representations import Representation
+from ...extras.highway_layer import HighwayLayer
 from ...model import Model
 from ...runtime import EncoderRuntime
+
+
+def _under(comp):
+    """what lies under a layer of the stack: its next_component, or -- SkipConnections=Highway -- what that highway layer
+    wraps (the next graph-convolution layer down)"""
+    below = comp.next_component
+    return below.next_component if isinstance(below, HighwayLayer) else below
 
 
 class MessageGcn(Model):
@@ -33,10 +41,10 @@ class MessageGcn(Model):
 
     def _runtime(self):
         """The runtime shared by the whole stack; built on first use from the TOP layer's view."""
-        below, comp = [self], self.next_component
+        below, comp = [self], _under(self)
         while isinstance(comp, MessageGcn):
             below.append(comp)
-            comp = comp.next_component
+            comp = _under(comp)
         # under the stack: the input layer and the graph, or (UseInputTransform=No) the graph itself
         affine, rep = (None, comp) if isinstance(comp, Representation) else (comp, comp.next_component)
         if rep.runtime is None:
@@ -46,16 +54,16 @@ class MessageGcn(Model):
             layers, c = [], top
             while isinstance(c, MessageGcn):
                 layers.append(c)
-                c = c.next_component
+                c = _under(c)
             rep.runtime = EncoderRuntime(list(reversed(layers)), affine, rep)
         return rep.runtime
 
     def local_initialize_train(self):
         self.create_variables()
         # the first layer initialised is the outermost one (model.py:156-164): remember it
-        comp = self.next_component
+        comp = _under(self)
         while isinstance(comp, MessageGcn):
-            comp = comp.next_component
+            comp = _under(comp)
         rep = comp if isinstance(comp, Representation) else comp.next_component
         if not hasattr(rep, '_top_gcn'):
             rep._top_gcn = self

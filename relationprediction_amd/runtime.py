@@ -32,6 +32,14 @@ class EncoderRuntime(object):
         if affine is None and self.kind != "basis":
             raise NotImplementedError("UseInputTransform=No with Concatenation=Yes: the reference's one-hot branch of "
                                       "ConcatGcn cannot execute (gcn_basis_concat.py:18-19,42-46)")
+        # SkipConnections=Highway: every layer carries its wrapper (extras/highway_layer.py), or none does
+        self.highways = [getattr(l, 'highway_layer', None) for l in layers]
+        if any(h is None for h in self.highways) and any(h is not None for h in self.highways):
+            raise NotImplementedError("highway layers around some graph-convolution layers only (the reference's one-hot "
+                                      "first layer gets none, model_builder.py:304: not built)")
+        self.highway = self.highways[0] is not None
+        if self.highway and affine is None:
+            raise NotImplementedError("SkipConnections=Highway with UseInputTransform=No (the one-hot follow-up)")
         s = top.settings
         self.V, self.R = top.entity_count, top.relation_count
         self.d = int(top.shape[1])
@@ -44,7 +52,8 @@ class EncoderRuntime(object):
         self.engine = _native.Engine(self.V, self.R, self.d, len(layers), self.kind, top.n_coefficients,
                                      keep_prob=top.dropout_keep_probability, norm_mode=norm,
                                      max_edges=max_edges, device=device,
-                                     input_mode="embedding" if affine is not None else "onehot")
+                                     input_mode="embedding" if affine is not None else "onehot",
+                                     skip="highway" if self.highway else "none")
         self._state = None        # (graph version, mode) of the activations held by the engine
         self._dev = {}            # persistent device buffers of the fused train step (name -> DeviceBuffer)
         self._dec_reserved = 0
@@ -58,7 +67,7 @@ class EncoderRuntime(object):
             affine.b.bind(*self._accessors("b_emb"))
         for i, l in enumerate(layers, start=1):
             l.layer_index = i
-            for var, base in l.engine_variables():
+            for var, base in l.engine_variables() + (self.highways[i - 1].engine_variables() if self.highway else []):
                 var.bind(*self._accessors("%s%d" % (base, i)))
 
     def _accessors(self, name):

@@ -1,0 +1,188 @@
+"""float64 numpy restatement of the encoder under SkipConnections=Highway (RGCN_SKIP_HIGHWAY; reference:
+code/extras/highway_layer.py around the layers of code/common/model_builder.py:273-309).  TEST INFRASTRUCTURE.
+
+    T_l = sigmoid(H_{l-1} . W_highway_l + b_highway_l)
+    H_l = T_l * N_l + (1 - T_l) * H_{l-1}          N_l = layer l's result without the skip connection (helpers.py's
+                                                   one-layer float64 functions: relu for l < L, none for l = L)
+
+Reverse mode, given G_l = dL/dH_l (G_L = dcodes):
+
+    D_l  = G_l T_l relu'(N_l)   (l = L: G_L T_L)        dS_l = D_l * dropout_l
+    dZ_l = G_l (N_l - H_{l-1}) T_l (1 - T_l)            dW_highway_l = H_{l-1}^T dZ_l, db_highway_l = column sums of dZ_l
+    G_{l-1} = [dH_{l-1} of layer l from D_l, dS_l] + dZ_l W_highway_l^T + G_l (1 - T_l)
+    dW_emb = G_0 relu'(H_0), db_emb = its column sums
+
+backward() takes the activations H_l, the inner results N_l and the gates T_l as inputs, so that it can be evaluated at
+an engine's own forward pass (its own relu gates)."""
+import numpy as np
+
+import oracle
+from helpers import chunked_basis_layer_float64, chunked_block_layer_float64
+
+F64 = np.float64
+
+
+def weight_names(kind, L):
+    """rgcn_param_info names of a highway context = Model.get_weights() order of the reference"""
+    per = ["W_f", "W_b", "W_self", "b"] if kind == "block" else ["W_f", "W_b", "C_f", "C_b", "W_self", "b"]
+    names = ["W_emb", "b_emb"]
+    for l in range(1, L + 1):
+        names += ["%s%d" % (n, l) for n in per] + ["W_highway%d" % l, "b_highway%d" % l]
+    return names + ["W_relation"]
+
+
+def init_params(V, R, d, L, kind, nb, rng):
+    """the reference's creation order (outermost component first, model.py:156-164): RelationEmbedding, then per layer
+    L..1 the highway layer's W (b = ones draws nothing) and the layer's own draws, then AffineTransform"""
+    from relationprediction_amd.common.shared_functions import glorot_variance
+    p = {"W_relation": rng.randn(V, d).astype(np.float32)}
+    for l in range(L, 0, -1):
+        p["W_highway%d" % l] = rng.normal(0, glorot_variance([d, d]), size=(d, d)).astype(np.float32)
+        p["b_highway%d" % l] = np.ones(d, dtype=np.float32)
+        if kind == "block":
+            sd = d // nb
+            var = glorot_variance([R, sd])
+            for n in ("W_f", "W_b"):
+                p["%s%d" % (n, l)] = rng.normal(0, var, size=(R, nb, sd, sd)).astype(np.float32)
+            p["W_self%d" % l] = rng.normal(0, var, size=(d, d)).astype(np.float32)
+        else:
+            var = glorot_variance([d, d])
+            for n in ("W_f", "W_b"):
+                p["%s%d" % (n, l)] = rng.normal(0, var, size=(d, nb, d)).astype(np.float32)
+            p["W_self%d" % l] = rng.normal(0, var, size=(d, d)).astype(np.float32)
+            for n in ("C_f", "C_b"):
+                p["%s%d" % (n, l)] = rng.normal(0, 1, size=(R, nb)).astype(np.float32)
+        p["b%d" % l] = np.zeros(d, dtype=np.float32)
+    p["W_emb"] = rng.normal(0, glorot_variance([V, d]), size=(V, d)).astype(np.float32)
+    p["b_emb"] = np.zeros(d, dtype=np.float32)
+    return p
+
+
+def make_case(V, R, d, L, kind, nb, triples, seed=0, keep=0.8):
+    """seeded weights (biases made non-trivial), masks and an upstream gradient for the given graph"""
+    rng = np.random.RandomState(seed)
+    p = init_params(V, R, d, L, kind, nb, rng)
+    p["b_emb"] = (rng.randn(d) * 0.05).astype(np.float32)
+    for l in range(1, L + 1):
+        p["b_highway%d" % l] = (1.0 + rng.randn(d) * 0.5).astype(np.float32)
+    masks = [(rng.rand(V, d) < keep).astype(np.uint8) for _ in range(L)]
+    dcodes = (rng.randn(V, d) * 1e-1).astype(np.float32)
+    return {"V": V, "R": R, "d": d, "L": L, "kind": kind, "nb": nb, "params": p, "masks": masks, "dcodes": dcodes,
+            "triples": np.asarray(triples, dtype=np.int32).reshape(-1, 3), "keep": keep}
+
+
+def sigmoid(z):
+    return 1.0 / (1.0 + np.exp(-z))
+
+
+def _layer(kind):
+    return chunked_block_layer_float64 if kind == "block" else chunked_basis_layer_float64
+
+
+def forward(kind, params, triples, V, L, mode="train", keep=0.8, masks=None, norm_mode=None):
+    """(H [0..L], N [None, 1..L], T [None, 1..L]) in float64"""
+    p = {k: np.asarray(v, dtype=F64) for k, v in params.items()}
+    H = [np.maximum(p["W_emb"] + p["b_emb"], 0.0)]
+    N, T = [None], [None]
+    for l in range(1, L + 1):
+        n = _layer(kind)(p, l, L, H[l - 1], triples, V, mode=mode, keep=keep,
+                         mask=masks[l - 1] if mode == "train" else None, norm_mode=norm_mode)
+        t = sigmoid(H[l - 1] @ p["W_highway%d" % l] + p["b_highway%d" % l])
+        N.append(n)
+        T.append(t)
+        H.append(t * n + (1.0 - t) * H[l - 1])
+    return H, N, T
+
+
+def forward_float32(kind, params, triples, V, L, mode="train", keep=0.8, masks=None):
+    """forward() once more with every array and every operation in numpy float32 (per-edge messages, np.add.at for the
+    scatter; 'intended' normalisation).  Its distance from forward() on the same inputs is the error scale of a correct
+    fp32 evaluation in ONE summation order: what the large-shape GPU test sizes its tolerance with."""
+    f32 = np.float32
+    p = {k: np.asarray(v, dtype=f32) for k, v in params.items()}
+    s, r, o = oracle.split_graph(triples)
+    E = len(s)
+    n_f = np.asarray(oracle.incidence_values(o, V, oracle.NORM_INTENDED), dtype=f32)
+    n_b = np.asarray(oracle.incidence_values(s, V, oracle.NORM_INTENDED), dtype=f32)
+    H = [np.maximum(p["W_emb"] + p["b_emb"], f32(0))]
+    N, T = [None], [None]
+    for l in range(1, L + 1):
+        Hin = H[l - 1]
+        pre = Hin @ p["W_self%d" % l]
+        if mode == "train":
+            pre = pre * (np.asarray(masks[l - 1], dtype=f32) * (f32(1) / f32(keep)))
+        for tag, rows_in, rows_out, nrm in (("f", s, o, n_f), ("b", o, s, n_b)):
+            W = p["W_%s%d" % (tag, l)]
+            if not E:
+                continue
+            if kind == "block":
+                Rr, nb, sd, _ = W.shape
+                m = np.einsum("ebij,ebj->ebi", W[r], Hin[rows_in].reshape(E, nb, sd)).reshape(E, nb * sd)
+            else:
+                d_in, B, d_out = W.shape
+                m = np.einsum("ebk,eb->ek", (Hin[rows_in] @ W.reshape(d_in, B * d_out)).reshape(E, B, d_out),
+                              p["C_%s%d" % (tag, l)][r])
+            np.add.at(pre, rows_out, m * nrm[:, None])
+        n = np.maximum(pre, f32(0)) if l < L else pre
+        t = f32(1) / (f32(1) + np.exp(-(Hin @ p["W_highway%d" % l] + p["b_highway%d" % l])))
+        h = t * n + (f32(1) - t) * Hin
+        assert n.dtype == t.dtype == h.dtype == f32
+        N.append(n)
+        T.append(t)
+        H.append(h)
+    return H, N, T
+
+
+def _layer_backward(kind, p, l, Hin, D, dS, triples, V, norm_mode):
+    """gradients of layer l's own weights from D = dL/dpre_l and dS = D * dropout_l, and the raw dL/dH_{l-1} through the
+    layer (no relu', no dropout copy): tf.gradients of gcn_basis_concat.py:35-83 / gcn_basis.py:39-88"""
+    norm_mode = oracle.NORM_INTENDED if norm_mode is None else norm_mode
+    s, r, o = oracle.split_graph(triples)
+    E = len(s)
+    n_f = np.asarray(oracle.incidence_values(o, V, norm_mode), dtype=F64)
+    n_b = np.asarray(oracle.incidence_values(s, V, norm_mode), dtype=F64)
+    g = {"W_self%d" % l: Hin.T @ dS, "b%d" % l: np.zeros(D.shape[1])}
+    dHin = dS @ p["W_self%d" % l].T
+    for tag, rows_in, rows_out, nrm in (("f", s, o, n_f), ("b", o, s, n_b)):
+        W = p["W_%s%d" % (tag, l)]
+        gW = np.zeros_like(W)
+        gm = D[rows_out] * nrm[:, None] if E else np.zeros((0, D.shape[1]))
+        if kind == "block":
+            R, nb, sd, _ = W.shape
+            g3, x3 = gm.reshape(E, nb, sd), Hin[rows_in].reshape(E, nb, sd)
+            np.add.at(gW, r, np.einsum("ebi,ebj->ebij", g3, x3))
+            np.add.at(dHin, rows_in, np.einsum("ebij,ebi->ebj", W[r], g3).reshape(E, nb * sd))
+        else:
+            C = p["C_%s%d" % (tag, l)]
+            gC = np.zeros_like(C)
+            d_in, B, d_out = W.shape
+            gterms = (C[r][:, :, None] * gm[:, None, :]).reshape(E, B * d_out)
+            x = Hin[rows_in]
+            terms = (x @ W.reshape(d_in, B * d_out)).reshape(E, B, d_out)
+            np.add.at(gC, r, np.einsum("ebk,ek->eb", terms, gm))
+            gW += (x.T @ gterms).reshape(W.shape)
+            np.add.at(dHin, rows_in, gterms @ W.reshape(d_in, B * d_out).T)
+            g["C_%s%d" % (tag, l)] = gC
+        g["W_%s%d" % (tag, l)] = gW
+    return g, dHin
+
+
+def backward(kind, params, triples, V, L, H, N, T, dcodes, mode="train", keep=0.8, masks=None, norm_mode=None):
+    """gradient of <dcodes, H_L> w.r.t. every encoder parameter, evaluated at the given H, N and T"""
+    p = {k: np.asarray(v, dtype=F64) for k, v in params.items()}
+    H = [np.asarray(a, dtype=F64) for a in H]
+    grads = {}
+    G = np.asarray(dcodes, dtype=F64)
+    for l in range(L, 0, -1):
+        n, t, Hin = np.asarray(N[l], dtype=F64), np.asarray(T[l], dtype=F64), H[l - 1]
+        D = G * t * (n > 0) if l < L else G * t
+        dS = D * (np.asarray(masks[l - 1], dtype=F64) / F64(keep)) if mode == "train" else D
+        dZ = G * (n - Hin) * t * (1.0 - t)
+        grads["W_highway%d" % l] = Hin.T @ dZ
+        grads["b_highway%d" % l] = dZ.sum(axis=0)
+        g, raw = _layer_backward(kind, p, l, Hin, D, dS, triples, V, norm_mode)
+        grads.update(g)
+        G = raw + dZ @ p["W_highway%d" % l].T + G * (1.0 - t)
+    g0 = G * (H[0] > 0)
+    grads["W_emb"], grads["b_emb"] = g0, g0.sum(axis=0)
+    return grads

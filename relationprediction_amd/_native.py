@@ -16,13 +16,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "librgcn.so")
 
 ABI_VERSION = 1
-KIND_BLOCK, KIND_BASIS = 0, 1
+KIND_BLOCK, KIND_BASIS, KIND_BASIS_TDIAG = 0, 1, 2
 NORM_INTENDED, NORM_TF_AS_EXECUTED, NORM_NONE, NORM_LOCAL = 0, 1, 2, 3
 BUF_EXCHANGE, BUF_SELF, BUF_DSELF_EXCHANGE, BUF_INDEG, BUF_OUTDEG, BUF_ROWPTR, BUF_NORM_EXCHANGE, \
     BUF_DBASIS_EXCHANGE, BUF_PERM_VERTEX, BUF_PERM_RELATION, BUF_RANK_ENERGIES, BUF_MSG_NORM, BUF_HIGHWAY_INNER, \
     BUF_HIGHWAY_GATE = range(14)
+BUF_TDIAG_PRODUCTS = 14      # basis_tdiag contexts: [2, V, B*d], P_f then P_b of the layer run last
 
-KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS}
+KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS, "basis_tdiag": KIND_BASIS_TDIAG}
 NORMS = {"intended": NORM_INTENDED, "tf_as_executed": NORM_TF_AS_EXECUTED, "none": NORM_NONE, "local": NORM_LOCAL}
 
 INPUT_EMBEDDING, INPUT_ONEHOT = 0, 1
@@ -676,6 +677,8 @@ class Engine:
             out = np.empty(1, dtype=np.float32)
         elif which == BUF_DBASIS_EXCHANGE:
             out = np.empty((2, int(self.cfg.num_bases), self.d, self.d), dtype=np.float32)
+        elif which == BUF_TDIAG_PRODUCTS:
+            out = np.empty((2, self.V, int(self.cfg.num_bases) * self.d), dtype=np.float32)
         else:
             out = np.empty((self.V, self.d), dtype=np.float32)
         self._check(self.lib.rgcn_read_buffer(self.ctx, which, _ptr(out), out.nbytes))

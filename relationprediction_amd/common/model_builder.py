@@ -1,14 +1,16 @@
 """Plugin registry (reference: code/common/model_builder.py): maps `Encoder.Name` and its flags to a
 chain of components.  Only the hot-path family is built: `Name=gcn_basis` with UseOutputTransform=No, SkipConnections
 None or Highway (every layer wrapped in extras/highway_layer.py; UseInputTransform=Yes only) and none of the
-experimental layer flags -- UseInputTransform=Yes (exactly settings/gcn_block.exp and settings/gcn_basis.exp) or, for
-the basis kind, UseInputTransform=No: the featureless encoder whose first layer reads one-hot entity ids
-(:140-165,277-283); everything else raises NotImplementedError naming SURVEY.md section 2's
+experimental layer flags except DiagonalCoefficients=Yes (BasisGcnTimesDiag, with the reference's precedence over
+Concatenation; UseInputTransform=Yes and SkipConnections=None only) -- UseInputTransform=Yes (exactly
+settings/gcn_block.exp and settings/gcn_basis.exp) or, for the basis kind, UseInputTransform=No: the featureless encoder
+whose first layer reads one-hot entity ids (:140-165,277-283); everything else raises NotImplementedError naming SURVEY.md section 2's
 out-of-scope row instead of silently building something different."""
 from ..decoders.bilinear_diag import BilinearDiag
 from ..encoders.affine_transform import AffineTransform
 from ..encoders.message_gcns.gcn_basis import BasisGcn
 from ..encoders.message_gcns.gcn_basis_concat import ConcatGcn
+from ..encoders.message_gcns.gcn_basis_times_diag import BasisGcnTimesDiag
 from ..encoders.relation_embedding import RelationEmbedding
 from ..extras.graph_representations import Representation
 from ..extras.highway_layer import HighwayLayer
@@ -27,12 +29,17 @@ def build_encoder(encoder_settings, triples):
     if input_transform not in ("Yes", "No"):
         raise NotImplementedError("UseInputTransform must be Yes or No (the reference reads it unconditionally, "
                                   "model_builder.py:140), got %r" % (input_transform,))
-    concat = _flag(encoder_settings, 'Concatenation') == "Yes"
+    # the reference picks the layer class in this order (model_builder.py:285-294): AddDiagonal, DiagonalCoefficients,
+    # StoreEdgeData, Concatenation -- AddDiagonal, ahead of DiagonalCoefficients, stays refused; Concatenation, behind it,
+    # loses to it; StoreEdgeData=Yes stays refused whatever the layer (the training loop reads it too, train.py:242)
+    if _flag(encoder_settings, 'AddDiagonal') == "Yes":
+        raise NotImplementedError("AddDiagonal=Yes selects a reference variant outside the hot path")
+    times_diag = _flag(encoder_settings, 'DiagonalCoefficients') == "Yes"
+    concat = _flag(encoder_settings, 'Concatenation') == "Yes" and not times_diag
     if input_transform == "No" and concat:
         raise NotImplementedError("UseInputTransform=No with Concatenation=Yes: the reference's one-hot branch of "
                                   "ConcatGcn cannot execute (gcn_basis_concat.py:18-19,42-46)")
-    for key in ('UseOutputTransform', 'AddDiagonal', 'DiagonalCoefficients', 'StoreEdgeData', 'RandomInput',
-                'PartiallyRandomInput'):
+    for key in ('UseOutputTransform', 'StoreEdgeData', 'RandomInput', 'PartiallyRandomInput'):
         if _flag(encoder_settings, key) == "Yes":
             raise NotImplementedError("%s=Yes selects a reference variant outside the hot path" % key)
     skip = _flag(encoder_settings, 'SkipConnections', 'None')
@@ -42,6 +49,13 @@ def build_encoder(encoder_settings, triples):
         raise NotImplementedError("SkipConnections=Highway with UseInputTransform=No is the one-hot follow-up: the "
                                   "reference gives the one-hot first layer no highway layer while the layers above it "
                                   "get one (model_builder.py:304-305), which the engine does not build")
+
+    if times_diag and input_transform == "No":
+        raise NotImplementedError("DiagonalCoefficients=Yes with UseInputTransform=No: the one-hot first layer of "
+                                  "BasisGcnTimesDiag is not built")
+    if times_diag and skip == 'Highway':
+        raise NotImplementedError("DiagonalCoefficients=Yes with SkipConnections=Highway: highway layers around "
+                                  "BasisGcnTimesDiag are not built")
 
     graph = Representation(triples, encoder_settings)
     input_shape = [int(encoder_settings['EntityCount']), int(encoder_settings['InternalEncoderDimension'])]
@@ -64,7 +78,10 @@ def build_encoder(encoder_settings, triples):
 
 def apply_basis_gcn(encoder_settings, encoding, internal_shape, layers, onehot_first=False):
     concat = 'Concatenation' in encoder_settings and encoder_settings['Concatenation'] == "Yes"
-    layer_class = ConcatGcn if concat else BasisGcn
+    if _flag(encoder_settings, 'DiagonalCoefficients') == "Yes":       # ahead of Concatenation (model_builder.py:287-292)
+        layer_class = BasisGcnTimesDiag
+    else:
+        layer_class = ConcatGcn if concat else BasisGcn
     highway = _flag(encoder_settings, 'SkipConnections', 'None') == 'Highway'
     for layer in range(layers):
         onehot_input = onehot_first and layer == 0

@@ -347,7 +347,8 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     RGCN_FAIL(c, RGCN_ERR_INVALID, "EntityCount, RelationCount, dimension, NumberOfLayers and "
                                    "NumberOfBasisFunctions must be positive");
   if (!(f.keep_prob > 0.0f && f.keep_prob <= 1.0f)) RGCN_FAIL(c, RGCN_ERR_INVALID, "DropoutKeepProbability must be in (0,1]");
-  if (f.kind != RGCN_KIND_BLOCK && f.kind != RGCN_KIND_BASIS) RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown kind");
+  if (f.kind != RGCN_KIND_BLOCK && f.kind != RGCN_KIND_BASIS && f.kind != RGCN_KIND_BASIS_TDIAG)
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown kind");
   if (f.norm_mode < 0 || f.norm_mode > RGCN_NORM_LOCAL) RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown norm_mode");
   if (f.world < 1 || f.rank < 0 || f.rank >= f.world) RGCN_FAIL(c, RGCN_ERR_INVALID, "need 0 <= rank < world");
   if (f.max_edges < 0 || f.max_edges > (int64_t)500 * 1000 * 1000) RGCN_FAIL(c, RGCN_ERR_INVALID, "max_edges out of range");
@@ -356,6 +357,21 @@ static rgcn_status create_impl(rgcn_ctx* c) {
   c->V = f.num_entities; c->R = f.num_relations; c->d = f.dim; c->L = f.num_layers; c->kind = f.kind;
   c->rank = f.rank; c->world = f.world;
   c->onehot = f.input_mode == RGCN_INPUT_ONEHOT;
+  if (f.kind == RGCN_KIND_BASIS_TDIAG) {
+    // BasisGcnTimesDiag (basis_tdiag.hip): one GPU, embedding input, no highway layers
+    if (f.world > 1)
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_TDIAG on a sharded context (the products P, dP and the coefficient "
+                                         "table have no exchange points)");
+    if (c->onehot)
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_TDIAG with RGCN_INPUT_ONEHOT (the reference's one-hot branch of "
+                                         "BasisGcnTimesDiag exists, gcn_basis_times_diag.py:21,70,76: not built)");
+    if (c->highway)
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_TDIAG with RGCN_SKIP_HIGHWAY (not built)");
+    if (f.num_bases > 64) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "NumberOfBasisFunctions > 64 (basis_tdiag)");
+    if (2 * (int64_t)f.num_entities * f.num_bases * (int64_t)f.dim >= ((int64_t)1 << 31))
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_TDIAG: 2 x EntityCount x NumberOfBasisFunctions x dimension must be "
+                                         "below 2^31");
+  }
   if (c->onehot) {
     // the featureless first layer (model_builder.py:277-283): BasisGcn only, per-entity tables on one GPU
     if (f.kind != RGCN_KIND_BASIS)
@@ -392,6 +408,7 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     c->B = f.num_bases;
     if (c->B > 64) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "NumberOfBasisFunctions > 64 (basis)");
   }
+  const bool tdiag = c->kind == RGCN_KIND_BASIS_TDIAG;
   // equal row chunks (the reduce-scatter / all-gather want them equal): rank g finishes rows [g * shard_rows, +shard_rows)
   c->shard_rows = (c->V + c->world - 1) / c->world;
   c->V_pad = c->shard_rows * c->world;
@@ -484,6 +501,19 @@ static rgcn_status create_impl(rgcn_ctx* c) {
       add_param(c, "W_f" + sl, {(int64_t)R, c->nb, c->sd, c->sd}, lb.wrel, lb.grel, LAYOUT_BLOCK_T);
       add_param(c, "W_b" + sl, {(int64_t)R, c->nb, c->sd, c->sd}, lb.wrel + per_dir, lb.grel + per_dir, LAYOUT_BLOCK_T);
       if (c->nb <= 512) RGCN_TRY(dmalloc(c, c->pool, &lb.wtile, block_rows_weight_floats(c), true));
+    } else if (tdiag) {
+      // gcn_basis_times_diag.py:38-42.  W_forward, W_backward stay in the host layout [d][B.d]: it is the B operand of
+      // P = H . W with N contiguous; the coefficients are [R,B,d] per direction, their sigmoid a table of the same shape
+      const size_t per_dir = (size_t)c->B * d * d, per_c = R * c->B * d;
+      RGCN_TRY(dmalloc(c, c->pool, &lb.wrel, 2 * per_dir, true));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.grel, 2 * per_dir, true));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.coef, 2 * per_c, true));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.gcoef, 2 * per_c, true));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.tdiag_g, 2 * per_c, true));
+      add_param(c, "W_f" + sl, {(int64_t)d, c->B, (int64_t)d}, lb.wrel, lb.grel, LAYOUT_PLAIN);
+      add_param(c, "W_b" + sl, {(int64_t)d, c->B, (int64_t)d}, lb.wrel + per_dir, lb.grel + per_dir, LAYOUT_PLAIN);
+      add_param(c, "C_f" + sl, {(int64_t)R, c->B, (int64_t)d}, lb.coef, lb.gcoef, LAYOUT_PLAIN);
+      add_param(c, "C_b" + sl, {(int64_t)R, c->B, (int64_t)d}, lb.coef + per_c, lb.gcoef + per_c, LAYOUT_PLAIN);
     } else {
       const size_t per_dir = (size_t)c->B * d * d;
       RGCN_TRY(dmalloc(c, c->pool, &lb.wrel, 2 * per_dir, true));
@@ -513,7 +543,7 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     RGCN_TRY(dmalloc(c, c->pool, &lb.gbias, d, true));
     add_param(c, "W_self" + sl, {(int64_t)d, (int64_t)d}, lb.wself, lb.gwself, LAYOUT_PLAIN);
     add_param(c, "b" + sl, {(int64_t)d}, lb.bias, lb.gbias, LAYOUT_PLAIN);
-    c->params.back().no_grad = true;
+    c->params.back().no_grad = !tdiag;      // (BasisGcnTimesDiag adds its bias, gcn_basis_times_diag.py:86)
     if (c->highway) {      // HighwayLayer.local_get_weights (highway_layer.py): [W, b], behind the layer it wraps
       RGCN_TRY(dmalloc(c, c->pool, &lb.whw, d * d, true));
       RGCN_TRY(dmalloc(c, c->pool, &lb.gwhw, d * d, true));
@@ -553,6 +583,16 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     RGCN_TRY(dmalloc(c, c->pool, &c->msgbuf, (M ? M : 1) * d, false));
     const size_t per_rel = (size_t)c->sd * c->sd * c->nb;
     c->slab_dw_floats = max_rel_chunks * per_rel;
+    RGCN_TRY(dmalloc(c, c->pool, &c->slab_dw, c->slab_dw_floats, false));
+  } else if (tdiag) {
+    const size_t pd = 2 * V * (size_t)c->B * d;      // [2][V][B.d]
+    c->tdiag_P.assign(c->L + 1, nullptr);
+    for (int l = 1; l <= c->L; ++l) RGCN_TRY(dmalloc(c, c->pool, &c->tdiag_P[l], pd, true));
+    RGCN_TRY(dmalloc(c, c->pool, &c->tdiag_dP, pd, true));
+    RGCN_TRY(dmalloc(c, c->pool, &c->tdiag_dh, 2 * V * d, true));
+    const size_t s2 = 16 * 2 * (size_t)c->B * d * d;      // dW_dir = H^T . dP_dir: two groups, at most 16 slabs each
+    if (s2 > slab) slab = s2;
+    c->slab_dw_floats = max_rel_chunks * (size_t)c->B * d;      // per-chunk partials of dG
     RGCN_TRY(dmalloc(c, c->pool, &c->slab_dw, c->slab_dw_floats, false));
   } else {
     const size_t zc = 2 * (size_t)c->B * d;
@@ -1145,6 +1185,9 @@ rgcn_status rgcn_capture_begin(rgcn_ctx* c) {
   if (c->highway)
     RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "rgcn_capture_begin: capture on an RGCN_SKIP_HIGHWAY context is not supported (a captured "
                                        "highway step has never been replayed against a reference)");
+  if (c->kind == RGCN_KIND_BASIS_TDIAG)
+    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "rgcn_capture_begin: capture on an RGCN_KIND_BASIS_TDIAG context is not supported (a "
+                                       "captured step of this kind has never been replayed against a reference)");
   if (c->world > 1 && knob("RGCN_CAPTURE_SHARDED", 0) != 1)
     RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "capture on a sharded context is experimental (never run against real RCCL on "
                                        "several GPUs): the devtools build enables it with RGCN_CAPTURE_SHARDED=1");
@@ -1344,6 +1387,10 @@ static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* byte
       if (!c->highway) RGCN_FAIL(c, RGCN_ERR_STATE, "not an RGCN_SKIP_HIGHWAY context");
       if (c->hw_last < 1) RGCN_FAIL(c, RGCN_ERR_STATE, "no rgcn_forward_layer_finish has run");
       *p = which == RGCN_BUF_HIGHWAY_INNER ? c->hw_N[c->hw_last] : c->hw_T[c->hw_last]; *bytes = Vd; return RGCN_OK;
+    case RGCN_BUF_TDIAG_PRODUCTS:
+      if (c->kind != RGCN_KIND_BASIS_TDIAG) RGCN_FAIL(c, RGCN_ERR_STATE, "not an RGCN_KIND_BASIS_TDIAG context");
+      if (c->tdiag_last < 1) RGCN_FAIL(c, RGCN_ERR_STATE, "no rgcn_forward_layer_finish has run");
+      *p = c->tdiag_P[c->tdiag_last]; *bytes = (int64_t)2 * c->V * c->B * c->d * 4; return RGCN_OK;
     default: RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown buffer id");
   }
 }

@@ -175,6 +175,10 @@ struct LayerBufs {
   uint64_t wtile_version = ~0ull;
   // highway context (RGCN_SKIP_HIGHWAY): the gate's weight [d,d] and bias [d] (highway_layer.py) and their gradients
   float *whw = nullptr, *gwhw = nullptr, *bhw = nullptr, *gbhw = nullptr;
+  // BASIS_TDIAG: wrel = [2][d][B*d] (W_forward, W_backward in the host layout: the B operand of P = H . W, N contiguous),
+  // coef = [2R][B][d]; tdiag_g = sigmoid(coef), rebuilt when the weights change (basis_tdiag.hip)
+  float* tdiag_g = nullptr;
+  uint64_t tdiag_g_version = ~0ull;
 };
 
 struct GraphBufs {
@@ -358,6 +362,12 @@ struct rgcn_ctx {
   float* hw_dz[2] = {nullptr, nullptr};   // dZ_l, ping-pong like D / dS (layer 2's dW_hw GEMM may trail beside layer 1)
   float* hw_carry = nullptr;              // G_l * (1 - T_l)
   int hw_last = 0;                        // the layer the last fwd_layer_finish ran (RGCN_BUF_HIGHWAY_INNER / _GATE)
+  // RGCN_KIND_BASIS_TDIAG (basis_tdiag.hip; one GPU, embedding input, no highway): P_l = H_{l-1} . [W_f | W_b] of every
+  // layer ([2][V][B.d], kept for dC), ONE dP of that shape, the two directions' dP . W^T products [2][V][d]
+  std::vector<float*> tdiag_P;            // [1..L]
+  float* tdiag_dP = nullptr;
+  float* tdiag_dh = nullptr;
+  int tdiag_last = 0;                     // the layer the last fwd_layer_finish ran (RGCN_BUF_TDIAG_PRODUCTS)
   bool onehot = false;          // featureless first layer (RGCN_INPUT_ONEHOT): no W_emb / b_emb / H_0, layer 1 is basis_onehot.hip
   int row_lo = 0, row_hi = 0;   // row shard of this rank: [rank * shard_rows, +shard_rows) cut at V
   int shard_rows = 0;           // ceil(V / world): equal chunks for the reduce-scatter / all-gather
@@ -595,6 +605,17 @@ double basis_units(rgcn_ctx* c);      // (row, direction) units of the current g
 rgcn_status basis_gather_units(rgcn_ctx* c, const float* D, float* Dc);
 rgcn_status basis_to_device_layout(rgcn_ctx* c, const float* host_layout_dev, float* dst);
 rgcn_status basis_from_device_layout(rgcn_ctx* c, const float* src, float* host_layout_dev);
+
+// ---- basis_tdiag.hip: the layer kernels of RGCN_KIND_BASIS_TDIAG (the GEMMs around them are the schedule's)
+rgcn_status tdiag_refresh_gates(rgcn_ctx* c, int layer);                 // tdiag_g = sigmoid(coef) where the weights changed
+// out = act(dropout(base) + sum over the row's messages of n sum_b G[rel,b,:] P_dir[src,b,:] + bias)
+rgcn_status tdiag_rows_forward(rgcn_ctx* c, int layer, const float* P, const CombineArgs& ca);
+// dP[dir][u][b][:] = sum over the messages u sends in direction dir of n G[rel,b,:] D[dst,:]; every row is written
+rgcn_status tdiag_dp(rgcn_ctx* c, int layer, const float* D, float* dP);
+// gcoef = G (1 - G) * sum over the relation's messages of n P_dir[src,b,:] D[dst,:]  (chunk slabs, chunk order)
+rgcn_status tdiag_dcoef(rgcn_ctx* c, int layer, const float* P, const float* D);
+// out = (base + dh[0] + dh[1]) * (gate > 0), out2 = out * dropout(drop2): the epilogue of the layer's backward pass
+rgcn_status tdiag_dh_join(rgcn_ctx* c, const float* dh, const CombineArgs& ca);
 
 // ---- basis_onehot.hip: the featureless first layer (rgcn_config::input_mode == RGCN_INPUT_ONEHOT, basis kind): layer 1's
 // weights are per-entity tables [2][V][B][d] (LayerBufs::wrel) and W_self [V,d], messages are table rows

@@ -137,6 +137,15 @@ static GemmBatch basis_batch(const rgcn_ctx* c, size_t strideA, size_t strideB, 
 }
 static double basis_unit_share(rgcn_ctx* c) { return basis_units(c) / (2.0 * c->V); }
 
+// BASIS_TDIAG: the two direction groups of a batched GEMM -- H (or its transpose) is the A operand of both, W_dir / dP_dir
+// the B operand, P_dir / dW_dir the product
+static GemmBatch tdiag_batch(size_t strideA, size_t strideB, size_t strideC) {
+  GemmBatch b;
+  b.groups = 2;
+  b.strideA = strideA; b.strideB = strideB; b.strideC = strideC;
+  return b;
+}
+
 rgcn_status fwd_layer_partial(rgcn_ctx* c, int l) {
   if (l < 1 || l > c->L) RGCN_FAIL(c, RGCN_ERR_INVALID, "layer out of range");
   // featureless first layer (world == 1): one destination-major kernel, messages looked up in the [V,B,d] tables, the
@@ -194,6 +203,27 @@ rgcn_status fwd_layer_partial(rgcn_ctx* c, int l) {
     a.drop = make_drop(c, l, true);
     a.drop2 = make_drop(c, l, false);
     RGCN_TRY(combine(c, "combine_fwd", a, 4.0 * d * (2.0 * V + Mmsg) + 4.0 * V));
+  } else if (c->kind == RGCN_KIND_BASIS_TDIAG) {
+    // transform first (basis_tdiag.hip): P_dir = H . W_dir.reshape(d, B.d), two groups of one batched GEMM over the same
+    // A operand, kept per layer for dC; the self-loop product beside it on side stream 1; then ONE destination-major
+    // kernel: H' = relu(dropout(S) + sum over the row's messages of n sum_b G[rel,b,:] P_dir[src,b,:] + b)
+    const int Bd = c->B * d;
+    RGCN_TRY(tdiag_refresh_gates(c, l));
+    {
+      StreamScope side(c, 1);
+      RGCN_TRY(gemm_f32(c, "gemm_self_fwd", self));
+    }
+    const GemmBatch gb = tdiag_batch(0, (size_t)d * Bd, (size_t)V * Bd);
+    RGCN_TRY(gemm_f32(c, "gemm_tdiag_fwd", true, false, V, Bd, d, Hin, d, c->layers[l].wrel, Bd, c->tdiag_P[l], Bd, 1, &gb));
+    RGCN_TRY(stream_join(c, 1));
+    CombineArgs a;
+    a.add = nullptr; a.msg = nullptr; a.row_ptr = nullptr; a.long_rows = nullptr; a.nlong = nullptr;
+    a.out = dst; a.out2 = nullptr; a.base = c->self_buf; a.gate = nullptr; a.V = V; a.d = d;
+    a.relu = l < c->L ? 1 : 0;
+    a.row_lo = lo; a.row_hi = hi;
+    a.drop = make_drop(c, l, true);
+    a.drop2 = make_drop(c, l, false);
+    RGCN_TRY(tdiag_rows_forward(c, l, c->tdiag_P[l], a));
   } else {
     // aggregate first, per (row, direction) unit: Zc[(v,dir),b,:] = sum n C[rel,b] H[src];
     // pre[v] = dropout(H.W_self)[v] + sum_dir Zc[(v,dir)] . W'_dir  -- two groups of one batched GEMM over the units
@@ -240,6 +270,7 @@ rgcn_status fwd_layer_finish(rgcn_ctx* c, int l) {
     RGCN_TRY(highway_forward(c, c->hw_T[l], c->layers[l].bhw, c->hw_N[l], c->H[l - 1], c->H[l]));
     c->hw_last = l;
   }
+  if (c->kind == RGCN_KIND_BASIS_TDIAG) c->tdiag_last = l;
   if (l == c->L) c->fwd_done = true;
   return RGCN_OK;
 }
@@ -444,6 +475,31 @@ rgcn_status bwd_layer_partial(rgcn_ctx* c, int l) {
     a.long_rows = c->g.long_rows;
     a.nlong = c->g.nlong;
     RGCN_TRY(combine(c, "combine_bwd", a, 4.0 * d * ((a.out2 ? 4.0 : 3.0) * V + Mmsg) + 4.0 * V));
+  } else if (c->kind == RGCN_KIND_BASIS_TDIAG) {
+    const int Bd = c->B * d;
+    // db = the column sums of D (this layer's bias is added, gcn_basis_times_diag.py:86); dP source-major from D and G
+    RGCN_TRY(tdiag_refresh_gates(c, l));
+    RGCN_TRY(column_sum(c, c->bwd_D, lb.gbias, V, d));
+    RGCN_TRY(tdiag_dp(c, l, c->bwd_D, c->tdiag_dP));
+    {   // dC needs P_l and D only: per relation chunk on side stream 0, beside the dense products
+      StreamScope side(c, 0);
+      RGCN_TRY(tdiag_dcoef(c, l, c->tdiag_P[l], c->bwd_D));
+    }
+    {   // the two weight gradients on side stream 1 (they share the split-K slabs: one stream, in order)
+      StreamScope side(c, 1);
+      RGCN_TRY(self_dw());
+      // dW_dir = H^T . dP_dir   ([d, V] x [V, B.d], split over the rows; two groups, the same A operand)
+      const GemmBatch gk = tdiag_batch(0, (size_t)V * Bd, (size_t)d * Bd);
+      int split = auto_split_k(d, 2 * Bd, V, true);
+      if (split > 16) split = 16;      // (the slabs are sized for 16: rgcn_create)
+      RGCN_TRY(gemm_f32(c, "gemm_tdiag_dw", false, false, d, Bd, V, Hin, d, c->tdiag_dP, Bd, lb.grel, Bd, split, &gk));
+    }
+    RGCN_TRY(self_dh());
+    // dH's relational part: dP_dir . W_dir^T   ([V, B.d] x [B.d, d], two groups), added by the epilogue kernel
+    const GemmBatch gm = tdiag_batch((size_t)V * Bd, (size_t)d * Bd, (size_t)V * d);
+    RGCN_TRY(gemm_f32(c, "gemm_tdiag_dh", true, true, V, d, Bd, c->tdiag_dP, Bd, lb.wrel, Bd, c->tdiag_dh, d, 1, &gm));
+    RGCN_TRY(tdiag_dh_join(c, c->tdiag_dh, a));
+    RGCN_TRY(stream_join(c, 0));      // (the next layer rewrites D's buffer, dP and the chunk slabs)
   } else {
     const int Bd = c->B * d;
     // The upstream rows of the units, compacted like Zc (the row operand of dZ, the depth operand of dW')

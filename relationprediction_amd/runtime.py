@@ -40,6 +40,9 @@ class EncoderRuntime(object):
         self.highway = self.highways[0] is not None
         if self.highway and affine is None:
             raise NotImplementedError("SkipConnections=Highway with UseInputTransform=No (the one-hot follow-up)")
+        if self.kind == "basis_tdiag" and (self.highway or affine is None):
+            raise NotImplementedError("DiagonalCoefficients=Yes with SkipConnections=Highway or UseInputTransform=No: "
+                                      "BasisGcnTimesDiag runs on embedding input without highway layers only")
         s = top.settings
         self.V, self.R = top.entity_count, top.relation_count
         self.d = int(top.shape[1])

@@ -602,7 +602,9 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     c->zsave.assign(c->L + 1, nullptr);
     // (a one-hot layer 1 has no Z)
     for (int l = c->onehot ? 2 : 1; l <= c->L; ++l) RGCN_TRY(dmalloc(c, c->pool, &c->zsave[l], V * zc, true));
-    const size_t s2 = 16 * zc * d;
+    // dW'_dir = Zc_dir^T . Dc_dir: two groups, split over V as bwd_layer_partial asks (auto_split_k: past 16 slabs at few
+    // tiles and many rows, e.g. 35 at B = 1, d = 260, V >= 4480), never fewer than 16
+    const size_t s2 = (size_t)std::max(16, auto_split_k((int)zc, (int)d, (int)V)) * zc * d;
     if (s2 > slab) slab = s2;
     c->slab_dw_floats = max_rel_chunks * (size_t)c->B;
     RGCN_TRY(dmalloc(c, c->pool, &c->slab_dw, c->slab_dw_floats, false));

@@ -133,20 +133,20 @@ def forward_float32(kind, params, triples, V, L, mode="train", keep=0.8, masks=N
     return H, N, T
 
 
-def _layer_backward(kind, p, l, Hin, D, dS, triples, V, norm_mode):
+def _layer_backward(kind, p, l, Hin, D, dS, triples, V, norm_mode, dtype=F64):
     """gradients of layer l's own weights from D = dL/dpre_l and dS = D * dropout_l, and the raw dL/dH_{l-1} through the
     layer (no relu', no dropout copy): tf.gradients of gcn_basis_concat.py:35-83 / gcn_basis.py:39-88"""
     norm_mode = oracle.NORM_INTENDED if norm_mode is None else norm_mode
     s, r, o = oracle.split_graph(triples)
     E = len(s)
-    n_f = np.asarray(oracle.incidence_values(o, V, norm_mode), dtype=F64)
-    n_b = np.asarray(oracle.incidence_values(s, V, norm_mode), dtype=F64)
-    g = {"W_self%d" % l: Hin.T @ dS, "b%d" % l: np.zeros(D.shape[1])}
+    n_f = np.asarray(oracle.incidence_values(o, V, norm_mode), dtype=dtype)
+    n_b = np.asarray(oracle.incidence_values(s, V, norm_mode), dtype=dtype)
+    g = {"W_self%d" % l: Hin.T @ dS, "b%d" % l: np.zeros(D.shape[1], dtype=dtype)}
     dHin = dS @ p["W_self%d" % l].T
     for tag, rows_in, rows_out, nrm in (("f", s, o, n_f), ("b", o, s, n_b)):
         W = p["W_%s%d" % (tag, l)]
         gW = np.zeros_like(W)
-        gm = D[rows_out] * nrm[:, None] if E else np.zeros((0, D.shape[1]))
+        gm = D[rows_out] * nrm[:, None] if E else np.zeros((0, D.shape[1]), dtype=dtype)
         if kind == "block":
             R, nb, sd, _ = W.shape
             g3, x3 = gm.reshape(E, nb, sd), Hin[rows_in].reshape(E, nb, sd)
@@ -167,22 +167,24 @@ def _layer_backward(kind, p, l, Hin, D, dS, triples, V, norm_mode):
     return g, dHin
 
 
-def backward(kind, params, triples, V, L, H, N, T, dcodes, mode="train", keep=0.8, masks=None, norm_mode=None):
-    """gradient of <dcodes, H_L> w.r.t. every encoder parameter, evaluated at the given H, N and T"""
-    p = {k: np.asarray(v, dtype=F64) for k, v in params.items()}
-    H = [np.asarray(a, dtype=F64) for a in H]
+def backward(kind, params, triples, V, L, H, N, T, dcodes, mode="train", keep=0.8, masks=None, norm_mode=None, dtype=F64):
+    """gradient of <dcodes, H_L> w.r.t. every encoder parameter, evaluated at the given H, N and T; dtype=np.float32
+    evaluates the same formulas with every array and every operation in float32 (forward_float32's counterpart)"""
+    one = dtype(1)
+    p = {k: np.asarray(v, dtype=dtype) for k, v in params.items()}
+    H = [np.asarray(a, dtype=dtype) for a in H]
     grads = {}
-    G = np.asarray(dcodes, dtype=F64)
+    G = np.asarray(dcodes, dtype=dtype)
     for l in range(L, 0, -1):
-        n, t, Hin = np.asarray(N[l], dtype=F64), np.asarray(T[l], dtype=F64), H[l - 1]
+        n, t, Hin = np.asarray(N[l], dtype=dtype), np.asarray(T[l], dtype=dtype), H[l - 1]
         D = G * t * (n > 0) if l < L else G * t
-        dS = D * (np.asarray(masks[l - 1], dtype=F64) / F64(keep)) if mode == "train" else D
-        dZ = G * (n - Hin) * t * (1.0 - t)
+        dS = D * (np.asarray(masks[l - 1], dtype=dtype) / dtype(keep)) if mode == "train" else D
+        dZ = G * (n - Hin) * t * (one - t)
         grads["W_highway%d" % l] = Hin.T @ dZ
         grads["b_highway%d" % l] = dZ.sum(axis=0)
-        g, raw = _layer_backward(kind, p, l, Hin, D, dS, triples, V, norm_mode)
+        g, raw = _layer_backward(kind, p, l, Hin, D, dS, triples, V, norm_mode, dtype=dtype)
         grads.update(g)
-        G = raw + dZ @ p["W_highway%d" % l].T + G * (1.0 - t)
+        G = raw + dZ @ p["W_highway%d" % l].T + G * (one - t)
     g0 = G * (H[0] > 0)
     grads["W_emb"], grads["b_emb"] = g0, g0.sum(axis=0)
     return grads

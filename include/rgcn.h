@@ -55,7 +55,7 @@ enum {
 
 /* Encoder.Concatenation=Yes -> ConcatGcn (block-diagonal), else BasisGcn:
  * code/common/model_builder.py:291-294. */
-enum { RGCN_KIND_BLOCK = 0, RGCN_KIND_BASIS = 1, RGCN_KIND_BASIS_TDIAG = 2 };
+enum { RGCN_KIND_BLOCK = 0, RGCN_KIND_BASIS = 1, RGCN_KIND_BASIS_TDIAG = 2, RGCN_KIND_BASIS_PDIAG = 3 };
 /* RGCN_KIND_BASIS_TDIAG = Encoder.DiagonalCoefficients=Yes -> BasisGcnTimesDiag
  * (code/encoders/message_gcns/gcn_basis_times_diag.py; model_builder.py:287-288, ahead of Concatenation): the
  * coefficient of a message is a VECTOR per (relation, basis) over the output channels,
@@ -71,6 +71,24 @@ enum { RGCN_KIND_BLOCK = 0, RGCN_KIND_BASIS = 1, RGCN_KIND_BASIS_TDIAG = 2 };
  *   - 2 * EntityCount * num_bases * dim >= 2^31 (the products are indexed with 32-bit ints per direction pair),
  * and rgcn_capture_begin returns RGCN_ERR_UNSUPPORTED on such a context (a captured step of this kind has never been
  * replayed against a reference).  Every RGCN_NORM_* mode and every rgcn_set_gemm_mode work; rgcn_set_fusion is ignored. */
+/* RGCN_KIND_BASIS_PDIAG = Encoder.AddDiagonal=Yes -> BasisGcnWithDiag (code/encoders/message_gcns/gcn_basis_plus_diag.py;
+ * model_builder.py:285-286, the flag the reference checks first): the basis layer plus a DistMult-like term per message,
+ * H[src] * D[rho], with a trained vector D[rho] per directed relation; the layer's bias b IS added and trained.
+ * AS EXECUTED by the reference (compute_messages unpacks the two basis products the other way round from how
+ * compute_basis_functions returns them, :51 against :75-79) the basis term of a message is formed from the DESTINATION's
+ * own features under the OTHER direction's basis tensor:
+ *     a_dir[v,b] = sum_{m -> v, dir(m) = dir} n_m C_dir[r_m,b]
+ *     pre[v]     = dropout(H . W_self)[v] + sum_dir sum_b a_dir[v,b] (H[v] . W_other(dir)[:,b,:])
+ *                  + sum_{m -> v} n_m D[rho_m,:] * H[src_m,:] + b
+ * num_bases = B (csrc/basis_pdiag.hip).  One GPU with embedding input and RGCN_SKIP_NONE only; rgcn_create /
+ * rgcn_create_ex return RGCN_ERR_UNSUPPORTED for
+ *   - world > 1 (the mixing table, the diagonal aggregate and dD have no exchange points),
+ *   - RGCN_INPUT_ONEHOT (the one-hot branch of this layer is not built),
+ *   - RGCN_SKIP_HIGHWAY,
+ *   - num_bases > 64,
+ *   - 2 * EntityCount * num_bases * dim >= 2^31 (the compacted unit rows are indexed with 32-bit ints per direction pair),
+ * and rgcn_capture_begin returns RGCN_ERR_UNSUPPORTED on such a context.  Every RGCN_NORM_* mode and every
+ * rgcn_set_gemm_mode work; rgcn_set_fusion is ignored. */
 
 /* Neighbour normalisation of the incidence matrices, normalization=('global', ...)
  * (code/extras/graph_representations.py:82-93,122-133).  INTENDED = 1/deg(row of this edge);
@@ -138,7 +156,11 @@ enum {
   RGCN_BUF_HIGHWAY_GATE = 13,   /* float [V,d] T_l, the transform gate */
   /* RGCN_KIND_BASIS_TDIAG contexts, of the layer the last rgcn_forward_layer_finish (or rgcn_forward: layer L) ran;
    * RGCN_ERR_STATE on every other context: */
-  RGCN_BUF_TDIAG_PRODUCTS = 14  /* float [2][V][B*d]: P_f = H_{l-1} . W_f.reshape(d, B*d), then P_b likewise */
+  RGCN_BUF_TDIAG_PRODUCTS = 14, /* float [2][V][B*d]: P_f = H_{l-1} . W_f.reshape(d, B*d), then P_b likewise */
+  /* RGCN_KIND_BASIS_PDIAG contexts, of the layer the last rgcn_forward_layer_finish (or rgcn_forward: layer L) ran;
+   * RGCN_ERR_STATE before any layer has run and on every other context: */
+  RGCN_BUF_PDIAG_MIX = 15,      /* float [2][V][B]: a_dir[v,b] = sum over the row's messages of direction dir of n C_dir[r,b] */
+  RGCN_BUF_PDIAG_AGG = 16       /* float [V,d]: the diagonal aggregate sum over the row's messages of n D[rho] * H_{l-1}[src] */
 };
 
 /*
@@ -155,7 +177,7 @@ typedef struct rgcn_config {
   int32_t dim;            /* d = InternalEncoderDimension (= CodeDimension, UseOutputTransform=No) */
   int32_t num_layers;     /* L = NumberOfLayers */
   int32_t kind;           /* RGCN_KIND_* */
-  int32_t num_bases;      /* NumberOfBasisFunctions: block count nb (BLOCK, d % nb == 0) or B (BASIS, BASIS_TDIAG) */
+  int32_t num_bases;      /* NumberOfBasisFunctions: block count nb (BLOCK, d % nb == 0) or B (BASIS, BASIS_TDIAG, BASIS_PDIAG) */
   float   keep_prob;      /* DropoutKeepProbability (self-loop dropout, train mode only) */
   int32_t norm_mode;      /* RGCN_NORM_* */
   int64_t max_edges;      /* capacity: largest E ever passed to rgcn_set_graph* */
@@ -201,6 +223,9 @@ rgcn_status rgcn_sync(rgcn_ctx* ctx);
  *                                                           (gcn_basis.py:33-37)
  *                      BASIS_TDIAG: W_f [d,B,d], W_b [d,B,d], C_f [R,B,d], C_b [R,B,d], W_self [d,d], b [d]
  *                                                           (gcn_basis_times_diag.py:38-42); b is a LIVE parameter here
+ *                      BASIS_PDIAG: W_f [d,B,d], W_b [d,B,d], C_f [R,B], C_b [R,B], D_b [R,d], D_f [R,d], W_self [d,d], b [d]
+ *                                                           (gcn_basis_plus_diag.py:42-47: the BACKWARD diagonal table comes
+ *                                                           first); b is a LIVE parameter here
  * RGCN_INPUT_ONEHOT (basis kind; model_builder.py:140-165,277-283, gcn_basis.py:16-24): no W_emb / b_emb, and layer 1 is
  *                      W_f [V,B,d], W_b [V,B,d], C_f [R,B], C_b [R,B], W_self [V,d], b [d]; layers 2..L as above.
  *                      rgcn_param_count / _info / rgcn_set_param / rgcn_get_param / rgcn_get_grad all follow that list.
@@ -208,7 +233,7 @@ rgcn_status rgcn_sync(rgcn_ctx* ctx);
  *                      order Model.get_weights() returns).  The same calls, the optimizer's clip norm and Adam follow.
  * Host layouts are the reference's (row-major, shapes above); the device layout is private.
  * `b` is created but never used by the reference's BLOCK and BASIS layers: it is stored, never read,
- * and its gradient is all zeros (BASIS_TDIAG adds it: gradient, clip norm and Adam follow).  The LAST parameter is the decoder's W_relation [EntityCount, d]
+ * and its gradient is all zeros (BASIS_TDIAG and BASIS_PDIAG add it: gradient, clip norm and Adam follow).  The LAST parameter is the decoder's W_relation [EntityCount, d]
  * (relation_embedding.py:15-18; only rows < RelationCount are ever used): the encoder path
  * does not touch it, the device decoder below does. */
 int32_t     rgcn_param_count(const rgcn_ctx* ctx);

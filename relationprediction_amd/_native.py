@@ -16,14 +16,17 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "librgcn.so")
 
 ABI_VERSION = 1
-KIND_BLOCK, KIND_BASIS, KIND_BASIS_TDIAG = 0, 1, 2
+KIND_BLOCK, KIND_BASIS, KIND_BASIS_TDIAG, KIND_BASIS_PDIAG = 0, 1, 2, 3
 NORM_INTENDED, NORM_TF_AS_EXECUTED, NORM_NONE, NORM_LOCAL = 0, 1, 2, 3
 BUF_EXCHANGE, BUF_SELF, BUF_DSELF_EXCHANGE, BUF_INDEG, BUF_OUTDEG, BUF_ROWPTR, BUF_NORM_EXCHANGE, \
     BUF_DBASIS_EXCHANGE, BUF_PERM_VERTEX, BUF_PERM_RELATION, BUF_RANK_ENERGIES, BUF_MSG_NORM, BUF_HIGHWAY_INNER, \
     BUF_HIGHWAY_GATE = range(14)
 BUF_TDIAG_PRODUCTS = 14      # basis_tdiag contexts: [2, V, B*d], P_f then P_b of the layer run last
+BUF_PDIAG_MIX = 15           # basis_pdiag contexts: [2, V, B], the mixing table a of the layer run last
+BUF_PDIAG_AGG = 16           # basis_pdiag contexts: [V, d], the diagonal aggregate of the layer run last
 
-KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS, "basis_tdiag": KIND_BASIS_TDIAG}
+KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS, "basis_tdiag": KIND_BASIS_TDIAG,
+         "basis_pdiag": KIND_BASIS_PDIAG}
 NORMS = {"intended": NORM_INTENDED, "tf_as_executed": NORM_TF_AS_EXECUTED, "none": NORM_NONE, "local": NORM_LOCAL}
 
 INPUT_EMBEDDING, INPUT_ONEHOT = 0, 1
@@ -395,7 +398,7 @@ class Engine:
         if t.ndim != 2 or t.shape[1] != 3:
             raise ValueError("graph_edges must be [E,3]")
         if t.dtype != np.int32:
-            # the reference feeds int64 numpy arrays into an int32 placeholder (SURVEY H13)
+            # the reference feeds int64 numpy arrays into an int32 placeholder (SURVEY H14)
             if t.size and (t.min() < -2 ** 31 or t.max() >= 2 ** 31):
                 raise ValueError("ids do not fit int32")
             t = t.astype(np.int32)
@@ -679,6 +682,8 @@ class Engine:
             out = np.empty((2, int(self.cfg.num_bases), self.d, self.d), dtype=np.float32)
         elif which == BUF_TDIAG_PRODUCTS:
             out = np.empty((2, self.V, int(self.cfg.num_bases) * self.d), dtype=np.float32)
+        elif which == BUF_PDIAG_MIX:
+            out = np.empty((2, self.V, int(self.cfg.num_bases)), dtype=np.float32)
         else:
             out = np.empty((self.V, self.d), dtype=np.float32)
         self._check(self.lib.rgcn_read_buffer(self.ctx, which, _ptr(out), out.nbytes))

@@ -2,7 +2,9 @@
 chain of components.  Only the hot-path family is built: `Name=gcn_basis` with UseOutputTransform=No, SkipConnections
 None or Highway (every layer wrapped in extras/highway_layer.py; UseInputTransform=Yes only) and none of the
 experimental layer flags except DiagonalCoefficients=Yes (BasisGcnTimesDiag, with the reference's precedence over
-Concatenation; UseInputTransform=Yes and SkipConnections=None only) -- UseInputTransform=Yes (exactly
+Concatenation; UseInputTransform=Yes and SkipConnections=None only) and AddDiagonal=Yes (BasisGcnWithDiag; the same two
+conditions, and with Concatenation=No and DiagonalCoefficients=No only: the reference lets AddDiagonal override both
+silently, a contradictory file is refused here) -- UseInputTransform=Yes (exactly
 settings/gcn_block.exp and settings/gcn_basis.exp) or, for the basis kind, UseInputTransform=No: the featureless encoder
 whose first layer reads one-hot entity ids (:140-165,277-283); everything else raises NotImplementedError naming SURVEY.md section 2's
 out-of-scope row instead of silently building something different."""
@@ -10,6 +12,7 @@ from ..decoders.bilinear_diag import BilinearDiag
 from ..encoders.affine_transform import AffineTransform
 from ..encoders.message_gcns.gcn_basis import BasisGcn
 from ..encoders.message_gcns.gcn_basis_concat import ConcatGcn
+from ..encoders.message_gcns.gcn_basis_plus_diag import BasisGcnWithDiag
 from ..encoders.message_gcns.gcn_basis_times_diag import BasisGcnTimesDiag
 from ..encoders.relation_embedding import RelationEmbedding
 from ..extras.graph_representations import Representation
@@ -30,10 +33,16 @@ def build_encoder(encoder_settings, triples):
         raise NotImplementedError("UseInputTransform must be Yes or No (the reference reads it unconditionally, "
                                   "model_builder.py:140), got %r" % (input_transform,))
     # the reference picks the layer class in this order (model_builder.py:285-294): AddDiagonal, DiagonalCoefficients,
-    # StoreEdgeData, Concatenation -- AddDiagonal, ahead of DiagonalCoefficients, stays refused; Concatenation, behind it,
-    # loses to it; StoreEdgeData=Yes stays refused whatever the layer (the training loop reads it too, train.py:242)
-    if _flag(encoder_settings, 'AddDiagonal') == "Yes":
-        raise NotImplementedError("AddDiagonal=Yes selects a reference variant outside the hot path")
+    # StoreEdgeData, Concatenation -- AddDiagonal (BasisGcnWithDiag) would silently override DiagonalCoefficients and
+    # Concatenation: a file that sets it beside either contradicts itself and is refused (honouring the reference's precedence
+    # is a follow-up); Concatenation, behind DiagonalCoefficients, loses to it; StoreEdgeData=Yes stays refused
+    # whatever the layer (the training loop reads it too, train.py:242)
+    add_diag = _flag(encoder_settings, 'AddDiagonal') == "Yes"
+    if add_diag:
+        for key in ('Concatenation', 'DiagonalCoefficients'):
+            if _flag(encoder_settings, key) == "Yes":
+                raise NotImplementedError("AddDiagonal=Yes with %s=Yes: the reference lets AddDiagonal win silently "
+                                          "(model_builder.py:285-292); the contradictory file is refused" % key)
     times_diag = _flag(encoder_settings, 'DiagonalCoefficients') == "Yes"
     concat = _flag(encoder_settings, 'Concatenation') == "Yes" and not times_diag
     if input_transform == "No" and concat:
@@ -57,6 +66,13 @@ def build_encoder(encoder_settings, triples):
         raise NotImplementedError("DiagonalCoefficients=Yes with SkipConnections=Highway: highway layers around "
                                   "BasisGcnTimesDiag are not built")
 
+    if add_diag and input_transform == "No":
+        raise NotImplementedError("AddDiagonal=Yes with UseInputTransform=No: the one-hot first layer of "
+                                  "BasisGcnWithDiag is not built")
+    if add_diag and skip == 'Highway':
+        raise NotImplementedError("AddDiagonal=Yes with SkipConnections=Highway: highway layers around "
+                                  "BasisGcnWithDiag are not built")
+
     graph = Representation(triples, encoder_settings)
     input_shape = [int(encoder_settings['EntityCount']), int(encoder_settings['InternalEncoderDimension'])]
     internal_shape = [int(encoder_settings['InternalEncoderDimension']),
@@ -78,7 +94,9 @@ def build_encoder(encoder_settings, triples):
 
 def apply_basis_gcn(encoder_settings, encoding, internal_shape, layers, onehot_first=False):
     concat = 'Concatenation' in encoder_settings and encoder_settings['Concatenation'] == "Yes"
-    if _flag(encoder_settings, 'DiagonalCoefficients') == "Yes":       # ahead of Concatenation (model_builder.py:287-292)
+    if _flag(encoder_settings, 'AddDiagonal') == "Yes":                # the first flag checked (model_builder.py:285-286)
+        layer_class = BasisGcnWithDiag
+    elif _flag(encoder_settings, 'DiagonalCoefficients') == "Yes":     # ahead of Concatenation (model_builder.py:287-292)
         layer_class = BasisGcnTimesDiag
     else:
         layer_class = ConcatGcn if concat else BasisGcn

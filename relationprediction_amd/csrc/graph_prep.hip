@@ -544,7 +544,7 @@ rgcn_status graph_alloc(rgcn_ctx* c, GraphBufs& g) {
     RGCN_TRY(dmalloc(c, g.pool, &g.s_rel, M, false));
     RGCN_TRY(dmalloc(c, g.pool, &g.s_norm, M, false));
   }
-  if (c->kind == RGCN_KIND_BASIS) {
+  if (c->kind == RGCN_KIND_BASIS || c->kind == RGCN_KIND_BASIS_PDIAG) {
     RGCN_TRY(dmalloc(c, g.pool, &g.has_dir, 2 * V, false));
     RGCN_TRY(dmalloc(c, g.pool, &g.unit_ptr, 2 * (V + 1), false));
     RGCN_TRY(dmalloc(c, g.pool, &g.unit_rows, 2 * V, false));

@@ -347,7 +347,8 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     RGCN_FAIL(c, RGCN_ERR_INVALID, "EntityCount, RelationCount, dimension, NumberOfLayers and "
                                    "NumberOfBasisFunctions must be positive");
   if (!(f.keep_prob > 0.0f && f.keep_prob <= 1.0f)) RGCN_FAIL(c, RGCN_ERR_INVALID, "DropoutKeepProbability must be in (0,1]");
-  if (f.kind != RGCN_KIND_BLOCK && f.kind != RGCN_KIND_BASIS && f.kind != RGCN_KIND_BASIS_TDIAG)
+  if (f.kind != RGCN_KIND_BLOCK && f.kind != RGCN_KIND_BASIS && f.kind != RGCN_KIND_BASIS_TDIAG &&
+      f.kind != RGCN_KIND_BASIS_PDIAG)
     RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown kind");
   if (f.norm_mode < 0 || f.norm_mode > RGCN_NORM_LOCAL) RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown norm_mode");
   if (f.world < 1 || f.rank < 0 || f.rank >= f.world) RGCN_FAIL(c, RGCN_ERR_INVALID, "need 0 <= rank < world");
@@ -370,6 +371,21 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     if (f.num_bases > 64) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "NumberOfBasisFunctions > 64 (basis_tdiag)");
     if (2 * (int64_t)f.num_entities * f.num_bases * (int64_t)f.dim >= ((int64_t)1 << 31))
       RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_TDIAG: 2 x EntityCount x NumberOfBasisFunctions x dimension must be "
+                                         "below 2^31");
+  }
+  if (f.kind == RGCN_KIND_BASIS_PDIAG) {
+    // BasisGcnWithDiag (basis_pdiag.hip): one GPU, embedding input, no highway layers
+    if (f.world > 1)
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_PDIAG on a sharded context (the mixing table, the diagonal aggregate "
+                                         "and the diagonal tables' gradient have no exchange points)");
+    if (c->onehot)
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_PDIAG with RGCN_INPUT_ONEHOT (the one-hot first layer of "
+                                         "BasisGcnWithDiag is not built)");
+    if (c->highway)
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_PDIAG with RGCN_SKIP_HIGHWAY (not built)");
+    if (f.num_bases > 64) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "NumberOfBasisFunctions > 64 (basis_pdiag)");
+    if (2 * (int64_t)f.num_entities * f.num_bases * (int64_t)f.dim >= ((int64_t)1 << 31))
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_PDIAG: 2 x EntityCount x NumberOfBasisFunctions x dimension must be "
                                          "below 2^31");
   }
   if (c->onehot) {
@@ -408,7 +424,7 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     c->B = f.num_bases;
     if (c->B > 64) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "NumberOfBasisFunctions > 64 (basis)");
   }
-  const bool tdiag = c->kind == RGCN_KIND_BASIS_TDIAG;
+  const bool tdiag = c->kind == RGCN_KIND_BASIS_TDIAG, pdiag = c->kind == RGCN_KIND_BASIS_PDIAG;
   // equal row chunks (the reduce-scatter / all-gather want them equal): rank g finishes rows [g * shard_rows, +shard_rows)
   c->shard_rows = (c->V + c->world - 1) / c->world;
   c->V_pad = c->shard_rows * c->world;
@@ -521,17 +537,25 @@ static rgcn_status create_impl(rgcn_ctx* c) {
       else RGCN_TRY(dmalloc(c, c->pool, &lb.grel, 2 * per_dir, true));
       RGCN_TRY(dmalloc(c, c->pool, &lb.coef, 2 * R * c->B, true));
       RGCN_TRY(dmalloc(c, c->pool, &lb.gcoef, 2 * R * c->B, true));
-      add_param(c, "W_f" + sl, {(int64_t)d, c->B, (int64_t)d}, lb.wrel, lb.grel, LAYOUT_BASIS_T);
-      add_param(c, "W_b" + sl, {(int64_t)d, c->B, (int64_t)d}, lb.wrel + per_dir, lb.grel + per_dir, LAYOUT_BASIS_T);
+      // (BASIS_PDIAG: the two direction groups swapped -- the forward-direction units contract with W_backward)
+      const size_t off_f = pdiag ? per_dir : 0, off_b = pdiag ? 0 : per_dir;
+      add_param(c, "W_f" + sl, {(int64_t)d, c->B, (int64_t)d}, lb.wrel + off_f, lb.grel + off_f, LAYOUT_BASIS_T);
+      add_param(c, "W_b" + sl, {(int64_t)d, c->B, (int64_t)d}, lb.wrel + off_b, lb.grel + off_b, LAYOUT_BASIS_T);
       add_param(c, "C_f" + sl, {(int64_t)R, c->B}, lb.coef, lb.gcoef, LAYOUT_PLAIN);
       add_param(c, "C_b" + sl, {(int64_t)R, c->B}, lb.coef + R * c->B, lb.gcoef + R * c->B, LAYOUT_PLAIN);
+      if (pdiag) {      // gcn_basis_plus_diag.py:42-47: the BACKWARD table comes first in get_weights(); device: [2R][d], forward first
+        RGCN_TRY(dmalloc(c, c->pool, &lb.dtab, 2 * R * d, true));
+        RGCN_TRY(dmalloc(c, c->pool, &lb.gdtab, 2 * R * d, true));
+        add_param(c, "D_b" + sl, {(int64_t)R, (int64_t)d}, lb.dtab + R * d, lb.gdtab + R * d, LAYOUT_PLAIN);
+        add_param(c, "D_f" + sl, {(int64_t)R, (int64_t)d}, lb.dtab, lb.gdtab, LAYOUT_PLAIN);
+      }
     }
     RGCN_TRY(dmalloc(c, c->pool, &lb.wself, d * d, true));
     {      // fragment tables (allocated here: a capture may be the first call that needs them)
       const size_t ws = 16 * gemm_bfrag_words((int)d, (int)d);
       RGCN_TRY(dmalloc(c, c->pool, &lb.wself_nn, ws, false));
       RGCN_TRY(dmalloc(c, c->pool, &lb.wself_nt, ws, false));
-      if (c->kind == RGCN_KIND_BASIS) {
+      if (c->kind == RGCN_KIND_BASIS || pdiag) {
         const int Bd = c->B * (int)d;
         RGCN_TRY(dmalloc(c, c->pool, &lb.wrel_nn, 2 * 16 * gemm_bfrag_words(Bd, (int)d), false));
         RGCN_TRY(dmalloc(c, c->pool, &lb.wrel_nt, 2 * 16 * gemm_bfrag_words((int)d, Bd), false));
@@ -543,7 +567,7 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     RGCN_TRY(dmalloc(c, c->pool, &lb.gbias, d, true));
     add_param(c, "W_self" + sl, {(int64_t)d, (int64_t)d}, lb.wself, lb.gwself, LAYOUT_PLAIN);
     add_param(c, "b" + sl, {(int64_t)d}, lb.bias, lb.gbias, LAYOUT_PLAIN);
-    c->params.back().no_grad = !tdiag;      // (BasisGcnTimesDiag adds its bias, gcn_basis_times_diag.py:86)
+    c->params.back().no_grad = !(tdiag || pdiag);      // (BasisGcnTimesDiag and BasisGcnWithDiag add their bias)
     if (c->highway) {      // HighwayLayer.local_get_weights (highway_layer.py): [W, b], behind the layer it wraps
       RGCN_TRY(dmalloc(c, c->pool, &lb.whw, d * d, true));
       RGCN_TRY(dmalloc(c, c->pool, &lb.gwhw, d * d, true));
@@ -607,7 +631,22 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     const size_t s2 = (size_t)std::max(16, auto_split_k((int)zc, (int)d, (int)V)) * zc * d;
     if (s2 > slab) slab = s2;
     c->slab_dw_floats = max_rel_chunks * (size_t)c->B;
-    RGCN_TRY(dmalloc(c, c->pool, &c->slab_dw, c->slab_dw_floats, false));
+    if (pdiag) {
+      // the chunk slabs of dC [chunks][B] and, behind them at a 16-byte boundary, of dD [chunks][d]; the mixing table of
+      // every layer, the diagonal aggregate, da and the row-local part of dH
+      const size_t dc = (max_rel_chunks * (size_t)c->B + 3) / 4 * 4;
+      c->slab_dw_floats = dc + max_rel_chunks * d;
+      c->pdiag_slab_chunks = max_rel_chunks;
+      RGCN_TRY(dmalloc(c, c->pool, &c->slab_dw, c->slab_dw_floats, false));
+      c->pdiag_slab_dd = c->slab_dw + dc;
+      c->pdiag_a.assign(c->L + 1, nullptr);
+      for (int l = 1; l <= c->L; ++l) RGCN_TRY(dmalloc(c, c->pool, &c->pdiag_a[l], 2 * V * (size_t)c->B, true));
+      RGCN_TRY(dmalloc(c, c->pool, &c->pdiag_da, 2 * V * (size_t)c->B, true));
+      RGCN_TRY(dmalloc(c, c->pool, &c->pdiag_agg, V * d, true));
+      RGCN_TRY(dmalloc(c, c->pool, &c->pdiag_dh, V * d, true));
+    } else {
+      RGCN_TRY(dmalloc(c, c->pool, &c->slab_dw, c->slab_dw_floats, false));
+    }
   }
   c->slab_floats = slab;
   RGCN_TRY(dmalloc(c, c->pool, &c->slab, slab, true));
@@ -1190,6 +1229,9 @@ rgcn_status rgcn_capture_begin(rgcn_ctx* c) {
   if (c->kind == RGCN_KIND_BASIS_TDIAG)
     RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "rgcn_capture_begin: capture on an RGCN_KIND_BASIS_TDIAG context is not supported (a "
                                        "captured step of this kind has never been replayed against a reference)");
+  if (c->kind == RGCN_KIND_BASIS_PDIAG)
+    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "rgcn_capture_begin: capture on an RGCN_KIND_BASIS_PDIAG context is not supported (a "
+                                       "captured step of this kind has never been replayed against a reference)");
   if (c->world > 1 && knob("RGCN_CAPTURE_SHARDED", 0) != 1)
     RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "capture on a sharded context is experimental (never run against real RCCL on "
                                        "several GPUs): the devtools build enables it with RGCN_CAPTURE_SHARDED=1");
@@ -1393,6 +1435,13 @@ static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* byte
       if (c->kind != RGCN_KIND_BASIS_TDIAG) RGCN_FAIL(c, RGCN_ERR_STATE, "not an RGCN_KIND_BASIS_TDIAG context");
       if (c->tdiag_last < 1) RGCN_FAIL(c, RGCN_ERR_STATE, "no rgcn_forward_layer_finish has run");
       *p = c->tdiag_P[c->tdiag_last]; *bytes = (int64_t)2 * c->V * c->B * c->d * 4; return RGCN_OK;
+    case RGCN_BUF_PDIAG_MIX:
+    case RGCN_BUF_PDIAG_AGG:
+      if (c->kind != RGCN_KIND_BASIS_PDIAG) RGCN_FAIL(c, RGCN_ERR_STATE, "not an RGCN_KIND_BASIS_PDIAG context");
+      if (c->pdiag_last < 1) RGCN_FAIL(c, RGCN_ERR_STATE, "no rgcn_forward_layer_finish has run");
+      if (which == RGCN_BUF_PDIAG_MIX) { *p = c->pdiag_a[c->pdiag_last]; *bytes = (int64_t)2 * c->V * c->B * 4; }
+      else { *p = c->pdiag_agg; *bytes = Vd; }
+      return RGCN_OK;
     default: RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown buffer id");
   }
 }

@@ -179,6 +179,10 @@ struct LayerBufs {
   // coef = [2R][B][d]; tdiag_g = sigmoid(coef), rebuilt when the weights change (basis_tdiag.hip)
   float* tdiag_g = nullptr;
   uint64_t tdiag_g_version = ~0ull;
+  // BASIS_PDIAG: wrel / grel / coef / gcoef / the fragment tables as BASIS, except that the two direction groups of wrel
+  // and grel are SWAPPED (group 0 = W_backward, group 1 = W_forward: the forward-direction units contract with W_backward,
+  // basis_pdiag.hip); dtab = [2R][d] (first R = D_types_forward), gdtab its gradient
+  float *dtab = nullptr, *gdtab = nullptr;
 };
 
 struct GraphBufs {
@@ -368,6 +372,16 @@ struct rgcn_ctx {
   float* tdiag_dP = nullptr;
   float* tdiag_dh = nullptr;
   int tdiag_last = 0;                     // the layer the last fwd_layer_finish ran (RGCN_BUF_TDIAG_PRODUCTS)
+  // RGCN_KIND_BASIS_PDIAG (basis_pdiag.hip; one GPU, embedding input, no highway): the mixing table a_l [2][V][B] of every
+  // layer (the backward pass reads it), the diagonal aggregate [V,d] of the layer run last, da [2][V][B], the row-local
+  // part of dH [V,d], the chunk slabs of dD ([chunks][d], inside slab_dw behind the [chunks][B] of dC)
+  std::vector<float*> pdiag_a;            // [1..L]
+  float* pdiag_agg = nullptr;
+  float* pdiag_da = nullptr;
+  float* pdiag_dh = nullptr;
+  float* pdiag_slab_dd = nullptr;
+  size_t pdiag_slab_chunks = 0;           // chunks either slab holds
+  int pdiag_last = 0;                     // the layer the last fwd_layer_finish ran (RGCN_BUF_PDIAG_MIX / _AGG)
   bool onehot = false;          // featureless first layer (RGCN_INPUT_ONEHOT): no W_emb / b_emb / H_0, layer 1 is basis_onehot.hip
   int row_lo = 0, row_hi = 0;   // row shard of this rank: [rank * shard_rows, +shard_rows) cut at V
   int shard_rows = 0;           // ceil(V / world): equal chunks for the reduce-scatter / all-gather
@@ -616,6 +630,21 @@ rgcn_status tdiag_dp(rgcn_ctx* c, int layer, const float* D, float* dP);
 rgcn_status tdiag_dcoef(rgcn_ctx* c, int layer, const float* P, const float* D);
 // out = (base + dh[0] + dh[1]) * (gate > 0), out2 = out * dropout(drop2): the epilogue of the layer's backward pass
 rgcn_status tdiag_dh_join(rgcn_ctx* c, const float* dh, const CombineArgs& ca);
+
+// ---- basis_pdiag.hip: the layer kernels of RGCN_KIND_BASIS_PDIAG (the dense products are the basis kind's, the schedule's)
+// one walk over every row's slots: a[dir][v][b] = sum n C[rel,b], agg[v] = sum n D[rel] * Hin[src], and the row's own
+// compacted unit rows Zc[(v,dir),b,:] = a[dir][v][b] Hin[v,:] for the units that exist
+rgcn_status pdiag_rows_forward(rgcn_ctx* c, int layer, const float* Hin, float* Zc, float* a, float* agg);
+// out = act(((dropout(base) + the row's unit products of both directions) + agg) + bias)
+rgcn_status pdiag_epilogue(rgcn_ctx* c, int layer, const float* prod, const float* agg, const CombineArgs& ca);
+// row-local: da[dir][v][b] = <Hin[v], dZc[(v,dir),b,:]> (0 without a unit), dh[v] = sum_dir sum_b a[dir][v][b] dZc[(v,dir),b,:]
+rgcn_status pdiag_row_backward(rgcn_ctx* c, const float* Hin, const float* dZc, const float* a, float* da, float* dh);
+// gcoef[rel,b] = sum over the relation's messages of n da[dir][dst][b]  (chunk slabs, chunk order)
+rgcn_status pdiag_dcoef(rgcn_ctx* c, int layer, const float* da);
+// gdtab[rel,:] = sum over the relation's messages of n Hin[src,:] * D[dst,:]  (chunk slabs, compensated chunk reduce)
+rgcn_status pdiag_ddiag(rgcn_ctx* c, int layer, const float* Hin, const float* D);
+// out = ((base + dh) + sum over the messages row v sends of n dtab[rel] * D[dst]) * (gate > 0), out2 = out * dropout(drop2)
+rgcn_status pdiag_dh_join(rgcn_ctx* c, int layer, const float* D, const float* dh, const CombineArgs& ca);
 
 // ---- basis_onehot.hip: the featureless first layer (rgcn_config::input_mode == RGCN_INPUT_ONEHOT, basis kind): layer 1's
 // weights are per-entity tables [2][V][B][d] (LayerBufs::wrel) and W_self [V,d], messages are table rows

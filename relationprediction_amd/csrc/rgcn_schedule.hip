@@ -80,7 +80,7 @@ static rgcn_status refresh_weight_fragments(rgcn_ctx* c) {
     if (!lb.wself_nn || !lb.wself_nt) continue;
     jobs.push_back(PresplitJob{lb.wself, lb.wself_nn, d, d, d, 0});      // H . W_self:      B (k, n) = W[k][n]
     jobs.push_back(PresplitJob{lb.wself, lb.wself_nt, d, d, d, 1});      // dS . W_self^T:   B (k, n) = W[n][k]
-    if (c->kind == RGCN_KIND_BASIS && lb.wrel_nn && lb.wrel_nt)
+    if ((c->kind == RGCN_KIND_BASIS || c->kind == RGCN_KIND_BASIS_PDIAG) && lb.wrel_nn && lb.wrel_nt)
       for (int g = 0; g < 2; ++g) {
         const float* W = lb.wrel + (size_t)g * Bd * d;                   // W'_dir [B.d, d]
         jobs.push_back(PresplitJob{W, static_cast<char*>(lb.wrel_nn) + 16 * g * gemm_bfrag_words(Bd, d), d, Bd, d, 0});
@@ -224,6 +224,32 @@ rgcn_status fwd_layer_partial(rgcn_ctx* c, int l) {
     a.drop = make_drop(c, l, true);
     a.drop2 = make_drop(c, l, false);
     RGCN_TRY(tdiag_rows_forward(c, l, c->tdiag_P[l], a));
+  } else if (c->kind == RGCN_KIND_BASIS_PDIAG) {
+    // basis_pdiag.hip: ONE destination-major walk forms the mixing table a_l, the diagonal aggregate and the rows' own unit
+    // rows Zc[(v,dir),b,:] = a_dir[v,b] H[v,:]; Zc . W' is the basis kind's batched product over the units (LayerBufs::wrel
+    // holds the two groups swapped: forward units x W_backward); the self-loop product beside both on side stream 1; then
+    // H' = relu(dropout(S) + the two unit products + aggregate + b)
+    const int Bd = c->B * d;
+    {
+      StreamScope side(c, 1);
+      RGCN_TRY(gemm_f32(c, "gemm_self_fwd", self));
+    }
+    RGCN_TRY(pdiag_rows_forward(c, l, Hin, c->zsave[l], c->pdiag_a[l], c->pdiag_agg));
+    GemmBatch gb = basis_batch(c, (size_t)V * Bd, (size_t)Bd * d, (size_t)V * d, false);
+    if (c->gemm_mode != 0) gb.bfrag = c->layers[l].wrel_nn;
+    gb.strideBfrag = gemm_bfrag_words(Bd, d);
+    gb.wide = 1;
+    RGCN_TRY(gemm_f32(c, "gemm_basis_fwd", true, false, V, d, Bd, c->zsave[l], Bd, c->layers[l].wrel, d,
+                      c->aggbuf, d, 1, &gb, basis_unit_share(c)));
+    RGCN_TRY(stream_join(c, 1));
+    CombineArgs a;
+    a.add = nullptr; a.msg = nullptr; a.row_ptr = nullptr; a.long_rows = nullptr; a.nlong = nullptr;
+    a.out = dst; a.out2 = nullptr; a.base = c->self_buf; a.gate = nullptr; a.V = V; a.d = d;
+    a.relu = l < c->L ? 1 : 0;
+    a.row_lo = lo; a.row_hi = hi;
+    a.drop = make_drop(c, l, true);
+    a.drop2 = make_drop(c, l, false);
+    RGCN_TRY(pdiag_epilogue(c, l, c->aggbuf, c->pdiag_agg, a));
   } else {
     // aggregate first, per (row, direction) unit: Zc[(v,dir),b,:] = sum n C[rel,b] H[src];
     // pre[v] = dropout(H.W_self)[v] + sum_dir Zc[(v,dir)] . W'_dir  -- two groups of one batched GEMM over the units
@@ -271,6 +297,7 @@ rgcn_status fwd_layer_finish(rgcn_ctx* c, int l) {
     c->hw_last = l;
   }
   if (c->kind == RGCN_KIND_BASIS_TDIAG) c->tdiag_last = l;
+  if (c->kind == RGCN_KIND_BASIS_PDIAG) c->pdiag_last = l;
   if (l == c->L) c->fwd_done = true;
   return RGCN_OK;
 }
@@ -336,7 +363,7 @@ rgcn_status bwd_layer_partial(rgcn_ctx* c, int l) {
   const int rows = hi - lo;
   LayerBufs& lb = c->layers[l];
   const double Mmsg = 2.0 * c->g.E / c->world;
-  const bool narrow_dw = c->kind == RGCN_KIND_BASIS || rows >= 32768;       // (see auto_split_k)
+  const bool narrow_dw = c->kind == RGCN_KIND_BASIS || c->kind == RGCN_KIND_BASIS_PDIAG || rows >= 32768;       // (see auto_split_k)
 
   // epilogue shared by both kinds: (self-loop gradient + relational gradient) -> relu' -> next D / dS
   CombineArgs a;
@@ -500,6 +527,37 @@ rgcn_status bwd_layer_partial(rgcn_ctx* c, int l) {
     RGCN_TRY(gemm_f32(c, "gemm_tdiag_dh", true, true, V, d, Bd, c->tdiag_dP, Bd, lb.wrel, Bd, c->tdiag_dh, d, 1, &gm));
     RGCN_TRY(tdiag_dh_join(c, c->tdiag_dh, a));
     RGCN_TRY(stream_join(c, 0));      // (the next layer rewrites D's buffer, dP and the chunk slabs)
+  } else if (c->kind == RGCN_KIND_BASIS_PDIAG) {
+    const int Bd = c->B * d;
+    // db = the column sums of G = dL/dpre (this layer's bias is added); dD needs H_{l-1} and G only: per relation chunk on
+    // side stream 0, beside the dense products
+    RGCN_TRY(column_sum(c, c->bwd_D, lb.gbias, V, d));
+    {
+      StreamScope side(c, 0);
+      RGCN_TRY(pdiag_ddiag(c, l, Hin, c->bwd_D));
+    }
+    // the dense products are the basis kind's, over the compacted units: G[units], dW'_dir = Zc_dir^T . G[units] beside
+    // dW_self on side stream 1, dZc_dir = G[units] . W'_dir^T on the main stream behind dS . W_self^T
+    RGCN_TRY(basis_gather_units(c, c->bwd_D, c->aggbuf));
+    {
+      StreamScope side(c, 1);
+      RGCN_TRY(self_dw());
+      const GemmBatch gk = basis_batch(c, (size_t)V * Bd, (size_t)V * d, (size_t)Bd * d, true);
+      RGCN_TRY(gemm_f32(c, "gemm_basis_dw", false, false, Bd, d, V, c->zsave[l], Bd, c->aggbuf, d, lb.grel, d,
+                        auto_split_k(2 * Bd, d, V), &gk, basis_unit_share(c)));
+    }
+    RGCN_TRY(self_dh());
+    GemmBatch gm = basis_batch(c, (size_t)V * d, (size_t)Bd * d, (size_t)V * Bd, false);
+    if (c->gemm_mode != 0) gm.bfrag = lb.wrel_nt;
+    gm.strideBfrag = gemm_bfrag_words(d, Bd);
+    RGCN_TRY(gemm_f32(c, "gemm_basis_dz", true, true, V, Bd, d, c->aggbuf, d, lb.wrel, d, c->msgbuf2, Bd, 1, &gm,
+                      basis_unit_share(c)));
+    // row-local: da and the a * dZc part of dH; dC from da per relation chunk; then the source-major diagonal gather joins
+    // the three parts of dH, applies relu' and writes the dropout copy
+    RGCN_TRY(pdiag_row_backward(c, Hin, c->msgbuf2, c->pdiag_a[l], c->pdiag_da, c->pdiag_dh));
+    RGCN_TRY(pdiag_dcoef(c, l, c->pdiag_da));
+    RGCN_TRY(pdiag_dh_join(c, l, c->bwd_D, c->pdiag_dh, a));
+    RGCN_TRY(stream_join(c, 0));      // (the next layer rewrites G's buffer and the dD slabs)
   } else {
     const int Bd = c->B * d;
     // The upstream rows of the units, compacted like Zc (the row operand of dZ, the depth operand of dW')

@@ -27,7 +27,7 @@ MIRRORED = {
     "common": ["auxilliaries", "evaluation", "io", "model_builder", "optimizer_parameter_parser", "settings_reader",
                "shared_functions"],
     "encoders": ["affine_transform", "relation_embedding", "message_gcns", "message_gcns.gcn_basis",
-                 "message_gcns.gcn_basis_concat", "message_gcns.gcn_basis_times_diag", "message_gcns.message_gcn"],
+                 "message_gcns.gcn_basis_concat", "message_gcns.gcn_basis_plus_diag", "message_gcns.gcn_basis_times_diag", "message_gcns.message_gcn"],
     "decoders": ["bilinear_diag"],
     "extras": ["graph_representations"],
     "optimization": ["optimize"],

@@ -43,6 +43,9 @@ class EncoderRuntime(object):
         if self.kind == "basis_tdiag" and (self.highway or affine is None):
             raise NotImplementedError("DiagonalCoefficients=Yes with SkipConnections=Highway or UseInputTransform=No: "
                                       "BasisGcnTimesDiag runs on embedding input without highway layers only")
+        if self.kind == "basis_pdiag" and (self.highway or affine is None):
+            raise NotImplementedError("AddDiagonal=Yes with SkipConnections=Highway or UseInputTransform=No: "
+                                      "BasisGcnWithDiag runs on embedding input without highway layers only")
         s = top.settings
         self.V, self.R = top.entity_count, top.relation_count
         self.d = int(top.shape[1])

@@ -18,9 +18,13 @@
  *   - device memory is owned by the context; `*_device` variants take device
  *     pointers (HIP, same device) that the caller owns and keeps alive until
  *     the next rgcn_sync();
- *   - one context per (process, GPU); a context is not thread-safe; calls are
- *     stream-ordered on the context's own HIP stream and asynchronous unless
- *     they return host data;
+ *   - a process may hold several contexts, on one GPU or on several: a context owns its streams, its device memory and
+ *     its error text, and the only state contexts share is the text of a failed rgcn_create and a pool of idle HIP
+ *     streams that destroyed contexts leave for later ones (both behind a mutex).  Contexts do not order themselves
+ *     against each other: a device pointer one context hands to another (rgcn_rank_energies_device into
+ *     rgcn_rank_mixed_device) is valid once the call that filled it has synchronised or rgcn_sync() has returned on
+ *     the owner.  A context itself is not thread-safe; its calls are stream-ordered on the context's own HIP stream
+ *     and asynchronous unless they return host data;
  *   - all floating point is float32, all indices int32 (reference:
  *     code/extras/graph_representations.py:174, code/common/shared_functions.py:17).
  */
@@ -55,7 +59,26 @@ enum {
 
 /* Encoder.Concatenation=Yes -> ConcatGcn (block-diagonal), else BasisGcn:
  * code/common/model_builder.py:291-294. */
-enum { RGCN_KIND_BLOCK = 0, RGCN_KIND_BASIS = 1, RGCN_KIND_BASIS_TDIAG = 2, RGCN_KIND_BASIS_PDIAG = 3 };
+enum { RGCN_KIND_BLOCK = 0, RGCN_KIND_BASIS = 1, RGCN_KIND_BASIS_TDIAG = 2, RGCN_KIND_BASIS_PDIAG = 3, RGCN_KIND_EMBEDDING = 4 };
+/* RGCN_KIND_EMBEDDING = Encoder.Name=embedding (model_builder.py:27-41; settings/distmult.exp): the DistMult baseline,
+ * RelationEmbedding(AffineTransform(onehot_input=True, use_bias=False, use_nonlinearity=False)).  No graph and no layer:
+ *   - num_layers must be 0 and num_bases 1 (RGCN_ERR_INVALID otherwise); max_edges may be 0; keep_prob and norm_mode are
+ *     checked as for every kind and not used; world > 1, RGCN_INPUT_ONEHOT and RGCN_SKIP_HIGHWAY: RGCN_ERR_UNSUPPORTED;
+ *   - parameters: W_emb [V,d], b_emb [d], W_relation [V,d].  b_emb is created, stored and checkpointed but never read
+ *     (use_bias=False; tf.gradients reports it unconnected): its gradient is all zeros and Adam leaves it alone;
+ *   - the codes ARE W_emb, in train and test mode alike (no bias, no relu, no dropout).  rgcn_forward needs no graph and
+ *     launches nothing; rgcn_codes_device returns the parameter's own storage, so after an optimizer step the codes are
+ *     the updated table -- what a new forward pass would return; rgcn_get_activation(0) returns the codes, any other
+ *     layer is RGCN_ERR_INVALID;
+ *   - rgcn_backward / rgcn_backward_device set the gradient of W_emb to dcodes; rgcn_dcodes_device IS that gradient's
+ *     storage, so the device decoder writes it in place;
+ *   - rgcn_train_step_device(ctx, NULL, 0, x, y, N, ...) = decoder loss + gradients, then clip + Adam if configured; a
+ *     non-NULL triple pointer or num_edges != 0 is RGCN_ERR_INVALID;
+ *   - RGCN_ERR_UNSUPPORTED, the message naming the kind: rgcn_set_graph*, rgcn_prefetch_graph*, rgcn_step_device,
+ *     rgcn_train_step_minibatch_device, rgcn_neighborhood_reserve, the phase API (rgcn_forward_begin ... rgcn_backward_end),
+ *     rgcn_set_relation_owner, rgcn_capture_begin; rgcn_read_buffer knows RGCN_BUF_RANK_ENERGIES only (RGCN_ERR_STATE);
+ *   - unchanged: rgcn_decoder_*, rgcn_negative_sample_device, rgcn_optimizer_*, rgcn_rank_device, rgcn_rank_mixed_device,
+ *     rgcn_topk_device, parameters, device memory, timer and profile. */
 /* RGCN_KIND_BASIS_TDIAG = Encoder.DiagonalCoefficients=Yes -> BasisGcnTimesDiag
  * (code/encoders/message_gcns/gcn_basis_times_diag.py; model_builder.py:287-288, ahead of Concatenation): the
  * coefficient of a message is a VECTOR per (relation, basis) over the output channels,
@@ -175,7 +198,7 @@ typedef struct rgcn_config {
   int32_t num_entities;   /* V = EntityCount */
   int32_t num_relations;  /* R = RelationCount */
   int32_t dim;            /* d = InternalEncoderDimension (= CodeDimension, UseOutputTransform=No) */
-  int32_t num_layers;     /* L = NumberOfLayers */
+  int32_t num_layers;     /* L = NumberOfLayers (RGCN_KIND_EMBEDDING: 0) */
   int32_t kind;           /* RGCN_KIND_* */
   int32_t num_bases;      /* NumberOfBasisFunctions: block count nb (BLOCK, d % nb == 0) or B (BASIS, BASIS_TDIAG, BASIS_PDIAG) */
   float   keep_prob;      /* DropoutKeepProbability (self-loop dropout, train mode only) */
@@ -282,7 +305,9 @@ rgcn_status rgcn_get_codes(rgcn_ctx* ctx, float* host, int64_t count);          
 /* RGCN_INPUT_ONEHOT: there is no H_0 (message_gcn.py:28-36 hands the layer the vertex ids); layer 0 is RGCN_ERR_INVALID */
 rgcn_status rgcn_get_activation(rgcn_ctx* ctx, int32_t layer, float* host, int64_t count); /* H_0..H_L */
 rgcn_status rgcn_get_dropout_mask(rgcn_ctx* ctx, int32_t layer /*1..L*/, uint8_t* host, int64_t count);
-const float* rgcn_codes_device(rgcn_ctx* ctx);                                      /* device H_L */
+const float* rgcn_codes_device(rgcn_ctx* ctx);                                      /* device H_L (RGCN_KIND_EMBEDDING: W_emb's
+                                                                                       own storage -- after an optimizer step the
+                                                                                       updated table) */
 
 /* ---- backward: tf.gradients(loss, weights) restricted to the encoder (abstract.py:117-118) -----
  * dcodes = dL/dH_L [V,d] (the decoder's gradient w.r.t. subject+object codes, already summed).
@@ -369,6 +394,29 @@ rgcn_status rgcn_rank_reserve(rgcn_ctx* ctx, int64_t max_queries);
 rgcn_status rgcn_rank_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t num_queries, int32_t predict_object,
                              const int64_t* filter_ptr_dev, const int32_t* filter_idx_dev, int32_t* raw_rank_dev,
                              int32_t* filtered_rank_dev);
+
+/* ---- ensemble ranks: the rank of the gold entity under the weighted sum of TWO models' scores -----------------
+ * The reference's R-GCN+ (code/tools/ensemble.py, WeightEnsemble.combine_prediction) on score matrices that never leave
+ * the device.  rgcn_rank_energies_device = the device pointer of RGCN_BUF_RANK_ENERGIES (NULL before rgcn_rank_reserve).
+ * partner_energies = float [num_queries, V], row-major: the OTHER model's energies for the same queries in the same
+ * order -- another context's rgcn_rank_energies_device or any buffer on this context's device; the caller guarantees
+ * that it is complete before the call and untouched until the call returns.
+ * The call scores the queries exactly as rgcn_rank_device does (same query kernel, same GEMM, same buffer:
+ * RGCN_BUF_RANK_ENERGIES holds the context's own energies afterwards, unmodified) and ranks on
+ *     m[e] = (float)((double)weight * s_own[e] + (1.0 - (double)weight) * s_partner[e])
+ * with s_* the fp32 sigmoid of each energy (evaluated in double, rounded once, as rgcn_rank_device's) and the mix
+ * evaluated in double without fused multiply-add and rounded once:
+ *     raw_rank[i]      = #{e : m[e] >= m[gold]}
+ *     filtered_rank[i] = raw_rank[i] - #{e in the row's filter list : m[e] >= m[gold]} + 1.
+ * weight = 1 returns rgcn_rank_device's ranks bit for bit (for finite partner energies); weight = 0 the partner's.
+ * Saturated scores tie, as there.  ONE chunk only: num_queries above what rgcn_rank_reserve sized is RGCN_ERR_INVALID
+ * (the partner's buffer has its own chunking).  weight outside [0, 1], or NaN: RGCN_ERR_INVALID.  Ids and filter lists
+ * are validated as by rgcn_rank_device, through the same check kernel; RGCN_ERR_STATE before a forward pass or before
+ * rgcn_rank_reserve.  Synchronises at the end, as rgcn_rank_device does. */
+const float* rgcn_rank_energies_device(rgcn_ctx* ctx);
+rgcn_status rgcn_rank_mixed_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t num_queries, int32_t predict_object,
+                                   const float* partner_energies_dev, float weight, const int64_t* filter_ptr_dev,
+                                   const int32_t* filter_idx_dev, int32_t* raw_rank_dev, int32_t* filtered_rank_dev);
 
 /* ---- prediction: the k most plausible entities of a query, best first ------------------------------------
  * What a trained link predictor is asked: given (s, r, ?) or (?, r, o), which entities complete it.  Selects from the

@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "librgcn.so")
 
 ABI_VERSION = 1
 KIND_BLOCK, KIND_BASIS, KIND_BASIS_TDIAG, KIND_BASIS_PDIAG = 0, 1, 2, 3
+KIND_EMBEDDING = 4           # Encoder.Name=embedding: no graph, no layers, the codes are W_emb (RGCN_KIND_EMBEDDING)
 NORM_INTENDED, NORM_TF_AS_EXECUTED, NORM_NONE, NORM_LOCAL = 0, 1, 2, 3
 BUF_EXCHANGE, BUF_SELF, BUF_DSELF_EXCHANGE, BUF_INDEG, BUF_OUTDEG, BUF_ROWPTR, BUF_NORM_EXCHANGE, \
     BUF_DBASIS_EXCHANGE, BUF_PERM_VERTEX, BUF_PERM_RELATION, BUF_RANK_ENERGIES, BUF_MSG_NORM, BUF_HIGHWAY_INNER, \
@@ -26,7 +27,7 @@ BUF_PDIAG_MIX = 15           # basis_pdiag contexts: [2, V, B], the mixing table
 BUF_PDIAG_AGG = 16           # basis_pdiag contexts: [V, d], the diagonal aggregate of the layer run last
 
 KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS, "basis_tdiag": KIND_BASIS_TDIAG,
-         "basis_pdiag": KIND_BASIS_PDIAG}
+         "basis_pdiag": KIND_BASIS_PDIAG, "embedding": KIND_EMBEDDING}
 NORMS = {"intended": NORM_INTENDED, "tf_as_executed": NORM_TF_AS_EXECUTED, "none": NORM_NONE, "local": NORM_LOCAL}
 
 INPUT_EMBEDDING, INPUT_ONEHOT = 0, 1
@@ -108,6 +109,8 @@ _SIGS = {
     "rgcn_negative_sample_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, _P, _P]),
     "rgcn_rank_reserve": (C.c_int32, [_P, C.c_int64]),
     "rgcn_rank_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
+    "rgcn_rank_energies_device": (_P, [_P]),
+    "rgcn_rank_mixed_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, C.c_float, _P, _P, _P, _P]),
     "rgcn_topk_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rgcn_optimizer_step": (C.c_int32, [_P]),
     "rgcn_optimizer_norm_partial": (C.c_int32, [_P]),
@@ -279,6 +282,8 @@ class NeighborhoodSampler:
 
 class Engine:
     """One rgcn_ctx: the encoder (input layer + L relational graph-convolution layers) on one GPU.
+    kind "embedding" with num_layers 0 and num_bases 1: the graph-less DistMult baseline (Encoder.Name=embedding), whose
+    codes are W_emb itself -- no set_graph, train_step_device(None, 0, ...); RGCN_KIND_EMBEDDING in include/rgcn.h.
     input_mode "embedding": AffineTransform under the layers (UseInputTransform=Yes); "onehot": no input layer, the
     first basis layer reads per-entity tables (UseInputTransform=No; include/rgcn.h RGCN_INPUT_ONEHOT).
     skip "highway": every layer wrapped in a highway layer (SkipConnections=Highway; RGCN_SKIP_HIGHWAY), created through
@@ -574,6 +579,56 @@ class Engine:
         self._check(self.lib.rgcn_copy_to_host(self.ctx, _ptr(out), C.c_void_p(base + off_out), 8 * n))
         return out[:n].copy(), out[n:].copy()
 
+    def rank_energies_device(self):
+        """device address of RGCN_BUF_RANK_ENERGIES (the [reserved queries, V] energies of the chunk scored last), or None
+        before rank_reserve: what another engine's ranks_mixed takes as `partner` once this one has synchronised"""
+        p = self.lib.rgcn_rank_energies_device(self.ctx)
+        return int(p) if p else None
+
+    def ranks_mixed(self, triples, predict_object, partner, weight, filter_ptr, filter_idx):
+        """Raw and filtered ranks under weight * own score + (1 - weight) * partner score (include/rgcn.h
+        rgcn_rank_mixed_device).  partner: the other model's energies for the same queries in the same order -- a
+        float32 [N, V] numpy array (uploaded), a DeviceBuffer, or a device address (rank_energies_device() of another
+        engine on the same GPU, complete and left alone until this call returns).  One chunk: N <= the reserve."""
+        x = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
+        n = len(x)
+        if n == 0:
+            return np.zeros(0, np.int32), np.zeros(0, np.int32)
+        fp = np.ascontiguousarray(filter_ptr, dtype=np.int64)
+        fi = np.ascontiguousarray(filter_idx, dtype=np.int32)
+        assert fp.shape == (n + 1,) and fp[-1] == len(fi)
+        own = None
+        if isinstance(partner, np.ndarray):
+            e = np.ascontiguousarray(partner, dtype=np.float32)
+            if e.shape != (n, self.V):
+                raise ValueError("partner energies must be [%d, %d], not %s" % (n, self.V, e.shape))
+            own = DeviceBuffer(self, e.nbytes).upload(e)
+            pp = own.ptr
+        elif isinstance(partner, DeviceBuffer):
+            pp = partner.ptr
+        else:
+            pp = C.c_void_p(int(partner))
+        try:
+            xd = DeviceBuffer(self, x.nbytes).upload(x)
+            fpd = DeviceBuffer(self, fp.nbytes).upload(fp)
+            fid = DeviceBuffer(self, max(fi.nbytes, 4))
+            if fi.nbytes:
+                self.copy_to_device(fid, fi)
+            out = DeviceBuffer(self, 8 * n)
+            base = out.ptr.value
+            try:
+                self._check(self.lib.rgcn_rank_mixed_device(self.ctx, xd.ptr, n, 1 if predict_object else 0, pp,
+                                                            C.c_float(float(weight)), fpd.ptr, fid.ptr, C.c_void_p(base),
+                                                            C.c_void_p(base + 4 * n)))
+                r = out.download(np.int32, (2 * n,))
+            finally:
+                for b in (xd, fpd, fid, out):
+                    b.free()
+        finally:
+            if own is not None:
+                own.free()
+        return r[:n].copy(), r[n:].copy()
+
     def topk(self, queries, predict_object, k, exclude_ptr=None, exclude_idx=None):
         """The k best completions of every query on the codes of the last forward, best first (include/rgcn.h
         rgcn_topk_device): (idx int32 [N,k], energy float32 [N,k]), rows short of k answers padded with (-1, -inf).
@@ -631,7 +686,9 @@ class Engine:
         self._check(self.lib.rgcn_optimizer_apply(self.ctx))
 
     def train_step_device(self, triples_dev, num_edges, x_dev, y_dev, num_triples, seed=0, reg_param=0.01):
-        self._check(self.lib.rgcn_train_step_device(self.ctx, triples_dev.ptr, int(num_edges), x_dev.ptr, y_dev.ptr,
+        """triples_dev None (with num_edges 0): the graph-less step of an "embedding" engine"""
+        self._check(self.lib.rgcn_train_step_device(self.ctx, triples_dev.ptr if triples_dev is not None else None,
+                                                    int(num_edges), x_dev.ptr, y_dev.ptr,
                                                     int(num_triples), C.c_uint64(seed), C.c_float(reg_param)))
         self.num_edges = int(num_edges)
 

@@ -7,7 +7,10 @@ conditions, and with Concatenation=No and DiagonalCoefficients=No only: the refe
 silently, a contradictory file is refused here) -- UseInputTransform=Yes (exactly
 settings/gcn_block.exp and settings/gcn_basis.exp) or, for the basis kind, UseInputTransform=No: the featureless encoder
 whose first layer reads one-hot entity ids (:140-165,277-283); everything else raises NotImplementedError naming SURVEY.md section 2's
-out-of-scope row instead of silently building something different."""
+out-of-scope row instead of silently building something different.  `Name=embedding` (settings/distmult.exp; :27-41) builds
+the graph-less DistMult baseline, RelationEmbedding over the bias-free lookup AffineTransform; a file that says
+`Name=embedding` and also carries keys of a graph-convolution stack (NumberOfLayers, Concatenation, ...) is refused as
+contradictory rather than having its layers dropped silently."""
 from ..decoders.bilinear_diag import BilinearDiag
 from ..encoders.affine_transform import AffineTransform
 from ..encoders.message_gcns.gcn_basis import BasisGcn
@@ -23,11 +26,30 @@ def _flag(settings, key, default="No"):
     return settings[key] if key in settings else default
 
 
+# Keys of the [Encoder] section that configure a stack of graph-convolution layers.  The reference's `embedding` branch reads
+# none of them (model_builder.py:27-41): a file that names the graph-less encoder AND describes a layer stack would get its
+# layers dropped silently, so -- as with AddDiagonal beside Concatenation below -- the contradictory file is refused.
+_LAYER_STACK_KEYS = ('NumberOfLayers', 'NumberOfBasisFunctions', 'InternalEncoderDimension', 'DropoutKeepProbability',
+                     'UseInputTransform', 'UseOutputTransform', 'Concatenation', 'AddDiagonal', 'DiagonalCoefficients',
+                     'SkipConnections', 'StoreEdgeData', 'RandomInput', 'PartiallyRandomInput')
+
+
 def build_encoder(encoder_settings, triples):
     name = encoder_settings['Name']
+    if name == "embedding":
+        stack_keys = [key for key in _LAYER_STACK_KEYS if key in encoder_settings]
+        if stack_keys:
+            raise NotImplementedError("Name=embedding beside %s: the embedding encoder has no graph-convolution layers and the "
+                                      "reference would ignore these keys silently (model_builder.py:27-41); the contradictory "
+                                      "file is refused -- settings/distmult.exp carries none of them" % ", ".join(stack_keys))
+        # model_builder.py:27-41; the model is built from EntityCount and CodeDimension only, as the reference's is
+        input_shape = [int(encoder_settings['EntityCount']), int(encoder_settings['CodeDimension'])]
+        embedding = AffineTransform(input_shape, encoder_settings, onehot_input=True, use_bias=False,
+                                    use_nonlinearity=False)
+        return RelationEmbedding(input_shape, encoder_settings, next_component=embedding)
     if name != "gcn_basis":
-        raise NotImplementedError("encoder '%s' is outside the accelerated path (SURVEY.md section 2); "
-                                  "only 'gcn_basis' (ConcatGcn / BasisGcn stacks) is built" % name)
+        raise NotImplementedError("encoder '%s' is outside the accelerated path (SURVEY.md section 2); only 'gcn_basis' "
+                                  "(ConcatGcn / BasisGcn stacks) and 'embedding' (the DistMult baseline) are built" % name)
     input_transform = _flag(encoder_settings, 'UseInputTransform', None)
     if input_transform not in ("Yes", "No"):
         raise NotImplementedError("UseInputTransform must be Yes or No (the reference reads it unconditionally, "

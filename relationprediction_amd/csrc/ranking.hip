@@ -19,6 +19,13 @@
 // bit patterns (32 sigmoids per query) and the [queries, V] pass compares energies -- 64 thousand double-precision
 // exponentials per 2,000 queries instead of 58 million, the same counts bit for bit.
 //
+// Ensemble ranks (rgcn_rank_mixed_device; the reference's code/tools/ensemble.py, WeightEnsemble.combine_prediction): the
+// rank is taken on  m = w sigmoid(own energy) + (1 - w) sigmoid(partner energy),  the partner's [queries, V] energies being
+// another model's RGCN_BUF_RANK_ENERGIES (or any device buffer of that shape).  The threshold bisection above does NOT carry
+// over: m is monotone in each energy but is a function of two, so no single threshold on either energy separates the
+// entities that reach the gold's mixed score from those that do not.  k_rank_rows_mixed therefore evaluates both sigmoids
+// for every entity -- two double-precision exponentials where k_rank_rows evaluates none -- on rows read once, coalesced.
+//
 // Top-k prediction (rgcn_topk_device) selects from the same energies: same query kernel, same GEMM, same buffers; one
 // workgroup per query picks and orders the k best entities that its exclusion list leaves (k_topk_rows below).
 #include "rgcn_internal.h"
@@ -112,6 +119,61 @@ __global__ void __launch_bounds__(256) k_rank_rows(const float* __restrict__ S, 
   if (threadIdx.x == 0) {
     raw_rank[row] = red[0][0];
     filt_rank[row] = red[0][0] - red[1][0] + 1;
+  }
+}
+
+// m = (float)(w s_a + (1 - w) s_b), both products and the sum in double, rounded once: numpy's float64 expression gives the
+// same bits (no fused multiply-add: a contraction would round the first product differently from the host)
+__device__ __forceinline__ float mixed_score(double w, float ea, float eb) {
+#pragma clang fp contract(off)
+  const double a = w * (double)sigmoid_f32(ea);
+  const double b = (1.0 - w) * (double)sigmoid_f32(eb);
+  return (float)(a + b);
+}
+
+// One workgroup of four wave64s per query, k_rank_rows' shape: the two energy rows are read once (lane-consecutive
+// entities), the filter list is walked 256 entries at a time, and the two counts are summed by shuffles inside each wave
+// and through eight LDS words across the four.  Sb = the partner's rows, same queries in the same order, row stride V.
+__global__ void __launch_bounds__(256)
+k_rank_rows_mixed(const float* __restrict__ Sa, const float* __restrict__ Sb, int V, const int32_t* __restrict__ X, int n,
+                  int predict_object, double w, const int64_t* __restrict__ filt_ptr, const int32_t* __restrict__ filt_idx,
+                  int32_t* __restrict__ raw_rank, int32_t* __restrict__ filt_rank, int32_t* __restrict__ bad,
+                  const int64_t* __restrict__ filt_end) {
+  const int row = blockIdx.x;
+  if (row >= n) return;
+  __shared__ int red[2][4];
+  const float* a = Sa + (size_t)row * V;
+  const float* b = Sb + (size_t)row * V;
+  int gold = X[3 * row + (predict_object ? 2 : 0)];
+  if ((unsigned)gold >= (unsigned)V) gold = 0;      // (k_rank_check has flagged it: the call fails, nothing may fault)
+  const float mg = mixed_score(w, a[gold], b[gold]);
+  int cnt = 0, fcnt = 0;
+  for (int e = threadIdx.x; e < V; e += 256) cnt += mixed_score(w, a[e], b[e]) >= mg ? 1 : 0;
+  int64_t fb = filt_ptr[row], fe = filt_ptr[row + 1];
+  // as k_rank_rows: a flagged range is not walked, an entry out of range fails the call and is never dereferenced
+  if (fb < 0 || fe < fb || fe > *filt_end) fb = fe = 0;
+  bool oob = false;
+  for (int64_t j = fb + threadIdx.x; j < fe; j += 256) {
+    const int fi = filt_idx[j];
+    const bool in = (unsigned)fi < (unsigned)V;
+    oob = oob || !in;
+    if (in) fcnt += mixed_score(w, a[fi], b[fi]) >= mg ? 1 : 0;
+  }
+  if (oob) atomicAdd(bad, 1);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    cnt += __shfl_down(cnt, off);
+    fcnt += __shfl_down(fcnt, off);
+  }
+  if ((threadIdx.x & 63u) == 0) {
+    red[0][threadIdx.x >> 6] = cnt;
+    red[1][threadIdx.x >> 6] = fcnt;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int raw = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+    raw_rank[row] = raw;
+    filt_rank[row] = raw - (red[1][0] + red[1][1] + red[1][2] + red[1][3]) + 1;
   }
 }
 
@@ -407,6 +469,37 @@ rgcn_status rank_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predi
   RGCN_HIP(c, hipMemcpyAsync(&bad, c->ranking.bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   RGCN_HIP(c, hipStreamSynchronize(c->stream));
   if (bad) RGCN_FAIL(c, RGCN_ERR_INVALID, "rank: entity / relation / filter index out of range");
+  return RGCN_OK;
+}
+
+// rank_compute's scoring (same check kernel, query kernel, GEMM and buffer) for ONE chunk, then the counts on the mixed
+// score.  c->ranking.s holds the context's own energies afterwards, unmodified; the partner's rows are only read.
+rgcn_status rank_mixed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, const float* partner,
+                               float weight, const int64_t* filt_ptr, const int32_t* filt_idx, int32_t* raw_out,
+                               int32_t* filt_out) {
+  const float* codes = c->H[c->L];
+  const int n = (int)N;
+  RGCN_HIP(c, hipMemsetAsync(c->ranking.bad, 0, sizeof(int32_t), c->stream));
+  hipLaunchKernelGGL(k_rank_check, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, X_dev, n, c->V, c->R,
+                     filt_ptr, filt_idx, c->ranking.bad);
+  RGCN_HIP(c, hipGetLastError());
+  {
+    ProfScope ps(c, "rank_query", 4.0 * 3 * n * c->d, 0);
+    hipLaunchKernelGGL(k_rank_query, dim3((unsigned)n), dim3(128), 0, c->stream, codes, c->w_rel, X_dev, n, c->d,
+                       predict_object, c->ranking.q, c->V, c->R);
+    RGCN_HIP(c, hipGetLastError());
+  }
+  RGCN_TRY(gemm_f32(c, "rank_scores", true, true, n, c->V, c->d, c->ranking.q, c->d, codes, c->d, c->ranking.s, c->V, 1));
+  {
+    ProfScope ps(c, "rank_rows_mixed", 8.0 * n * c->V, 0);
+    hipLaunchKernelGGL(k_rank_rows_mixed, dim3((unsigned)n), dim3(256), 0, c->stream, c->ranking.s, partner, c->V, X_dev, n,
+                       predict_object, (double)weight, filt_ptr, filt_idx, raw_out, filt_out, c->ranking.bad, filt_ptr + N);
+    RGCN_HIP(c, hipGetLastError());
+  }
+  int32_t bad = 0;
+  RGCN_HIP(c, hipMemcpyAsync(&bad, c->ranking.bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  RGCN_HIP(c, hipStreamSynchronize(c->stream));
+  if (bad) RGCN_FAIL(c, RGCN_ERR_INVALID, "rank (mixed): entity / relation / filter index out of range");
   return RGCN_OK;
 }
 

@@ -340,15 +340,45 @@ static void free_all(rgcn_ctx* c) {
   delete c;
 }
 
+// RGCN_KIND_EMBEDDING: the parameters in Model.get_weights() order (affine_transform.py:30-31, relation_embedding.py:15-18)
+// and what the decoder, the optimizer and the ranking calls touch outside their own pools.  No graph set, no activations.
+static rgcn_status create_embedding(rgcn_ctx* c) {
+  const size_t V = c->V, d = c->d;
+  RGCN_TRY(dmalloc(c, c->pool, &c->w_emb, V * d, true));
+  RGCN_TRY(dmalloc(c, c->pool, &c->g_emb, V * d, true));
+  RGCN_TRY(dmalloc(c, c->pool, &c->b_emb, d, true));
+  RGCN_TRY(dmalloc(c, c->pool, &c->gb_emb, d, true));
+  add_param(c, "W_emb", {(int64_t)V, (int64_t)d}, c->w_emb, c->g_emb, LAYOUT_PLAIN);
+  add_param(c, "b_emb", {(int64_t)d}, c->b_emb, c->gb_emb, LAYOUT_PLAIN);
+  c->params.back().no_grad = true;      // use_bias=False: created, checkpointed, never read (TF reports it unconnected)
+  RGCN_TRY(dmalloc(c, c->pool, &c->w_rel, V * d, true));
+  RGCN_TRY(dmalloc(c, c->pool, &c->g_rel, V * d, true));
+  add_param(c, "W_relation", {(int64_t)V, (int64_t)d}, c->w_rel, c->g_rel, LAYOUT_PLAIN);
+  c->layers.resize(1);
+  c->H.assign(1, c->w_emb);             // the codes ARE the table
+  c->dcodes_own = c->g_emb;             // the decoder's dL/dcodes lands where the optimizer reads dL/dW_emb
+  // the ranking GEMM's launcher wants the zero page and a slab pointer (split_k = 1: no slab is ever written)
+  c->slab_floats = 1024;
+  RGCN_TRY(dmalloc(c, c->pool, &c->slab, c->slab_floats, true));
+  RGCN_TRY(dmalloc(c, c->pool, &c->zeros, 1024, true));
+  RGCN_TRY(dmalloc(c, c->pool, &c->g.errflag, 1, true));
+  c->g_alt.errflag = c->g.errflag;
+  RGCN_HIP(c, hipStreamSynchronize(c->stream));
+  return RGCN_OK;
+}
+
 static rgcn_status create_impl(rgcn_ctx* c) {
   const rgcn_config& f = c->cfg;
   if (f.abi_version != RGCN_ABI_VERSION) RGCN_FAIL(c, RGCN_ERR_INVALID, "abi_version mismatch");
-  if (f.num_entities <= 0 || f.num_relations <= 0 || f.dim <= 0 || f.num_layers <= 0 || f.num_bases <= 0)
+  const bool emb = f.kind == RGCN_KIND_EMBEDDING;
+  if (f.num_entities <= 0 || f.num_relations <= 0 || f.dim <= 0 || (!emb && f.num_layers <= 0) || f.num_bases <= 0)
     RGCN_FAIL(c, RGCN_ERR_INVALID, "EntityCount, RelationCount, dimension, NumberOfLayers and "
                                    "NumberOfBasisFunctions must be positive");
+  if (emb && (f.num_layers != 0 || f.num_bases != 1))
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "RGCN_KIND_EMBEDDING has no layers: num_layers must be 0 and num_bases 1");
   if (!(f.keep_prob > 0.0f && f.keep_prob <= 1.0f)) RGCN_FAIL(c, RGCN_ERR_INVALID, "DropoutKeepProbability must be in (0,1]");
   if (f.kind != RGCN_KIND_BLOCK && f.kind != RGCN_KIND_BASIS && f.kind != RGCN_KIND_BASIS_TDIAG &&
-      f.kind != RGCN_KIND_BASIS_PDIAG)
+      f.kind != RGCN_KIND_BASIS_PDIAG && !emb)
     RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown kind");
   if (f.norm_mode < 0 || f.norm_mode > RGCN_NORM_LOCAL) RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown norm_mode");
   if (f.world < 1 || f.rank < 0 || f.rank >= f.world) RGCN_FAIL(c, RGCN_ERR_INVALID, "need 0 <= rank < world");
@@ -358,6 +388,13 @@ static rgcn_status create_impl(rgcn_ctx* c) {
   c->V = f.num_entities; c->R = f.num_relations; c->d = f.dim; c->L = f.num_layers; c->kind = f.kind;
   c->rank = f.rank; c->world = f.world;
   c->onehot = f.input_mode == RGCN_INPUT_ONEHOT;
+  c->embedding = emb;
+  if (emb) {
+    // the Name=embedding encoder (model_builder.py:27-41): one GPU, no input-mode or skip variants
+    if (f.world > 1) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_EMBEDDING on a sharded context (nothing to shard by relation)");
+    if (c->onehot) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_EMBEDDING with RGCN_INPUT_ONEHOT (there is no first layer)");
+    if (c->highway) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_EMBEDDING with RGCN_SKIP_HIGHWAY (there is no layer to skip)");
+  }
   if (f.kind == RGCN_KIND_BASIS_TDIAG) {
     // BasisGcnTimesDiag (basis_tdiag.hip): one GPU, embedding input, no highway layers
     if (f.world > 1)
@@ -464,6 +501,7 @@ static rgcn_status create_impl(rgcn_ctx* c) {
   c->gemm_mode = 6;
   RGCN_HIP(c, hipEventCreate(&c->t0));
   RGCN_HIP(c, hipEventCreate(&c->t1));
+  if (emb) return create_embedding(c);
 
   // every [V,d] buffer carries V_pad rows (== V on one GPU): the collectives work on world equal chunks, the
   // padding rows stay zero
@@ -788,6 +826,7 @@ rgcn_status rgcn_get_grad(rgcn_ctx* c, int32_t index, float* host, int64_t count
 
 rgcn_status rgcn_set_graph(rgcn_ctx* c, const int32_t* tri, int64_t E) {
   RGCN_NEED(c);
+  RGCN_NO_EMBEDDING(c, "rgcn_set_graph");
   if (E < 0 || E > c->cfg.max_edges) RGCN_FAIL(c, RGCN_ERR_INVALID, "num_edges outside [0, max_edges]");
   if (E > 0 && !tri) RGCN_FAIL(c, RGCN_ERR_INVALID, "NULL triples");
   for (int64_t e = 0; e < E; ++e) {
@@ -802,6 +841,7 @@ rgcn_status rgcn_set_graph(rgcn_ctx* c, const int32_t* tri, int64_t E) {
 
 rgcn_status rgcn_set_graph_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t E) {
   RGCN_NEED(c);
+  RGCN_NO_EMBEDDING(c, "rgcn_set_graph_device");
   if (E < 0 || E > c->cfg.max_edges) RGCN_FAIL(c, RGCN_ERR_INVALID, "num_edges outside [0, max_edges]");
   if (E > 0 && !tri_dev) RGCN_FAIL(c, RGCN_ERR_INVALID, "NULL triples");
   RGCN_TRY(join_abandoned_side_work(c));
@@ -895,6 +935,7 @@ static rgcn_status step_end(rgcn_ctx* c) {
 rgcn_status rgcn_step_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t E, int32_t train,
                              uint64_t seed, const float* dcodes_dev) {
   RGCN_NEED(c);
+  RGCN_NO_EMBEDDING(c, "rgcn_step_device");
   if (E < 0 || E > c->cfg.max_edges) RGCN_FAIL(c, RGCN_ERR_INVALID, "num_edges outside [0, max_edges]");
   RGCN_TRY(step_begin(c, tri_dev, E, false));
   // (Round 5 tried forming the top layer's dS = dL/dcodes * dropout_L -- which depends on the caller's gradient and the seed
@@ -980,6 +1021,26 @@ rgcn_status rgcn_rank_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32
   if (c->ranking.max <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_rank_reserve first");
   if (n == 0) return RGCN_OK;
   return rank_compute(c, x_dev, n, predict_object ? 1 : 0, filter_ptr_dev, filter_idx_dev, raw_rank_dev, filtered_rank_dev);
+}
+
+const float* rgcn_rank_energies_device(rgcn_ctx* c) { return c ? c->ranking.s : nullptr; }
+
+rgcn_status rgcn_rank_mixed_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32_t predict_object,
+                                   const float* partner_energies_dev, float weight, const int64_t* filter_ptr_dev,
+                                   const int32_t* filter_idx_dev, int32_t* raw_rank_dev, int32_t* filtered_rank_dev) {
+  RGCN_NEED(c);
+  if (n < 0 || (n > 0 && (!x_dev || !partner_energies_dev || !filter_ptr_dev || !raw_rank_dev || !filtered_rank_dev)))
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
+  if (!(weight >= 0.0f && weight <= 1.0f)) RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_rank_mixed_device: weight must be in [0, 1]");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "this call synchronises with the device: not allowed between rgcn_capture_begin and rgcn_capture_end");
+  if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_rank_mixed_device needs a completed rgcn_forward (test mode on the full graph)");
+  if (c->ranking.max <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_rank_reserve first");
+  if (n > c->ranking.max)
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_rank_mixed_device: one chunk only -- num_queries above what rgcn_rank_reserve sized "
+                                   "(the partner's buffer has its own chunking)");
+  if (n == 0) return RGCN_OK;
+  return rank_mixed_compute(c, x_dev, n, predict_object ? 1 : 0, partner_energies_dev, weight, filter_ptr_dev, filter_idx_dev,
+                            raw_rank_dev, filtered_rank_dev);
 }
 
 rgcn_status rgcn_topk_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32_t predict_object, int32_t k,
@@ -1115,22 +1176,37 @@ static rgcn_status prefetch_impl(rgcn_ctx* c, const int32_t* tri_dev, int64_t E,
 rgcn_status rgcn_train_step_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t E, const int32_t* X_dev,
                                    const float* Y_dev, int64_t N, uint64_t seed, float reg_param) {
   RGCN_NEED(c);
+  if (c->embedding && (tri_dev || E != 0))
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "an RGCN_KIND_EMBEDDING context takes no graph: pass NULL triples and num_edges 0");
   if (E < 0 || E > c->cfg.max_edges) RGCN_FAIL(c, RGCN_ERR_INVALID, "num_edges outside [0, max_edges]");
   if (!X_dev || !Y_dev || N <= 0) RGCN_FAIL(c, RGCN_ERR_INVALID, "bad decoder batch");
   if (c->world > 1 && !c->comm)
     RGCN_FAIL(c, RGCN_ERR_STATE, "world > 1: call rgcn_comm_init first (or drive the phase API yourself)");
   if (c->dec.maxN < N) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_decoder_reserve(ctx, max_triples) first");
+  if (c->embedding) {
+    // the DistMult baseline's step: decoder loss + gradients on the table itself (dL/dcodes is written into W_emb's
+    // gradient), then clip + Adam.  One chain on the main stream but for the relation gradient's side stream.
+    RGCN_TRY(forward_all(c, 1, seed, nullptr));
+    RGCN_TRY(decoder_prepare(c, X_dev, N));
+    RGCN_TRY(decoder_compute(c, c->H[0], Y_dev, reg_param));
+    RGCN_TRY(stream_join(c, 2));
+    c->dec.loss_valid = true;
+    if (c->opt.configured) RGCN_TRY(optimizer_step(c));
+    return RGCN_OK;
+  }
   RGCN_TRY(step_begin(c, tri_dev, E, true));
   return train_step_tail(c, X_dev, Y_dev, N, seed, reg_param);
 }
 
 rgcn_status rgcn_prefetch_graph_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t E) {
   RGCN_NEED(c);
+  RGCN_NO_EMBEDDING(c, "rgcn_prefetch_graph_device");
   return prefetch_impl(c, tri_dev, E, -1, 0);
 }
 rgcn_status rgcn_prefetch_graph_dropout_device(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int64_t keep,
                                                uint64_t seed) {
   RGCN_NEED(c);
+  RGCN_NO_EMBEDDING(c, "rgcn_prefetch_graph_dropout_device");
   if (keep < 0) RGCN_FAIL(c, RGCN_ERR_INVALID, "edge dropout: keep outside [0, num_edges]");
   return prefetch_impl(c, batch_dev, n, keep, seed);
 }
@@ -1138,6 +1214,7 @@ rgcn_status rgcn_prefetch_graph_dropout_device(rgcn_ctx* c, const int32_t* batch
 rgcn_status rgcn_set_graph_dropout_device(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int64_t keep, uint64_t seed,
                                           const uint8_t* keep_mask_dev) {
   RGCN_NEED(c);
+  RGCN_NO_EMBEDDING(c, "rgcn_set_graph_dropout_device");
   if (n < 0 || n > c->cfg.max_edges) RGCN_FAIL(c, RGCN_ERR_INVALID, "num_edges outside [0, max_edges]");
   if (keep < 0 || keep > n) RGCN_FAIL(c, RGCN_ERR_INVALID, "edge dropout: keep outside [0, num_edges]");
   if (n >= ((int64_t)1 << 24)) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "edge dropout: more than 2^24 batch edges");
@@ -1148,7 +1225,7 @@ rgcn_status rgcn_set_graph_dropout_device(rgcn_ctx* c, const int32_t* batch_dev,
 
 rgcn_status rgcn_get_graph_edges(rgcn_ctx* c, int32_t* host, int64_t count) {
   RGCN_NEED(c);
-  if (!c->g.ready) RGCN_FAIL(c, RGCN_ERR_STATE, "no graph has been set");
+  if (!c->g.ready) RGCN_FAIL(c, RGCN_ERR_STATE, "no graph has been set");      // (always, on an RGCN_KIND_EMBEDDING context)
   if (count != c->g.E || (count > 0 && !host)) RGCN_FAIL(c, RGCN_ERR_INVALID, "need an [E,3] host buffer of the current graph's size");
   if (count == 0) return RGCN_OK;
   RGCN_TRY(check_dev_flag(c));
@@ -1160,6 +1237,7 @@ rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* c, const int32_t* batch_d
                                              int32_t* x_scratch_dev, float* y_scratch_dev, uint64_t dropout_seed,
                                              float reg_param) {
   RGCN_NEED(c);
+  RGCN_NO_EMBEDDING(c, "rgcn_train_step_minibatch_device");
   if (n <= 0 || n > c->cfg.max_edges) RGCN_FAIL(c, RGCN_ERR_INVALID, "num_edges outside [1, max_edges]");
   if (keep < 0 || keep > n) RGCN_FAIL(c, RGCN_ERR_INVALID, "edge dropout: keep outside [0, num_edges]");
   if (n >= ((int64_t)1 << 24)) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "edge dropout: more than 2^24 batch edges");
@@ -1181,6 +1259,7 @@ rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* c, const int32_t* batch_d
 // ---- neighbourhood edge sampler on the device ------------------------------------------
 rgcn_status rgcn_neighborhood_reserve(rgcn_ctx* c, const int32_t* triples_host, int64_t n) {
   RGCN_NEED(c);
+  RGCN_NO_EMBEDDING(c, "rgcn_neighborhood_reserve");
   if (n <= 0 || n >= ((int64_t)1 << 31) / 3 || !triples_host) RGCN_FAIL(c, RGCN_ERR_INVALID, "need the training triples");
   if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
   for (int64_t e = 0; e < n; ++e) {
@@ -1214,6 +1293,7 @@ __global__ void k_bump_counter(uint64_t* counter) { counter[0] += 1; }
 
 rgcn_status rgcn_capture_begin(rgcn_ctx* c) {
   RGCN_NEED(c);
+  RGCN_NO_EMBEDDING(c, "rgcn_capture_begin");
   if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "a capture is already running");
   if (c->prof_on) RGCN_FAIL(c, RGCN_ERR_STATE, "switch the per-kernel profile off before capturing");
   if (c->onehot)
@@ -1337,6 +1417,7 @@ rgcn_status rgcn_graph_destroy(rgcn_ctx* c, int32_t graph_id) {
 
 rgcn_status rgcn_set_relation_owner(rgcn_ctx* c, const int32_t* owner, int32_t count) {
   RGCN_NEED(c);
+  RGCN_NO_EMBEDDING(c, "rgcn_set_relation_owner");
   if (!owner || count != c->R) RGCN_FAIL(c, RGCN_ERR_INVALID, "owner must have RelationCount entries");
   for (int r = 0; r < count; ++r)
     if (owner[r] < 0 || owner[r] >= c->world) RGCN_FAIL(c, RGCN_ERR_INVALID, "owner[r] outside [0, world)");
@@ -1398,6 +1479,8 @@ rgcn_status rgcn_backward_end(rgcn_ctx* c) { RGCN_NEED(c); return bwd_end(c); }
 
 static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* bytes) {
   const int64_t Vd = (int64_t)c->V * c->d * 4;
+  if (c->embedding && which != RGCN_BUF_RANK_ENERGIES)
+    RGCN_FAIL(c, RGCN_ERR_STATE, "an RGCN_KIND_EMBEDDING context has the ranking energies only (no graph, no layer buffers)");
   switch (which) {
     case RGCN_BUF_EXCHANGE:
       if (!c->exch) RGCN_FAIL(c, RGCN_ERR_STATE, "no exchange buffer on a world == 1 context");

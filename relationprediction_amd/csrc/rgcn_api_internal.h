@@ -17,6 +17,14 @@
     (void)hipSetDevice((c)->cfg.device); \
   } while (0)
 
+// the calls an RGCN_KIND_EMBEDDING context has no graph, layer or shard for
+#define RGCN_NO_EMBEDDING(c, call)                                                                                  \
+  do {                                                                                                              \
+    if ((c)->embedding)                                                                                             \
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, call ": not on an RGCN_KIND_EMBEDDING context (no graph, no layers, one GPU, " \
+                                              "no capture: the codes are the W_emb table)");                        \
+  } while (0)
+
 namespace rgcn {
 
 // ---- rgcn_api.hip

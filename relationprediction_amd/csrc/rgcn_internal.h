@@ -382,6 +382,10 @@ struct rgcn_ctx {
   float* pdiag_slab_dd = nullptr;
   size_t pdiag_slab_chunks = 0;           // chunks either slab holds
   int pdiag_last = 0;                     // the layer the last fwd_layer_finish ran (RGCN_BUF_PDIAG_MIX / _AGG)
+  // RGCN_KIND_EMBEDDING (the reference's Name=embedding encoder, the DistMult baseline): no graph and no layer.  The codes
+  // ARE W_emb (H[0] = w_emb), their gradient is written where the optimizer reads it (dcodes_own = g_emb): of the buffers
+  // below only the parameters, their gradients, the error flag, `zeros` and a one-tile slab exist on such a context
+  bool embedding = false;
   bool onehot = false;          // featureless first layer (RGCN_INPUT_ONEHOT): no W_emb / b_emb / H_0, layer 1 is basis_onehot.hip
   int row_lo = 0, row_hi = 0;   // row shard of this rank: [rank * shard_rows, +shard_rows) cut at V
   int shard_rows = 0;           // ceil(V / world): equal chunks for the reduce-scatter / all-gather
@@ -732,6 +736,9 @@ rgcn_status rank_reserve(rgcn_ctx* c, int64_t max_queries);
 void rank_free(rgcn_ctx* c);
 rgcn_status rank_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, const int64_t* filt_ptr,
                          const int32_t* filt_idx, int32_t* raw_out, int32_t* filt_out);
+rgcn_status rank_mixed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, const float* partner_dev,
+                               float weight, const int64_t* filt_ptr, const int32_t* filt_idx, int32_t* raw_out,
+                               int32_t* filt_out);
 rgcn_status topk_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, int k,
                          const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out, float* energy_out);
 void optimizer_free(rgcn_ctx* c);

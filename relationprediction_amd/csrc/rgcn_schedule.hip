@@ -15,6 +15,7 @@ namespace rgcn {
 static bool h0_by_self_loop_gemm(const rgcn_ctx* c);
 
 rgcn_status fwd_begin(rgcn_ctx* c, int train, uint64_t seed, const uint8_t* masks_host) {
+  RGCN_NO_EMBEDDING(c, "rgcn_forward_begin");      // (rgcn_forward / rgcn_backward never come here on such a context)
   if (!c->g.ready) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_forward before rgcn_set_graph");
   // (side kernels the main stream has not joined -- a step that ended unjoined, rgcn_step_device; a backward pass driven
   // layer by layer and abandoned between layers 2 and 1 -- read the activations this pass overwrites.  Nothing is queued
@@ -147,6 +148,7 @@ static GemmBatch tdiag_batch(size_t strideA, size_t strideB, size_t strideC) {
 }
 
 rgcn_status fwd_layer_partial(rgcn_ctx* c, int l) {
+  RGCN_NO_EMBEDDING(c, "rgcn_forward_layer_partial");
   if (l < 1 || l > c->L) RGCN_FAIL(c, RGCN_ERR_INVALID, "layer out of range");
   // featureless first layer (world == 1): one destination-major kernel, messages looked up in the [V,B,d] tables, the
   // combine -- W_self row, dropout, relu -- as its epilogue; no GEMM
@@ -285,6 +287,7 @@ rgcn_status fwd_layer_partial(rgcn_ctx* c, int l) {
 }
 
 rgcn_status fwd_layer_finish(rgcn_ctx* c, int l) {
+  RGCN_NO_EMBEDDING(c, "rgcn_forward_layer_finish");
   if (l < 1 || l > c->L) RGCN_FAIL(c, RGCN_ERR_INVALID, "layer out of range");
   if (c->world > 1)
     RGCN_TRY(relu_copy(c, c->exch, c->H[l], (int64_t)c->V * c->d, l < c->L ? 1 : 0));
@@ -316,6 +319,7 @@ static bool deferred_schedule(const rgcn_ctx* c) {
 // ds_ready: dcodes * dropout of the top layer, already written by the producer of dcodes (the device decoder does,
 // inside a train step): the scale-and-copy pass over [V,d] is skipped
 rgcn_status bwd_begin(rgcn_ctx* c, const float* dcodes_dev, const float* ds_ready) {
+  RGCN_NO_EMBEDDING(c, "rgcn_backward_begin");
   if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_backward needs a completed rgcn_forward on the current graph");
   if (!dcodes_dev) RGCN_FAIL(c, RGCN_ERR_INVALID, "dcodes is NULL");
   // Unjoined side kernels read the dS / D buffers this pass rewrites and write the gradients, slabs and column-sum partials
@@ -342,6 +346,7 @@ rgcn_status bwd_begin(rgcn_ctx* c, const float* dcodes_dev, const float* ds_read
 }
 
 rgcn_status bwd_layer_partial(rgcn_ctx* c, int l) {
+  RGCN_NO_EMBEDDING(c, "rgcn_backward_layer_partial");
   if (l != c->bwd_layer || l < 1) RGCN_FAIL(c, RGCN_ERR_STATE, "backward layers must run L..1 in order");
   if (c->onehot && l == 1) {
     // Featureless first layer: D = dL/dpre1 (the layer above applied relu'(H_1); L = 1: the codes' gradient), dS = D *
@@ -601,6 +606,7 @@ rgcn_status bwd_layer_partial(rgcn_ctx* c, int l) {
 }
 
 rgcn_status bwd_layer_finish(rgcn_ctx* c, int l) {
+  RGCN_NO_EMBEDDING(c, "rgcn_backward_layer_finish");
   if (l != c->bwd_layer || l < 1) RGCN_FAIL(c, RGCN_ERR_STATE, "backward layers must run L..1 in order");
   float* out = (l - 1 == 0) ? c->g_emb : c->dbuf[(l - 1) & 1];
   DropSpec d2 = make_drop(c, l - 1, l - 1 >= 1);
@@ -621,6 +627,7 @@ rgcn_status bwd_layer_finish(rgcn_ctx* c, int l) {
 }
 
 rgcn_status bwd_end(rgcn_ctx* c) {
+  RGCN_NO_EMBEDDING(c, "rgcn_backward_end");
   if (c->bwd_layer != 0) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_backward_end before all layers ran");
   if (c->onehot) {      // no W_emb / b_emb: nothing of the bottom-layer work exists (no relu' of H_0, no column sums)
     if (c->side_state != rgcn_ctx::SIDE_NONE) RGCN_TRY(join_abandoned_side_work(c));
@@ -692,6 +699,14 @@ static rgcn_status bwd_exchange(rgcn_ctx* c, int l) {
 }
 
 rgcn_status forward_all(rgcn_ctx* c, int train, uint64_t seed, const uint8_t* masks) {
+  if (c->embedding) {
+    // RelationEmbedding(AffineTransform(onehot_input, no bias, no relu)), model_builder.py:27-41: the codes are the table
+    // itself in either mode -- no graph, no dropout, no kernel.  H[0] is W_emb's own storage.
+    c->fwd_train = train ? 1 : 0;
+    c->seed = seed;
+    c->fwd_done = true;
+    return RGCN_OK;
+  }
   if (c->world > 1 && !c->comm)
     RGCN_FAIL(c, RGCN_ERR_STATE, "world > 1: call rgcn_comm_init first (or drive the phase API yourself)");
   RGCN_TRY(fwd_begin(c, train, seed, masks));
@@ -704,6 +719,15 @@ rgcn_status forward_all(rgcn_ctx* c, int train, uint64_t seed, const uint8_t* ma
 }
 
 rgcn_status backward_all(rgcn_ctx* c, const float* dcodes_dev, const float* ds_ready) {
+  if (c->embedding) {
+    // dL/dW_emb = dL/dcodes.  The device decoder and rgcn_backward write it in place (dcodes_own IS g_emb); a caller's own
+    // buffer is copied.  b_emb is never read: its gradient stays the zeros it was created with.
+    if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_backward needs a completed rgcn_forward");
+    if (!dcodes_dev) RGCN_FAIL(c, RGCN_ERR_INVALID, "dcodes is NULL");
+    if (dcodes_dev != c->g_emb)
+      RGCN_HIP(c, hipMemcpyAsync(c->g_emb, dcodes_dev, sizeof(float) * (size_t)c->V * c->d, hipMemcpyDeviceToDevice, c->stream));
+    return RGCN_OK;
+  }
   if (c->world > 1 && !c->comm)
     RGCN_FAIL(c, RGCN_ERR_STATE, "world > 1: call rgcn_comm_init first (or drive the phase API yourself)");
   RGCN_TRY(bwd_begin(c, dcodes_dev, ds_ready));

@@ -76,7 +76,8 @@ class BilinearDiag(Model):
         self.next_component.get_runtime().configure_optimizer(learning_rate, beta1, beta2, epsilon, max_grad_norm)
 
     def device_train_step(self, graph_edges, x, y, seed):
-        """loss + regularisation, all gradients, clip and Adam in one asynchronous device step."""
+        """loss + regularisation, all gradients, clip and Adam in one asynchronous device step (graph_edges None: a
+        graph-less encoder, Name=embedding)."""
         self.next_component.get_runtime().train_step(graph_edges, x, y, self.regularization_parameter, seed)
 
     def device_train_step_negatives(self, graph_edges, batch, rate, seed):
@@ -85,7 +86,9 @@ class BilinearDiag(Model):
                                                                       self.regularization_parameter, seed)
 
     def device_stage(self, graph_edges, batch=None):
-        """feed the next train step beside the running one (runtime.stage)"""
+        """feed the next train step beside the running one (runtime.stage); a graph-less encoder has nothing to stage"""
+        if graph_edges is None:
+            return
         self.next_component.get_runtime().stage(graph_edges, batch)
 
     def device_train_step_minibatch(self, minibatch, seed):
@@ -105,10 +108,22 @@ class BilinearDiag(Model):
         """Ranks of the gold subjects / objects of `triplets` against every entity, codes from a test-mode
         pass over `graph` (what score_all_subjects / score_all_objects + MrrScore.append_line compute)."""
         variables = self.get_test_input_variables()
-        if getattr(self, '_ranks_graph', None) is not graph or variables[0].value is None:
+        if self.needs_graph() and (getattr(self, '_ranks_graph', None) is not graph or variables[0].value is None):
             variables[0].feed(graph)          # re-encoded only when the graph or the weights changed
             self._ranks_graph = graph
         return self.next_component.get_runtime().ranks(triplets, predict_object, filter_ptr, filter_idx)
+
+    def device_ranks_mixed(self, graph, triplets, predict_object, partner, weight, filter_ptr, filter_idx):
+        """device_ranks under weight * this model's score + (1 - weight) * another model's (rgcn_rank_mixed_device):
+        partner = that model's energies for the same triplets in the same order, a float32 [N, EntityCount] array or the
+        device address of its engine's score buffer (Engine.rank_energies_device, same GPU); one chunk of at most
+        Scorer.chunk_size triplets."""
+        variables = self.get_test_input_variables()
+        if self.needs_graph() and (getattr(self, '_ranks_graph', None) is not graph or variables[0].value is None):
+            variables[0].feed(graph)
+            self._ranks_graph = graph
+        return self.next_component.get_runtime().ranks_mixed(triplets, predict_object, partner, weight, filter_ptr,
+                                                             filter_idx)
 
     def device_topk(self, graph, queries, predict_object, k, exclude_ptr=None, exclude_idx=None):
         """The k most plausible objects of (s, r, ?) (predict_object) or subjects of (?, r, o) for every row of
@@ -116,7 +131,7 @@ class BilinearDiag(Model):
         test-mode pass over `graph`.  Returns (entity ids int32 [N,k], energies float32 [N,k]); the column being
         predicted is not read; rows short of k answers end in (-1, -inf).  Scores are _sigmoid(energies)."""
         variables = self.get_test_input_variables()
-        if getattr(self, '_ranks_graph', None) is not graph or variables[0].value is None:
+        if self.needs_graph() and (getattr(self, '_ranks_graph', None) is not graph or variables[0].value is None):
             variables[0].feed(graph)          # re-encoded only when the graph or the weights changed
             self._ranks_graph = graph
         return self.next_component.get_runtime().topk(queries, predict_object, k, exclude_ptr, exclude_idx)

@@ -1,13 +1,17 @@
 """Input embedding layer (reference: code/encoders/affine_transform.py).
 
 With `onehot_input=True` the layer is a lookup table plus bias plus relu: `H0 = relu(W + b)`
-(:63-83), `W ~ N(0, glorot_variance(shape))`, `b = 0` (:24-28).  That is the only configuration the
-BASELINE settings build (UseInputTransform=Yes, model_builder.py:141-146) and the only one wired to
-the engine (kernel k_input_fwd).  The dense branch (`matmul(code, W)`, used only by
-UseOutputTransform=Yes) is out of scope.
+(:63-83), `W ~ N(0, glorot_variance(shape))`, `b = 0` (:24-28).  That is the configuration the
+gcn_basis settings build (UseInputTransform=Yes, model_builder.py:141-146), wired to the engine's
+kernel k_input_fwd.  The second one built is the bias-free lookup of `Name=embedding`
+(model_builder.py:27-41: onehot_input=True, use_bias=False, use_nonlinearity=False, nothing beneath
+it): the codes ARE `W`, `b` is created and checkpointed but never read, and the component owns a
+graph-less runtime (runtime.EmbeddingRuntime, an RGCN_KIND_EMBEDDING engine context).  The dense
+branch (`matmul(code, W)`, used only by UseOutputTransform=Yes) is out of scope.
 """
 from ..common.shared_functions import glorot_variance, make_variable, make_bias
 from ..model import Model, Variable
+from ..runtime import EmbeddingRuntime
 
 
 class AffineTransform(Model):
@@ -25,11 +29,15 @@ class AffineTransform(Model):
         self.use_nonlinearity = use_nonlinearity
         self.use_bias = use_bias
         self.onehot_input = onehot_input
-        if not (onehot_input and use_bias and use_nonlinearity):
+        # the lookup of Name=embedding: bias-free, linear, with no component beneath it
+        self.lookup = bool(onehot_input and not use_bias and not use_nonlinearity and next_component is None)
+        self._lookup_runtime = None         # (the graph's runtime lives on the Representation; only the lookup owns one)
+        if not (onehot_input and use_bias and use_nonlinearity) and not self.lookup:
             raise NotImplementedError(
-                "AffineTransform is implemented as the encoder's input layer only "
-                "(onehot_input=True, use_bias=True, use_nonlinearity=True); the dense / bias-free "
-                "variants belong to UseOutputTransform=Yes and the 'embedding' encoder (out of scope)")
+                "AffineTransform is implemented as the encoder's input layer (onehot_input=True, use_bias=True, "
+                "use_nonlinearity=True) and as the 'embedding' encoder's lookup (onehot_input=True, use_bias=False, "
+                "use_nonlinearity=False, no component beneath it); the dense variants belong to "
+                "UseOutputTransform=Yes (out of scope)")
 
     def local_initialize_train(self):
         variance = glorot_variance(self.shape)
@@ -39,7 +47,19 @@ class AffineTransform(Model):
     def local_get_weights(self):
         return [self.W, self.b]
 
+    def needs_graph(self):
+        return False if self.lookup else Model.needs_graph(self)
+
+    def get_runtime(self):
+        return self._runtime() if self.lookup else Model.get_runtime(self)
+
     def _runtime(self):
+        if self.lookup:
+            if self._lookup_runtime is None:
+                if self.W is None:
+                    raise RuntimeError("initialize_train() has not drawn the weights yet")
+                self._lookup_runtime = EmbeddingRuntime(self)
+            return self._lookup_runtime
         rep = self.next_component
         if rep.runtime is None:
             raise RuntimeError("the encoder has no graph-convolution layer above the input layer")
@@ -56,4 +76,7 @@ class AffineTransform(Model):
         return self.get_all_codes(mode)[2]
 
     def backward(self, runtime):
+        if self.lookup:      # `runtime` is dL/dcodes [V,d], handed down by RelationEmbedding: it IS W's gradient
+            rt = self._runtime().backward(runtime)
+            return [rt.grad("W_emb"), rt.grad("b_emb")]
         return self.next_component.backward(runtime) + [runtime.grad("W_emb"), runtime.grad("b_emb")]

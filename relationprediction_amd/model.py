@@ -210,6 +210,9 @@ class Model(object):
     def device_ranks(self, *args):
         return self.__delegate__('device_ranks', *args)
 
+    def device_ranks_mixed(self, *args):
+        return self.__delegate__('device_ranks_mixed', *args)
+
     def device_topk(self, *args, **kwargs):
         return self.__delegate__('device_topk', *args, **kwargs)
 

@@ -266,7 +266,8 @@ def build_stack(parameters):
 
 class DeviceNegatives(object):
     """A processed batch whose decoder triples are still to be drawn — on the device, at step time — from
-    `batch` (NegativeSampler.transform's distribution: rgcn_negative_sample_device)."""
+    `batch` (NegativeSampler.transform's distribution: rgcn_negative_sample_device).  graph_edges None: the model has no
+    graph (Name=embedding) and `batch`, the whole training set, stays resident on the device while the same array is fed."""
 
     def __init__(self, graph_edges, batch, rate):
         self.graph_edges, self.batch, self.rate = graph_edges, batch, int(rate)
@@ -309,6 +310,8 @@ class HipOptimizer(object):
             self.model.device_train_step_negatives(processed_batch.graph_edges, processed_batch.batch,
                                                    processed_batch.rate, seed)
             return
+        if len(processed_batch) == 2:             # a graph-less model's (X, Y), as the reference's t_func returns it
+            processed_batch = (None,) + tuple(processed_batch)
         graph_edges, x, y = processed_batch
         self.model.device_train_step(graph_edges, x, y, seed)
 
@@ -321,7 +324,7 @@ class HipOptimizer(object):
             self.model.device_stage_minibatch(processed_batch)
         elif isinstance(processed_batch, DeviceNegatives):
             stage(processed_batch.graph_edges, processed_batch.batch)
-        else:
+        elif len(processed_batch) == 3:           # ((X, Y) of a graph-less model: nothing to stage)
             stage(processed_batch[0], None)
 
     def presample(self, processed_batch):

@@ -305,6 +305,15 @@ class EncoderRuntime(object):
             self._rank_reserved = chunk
         return self.engine.ranks(triples, predict_object, filter_ptr, filter_idx)
 
+    def ranks_mixed(self, triples, predict_object, partner, weight, filter_ptr, filter_idx, chunk=2048):
+        """ranks() on weight * own score + (1 - weight) * partner score (rgcn_rank_mixed_device); partner: the other
+        model's [N, V] energies for the same triples, an array or a device address; N <= chunk."""
+        self.forward('test')
+        if self._rank_reserved < chunk:
+            self.engine.rank_reserve(chunk)
+            self._rank_reserved = chunk
+        return self.engine.ranks_mixed(triples, predict_object, partner, weight, filter_ptr, filter_idx)
+
     def topk(self, queries, predict_object, k, exclude_ptr=None, exclude_idx=None, chunk=2048):
         """The k best completions of every query, best first, on the codes of a test-mode forward over the fed graph
         (rgcn_topk_device): (entity ids int32 [N,k], energies float32 [N,k])."""
@@ -322,3 +331,80 @@ class EncoderRuntime(object):
 
     def grad(self, name):
         return self.engine.get_grad(name)
+
+
+class EmbeddingRuntime(EncoderRuntime):
+    """The graph-less runtime of `Name=embedding` (the DistMult baseline): ONE RGCN_KIND_EMBEDDING engine context, owned by
+    the lookup AffineTransform at the bottom of the chain.  The codes are W_emb itself; a step is the decoder's loss and
+    gradients, clip and Adam (rgcn_train_step_device without a graph).  EncoderRuntime's method names and meanings; the
+    `graph_edges` arguments are None."""
+
+    def __init__(self, affine):
+        self.layers, self.affine, self.representation = [], affine, None
+        self.kind = "embedding"
+        self.highway = False
+        s = affine.settings
+        self.V, self.R = affine.entity_count, affine.relation_count
+        self.d = int(affine.shape[1])
+        device = int(s['Device']) if 'Device' in s else 0
+        self.engine = _native.Engine(self.V, self.R, self.d, 0, "embedding", 1, keep_prob=1.0, max_edges=0, device=device)
+        self._state = None
+        self._dev = {}
+        self._dec_reserved = 0
+        self._rank_reserved = 0
+        self._graph_version = None
+        self.weights_version = 0
+        self._resident = None         # the positives array whose device copy is in self._dev["batch"]
+        affine.W.bind(*self._accessors("W_emb"))
+        affine.b.bind(*self._accessors("b_emb"))
+
+    def forward(self, mode):
+        key = (0, mode, self.weights_version)
+        if self._state != key:
+            self.engine.forward(train=mode == 'train', seed=0)
+            self._state = key
+        return self
+
+    def stage(self, graph_edges, batch=None):
+        pass
+
+    def train_step(self, graph_edges, x, y, reg_param, seed):
+        if graph_edges is not None:
+            raise ValueError("a graph-less encoder takes no graph_edges")
+        x = np.ascontiguousarray(x, dtype=np.int32).reshape(-1, 3)
+        y = np.ascontiguousarray(y, dtype=np.float32).ravel()
+        if len(x) != len(y) or len(x) == 0:
+            raise ValueError("decoder batch: X [N,3] and Y [N] must have the same non-zero length")
+        if len(x) > self._dec_reserved:
+            self.engine.decoder_reserve(len(x))
+            self._dec_reserved = len(x)
+        xd, yd = self._upload("X", x), self._upload("Y", y)
+        self.engine.train_step_device(None, 0, xd, yd, len(x), seed=seed, reg_param=reg_param)
+        self._state = None
+        self.weights_version += 1
+
+    def train_step_device_negatives(self, graph_edges, batch, rate, reg_param, seed):
+        """The positives are uploaded once and stay resident while the SAME array object is fed (the training set, every
+        iteration); the corruptions are drawn on the device.  A caller that rewrites the array in place feeds a new one."""
+        if graph_edges is not None:
+            raise ValueError("a graph-less encoder takes no graph_edges")
+        nb = len(batch)
+        n = nb * (int(rate) + 1)
+        if n == 0:
+            raise ValueError("empty decoder batch")
+        if n > self._dec_reserved:
+            self.engine.decoder_reserve(n)
+            self._dec_reserved = n
+        if self._resident is not batch or "batch" not in self._dev:
+            self._upload("batch", np.ascontiguousarray(batch, dtype=np.int32).reshape(-1, 3))
+            self._resident = batch
+        xd, yd = self._buffer("X", 12 * n), self._buffer("Y", 4 * n)
+        self.engine.negative_sample_device(self._dev["batch"], nb, rate, seed ^ 0x5bd1e995, xd, yd)
+        self.engine.train_step_device(None, 0, xd, yd, n, seed=seed, reg_param=reg_param)
+        self._state = None
+        self.weights_version += 1
+
+    def _no_graph(self, *args, **kwargs):
+        raise NotImplementedError("a graph-less encoder (Name=embedding) has no graph batches to stage, sample or drop edges from")
+
+    stage_minibatch = presample_minibatch = train_step_minibatch = _no_graph

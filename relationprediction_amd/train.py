@@ -8,7 +8,9 @@ minibatch transform (neighbourhood graph batch -> edge dropout split -> negative
 Converge loop (:255-284).  What runs where: the chain's components configure ONE HIP engine context; every
 iteration is one asynchronous device step (graph prep, R-GCN forward, DistMult loss, backward, clip, Adam);
 the host draws the next minibatch meanwhile (neighbourhood sampler in librgcn.so, O(log V) per pick); validation
-encodes the training graph once and ranks on the device."""
+encodes the training graph once and ranks on the device.  `Name=embedding` (settings/distmult.exp, the DistMult baseline)
+has no graph: every iteration's positives are the whole training set, resident on the device, and the step is the
+decoder's loss and gradients, clip and Adam."""
 import argparse
 
 import numpy as np
@@ -44,7 +46,8 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
     import threading
     ns = auxilliaries.NegativeSampler(int(general_settings['NegativeSampleRate']), general_settings['EntityCount'])
     ns.set_known_positives(train_triplets)
-    use_sampler = 'GraphBatchSize' in general_settings
+    # (a graph-less encoder never reaches the sampler: settings/distmult.exp carries a GraphBatchSize it does not use)
+    use_sampler = 'GraphBatchSize' in general_settings and encoder.needs_graph()
     if use_sampler and int(general_settings['GraphBatchSize']) > len(train_triplets):
         # the reference's sampler runs out of edges and dies on NaN probabilities (train.py:173-178)
         raise ValueError("General.GraphBatchSize = %d exceeds the %d training edges (EdgeCount): remove the key to "
@@ -57,6 +60,11 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
         rng = np.random.RandomState(seed)
         arr = np.asarray(x)
         if not encoder.needs_graph():
+            # Name=embedding (train.py:227-229): no graph batch, no edge dropout -- every iteration's positives are the
+            # whole training set.  Device negatives: the array itself is handed on, so that the step finds it resident
+            if device_negatives:
+                from .optimization.optimize import DeviceNegatives
+                return DeviceNegatives(None, arr, ns.negative_sample_rate)
             return ns.transform(arr, rng)
         if use_sampler and device_sampler and device_dropout:
             # all three draws on the device: the iteration is three seeds, nothing is built on the host or uploaded

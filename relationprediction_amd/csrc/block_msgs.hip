@@ -204,11 +204,9 @@ rgcn_status dispatch_sd(rgcn_ctx* c, F&& f) {
 
 }  // namespace
 
-// Launch geometry: G message slots x nb lanes per workgroup, padded to whole wavefronts.
+// Launch geometry: G message slots x nb lanes per workgroup, padded to whole wavefronts.  (At most 512 blocks of a compiled
+// size: config_check.h refuses the rest before a context exists.)
 rgcn_status block_geometry(rgcn_ctx* c) {
-  if (c->nb > 512) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "NumberOfBasisFunctions (block count) > 512");
-  if (!(c->sd == 1 || c->sd == 2 || c->sd == 3 || c->sd == 4 || c->sd == 5 || c->sd == 8))
-    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "block size d/nb must be one of 1,2,3,4,5,8");
   int best_block = 0, best_g = 0;
   double best_util = 0.0;
   for (int blk = 64; blk <= 512; blk += 64) {

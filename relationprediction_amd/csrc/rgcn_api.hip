@@ -6,6 +6,7 @@
 #include <utility>
 #include <new>
 
+#include "config_check.h"
 #include "rgcn_api_internal.h"
 
 namespace rgcn {
@@ -367,107 +368,11 @@ static rgcn_status create_embedding(rgcn_ctx* c) {
   return RGCN_OK;
 }
 
-static rgcn_status create_impl(rgcn_ctx* c) {
+// ---- rgcn_create, piece by piece: streams and events; the parameter table, layer by layer (one function per layer form and
+// the tail every form shares); the activations; the scratch of each kind; the tail every kind shares.  What a configuration
+// is refused for is config_check.h's.
+static rgcn_status create_streams(rgcn_ctx* c) {
   const rgcn_config& f = c->cfg;
-  if (f.abi_version != RGCN_ABI_VERSION) RGCN_FAIL(c, RGCN_ERR_INVALID, "abi_version mismatch");
-  const bool emb = f.kind == RGCN_KIND_EMBEDDING;
-  if (f.num_entities <= 0 || f.num_relations <= 0 || f.dim <= 0 || (!emb && f.num_layers <= 0) || f.num_bases <= 0)
-    RGCN_FAIL(c, RGCN_ERR_INVALID, "EntityCount, RelationCount, dimension, NumberOfLayers and "
-                                   "NumberOfBasisFunctions must be positive");
-  if (emb && (f.num_layers != 0 || f.num_bases != 1))
-    RGCN_FAIL(c, RGCN_ERR_INVALID, "RGCN_KIND_EMBEDDING has no layers: num_layers must be 0 and num_bases 1");
-  if (!(f.keep_prob > 0.0f && f.keep_prob <= 1.0f)) RGCN_FAIL(c, RGCN_ERR_INVALID, "DropoutKeepProbability must be in (0,1]");
-  if (f.kind != RGCN_KIND_BLOCK && f.kind != RGCN_KIND_BASIS && f.kind != RGCN_KIND_BASIS_TDIAG &&
-      f.kind != RGCN_KIND_BASIS_PDIAG && !emb)
-    RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown kind");
-  if (f.norm_mode < 0 || f.norm_mode > RGCN_NORM_LOCAL) RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown norm_mode");
-  if (f.world < 1 || f.rank < 0 || f.rank >= f.world) RGCN_FAIL(c, RGCN_ERR_INVALID, "need 0 <= rank < world");
-  if (f.max_edges < 0 || f.max_edges > (int64_t)500 * 1000 * 1000) RGCN_FAIL(c, RGCN_ERR_INVALID, "max_edges out of range");
-  if (f.input_mode != RGCN_INPUT_EMBEDDING && f.input_mode != RGCN_INPUT_ONEHOT)
-    RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown input_mode (0: embedding input, 1: RGCN_INPUT_ONEHOT)");
-  c->V = f.num_entities; c->R = f.num_relations; c->d = f.dim; c->L = f.num_layers; c->kind = f.kind;
-  c->rank = f.rank; c->world = f.world;
-  c->onehot = f.input_mode == RGCN_INPUT_ONEHOT;
-  c->embedding = emb;
-  if (emb) {
-    // the Name=embedding encoder (model_builder.py:27-41): one GPU, no input-mode or skip variants
-    if (f.world > 1) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_EMBEDDING on a sharded context (nothing to shard by relation)");
-    if (c->onehot) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_EMBEDDING with RGCN_INPUT_ONEHOT (there is no first layer)");
-    if (c->highway) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_EMBEDDING with RGCN_SKIP_HIGHWAY (there is no layer to skip)");
-  }
-  if (f.kind == RGCN_KIND_BASIS_TDIAG) {
-    // BasisGcnTimesDiag (basis_tdiag.hip): one GPU, embedding input, no highway layers
-    if (f.world > 1)
-      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_TDIAG on a sharded context (the products P, dP and the coefficient "
-                                         "table have no exchange points)");
-    if (c->onehot)
-      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_TDIAG with RGCN_INPUT_ONEHOT (the reference's one-hot branch of "
-                                         "BasisGcnTimesDiag exists, gcn_basis_times_diag.py:21,70,76: not built)");
-    if (c->highway)
-      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_TDIAG with RGCN_SKIP_HIGHWAY (not built)");
-    if (f.num_bases > 64) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "NumberOfBasisFunctions > 64 (basis_tdiag)");
-    if (2 * (int64_t)f.num_entities * f.num_bases * (int64_t)f.dim >= ((int64_t)1 << 31))
-      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_TDIAG: 2 x EntityCount x NumberOfBasisFunctions x dimension must be "
-                                         "below 2^31");
-  }
-  if (f.kind == RGCN_KIND_BASIS_PDIAG) {
-    // BasisGcnWithDiag (basis_pdiag.hip): one GPU, embedding input, no highway layers
-    if (f.world > 1)
-      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_PDIAG on a sharded context (the mixing table, the diagonal aggregate "
-                                         "and the diagonal tables' gradient have no exchange points)");
-    if (c->onehot)
-      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_PDIAG with RGCN_INPUT_ONEHOT (the one-hot first layer of "
-                                         "BasisGcnWithDiag is not built)");
-    if (c->highway)
-      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_PDIAG with RGCN_SKIP_HIGHWAY (not built)");
-    if (f.num_bases > 64) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "NumberOfBasisFunctions > 64 (basis_pdiag)");
-    if (2 * (int64_t)f.num_entities * f.num_bases * (int64_t)f.dim >= ((int64_t)1 << 31))
-      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_KIND_BASIS_PDIAG: 2 x EntityCount x NumberOfBasisFunctions x dimension must be "
-                                         "below 2^31");
-  }
-  if (c->onehot) {
-    // the featureless first layer (model_builder.py:277-283): BasisGcn only, per-entity tables on one GPU
-    if (f.kind != RGCN_KIND_BASIS)
-      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_INPUT_ONEHOT with the block kind: the reference's one-hot branch of ConcatGcn "
-                                         "cannot execute (gcn_basis_concat.py:18-19,42-46)");
-    if (f.world > 1)
-      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_INPUT_ONEHOT on a sharded context (the [V,B,d] tables are not sharded)");
-    if ((int64_t)f.num_entities * f.num_bases * (int64_t)f.dim >= ((int64_t)1 << 31))
-      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_INPUT_ONEHOT: EntityCount x NumberOfBasisFunctions x dimension must be below 2^31");
-  }
-  if (c->highway) {
-    if (f.world > 1)
-      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_SKIP_HIGHWAY on a sharded context (the highway passes have no exchange points)");
-    if (c->onehot)
-      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "RGCN_SKIP_HIGHWAY with RGCN_INPUT_ONEHOT (in the reference the one-hot first layer "
-                                         "gets no highway layer while the layers above it do: not built)");
-  }
-  // the library's radix sort takes keys below 2^24 (csr_sort.hip): vertex ids and directed-relation ids
-  if (c->V >= (1 << 24) || 2 * (int64_t)c->R >= (1 << 24))
-    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "EntityCount and 2 x RelationCount must be below 2^24 (sort key range of this build)");
-  if ((int64_t)c->V * c->d > (int64_t)1 << 31 || 2 * f.max_edges * (int64_t)c->d > ((int64_t)1 << 40))
-    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "problem too large for this build");
-  // messages per relation chunk: 48 at minibatch scale; grows with the capacity so that a full-graph
-  // context does not cut a popular relation into thousands of chunks
-  if (2 * f.max_edges > 65536) c->chunk = 48 * (int)((2 * f.max_edges + 65535) / 65536);
-  if (c->kind == RGCN_KIND_BLOCK) {
-    c->nb = f.num_bases;
-    if (c->d % c->nb != 0)
-      RGCN_FAIL(c, RGCN_ERR_INVALID, "InternalEncoderDimension must be divisible by NumberOfBasisFunctions "
-                                     "(the reference silently mis-groups otherwise: gcn_basis_concat.py:15,42)");
-    c->sd = c->d / c->nb;
-    RGCN_TRY(block_geometry(c));
-  } else {
-    c->B = f.num_bases;
-    if (c->B > 64) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "NumberOfBasisFunctions > 64 (basis)");
-  }
-  const bool tdiag = c->kind == RGCN_KIND_BASIS_TDIAG, pdiag = c->kind == RGCN_KIND_BASIS_PDIAG;
-  // equal row chunks (the reduce-scatter / all-gather want them equal): rank g finishes rows [g * shard_rows, +shard_rows)
-  c->shard_rows = (c->V + c->world - 1) / c->world;
-  c->V_pad = c->shard_rows * c->world;
-  c->row_lo = std::min(c->V, c->rank * c->shard_rows);
-  c->row_hi = std::min(c->V, c->row_lo + c->shard_rows);
-
   RGCN_HIP(c, hipSetDevice(f.device));
   RGCN_HIP(c, acquire_stream(f.device, 0, &c->stream));
   c->main_stream = c->stream;
@@ -501,12 +406,128 @@ static rgcn_status create_impl(rgcn_ctx* c) {
   c->gemm_mode = 6;
   RGCN_HIP(c, hipEventCreate(&c->t0));
   RGCN_HIP(c, hipEventCreate(&c->t1));
-  if (emb) return create_embedding(c);
+  return RGCN_OK;
+}
 
+// BasisGcn with onehot_input=True (gcn_basis.py:16-24): vertex_feature_dimension = EntityCount -- W_forward,
+// W_backward [V,B,d] and W_self [V,d] are lookup tables, kept in the host layout; no GEMM, no fragment tables
+static rgcn_status create_onehot_layer(rgcn_ctx* c, LayerBufs& lb) {
+  const size_t V = c->V, d = c->d, R = c->R;
+  const size_t per_dir = V * (size_t)c->B * d;
+  RGCN_TRY(dmalloc(c, c->pool, &lb.wrel, 2 * per_dir, true));
+  RGCN_TRY(dmalloc(c, c->pool, &lb.grel, 2 * per_dir, true));
+  RGCN_TRY(dmalloc(c, c->pool, &lb.coef, 2 * R * c->B, true));
+  RGCN_TRY(dmalloc(c, c->pool, &lb.gcoef, 2 * R * c->B, true));
+  add_param(c, "W_f1", {(int64_t)V, c->B, (int64_t)d}, lb.wrel, lb.grel, LAYOUT_PLAIN);
+  add_param(c, "W_b1", {(int64_t)V, c->B, (int64_t)d}, lb.wrel + per_dir, lb.grel + per_dir, LAYOUT_PLAIN);
+  add_param(c, "C_f1", {(int64_t)R, c->B}, lb.coef, lb.gcoef, LAYOUT_PLAIN);
+  add_param(c, "C_b1", {(int64_t)R, c->B}, lb.coef + R * c->B, lb.gcoef + R * c->B, LAYOUT_PLAIN);
+  RGCN_TRY(dmalloc(c, c->pool, &lb.wself, V * d, true));
+  RGCN_TRY(dmalloc(c, c->pool, &lb.gwself, V * d, true));
+  RGCN_TRY(dmalloc(c, c->pool, &lb.bias, d, true));
+  RGCN_TRY(dmalloc(c, c->pool, &lb.gbias, d, true));
+  add_param(c, "W_self1", {(int64_t)V, (int64_t)d}, lb.wself, lb.gwself, LAYOUT_PLAIN);
+  add_param(c, "b1", {(int64_t)d}, lb.bias, lb.gbias, LAYOUT_PLAIN);
+  c->params.back().no_grad = true;
+  return RGCN_OK;
+}
+
+static rgcn_status create_block_layer(rgcn_ctx* c, LayerBufs& lb, const std::string& sl) {
+  const size_t R = c->R;
+  const size_t per_dir = R * c->nb * c->sd * c->sd;
+  RGCN_TRY(dmalloc(c, c->pool, &lb.wrel, 2 * per_dir, true));
+  RGCN_TRY(dmalloc(c, c->pool, &lb.grel, 2 * per_dir, true));
+  add_param(c, "W_f" + sl, {(int64_t)R, c->nb, c->sd, c->sd}, lb.wrel, lb.grel, LAYOUT_BLOCK_T);
+  add_param(c, "W_b" + sl, {(int64_t)R, c->nb, c->sd, c->sd}, lb.wrel + per_dir, lb.grel + per_dir, LAYOUT_BLOCK_T);
+  return dmalloc(c, c->pool, &lb.wtile, block_rows_weight_floats(c), true);
+}
+
+// gcn_basis_times_diag.py:38-42.  W_forward, W_backward stay in the host layout [d][B.d]: it is the B operand of
+// P = H . W with N contiguous; the coefficients are [R,B,d] per direction, their sigmoid a table of the same shape
+static rgcn_status create_tdiag_layer(rgcn_ctx* c, LayerBufs& lb, const std::string& sl) {
+  const size_t d = c->d, R = c->R;
+  const size_t per_dir = (size_t)c->B * d * d, per_c = R * c->B * d;
+  RGCN_TRY(dmalloc(c, c->pool, &lb.wrel, 2 * per_dir, true));
+  RGCN_TRY(dmalloc(c, c->pool, &lb.grel, 2 * per_dir, true));
+  RGCN_TRY(dmalloc(c, c->pool, &lb.coef, 2 * per_c, true));
+  RGCN_TRY(dmalloc(c, c->pool, &lb.gcoef, 2 * per_c, true));
+  RGCN_TRY(dmalloc(c, c->pool, &lb.tdiag_g, 2 * per_c, true));
+  add_param(c, "W_f" + sl, {(int64_t)d, c->B, (int64_t)d}, lb.wrel, lb.grel, LAYOUT_PLAIN);
+  add_param(c, "W_b" + sl, {(int64_t)d, c->B, (int64_t)d}, lb.wrel + per_dir, lb.grel + per_dir, LAYOUT_PLAIN);
+  add_param(c, "C_f" + sl, {(int64_t)R, c->B, (int64_t)d}, lb.coef, lb.gcoef, LAYOUT_PLAIN);
+  add_param(c, "C_b" + sl, {(int64_t)R, c->B, (int64_t)d}, lb.coef + per_c, lb.gcoef + per_c, LAYOUT_PLAIN);
+  return RGCN_OK;
+}
+
+// repl: the layer's slice of rgcn_ctx::repl_grads (sharded run), or null
+static rgcn_status create_basis_layer(rgcn_ctx* c, LayerBufs& lb, const std::string& sl, float* repl) {
+  const size_t d = c->d, R = c->R;
+  const size_t per_dir = (size_t)c->B * d * d;
+  RGCN_TRY(dmalloc(c, c->pool, &lb.wrel, 2 * per_dir, true));
+  if (repl) lb.grel = repl + d * d;
+  else RGCN_TRY(dmalloc(c, c->pool, &lb.grel, 2 * per_dir, true));
+  RGCN_TRY(dmalloc(c, c->pool, &lb.coef, 2 * R * c->B, true));
+  RGCN_TRY(dmalloc(c, c->pool, &lb.gcoef, 2 * R * c->B, true));
+  // (BASIS_PDIAG: the two direction groups swapped -- the forward-direction units contract with W_backward)
+  const bool pdiag = c->kind == RGCN_KIND_BASIS_PDIAG;
+  const size_t off_f = pdiag ? per_dir : 0, off_b = pdiag ? 0 : per_dir;
+  add_param(c, "W_f" + sl, {(int64_t)d, c->B, (int64_t)d}, lb.wrel + off_f, lb.grel + off_f, LAYOUT_BASIS_T);
+  add_param(c, "W_b" + sl, {(int64_t)d, c->B, (int64_t)d}, lb.wrel + off_b, lb.grel + off_b, LAYOUT_BASIS_T);
+  add_param(c, "C_f" + sl, {(int64_t)R, c->B}, lb.coef, lb.gcoef, LAYOUT_PLAIN);
+  add_param(c, "C_b" + sl, {(int64_t)R, c->B}, lb.coef + R * c->B, lb.gcoef + R * c->B, LAYOUT_PLAIN);
+  return RGCN_OK;
+}
+
+// the basis layer's tensors and, behind them, the diagonal tables
+static rgcn_status create_pdiag_layer(rgcn_ctx* c, LayerBufs& lb, const std::string& sl) {
+  const size_t d = c->d, R = c->R;
+  RGCN_TRY(create_basis_layer(c, lb, sl, nullptr));
+  // gcn_basis_plus_diag.py:42-47: the BACKWARD table comes first in get_weights(); device: [2R][d], forward first
+  RGCN_TRY(dmalloc(c, c->pool, &lb.dtab, 2 * R * d, true));
+  RGCN_TRY(dmalloc(c, c->pool, &lb.gdtab, 2 * R * d, true));
+  add_param(c, "D_b" + sl, {(int64_t)R, (int64_t)d}, lb.dtab + R * d, lb.gdtab + R * d, LAYOUT_PLAIN);
+  add_param(c, "D_f" + sl, {(int64_t)R, (int64_t)d}, lb.dtab, lb.gdtab, LAYOUT_PLAIN);
+  return RGCN_OK;
+}
+
+// what every layer form but the one-hot first layer ends with: W_self and the fragment tables, the bias, the highway pair
+static rgcn_status create_layer_tail(rgcn_ctx* c, LayerBufs& lb, const std::string& sl, float* repl) {
+  const size_t d = c->d;
+  const bool tdiag = c->kind == RGCN_KIND_BASIS_TDIAG, pdiag = c->kind == RGCN_KIND_BASIS_PDIAG;
+  RGCN_TRY(dmalloc(c, c->pool, &lb.wself, d * d, true));
+  {      // fragment tables (allocated here: a capture may be the first call that needs them)
+    const size_t ws = 16 * gemm_bfrag_words((int)d, (int)d);
+    RGCN_TRY(dmalloc(c, c->pool, &lb.wself_nn, ws, false));
+    RGCN_TRY(dmalloc(c, c->pool, &lb.wself_nt, ws, false));
+    if (c->kind == RGCN_KIND_BASIS || pdiag) {
+      const int Bd = c->B * (int)d;
+      RGCN_TRY(dmalloc(c, c->pool, &lb.wrel_nn, 2 * 16 * gemm_bfrag_words(Bd, (int)d), false));
+      RGCN_TRY(dmalloc(c, c->pool, &lb.wrel_nt, 2 * 16 * gemm_bfrag_words((int)d, Bd), false));
+    }
+  }
+  if (repl) lb.gwself = repl;
+  else RGCN_TRY(dmalloc(c, c->pool, &lb.gwself, d * d, true));
+  RGCN_TRY(dmalloc(c, c->pool, &lb.bias, d, true));
+  RGCN_TRY(dmalloc(c, c->pool, &lb.gbias, d, true));
+  add_param(c, "W_self" + sl, {(int64_t)d, (int64_t)d}, lb.wself, lb.gwself, LAYOUT_PLAIN);
+  add_param(c, "b" + sl, {(int64_t)d}, lb.bias, lb.gbias, LAYOUT_PLAIN);
+  c->params.back().no_grad = !(tdiag || pdiag);      // (BasisGcnTimesDiag and BasisGcnWithDiag add their bias)
+  if (c->highway) {      // HighwayLayer.local_get_weights (highway_layer.py): [W, b], behind the layer it wraps
+    RGCN_TRY(dmalloc(c, c->pool, &lb.whw, d * d, true));
+    RGCN_TRY(dmalloc(c, c->pool, &lb.gwhw, d * d, true));
+    RGCN_TRY(dmalloc(c, c->pool, &lb.bhw, d, true));
+    RGCN_TRY(dmalloc(c, c->pool, &lb.gbhw, d, true));
+    add_param(c, "W_highway" + sl, {(int64_t)d, (int64_t)d}, lb.whw, lb.gwhw, LAYOUT_PLAIN);
+    add_param(c, "b_highway" + sl, {(int64_t)d}, lb.bhw, lb.gbhw, LAYOUT_PLAIN);
+  }
+  return RGCN_OK;
+}
+
+// the parameter table in Model.get_weights() order: the input layer, then layer after layer
+static rgcn_status create_params(rgcn_ctx* c) {
   // every [V,d] buffer carries V_pad rows (== V on one GPU): the collectives work on world equal chunks, the
   // padding rows stay zero
-  const size_t V = c->V, d = c->d, R = c->R, Vd = (size_t)c->V_pad * d;
-  RGCN_HIP(c, hipEventCreateWithFlags(&c->ev_gather, hipEventDisableTiming));
+  const size_t V = c->V, d = c->d, Vd = (size_t)c->V_pad * d;
   if (!c->onehot) {      // (one-hot input: no AffineTransform under the layers, model_builder.py:140-165)
     RGCN_TRY(dmalloc(c, c->pool, &c->w_emb, Vd, true));
     RGCN_TRY(dmalloc(c, c->pool, &c->g_emb, Vd, true));
@@ -518,7 +539,7 @@ static rgcn_status create_impl(rgcn_ctx* c) {
   c->layers.resize(c->L + 1);
   // world > 1: the gradients every rank holds a partial sum of -- W_self, and the basis tensors -- sit in ONE
   // allocation, layer after layer, so that the backward pass ends with one all-reduce instead of 2-3 per layer
-  const size_t repl_per_layer = d * d + (c->kind == RGCN_KIND_BASIS ? 2 * (size_t)f.num_bases * d * d : 0);
+  const size_t repl_per_layer = d * d + (c->kind == RGCN_KIND_BASIS ? 2 * (size_t)c->cfg.num_bases * d * d : 0);
   if (c->world > 1) {
     c->repl_grads_floats = repl_per_layer * c->L;
     RGCN_TRY(dmalloc(c, c->pool, &c->repl_grads, c->repl_grads_floats, true));
@@ -528,93 +549,23 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     const std::string sl = std::to_string(l);
     float* repl = c->repl_grads ? c->repl_grads + repl_per_layer * (l - 1) : nullptr;
     if (c->onehot && l == 1) {
-      // BasisGcn with onehot_input=True (gcn_basis.py:16-24): vertex_feature_dimension = EntityCount -- W_forward,
-      // W_backward [V,B,d] and W_self [V,d] are lookup tables, kept in the host layout; no GEMM, no fragment tables
-      const size_t per_dir = V * (size_t)c->B * d;
-      RGCN_TRY(dmalloc(c, c->pool, &lb.wrel, 2 * per_dir, true));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.grel, 2 * per_dir, true));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.coef, 2 * R * c->B, true));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.gcoef, 2 * R * c->B, true));
-      add_param(c, "W_f1", {(int64_t)V, c->B, (int64_t)d}, lb.wrel, lb.grel, LAYOUT_PLAIN);
-      add_param(c, "W_b1", {(int64_t)V, c->B, (int64_t)d}, lb.wrel + per_dir, lb.grel + per_dir, LAYOUT_PLAIN);
-      add_param(c, "C_f1", {(int64_t)R, c->B}, lb.coef, lb.gcoef, LAYOUT_PLAIN);
-      add_param(c, "C_b1", {(int64_t)R, c->B}, lb.coef + R * c->B, lb.gcoef + R * c->B, LAYOUT_PLAIN);
-      RGCN_TRY(dmalloc(c, c->pool, &lb.wself, V * d, true));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.gwself, V * d, true));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.bias, d, true));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.gbias, d, true));
-      add_param(c, "W_self1", {(int64_t)V, (int64_t)d}, lb.wself, lb.gwself, LAYOUT_PLAIN);
-      add_param(c, "b1", {(int64_t)d}, lb.bias, lb.gbias, LAYOUT_PLAIN);
-      c->params.back().no_grad = true;
+      RGCN_TRY(create_onehot_layer(c, lb));
       continue;
     }
-    if (c->kind == RGCN_KIND_BLOCK) {
-      const size_t per_dir = R * c->nb * c->sd * c->sd;
-      RGCN_TRY(dmalloc(c, c->pool, &lb.wrel, 2 * per_dir, true));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.grel, 2 * per_dir, true));
-      add_param(c, "W_f" + sl, {(int64_t)R, c->nb, c->sd, c->sd}, lb.wrel, lb.grel, LAYOUT_BLOCK_T);
-      add_param(c, "W_b" + sl, {(int64_t)R, c->nb, c->sd, c->sd}, lb.wrel + per_dir, lb.grel + per_dir, LAYOUT_BLOCK_T);
-      if (c->nb <= 512) RGCN_TRY(dmalloc(c, c->pool, &lb.wtile, block_rows_weight_floats(c), true));
-    } else if (tdiag) {
-      // gcn_basis_times_diag.py:38-42.  W_forward, W_backward stay in the host layout [d][B.d]: it is the B operand of
-      // P = H . W with N contiguous; the coefficients are [R,B,d] per direction, their sigmoid a table of the same shape
-      const size_t per_dir = (size_t)c->B * d * d, per_c = R * c->B * d;
-      RGCN_TRY(dmalloc(c, c->pool, &lb.wrel, 2 * per_dir, true));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.grel, 2 * per_dir, true));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.coef, 2 * per_c, true));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.gcoef, 2 * per_c, true));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.tdiag_g, 2 * per_c, true));
-      add_param(c, "W_f" + sl, {(int64_t)d, c->B, (int64_t)d}, lb.wrel, lb.grel, LAYOUT_PLAIN);
-      add_param(c, "W_b" + sl, {(int64_t)d, c->B, (int64_t)d}, lb.wrel + per_dir, lb.grel + per_dir, LAYOUT_PLAIN);
-      add_param(c, "C_f" + sl, {(int64_t)R, c->B, (int64_t)d}, lb.coef, lb.gcoef, LAYOUT_PLAIN);
-      add_param(c, "C_b" + sl, {(int64_t)R, c->B, (int64_t)d}, lb.coef + per_c, lb.gcoef + per_c, LAYOUT_PLAIN);
-    } else {
-      const size_t per_dir = (size_t)c->B * d * d;
-      RGCN_TRY(dmalloc(c, c->pool, &lb.wrel, 2 * per_dir, true));
-      if (repl) lb.grel = repl + d * d;
-      else RGCN_TRY(dmalloc(c, c->pool, &lb.grel, 2 * per_dir, true));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.coef, 2 * R * c->B, true));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.gcoef, 2 * R * c->B, true));
-      // (BASIS_PDIAG: the two direction groups swapped -- the forward-direction units contract with W_backward)
-      const size_t off_f = pdiag ? per_dir : 0, off_b = pdiag ? 0 : per_dir;
-      add_param(c, "W_f" + sl, {(int64_t)d, c->B, (int64_t)d}, lb.wrel + off_f, lb.grel + off_f, LAYOUT_BASIS_T);
-      add_param(c, "W_b" + sl, {(int64_t)d, c->B, (int64_t)d}, lb.wrel + off_b, lb.grel + off_b, LAYOUT_BASIS_T);
-      add_param(c, "C_f" + sl, {(int64_t)R, c->B}, lb.coef, lb.gcoef, LAYOUT_PLAIN);
-      add_param(c, "C_b" + sl, {(int64_t)R, c->B}, lb.coef + R * c->B, lb.gcoef + R * c->B, LAYOUT_PLAIN);
-      if (pdiag) {      // gcn_basis_plus_diag.py:42-47: the BACKWARD table comes first in get_weights(); device: [2R][d], forward first
-        RGCN_TRY(dmalloc(c, c->pool, &lb.dtab, 2 * R * d, true));
-        RGCN_TRY(dmalloc(c, c->pool, &lb.gdtab, 2 * R * d, true));
-        add_param(c, "D_b" + sl, {(int64_t)R, (int64_t)d}, lb.dtab + R * d, lb.gdtab + R * d, LAYOUT_PLAIN);
-        add_param(c, "D_f" + sl, {(int64_t)R, (int64_t)d}, lb.dtab, lb.gdtab, LAYOUT_PLAIN);
-      }
+    switch (c->kind) {
+      case RGCN_KIND_BLOCK: RGCN_TRY(create_block_layer(c, lb, sl)); break;
+      case RGCN_KIND_BASIS_TDIAG: RGCN_TRY(create_tdiag_layer(c, lb, sl)); break;
+      case RGCN_KIND_BASIS_PDIAG: RGCN_TRY(create_pdiag_layer(c, lb, sl)); break;
+      default: RGCN_TRY(create_basis_layer(c, lb, sl, repl)); break;
     }
-    RGCN_TRY(dmalloc(c, c->pool, &lb.wself, d * d, true));
-    {      // fragment tables (allocated here: a capture may be the first call that needs them)
-      const size_t ws = 16 * gemm_bfrag_words((int)d, (int)d);
-      RGCN_TRY(dmalloc(c, c->pool, &lb.wself_nn, ws, false));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.wself_nt, ws, false));
-      if (c->kind == RGCN_KIND_BASIS || pdiag) {
-        const int Bd = c->B * (int)d;
-        RGCN_TRY(dmalloc(c, c->pool, &lb.wrel_nn, 2 * 16 * gemm_bfrag_words(Bd, (int)d), false));
-        RGCN_TRY(dmalloc(c, c->pool, &lb.wrel_nt, 2 * 16 * gemm_bfrag_words((int)d, Bd), false));
-      }
-    }
-    if (repl) lb.gwself = repl;
-    else RGCN_TRY(dmalloc(c, c->pool, &lb.gwself, d * d, true));
-    RGCN_TRY(dmalloc(c, c->pool, &lb.bias, d, true));
-    RGCN_TRY(dmalloc(c, c->pool, &lb.gbias, d, true));
-    add_param(c, "W_self" + sl, {(int64_t)d, (int64_t)d}, lb.wself, lb.gwself, LAYOUT_PLAIN);
-    add_param(c, "b" + sl, {(int64_t)d}, lb.bias, lb.gbias, LAYOUT_PLAIN);
-    c->params.back().no_grad = !(tdiag || pdiag);      // (BasisGcnTimesDiag and BasisGcnWithDiag add their bias)
-    if (c->highway) {      // HighwayLayer.local_get_weights (highway_layer.py): [W, b], behind the layer it wraps
-      RGCN_TRY(dmalloc(c, c->pool, &lb.whw, d * d, true));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.gwhw, d * d, true));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.bhw, d, true));
-      RGCN_TRY(dmalloc(c, c->pool, &lb.gbhw, d, true));
-      add_param(c, "W_highway" + sl, {(int64_t)d, (int64_t)d}, lb.whw, lb.gwhw, LAYOUT_PLAIN);
-      add_param(c, "b_highway" + sl, {(int64_t)d}, lb.bhw, lb.gbhw, LAYOUT_PLAIN);
-    }
+    RGCN_TRY(create_layer_tail(c, lb, sl, repl));
   }
+  return RGCN_OK;
+}
+
+// W_relation (the decoder's, behind the layers in get_weights()) and what every kind keeps per layer and per pass
+static rgcn_status create_activations(rgcn_ctx* c) {
+  const size_t V = c->V, d = c->d, Vd = (size_t)c->V_pad * d;
   RGCN_TRY(dmalloc(c, c->pool, &c->w_rel, Vd, true));
   RGCN_TRY(dmalloc(c, c->pool, &c->g_rel, Vd, true));
   add_param(c, "W_relation", {(int64_t)V, (int64_t)d}, c->w_rel, c->g_rel, LAYOUT_PLAIN);
@@ -636,56 +587,69 @@ static rgcn_status create_impl(rgcn_ctx* c) {
     RGCN_TRY(dmalloc(c, c->pool, &c->dbuf[k], Vd, true));
     RGCN_TRY(dmalloc(c, c->pool, &c->dsbuf[k], Vd, true));
   }
-  const size_t M = 2 * (size_t)f.max_edges;
-  size_t slab = 64 * d * d;   // split-K slabs of the dW_self GEMM
-  // most relation chunks any graph that fits the context can have: the chunk size follows the graph's own size
-  // (graph_build), so a graph of 65536 messages cut at 48 can have more chunks than the largest graph cut coarser
-  const size_t max_rel_chunks = std::max((M + c->chunk - 1) / c->chunk, (std::min<size_t>(M, 65536) + 47) / 48) + 2 * R;
-  if (c->kind == RGCN_KIND_BLOCK) {
-    RGCN_TRY(dmalloc(c, c->pool, &c->msgbuf, (M ? M : 1) * d, false));
-    const size_t per_rel = (size_t)c->sd * c->sd * c->nb;
-    c->slab_dw_floats = max_rel_chunks * per_rel;
-    RGCN_TRY(dmalloc(c, c->pool, &c->slab_dw, c->slab_dw_floats, false));
-  } else if (tdiag) {
-    const size_t pd = 2 * V * (size_t)c->B * d;      // [2][V][B.d]
-    c->tdiag_P.assign(c->L + 1, nullptr);
-    for (int l = 1; l <= c->L; ++l) RGCN_TRY(dmalloc(c, c->pool, &c->tdiag_P[l], pd, true));
-    RGCN_TRY(dmalloc(c, c->pool, &c->tdiag_dP, pd, true));
-    RGCN_TRY(dmalloc(c, c->pool, &c->tdiag_dh, 2 * V * d, true));
-    const size_t s2 = 16 * 2 * (size_t)c->B * d * d;      // dW_dir = H^T . dP_dir: two groups, at most 16 slabs each
-    if (s2 > slab) slab = s2;
-    c->slab_dw_floats = max_rel_chunks * (size_t)c->B * d;      // per-chunk partials of dG
-    RGCN_TRY(dmalloc(c, c->pool, &c->slab_dw, c->slab_dw_floats, false));
-  } else {
-    const size_t zc = 2 * (size_t)c->B * d;
-    RGCN_TRY(dmalloc(c, c->pool, &c->msgbuf2, V * zc, true));
-    // aggbuf [2][V][d]: unit products (forward), gathered upstream rows (backward)
-    RGCN_TRY(dmalloc(c, c->pool, &c->aggbuf, 2 * V * d, true));
-    c->zsave.assign(c->L + 1, nullptr);
-    // (a one-hot layer 1 has no Z)
-    for (int l = c->onehot ? 2 : 1; l <= c->L; ++l) RGCN_TRY(dmalloc(c, c->pool, &c->zsave[l], V * zc, true));
-    // dW'_dir = Zc_dir^T . Dc_dir: two groups, split over V as bwd_layer_partial asks (auto_split_k: past 16 slabs at few
-    // tiles and many rows, e.g. 35 at B = 1, d = 260, V >= 4480), never fewer than 16
-    const size_t s2 = (size_t)std::max(16, auto_split_k((int)zc, (int)d, (int)V)) * zc * d;
-    if (s2 > slab) slab = s2;
-    c->slab_dw_floats = max_rel_chunks * (size_t)c->B;
-    if (pdiag) {
-      // the chunk slabs of dC [chunks][B] and, behind them at a 16-byte boundary, of dD [chunks][d]; the mixing table of
-      // every layer, the diagonal aggregate, da and the row-local part of dH
-      const size_t dc = (max_rel_chunks * (size_t)c->B + 3) / 4 * 4;
-      c->slab_dw_floats = dc + max_rel_chunks * d;
-      c->pdiag_slab_chunks = max_rel_chunks;
-      RGCN_TRY(dmalloc(c, c->pool, &c->slab_dw, c->slab_dw_floats, false));
-      c->pdiag_slab_dd = c->slab_dw + dc;
-      c->pdiag_a.assign(c->L + 1, nullptr);
-      for (int l = 1; l <= c->L; ++l) RGCN_TRY(dmalloc(c, c->pool, &c->pdiag_a[l], 2 * V * (size_t)c->B, true));
-      RGCN_TRY(dmalloc(c, c->pool, &c->pdiag_da, 2 * V * (size_t)c->B, true));
-      RGCN_TRY(dmalloc(c, c->pool, &c->pdiag_agg, V * d, true));
-      RGCN_TRY(dmalloc(c, c->pool, &c->pdiag_dh, V * d, true));
-    } else {
-      RGCN_TRY(dmalloc(c, c->pool, &c->slab_dw, c->slab_dw_floats, false));
-    }
-  }
+  return RGCN_OK;
+}
+
+// The scratch of each kind.  M: message capacity; max_rel_chunks: most relation chunks a graph that fits can have; slab: the
+// split-K slab floats the kind's own weight-gradient GEMM needs, where that is more than the dW_self GEMM's
+static rgcn_status create_block_scratch(rgcn_ctx* c, size_t M, size_t max_rel_chunks) {
+  RGCN_TRY(dmalloc(c, c->pool, &c->msgbuf, (M ? M : 1) * c->d, false));
+  const size_t per_rel = (size_t)c->sd * c->sd * c->nb;
+  c->slab_dw_floats = max_rel_chunks * per_rel;
+  return dmalloc(c, c->pool, &c->slab_dw, c->slab_dw_floats, false);
+}
+
+static rgcn_status create_tdiag_scratch(rgcn_ctx* c, size_t max_rel_chunks, size_t& slab) {
+  const size_t V = c->V, d = c->d;
+  const size_t pd = 2 * V * (size_t)c->B * d;      // [2][V][B.d]
+  c->tdiag_P.assign(c->L + 1, nullptr);
+  for (int l = 1; l <= c->L; ++l) RGCN_TRY(dmalloc(c, c->pool, &c->tdiag_P[l], pd, true));
+  RGCN_TRY(dmalloc(c, c->pool, &c->tdiag_dP, pd, true));
+  RGCN_TRY(dmalloc(c, c->pool, &c->tdiag_dh, 2 * V * d, true));
+  const size_t s2 = 16 * 2 * (size_t)c->B * d * d;      // dW_dir = H^T . dP_dir: two groups, at most 16 slabs each
+  if (s2 > slab) slab = s2;
+  c->slab_dw_floats = max_rel_chunks * (size_t)c->B * d;      // per-chunk partials of dG
+  return dmalloc(c, c->pool, &c->slab_dw, c->slab_dw_floats, false);
+}
+
+// BASIS_PDIAG on top of the basis kind's: the chunk slabs of dC [chunks][B] and, behind them at a 16-byte boundary, of dD
+// [chunks][d]; the mixing table of every layer, the diagonal aggregate, da and the row-local part of dH
+static rgcn_status create_pdiag_extras(rgcn_ctx* c, size_t max_rel_chunks) {
+  const size_t V = c->V, d = c->d;
+  const size_t dc = (max_rel_chunks * (size_t)c->B + 3) / 4 * 4;
+  c->slab_dw_floats = dc + max_rel_chunks * d;
+  c->pdiag_slab_chunks = max_rel_chunks;
+  RGCN_TRY(dmalloc(c, c->pool, &c->slab_dw, c->slab_dw_floats, false));
+  c->pdiag_slab_dd = c->slab_dw + dc;
+  c->pdiag_a.assign(c->L + 1, nullptr);
+  for (int l = 1; l <= c->L; ++l) RGCN_TRY(dmalloc(c, c->pool, &c->pdiag_a[l], 2 * V * (size_t)c->B, true));
+  RGCN_TRY(dmalloc(c, c->pool, &c->pdiag_da, 2 * V * (size_t)c->B, true));
+  RGCN_TRY(dmalloc(c, c->pool, &c->pdiag_agg, V * d, true));
+  return dmalloc(c, c->pool, &c->pdiag_dh, V * d, true);
+}
+
+static rgcn_status create_basis_scratch(rgcn_ctx* c, size_t max_rel_chunks, size_t& slab) {
+  const size_t V = c->V, d = c->d;
+  const size_t zc = 2 * (size_t)c->B * d;
+  RGCN_TRY(dmalloc(c, c->pool, &c->msgbuf2, V * zc, true));
+  // aggbuf [2][V][d]: unit products (forward), gathered upstream rows (backward)
+  RGCN_TRY(dmalloc(c, c->pool, &c->aggbuf, 2 * V * d, true));
+  c->zsave.assign(c->L + 1, nullptr);
+  // (a one-hot layer 1 has no Z)
+  for (int l = c->onehot ? 2 : 1; l <= c->L; ++l) RGCN_TRY(dmalloc(c, c->pool, &c->zsave[l], V * zc, true));
+  // dW'_dir = Zc_dir^T . Dc_dir: two groups, split over V as units_product_dw asks (auto_split_k: past 16 slabs at few
+  // tiles and many rows, e.g. 35 at B = 1, d = 260, V >= 4480), never fewer than 16
+  const size_t s2 = (size_t)std::max(16, auto_split_k((int)zc, (int)d, (int)V)) * zc * d;
+  if (s2 > slab) slab = s2;
+  if (c->kind == RGCN_KIND_BASIS_PDIAG) return create_pdiag_extras(c, max_rel_chunks);
+  c->slab_dw_floats = max_rel_chunks * (size_t)c->B;
+  return dmalloc(c, c->pool, &c->slab_dw, c->slab_dw_floats, false);
+}
+
+// what every kind ends with: the split-K slabs, the staging buffer of the layout conversions, the column-sum scratch, the
+// zero page, the two graph sets, the relation owner table
+static rgcn_status create_shared_tail(rgcn_ctx* c, size_t slab) {
+  const size_t V = c->V, d = c->d, R = c->R, Vd = (size_t)c->V_pad * d;
   c->slab_floats = slab;
   RGCN_TRY(dmalloc(c, c->pool, &c->slab, slab, true));
   size_t stage = Vd;
@@ -709,6 +673,48 @@ static rgcn_status create_impl(rgcn_ctx* c) {
   }
   RGCN_HIP(c, hipStreamSynchronize(c->stream));
   return RGCN_OK;
+}
+
+static rgcn_status create_impl(rgcn_ctx* c) {
+  const rgcn_config& f = c->cfg;
+  const ConfigVerdict verdict = check_config(f, c->highway);
+  if (verdict.status != RGCN_OK) RGCN_FAIL(c, verdict.status, verdict.message);
+  c->V = f.num_entities; c->R = f.num_relations; c->d = f.dim; c->L = f.num_layers; c->kind = f.kind;
+  c->rank = f.rank; c->world = f.world;
+  c->onehot = f.input_mode == RGCN_INPUT_ONEHOT;
+  c->embedding = f.kind == RGCN_KIND_EMBEDDING;
+  // messages per relation chunk: 48 at minibatch scale; grows with the capacity so that a full-graph
+  // context does not cut a popular relation into thousands of chunks
+  if (2 * f.max_edges > 65536) c->chunk = 48 * (int)((2 * f.max_edges + 65535) / 65536);
+  if (c->kind == RGCN_KIND_BLOCK) {
+    c->nb = f.num_bases;
+    c->sd = c->d / c->nb;
+    RGCN_TRY(block_geometry(c));
+  } else {
+    c->B = f.num_bases;
+  }
+  // equal row chunks (the reduce-scatter / all-gather want them equal): rank g finishes rows [g * shard_rows, +shard_rows)
+  c->shard_rows = (c->V + c->world - 1) / c->world;
+  c->V_pad = c->shard_rows * c->world;
+  c->row_lo = std::min(c->V, c->rank * c->shard_rows);
+  c->row_hi = std::min(c->V, c->row_lo + c->shard_rows);
+
+  RGCN_TRY(create_streams(c));
+  if (c->embedding) return create_embedding(c);
+  RGCN_HIP(c, hipEventCreateWithFlags(&c->ev_gather, hipEventDisableTiming));
+  RGCN_TRY(create_params(c));
+  RGCN_TRY(create_activations(c));
+  const size_t M = 2 * (size_t)f.max_edges;
+  size_t slab = 64 * (size_t)c->d * c->d;   // split-K slabs of the dW_self GEMM
+  // most relation chunks any graph that fits the context can have: the chunk size follows the graph's own size
+  // (graph_build), so a graph of 65536 messages cut at 48 can have more chunks than the largest graph cut coarser
+  const size_t max_rel_chunks = std::max((M + c->chunk - 1) / c->chunk, (std::min<size_t>(M, 65536) + 47) / 48) + 2 * (size_t)c->R;
+  switch (c->kind) {
+    case RGCN_KIND_BLOCK: RGCN_TRY(create_block_scratch(c, M, max_rel_chunks)); break;
+    case RGCN_KIND_BASIS_TDIAG: RGCN_TRY(create_tdiag_scratch(c, max_rel_chunks, slab)); break;
+    default: RGCN_TRY(create_basis_scratch(c, max_rel_chunks, slab)); break;      // (BASIS_PDIAG: with its extras)
+  }
+  return create_shared_tail(c, slab);
 }
 
 // ---------------------------------------------------------------- layout conversion

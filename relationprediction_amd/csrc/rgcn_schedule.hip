@@ -93,6 +93,10 @@ static rgcn_status refresh_weight_fragments(rgcn_ctx* c) {
   c->frag_version = c->capturing ? ~0ull : c->weights_version;
   return RGCN_OK;
 }
+// the rows whose self-loop term and epilogue this rank owns: its shard of a sharded run, every row on one GPU
+struct RowShard { int lo, hi; };
+static RowShard row_shard(const rgcn_ctx* c) { return c->world > 1 ? RowShard{c->row_lo, c->row_hi} : RowShard{0, c->V}; }
+
 // the self-loop products: one group, W_self as the pre-split B operand (forward: [k][n]; dH: used transposed, [n][k]);
 // whoever launches one refreshes the fragment tables first
 static GemmBatch self_loop_batch(const rgcn_ctx* c, int l, bool transposed) {
@@ -104,7 +108,7 @@ static GemmBatch self_loop_batch(const rgcn_ctx* c, int l, bool transposed) {
 // S = H_{l-1} . W_self of layer l over this rank's row shard; form_h0 (layer 1): W_emb is the A operand and the product
 // forms H0 = relu(W_emb + b_emb) on load and writes it back (GemmBatch::a_bias / a_out)
 static GemmCall self_fwd_call(const rgcn_ctx* c, int l, bool form_h0) {
-  const int d = c->d, lo = c->world > 1 ? c->row_lo : 0, hi = c->world > 1 ? c->row_hi : c->V;
+  const int d = c->d, lo = row_shard(c).lo, hi = row_shard(c).hi;
   GemmCall q{true, false, hi - lo, d, d, (form_h0 ? c->w_emb : c->H[l - 1]) + (size_t)lo * d, d, c->layers[l].wself, d,
              c->self_buf + (size_t)lo * d, d, 1, c->slab, self_loop_batch(c, l, false)};
   if (form_h0) {
@@ -147,18 +151,149 @@ static GemmBatch tdiag_batch(size_t strideA, size_t strideB, size_t strideC) {
   return b;
 }
 
+// The three batched GEMMs over the (row, direction) units that the basis and the BASIS_PDIAG layer share (LayerBufs::wrel of
+// the latter holds the two groups swapped: forward units x W_backward).  Whoever launches one has refreshed the fragment
+// tables (fwd_layer_partial, bwd_layer_partial).
+// forward: aggbuf[dir] = Zc_dir . W'_dir   ([units, B.d] x [B.d, d], two groups)
+static rgcn_status units_product_fwd(rgcn_ctx* c, int l) {
+  const int d = c->d, V = c->V, Bd = c->B * d;
+  GemmBatch gb = basis_batch(c, (size_t)V * Bd, (size_t)Bd * d, (size_t)V * d, false);
+  if (c->gemm_mode != 0) gb.bfrag = c->layers[l].wrel_nn;
+  gb.strideBfrag = gemm_bfrag_words(Bd, d);
+  gb.wide = 1;
+  return gemm_f32(c, "gemm_basis_fwd", true, false, V, d, Bd, c->zsave[l], Bd, c->layers[l].wrel, d,
+                  c->aggbuf, d, 1, &gb, basis_unit_share(c));
+}
+// dW'_dir = Zc_dir^T . Dc_dir   ([B.d, units] x [units, d], split over the units; two groups); Dc: the upstream rows of the
+// units in aggbuf (basis_gather_units)
+static rgcn_status units_product_dw(rgcn_ctx* c, int l) {
+  const int d = c->d, V = c->V, Bd = c->B * d;
+  const GemmBatch gk = basis_batch(c, (size_t)V * Bd, (size_t)V * d, (size_t)Bd * d, true);
+  return gemm_f32(c, "gemm_basis_dw", false, false, Bd, d, V, c->zsave[l], Bd, c->aggbuf, d, c->layers[l].grel, d,
+                  auto_split_k(2 * Bd, d, V), &gk, basis_unit_share(c));
+}
+// dZc_dir = Dc_dir . W'_dir^T   ([units, d] x [d, B.d], two groups), into msgbuf2
+static rgcn_status units_product_dz(rgcn_ctx* c, int l) {
+  const int d = c->d, V = c->V, Bd = c->B * d;
+  GemmBatch gm = basis_batch(c, (size_t)V * d, (size_t)Bd * d, (size_t)V * Bd, false);
+  if (c->gemm_mode != 0) gm.bfrag = c->layers[l].wrel_nt;
+  gm.strideBfrag = gemm_bfrag_words(d, Bd);
+  return gemm_f32(c, "gemm_basis_dz", true, true, V, Bd, d, c->aggbuf, d, c->layers[l].wrel, d, c->msgbuf2, Bd, 1, &gm,
+                  basis_unit_share(c));
+}
+
+// The six forms a layer takes; fwd_layer_partial and bwd_layer_partial run one function each per form.
+enum LayerForm { FORM_ONEHOT, FORM_BLOCK_ROWS, FORM_BLOCK_TWO_KERNEL, FORM_BASIS, FORM_TDIAG, FORM_PDIAG };
+static LayerForm layer_form(const rgcn_ctx* c, int l) {
+  if (c->onehot && l == 1) return FORM_ONEHOT;
+  if (c->kind == RGCN_KIND_BLOCK) return rows_layer(c) ? FORM_BLOCK_ROWS : FORM_BLOCK_TWO_KERNEL;
+  if (c->kind == RGCN_KIND_BASIS_TDIAG) return FORM_TDIAG;
+  return c->kind == RGCN_KIND_BASIS_PDIAG ? FORM_PDIAG : FORM_BASIS;
+}
+
+// the forward epilogue every form but the one-hot first layer ends with: dst = relu?(dropout(S) + the form's own terms) over
+// this rank's rows (a sharded run leaves the PARTIAL pre-activations, no relu, for the reduce-scatter that follows)
+static CombineArgs fwd_epilogue_args(rgcn_ctx* c, int l, float* dst) {
+  CombineArgs a;
+  a.add = nullptr; a.msg = nullptr; a.row_ptr = nullptr; a.long_rows = nullptr; a.nlong = nullptr;
+  a.out = dst; a.out2 = nullptr; a.base = c->self_buf; a.gate = nullptr; a.V = c->V; a.d = c->d;
+  a.relu = (c->world == 1 && l < c->L) ? 1 : 0;
+  a.row_lo = row_shard(c).lo; a.row_hi = row_shard(c).hi;
+  a.drop = make_drop(c, l, true);
+  a.drop2 = make_drop(c, l, false);
+  return a;
+}
+
+// self: S = H . W_self over the rows of this rank's shard (self_fwd_call); dst: where the layer's result goes
+static rgcn_status fwd_block_rows(rgcn_ctx* c, int l, const GemmCall& self, float* dst) {
+  // S = H . W_self, then ONE kernel: H' = relu(dropout(S) + sum over the row's messages of n W_r H[src]) straight from
+  // the incidence CSR (no message buffer)
+  // (sharded run: the self-loop GEMM covers this rank's row shard, the kernel walks the rank's own messages and writes
+  // the PARTIAL pre-activations -- the self-loop term inside the shard only, no relu -- for the reduce-scatter that
+  // follows)
+  RGCN_TRY(gemm_f32(c, "gemm_self_fwd", self));
+  RGCN_TRY(wait_gather(c));
+  return block_rows(c, "block_rows_fwd", l, false, c->H[l - 1], fwd_epilogue_args(c, l, dst));
+}
+
+static rgcn_status fwd_block_two_kernel(rgcn_ctx* c, int l, const GemmCall& self, float* dst) {
+  const int d = c->d, V = c->V;
+  const double Mmsg = 2.0 * c->g.E / c->world;
+  // Two-kernel form.  The relational messages (HBM-bound) run beside the self-loop GEMM.  A stream that blocks on
+  // another stream's event resumes ~10 us after the event fires, so the chain that continues (the combine) stays on
+  // the stream of the kernel that finishes LAST: the messages on the main stream, the (shorter) GEMM forked.
+  {
+    StreamScope side(c, 0);
+    RGCN_TRY(gemm_f32(c, "gemm_self_fwd", self));
+  }
+  RGCN_TRY(wait_gather(c));
+  RGCN_TRY(block_msg_forward(c, l, c->H[l - 1], c->msgbuf));
+  RGCN_TRY(stream_join(c, 0));
+  CombineArgs a = fwd_epilogue_args(c, l, dst);
+  a.msg = c->g.E > 0 ? c->msgbuf : nullptr;
+  a.row_ptr = c->g.row_ptr; a.long_rows = c->g.long_rows; a.nlong = c->g.nlong;
+  return combine(c, "combine_fwd", a, 4.0 * d * (2.0 * V + Mmsg) + 4.0 * V);
+}
+
+static rgcn_status fwd_tdiag(rgcn_ctx* c, int l, const GemmCall& self, float* dst) {
+  // transform first (basis_tdiag.hip): P_dir = H . W_dir.reshape(d, B.d), two groups of one batched GEMM over the same
+  // A operand, kept per layer for dC; the self-loop product beside it on side stream 1; then ONE destination-major
+  // kernel: H' = relu(dropout(S) + sum over the row's messages of n sum_b G[rel,b,:] P_dir[src,b,:] + b)
+  const int d = c->d, V = c->V, Bd = c->B * d;
+  RGCN_TRY(tdiag_refresh_gates(c, l));
+  {
+    StreamScope side(c, 1);
+    RGCN_TRY(gemm_f32(c, "gemm_self_fwd", self));
+  }
+  const GemmBatch gb = tdiag_batch(0, (size_t)d * Bd, (size_t)V * Bd);
+  RGCN_TRY(gemm_f32(c, "gemm_tdiag_fwd", true, false, V, Bd, d, c->H[l - 1], d, c->layers[l].wrel, Bd, c->tdiag_P[l], Bd, 1, &gb));
+  RGCN_TRY(stream_join(c, 1));
+  return tdiag_rows_forward(c, l, c->tdiag_P[l], fwd_epilogue_args(c, l, dst));
+}
+
+static rgcn_status fwd_pdiag(rgcn_ctx* c, int l, const GemmCall& self, float* dst) {
+  // basis_pdiag.hip: ONE destination-major walk forms the mixing table a_l, the diagonal aggregate and the rows' own unit
+  // rows Zc[(v,dir),b,:] = a_dir[v,b] H[v,:]; Zc . W' is the basis kind's batched product over the units (LayerBufs::wrel
+  // holds the two groups swapped: forward units x W_backward); the self-loop product beside both on side stream 1; then
+  // H' = relu(dropout(S) + the two unit products + aggregate + b)
+  {
+    StreamScope side(c, 1);
+    RGCN_TRY(gemm_f32(c, "gemm_self_fwd", self));
+  }
+  RGCN_TRY(pdiag_rows_forward(c, l, c->H[l - 1], c->zsave[l], c->pdiag_a[l], c->pdiag_agg));
+  RGCN_TRY(units_product_fwd(c, l));
+  RGCN_TRY(stream_join(c, 1));
+  return pdiag_epilogue(c, l, c->aggbuf, c->pdiag_agg, fwd_epilogue_args(c, l, dst));
+}
+
+static rgcn_status fwd_basis(rgcn_ctx* c, int l, const GemmCall& self, float* dst) {
+  // aggregate first, per (row, direction) unit: Zc[(v,dir),b,:] = sum n C[rel,b] H[src];
+  // pre[v] = dropout(H.W_self)[v] + sum_dir Zc[(v,dir)] . W'_dir  -- two groups of one batched GEMM over the units
+  const int d = c->d, V = c->V;
+  // the self-loop GEMM needs the layer input only: it runs on side stream 1 beside the aggregation (HBM-bound) and
+  // then beside the basis GEMM
+  {
+    StreamScope side(c, 1);
+    RGCN_TRY(gemm_f32(c, "gemm_self_fwd", self));
+  }
+  RGCN_TRY(wait_gather(c));
+  RGCN_TRY(basis_aggregate_forward(c, l, c->H[l - 1], c->zsave[l]));
+  RGCN_TRY(units_product_fwd(c, l));
+  RGCN_TRY(stream_join(c, 1));
+  CombineArgs a = fwd_epilogue_args(c, l, dst);
+  a.add_units = c->aggbuf; a.unit_ptr = c->g.unit_ptr;
+  return combine(c, "combine_fwd", a, 4.0 * d * (2.0 * V + 2.0 * V * basis_unit_share(c)) + 8.0 * V);
+}
+
 rgcn_status fwd_layer_partial(rgcn_ctx* c, int l) {
   RGCN_NO_EMBEDDING(c, "rgcn_forward_layer_partial");
   if (l < 1 || l > c->L) RGCN_FAIL(c, RGCN_ERR_INVALID, "layer out of range");
+  const LayerForm form = layer_form(c, l);
   // featureless first layer (world == 1): one destination-major kernel, messages looked up in the [V,B,d] tables, the
   // combine -- W_self row, dropout, relu -- as its epilogue; no GEMM
-  if (c->onehot && l == 1) return onehot_forward(c, c->H[1]);
-  const float* Hin = c->H[l - 1];
-  const int d = c->d, V = c->V;
-  const int lo = c->world > 1 ? c->row_lo : 0, hi = c->world > 1 ? c->row_hi : V;
+  if (form == FORM_ONEHOT) return onehot_forward(c, c->H[1]);
   // highway context: the layer's result is N_l; fwd_layer_finish forms H_l from it
   float* dst = c->world > 1 ? c->exch : c->highway ? c->hw_N[l] : c->H[l];
-  const double Mmsg = 2.0 * c->g.E / c->world;
   RGCN_TRY(refresh_weight_fragments(c));
   bool form_h0 = false;
   if (l == 1 && c->h0_in_gemm) {
@@ -169,121 +304,13 @@ rgcn_status fwd_layer_partial(rgcn_ctx* c, int l) {
     if (!form_h0) RGCN_TRY(input_forward(c));
   }
   const GemmCall self = self_fwd_call(c, l, form_h0);      // S = H . W_self  (rows of this rank's shard)
-  if (c->kind == RGCN_KIND_BLOCK && rows_layer(c)) {
-    // S = H . W_self, then ONE kernel: H' = relu(dropout(S) + sum over the row's messages of n W_r H[src]) straight from
-    // the incidence CSR (no message buffer)
-    // (sharded run: the self-loop GEMM covers this rank's row shard, the kernel walks the rank's own messages and writes
-    // the PARTIAL pre-activations -- the self-loop term inside the shard only, no relu -- for the reduce-scatter that
-    // follows)
-    RGCN_TRY(gemm_f32(c, "gemm_self_fwd", self));
-    RGCN_TRY(wait_gather(c));
-    CombineArgs a;
-    a.add = nullptr; a.msg = nullptr; a.row_ptr = nullptr; a.long_rows = nullptr; a.nlong = nullptr;
-    a.out = dst; a.out2 = nullptr; a.base = c->self_buf; a.gate = nullptr; a.V = V; a.d = d;
-    a.relu = (c->world == 1 && l < c->L) ? 1 : 0;
-    a.row_lo = lo; a.row_hi = hi;
-    a.drop = make_drop(c, l, true);
-    a.drop2 = make_drop(c, l, false);
-    RGCN_TRY(block_rows(c, "block_rows_fwd", l, false, c->H[l - 1], a));
-  } else if (c->kind == RGCN_KIND_BLOCK) {
-    // Two-kernel form.  The relational messages (HBM-bound) run beside the self-loop GEMM.  A stream that blocks on
-    // another stream's event resumes ~10 us after the event fires, so the chain that continues (the combine) stays on
-    // the stream of the kernel that finishes LAST: the messages on the main stream, the (shorter) GEMM forked.
-    {
-      StreamScope side(c, 0);
-      RGCN_TRY(gemm_f32(c, "gemm_self_fwd", self));
-    }
-    RGCN_TRY(wait_gather(c));
-    RGCN_TRY(block_msg_forward(c, l, Hin, c->msgbuf));
-    RGCN_TRY(stream_join(c, 0));
-    CombineArgs a;
-    a.add = nullptr;
-    a.out = dst; a.out2 = nullptr; a.base = c->self_buf; a.msg = c->g.E > 0 ? c->msgbuf : nullptr;
-    a.row_ptr = c->g.row_ptr; a.long_rows = c->g.long_rows; a.nlong = c->g.nlong; a.gate = nullptr; a.V = V; a.d = d;
-    a.relu = (c->world == 1 && l < c->L) ? 1 : 0;
-    a.row_lo = lo; a.row_hi = hi;
-    a.drop = make_drop(c, l, true);
-    a.drop2 = make_drop(c, l, false);
-    RGCN_TRY(combine(c, "combine_fwd", a, 4.0 * d * (2.0 * V + Mmsg) + 4.0 * V));
-  } else if (c->kind == RGCN_KIND_BASIS_TDIAG) {
-    // transform first (basis_tdiag.hip): P_dir = H . W_dir.reshape(d, B.d), two groups of one batched GEMM over the same
-    // A operand, kept per layer for dC; the self-loop product beside it on side stream 1; then ONE destination-major
-    // kernel: H' = relu(dropout(S) + sum over the row's messages of n sum_b G[rel,b,:] P_dir[src,b,:] + b)
-    const int Bd = c->B * d;
-    RGCN_TRY(tdiag_refresh_gates(c, l));
-    {
-      StreamScope side(c, 1);
-      RGCN_TRY(gemm_f32(c, "gemm_self_fwd", self));
-    }
-    const GemmBatch gb = tdiag_batch(0, (size_t)d * Bd, (size_t)V * Bd);
-    RGCN_TRY(gemm_f32(c, "gemm_tdiag_fwd", true, false, V, Bd, d, Hin, d, c->layers[l].wrel, Bd, c->tdiag_P[l], Bd, 1, &gb));
-    RGCN_TRY(stream_join(c, 1));
-    CombineArgs a;
-    a.add = nullptr; a.msg = nullptr; a.row_ptr = nullptr; a.long_rows = nullptr; a.nlong = nullptr;
-    a.out = dst; a.out2 = nullptr; a.base = c->self_buf; a.gate = nullptr; a.V = V; a.d = d;
-    a.relu = l < c->L ? 1 : 0;
-    a.row_lo = lo; a.row_hi = hi;
-    a.drop = make_drop(c, l, true);
-    a.drop2 = make_drop(c, l, false);
-    RGCN_TRY(tdiag_rows_forward(c, l, c->tdiag_P[l], a));
-  } else if (c->kind == RGCN_KIND_BASIS_PDIAG) {
-    // basis_pdiag.hip: ONE destination-major walk forms the mixing table a_l, the diagonal aggregate and the rows' own unit
-    // rows Zc[(v,dir),b,:] = a_dir[v,b] H[v,:]; Zc . W' is the basis kind's batched product over the units (LayerBufs::wrel
-    // holds the two groups swapped: forward units x W_backward); the self-loop product beside both on side stream 1; then
-    // H' = relu(dropout(S) + the two unit products + aggregate + b)
-    const int Bd = c->B * d;
-    {
-      StreamScope side(c, 1);
-      RGCN_TRY(gemm_f32(c, "gemm_self_fwd", self));
-    }
-    RGCN_TRY(pdiag_rows_forward(c, l, Hin, c->zsave[l], c->pdiag_a[l], c->pdiag_agg));
-    GemmBatch gb = basis_batch(c, (size_t)V * Bd, (size_t)Bd * d, (size_t)V * d, false);
-    if (c->gemm_mode != 0) gb.bfrag = c->layers[l].wrel_nn;
-    gb.strideBfrag = gemm_bfrag_words(Bd, d);
-    gb.wide = 1;
-    RGCN_TRY(gemm_f32(c, "gemm_basis_fwd", true, false, V, d, Bd, c->zsave[l], Bd, c->layers[l].wrel, d,
-                      c->aggbuf, d, 1, &gb, basis_unit_share(c)));
-    RGCN_TRY(stream_join(c, 1));
-    CombineArgs a;
-    a.add = nullptr; a.msg = nullptr; a.row_ptr = nullptr; a.long_rows = nullptr; a.nlong = nullptr;
-    a.out = dst; a.out2 = nullptr; a.base = c->self_buf; a.gate = nullptr; a.V = V; a.d = d;
-    a.relu = l < c->L ? 1 : 0;
-    a.row_lo = lo; a.row_hi = hi;
-    a.drop = make_drop(c, l, true);
-    a.drop2 = make_drop(c, l, false);
-    RGCN_TRY(pdiag_epilogue(c, l, c->aggbuf, c->pdiag_agg, a));
-  } else {
-    // aggregate first, per (row, direction) unit: Zc[(v,dir),b,:] = sum n C[rel,b] H[src];
-    // pre[v] = dropout(H.W_self)[v] + sum_dir Zc[(v,dir)] . W'_dir  -- two groups of one batched GEMM over the units
-    const int Bd = c->B * d;
-    // the self-loop GEMM needs the layer input only: it runs on side stream 1 beside the aggregation (HBM-bound) and
-    // then beside the basis GEMM
-    {
-      StreamScope side(c, 1);
-      RGCN_TRY(gemm_f32(c, "gemm_self_fwd", self));
-    }
-    RGCN_TRY(wait_gather(c));
-    RGCN_TRY(basis_aggregate_forward(c, l, Hin, c->zsave[l]));
-    GemmBatch gb = basis_batch(c, (size_t)V * Bd, (size_t)Bd * d, (size_t)V * d, false);
-    RGCN_TRY(refresh_weight_fragments(c));
-    if (c->gemm_mode != 0) gb.bfrag = c->layers[l].wrel_nn;
-    gb.strideBfrag = gemm_bfrag_words(Bd, d);
-    gb.wide = 1;
-    RGCN_TRY(gemm_f32(c, "gemm_basis_fwd", true, false, V, d, Bd, c->zsave[l], Bd, c->layers[l].wrel, d,
-                      c->aggbuf, d, 1, &gb, basis_unit_share(c)));
-    RGCN_TRY(stream_join(c, 1));
-    CombineArgs a;
-    a.add = nullptr;
-    a.add_units = c->aggbuf; a.unit_ptr = c->g.unit_ptr;
-    a.out = dst; a.out2 = nullptr; a.base = c->self_buf; a.msg = nullptr; a.row_ptr = nullptr;
-    a.long_rows = nullptr; a.nlong = nullptr; a.gate = nullptr; a.V = V; a.d = d;
-    a.relu = (c->world == 1 && l < c->L) ? 1 : 0;
-    a.row_lo = lo; a.row_hi = hi;
-    a.drop = make_drop(c, l, true);
-    a.drop2 = make_drop(c, l, false);
-    RGCN_TRY(combine(c, "combine_fwd", a, 4.0 * d * (2.0 * V + 2.0 * V * basis_unit_share(c)) + 8.0 * V));
+  switch (form) {
+    case FORM_BLOCK_ROWS: return fwd_block_rows(c, l, self, dst);
+    case FORM_BLOCK_TWO_KERNEL: return fwd_block_two_kernel(c, l, self, dst);
+    case FORM_TDIAG: return fwd_tdiag(c, l, self, dst);
+    case FORM_PDIAG: return fwd_pdiag(c, l, self, dst);
+    default: return fwd_basis(c, l, self, dst);
   }
-  return RGCN_OK;
 }
 
 rgcn_status fwd_layer_finish(rgcn_ctx* c, int l) {
@@ -307,7 +334,7 @@ rgcn_status fwd_layer_finish(rgcn_ctx* c, int l) {
 
 // ---------------------------------------------------------------- backward
 // The schedule whose end-of-pass joins may be deferred (rgcn_ctx::defer_end_joins): the single-pass block layer at
-// minibatch scale on one GPU with the side streams on, outside a capture, two layers or more (bwd_layer_partial's first
+// minibatch scale on one GPU with the side streams on, outside a capture, two layers or more (bwd_block_rows' first
 // branch).  In that schedule dW_self always runs on side stream 1 and the relation-weight kernels on side stream 0, so a
 // pass that starts while the previous one's side kernels are unjoined queues its own behind them IN STREAM ORDER: the
 // slabs and the gradients they share need no event.
@@ -345,62 +372,260 @@ rgcn_status bwd_begin(rgcn_ctx* c, const float* dcodes_dev, const float* ds_read
   return RGCN_OK;
 }
 
+// What the forms of a backward layer share (bwd_layer_partial fills it in): the layer and its input, this rank's row shard,
+// the split rule of the weight gradients, and the epilogue
+// (self-loop gradient + relational gradient) -> relu' -> next D / dS.
+struct BwdLayer {
+  int l;
+  const float* Hin;
+  LayerBufs* lb;
+  int lo, rows;
+  bool narrow_dw;      // (see auto_split_k)
+  CombineArgs a;
+};
+// the dense pieces every form but the one-hot first layer is made of; whoever launches self_dh has refreshed the fragment tables
+static rgcn_status self_dw(rgcn_ctx* c, const BwdLayer& s) {      // dW_self = H_in^T . dS   (split-K)
+  const int d = c->d;
+  return gemm_f32(c, "gemm_self_dw", false, false, d, d, s.rows, s.Hin + (size_t)s.lo * d, d, c->bwd_dS + (size_t)s.lo * d, d,
+                  s.lb->gwself, d, auto_split_k(d, d, s.rows, s.narrow_dw));
+}
+static rgcn_status self_dh(rgcn_ctx* c, const BwdLayer& s) {      // G = dS . W_self^T
+  const int d = c->d;
+  const GemmBatch sbt = self_loop_batch(c, s.l, true);
+  return gemm_f32(c, "gemm_self_dh", true, true, s.rows, d, d, c->bwd_dS + (size_t)s.lo * d, d, s.lb->wself, d,
+                  c->self_buf + (size_t)s.lo * d, d, 1, &sbt);
+}
+
+static rgcn_status bwd_onehot(rgcn_ctx* c) {
+  // Featureless first layer: D = dL/dpre1 (the layer above applied relu'(H_1); L = 1: the codes' gradient), dS = D *
+  // dropout_1.  Nothing lies below, so there is no dH -- no self-loop GEMMs, no relu' of an H_0, no column sums:
+  //   dW_self = dS (a copy), the tables' gradient source-major, the coefficients' per relation chunk.
+  // The coefficient kernel reads the tables and D, the table kernel writes the tables' gradient: independent, the former
+  // on side stream 0 beside the latter (which is bound by its 2 V B d writes).
+  {
+    StreamScope side(c, 0);
+    RGCN_TRY(onehot_dcoef(c, c->bwd_D));
+  }
+  RGCN_TRY(relu_copy(c, c->bwd_dS, c->layers[1].gwself, (int64_t)c->V * c->d, 0));
+  RGCN_TRY(onehot_backward_tables(c, c->bwd_D));
+  return stream_join(c, 0);
+}
+
+// *defer_joins: the layer leaves its side kernels unjoined (bwd_layer_partial then skips its own join of side stream 1)
+static rgcn_status bwd_block_rows(rgcn_ctx* c, const BwdLayer& s, bool* defer_joins) {
+  // Row gradients: the single-pass kernel behind G = dS . W_self^T.  Relation-weight gradients (dW_r = sum n g (x) x,
+  // relation-major, two row gathers per message): k_block_msg_bwd<dW only> + its slab reduce.  ONE schedule per
+  // situation, each the measured best of round 4's A/Bs (profiles/r04_rowmajor_spmm_ab.md, r04_block_forms_ab.txt):
+  //   minibatch scale, one GPU, side streams on:  dW_self forked BEFORE dH is launched (MFMA beside MFMA: the second
+  //       GEMM fills the slots the first leaves idle, 456 workgroups on 512, and its tail), the relation-weight kernels
+  //       forked BEHIND dH, beside the row-gradient kernel (two gather kernels share the chip better than either does
+  //       with a GEMM), joined at the end of the layer: 0.553-0.556 ms per step against 0.597-0.599 as a chain (round 5,
+  //       same box: dW_self forked BEHIND dH instead, beside the row-gradient kernel: 0.567-0.578 against 0.541-0.547);
+  //   the same inside a capture (a captured step is a chain, rgcn_capture_begin) or with the side streams off: the
+  //       chain, with the one fork a replayed graph gains from -- the slab reduce + dW_self beside dH;
+  //   full-graph scale or a sharded run: the relation-weight kernels on side stream 0 from the start of the layer
+  //       (at 272,115 edges they are five GEMMs long; a sharded run's all-gather rides on side stream 1), joined
+  //       before the next layer overwrites D.
+  const bool minibatch = c->world == 1 && c->g.E <= 65536;
+  if (minibatch && c->use_aux) {
+    {
+      StreamScope side(c, 1);
+      RGCN_TRY(self_dw(c, s));
+    }
+    RGCN_TRY(self_dh(c, s));
+    {
+      StreamScope side(c, 0);
+      RGCN_TRY(block_msg_backward(c, s.l, s.Hin, c->bwd_D, nullptr));
+      RGCN_TRY(block_dw_reduce(c, s.l));
+    }
+    RGCN_TRY(block_rows(c, "block_rows_bwd", s.l, true, c->bwd_D, s.a));
+    // Layer 2's side kernels read H_1, D_2 and dS_2 and write their own slabs and gradients.  Layer 1, next, overwrites
+    // none of those (its rows go to g_emb) and queues its side kernels behind them in stream order: its joins cover
+    // both layers, and the main stream saves two waits between the layers.
+    *defer_joins = s.l == 2;
+    // Layer 1 of a step that may end unjoined (rgcn_step_device): nothing on the main stream behind this layer touches
+    // what the side kernels read or write, so the main stream does not wait for them either.  One event marks their end
+    // (record_side_done); the next forward pass, the prefetch stream and whoever wants the gradients wait for it --
+    // DESIGN.md section 5.1 lists who.
+    if (s.l == 1 && deferred_schedule(c)) {
+      RGCN_TRY(record_side_done(c));
+      *defer_joins = true;
+    }
+    return *defer_joins ? RGCN_OK : stream_join_both(c);
+  } else if (minibatch) {
+    RGCN_TRY(block_msg_backward(c, s.l, s.Hin, c->bwd_D, nullptr));
+    {
+      StreamScope side(c, 1, /*in_capture=*/true);
+      RGCN_TRY(block_dw_reduce(c, s.l));
+      RGCN_TRY(self_dw(c, s));
+    }
+    RGCN_TRY(self_dh(c, s));
+    return block_rows(c, "block_rows_bwd", s.l, true, c->bwd_D, s.a);
+  } else {
+    {
+      StreamScope side(c, 0);
+      RGCN_TRY(wait_gather(c));          // D_l of every row (sharded run: gathered beside the self-loop GEMMs)
+      RGCN_TRY(block_msg_backward(c, s.l, s.Hin, c->bwd_D, nullptr));
+      RGCN_TRY(block_dw_reduce(c, s.l));
+      c->dw_pending = side.active;
+    }
+    {
+      StreamScope side(c, 1);
+      RGCN_TRY(self_dw(c, s));
+    }
+    RGCN_TRY(self_dh(c, s));
+    RGCN_TRY(wait_gather(c));
+    return block_rows(c, "block_rows_bwd", s.l, true, c->bwd_D, s.a);
+  }
+}
+
+static rgcn_status bwd_block_two_kernel(rgcn_ctx* c, const BwdLayer& s) {
+  const int l = s.l, d = c->d, V = c->V;
+  const double Mmsg = 2.0 * c->g.E / c->world;
+  {   // two-kernel form: the relational gradient kernels (HBM-bound) on a side stream beside the self-loop GEMMs
+    StreamScope side(c, 0);
+    RGCN_TRY(wait_gather(c));          // D_l of every row (sharded run: gathered beside the self-loop GEMMs)
+    RGCN_TRY(block_msg_backward(c, l, s.Hin, c->bwd_D, c->msgbuf));
+    // the combine below needs only the message rows: mark the join point here, then let the
+    // per-relation dW reduction trail behind on the side stream
+    if (side.active) RGCN_HIP(c, hipEventRecord(c->ev_join[0], c->aux[0]));
+    RGCN_TRY(block_dw_reduce(c, l));
+  }
+  RGCN_TRY(self_dh(c, s));
+  {   // dW_self on side stream 1, queued behind the dH GEMM
+    StreamScope side(c, 1);
+    RGCN_TRY(self_dw(c, s));
+  }
+  if (c->use_aux) RGCN_HIP(c, hipStreamWaitEvent(c->main_stream, c->ev_join[0], 0));
+  CombineArgs a = s.a;
+  a.msg = c->g.E > 0 ? c->msgbuf : nullptr;
+  a.row_ptr = c->g.row_ptr; a.long_rows = c->g.long_rows; a.nlong = c->g.nlong;
+  return combine(c, "combine_bwd", a, 4.0 * d * ((a.out2 ? 4.0 : 3.0) * V + Mmsg) + 4.0 * V);
+}
+
+static rgcn_status bwd_tdiag(rgcn_ctx* c, const BwdLayer& s) {
+  const int l = s.l, d = c->d, V = c->V, Bd = c->B * d;
+  // db = the column sums of D (this layer's bias is added, gcn_basis_times_diag.py:86); dP source-major from D and G
+  RGCN_TRY(tdiag_refresh_gates(c, l));
+  RGCN_TRY(column_sum(c, c->bwd_D, s.lb->gbias, V, d));
+  RGCN_TRY(tdiag_dp(c, l, c->bwd_D, c->tdiag_dP));
+  {   // dC needs P_l and D only: per relation chunk on side stream 0, beside the dense products
+    StreamScope side(c, 0);
+    RGCN_TRY(tdiag_dcoef(c, l, c->tdiag_P[l], c->bwd_D));
+  }
+  {   // the two weight gradients on side stream 1 (they share the split-K slabs: one stream, in order)
+    StreamScope side(c, 1);
+    RGCN_TRY(self_dw(c, s));
+    // dW_dir = H^T . dP_dir   ([d, V] x [V, B.d], split over the rows; two groups, the same A operand)
+    const GemmBatch gk = tdiag_batch(0, (size_t)V * Bd, (size_t)d * Bd);
+    int split = auto_split_k(d, 2 * Bd, V, true);
+    if (split > 16) split = 16;      // (the slabs are sized for 16: rgcn_create)
+    RGCN_TRY(gemm_f32(c, "gemm_tdiag_dw", false, false, d, Bd, V, s.Hin, d, c->tdiag_dP, Bd, s.lb->grel, Bd, split, &gk));
+  }
+  RGCN_TRY(self_dh(c, s));
+  // dH's relational part: dP_dir . W_dir^T   ([V, B.d] x [B.d, d], two groups), added by the epilogue kernel
+  const GemmBatch gm = tdiag_batch((size_t)V * Bd, (size_t)d * Bd, (size_t)V * d);
+  RGCN_TRY(gemm_f32(c, "gemm_tdiag_dh", true, true, V, d, Bd, c->tdiag_dP, Bd, s.lb->wrel, Bd, c->tdiag_dh, d, 1, &gm));
+  RGCN_TRY(tdiag_dh_join(c, c->tdiag_dh, s.a));
+  return stream_join(c, 0);      // (the next layer rewrites D's buffer, dP and the chunk slabs)
+}
+
+static rgcn_status bwd_pdiag(rgcn_ctx* c, const BwdLayer& s) {
+  const int l = s.l;
+  // db = the column sums of G = dL/dpre (this layer's bias is added); dD needs H_{l-1} and G only: per relation chunk on
+  // side stream 0, beside the dense products
+  RGCN_TRY(column_sum(c, c->bwd_D, s.lb->gbias, c->V, c->d));
+  {
+    StreamScope side(c, 0);
+    RGCN_TRY(pdiag_ddiag(c, l, s.Hin, c->bwd_D));
+  }
+  // the dense products are the basis kind's, over the compacted units: G[units], dW'_dir = Zc_dir^T . G[units] beside
+  // dW_self on side stream 1, dZc_dir = G[units] . W'_dir^T on the main stream behind dS . W_self^T
+  RGCN_TRY(basis_gather_units(c, c->bwd_D, c->aggbuf));
+  {
+    StreamScope side(c, 1);
+    RGCN_TRY(self_dw(c, s));
+    RGCN_TRY(units_product_dw(c, l));
+  }
+  RGCN_TRY(self_dh(c, s));
+  RGCN_TRY(units_product_dz(c, l));
+  // row-local: da and the a * dZc part of dH; dC from da per relation chunk; then the source-major diagonal gather joins
+  // the three parts of dH, applies relu' and writes the dropout copy
+  RGCN_TRY(pdiag_row_backward(c, s.Hin, c->msgbuf2, c->pdiag_a[l], c->pdiag_da, c->pdiag_dh));
+  RGCN_TRY(pdiag_dcoef(c, l, c->pdiag_da));
+  RGCN_TRY(pdiag_dh_join(c, l, c->bwd_D, c->pdiag_dh, s.a));
+  return stream_join(c, 0);      // (the next layer rewrites G's buffer and the dD slabs)
+}
+
+static rgcn_status bwd_basis(rgcn_ctx* c, const BwdLayer& s) {
+  const int l = s.l;
+  // The upstream rows of the units, compacted like Zc (the row operand of dZ, the depth operand of dW')
+  RGCN_TRY(wait_gather(c));            // D_l of every row
+  RGCN_TRY(basis_gather_units(c, c->bwd_D, c->aggbuf));
+  // The four dense contractions of the layer depend on D_l / dS_l only.  Two of them -- the weight gradients dW_self =
+  // H^T.dS and dW'_dir = Zc_dir^T.D[units], needed at the end of the pass -- go to side stream 1, the two whose
+  // products the gather kernels below consume (dH's self-loop part, dZ) stay on the main stream: the pairs fill each
+  // other's idle CU slots and tails.
+  {
+    StreamScope side(c, 1);
+    RGCN_TRY(self_dw(c, s));
+    RGCN_TRY(units_product_dw(c, l));
+  }
+  RGCN_TRY(self_dh(c, s));
+  RGCN_TRY(units_product_dz(c, l));
+  RGCN_TRY(basis_dcoef(c, l, s.Hin, c->msgbuf2));
+  return basis_backward_gather(c, l, c->msgbuf2, s.a, true);
+}
+
+// Highway context, ahead of the layer's own form: the highway pass of layer l and its weight gradient.
+static rgcn_status bwd_highway_open(rgcn_ctx* c, const BwdLayer& s) {
+  const int l = s.l, d = c->d, V = c->V;
+  // G_l (bwd_D; l < L: in dbuf[l & 1], turned into D_l in place) -> D_l, dS_l, dZ_l, the carry, db_hw's partials
+  const DropSpec dl = make_drop(c, l, true);
+  float* dS = dl.mode != DROP_NONE ? c->dsbuf[l & 1] : nullptr;
+  int nparts = 0;
+  RGCN_TRY(highway_backward(c, c->bwd_D, c->hw_T[l], c->hw_N[l], s.Hin, c->dbuf[l & 1], dS, c->hw_dz[l & 1], c->hw_carry,
+                            l < c->L ? 1 : 0, dl, &nparts));
+  RGCN_TRY(column_sum_finish(c, s.lb->gbhw, nparts, d));
+  c->bwd_D = c->dbuf[l & 1];
+  c->bwd_dS = dS ? dS : c->dbuf[l & 1];
+  {   // dW_hw = H_{l-1}^T . dZ (split-K): side stream 1, AHEAD of the layer's dW_self there -- the two share the slabs
+    StreamScope side(c, 1);
+    RGCN_TRY(gemm_f32(c, "gemm_highway_dw", false, false, d, d, V, s.Hin, d, c->hw_dz[l & 1], d, s.lb->gwhw, d,
+                      auto_split_k(d, d, V, s.narrow_dw)));
+  }
+  return RGCN_OK;
+}
+
 rgcn_status bwd_layer_partial(rgcn_ctx* c, int l) {
   RGCN_NO_EMBEDDING(c, "rgcn_backward_layer_partial");
   if (l != c->bwd_layer || l < 1) RGCN_FAIL(c, RGCN_ERR_STATE, "backward layers must run L..1 in order");
-  if (c->onehot && l == 1) {
-    // Featureless first layer: D = dL/dpre1 (the layer above applied relu'(H_1); L = 1: the codes' gradient), dS = D *
-    // dropout_1.  Nothing lies below, so there is no dH -- no self-loop GEMMs, no relu' of an H_0, no column sums:
-    //   dW_self = dS (a copy), the tables' gradient source-major, the coefficients' per relation chunk.
-    // The coefficient kernel reads the tables and D, the table kernel writes the tables' gradient: independent, the former
-    // on side stream 0 beside the latter (which is bound by its 2 V B d writes).
-    {
-      StreamScope side(c, 0);
-      RGCN_TRY(onehot_dcoef(c, c->bwd_D));
-    }
-    RGCN_TRY(relu_copy(c, c->bwd_dS, c->layers[1].gwself, (int64_t)c->V * c->d, 0));
-    RGCN_TRY(onehot_backward_tables(c, c->bwd_D));
-    return stream_join(c, 0);
-  }
-  const float* Hin = c->H[l - 1];
+  const LayerForm form = layer_form(c, l);
+  if (form == FORM_ONEHOT) return bwd_onehot(c);
   const int d = c->d, V = c->V;
-  const int lo = c->world > 1 ? c->row_lo : 0, hi = c->world > 1 ? c->row_hi : V;
-  const int rows = hi - lo;
-  LayerBufs& lb = c->layers[l];
-  const double Mmsg = 2.0 * c->g.E / c->world;
-  const bool narrow_dw = c->kind == RGCN_KIND_BASIS || c->kind == RGCN_KIND_BASIS_PDIAG || rows >= 32768;       // (see auto_split_k)
+  const RowShard rs = row_shard(c);
+  BwdLayer s;
+  s.l = l; s.Hin = c->H[l - 1]; s.lb = &c->layers[l]; s.lo = rs.lo; s.rows = rs.hi - rs.lo;
+  s.narrow_dw = c->kind == RGCN_KIND_BASIS || c->kind == RGCN_KIND_BASIS_PDIAG || s.rows >= 32768;       // (see auto_split_k)
 
   // epilogue shared by both kinds: (self-loop gradient + relational gradient) -> relu' -> next D / dS
-  CombineArgs a;
+  CombineArgs& a = s.a;
   a.add = nullptr;
   a.base = c->self_buf; a.msg = nullptr; a.row_ptr = nullptr; a.long_rows = nullptr; a.nlong = nullptr;
-  a.V = V; a.d = d; a.relu = 0; a.row_lo = lo; a.row_hi = hi;
+  a.V = c->V; a.d = c->d; a.relu = 0; a.row_lo = rs.lo; a.row_hi = rs.hi;
   a.drop = make_drop(c, l, false);
   if (c->highway) {
     // The epilogue leaves the RAW dH_{l-1}: relu' belongs to N_{l-1}, not to H_{l-1}, and applies to the sum with the
     // highway terms -- the gate, the dropout copy and (l = 1) relu'(H_0) with db_emb's column sums are highway.hip's.
     a.out = (l - 1 == 0) ? c->g_emb : c->dbuf[(l - 1) & 1];
     a.out2 = nullptr; a.gate = nullptr; a.drop2 = make_drop(c, l - 1, false);
-    // G_l (bwd_D; l < L: in dbuf[l & 1], turned into D_l in place) -> D_l, dS_l, dZ_l, the carry, db_hw's partials
-    const DropSpec dl = make_drop(c, l, true);
-    float* dS = dl.mode != DROP_NONE ? c->dsbuf[l & 1] : nullptr;
-    int nparts = 0;
-    RGCN_TRY(highway_backward(c, c->bwd_D, c->hw_T[l], c->hw_N[l], Hin, c->dbuf[l & 1], dS, c->hw_dz[l & 1], c->hw_carry,
-                              l < c->L ? 1 : 0, dl, &nparts));
-    RGCN_TRY(column_sum_finish(c, lb.gbhw, nparts, d));
-    c->bwd_D = c->dbuf[l & 1];
-    c->bwd_dS = dS ? dS : c->dbuf[l & 1];
-    {   // dW_hw = H_{l-1}^T . dZ (split-K): side stream 1, AHEAD of the layer's dW_self there -- the two share the slabs
-      StreamScope side(c, 1);
-      RGCN_TRY(gemm_f32(c, "gemm_highway_dw", false, false, d, d, V, Hin, d, c->hw_dz[l & 1], d, lb.gwhw, d,
-                        auto_split_k(d, d, V, narrow_dw)));
-    }
+    RGCN_TRY(bwd_highway_open(c, s));
   } else if (c->world == 1) {
     a.out = (l - 1 == 0) ? c->g_emb : c->dbuf[(l - 1) & 1];
     a.colsum = (l - 1 == 0) ? 1 : 0;       // db_emb = the column sums of dL/dH0 * relu'(H0): partials from the kernel that writes it
     a.drop2 = make_drop(c, l - 1, l - 1 >= 1);
     a.out2 = a.drop2.mode != DROP_NONE ? c->dsbuf[(l - 1) & 1] : nullptr;
-    a.gate = Hin;
+    a.gate = s.Hin;
   } else {
     a.out = c->exch; a.out2 = nullptr; a.gate = nullptr; a.drop2 = make_drop(c, l, false);
   }
@@ -409,194 +634,21 @@ rgcn_status bwd_layer_partial(rgcn_ctx* c, int l) {
     RGCN_TRY(stream_join(c, 0));
     c->dw_pending = false;
   }
-  // the three dense / relation-weight pieces every block schedule below is made of
-  auto self_dw = [&]() {      // dW_self = H_in^T . dS   (split-K)
-    return gemm_f32(c, "gemm_self_dw", false, false, d, d, rows, Hin + (size_t)lo * d, d, c->bwd_dS + (size_t)lo * d, d,
-                    lb.gwself, d, auto_split_k(d, d, rows, narrow_dw));
-  };
   RGCN_TRY(refresh_weight_fragments(c));
-  const GemmBatch sbt = self_loop_batch(c, l, true);
-  auto self_dh = [&]() {      // G = dS . W_self^T
-    return gemm_f32(c, "gemm_self_dh", true, true, rows, d, d, c->bwd_dS + (size_t)lo * d, d, lb.wself, d,
-                    c->self_buf + (size_t)lo * d, d, 1, &sbt);
-  };
   bool defer_joins = false;
-  if (c->kind == RGCN_KIND_BLOCK && rows_layer(c)) {
-    // Row gradients: the single-pass kernel behind G = dS . W_self^T.  Relation-weight gradients (dW_r = sum n g (x) x,
-    // relation-major, two row gathers per message): k_block_msg_bwd<dW only> + its slab reduce.  ONE schedule per
-    // situation, each the measured best of round 4's A/Bs (profiles/r04_rowmajor_spmm_ab.md, r04_block_forms_ab.txt):
-    //   minibatch scale, one GPU, side streams on:  dW_self forked BEFORE dH is launched (MFMA beside MFMA: the second
-    //       GEMM fills the slots the first leaves idle, 456 workgroups on 512, and its tail), the relation-weight kernels
-    //       forked BEHIND dH, beside the row-gradient kernel (two gather kernels share the chip better than either does
-    //       with a GEMM), joined at the end of the layer: 0.553-0.556 ms per step against 0.597-0.599 as a chain (round 5,
-    //       same box: dW_self forked BEHIND dH instead, beside the row-gradient kernel: 0.567-0.578 against 0.541-0.547);
-    //   the same inside a capture (a captured step is a chain, rgcn_capture_begin) or with the side streams off: the
-    //       chain, with the one fork a replayed graph gains from -- the slab reduce + dW_self beside dH;
-    //   full-graph scale or a sharded run: the relation-weight kernels on side stream 0 from the start of the layer
-    //       (at 272,115 edges they are five GEMMs long; a sharded run's all-gather rides on side stream 1), joined
-    //       before the next layer overwrites D.
-    const bool minibatch = c->world == 1 && c->g.E <= 65536;
-    if (minibatch && c->use_aux) {
-      {
-        StreamScope side(c, 1);
-        RGCN_TRY(self_dw());
-      }
-      RGCN_TRY(self_dh());
-      {
-        StreamScope side(c, 0);
-        RGCN_TRY(block_msg_backward(c, l, Hin, c->bwd_D, nullptr));
-        RGCN_TRY(block_dw_reduce(c, l));
-      }
-      RGCN_TRY(block_rows(c, "block_rows_bwd", l, true, c->bwd_D, a));
-      // Layer 2's side kernels read H_1, D_2 and dS_2 and write their own slabs and gradients.  Layer 1, next, overwrites
-      // none of those (its rows go to g_emb) and queues its side kernels behind them in stream order: its joins cover
-      // both layers, and the main stream saves two waits between the layers.
-      defer_joins = l == 2;
-      // Layer 1 of a step that may end unjoined (rgcn_step_device): nothing on the main stream behind this layer touches
-      // what the side kernels read or write, so the main stream does not wait for them either.  One event marks their end
-      // (record_side_done); the next forward pass, the prefetch stream and whoever wants the gradients wait for it --
-      // DESIGN.md section 5.1 lists who.
-      if (l == 1 && deferred_schedule(c)) {
-        RGCN_TRY(record_side_done(c));
-        defer_joins = true;
-      }
-      if (!defer_joins) RGCN_TRY(stream_join_both(c));
-    } else if (minibatch) {
-      RGCN_TRY(block_msg_backward(c, l, Hin, c->bwd_D, nullptr));
-      {
-        StreamScope side(c, 1, /*in_capture=*/true);
-        RGCN_TRY(block_dw_reduce(c, l));
-        RGCN_TRY(self_dw());
-      }
-      RGCN_TRY(self_dh());
-      RGCN_TRY(block_rows(c, "block_rows_bwd", l, true, c->bwd_D, a));
-    } else {
-      {
-        StreamScope side(c, 0);
-        RGCN_TRY(wait_gather(c));          // D_l of every row (sharded run: gathered beside the self-loop GEMMs)
-        RGCN_TRY(block_msg_backward(c, l, Hin, c->bwd_D, nullptr));
-        RGCN_TRY(block_dw_reduce(c, l));
-        c->dw_pending = side.active;
-      }
-      {
-        StreamScope side(c, 1);
-        RGCN_TRY(self_dw());
-      }
-      RGCN_TRY(self_dh());
-      RGCN_TRY(wait_gather(c));
-      RGCN_TRY(block_rows(c, "block_rows_bwd", l, true, c->bwd_D, a));
-    }
-  } else if (c->kind == RGCN_KIND_BLOCK) {
-    {   // two-kernel form: the relational gradient kernels (HBM-bound) on a side stream beside the self-loop GEMMs
-      StreamScope side(c, 0);
-      RGCN_TRY(wait_gather(c));          // D_l of every row (sharded run: gathered beside the self-loop GEMMs)
-      RGCN_TRY(block_msg_backward(c, l, Hin, c->bwd_D, c->msgbuf));
-      // the combine below needs only the message rows: mark the join point here, then let the
-      // per-relation dW reduction trail behind on the side stream
-      if (side.active) RGCN_HIP(c, hipEventRecord(c->ev_join[0], c->aux[0]));
-      RGCN_TRY(block_dw_reduce(c, l));
-    }
-    RGCN_TRY(self_dh());
-    {   // dW_self on side stream 1, queued behind the dH GEMM
-      StreamScope side(c, 1);
-      RGCN_TRY(self_dw());
-    }
-    if (c->use_aux) RGCN_HIP(c, hipStreamWaitEvent(c->main_stream, c->ev_join[0], 0));
-    a.msg = c->g.E > 0 ? c->msgbuf : nullptr;
-    a.row_ptr = c->g.row_ptr;
-    a.long_rows = c->g.long_rows;
-    a.nlong = c->g.nlong;
-    RGCN_TRY(combine(c, "combine_bwd", a, 4.0 * d * ((a.out2 ? 4.0 : 3.0) * V + Mmsg) + 4.0 * V));
-  } else if (c->kind == RGCN_KIND_BASIS_TDIAG) {
-    const int Bd = c->B * d;
-    // db = the column sums of D (this layer's bias is added, gcn_basis_times_diag.py:86); dP source-major from D and G
-    RGCN_TRY(tdiag_refresh_gates(c, l));
-    RGCN_TRY(column_sum(c, c->bwd_D, lb.gbias, V, d));
-    RGCN_TRY(tdiag_dp(c, l, c->bwd_D, c->tdiag_dP));
-    {   // dC needs P_l and D only: per relation chunk on side stream 0, beside the dense products
-      StreamScope side(c, 0);
-      RGCN_TRY(tdiag_dcoef(c, l, c->tdiag_P[l], c->bwd_D));
-    }
-    {   // the two weight gradients on side stream 1 (they share the split-K slabs: one stream, in order)
-      StreamScope side(c, 1);
-      RGCN_TRY(self_dw());
-      // dW_dir = H^T . dP_dir   ([d, V] x [V, B.d], split over the rows; two groups, the same A operand)
-      const GemmBatch gk = tdiag_batch(0, (size_t)V * Bd, (size_t)d * Bd);
-      int split = auto_split_k(d, 2 * Bd, V, true);
-      if (split > 16) split = 16;      // (the slabs are sized for 16: rgcn_create)
-      RGCN_TRY(gemm_f32(c, "gemm_tdiag_dw", false, false, d, Bd, V, Hin, d, c->tdiag_dP, Bd, lb.grel, Bd, split, &gk));
-    }
-    RGCN_TRY(self_dh());
-    // dH's relational part: dP_dir . W_dir^T   ([V, B.d] x [B.d, d], two groups), added by the epilogue kernel
-    const GemmBatch gm = tdiag_batch((size_t)V * Bd, (size_t)d * Bd, (size_t)V * d);
-    RGCN_TRY(gemm_f32(c, "gemm_tdiag_dh", true, true, V, d, Bd, c->tdiag_dP, Bd, lb.wrel, Bd, c->tdiag_dh, d, 1, &gm));
-    RGCN_TRY(tdiag_dh_join(c, c->tdiag_dh, a));
-    RGCN_TRY(stream_join(c, 0));      // (the next layer rewrites D's buffer, dP and the chunk slabs)
-  } else if (c->kind == RGCN_KIND_BASIS_PDIAG) {
-    const int Bd = c->B * d;
-    // db = the column sums of G = dL/dpre (this layer's bias is added); dD needs H_{l-1} and G only: per relation chunk on
-    // side stream 0, beside the dense products
-    RGCN_TRY(column_sum(c, c->bwd_D, lb.gbias, V, d));
-    {
-      StreamScope side(c, 0);
-      RGCN_TRY(pdiag_ddiag(c, l, Hin, c->bwd_D));
-    }
-    // the dense products are the basis kind's, over the compacted units: G[units], dW'_dir = Zc_dir^T . G[units] beside
-    // dW_self on side stream 1, dZc_dir = G[units] . W'_dir^T on the main stream behind dS . W_self^T
-    RGCN_TRY(basis_gather_units(c, c->bwd_D, c->aggbuf));
-    {
-      StreamScope side(c, 1);
-      RGCN_TRY(self_dw());
-      const GemmBatch gk = basis_batch(c, (size_t)V * Bd, (size_t)V * d, (size_t)Bd * d, true);
-      RGCN_TRY(gemm_f32(c, "gemm_basis_dw", false, false, Bd, d, V, c->zsave[l], Bd, c->aggbuf, d, lb.grel, d,
-                        auto_split_k(2 * Bd, d, V), &gk, basis_unit_share(c)));
-    }
-    RGCN_TRY(self_dh());
-    GemmBatch gm = basis_batch(c, (size_t)V * d, (size_t)Bd * d, (size_t)V * Bd, false);
-    if (c->gemm_mode != 0) gm.bfrag = lb.wrel_nt;
-    gm.strideBfrag = gemm_bfrag_words(d, Bd);
-    RGCN_TRY(gemm_f32(c, "gemm_basis_dz", true, true, V, Bd, d, c->aggbuf, d, lb.wrel, d, c->msgbuf2, Bd, 1, &gm,
-                      basis_unit_share(c)));
-    // row-local: da and the a * dZc part of dH; dC from da per relation chunk; then the source-major diagonal gather joins
-    // the three parts of dH, applies relu' and writes the dropout copy
-    RGCN_TRY(pdiag_row_backward(c, Hin, c->msgbuf2, c->pdiag_a[l], c->pdiag_da, c->pdiag_dh));
-    RGCN_TRY(pdiag_dcoef(c, l, c->pdiag_da));
-    RGCN_TRY(pdiag_dh_join(c, l, c->bwd_D, c->pdiag_dh, a));
-    RGCN_TRY(stream_join(c, 0));      // (the next layer rewrites G's buffer and the dD slabs)
-  } else {
-    const int Bd = c->B * d;
-    // The upstream rows of the units, compacted like Zc (the row operand of dZ, the depth operand of dW')
-    RGCN_TRY(wait_gather(c));            // D_l of every row
-    RGCN_TRY(basis_gather_units(c, c->bwd_D, c->aggbuf));
-    // The four dense contractions of the layer depend on D_l / dS_l only.  Two of them -- the weight gradients dW_self =
-    // H^T.dS and dW'_dir = Zc_dir^T.D[units], needed at the end of the pass -- go to side stream 1, the two whose
-    // products the gather kernels below consume (dH's self-loop part, dZ) stay on the main stream: the pairs fill each
-    // other's idle CU slots and tails.
-    {
-      StreamScope side(c, 1);
-      RGCN_TRY(self_dw());
-      // dW'_dir = Zc_dir^T . Dc_dir   ([B.d, units] x [units, d], split over the units; two groups)
-      const GemmBatch gk = basis_batch(c, (size_t)V * Bd, (size_t)V * d, (size_t)Bd * d, true);
-      RGCN_TRY(gemm_f32(c, "gemm_basis_dw", false, false, Bd, d, V, c->zsave[l], Bd, c->aggbuf, d, lb.grel, d,
-                        auto_split_k(2 * Bd, d, V), &gk, basis_unit_share(c)));
-    }
-    RGCN_TRY(self_dh());
-    // dZc_dir = Dc_dir . W'_dir^T   ([units, d] x [d, B.d], two groups)
-    GemmBatch gm = basis_batch(c, (size_t)V * d, (size_t)Bd * d, (size_t)V * Bd, false);
-    RGCN_TRY(refresh_weight_fragments(c));
-    if (c->gemm_mode != 0) gm.bfrag = lb.wrel_nt;
-    gm.strideBfrag = gemm_bfrag_words(d, Bd);
-    RGCN_TRY(gemm_f32(c, "gemm_basis_dz", true, true, V, Bd, d, c->aggbuf, d, lb.wrel, d, c->msgbuf2, Bd, 1, &gm,
-                      basis_unit_share(c)));
-    RGCN_TRY(basis_dcoef(c, l, Hin, c->msgbuf2));
-    RGCN_TRY(basis_backward_gather(c, l, c->msgbuf2, a, true));
+  switch (form) {
+    case FORM_BLOCK_ROWS: RGCN_TRY(bwd_block_rows(c, s, &defer_joins)); break;
+    case FORM_BLOCK_TWO_KERNEL: RGCN_TRY(bwd_block_two_kernel(c, s)); break;
+    case FORM_TDIAG: RGCN_TRY(bwd_tdiag(c, s)); break;
+    case FORM_PDIAG: RGCN_TRY(bwd_pdiag(c, s)); break;
+    default: RGCN_TRY(bwd_basis(c, s)); break;
   }
   if (c->highway) {
     // G_{l-1} = raw dH_{l-1} + dZ_l . W_hw^T + G_l (1 - T_l), in place over the raw rows; the product goes through the
     // self-loop buffer, free since the epilogue above read it
-    RGCN_TRY(gemm_f32(c, "gemm_highway_dh", true, true, V, d, d, c->hw_dz[l & 1], d, lb.whw, d, c->self_buf, d, 1));
+    RGCN_TRY(gemm_f32(c, "gemm_highway_dh", true, true, V, d, d, c->hw_dz[l & 1], d, s.lb->whw, d, c->self_buf, d, 1));
     int nparts = 0;
-    RGCN_TRY(highway_join(c, a.out, c->self_buf, c->hw_carry, l == 1 ? Hin : nullptr, &nparts));
+    RGCN_TRY(highway_join(c, a.out, c->self_buf, c->hw_carry, l == 1 ? s.Hin : nullptr, &nparts));
     if (l == 1) c->colsum_parts = nparts;      // db_emb: bwd_end adds them
   }
   // the dW_self GEMM must be done before the next layer overwrites its dS operand / the caller
@@ -605,23 +657,26 @@ rgcn_status bwd_layer_partial(rgcn_ctx* c, int l) {
   return RGCN_OK;
 }
 
+// The finish of a sharded layer: D_{l-1} = (the reduced dH in exch) * relu'(H_{l-1}), dS_{l-1} its dropout copy, over the rows
+// [row_lo, row_hi).  On one GPU the layer's own epilogue has written both; out / out2 say where.
+static CombineArgs bwd_finish_args(rgcn_ctx* c, int l, int row_lo, int row_hi) {
+  CombineArgs a;
+  a.add = nullptr; a.msg = nullptr; a.row_ptr = nullptr; a.long_rows = nullptr; a.nlong = nullptr;
+  a.drop = make_drop(c, l, false);
+  a.drop2 = make_drop(c, l - 1, l - 1 >= 1);
+  a.out = (l - 1 == 0) ? c->g_emb : c->dbuf[(l - 1) & 1];
+  a.out2 = a.drop2.mode != DROP_NONE ? c->dsbuf[(l - 1) & 1] : nullptr;
+  a.base = c->exch; a.gate = c->H[l - 1]; a.V = c->V; a.d = c->d; a.relu = 0; a.row_lo = row_lo; a.row_hi = row_hi;
+  return a;
+}
+
 rgcn_status bwd_layer_finish(rgcn_ctx* c, int l) {
   RGCN_NO_EMBEDDING(c, "rgcn_backward_layer_finish");
   if (l != c->bwd_layer || l < 1) RGCN_FAIL(c, RGCN_ERR_STATE, "backward layers must run L..1 in order");
-  float* out = (l - 1 == 0) ? c->g_emb : c->dbuf[(l - 1) & 1];
-  DropSpec d2 = make_drop(c, l - 1, l - 1 >= 1);
-  float* out2 = d2.mode != DROP_NONE ? c->dsbuf[(l - 1) & 1] : nullptr;
-  if (c->world > 1) {
-    CombineArgs a;
-    a.add = nullptr;
-    a.out = out; a.out2 = out2; a.base = c->exch; a.msg = nullptr; a.row_ptr = nullptr; a.long_rows = nullptr; a.nlong = nullptr;
-    a.gate = c->H[l - 1]; a.V = c->V; a.d = c->d; a.relu = 0; a.row_lo = 0; a.row_hi = c->V;
-    a.drop = make_drop(c, l, false);
-    a.drop2 = d2;
-    RGCN_TRY(combine(c, "combine_bwd_finish", a, 4.0 * c->d * (out2 ? 4.0 : 3.0) * c->V));
-  }
-  c->bwd_D = out;
-  c->bwd_dS = out2 ? out2 : out;
+  const CombineArgs a = bwd_finish_args(c, l, 0, c->V);
+  if (c->world > 1) RGCN_TRY(combine(c, "combine_bwd_finish", a, 4.0 * c->d * (a.out2 ? 4.0 : 3.0) * c->V));
+  c->bwd_D = a.out;
+  c->bwd_dS = a.out2 ? a.out2 : a.out;
   c->bwd_layer = l - 1;
   return RGCN_OK;
 }
@@ -680,20 +735,12 @@ static rgcn_status fwd_exchange(rgcn_ctx* c, int l) {
 static rgcn_status bwd_exchange(rgcn_ctx* c, int l) {
   const int64_t chunk = (int64_t)c->shard_rows * c->d;
   RGCN_TRY(comm_reduce_scatter(c, c->exch, chunk));
-  float* out = (l - 1 == 0) ? c->g_emb : c->dbuf[(l - 1) & 1];
-  DropSpec d2 = make_drop(c, l - 1, l - 1 >= 1);
-  float* out2 = d2.mode != DROP_NONE ? c->dsbuf[(l - 1) & 1] : nullptr;
-  CombineArgs a;
-  a.add = nullptr;
-  a.out = out; a.out2 = out2; a.base = c->exch; a.msg = nullptr; a.row_ptr = nullptr; a.long_rows = nullptr; a.nlong = nullptr;
-  a.gate = c->H[l - 1]; a.V = c->V; a.d = c->d; a.relu = 0; a.row_lo = c->row_lo; a.row_hi = c->row_hi;
-  a.v_begin = c->row_lo; a.v_count = c->row_hi - c->row_lo;
-  a.drop = make_drop(c, l, false);
-  a.drop2 = d2;
-  if (a.v_count > 0) RGCN_TRY(combine(c, "combine_bwd_finish", a, 4.0 * c->d * (out2 ? 4.0 : 3.0) * a.v_count));
-  RGCN_TRY(gather_rows(c, out));
-  c->bwd_D = out;
-  c->bwd_dS = out2 ? out2 : out;      // own rows only: all the row-sharded self-loop GEMMs read
+  CombineArgs a = bwd_finish_args(c, l, c->row_lo, c->row_hi);
+  a.v_begin = c->row_lo; a.v_count = c->row_hi - c->row_lo;      // (the launch walks the rank's own rows only)
+  if (a.v_count > 0) RGCN_TRY(combine(c, "combine_bwd_finish", a, 4.0 * c->d * (a.out2 ? 4.0 : 3.0) * a.v_count));
+  RGCN_TRY(gather_rows(c, a.out));
+  c->bwd_D = a.out;
+  c->bwd_dS = a.out2 ? a.out2 : a.out;      // own rows only: all the row-sharded self-loop GEMMs read
   c->bwd_layer = l - 1;
   return RGCN_OK;
 }

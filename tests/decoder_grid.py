@@ -15,7 +15,7 @@ tests/test_decoder_grid.py keeps the table honest without a GPU; tests/test_gpu_
 import numpy as np
 
 BLOCK_SIZES = (1, 2, 3, 4, 5, 8)      # block_msgs.hip:193-201: the block sizes d / nb the encoder is compiled for
-MAX_BLOCKS = 512                      # block_msgs.hip:209
+MAX_BLOCKS = 512                      # config_check.h (check_config)
 LONG_ROW = 256                        # decoder.hip:26 (kDecLongRow): a row with more incidences is cut into pieces
 PIECE = 512                           # decoder.hip:27 (kDecPiece): incidences per piece
 CHUNK = 128                           # decoder.hip:29 (kDecChunk): triples per relation chunk

@@ -17,8 +17,8 @@ GROUP_WIDTHS = (8, 16, 32, 64)
 TILE_SIZES = (64, 32, 16, 8)
 LONG_ROW = 32                         # rgcn_internal.h:93 (kLongRow): a row with more slots takes the long-row path
 GIANT_ROW = 2048                      # rgcn_internal.h:96 (kGiantRow): full-graph scale only, never reached here
-MAX_BLOCKS = 512                      # block_msgs.hip:209
-MAX_BASES = 64                        # rgcn_api.hip:349
+MAX_BLOCKS = 512                      # config_check.h (check_config)
+MAX_BASES = 64                        # config_check.h (check_config)
 BASIS_BT = 8                          # basis.hip:26 (BT): basis functions per pass
 D500_BLOCK_COUNTS = (100, 125, 250, 500)   # every nb that divides the shipped d = 500 into a compiled block size
 
@@ -35,7 +35,7 @@ def long_tile(sd, gw):
 
 
 def block_slots(nb, sd):
-    """block_msgs.hip:208-227 (block_geometry): (workgroup size, G message slots per workgroup) of k_block_msg_fwd/_bwd."""
+    """block_msgs.hip (block_geometry): (workgroup size, G message slots per workgroup) of k_block_msg_fwd/_bwd."""
     best_block = best_g = 0
     best_util = 0.0
     for blk in range(64, 513, 64):

@@ -22,7 +22,7 @@
  *     its error text, and the only state contexts share is the text of a failed rgcn_create and a pool of idle HIP
  *     streams that destroyed contexts leave for later ones (both behind a mutex).  Contexts do not order themselves
  *     against each other: a device pointer one context hands to another (rgcn_rank_energies_device into
- *     rgcn_rank_mixed_device) is valid once the call that filled it has synchronised or rgcn_sync() has returned on
+ *     rgcn_rank_mixed_device or rgcn_topk_mixed_device) is valid once the call that filled it has synchronised or rgcn_sync() has returned on
  *     the owner.  A context itself is not thread-safe; its calls are stream-ordered on the context's own HIP stream
  *     and asynchronous unless they return host data;
  *   - all floating point is float32, all indices int32 (reference:
@@ -76,9 +76,10 @@ enum { RGCN_KIND_BLOCK = 0, RGCN_KIND_BASIS = 1, RGCN_KIND_BASIS_TDIAG = 2, RGCN
  *     non-NULL triple pointer or num_edges != 0 is RGCN_ERR_INVALID;
  *   - RGCN_ERR_UNSUPPORTED, the message naming the kind: rgcn_set_graph*, rgcn_prefetch_graph*, rgcn_step_device,
  *     rgcn_train_step_minibatch_device, rgcn_neighborhood_reserve, the phase API (rgcn_forward_begin ... rgcn_backward_end),
- *     rgcn_set_relation_owner, rgcn_capture_begin; rgcn_read_buffer knows RGCN_BUF_RANK_ENERGIES only (RGCN_ERR_STATE);
+ *     rgcn_set_relation_owner, rgcn_capture_begin; rgcn_read_buffer knows RGCN_BUF_RANK_ENERGIES and
+ *     RGCN_BUF_RANK_MIXED_SCORES only (RGCN_ERR_STATE);
  *   - unchanged: rgcn_decoder_*, rgcn_negative_sample_device, rgcn_optimizer_*, rgcn_rank_device, rgcn_rank_mixed_device,
- *     rgcn_topk_device, parameters, device memory, timer and profile. */
+ *     rgcn_topk_device, rgcn_score_queries_device, rgcn_topk_mixed_device, parameters, device memory, timer and profile. */
 /* RGCN_KIND_BASIS_TDIAG = Encoder.DiagonalCoefficients=Yes -> BasisGcnTimesDiag
  * (code/encoders/message_gcns/gcn_basis_times_diag.py; model_builder.py:287-288, ahead of Concatenation): the
  * coefficient of a message is a VECTOR per (relation, basis) over the output channels,
@@ -168,8 +169,8 @@ enum {
    * directed relation r (m < E) or R + r */
   RGCN_BUF_PERM_VERTEX = 8,     /* int32 [2E] incidence ids in incidence-CSR order (by vertex, ties by id) */
   RGCN_BUF_PERM_RELATION = 9,   /* int32 [2E] message ids in message-list order (by directed relation, ties by id) */
-  RGCN_BUF_RANK_ENERGIES = 10,  /* float [reserved queries, V] energies of the last chunk rgcn_rank_device or
-                                   rgcn_topk_device scored (the float half of the ranking; the counts and the selection
+  RGCN_BUF_RANK_ENERGIES = 10,  /* float [reserved queries, V] energies of the last chunk rgcn_rank_device,
+                                   rgcn_topk_device or one of their mixed and score-only forms scored (the float half of the ranking; the counts and the selection
                                    are integer work on exactly these values) */
   RGCN_BUF_MSG_NORM = 11,       /* float [2E] normalisation of every message, in message-list order: entry j belongs to
                                    message RGCN_BUF_PERM_RELATION[j] (every RGCN_NORM_* mode).  Sharded context: only
@@ -183,7 +184,10 @@ enum {
   /* RGCN_KIND_BASIS_PDIAG contexts, of the layer the last rgcn_forward_layer_finish (or rgcn_forward: layer L) ran;
    * RGCN_ERR_STATE before any layer has run and on every other context: */
   RGCN_BUF_PDIAG_MIX = 15,      /* float [2][V][B]: a_dir[v,b] = sum over the row's messages of direction dir of n C_dir[r,b] */
-  RGCN_BUF_PDIAG_AGG = 16       /* float [V,d]: the diagonal aggregate sum over the row's messages of n D[rho] * H_{l-1}[src] */
+  RGCN_BUF_PDIAG_AGG = 16,      /* float [V,d]: the diagonal aggregate sum over the row's messages of n D[rho] * H_{l-1}[src] */
+  RGCN_BUF_RANK_MIXED_SCORES = 17 /* float [reserved queries, V]: the mixed scores of the last rgcn_topk_mixed_device (what
+                                   it selected from, bit for bit).  RGCN_ERR_STATE before the first such call, and again
+                                   after a growing rgcn_rank_reserve until the next one */
 };
 
 /*
@@ -446,6 +450,41 @@ rgcn_status rgcn_rank_mixed_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t 
 rgcn_status rgcn_topk_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t num_queries, int32_t predict_object,
                              int32_t k, const int64_t* exclude_ptr_dev, const int32_t* exclude_idx_dev,
                              int32_t* topk_idx_dev, float* topk_energy_dev);
+
+/* ---- ensemble prediction: the k most plausible entities under the weighted sum of TWO models' scores -----------
+ * rgcn_topk_device's question put to the mixture rgcn_rank_mixed_device ranks (the reference's R-GCN+).
+ *
+ * rgcn_score_queries_device is how the partner model produces its energies for queries that have no gold entity: it runs
+ * rgcn_topk_device's validation (the two ids that are read, on the device; the predicted column is not read and may be
+ * -1), query kernel and GEMM and nothing after them, so that RGCN_BUF_RANK_ENERGIES (rgcn_rank_energies_device) holds,
+ * bit for bit, what rgcn_topk_device leaves there for the same queries.  ONE chunk only: num_queries above what
+ * rgcn_rank_reserve sized is RGCN_ERR_INVALID (the buffer holds one chunk).  RGCN_ERR_STATE before a forward pass or
+ * before rgcn_rank_reserve.  Synchronises at the end (it reads the validation verdict): not capturable.
+ *
+ * rgcn_topk_mixed_device: queries, their validation, the limits on k, the exclusion CSR, RGCN_MAX_TOPK and
+ * RGCN_MAX_TOPK_ENTITIES are rgcn_topk_device's; partner_energies (float [num_queries, V], row-major, on this device,
+ * complete before the call, untouched until it returns, only read) and weight (outside [0, 1] or NaN: RGCN_ERR_INVALID)
+ * are rgcn_rank_mixed_device's.  The partner may be this context's own RGCN_BUF_RANK_ENERGIES of an earlier call only
+ * through a copy: the call rewrites that buffer with its own energies.  ONE chunk only, as the mixed rank.
+ * The call scores its queries as rgcn_topk_device does (RGCN_BUF_RANK_ENERGIES holds the context's own energies
+ * afterwards, unmodified), then forms for every entity of every row
+ *     m[e] = (float)((double)weight * s_own[e] + (1.0 - (double)weight) * s_partner[e])
+ * exactly as rgcn_rank_mixed_device does (the same device function: fp32 sigmoids evaluated in double and rounded once,
+ * the mix in double without fused multiply-add, rounded once) into a scratch of [reserved queries, V] floats,
+ * RGCN_BUF_RANK_MIXED_SCORES, and selects from that scratch with rgcn_topk_device's selection: row i of the result holds
+ * the min(k, V - #distinct excluded) best remaining entities ordered by (m descending, entity id ascending) -- a total
+ * order on the stored floats, so two calls on the same inputs return the same bytes.  topk_idx int32 [N,k], topk_score
+ * float [N,k] (the scratch's values, bit for bit); slots a row cannot fill hold id -1 and score -INFINITY.  NaN partner
+ * energies leave that row's answer unspecified; nothing faults.
+ * The scratch is allocated by the first call after rgcn_rank_reserve (RGCN_ERR_NOMEM if it does not fit) and released
+ * with the other ranking buffers: a context that is never asked for the mixture never holds it.
+ * Synchronising, capture (RGCN_ERR_STATE), relation-sharded contexts and RGCN_KIND_EMBEDDING: as rgcn_topk_device. */
+rgcn_status rgcn_score_queries_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t num_queries,
+                                      int32_t predict_object);
+rgcn_status rgcn_topk_mixed_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t num_queries, int32_t predict_object,
+                                   int32_t k, const float* partner_energies_dev, float weight,
+                                   const int64_t* exclude_ptr_dev, const int32_t* exclude_idx_dev,
+                                   int32_t* topk_idx_dev, float* topk_score_dev);
 
 /* GradientClipping(max_norm) + Adam(lr) of the Converge chain (optimization/tensorflow_backend/
  * algorithms.py:27-42,58-68).  max_grad_norm = 0 disables clipping. */

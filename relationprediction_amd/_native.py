@@ -25,6 +25,7 @@ BUF_EXCHANGE, BUF_SELF, BUF_DSELF_EXCHANGE, BUF_INDEG, BUF_OUTDEG, BUF_ROWPTR, B
 BUF_TDIAG_PRODUCTS = 14      # basis_tdiag contexts: [2, V, B*d], P_f then P_b of the layer run last
 BUF_PDIAG_MIX = 15           # basis_pdiag contexts: [2, V, B], the mixing table a of the layer run last
 BUF_PDIAG_AGG = 16           # basis_pdiag contexts: [V, d], the diagonal aggregate of the layer run last
+BUF_RANK_MIXED_SCORES = 17   # [reserved queries, V], the mixed scores the last topk_mixed selected from
 
 KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS, "basis_tdiag": KIND_BASIS_TDIAG,
          "basis_pdiag": KIND_BASIS_PDIAG, "embedding": KIND_EMBEDDING}
@@ -112,6 +113,8 @@ _SIGS = {
     "rgcn_rank_energies_device": (_P, [_P]),
     "rgcn_rank_mixed_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, C.c_float, _P, _P, _P, _P]),
     "rgcn_topk_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "rgcn_score_queries_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32]),
+    "rgcn_topk_mixed_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_float, _P, _P, _P, _P]),
     "rgcn_optimizer_step": (C.c_int32, [_P]),
     "rgcn_optimizer_norm_partial": (C.c_int32, [_P]),
     "rgcn_optimizer_apply": (C.c_int32, [_P]),
@@ -673,6 +676,71 @@ class Engine:
         self._check(self.lib.rgcn_copy_to_host(self.ctx, _ptr(out), C.c_void_p(base + off_out), 8 * n * k))
         return out[:n * k].reshape(n, k).copy(), out[n * k:].view(np.float32).reshape(n, k).copy()
 
+    def score_queries(self, queries, predict_object):
+        """Energies of every entity for each query into RGCN_BUF_RANK_ENERGIES and nothing else (include/rgcn.h
+        rgcn_score_queries_device): what topk leaves there, for another engine's topk_mixed to read through
+        rank_energies_device().  queries [N,3] rows (s, r, o) of which the predicted column is not read; one chunk: N <=
+        the reserve.  Synchronises."""
+        x = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1, 3)
+        if len(x) == 0:
+            return
+        xd = DeviceBuffer(self, x.nbytes).upload(x)
+        try:
+            self._check(self.lib.rgcn_score_queries_device(self.ctx, xd.ptr, len(x), 1 if predict_object else 0))
+        finally:
+            xd.free()
+
+    def topk_mixed(self, queries, predict_object, k, partner, weight, exclude_ptr=None, exclude_idx=None):
+        """topk() under weight * own score + (1 - weight) * partner score (include/rgcn.h rgcn_topk_mixed_device): (idx
+        int32 [N,k], mixed score float32 [N,k]) ordered by (mixed score descending, entity id ascending), rows short of k
+        answers padded with (-1, -inf).  partner as for ranks_mixed: the other model's energies for the same queries in the
+        same order -- a float32 [N, V] numpy array (uploaded), a DeviceBuffer, or a device address
+        (rank_energies_device() of another engine on the same GPU after its score_queries, left alone until this call
+        returns).  One chunk: N <= the reserve."""
+        x = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1, 3)
+        n, k = len(x), int(k)
+        if (exclude_ptr is None) != (exclude_idx is None):
+            raise ValueError("exclude_ptr and exclude_idx come together")
+        if n == 0:
+            return np.zeros((0, max(k, 0)), np.int32), np.zeros((0, max(k, 0)), np.float32)
+        has = exclude_ptr is not None
+        fp = np.ascontiguousarray(exclude_ptr if has else np.zeros(n + 1), dtype=np.int64)
+        fi = np.ascontiguousarray(exclude_idx if has else np.zeros(0), dtype=np.int32)
+        assert fp.shape == (n + 1,) and fp[-1] == len(fi)
+        own = None
+        if isinstance(partner, np.ndarray):
+            e = np.ascontiguousarray(partner, dtype=np.float32)
+            if e.shape != (n, self.V):
+                raise ValueError("partner energies must be [%d, %d], not %s" % (n, self.V, e.shape))
+            own = DeviceBuffer(self, e.nbytes).upload(e)
+            pp = own.ptr
+        elif isinstance(partner, DeviceBuffer):
+            pp = partner.ptr
+        else:
+            pp = C.c_void_p(int(partner))
+        room = min(max(k, 0), 1024)        # (a k outside [1, RGCN_MAX_TOPK] is the library's to refuse: it writes nothing)
+        try:
+            xd = DeviceBuffer(self, x.nbytes).upload(x)
+            fpd = DeviceBuffer(self, fp.nbytes).upload(fp)
+            fid = DeviceBuffer(self, max(fi.nbytes, 4))
+            if fi.nbytes:
+                self.copy_to_device(fid, fi)
+            out = DeviceBuffer(self, max(8 * n * room, 8))
+            base = out.ptr.value
+            try:
+                self._check(self.lib.rgcn_topk_mixed_device(self.ctx, xd.ptr, n, 1 if predict_object else 0, k, pp,
+                                                            C.c_float(float(weight)), fpd.ptr if has else None,
+                                                            fid.ptr if has else None, C.c_void_p(base),
+                                                            C.c_void_p(base + 4 * n * room)))
+                r = out.download(np.int32, (2 * n * room,))
+            finally:
+                for b in (xd, fpd, fid, out):
+                    b.free()
+        finally:
+            if own is not None:
+                own.free()
+        return r[:n * k].reshape(n, k).copy(), r[n * k:].view(np.float32).reshape(n, k).copy()
+
     def optimizer_config(self, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, max_grad_norm=1.0):
         self._check(self.lib.rgcn_optimizer_config(self.ctx, lr, beta1, beta2, eps, max_grad_norm))
 
@@ -729,7 +797,7 @@ class Engine:
             out = np.empty(2 * self.num_edges, dtype=np.int32)
         elif which == BUF_MSG_NORM:
             out = np.empty(2 * self.num_edges, dtype=np.float32)
-        elif which == BUF_RANK_ENERGIES:
+        elif which in (BUF_RANK_ENERGIES, BUF_RANK_MIXED_SCORES):
             out = np.empty((getattr(self, "_rank_reserved", 0), self.V), dtype=np.float32)
         elif which == BUF_DSELF_EXCHANGE:
             out = np.empty((self.d, self.d), dtype=np.float32)

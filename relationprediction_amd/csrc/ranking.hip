@@ -28,6 +28,11 @@
 //
 // Top-k prediction (rgcn_topk_device) selects from the same energies: same query kernel, same GEMM, same buffers; one
 // workgroup per query picks and orders the k best entities that its exclusion list leaves (k_topk_rows below).
+//
+// Ensemble top-k (rgcn_topk_mixed_device) is the two together: k_mix_rows writes m for every entity of every query into a
+// scratch of its own, through the mixed_score k_rank_rows_mixed compares with, and k_topk_rows selects from that scratch
+// exactly as it selects from energies (it orders any floats).  rgcn_score_queries_device is how the partner produces its
+// energies for queries that have no gold entity: the top-k call's check, query kernel and GEMM, nothing after them.
 #include "rgcn_internal.h"
 
 namespace rgcn {
@@ -175,6 +180,19 @@ k_rank_rows_mixed(const float* __restrict__ Sa, const float* __restrict__ Sb, in
     raw_rank[row] = raw;
     filt_rank[row] = raw - (red[1][0] + red[1][1] + red[1][2] + red[1][3]) + 1;
   }
+}
+
+// M[row, e] = mixed_score(w, Sa[row, e], Sb[row, e]): the mixed scores rgcn_topk_mixed_device selects from, the very
+// floats k_rank_rows_mixed compares.  Its shape -- one workgroup of four wave64s per query, both energy rows read once with
+// lane-consecutive entities -- and its cost, two double-precision exponentials per entity; the one write is the addition.
+__global__ void __launch_bounds__(256)
+k_mix_rows(const float* __restrict__ Sa, const float* __restrict__ Sb, int V, int n, double w, float* __restrict__ M) {
+  const int row = blockIdx.x;
+  if (row >= n) return;
+  const float* a = Sa + (size_t)row * V;
+  const float* b = Sb + (size_t)row * V;
+  float* m = M + (size_t)row * V;
+  for (int e = threadIdx.x; e < V; e += 256) m[e] = mixed_score(w, a[e], b[e]);
 }
 
 // (the last entry of filt_ptr is the list's declared length: no range may end beyond it)
@@ -503,13 +521,10 @@ rgcn_status rank_mixed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int
   return RGCN_OK;
 }
 
-rgcn_status topk_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, int k,
-                         const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out, float* energy_out) {
-  const float* codes = c->H[c->L];
-  const size_t mask_bytes = (size_t)((c->V + 31) / 32) * sizeof(uint32_t);
-  // the mask is dynamic LDS, above the default limit for large V: raise the kernel's limit on the context's device (every
-  // API entry selects it) the first time it launches there.  One bit per device id, per process and unguarded like the
-  // GEMM launchers' (a context is single-threaded); past 64 devices the attribute is set on every call.
+// k_topk_rows' exclusion mask is dynamic LDS, above the default limit for large V: raise the kernel's limit on the context's
+// device (every API entry selects it) the first time it launches there.  One bit per device id, per process and unguarded
+// like the GEMM launchers' (a context is single-threaded); past 64 devices the attribute is set on every call.
+static rgcn_status topk_rows_configure(rgcn_ctx* c) {
   static uint64_t lds_configured = 0;
   const uint64_t device_bit = c->cfg.device < 64 ? 1ull << c->cfg.device : 0;
   if (!(lds_configured & device_bit)) {
@@ -517,6 +532,14 @@ rgcn_status topk_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predi
                                     (int)((size_t)((RGCN_MAX_TOPK_ENTITIES + 31) / 32) * sizeof(uint32_t))));
     lds_configured |= device_bit;
   }
+  return RGCN_OK;
+}
+
+rgcn_status topk_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, int k,
+                         const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out, float* energy_out) {
+  const float* codes = c->H[c->L];
+  const size_t mask_bytes = (size_t)((c->V + 31) / 32) * sizeof(uint32_t);
+  RGCN_TRY(topk_rows_configure(c));
   // as rank_compute: ids are validated on the device, id 0 stands in for a bad one until the verdict is read back at the
   // end of the call, and the (meaningless) answers of a rejected call are not to be used
   RGCN_HIP(c, hipMemsetAsync(c->ranking.bad, 0, sizeof(int32_t), c->stream));
@@ -546,6 +569,73 @@ rgcn_status topk_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predi
   RGCN_HIP(c, hipMemcpyAsync(&bad, c->ranking.bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   RGCN_HIP(c, hipStreamSynchronize(c->stream));
   if (bad) RGCN_FAIL(c, RGCN_ERR_INVALID, "topk: entity / relation / exclusion index out of range");
+  return RGCN_OK;
+}
+
+// topk_compute's validation, query kernel and GEMM for ONE chunk and nothing after them: c->ranking.s holds the energies of
+// queries that have no gold entity -- what the partner model of an ensemble top-k hands over
+rgcn_status score_queries_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object) {
+  const float* codes = c->H[c->L];
+  const int n = (int)N;
+  RGCN_HIP(c, hipMemsetAsync(c->ranking.bad, 0, sizeof(int32_t), c->stream));
+  hipLaunchKernelGGL(k_topk_check, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, X_dev, n, c->V, c->R,
+                     predict_object, (const int64_t*)nullptr, c->ranking.bad);
+  RGCN_HIP(c, hipGetLastError());
+  {
+    ProfScope ps(c, "rank_query", 4.0 * 3 * n * c->d, 0);
+    hipLaunchKernelGGL(k_rank_query, dim3((unsigned)n), dim3(128), 0, c->stream, codes, c->w_rel, X_dev, n, c->d,
+                       predict_object, c->ranking.q, c->V, c->R);
+    RGCN_HIP(c, hipGetLastError());
+  }
+  RGCN_TRY(gemm_f32(c, "rank_scores", true, true, n, c->V, c->d, c->ranking.q, c->d, codes, c->d, c->ranking.s, c->V, 1));
+  int32_t bad = 0;
+  RGCN_HIP(c, hipMemcpyAsync(&bad, c->ranking.bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  RGCN_HIP(c, hipStreamSynchronize(c->stream));
+  if (bad) RGCN_FAIL(c, RGCN_ERR_INVALID, "score queries: entity / relation index out of range");
+  return RGCN_OK;
+}
+
+// topk_compute's scoring for ONE chunk, then the mixed scores of every entity into c->ranking.mixed (k_mix_rows) and
+// k_topk_rows, as it stands, on those instead of on the energies.  c->ranking.s holds the context's own energies afterwards,
+// unmodified; the partner's rows are only read.  The [reserved queries, V] scratch is allocated here, on the first call
+// after a (growing) rank_reserve: a context that never asks the ensemble never holds it.
+rgcn_status topk_mixed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, int k, const float* partner,
+                               float weight, const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out,
+                               float* score_out) {
+  const float* codes = c->H[c->L];
+  const int n = (int)N;
+  const size_t mask_bytes = (size_t)((c->V + 31) / 32) * sizeof(uint32_t);
+  RGCN_TRY(topk_rows_configure(c));
+  RankBufs& q = c->ranking;
+  if (!q.mixed) RGCN_TRY(dmalloc(c, q.pool, &q.mixed, (size_t)q.max * c->V, false));
+  RGCN_HIP(c, hipMemsetAsync(q.bad, 0, sizeof(int32_t), c->stream));
+  hipLaunchKernelGGL(k_topk_check, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, X_dev, n, c->V, c->R,
+                     predict_object, excl_ptr, q.bad);
+  RGCN_HIP(c, hipGetLastError());
+  {
+    ProfScope ps(c, "rank_query", 4.0 * 3 * n * c->d, 0);
+    hipLaunchKernelGGL(k_rank_query, dim3((unsigned)n), dim3(128), 0, c->stream, codes, c->w_rel, X_dev, n, c->d,
+                       predict_object, q.q, c->V, c->R);
+    RGCN_HIP(c, hipGetLastError());
+  }
+  RGCN_TRY(gemm_f32(c, "rank_scores", true, true, n, c->V, c->d, q.q, c->d, codes, c->d, q.s, c->V, 1));
+  {
+    // two rows read, one written, each byte once
+    ProfScope ps(c, "topk_mix_rows", 12.0 * n * c->V, 0);
+    hipLaunchKernelGGL(k_mix_rows, dim3((unsigned)n), dim3(256), 0, c->stream, q.s, partner, c->V, n, (double)weight, q.mixed);
+    RGCN_HIP(c, hipGetLastError());
+  }
+  {
+    // design bytes: as topk_rows -- four select passes and the gather read the row (from L2 after the first)
+    ProfScope ps(c, "topk_rows_mixed", 5.0 * 4.0 * n * c->V + 8.0 * n * k, 0, 4.0 * n * c->V + 8.0 * n * k);
+    hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)n), dim3(TOPK_THREADS), mask_bytes, c->stream, q.mixed, c->V, n, k, excl_ptr,
+                       excl_idx, excl_ptr ? excl_ptr + N : nullptr, idx_out, score_out, q.bad);
+    RGCN_HIP(c, hipGetLastError());
+  }
+  int32_t bad = 0;
+  RGCN_HIP(c, hipMemcpyAsync(&bad, q.bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  RGCN_HIP(c, hipStreamSynchronize(c->stream));
+  if (bad) RGCN_FAIL(c, RGCN_ERR_INVALID, "topk (mixed): entity / relation / exclusion index out of range");
   return RGCN_OK;
 }
 

@@ -1068,6 +1068,43 @@ rgcn_status rgcn_topk_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32
   return topk_compute(c, x_dev, n, predict_object ? 1 : 0, k, exclude_ptr_dev, exclude_idx_dev, topk_idx_dev, topk_energy_dev);
 }
 
+rgcn_status rgcn_score_queries_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32_t predict_object) {
+  RGCN_NEED(c);
+  if (n < 0 || (n > 0 && !x_dev)) RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "this call synchronises with the device: not allowed between rgcn_capture_begin and rgcn_capture_end");
+  if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_score_queries_device needs a completed rgcn_forward (test mode on the full graph)");
+  if (c->ranking.max <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_rank_reserve first");
+  if (n > c->ranking.max)
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_score_queries_device: one chunk only -- num_queries above what rgcn_rank_reserve "
+                                   "sized (the buffer holds one chunk)");
+  if (n == 0) return RGCN_OK;
+  return score_queries_compute(c, x_dev, n, predict_object ? 1 : 0);
+}
+
+rgcn_status rgcn_topk_mixed_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32_t predict_object, int32_t k,
+                                   const float* partner_energies_dev, float weight, const int64_t* exclude_ptr_dev,
+                                   const int32_t* exclude_idx_dev, int32_t* topk_idx_dev, float* topk_score_dev) {
+  RGCN_NEED(c);
+  if (n < 0 || (n > 0 && (!x_dev || !partner_energies_dev || !topk_idx_dev || !topk_score_dev)) ||
+      (!exclude_ptr_dev != !exclude_idx_dev))
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
+  if (!(weight >= 0.0f && weight <= 1.0f)) RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_topk_mixed_device: weight must be in [0, 1]");
+  if (k < 1 || k > c->V || k > RGCN_MAX_TOPK)
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_topk_mixed_device: k must be in [1, min(EntityCount, " + std::to_string(RGCN_MAX_TOPK) + ")]");
+  if (c->V > RGCN_MAX_TOPK_ENTITIES)
+    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "rgcn_topk_mixed_device: EntityCount above " + std::to_string(RGCN_MAX_TOPK_ENTITIES) +
+                                           " (a row's exclusion mask must fit in LDS)");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "this call synchronises with the device: not allowed between rgcn_capture_begin and rgcn_capture_end");
+  if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_topk_mixed_device needs a completed rgcn_forward (test mode on the full graph)");
+  if (c->ranking.max <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_rank_reserve first");
+  if (n > c->ranking.max)
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_topk_mixed_device: one chunk only -- num_queries above what rgcn_rank_reserve sized "
+                                   "(the partner's buffer has its own chunking)");
+  if (n == 0) return RGCN_OK;
+  return topk_mixed_compute(c, x_dev, n, predict_object ? 1 : 0, k, partner_energies_dev, weight, exclude_ptr_dev,
+                            exclude_idx_dev, topk_idx_dev, topk_score_dev);
+}
+
 rgcn_status rgcn_optimizer_config(rgcn_ctx* c, float lr, float beta1, float beta2, float eps, float max_grad_norm) {
   RGCN_NEED(c);
   if (!(lr > 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps > 0.f) ||
@@ -1485,8 +1522,8 @@ rgcn_status rgcn_backward_end(rgcn_ctx* c) { RGCN_NEED(c); return bwd_end(c); }
 
 static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* bytes) {
   const int64_t Vd = (int64_t)c->V * c->d * 4;
-  if (c->embedding && which != RGCN_BUF_RANK_ENERGIES)
-    RGCN_FAIL(c, RGCN_ERR_STATE, "an RGCN_KIND_EMBEDDING context has the ranking energies only (no graph, no layer buffers)");
+  if (c->embedding && which != RGCN_BUF_RANK_ENERGIES && which != RGCN_BUF_RANK_MIXED_SCORES)
+    RGCN_FAIL(c, RGCN_ERR_STATE, "an RGCN_KIND_EMBEDDING context has the ranking buffers only (no graph, no layer buffers)");
   switch (which) {
     case RGCN_BUF_EXCHANGE:
       if (!c->exch) RGCN_FAIL(c, RGCN_ERR_STATE, "no exchange buffer on a world == 1 context");
@@ -1515,6 +1552,9 @@ static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* byte
     case RGCN_BUF_RANK_ENERGIES:
       if (!c->ranking.s) RGCN_FAIL(c, RGCN_ERR_STATE, "no score buffer (rgcn_rank_reserve first)");
       *p = c->ranking.s; *bytes = (int64_t)c->ranking.max * c->V * 4; return RGCN_OK;
+    case RGCN_BUF_RANK_MIXED_SCORES:
+      if (!c->ranking.mixed) RGCN_FAIL(c, RGCN_ERR_STATE, "no mixed scores (no rgcn_topk_mixed_device since the last rgcn_rank_reserve)");
+      *p = c->ranking.mixed; *bytes = (int64_t)c->ranking.max * c->V * 4; return RGCN_OK;
     case RGCN_BUF_HIGHWAY_INNER:
     case RGCN_BUF_HIGHWAY_GATE:
       if (!c->highway) RGCN_FAIL(c, RGCN_ERR_STATE, "not an RGCN_SKIP_HIGHWAY context");

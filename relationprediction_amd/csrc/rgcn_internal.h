@@ -346,6 +346,7 @@ struct RankBufs {
   float *q = nullptr, *s = nullptr;      // query rows [max,d], energies [max,V]
   int32_t* bad = nullptr;
   float* thr = nullptr;                  // per query: the smallest energy whose fp32 sigmoid reaches the gold entity's
+  float* mixed = nullptr;                // mixed scores [max,V]: null until the first rgcn_topk_mixed_device at this size
   int64_t max = 0;
 };
 
@@ -741,6 +742,10 @@ rgcn_status rank_mixed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int
                                int32_t* filt_out);
 rgcn_status topk_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, int k,
                          const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out, float* energy_out);
+rgcn_status score_queries_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object);
+rgcn_status topk_mixed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, int k,
+                               const float* partner_dev, float weight, const int64_t* excl_ptr, const int32_t* excl_idx,
+                               int32_t* idx_out, float* score_out);
 void optimizer_free(rgcn_ctx* c);
 
 // ---- comm.cpp (RCCL via dlopen)

@@ -136,6 +136,28 @@ class BilinearDiag(Model):
             self._ranks_graph = graph
         return self.next_component.get_runtime().topk(queries, predict_object, k, exclude_ptr, exclude_idx)
 
+    def device_score_queries(self, graph, queries, predict_object):
+        """Energies of every entity for each row of `queries` (the column being predicted is not read), left in the
+        engine's score buffer (rgcn_score_queries_device; Engine.rank_energies_device is its address): what the other
+        model of an ensemble hands to device_topk_mixed.  One chunk of at most Scorer.chunk_size queries."""
+        variables = self.get_test_input_variables()
+        if self.needs_graph() and (getattr(self, '_ranks_graph', None) is not graph or variables[0].value is None):
+            variables[0].feed(graph)          # re-encoded only when the graph or the weights changed
+            self._ranks_graph = graph
+        self.next_component.get_runtime().score_queries(queries, predict_object)
+
+    def device_topk_mixed(self, graph, queries, predict_object, k, partner, weight, exclude_ptr=None, exclude_idx=None):
+        """device_topk under weight * this model's score + (1 - weight) * another model's (rgcn_topk_mixed_device):
+        partner = that model's energies for the same queries in the same order, a float32 [N, EntityCount] array or the
+        device address of its engine's score buffer (same GPU).  Returns (entity ids int32 [N,k], mixed scores float32
+        [N,k]) ordered by (mixed score descending, entity id ascending); one chunk of at most Scorer.chunk_size queries."""
+        variables = self.get_test_input_variables()
+        if self.needs_graph() and (getattr(self, '_ranks_graph', None) is not graph or variables[0].value is None):
+            variables[0].feed(graph)
+            self._ranks_graph = graph
+        return self.next_component.get_runtime().topk_mixed(queries, predict_object, k, partner, weight, exclude_ptr,
+                                                            exclude_idx)
+
     def predict_top(self, predict_object, k, exclude_ptr=None, exclude_idx=None):
         """device_topk restated eagerly on predict_all_object_scores / predict_all_subject_scores of the triples fed
         to X (all three columns valid ids): (entity ids int32 [N,k], scores float32 [N,k]) ordered by (score

@@ -216,6 +216,12 @@ class Model(object):
     def device_topk(self, *args, **kwargs):
         return self.__delegate__('device_topk', *args, **kwargs)
 
+    def device_score_queries(self, *args):
+        return self.__delegate__('device_score_queries', *args)
+
+    def device_topk_mixed(self, *args, **kwargs):
+        return self.__delegate__('device_topk_mixed', *args, **kwargs)
+
     def predict_top(self, *args, **kwargs):
         return self.__delegate__('predict_top', *args, **kwargs)
 

@@ -1,7 +1,8 @@
 """Ask a trained model: the k most plausible completions of (entity, relation, ?) or (?, relation, entity).
 
     python -m relationprediction_amd.predict --settings settings/gcn_block.exp --dataset data/FB-Toutanova \
-        --model models/GcnBlock-3.npz --queries queries.txt --k 10 [--side object|subject] [--keep-known] [--out FILE]
+        --model models/GcnBlock-3.npz --queries queries.txt --k 10 [--side object|subject] [--keep-known] [--out FILE] \
+        [--settings2 settings/distmult.exp --model2 models/Distmult-3.npz [--weight 0.5]]
 
 The model is built exactly as train.py builds it (same settings merge, same chain), the checkpoint is one written by
 Model.save, the training graph is encoded once in test mode and the selection runs on the device (rgcn_topk_device:
@@ -16,7 +17,14 @@ Completions already known from train / valid / test are left out unless --keep-k
     query_entity<TAB>relation<TAB>answer_entity<TAB>position<TAB>score
 
 position counts from 1 (best); score = sigmoid(energy), evaluated in double and rounded once to float32 as everywhere
-else (csrc/ranking.hip).  Answers are ordered by (energy descending, entity id ascending)."""
+else (csrc/ranking.hip).  Answers are ordered by (energy descending, entity id ascending).
+
+--settings2 and --model2 (together) ask the R-GCN+ ensemble instead: a second model, built and loaded the same way on the
+same GPU, is scored with the first as `weight * score_1 + (1 - weight) * score_2` (ensemble.py's mixture; --weight is
+model 1's weight, in [0, 1], default 0.5).  Per chunk of Scorer.chunk_size queries model 2 leaves its energies in its
+engine's score buffer (rgcn_score_queries_device) and model 1's engine mixes and selects reading that buffer in place
+(rgcn_topk_mixed_device); the dataset is loaded once, under model 1's Evaluation.Metric.  The lines keep their format; the
+last column is the mixed score, and the answers are ordered by (mixed score descending, entity id ascending)."""
 import argparse
 import sys
 
@@ -71,7 +79,19 @@ def main(argv=None, out=None):
     parser.add_argument("--keep-known", action="store_true",
                         help="do not leave out the completions known from train / valid / test")
     parser.add_argument("--out", default=None, help="write the answers here instead of standard output")
+    parser.add_argument("--settings2", default=None, help="settings file of model 2: answer under the ensemble of the two")
+    parser.add_argument("--model2", default=None, help="checkpoint of model 2")
+    parser.add_argument("--weight", type=float, default=None,
+                        help="weight of model 1's score; model 2 gets 1 - weight (default 0.5; needs --settings2 / --model2)")
     args = parser.parse_args(argv)
+    if (args.settings2 is None) != (args.model2 is None):
+        raise ValueError("--settings2 and --model2 come together")
+    ensemble = args.settings2 is not None
+    if args.weight is not None and not ensemble:
+        raise ValueError("--weight needs --settings2 and --model2")
+    weight = 0.5 if args.weight is None else args.weight
+    if not 0.0 <= weight <= 1.0:                 # (NaN fails both comparisons)
+        raise ValueError("--weight %r: must lie in [0, 1]" % (weight,))
 
     settings = settings_reader.read(args.settings)
     from .train import load_dataset
@@ -97,8 +117,29 @@ def main(argv=None, out=None):
     if pairs:
         queries[:, 0 if predict_object else 2] = [p[0] for p in pairs]
         queries[:, 1] = [p[1] for p in pairs]
-    top, energies = model.device_topk(model.test_graph, queries, predict_object, args.k, ptr, idx)
-    scores = sigmoid_f32(energies)
+    if ensemble:
+        second = build_model(settings_reader.read(args.settings2), splits, len(entities), len(relations))
+        second.load(args.model2)
+        devices = [m.get_runtime().engine.cfg.device for m in (model, second)]
+        if devices[0] != devices[1]:
+            raise ValueError("the two models must run on one GPU (Device %d and %d): model 1 reads model 2's scores in place"
+                             % tuple(devices))
+        top, scores = np.full((len(pairs), args.k), -1, np.int32), np.full((len(pairs), args.k), -np.inf, np.float32)
+        chunk_size = evaluation.Scorer.chunk_size
+        for lo in range(0, len(pairs), chunk_size):
+            hi = min(lo + chunk_size, len(pairs))
+            chunk_ptr = chunk_idx = None
+            if ptr is not None:
+                chunk_ptr, chunk_idx = ptr[lo:hi + 1] - ptr[lo], idx[ptr[lo]:ptr[hi]]
+            # model 2 first: the call synchronises, and its energies of THIS chunk stay in its engine's buffer until its
+            # next scoring call
+            second.device_score_queries(second.test_graph, queries[lo:hi], predict_object)
+            partner = second.get_runtime().engine.rank_energies_device()
+            top[lo:hi], scores[lo:hi] = model.device_topk_mixed(model.test_graph, queries[lo:hi], predict_object, args.k,
+                                                                partner, weight, chunk_ptr, chunk_idx)
+    else:
+        top, energies = model.device_topk(model.test_graph, queries, predict_object, args.k, ptr, idx)
+        scores = sigmoid_f32(energies)
 
     sink = open(args.out, "w") if args.out else (out or sys.stdout)
     try:

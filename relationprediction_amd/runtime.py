@@ -323,6 +323,25 @@ class EncoderRuntime(object):
             self._rank_reserved = chunk
         return self.engine.topk(queries, predict_object, k, exclude_ptr, exclude_idx)
 
+    def score_queries(self, queries, predict_object, chunk=2048):
+        """The energies of every entity for each query, left in the engine's score buffer (rgcn_score_queries_device):
+        what another runtime's topk_mixed reads through engine.rank_energies_device(); N <= chunk."""
+        self.forward('test')
+        if self._rank_reserved < chunk:
+            self.engine.rank_reserve(chunk)
+            self._rank_reserved = chunk
+        self.engine.score_queries(queries, predict_object)
+
+    def topk_mixed(self, queries, predict_object, k, partner, weight, exclude_ptr=None, exclude_idx=None, chunk=2048):
+        """topk() on weight * own score + (1 - weight) * partner score (rgcn_topk_mixed_device): (entity ids int32 [N,k],
+        mixed scores float32 [N,k]); partner: the other model's [N, V] energies for the same queries, an array or a
+        device address; N <= chunk."""
+        self.forward('test')
+        if self._rank_reserved < chunk:
+            self.engine.rank_reserve(chunk)
+            self._rank_reserved = chunk
+        return self.engine.topk_mixed(queries, predict_object, k, partner, weight, exclude_ptr, exclude_idx)
+
     def backward(self, dcodes):
         if self._state is None or self._state[1] != 'train':
             raise RuntimeError("backward() needs a train-mode forward pass on the current graph")

@@ -19,7 +19,9 @@ extern "C" {
 /* ---- the dense contractions on their own (GPU parity tests of the GEMM kernels, tools/gemm_*.py) ---- */
 /* C[M,N] = op(A) . op(B) through the library's fp32-MFMA GEMM.  trans_a == 0: A is [M,K] row-major,
  * else A is [K,M] row-major (used transposed); trans_b == 0: B is [K,N], else [N,K].
- * split_k == 0 picks the split the encoder would use; > 1 forces that many K slabs. */
+ * split_k == 0 picks the split the encoder would use (and falls back to none when its slabs do not fit the context's
+ * slab); > 1 forces that many K slabs (as many as K has k-tiles for), and is RGCN_ERR_INVALID when slabs * M * N floats
+ * do not fit: an explicit split is never lowered. */
 rgcn_status rgcn_debug_gemm(rgcn_ctx* ctx, int32_t trans_a, int32_t trans_b, int32_t M, int32_t N,
                             int32_t K, int32_t split_k, const float* a_host, const float* b_host,
                             float* c_host);
@@ -47,6 +49,39 @@ rgcn_status rgcn_debug_gemm_presplit(rgcn_ctx* ctx, int32_t trans_b, int32_t M, 
 rgcn_status rgcn_debug_gemm_prologue(rgcn_ctx* ctx, int32_t wide, int32_t prologue, int32_t M, int32_t N, int32_t K,
                                      int32_t lda, int32_t row_limit, const float* a_host, const float* bias_host,
                                      const float* b_host, float* a_out_host, float* c_host);
+
+/* Any call the dense contractions take (csrc/gemm_plan.h GemmCall / GemmBatch), one launch, and the plan it obeyed.
+ * tests/test_gpu_gemm_launch_grid.py runs every launch form through it and asserts which cell of the plan it reached. */
+typedef struct rgcn_debug_gemm_desc {
+  int32_t a_kc, b_kc;                 /* A stored [m][k] (else [k][m]); B stored [n][k] (else [k][n]) */
+  int32_t M, N, K;
+  int32_t lda, ldb, ldc;              /* >= the contiguous extent of the operand */
+  int32_t split_k;                    /* as GemmCall::split_k: <= 1 no split, > 1 that many slices of K (never lowered) */
+  int32_t groups;                     /* >= 1 */
+  int64_t strideA, strideB, strideC;  /* floats between consecutive groups' operands */
+  const int32_t* limit;               /* host, (groups - 1) * limit_stride + 1 entries, or NULL: extent of group g at
+                                       * limit[g * limit_stride], 0 .. M (rows) resp. 0 .. K (limit_on_k) */
+  int32_t limit_stride, limit_on_k;
+  int32_t presplit_b;                 /* != 0: B also comes pre-split, one fragment table per group (GemmBatch::bfrag) */
+  int32_t wide, w8_knob;              /* GemmBatch::wide and gemm_plan's knob argument, as given */
+  int32_t a_offset, b_offset, c_offset;   /* 0 .. 3 floats added to the 16-byte-aligned device base of A, B, C */
+  int64_t a_floats, b_floats, c_floats;   /* sizes of the host buffers: at least (groups - 1) * stride + rows * ld */
+} rgcn_debug_gemm_desc;
+
+typedef struct rgcn_debug_gemm_plan {
+  int32_t kernel;                     /* GemmKernel: 0 none, 1 f32, 2 staged, 3 presplit, 4 w8 */
+  int32_t terms, vec, vecC, table, prologue, swizzle;
+  int32_t splits, k_per_split, slabs, ldc;
+  int32_t tiles_m, tiles_n, grid_x, grid_y;
+} rgcn_debug_gemm_plan;
+
+/* a_host, b_host: the whole strided extent of the operands.  c_host (in and out) is copied to the device before the
+ * launch and back after it: what the launch leaves untouched keeps the caller's values.  *plan: what gemm_plan answered
+ * (filled before anything is launched, also when the call fails).  A split whose slabs (groups * splits * M * N floats) do
+ * not fit the context's slab is RGCN_ERR_INVALID, the message naming both numbers; an extent on K that is no multiple of
+ * 4 together with 16-byte loads of a k-contiguous operand likewise; what gemm_plan refuses is RGCN_ERR_UNSUPPORTED. */
+rgcn_status rgcn_debug_gemm_call(rgcn_ctx* ctx, const rgcn_debug_gemm_desc* desc, const float* a_host,
+                                 const float* b_host, float* c_host, rgcn_debug_gemm_plan* plan);
 
 /* ---- placement self-check ---- */
 /* out_host[b] = the XCD (HW_REG_XCC_ID) workgroup b of a plain 1-D launch of n_blocks workgroups ran on.  The

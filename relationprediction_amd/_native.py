@@ -168,7 +168,32 @@ _DEVTOOLS_SIGS = {
                                          C.c_int32, _P, _P, C.POINTER(C.c_float)]),
     "rgcn_debug_gemm_prologue": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_int32, _P, _P, _P, _P, _P]),
+    "rgcn_debug_gemm_call": (C.c_int32, [_P, _P, _P, _P, _P, _P]),
 }
+
+
+class DebugGemmDesc(C.Structure):
+    """rgcn_debug_gemm_desc of include/rgcn_devtools.h"""
+    _fields_ = [("a_kc", C.c_int32), ("b_kc", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+                ("lda", C.c_int32), ("ldb", C.c_int32), ("ldc", C.c_int32), ("split_k", C.c_int32), ("groups", C.c_int32),
+                ("strideA", C.c_int64), ("strideB", C.c_int64), ("strideC", C.c_int64), ("limit", C.c_void_p),
+                ("limit_stride", C.c_int32), ("limit_on_k", C.c_int32), ("presplit_b", C.c_int32), ("wide", C.c_int32),
+                ("w8_knob", C.c_int32), ("a_offset", C.c_int32), ("b_offset", C.c_int32), ("c_offset", C.c_int32),
+                ("a_floats", C.c_int64), ("b_floats", C.c_int64), ("c_floats", C.c_int64)]
+
+
+GEMM_KERNEL_NAMES = ("none", "f32", "staged", "presplit", "w8")      # GemmKernel of csrc/gemm_plan.h
+
+
+class DebugGemmPlan(C.Structure):
+    """rgcn_debug_gemm_plan of include/rgcn_devtools.h: the plan a rgcn_debug_gemm_call obeyed"""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "terms", "vec", "vecC", "table", "prologue", "swizzle", "splits",
+                                         "k_per_split", "slabs", "ldc", "tiles_m", "tiles_n", "grid_x", "grid_y")]
+
+    def as_dict(self):
+        out = {n: int(getattr(self, n)) for n, _ in self._fields_}
+        out["kernel"] = GEMM_KERNEL_NAMES[out["kernel"]]
+        return out
 _lib_devtools = None
 
 
@@ -942,6 +967,40 @@ class Engine:
         self._check(self.lib.rgcn_debug_gemm_prologue(self.ctx, int(bool(wide)), int(bool(prologue)), M, N, K, lda,
                                                       int(row_limit), _ptr(a), _ptr(bias), _ptr(b), _ptr(out_a), _ptr(out)))
         return out, out_a
+
+    def debug_gemm_call(self, a, b, c, M, N, K, a_kc=True, b_kc=False, lda=None, ldb=None, ldc=None, split_k=1, groups=1,
+                        strideA=0, strideB=0, strideC=0, limit=None, limit_stride=1, limit_on_k=False, presplit_b=False,
+                        wide=0, w8_knob=1, a_offset=0, b_offset=0, c_offset=0):
+        """One launch of the dense contractions as csrc/gemm_plan.h describes a call (devtools build; include/
+        rgcn_devtools.h rgcn_debug_gemm_call).  a, b, c: flat float32 buffers holding the whole strided extent of the
+        operands; c is what the device copy of C holds before the launch.  Returns (C after the launch, flat, and the plan
+        the call obeyed as a dict).  Nothing is adjusted on the way: what does not fit or is refused raises RgcnError."""
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+        out = np.array(c, dtype=np.float32, order="C", copy=True).reshape(-1)
+        d = DebugGemmDesc()
+        d.a_kc, d.b_kc, d.M, d.N, d.K = int(bool(a_kc)), int(bool(b_kc)), int(M), int(N), int(K)
+        d.lda = int(lda if lda is not None else (K if a_kc else M))
+        d.ldb = int(ldb if ldb is not None else (K if b_kc else N))
+        d.ldc = int(ldc if ldc is not None else N)
+        d.split_k, d.groups = int(split_k), int(groups)
+        d.strideA, d.strideB, d.strideC = int(strideA), int(strideB), int(strideC)
+        lim = None
+        if limit is not None:
+            lim = np.ascontiguousarray(limit, dtype=np.int32).reshape(-1)
+            assert lim.size == (d.groups - 1) * int(limit_stride) + 1, (lim.size, d.groups, limit_stride)
+            d.limit = lim.ctypes.data
+        d.limit_stride, d.limit_on_k = int(limit_stride), int(bool(limit_on_k))
+        d.presplit_b, d.wide, d.w8_knob = int(bool(presplit_b)), int(wide), int(w8_knob)
+        d.a_offset, d.b_offset, d.c_offset = int(a_offset), int(b_offset), int(c_offset)
+        d.a_floats, d.b_floats, d.c_floats = a.size, b.size, out.size
+        plan = DebugGemmPlan()
+        try:
+            self._check(self.lib.rgcn_debug_gemm_call(self.ctx, C.byref(d), _ptr(a), _ptr(b), _ptr(out), C.byref(plan)))
+        except RgcnError as e:
+            e.plan = plan.as_dict()
+            raise
+        return out, plan.as_dict()
 
     def debug_xcd_map(self, n_blocks):
         """XCD of every workgroup of a plain 1-D launch (devtools build)"""

@@ -401,9 +401,11 @@ __global__ void __launch_bounds__(NTH, 2) k_gemm_bf16x3(XArgs g) {
       constexpr int m = decltype(mi)::value;
       constexpr int t = NP - TERMS + m / 4, i = (m / 2) % 2, j = m % 2;
       acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][pa_[t]], fb[j][pb_[t]], acc[i][j], 0, 0, 0);
-      // (B_PRE: the twelve chunks of A behind every other MFMA, as far apart as before)
-      constexpr int c0 = B_PRE ? (m % 2 == 0 ? m / 2 : 12) : (m * PER < 24 ? m * PER : 24);
-      constexpr int c1 = B_PRE ? (m % 2 == 0 ? (m / 2 + 1 < 12 ? m / 2 + 1 : 12) : 12) : ((m + 1) * PER < 24 ? (m + 1) * PER : 24);
+      // (B_PRE: the twelve chunks of A behind every other MFMA, as far apart as before -- behind every one of the twelve
+      // MFMAs of TERMS = 3, which otherwise staged only half of the next A tile)
+      constexpr int EVERY = NM >= 24 ? 2 : 1;
+      constexpr int c0 = B_PRE ? (m % EVERY == 0 ? m / EVERY : 12) : (m * PER < 24 ? m * PER : 24);
+      constexpr int c1 = B_PRE ? (m % EVERY == 0 ? (m / EVERY + 1 < 12 ? m / EVERY + 1 : 12) : 12) : ((m + 1) * PER < 24 ? (m + 1) * PER : 24);
       split_chunks<A_KC, PA, (c0 < 12 ? c0 : 12), (c1 < 12 ? c1 : 12)>(ra[1 - P], st, nxt, negmask);
       if constexpr (!B_PRE)
         split_chunks<B_KC, PB, (c0 > 12 ? c0 - 12 : 0), (c1 > 12 ? c1 - 12 : 0)>(rb[1 - P], st, nxt + TA);

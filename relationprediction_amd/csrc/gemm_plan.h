@@ -20,7 +20,10 @@ struct GemmBatch {
   size_t strideA = 0, strideB = 0, strideC = 0;   // floats between consecutive groups' operands
   const int32_t* limit = nullptr;                 // device, limit[g * limit_stride]: extent of group g (<= M resp. K)
   int limit_stride = 1;
-  int limit_on_k = 0;                             // 0: rows of A / C; 1: depth K
+  int limit_on_k = 0;                             // 0: rows of A / C (never with split_k > 1: gemm_plan refuses); 1: depth K
+  // (an extent on K that is no multiple of 4 needs operands that are NOT k-contiguous, or dword loads: the plan cannot see
+  // the extent, and a 16-byte load of a k-contiguous operand takes its four k all or nothing.  The one call site,
+  // units_product_dw, is the TN form.)
   // optional: B already split into bf16 planes in MFMA fragment order (gemm_presplit_b; a weight, split once per weight
   // update instead of once per tile and step).  Used by the split-arithmetic kernel when A is k-contiguous and there is no
   // split over K; ignored otherwise (B itself must still be passed).  strideBfrag: 16-byte words between groups.
@@ -102,6 +105,10 @@ inline GemmPlan gemm_plan(const GemmCall& q, int gemm_mode, int w8_knob) {
   const char* const no_prologue = "gemm: the A-operand prologue exists in the pre-split-weight NN kernels only";
   const bool nn = q.a_kc && !q.b_kc;
   if (b.a_bias != nullptr && (gemm_mode == 0 || !nn || q.split_k > 1)) return refuse(no_prologue);
+  // (tiles beyond a row extent leave without writing their slab, and the reduce sums whole slabs: rows beyond the extent
+  // would receive what an earlier call left there)
+  if (b.limit != nullptr && !b.limit_on_k && q.split_k > 1)
+    return refuse("gemm: a row limit cannot be combined with a split over K");
   p.a_kc = q.a_kc; p.b_kc = q.b_kc;
   p.terms = gemm_mode == 0 ? 0 : gemm_mode == 9 ? 9 : gemm_mode == 3 ? 3 : 6;
   // (the NN product with a pre-split weight fetches B from its fragment table and never loads B itself: B's own alignment
@@ -118,7 +125,9 @@ inline GemmPlan gemm_plan(const GemmCall& q, int gemm_mode, int w8_knob) {
   p.splits = q.K > 0 ? (q.K + kps - 1) / kps : 1;
   p.slabs = p.splits > 1;
   p.ldc = p.slabs ? q.N : q.ldc;
-  p.vecC = ((reinterpret_cast<uintptr_t>(p.slabs ? q.slab : q.C) & 15u) == 0 && p.ldc % 4 == 0 && q.N % 4 == 0) ? 1 : 0;
+  // (every group's product starts 16-byte aligned: slabs lie splits * M * N floats apart, a multiple of 4 with N)
+  p.vecC = ((reinterpret_cast<uintptr_t>(p.slabs ? q.slab : q.C) & 15u) == 0 && p.ldc % 4 == 0 && q.N % 4 == 0 &&
+            (p.slabs || b.groups <= 1 || b.strideC % 4 == 0)) ? 1 : 0;
   p.kernel = GEMM_F32;
   int bn = kGemmBN;
   if (gemm_mode != 0) {

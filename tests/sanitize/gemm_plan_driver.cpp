@@ -116,6 +116,17 @@ int main() {
     show("groups_row_limit", q);
     q.batch.strideA += 1;
     show("groups_row_limit_strideA_odd", q);
+    q.batch.strideA -= 1;
+    q.batch.strideC += 1;      // the second group's product is not 16-byte aligned
+    show("groups_row_limit_strideC_odd", q);
+  }
+  // a row limit and a split over K: refused (the reduce sums whole slabs); an extent on K splits as before
+  {
+    GemmCall q = call(false, false, 500, 500, 14541, 8);
+    q.batch.limit = lim;
+    show("row_limit_split8", q);
+    q.batch.limit_on_k = 1;
+    show("limit_on_k_split8", q);
   }
   {
     GemmCall q = table(call(true, false, 256, 128, 500), 1);

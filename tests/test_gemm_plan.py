@@ -70,6 +70,11 @@ EXPECTED = {
     # a device-side row limit: swizzle 2, ceil(9 / 8) * 8 row panels x the column tiles; a wide request stays wide
     "groups_row_limit": "w8<1,0> terms=6 vec=1 table=1 pro=0 swz=2 splits=1 kps=512 slabs=0 ldc=500 vecC=1 tiles=9x2 grid=32",
     "groups_row_limit_strideA_odd": "staged<1,0> terms=6 vec=0 table=0 pro=0 swz=2 splits=1 kps=512 slabs=0 ldc=500 vecC=1 tiles=9x4 grid=64",
+    # groups whose products lie an odd number of floats apart: no 16-byte stores
+    "groups_row_limit_strideC_odd": "w8<1,0> terms=6 vec=1 table=1 pro=0 swz=2 splits=1 kps=512 slabs=0 ldc=500 vecC=0 tiles=9x2 grid=32",
+    # a row limit with a split over K is refused: tiles beyond the extent write no slab, and the reduce sums whole slabs
+    "row_limit_split8": "refused: gemm: a row limit cannot be combined with a split over K",
+    "limit_on_k_split8": "staged<0,0> terms=6 vec=1 table=0 pro=0 swz=1 splits=8 kps=1824 slabs=1 ldc=500 vecC=1 tiles=4x4 grid=128",
     # a limit on K never reaches the eight-wavefront kernel (it reads the limit as a row limit)
     "limit_on_k_knob3": "presplit<1,0> terms=6 vec=1 table=1 pro=0 swz=1 splits=1 kps=512 slabs=0 ldc=128 vecC=1 tiles=2x1 grid=2",
 }

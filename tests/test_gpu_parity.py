@@ -89,12 +89,18 @@ GEMM_SHAPES = [
 @pytest.mark.parametrize("mode", [6, 9, 0])
 def test_gemm_forms(native, M, N, K, form, mode):
     """Every storage form on every arithmetic (include/rgcn.h rgcn_set_gemm_mode): 6 / 9 = exact bf16
-    operand split on the bf16 matrix cores, 0 = fp32 MFMA.  Same tolerance for all three."""
+    operand split on the bf16 matrix cores, 0 = fp32 MFMA.  Same tolerance for all three.  TN also with a split over K in
+    three: the engine's slab (64 d^2 floats) is sized to hold the three slabs -- an explicit split that does not fit is an
+    error, never lowered -- and the plan the call obeyed says how many slices ran: 3 wherever K has three k-tiles."""
     rng = np.random.RandomState(M * 7 + N * 3 + K)
     A = rng.randn(M, K).astype(np.float32)
     B = rng.randn(K, N).astype(np.float32)
     ref = A.astype(np.float64) @ B.astype(np.float64)
-    eng = native.Engine(16, 2, 8, 1, "block", 2, max_edges=4, devtools=True)   # rgcn_debug_gemm: devtools build only
+    d = 8
+    if form == "TN":
+        while 64 * d * d < 3 * M * N:
+            d += 8
+    eng = native.Engine(16, 2, d, 1, "block", d // 4, max_edges=4, devtools=True)   # rgcn_debug_gemm: devtools build only
     try:
         eng.set_gemm_mode(mode)
         if form == "NN":
@@ -102,9 +108,13 @@ def test_gemm_forms(native, M, N, K, form, mode):
         elif form == "NT":
             got = eng.debug_gemm(A, np.ascontiguousarray(B.T), trans_b=True)
         else:
-            got = eng.debug_gemm(np.ascontiguousarray(A.T), B, trans_a=True)
-            got2 = eng.debug_gemm(np.ascontiguousarray(A.T), B, trans_a=True, split_k=3)
+            At = np.ascontiguousarray(A.T)
+            got = eng.debug_gemm(At, B, trans_a=True)
+            got2 = eng.debug_gemm(At, B, trans_a=True, split_k=3)
             assert_close(got2, ref, rel=1e-5, spike=1e-5, name="TN split 3")
+            got3, plan = eng.debug_gemm_call(At, B, np.zeros((M, N), np.float32), M, N, K, a_kc=False, b_kc=False, split_k=3)
+            assert plan["splits"] == (3 if K >= 33 else 1) and plan["slabs"] == (1 if K >= 33 else 0), plan
+            np.testing.assert_array_equal(got3.reshape(M, N), got2)      # the same call: rgcn_debug_gemm did not lower the split
     finally:
         eng.close()
     # asymmetric random operands: a swapped row/col mapping cannot pass

@@ -18,34 +18,11 @@
 //     dH[u]     += sum_{m: src_m = u} n_m sum_b C[rel_m,b] dZ[(dst_m,dir),b,:]      (source-major gather,
 //                  fused with the self-loop gradient add, relu' and the dropout-scaled copy).
 #include "rgcn_internal.h"
+#include "row_walk.h"
 
 namespace rgcn {
 
 namespace {
-
-constexpr int BT = 8;   // basis functions handled per launch (register budget); B > 8 loops on the host
-
-template <int VEC>
-__device__ __forceinline__ void vload(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = *p;
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void vstore(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else *p = v[0];
-}
-
-__device__ __forceinline__ float drop_scale(const DropSpec& ds, size_t idx) { return drop_factor(ds, idx); }
-
-constexpr int kRowThreads = 1024;
-// leading workgroups of a row launch that walk the long-row list: 64 at minibatch scale, 512 at full-graph scale (the
-// 272,115-edge training graph has 5,000+ long rows and a 2,397-slot hub)
-inline int long_blocks(const rgcn_ctx* c) { return 2 * c->g.E > 65536 ? 512 : 64; }
 
 struct AggArgs {
   const float* Hin;          // [V,d]
@@ -109,80 +86,33 @@ __device__ __forceinline__ void agg_range(const AggArgs& a, int s0, int s1, int 
   }
 }
 
-// Workgroups [0, n_long_blocks): one LONG row at a time, 8 slot-lanes x 128 column lanes, partial sums
-// combined through LDS in a fixed order.  The others: TPR lanes per destination row, 1024/TPR rows per
-// workgroup.  Forward-direction messages (rel < R) feed the first B column blocks, backward the last B.
+// The banked row walk (row_walk.h) over the destination rows.  Forward-direction messages (rel < R) feed the first B
+// column blocks, backward the last B; a (row, direction) without a unit stores nothing.
+struct AggRow {
+  float* z[2];               // the row's unit rows of the two directions, at basis b0
+  bool has[2];
+};
+
 template <int VEC, int TPR>
 __global__ void __launch_bounds__(kRowThreads) k_basis_agg(AggArgs a, int n_long_blocks) {
-  const int nvec = a.d / VEC;
   const size_t zstride = (size_t)a.B * a.d;
-  if ((int)blockIdx.x < n_long_blocks) {
-    __shared__ float red[8][128 * VEC];
-    const int cl = threadIdx.x & 127, sl = threadIdx.x >> 7;
-    const int n = *a.nlong;
-    for (int lb = blockIdx.x; lb < n; lb += n_long_blocks) {
-      const int v = a.long_rows[lb];
-      const int beg = a.row_ptr[v], end = a.row_ptr[v + 1];
-      for (int c0 = 0; c0 < nvec; c0 += 128) {
-        const int cidx = c0 + cl;
-        float accf[BT][VEC], accb[BT][VEC];
-#pragma unroll
-        for (int b = 0; b < BT; ++b)
-#pragma unroll
-          for (int k = 0; k < VEC; ++k) { accf[b][k] = 0.f; accb[b][k] = 0.f; }
-        if (cidx < nvec) agg_range<VEC>(a, beg + sl, end, 8, cidx, accf, accb);
-#pragma unroll
-        for (int q = 0; q < 2 * BT; ++q) {
-          const int b = q % BT;
-          if (b < a.nbt) {
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) red[sl][cl * VEC + k] = q < BT ? accf[b][k] : accb[b][k];
-            __syncthreads();
-            if (sl == 0 && cidx < nvec) {
-              float t[VEC];
-#pragma unroll
-              for (int k = 0; k < VEC; ++k) {
-                float u = red[0][cl * VEC + k];
-#pragma unroll
-                for (int w = 1; w < 8; ++w) u += red[w][cl * VEC + k];
-                t[k] = u;
-              }
-              const int dir = q < BT ? 0 : 1;
-              const int32_t* up = a.unit_ptr + (size_t)dir * (a.V + 1) + v;
-              const int u = up[0];
-              if (up[1] > u)
-                vstore<VEC>(a.Z + ((size_t)dir * a.V + u) * zstride + (size_t)(a.b0 + b) * a.d + (size_t)cidx * VEC, t);
-            }
-            __syncthreads();
-          }
-        }
-      }
-    }
-    return;
-  }
-  const int v = ((int)blockIdx.x - n_long_blocks) * (kRowThreads / TPR) + threadIdx.x / TPR;
-  if (v >= a.V) return;
-  const int lane = threadIdx.x % TPR;
-  const int beg = a.row_ptr[v], end = a.row_ptr[v + 1];
-  if (end == beg || end - beg > kLongRow) return;      // no unit at all / a long-row workgroup of this launch owns it
-  const int uf = a.unit_ptr[v], ub = a.unit_ptr[(size_t)a.V + 1 + v];
-  const bool has_f = a.unit_ptr[v + 1] > uf, has_b = a.unit_ptr[(size_t)a.V + 2 + v] > ub;
-  float* zf = a.Z + (size_t)uf * zstride + (size_t)a.b0 * a.d;
-  float* zb = a.Z + ((size_t)a.V + ub) * zstride + (size_t)a.b0 * a.d;
-  for (int cidx = lane; cidx < nvec; cidx += TPR) {
-    float accf[BT][VEC], accb[BT][VEC];
-#pragma unroll
-    for (int b = 0; b < BT; ++b)
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) { accf[b][k] = 0.f; accb[b][k] = 0.f; }
-    agg_range<VEC>(a, beg, end, 1, cidx, accf, accb);
-#pragma unroll
-    for (int b = 0; b < BT; ++b)
-      if (b < a.nbt) {
-        if (has_f) vstore<VEC>(zf + (size_t)b * a.d + (size_t)cidx * VEC, accf[b]);
-        if (has_b) vstore<VEC>(zb + (size_t)b * a.d + (size_t)cidx * VEC, accb[b]);
-      }
-  }
+  row_walk_banked<VEC, TPR, AggRow>(
+      a.row_ptr, a.long_rows, a.nlong, a.V, a.d / VEC, a.nbt, n_long_blocks,
+      [&a, zstride](int v, int beg, int end, AggRow& r) {
+        if (end == beg) return false;      // no unit at all
+        const int uf = a.unit_ptr[v], ub = a.unit_ptr[(size_t)a.V + 1 + v];
+        r.has[0] = a.unit_ptr[v + 1] > uf;
+        r.has[1] = a.unit_ptr[(size_t)a.V + 2 + v] > ub;
+        r.z[0] = a.Z + (size_t)uf * zstride + (size_t)a.b0 * a.d;
+        r.z[1] = a.Z + ((size_t)a.V + ub) * zstride + (size_t)a.b0 * a.d;
+        return true;
+      },
+      [&a](int s0, int s1, int step, int cidx, float (&accf)[BT][VEC], float (&accb)[BT][VEC]) {
+        agg_range<VEC>(a, s0, s1, step, cidx, accf, accb);
+      },
+      [&a](const AggRow& r, int dir, int b, int cidx, const float (&t)[VEC]) {
+        if (r.has[dir]) vstore<VEC>(r.z[dir] + (size_t)b * a.d + (size_t)cidx * VEC, t);
+      });
 }
 
 // Dc[dir][i][:] = D[unit_rows[dir][i]][:] for the units of both directions: the row operand of dZ = D.W'^T and the
@@ -264,62 +194,20 @@ __device__ __forceinline__ void gather_epilogue(const BwdGatherArgs& a, int v, s
   if (a.c.out2 != nullptr) {
     float o2[VEC];
 #pragma unroll
-    for (int k = 0; k < VEC; ++k) o2[k] = acc[k] * drop_scale(a.c.drop2, off + k);
+    for (int k = 0; k < VEC; ++k) o2[k] = acc[k] * drop_factor(a.c.drop2, off + k);
     vstore<VEC>(a.c.out2 + off, o2);
   }
 }
 
+// The single-accumulator row walk (row_walk.h) over the source rows; without a relational part (row_ptr == nullptr,
+// no long-row workgroups) every row is its epilogue alone.
 template <int VEC, int TPR>
 __global__ void __launch_bounds__(kRowThreads) k_basis_bwd_gather(BwdGatherArgs a, int n_long_blocks) {
   const int d = a.c.d;
-  const int nvec = d / VEC;
-  if ((int)blockIdx.x < n_long_blocks) {
-    __shared__ float red[8][128 * VEC];
-    const int cl = threadIdx.x & 127, sl = threadIdx.x >> 7;
-    const int n = *a.nlong;
-    for (int lb = blockIdx.x; lb < n; lb += n_long_blocks) {
-      const int v = a.long_rows[lb];
-      const int beg = a.row_ptr[v], end = a.row_ptr[v + 1];
-      for (int c0 = 0; c0 < nvec; c0 += 128) {
-        const int cidx = c0 + cl;
-        float acc[VEC];
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
-        if (cidx < nvec) gather_range<VEC>(a, beg + sl, end, 8, d, cidx, acc);
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) red[sl][cl * VEC + k] = acc[k];
-        __syncthreads();
-        if (sl == 0 && cidx < nvec) {
-#pragma unroll
-          for (int k = 0; k < VEC; ++k) {
-            float u = red[0][cl * VEC + k];
-#pragma unroll
-            for (int w = 1; w < 8; ++w) u += red[w][cl * VEC + k];
-            acc[k] = u;
-          }
-          gather_epilogue<VEC>(a, v, (size_t)v * d + (size_t)cidx * VEC, acc);
-        }
-        __syncthreads();
-      }
-    }
-    return;
-  }
-  const int v = ((int)blockIdx.x - n_long_blocks) * (kRowThreads / TPR) + threadIdx.x / TPR;
-  if (v >= a.c.V) return;
-  const int lane = threadIdx.x % TPR;
-  int beg = 0, end = 0;
-  if (a.row_ptr != nullptr) {
-    beg = a.row_ptr[v];
-    end = a.row_ptr[v + 1];
-    if (end - beg > kLongRow) return;
-  }
-  for (int cidx = lane; cidx < nvec; cidx += TPR) {
-    float acc[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
-    gather_range<VEC>(a, beg, end, 1, d, cidx, acc);
-    gather_epilogue<VEC>(a, v, (size_t)v * d + (size_t)cidx * VEC, acc);
-  }
+  row_walk<VEC, TPR, true>(
+      a.row_ptr, a.long_rows, a.nlong, a.c.V, d / VEC, n_long_blocks,
+      [&a, d](int s0, int s1, int step, int cidx, float (&acc)[VEC]) { gather_range<VEC>(a, s0, s1, step, d, cidx, acc); },
+      [&a, d](int v, int cidx, float (&acc)[VEC]) { gather_epilogue<VEC>(a, v, (size_t)v * d + (size_t)cidx * VEC, acc); });
 }
 
 struct DcoefArgs {
@@ -335,15 +223,6 @@ struct DcoefArgs {
   float* slab;               // [chunks][B]
   int32_t R, B, d, chunk;
 };
-
-__device__ __forceinline__ int find_segment(const int32_t* __restrict__ ptr, int n_seg, int x) {
-  int lo = 0, hi = n_seg;
-  while (hi - lo > 1) {
-    int mid = (lo + hi) >> 1;
-    if (ptr[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 
 // One workgroup (4 waves) per relation chunk; wave w takes messages beg+w, beg+w+4, ...; the wave's
 // lanes split the d features, reduce the B dot products by shuffles, partial sums meet in LDS.
@@ -428,8 +307,6 @@ __global__ void k_basis_transpose(const float* __restrict__ in, float* __restric
   if (to_device) out[i] = in[h]; else out[h] = in[i];
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 // Number of (row, direction) units of the current graph, for the profile accounting only (the kernels read the counts
@@ -464,10 +341,9 @@ rgcn_status basis_aggregate_forward(rgcn_ctx* c, int layer, const float* Hin, fl
   a.V = c->V; a.d = c->d; a.B = c->B; a.R = c->R;
   const bool vec4 = (c->d % 4 == 0) && aligned16(Hin) && aligned16(Z);
   const int nvec = vec4 ? c->d / 4 : c->d;
-  const int tpr = nvec <= 64 ? 64 : (nvec <= 128 ? 128 : 256);
-  const int rpb = kRowThreads / tpr;
+  const int tpr = row_lanes(nvec);
   const int nlb = long_blocks(c);
-  dim3 grid(nlb + (c->V + rpb - 1) / rpb), block(kRowThreads);
+  dim3 grid = row_grid(nlb, c->V, tpr), block(kRowThreads);
   const double M = 2.0 * c->g.E / c->world;
   for (int b0 = 0; b0 < c->B; b0 += BT) {
     a.b0 = b0;
@@ -476,14 +352,7 @@ rgcn_status basis_aggregate_forward(rgcn_ctx* c, int layer, const float* Hin, fl
     const double units = basis_units(c);
     ProfScope ps(c, "basis_aggregate", 4.0 * c->d * (M + a.nbt * units) + 20.0 * M, 4.0 * M * a.nbt * c->d,
                  4.0 * c->d * (rows + a.nbt * units) + 20.0 * M);
-#define RGCN_LAUNCH_AGG(VEC, TPR) \
-  hipLaunchKernelGGL((k_basis_agg<VEC, TPR>), grid, block, 0, c->stream, a, nlb)
-    if (vec4) {
-      if (tpr == 64) RGCN_LAUNCH_AGG(4, 64); else if (tpr == 128) RGCN_LAUNCH_AGG(4, 128); else RGCN_LAUNCH_AGG(4, 256);
-    } else {
-      if (tpr == 64) RGCN_LAUNCH_AGG(1, 64); else if (tpr == 128) RGCN_LAUNCH_AGG(1, 128); else RGCN_LAUNCH_AGG(1, 256);
-    }
-#undef RGCN_LAUNCH_AGG
+    RGCN_LAUNCH_ROWS(k_basis_agg, vec4, tpr, grid, block, c->stream, a, nlb);
     RGCN_HIP(c, hipGetLastError());
   }
   return RGCN_OK;
@@ -501,23 +370,15 @@ rgcn_status basis_backward_gather(rgcn_ctx* c, int layer, const float* dZ, const
   const bool vec4 = (c->d % 4 == 0) && aligned16(dZ) && aligned16(ca.out) && aligned16(ca.base) &&
                     aligned16(ca.gate) && aligned16(ca.out2);
   const int nvec = vec4 ? c->d / 4 : c->d;
-  const int tpr = nvec <= 64 ? 64 : (nvec <= 128 ? 128 : 256);
-  const int rpb = kRowThreads / tpr;
+  const int tpr = row_lanes(nvec);
   const int nlb = with_messages ? long_blocks(c) : 0;
-  dim3 grid(nlb + (c->V + rpb - 1) / rpb), block(kRowThreads);
+  dim3 grid = row_grid(nlb, c->V, tpr), block(kRowThreads);
   const double M = 2.0 * c->g.E / c->world;
   const double units = basis_units(c);
   // compulsory: dZ of every unit once, base / gate / out / out2 once each
   ProfScope ps(c, "basis_bwd_gather", 4.0 * c->d * (M * c->B + 4.0 * c->V) + 20.0 * M, 2.0 * M * c->B * c->d,
                4.0 * c->d * (c->B * units + 4.0 * c->V) + 20.0 * M);
-#define RGCN_LAUNCH_BG(VEC, TPR) \
-  hipLaunchKernelGGL((k_basis_bwd_gather<VEC, TPR>), grid, block, 0, c->stream, a, nlb)
-  if (vec4) {
-    if (tpr == 64) RGCN_LAUNCH_BG(4, 64); else if (tpr == 128) RGCN_LAUNCH_BG(4, 128); else RGCN_LAUNCH_BG(4, 256);
-  } else {
-    if (tpr == 64) RGCN_LAUNCH_BG(1, 64); else if (tpr == 128) RGCN_LAUNCH_BG(1, 128); else RGCN_LAUNCH_BG(1, 256);
-  }
-#undef RGCN_LAUNCH_BG
+  RGCN_LAUNCH_ROWS(k_basis_bwd_gather, vec4, tpr, grid, block, c->stream, a, nlb);
   RGCN_HIP(c, hipGetLastError());
   return RGCN_OK;
 }

@@ -19,31 +19,11 @@
 // form for d % 4 != 0, rows above kLongRow slots by a whole workgroup from the long-row list (the basis kind never cuts
 // giant rows: a workgroup walks a hub of any length, eight slots at a time), no atomics, fixed summation order.
 #include "rgcn_internal.h"
+#include "row_walk.h"
 
 namespace rgcn {
 
 namespace {
-
-constexpr int BT = 8;   // basis functions per launch of the table-gradient kernel (register budget); B > 8 loops on the host
-
-template <int VEC>
-__device__ __forceinline__ void vload(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = *p;
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void vstore(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else *p = v[0];
-}
-
-constexpr int kRowThreads = 1024;
-inline int long_blocks(const rgcn_ctx* c) { return 2 * c->g.E > 65536 ? 512 : 64; }
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // ---------------------------------------------------------------- forward
 struct OnehotFwdArgs {
@@ -99,55 +79,14 @@ __device__ __forceinline__ void lookup_epilogue(const OnehotFwdArgs& a, const Dr
   vstore<VEC>(a.out + off, acc);
 }
 
-// Workgroups [0, n_long_blocks): one LONG row at a time, 8 slot-lanes x 128 column lanes, partial sums combined through
-// LDS in a fixed order.  The others: TPR lanes per destination row, 1024 / TPR rows per workgroup.
+// the single-accumulator row walk (row_walk.h) over the destination rows
 template <int VEC, int TPR>
 __global__ void __launch_bounds__(kRowThreads) k_onehot_fwd(OnehotFwdArgs a, int n_long_blocks) {
-  const int nvec = a.d / VEC;
   const DropKey key = drop_key(a.drop);
-  if ((int)blockIdx.x < n_long_blocks) {
-    __shared__ float red[8][128 * VEC];
-    const int cl = threadIdx.x & 127, sl = threadIdx.x >> 7;
-    const int n = *a.nlong;
-    for (int lb = blockIdx.x; lb < n; lb += n_long_blocks) {
-      const int v = a.long_rows[lb];
-      const int beg = a.row_ptr[v], end = a.row_ptr[v + 1];
-      for (int c0 = 0; c0 < nvec; c0 += 128) {
-        const int cidx = c0 + cl;
-        float acc[VEC];
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
-        if (cidx < nvec) lookup_range<VEC>(a, beg + sl, end, 8, cidx, acc);
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) red[sl][cl * VEC + k] = acc[k];
-        __syncthreads();
-        if (sl == 0 && cidx < nvec) {
-#pragma unroll
-          for (int k = 0; k < VEC; ++k) {
-            float u = red[0][cl * VEC + k];
-#pragma unroll
-            for (int w = 1; w < 8; ++w) u += red[w][cl * VEC + k];
-            acc[k] = u;
-          }
-          lookup_epilogue<VEC>(a, key, (size_t)v * a.d + (size_t)cidx * VEC, acc);
-        }
-        __syncthreads();
-      }
-    }
-    return;
-  }
-  const int v = ((int)blockIdx.x - n_long_blocks) * (kRowThreads / TPR) + threadIdx.x / TPR;
-  if (v >= a.V) return;
-  const int lane = threadIdx.x % TPR;
-  const int beg = a.row_ptr[v], end = a.row_ptr[v + 1];
-  if (end - beg > kLongRow) return;      // a long-row workgroup of this launch owns it
-  for (int cidx = lane; cidx < nvec; cidx += TPR) {
-    float acc[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
-    lookup_range<VEC>(a, beg, end, 1, cidx, acc);
-    lookup_epilogue<VEC>(a, key, (size_t)v * a.d + (size_t)cidx * VEC, acc);
-  }
+  row_walk<VEC, TPR>(
+      a.row_ptr, a.long_rows, a.nlong, a.V, a.d / VEC, n_long_blocks,
+      [&a](int s0, int s1, int step, int cidx, float (&acc)[VEC]) { lookup_range<VEC>(a, s0, s1, step, cidx, acc); },
+      [&a, &key](int v, int cidx, float (&acc)[VEC]) { lookup_epilogue<VEC>(a, key, (size_t)v * a.d + (size_t)cidx * VEC, acc); });
 }
 
 // ---------------------------------------------------------------- table gradients
@@ -212,7 +151,10 @@ __device__ __forceinline__ void tables_range(const OnehotTablesArgs& a, int s0, 
   }
 }
 
-// Every row u writes its nbt basis rows of BOTH tables (zeros where it sends nothing in that direction).
+// Every row u writes its nbt basis rows of BOTH tables (zeros where it sends nothing in that direction).  The walk is
+// row_walk.h's banked form written out: through the template the float4 variants take 105 VGPRs, not 103, which at 1024
+// threads is 112 per wave, not 104, and leaves no room on a SIMD for a wave of k_onehot_dcoef (67 VGPRs), which runs
+// beside this kernel on side stream 0 -- measured as 6 % on this kernel and 0.8 % on the one-hot train step.
 template <int VEC, int TPR>
 __global__ void __launch_bounds__(kRowThreads) k_onehot_tables(OnehotTablesArgs a, int n_long_blocks) {
   const int nvec = a.d / VEC;
@@ -242,12 +184,7 @@ __global__ void __launch_bounds__(kRowThreads) k_onehot_tables(OnehotTablesArgs 
             if (sl == 0 && cidx < nvec) {
               float t[VEC];
 #pragma unroll
-              for (int k = 0; k < VEC; ++k) {
-                float r = red[0][cl * VEC + k];
-#pragma unroll
-                for (int w = 1; w < 8; ++w) r += red[w][cl * VEC + k];
-                t[k] = r;
-              }
+              for (int k = 0; k < VEC; ++k) t[k] = lds_sum8<VEC>(red, cl * VEC + k);
               vstore<VEC>(a.G + (q < BT ? 0 : dstride) + (size_t)u * tstride + (size_t)(a.b0 + b) * a.d + (size_t)cidx * VEC, t);
             }
             __syncthreads();
@@ -292,15 +229,6 @@ struct OnehotDcoefArgs {
   float* slab;               // [chunks][B]
   int32_t V, R, B, d, chunk;
 };
-
-__device__ __forceinline__ int find_segment(const int32_t* __restrict__ ptr, int n_seg, int x) {
-  int lo = 0, hi = n_seg;
-  while (hi - lo > 1) {
-    int mid = (lo + hi) >> 1;
-    if (ptr[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 
 // One workgroup (4 waves) per relation chunk; wave w takes messages beg+w, beg+w+4, ...; the wave's lanes split the d
 // features, reduce the B dot products by shuffles, partial sums meet in LDS.
@@ -367,21 +295,14 @@ rgcn_status onehot_forward(rgcn_ctx* c, float* out) {
   a.drop = make_drop(c, 1, true);
   const bool vec4 = (c->d % 4 == 0) && aligned16(a.W) && aligned16(a.wself) && aligned16(out);
   const int nvec = vec4 ? c->d / 4 : c->d;
-  const int tpr = nvec <= 64 ? 64 : (nvec <= 128 ? 128 : 256);
-  const int rpb = kRowThreads / tpr;
+  const int tpr = row_lanes(nvec);
   const int nlb = long_blocks(c);
-  dim3 grid(nlb + (c->V + rpb - 1) / rpb), block(kRowThreads);
+  dim3 grid = row_grid(nlb, c->V, tpr), block(kRowThreads);
   const double M = 2.0 * c->g.E, V = c->V, Bd = (double)c->B * c->d;
   const double senders = M < 2.0 * V ? M : 2.0 * V;      // compulsory: each (sender, direction) table row once
   ProfScope ps(c, "onehot_fwd", 4.0 * Bd * M + 12.0 * M + 8.0 * V * c->d, 2.0 * M * Bd,
                4.0 * Bd * senders + 12.0 * M + 8.0 * V * c->d);
-#define RGCN_LAUNCH_OH(VEC, TPR) hipLaunchKernelGGL((k_onehot_fwd<VEC, TPR>), grid, block, 0, c->stream, a, nlb)
-  if (vec4) {
-    if (tpr == 64) RGCN_LAUNCH_OH(4, 64); else if (tpr == 128) RGCN_LAUNCH_OH(4, 128); else RGCN_LAUNCH_OH(4, 256);
-  } else {
-    if (tpr == 64) RGCN_LAUNCH_OH(1, 64); else if (tpr == 128) RGCN_LAUNCH_OH(1, 128); else RGCN_LAUNCH_OH(1, 256);
-  }
-#undef RGCN_LAUNCH_OH
+  RGCN_LAUNCH_ROWS(k_onehot_fwd, vec4, tpr, grid, block, c->stream, a, nlb);
   RGCN_HIP(c, hipGetLastError());
   return RGCN_OK;
 }
@@ -395,10 +316,9 @@ rgcn_status onehot_backward_tables(rgcn_ctx* c, const float* D) {
   a.V = c->V; a.d = c->d; a.B = c->B; a.R = c->R;
   const bool vec4 = (c->d % 4 == 0) && aligned16(D) && aligned16(a.G);
   const int nvec = vec4 ? c->d / 4 : c->d;
-  const int tpr = nvec <= 64 ? 64 : (nvec <= 128 ? 128 : 256);
-  const int rpb = kRowThreads / tpr;
+  const int tpr = row_lanes(nvec);
   const int nlb = long_blocks(c);
-  dim3 grid(nlb + (c->V + rpb - 1) / rpb), block(kRowThreads);
+  dim3 grid = row_grid(nlb, c->V, tpr), block(kRowThreads);
   const double M = 2.0 * c->g.E, V = c->V;
   const double rows = M < V ? M : V;                     // compulsory: each gathered row of D once
   for (int b0 = 0; b0 < c->B; b0 += BT) {
@@ -407,13 +327,7 @@ rgcn_status onehot_backward_tables(rgcn_ctx* c, const float* D) {
     // the write of both tables' gradient -- 2 V nbt d floats, zeros included -- is the kernel's traffic
     ProfScope ps(c, "onehot_tables_bwd", 4.0 * c->d * (M + 2.0 * V * a.nbt) + 12.0 * M, 2.0 * M * a.nbt * c->d,
                  4.0 * c->d * (rows + 2.0 * V * a.nbt) + 12.0 * M);
-#define RGCN_LAUNCH_OT(VEC, TPR) hipLaunchKernelGGL((k_onehot_tables<VEC, TPR>), grid, block, 0, c->stream, a, nlb)
-    if (vec4) {
-      if (tpr == 64) RGCN_LAUNCH_OT(4, 64); else if (tpr == 128) RGCN_LAUNCH_OT(4, 128); else RGCN_LAUNCH_OT(4, 256);
-    } else {
-      if (tpr == 64) RGCN_LAUNCH_OT(1, 64); else if (tpr == 128) RGCN_LAUNCH_OT(1, 128); else RGCN_LAUNCH_OT(1, 256);
-    }
-#undef RGCN_LAUNCH_OT
+    RGCN_LAUNCH_ROWS(k_onehot_tables, vec4, tpr, grid, block, c->stream, a, nlb);
     RGCN_HIP(c, hipGetLastError());
   }
   return RGCN_OK;

@@ -23,31 +23,13 @@
 //                       * relu'(H), and the dropout-scaled copy
 // No float atomics: every sum has a fixed order, two passes over the same inputs give the same bits.
 #include "rgcn_internal.h"
+#include "row_walk.h"
 
 namespace rgcn {
 
 namespace {
 
-template <int VEC>
-__device__ __forceinline__ void vload(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = *p;
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void vstore(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else *p = v[0];
-}
-
-constexpr int kRowThreads = 1024;
 constexpr int kMixLanes = 128;      // 2 B <= 128 mixing scalars per row (B <= 64: rgcn_create)
-// leading workgroups of a row launch that walk the long-row list (as basis.hip)
-inline int long_blocks(const rgcn_ctx* c) { return 2 * c->g.E > 65536 ? 512 : 64; }
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // ---------------------------------------------------------------- forward: destination-major rows
 struct RowArgs {
@@ -135,9 +117,7 @@ __global__ void __launch_bounds__(kRowThreads) k_pdiag_rows(RowArgs a, int n_lon
       red[sl][cl] = cl < nmix ? mix_range(a, beg + sl, end, 8, cl) : 0.f;
       __syncthreads();
       if (sl == 0 && cl < nmix) {
-        float u = red[0][cl];
-#pragma unroll
-        for (int w = 1; w < 8; ++w) u += red[w][cl];
+        const float u = lds_sum8<VEC>(red, cl);
         mix[cl] = u;
         a.a[((size_t)(cl / a.B) * a.V + v) * a.B + cl % a.B] = u;
       }
@@ -153,12 +133,7 @@ __global__ void __launch_bounds__(kRowThreads) k_pdiag_rows(RowArgs a, int n_lon
         __syncthreads();
         if (sl == 0 && cidx < nvec) {
 #pragma unroll
-          for (int k = 0; k < VEC; ++k) {
-            float u = red[0][cl * VEC + k];
-#pragma unroll
-            for (int w = 1; w < 8; ++w) u += red[w][cl * VEC + k];
-            acc[k] = u;
-          }
+          for (int k = 0; k < VEC; ++k) acc[k] = lds_sum8<VEC>(red, cl * VEC + k);
           row_store<VEC>(a, v, cidx, acc, mix);
         }
         __syncthreads();
@@ -324,15 +299,6 @@ struct RelArgs {
   int32_t V, R, B, d, chunk;
 };
 
-__device__ __forceinline__ int find_segment(const int32_t* __restrict__ ptr, int n_seg, int x) {
-  int lo = 0, hi = n_seg;
-  while (hi - lo > 1) {
-    int mid = (lo + hi) >> 1;
-    if (ptr[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // One workgroup (one wave) per relation chunk; lane b adds the chunk's messages in list order.
 __global__ void __launch_bounds__(64) k_pdiag_dcoef(RelArgs a) {
   const int bid = blockIdx.x;
@@ -447,57 +413,16 @@ __device__ __forceinline__ void join_epilogue(const JoinArgs& a, const DropKey& 
   }
 }
 
+// the single-accumulator row walk (row_walk.h) over the source rows
 template <int VEC, int TPR>
 __global__ void __launch_bounds__(kRowThreads) k_pdiag_dh_join(JoinArgs a, int n_long_blocks) {
-  const int d = a.c.d, nvec = d / VEC;
+  const int d = a.c.d;
   const DropKey key = drop_key(a.c.drop2);
-  if ((int)blockIdx.x < n_long_blocks) {
-    __shared__ float red[8][128 * VEC];
-    const int cl = threadIdx.x & 127, sl = threadIdx.x >> 7;
-    const int n = *a.nlong;
-    for (int lb = blockIdx.x; lb < n; lb += n_long_blocks) {
-      const int v = a.long_rows[lb];
-      const int beg = a.row_ptr[v], end = a.row_ptr[v + 1];
-      for (int c0 = 0; c0 < nvec; c0 += 128) {
-        const int cidx = c0 + cl;
-        float acc[VEC];
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
-        if (cidx < nvec) join_range<VEC>(a, beg + sl, end, 8, cidx, acc);
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) red[sl][cl * VEC + k] = acc[k];
-        __syncthreads();
-        if (sl == 0 && cidx < nvec) {
-#pragma unroll
-          for (int k = 0; k < VEC; ++k) {
-            float u = red[0][cl * VEC + k];
-#pragma unroll
-            for (int w = 1; w < 8; ++w) u += red[w][cl * VEC + k];
-            acc[k] = u;
-          }
-          join_epilogue<VEC>(a, key, (size_t)v * d + (size_t)cidx * VEC, acc);
-        }
-        __syncthreads();
-      }
-    }
-    return;
-  }
-  const int v = ((int)blockIdx.x - n_long_blocks) * (kRowThreads / TPR) + threadIdx.x / TPR;
-  if (v >= a.c.V) return;
-  const int lane = threadIdx.x % TPR;
-  const int beg = a.row_ptr[v], end = a.row_ptr[v + 1];
-  if (end - beg > kLongRow) return;      // a long-row workgroup of this launch owns it
-  for (int cidx = lane; cidx < nvec; cidx += TPR) {
-    float acc[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
-    join_range<VEC>(a, beg, end, 1, cidx, acc);
-    join_epilogue<VEC>(a, key, (size_t)v * d + (size_t)cidx * VEC, acc);
-  }
+  row_walk<VEC, TPR>(
+      a.row_ptr, a.long_rows, a.nlong, a.c.V, d / VEC, n_long_blocks,
+      [&a](int s0, int s1, int step, int cidx, float (&acc)[VEC]) { join_range<VEC>(a, s0, s1, step, cidx, acc); },
+      [&a, &key, d](int v, int cidx, const float (&acc)[VEC]) { join_epilogue<VEC>(a, key, (size_t)v * d + (size_t)cidx * VEC, acc); });
 }
-
-// lanes per row of the two row kernels with a long-row path: 64, 128 or 256 by the number of column vectors
-inline int row_lanes(int nvec) { return nvec <= 64 ? 64 : (nvec <= 128 ? 128 : 256); }
 
 }  // namespace
 
@@ -512,21 +437,14 @@ rgcn_status pdiag_rows_forward(rgcn_ctx* c, int layer, const float* Hin, float* 
   const bool vec4 = (c->d % 4 == 0) && aligned16(Hin) && aligned16(a.dtab) && aligned16(Zc) && aligned16(agg);
   const int nvec = vec4 ? c->d / 4 : c->d;
   const int tpr = row_lanes(nvec);
-  const int rpb = kRowThreads / tpr;
   const int nlb = long_blocks(c);
-  dim3 grid(nlb + (c->V + rpb - 1) / rpb), block(kRowThreads);
+  dim3 grid = row_grid(nlb, c->V, tpr), block(kRowThreads);
   const double M = 2.0 * c->g.E, units = basis_units(c);
   const double rows = M < c->V ? M : (double)c->V;      // compulsory: each gathered row of H once
   ProfScope ps(c, "pdiag_rows_fwd", 4.0 * c->d * (2.0 * M + c->V + c->B * units) + 12.0 * M + 8.0 * c->V * c->B,
                2.0 * M * (c->d + c->B) + c->B * units * c->d,
                4.0 * c->d * (rows + 2.0 * c->R + c->V + c->B * units) + 12.0 * M + 8.0 * c->V * c->B);
-#define RGCN_LAUNCH_PR(VEC, TPR) hipLaunchKernelGGL((k_pdiag_rows<VEC, TPR>), grid, block, 0, c->stream, a, nlb)
-  if (vec4) {
-    if (tpr == 64) RGCN_LAUNCH_PR(4, 64); else if (tpr == 128) RGCN_LAUNCH_PR(4, 128); else RGCN_LAUNCH_PR(4, 256);
-  } else {
-    if (tpr == 64) RGCN_LAUNCH_PR(1, 64); else if (tpr == 128) RGCN_LAUNCH_PR(1, 128); else RGCN_LAUNCH_PR(1, 256);
-  }
-#undef RGCN_LAUNCH_PR
+  RGCN_LAUNCH_ROWS(k_pdiag_rows, vec4, tpr, grid, block, c->stream, a, nlb);
   RGCN_HIP(c, hipGetLastError());
   return RGCN_OK;
 }
@@ -619,20 +537,13 @@ rgcn_status pdiag_dh_join(rgcn_ctx* c, int layer, const float* D, const float* d
                     aligned16(ca.out) && aligned16(ca.gate) && aligned16(ca.out2);
   const int nvec = vec4 ? c->d / 4 : c->d;
   const int tpr = row_lanes(nvec);
-  const int rpb = kRowThreads / tpr;
   const int nlb = long_blocks(c);
-  dim3 grid(nlb + (c->V + rpb - 1) / rpb), block(kRowThreads);
+  dim3 grid = row_grid(nlb, c->V, tpr), block(kRowThreads);
   const double M = 2.0 * c->g.E;
   const double rows = M < c->V ? M : (double)c->V;
   ProfScope ps(c, "pdiag_dh_join", 4.0 * c->d * (2.0 * M + (ca.out2 ? 5.0 : 4.0) * c->V) + 12.0 * M, 3.0 * M * c->d,
                4.0 * c->d * (rows + 2.0 * c->R + (ca.out2 ? 5.0 : 4.0) * c->V) + 12.0 * M);
-#define RGCN_LAUNCH_PJ(VEC, TPR) hipLaunchKernelGGL((k_pdiag_dh_join<VEC, TPR>), grid, block, 0, c->stream, a, nlb)
-  if (vec4) {
-    if (tpr == 64) RGCN_LAUNCH_PJ(4, 64); else if (tpr == 128) RGCN_LAUNCH_PJ(4, 128); else RGCN_LAUNCH_PJ(4, 256);
-  } else {
-    if (tpr == 64) RGCN_LAUNCH_PJ(1, 64); else if (tpr == 128) RGCN_LAUNCH_PJ(1, 128); else RGCN_LAUNCH_PJ(1, 256);
-  }
-#undef RGCN_LAUNCH_PJ
+  RGCN_LAUNCH_ROWS(k_pdiag_dh_join, vec4, tpr, grid, block, c->stream, a, nlb);
   RGCN_HIP(c, hipGetLastError());
   return RGCN_OK;
 }

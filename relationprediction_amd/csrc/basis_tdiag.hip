@@ -16,32 +16,11 @@
 //     dH            = dS . W_self^T + dP_f . W_f^T + dP_b . W_b^T                   GEMMs; k_tdiag_dh_join adds, gates, copies
 // No float atomics: every sum has a fixed order, two passes over the same inputs give the same bits.
 #include "rgcn_internal.h"
+#include "row_walk.h"
 
 namespace rgcn {
 
 namespace {
-
-constexpr int BT = 8;   // basis functions per launch of the source-major kernel (register budget); B > 8 loops on the host
-
-template <int VEC>
-__device__ __forceinline__ void vload(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = *p;
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void vstore(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else *p = v[0];
-}
-
-constexpr int kRowThreads = 1024;
-// leading workgroups of a row launch that walk the long-row list (as basis.hip)
-inline int long_blocks(const rgcn_ctx* c) { return 2 * c->g.E > 65536 ? 512 : 64; }
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // sigmoid without special cases: z = +inf -> 1 / (1 + 0) = 1, z = -inf -> 1 / (1 + inf) = 0
 __global__ void k_tdiag_sigmoid(const float* __restrict__ C, float* __restrict__ G, int64_t n) {
@@ -106,55 +85,14 @@ __device__ __forceinline__ void row_epilogue(const RowArgs& a, const DropKey& ke
   vstore<VEC>(a.c.out + off, o);
 }
 
-// Workgroups [0, n_long_blocks): one LONG row (more than kLongRow slots) at a time, 8 slot lanes x 128 column lanes, the
-// eight partial sums added through LDS in lane order.  The others: TPR lanes per destination row, 1024 / TPR rows each.
+// the single-accumulator row walk (row_walk.h) over the destination rows
 template <int VEC, int TPR>
 __global__ void __launch_bounds__(kRowThreads) k_tdiag_rows(RowArgs a, int n_long_blocks) {
-  const int nvec = a.c.d / VEC;
   const DropKey key = drop_key(a.c.drop);
-  if ((int)blockIdx.x < n_long_blocks) {
-    __shared__ float red[8][128 * VEC];
-    const int cl = threadIdx.x & 127, sl = threadIdx.x >> 7;
-    const int n = *a.nlong;
-    for (int lb = blockIdx.x; lb < n; lb += n_long_blocks) {
-      const int v = a.long_rows[lb];
-      const int beg = a.row_ptr[v], end = a.row_ptr[v + 1];
-      for (int c0 = 0; c0 < nvec; c0 += 128) {
-        const int cidx = c0 + cl;
-        float acc[VEC];
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
-        if (cidx < nvec) row_range<VEC>(a, beg + sl, end, 8, cidx, acc);
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) red[sl][cl * VEC + k] = acc[k];
-        __syncthreads();
-        if (sl == 0 && cidx < nvec) {
-#pragma unroll
-          for (int k = 0; k < VEC; ++k) {
-            float u = red[0][cl * VEC + k];
-#pragma unroll
-            for (int w = 1; w < 8; ++w) u += red[w][cl * VEC + k];
-            acc[k] = u;
-          }
-          row_epilogue<VEC>(a, key, v, cidx, acc);
-        }
-        __syncthreads();
-      }
-    }
-    return;
-  }
-  const int v = ((int)blockIdx.x - n_long_blocks) * (kRowThreads / TPR) + threadIdx.x / TPR;
-  if (v >= a.c.V) return;
-  const int lane = threadIdx.x % TPR;
-  const int beg = a.row_ptr[v], end = a.row_ptr[v + 1];
-  if (end - beg > kLongRow) return;      // a long-row workgroup of this launch owns it
-  for (int cidx = lane; cidx < nvec; cidx += TPR) {
-    float acc[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
-    row_range<VEC>(a, beg, end, 1, cidx, acc);
-    row_epilogue<VEC>(a, key, v, cidx, acc);
-  }
+  row_walk<VEC, TPR>(
+      a.row_ptr, a.long_rows, a.nlong, a.c.V, a.c.d / VEC, n_long_blocks,
+      [&a](int s0, int s1, int step, int cidx, float (&acc)[VEC]) { row_range<VEC>(a, s0, s1, step, cidx, acc); },
+      [&a, &key](int v, int cidx, const float (&acc)[VEC]) { row_epilogue<VEC>(a, key, v, cidx, acc); });
 }
 
 // ---------------------------------------------------------------- backward: source-major dP
@@ -205,72 +143,28 @@ __device__ __forceinline__ void dp_range(const DpArgs& a, int s0, int s1, int st
   }
 }
 
+struct DpRow {
+  float* p[2];               // the row's dP rows of the two directions, at basis b0
+};
+
+// The banked row walk (row_walk.h) over the source rows.  A row that sends nothing writes its zeros: dW = H^T . dP reads
+// every row.
 template <int VEC, int TPR>
 __global__ void __launch_bounds__(kRowThreads) k_tdiag_dp(DpArgs a, int n_long_blocks) {
-  const int nvec = a.d / VEC;
   const size_t Bd = (size_t)a.B * a.d;
-  if ((int)blockIdx.x < n_long_blocks) {
-    __shared__ float red[8][128 * VEC];
-    const int cl = threadIdx.x & 127, sl = threadIdx.x >> 7;
-    const int n = *a.nlong;
-    for (int lb = blockIdx.x; lb < n; lb += n_long_blocks) {
-      const int v = a.long_rows[lb];
-      const int beg = a.row_ptr[v], end = a.row_ptr[v + 1];
-      for (int c0 = 0; c0 < nvec; c0 += 128) {
-        const int cidx = c0 + cl;
-        float accf[BT][VEC], accb[BT][VEC];
-#pragma unroll
-        for (int b = 0; b < BT; ++b)
-#pragma unroll
-          for (int k = 0; k < VEC; ++k) { accf[b][k] = 0.f; accb[b][k] = 0.f; }
-        if (cidx < nvec) dp_range<VEC>(a, beg + sl, end, 8, cidx, accf, accb);
-#pragma unroll
-        for (int q = 0; q < 2 * BT; ++q) {
-          const int b = q % BT;
-          if (b < a.nbt) {
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) red[sl][cl * VEC + k] = q < BT ? accf[b][k] : accb[b][k];
-            __syncthreads();
-            if (sl == 0 && cidx < nvec) {
-              float t[VEC];
-#pragma unroll
-              for (int k = 0; k < VEC; ++k) {
-                float u = red[0][cl * VEC + k];
-#pragma unroll
-                for (int w = 1; w < 8; ++w) u += red[w][cl * VEC + k];
-                t[k] = u;
-              }
-              const int dir = q < BT ? 0 : 1;
-              vstore<VEC>(a.dP + ((size_t)dir * a.V + v) * Bd + (size_t)(a.b0 + b) * a.d + (size_t)cidx * VEC, t);
-            }
-            __syncthreads();
-          }
-        }
-      }
-    }
-    return;
-  }
-  const int v = ((int)blockIdx.x - n_long_blocks) * (kRowThreads / TPR) + threadIdx.x / TPR;
-  if (v >= a.V) return;
-  const int lane = threadIdx.x % TPR;
-  const int beg = a.row_ptr[v], end = a.row_ptr[v + 1];
-  if (end - beg > kLongRow) return;      // a long-row workgroup of this launch owns it
-  float* pf = a.dP + (size_t)v * Bd + (size_t)a.b0 * a.d;
-  float* pb = a.dP + ((size_t)a.V + v) * Bd + (size_t)a.b0 * a.d;
-  for (int cidx = lane; cidx < nvec; cidx += TPR) {
-    float accf[BT][VEC], accb[BT][VEC];
-#pragma unroll
-    for (int b = 0; b < BT; ++b)
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) { accf[b][k] = 0.f; accb[b][k] = 0.f; }
-    dp_range<VEC>(a, beg, end, 1, cidx, accf, accb);
-#pragma unroll
-    for (int b = 0; b < BT; ++b)
-      if (b < a.nbt) {      // a row that sends nothing writes its zeros: dW = H^T . dP reads every row
-        vstore<VEC>(pf + (size_t)b * a.d + (size_t)cidx * VEC, accf[b]);
-        vstore<VEC>(pb + (size_t)b * a.d + (size_t)cidx * VEC, accb[b]);
-      }
-  }
+  row_walk_banked<VEC, TPR, DpRow>(
+      a.row_ptr, a.long_rows, a.nlong, a.V, a.d / VEC, a.nbt, n_long_blocks,
+      [&a, Bd](int v, int, int, DpRow& r) {
+        r.p[0] = a.dP + (size_t)v * Bd + (size_t)a.b0 * a.d;
+        r.p[1] = a.dP + ((size_t)a.V + v) * Bd + (size_t)a.b0 * a.d;
+        return true;
+      },
+      [&a](int s0, int s1, int step, int cidx, float (&accf)[BT][VEC], float (&accb)[BT][VEC]) {
+        dp_range<VEC>(a, s0, s1, step, cidx, accf, accb);
+      },
+      [&a](const DpRow& r, int dir, int b, int cidx, const float (&t)[VEC]) {
+        vstore<VEC>(r.p[dir] + (size_t)b * a.d + (size_t)cidx * VEC, t);
+      });
 }
 
 // ---------------------------------------------------------------- backward: coefficient gradient
@@ -285,15 +179,6 @@ struct DcoefArgs {
   float* slab;               // [chunks][B*d]
   int32_t V, R, B, d, chunk;
 };
-
-__device__ __forceinline__ int find_segment(const int32_t* __restrict__ ptr, int n_seg, int x) {
-  int lo = 0, hi = n_seg;
-  while (hi - lo > 1) {
-    int mid = (lo + hi) >> 1;
-    if (ptr[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 
 // One workgroup per relation chunk; every thread owns VEC of the B.d entries of the chunk's slab row and adds the chunk's
 // messages in list order.
@@ -398,21 +283,14 @@ rgcn_status tdiag_rows_forward(rgcn_ctx* c, int layer, const float* P, const Com
   const bool vec4 = (c->d % 4 == 0) && aligned16(P) && aligned16(a.G) && aligned16(a.bias) && aligned16(ca.base) &&
                     aligned16(ca.out);
   const int nvec = vec4 ? c->d / 4 : c->d;
-  const int tpr = nvec <= 64 ? 64 : (nvec <= 128 ? 128 : 256);
-  const int rpb = kRowThreads / tpr;
+  const int tpr = row_lanes(nvec);
   const int nlb = long_blocks(c);
-  dim3 grid(nlb + (c->V + rpb - 1) / rpb), block(kRowThreads);
+  dim3 grid = row_grid(nlb, c->V, tpr), block(kRowThreads);
   const double M = 2.0 * c->g.E, Bd = (double)c->B * c->d;
   const double rows = M < 2.0 * c->V ? M : 2.0 * c->V;      // compulsory: each gathered row of P once, G once
   ProfScope ps(c, "tdiag_rows_fwd", 4.0 * (2.0 * M * Bd + 2.0 * c->V * c->d) + 12.0 * M, 2.0 * M * Bd + 2.0 * M * c->d,
                4.0 * (rows * Bd + 2.0 * c->R * Bd + 2.0 * c->V * c->d) + 12.0 * M);
-#define RGCN_LAUNCH_TR(VEC, TPR) hipLaunchKernelGGL((k_tdiag_rows<VEC, TPR>), grid, block, 0, c->stream, a, nlb)
-  if (vec4) {
-    if (tpr == 64) RGCN_LAUNCH_TR(4, 64); else if (tpr == 128) RGCN_LAUNCH_TR(4, 128); else RGCN_LAUNCH_TR(4, 256);
-  } else {
-    if (tpr == 64) RGCN_LAUNCH_TR(1, 64); else if (tpr == 128) RGCN_LAUNCH_TR(1, 128); else RGCN_LAUNCH_TR(1, 256);
-  }
-#undef RGCN_LAUNCH_TR
+  RGCN_LAUNCH_ROWS(k_tdiag_rows, vec4, tpr, grid, block, c->stream, a, nlb);
   RGCN_HIP(c, hipGetLastError());
   return RGCN_OK;
 }
@@ -425,10 +303,9 @@ rgcn_status tdiag_dp(rgcn_ctx* c, int layer, const float* D, float* dP) {
   a.V = c->V; a.d = c->d; a.B = c->B; a.R = c->R;
   const bool vec4 = (c->d % 4 == 0) && aligned16(D) && aligned16(a.G) && aligned16(dP);
   const int nvec = vec4 ? c->d / 4 : c->d;
-  const int tpr = nvec <= 64 ? 64 : (nvec <= 128 ? 128 : 256);
-  const int rpb = kRowThreads / tpr;
+  const int tpr = row_lanes(nvec);
   const int nlb = long_blocks(c);
-  dim3 grid(nlb + (c->V + rpb - 1) / rpb), block(kRowThreads);
+  dim3 grid = row_grid(nlb, c->V, tpr), block(kRowThreads);
   const double M = 2.0 * c->g.E;
   for (int b0 = 0; b0 < c->B; b0 += BT) {
     a.b0 = b0;
@@ -436,13 +313,7 @@ rgcn_status tdiag_dp(rgcn_ctx* c, int layer, const float* D, float* dP) {
     const double rows = M < c->V ? M : (double)c->V;
     ProfScope ps(c, "tdiag_dp", 4.0 * c->d * (M * (1.0 + a.nbt) + 2.0 * c->V * a.nbt) + 12.0 * M, 2.0 * M * a.nbt * c->d,
                  4.0 * c->d * (rows + 2.0 * c->R * a.nbt + 2.0 * c->V * a.nbt) + 12.0 * M);
-#define RGCN_LAUNCH_DP(VEC, TPR) hipLaunchKernelGGL((k_tdiag_dp<VEC, TPR>), grid, block, 0, c->stream, a, nlb)
-    if (vec4) {
-      if (tpr == 64) RGCN_LAUNCH_DP(4, 64); else if (tpr == 128) RGCN_LAUNCH_DP(4, 128); else RGCN_LAUNCH_DP(4, 256);
-    } else {
-      if (tpr == 64) RGCN_LAUNCH_DP(1, 64); else if (tpr == 128) RGCN_LAUNCH_DP(1, 128); else RGCN_LAUNCH_DP(1, 256);
-    }
-#undef RGCN_LAUNCH_DP
+    RGCN_LAUNCH_ROWS(k_tdiag_dp, vec4, tpr, grid, block, c->stream, a, nlb);
     RGCN_HIP(c, hipGetLastError());
   }
   return RGCN_OK;

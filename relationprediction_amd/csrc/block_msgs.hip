@@ -20,20 +20,11 @@
 #include <type_traits>
 
 #include "rgcn_internal.h"
+#include "row_walk.h"
 
 namespace rgcn {
 
 namespace {
-
-__device__ __forceinline__ int find_segment(const int32_t* __restrict__ ptr, int n_seg, int x) {
-  // largest s in [0, n_seg) with ptr[s] <= x   (ptr has n_seg + 1 entries, ptr[n_seg] > x)
-  int lo = 0, hi = n_seg;
-  while (hi - lo > 1) {
-    int mid = (lo + hi) >> 1;
-    if (ptr[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 
 struct MsgArgs {
   const float* Hin;       // [V,d] layer input

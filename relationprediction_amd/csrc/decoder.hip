@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "rgcn_internal.h"
+#include "row_walk.h"
 
 namespace rgcn {
 
@@ -27,22 +28,6 @@ constexpr int kDecLongRow = 256;    // entity rows with more incidences are cut 
 constexpr int kDecPiece = 512;      // incidences per piece: a hub entity (tens of thousands of incidences in a
                                     // neighbourhood-sampled batch with its tiled negatives) spreads over many CUs
 constexpr int kDecChunk = 128;      // triples per relation chunk
-constexpr int kRowThreads = 1024;
-
-template <int VEC>
-__device__ __forceinline__ void vload(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = *p;
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void vstore(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else *p = v[0];
-}
 
 __device__ __forceinline__ int lower_bound_u32(const uint32_t* a, int n, uint32_t x) {
   int lo = 0, hi = n;
@@ -584,15 +569,6 @@ __global__ void __launch_bounds__(64 * kLineWaves) k_dec_entity_lines(EntArgs a,
 }
 
 // ---- K3: relation gradients ------------------------------------------------------------------------
-__device__ __forceinline__ int find_segment(const int32_t* __restrict__ ptr, int n_seg, int x) {
-  int lo = 0, hi = n_seg;
-  while (hi - lo > 1) {
-    int mid = (lo + hi) >> 1;
-    if (ptr[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 template <int VEC>
 __global__ void __launch_bounds__(kRowThreads) k_dec_rel_partial(const float* __restrict__ codes,
                                                                  const float* __restrict__ dx,
@@ -814,8 +790,6 @@ int bits_for(uint32_t max_value) {
   while (b < 32 && (1ull << b) <= max_value) ++b;
   return b;
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 
@@ -1052,7 +1026,7 @@ rgcn_status decoder_compute(rgcn_ctx* c, const float* codes, const float* Y, flo
       else hipLaunchKernelGGL((k_dec_entity_lines<false>), grid, block, 0, c->stream, a, b);
     } else {
       const int nvec = vec4 ? d / 4 : d;
-      const int tpr = nvec <= 64 ? 64 : (nvec <= 128 ? 128 : 256);
+      const int tpr = row_lanes(nvec);
       const int rpb = kEntThreads / tpr;
       int64_t want = 2 * (int64_t)N / 2048;
       // (sized for 1024-thread workgroups; four times as many of the 256-thread ones walk the long-row pieces)
@@ -1062,13 +1036,7 @@ rgcn_status decoder_compute(rgcn_ctx* c, const float* codes, const float* Y, flo
       // once, the incidence lists and per-triple gradients once, dL/dcodes written once
       ProfScope ps(c, "dec_entity_grad", 16.0 * N * d + 8.0 * V * d, 6.0 * N * d,
                    4.0 * d * (2.0 * V + R) + 32.0 * N);
-#define RGCN_LAUNCH_EG(VEC, TPR) hipLaunchKernelGGL((k_dec_entity_grad<VEC, TPR>), grid, block, 0, c->stream, a, nlb)
-      if (vec4) {
-        if (tpr == 64) RGCN_LAUNCH_EG(4, 64); else if (tpr == 128) RGCN_LAUNCH_EG(4, 128); else RGCN_LAUNCH_EG(4, 256);
-      } else {
-        if (tpr == 64) RGCN_LAUNCH_EG(1, 64); else if (tpr == 128) RGCN_LAUNCH_EG(1, 128); else RGCN_LAUNCH_EG(1, 256);
-      }
-#undef RGCN_LAUNCH_EG
+      RGCN_LAUNCH_ROWS(k_dec_entity_grad, vec4, tpr, grid, block, c->stream, a, nlb);
     }
     if (vec4) hipLaunchKernelGGL((k_dec_long_finish<4>), dim3(128), dim3(256), 0, c->stream, a);
     else hipLaunchKernelGGL((k_dec_long_finish<1>), dim3(128), dim3(256), 0, c->stream, a);

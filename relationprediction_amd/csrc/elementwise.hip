@@ -9,6 +9,7 @@
 // One group of 64/128/256 lanes walks one row with float4 accesses (d % 4 == 0) so every
 // global access is a full coalesced 16 B/lane stream; rows are independent => no atomics.
 #include "rgcn_internal.h"
+#include "row_walk.h"
 
 namespace rgcn {
 
@@ -26,24 +27,6 @@ template <>
 struct VecT<1> {
   using type = float;
 };
-
-template <int VEC>
-__device__ __forceinline__ void vload(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = *p;
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void vstore(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    *p = v[0];
-  }
-}
 
 // Epilogue shared by the row kernels: gate (relu'), relu, store, dropout-scaled second copy.
 template <int VEC>
@@ -414,8 +397,6 @@ int grid_for(int64_t n, int threads) {
   return (int)b;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 DropSpec make_drop(const rgcn_ctx* c, int layer, bool active) {
@@ -450,7 +431,7 @@ rgcn_status combine(rgcn_ctx* c, const char* tag, const CombineArgs& a_in, doubl
   const bool vec4 = (a.d % 4 == 0) && aligned16(a.out) && aligned16(a.base) && aligned16(a.msg) && aligned16(a.add) &&
                     aligned16(a.gate) && aligned16(a.out2);
   const int nvec = vec4 ? a.d / 4 : a.d;
-  const int tpr = nvec <= 64 ? 64 : (nvec <= 128 ? 128 : 256);
+  const int tpr = row_lanes(nvec);
   const int nrows = a.v_count < 0 ? a.V : a.v_count;
   // enough long-row workgroups for the graph at hand: one per ~1024 slots, at least 64, at most 1024
   int n_long_blocks = 0;
@@ -463,18 +444,7 @@ rgcn_status combine(rgcn_ctx* c, const char* tag, const CombineArgs& a_in, doubl
   const int nb_rows = (nrows + rows_per_block - 1) / rows_per_block;
   dim3 grid(nb_rows + n_long_blocks), block(kCombineThreads);
   ProfScope ps(c, tag, alg_bytes, 0);
-#define RGCN_LAUNCH_COMBINE(VEC, TPR) \
-  hipLaunchKernelGGL((k_combine<VEC, TPR>), grid, block, 0, c->stream, a, n_long_blocks)
-  if (vec4) {
-    if (tpr == 64) RGCN_LAUNCH_COMBINE(4, 64);
-    else if (tpr == 128) RGCN_LAUNCH_COMBINE(4, 128);
-    else RGCN_LAUNCH_COMBINE(4, 256);
-  } else {
-    if (tpr == 64) RGCN_LAUNCH_COMBINE(1, 64);
-    else if (tpr == 128) RGCN_LAUNCH_COMBINE(1, 128);
-    else RGCN_LAUNCH_COMBINE(1, 256);
-  }
-#undef RGCN_LAUNCH_COMBINE
+  RGCN_LAUNCH_ROWS(k_combine, vec4, tpr, grid, block, c->stream, a, n_long_blocks);
   if (giant) {
     if (vec4) hipLaunchKernelGGL((k_combine_giant_finish<4>), dim3(64), dim3(256), 0, c->stream, a);
     else hipLaunchKernelGGL((k_combine_giant_finish<1>), dim3(64), dim3(256), 0, c->stream, a);

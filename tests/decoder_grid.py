@@ -14,13 +14,13 @@ tests/test_decoder_grid.py keeps the table honest without a GPU; tests/test_gpu_
 """
 import numpy as np
 
-BLOCK_SIZES = (1, 2, 3, 4, 5, 8)      # block_msgs.hip:193-201: the block sizes d / nb the encoder is compiled for
+BLOCK_SIZES = (1, 2, 3, 4, 5, 8)      # block_msgs.hip:184-192: the block sizes d / nb the encoder is compiled for
 MAX_BLOCKS = 512                      # config_check.h (check_config)
-LONG_ROW = 256                        # decoder.hip:26 (kDecLongRow): a row with more incidences is cut into pieces
-PIECE = 512                           # decoder.hip:27 (kDecPiece): incidences per piece
-CHUNK = 128                           # decoder.hip:29 (kDecChunk): triples per relation chunk
-LINE = 32                             # decoder.hip:441 (kLine): floats per (row, band) of the line form
-BANDS_PER_PASS = 8                    # decoder.hip:538: workgroup x takes bands x, x + 8, ...
+LONG_ROW = 256                        # decoder.hip:27 (kDecLongRow): a row with more incidences is cut into pieces
+PIECE = 512                           # decoder.hip:28 (kDecPiece): incidences per piece
+CHUNK = 128                           # decoder.hip:30 (kDecChunk): triples per relation chunk
+LINE = 32                             # decoder.hip:426 (kLine): floats per (row, band) of the line form
+BANDS_PER_PASS = 8                    # decoder.hip:523: workgroup x takes bands x, x + 8, ...
 MAX_DECODER_TRIPLES = 1 << 29         # include/rgcn.h (RGCN_MAX_DECODER_TRIPLES)
 
 ENERGY_CELLS = [("energy_rel", 4, 1), ("energy_rel", 4, 2), ("energy_rel", 4, 4),
@@ -30,12 +30,12 @@ ENTITY_CELLS = [("lines", True), ("lines", False), ("rows", 1, 64), ("rows", 1, 
 
 
 def vec_width(d):
-    """decoder.hip:963: float4 columns when d % 4 == 0 (the engine's buffers are 16-byte aligned)."""
+    """decoder.hip:939: float4 columns when d % 4 == 0 (the engine's buffers are 16-byte aligned)."""
     return 4 if d % 4 == 0 else 1
 
 
 def energy_cell(d):
-    """decoder.hip:968-971: fused while nvec_e <= 256, T = 1 / 2 / 4 register tiles for up to 64 / 128 / 256 vectors."""
+    """decoder.hip:945-947: fused while nvec_e <= 256, T = 1 / 2 / 4 register tiles for up to 64 / 128 / 256 vectors."""
     vec = vec_width(d)
     nvec = d // vec
     if nvec > 256:
@@ -44,50 +44,50 @@ def energy_cell(d):
 
 
 def rel_partial_passes(d):
-    """decoder.hip:612: k_dec_rel_partial (unfused rows only) walks the row in passes of 128 column vectors."""
+    """decoder.hip:588: k_dec_rel_partial (unfused rows only) walks the row in passes of 128 column vectors."""
     return -(-(d // vec_width(d)) // 128)
 
 
 def relation_lds(R):
-    """decoder.hip:1040-1041: the line form keeps the relation band [R][32] floats in LDS up to 64 KB."""
+    """decoder.hip:1016-1017: the line form keeps the relation band [R][32] floats in LDS up to 64 KB."""
     return R * LINE * 4 <= 64 * 1024
 
 
 def entity_tpr(d):
-    """decoder.hip:1052-1053: lanes per row of k_dec_entity_grad."""
+    """decoder.hip:1029 (row_walk.h:48, row_lanes): lanes per row of k_dec_entity_grad."""
     nvec = d // vec_width(d)
     return 64 if nvec <= 64 else (128 if nvec <= 128 else 256)
 
 
 def entity_cell(d, R):
-    """decoder.hip:1027: the line form whenever the rows are float4-addressable, else the full-row kernel."""
+    """decoder.hip:1003: the line form whenever the rows are float4-addressable, else the full-row kernel."""
     if vec_width(d) == 4:
         return ("lines", relation_lds(R))
     return ("rows", 1, entity_tpr(d))
 
 
 def bands(d):
-    """decoder.hip:863: column bands of one line; the last one partial when d % 32 != 0."""
+    """decoder.hip:840: column bands of one line; the last one partial when d % 32 != 0."""
     return -(-d // LINE)
 
 
 def band_passes(d):
-    """decoder.hip:538: passes of the line form's band loop (8 bands per pass, one per XCD)."""
+    """decoder.hip:523: passes of the line form's band loop (8 bands per pass, one per XCD)."""
     return -(-bands(d) // BANDS_PER_PASS)
 
 
 def pieces(incidences):
-    """decoder.hip:144-147: pieces of a long row (0 for a row the short-row kernels take)."""
+    """decoder.hip:129-132: pieces of a long row (0 for a row the short-row kernels take)."""
     return -(-incidences // PIECE) if incidences > LONG_ROW else 0
 
 
 def chunks(triples):
-    """decoder.hip:113: chunks of one relation's triples."""
+    """decoder.hip:98: chunks of one relation's triples."""
     return -(-triples // CHUNK)
 
 
 def copies(case):
-    """decoder.hip:910-914: a batch the sampler tiled is decoded as `rate + 1` copies when its period n is > 1."""
+    """decoder.hip:884-888: a batch the sampler tiled is decoded as `rate + 1` copies when its period n is > 1."""
     if case.get("rate") is None or case["n"] <= 1:
         return 1
     return case["rate"] + 1
@@ -99,7 +99,7 @@ def cell_of(case):
 
 
 def incidences(X, V):
-    """Incidences of every entity row over both sides (decoder.hip:57-70: 2N keys, a self edge counts twice)."""
+    """Incidences of every entity row over both sides (decoder.hip:42-55: 2N keys, a self edge counts twice)."""
     X = np.asarray(X).reshape(-1, 3)
     return np.bincount(np.concatenate([X[:, 0], X[:, 2]]), minlength=V)
 

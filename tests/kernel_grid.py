@@ -12,14 +12,14 @@ import numpy as np
 
 from helpers import make_case
 
-BLOCK_SIZES = (1, 2, 3, 4, 5, 8)      # block_msgs.hip:193-201 (dispatch_sd) and block_rows.hip:701-703
+BLOCK_SIZES = (1, 2, 3, 4, 5, 8)      # block_msgs.hip:184-192 (dispatch_sd) and block_rows.hip:701-703
 GROUP_WIDTHS = (8, 16, 32, 64)
 TILE_SIZES = (64, 32, 16, 8)
 LONG_ROW = 32                         # rgcn_internal.h:93 (kLongRow): a row with more slots takes the long-row path
 GIANT_ROW = 2048                      # rgcn_internal.h:96 (kGiantRow): full-graph scale only, never reached here
 MAX_BLOCKS = 512                      # config_check.h (check_config)
 MAX_BASES = 64                        # config_check.h (check_config)
-BASIS_BT = 8                          # basis.hip:26 (BT): basis functions per pass
+BASIS_BT = 8                          # row_walk.h:15 (BT): basis functions per pass
 D500_BLOCK_COUNTS = (100, 125, 250, 500)   # every nb that divides the shipped d = 500 into a compiled block size
 
 
@@ -52,8 +52,8 @@ def block_slots(nb, sd):
 
 
 def basis_vec_tpr(d):
-    """basis.hip:465-467 (and the other launchers, :501-504): float4 columns when d % 4 == 0 (the engine's buffers are
-    16-byte aligned), then 64 / 128 / 256 lanes per row for up to 64 / 128 / more column vectors."""
+    """basis.hip:342-344 (and the other launchers, :370-373): float4 columns when d % 4 == 0 (the engine's buffers are
+    16-byte aligned), then row_walk.h:48 (row_lanes): 64 / 128 / 256 lanes per row for up to 64 / 128 / more column vectors."""
     vec = 4 if d % 4 == 0 else 1
     nvec = d // vec
     return vec, (64 if nvec <= 64 else (128 if nvec <= 128 else 256))

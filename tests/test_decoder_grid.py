@@ -127,7 +127,8 @@ def test_case_shapes_are_valid_configurations():
 @pytest.mark.parametrize("source,text", [
     ("decoder.hip", "const bool fused = nvec_e <= 256;"),
     ("decoder.hip", "const int T = nvec_e <= 64 ? 1 : (nvec_e <= 128 ? 2 : 4);"),
-    ("decoder.hip", "const int tpr = nvec <= 64 ? 64 : (nvec <= 128 ? 128 : 256);"),
+    ("row_walk.h", "inline int row_lanes(int nvec) { return nvec <= 64 ? 64 : (nvec <= 128 ? 128 : 256); }"),
+    ("decoder.hip", "const int tpr = row_lanes(nvec);"),
     ("decoder.hip", "const bool rlds = lds <= 64 * 1024;"),
     ("decoder.hip", "const size_t lds = (size_t)R * kLine * sizeof(float);"),
     ("decoder.hip", "const bool vec4 = (d % 4 == 0) && aligned16(codes)"),

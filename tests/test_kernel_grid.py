@@ -94,8 +94,9 @@ def test_case_shapes_are_valid_configurations():
     ("block_rows.hip", "TS = GW * SD <= 80 ? 64 : (GW * SD <= 160 ? 32 : (GW * SD <= 320 ? 16 : 8));"),
     ("block_rows.hip", "const int b0 = (x * nb) >> 3, b1 = ((x + 1) * nb) >> 3;"),
     ("block_msgs.hip", "while (g > 1 && (size_t)(g - 1) * c->sd * c->sd * c->nb * sizeof(float) > 60 * 1024) --g;"),
-    ("basis.hip", "const int tpr = nvec <= 64 ? 64 : (nvec <= 128 ? 128 : 256);"),
-    ("basis.hip", "constexpr int BT = 8;"),
+    ("row_walk.h", "inline int row_lanes(int nvec) { return nvec <= 64 ? 64 : (nvec <= 128 ? 128 : 256); }"),
+    ("basis.hip", "const int tpr = row_lanes(nvec);"),
+    ("row_walk.h", "constexpr int BT = 8;"),
     ("rgcn_internal.h", "constexpr int kLongRow = 32;"),
 ])
 def test_host_mirrors_follow_the_kernel_sources(source, text):

@@ -2,6 +2,7 @@
 every loop of theirs beyond its first trip and every boundary of their dispatch, and every case's graph holds the rows
 and relations it is meant to hold.  No GPU: a later edit of the table that drops a cell fails here, naming the cell."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -157,11 +158,15 @@ def test_case_names_are_unique():
 
 # ----------------------------------------------------------------------------- the mirrors follow the sources
 @pytest.mark.parametrize("source,text", [
-    ("basis_onehot.hip", "const int tpr = nvec <= 64 ? 64 : (nvec <= 128 ? 128 : 256);"),
-    ("basis_onehot.hip", "constexpr int BT = 8;"),
-    ("basis_onehot.hip", "inline int long_blocks(const rgcn_ctx* c) { return 2 * c->g.E > 65536 ? 512 : 64; }"),
+    ("row_walk.h", "inline int row_lanes(int nvec) { return nvec <= 64 ? 64 : (nvec <= 128 ? 128 : 256); }"),
+    ("basis_onehot.hip", "const int tpr = row_lanes(nvec);"),
+    ("row_walk.h", "constexpr int BT = 8;"),
+    ("row_walk.h", "inline int long_blocks(const rgcn_ctx* c) { return 2 * c->g.E > 65536 ? 512 : 64; }"),
+    # (k_onehot_fwd's walk is row_walk.h's; k_onehot_tables keeps a body of its own)
     ("basis_onehot.hip", "__shared__ float red[8][128 * VEC];"),
+    ("row_walk.h", "__shared__ float red[8][128 * VEC];"),
     ("basis_onehot.hip", "for (int c0 = 0; c0 < nvec; c0 += 128) {"),
+    ("row_walk.h", "for (int c0 = 0; c0 < nvec; c0 += 128) {"),
     ("graph_prep.hip", "g.chunk = std::min(c->chunk, 48 * (int)std::max<int64_t>(1, ((int64_t)M + 65535) / 65536));"),
     ("rgcn_api.hip", "if (2 * f.max_edges > 65536) c->chunk = 48 * (int)((2 * f.max_edges + 65535) / 65536);"),
     ("rgcn_internal.h", "constexpr int kLongRow = 32;"),
@@ -170,3 +175,18 @@ def test_host_mirrors_follow_the_kernel_sources(source, text):
     """The mirrors in onehot_grid.py are copies of these dispatch lines: when one changes, the table has to be re-derived."""
     with open(os.path.join(CSRC, source)) as f:
         assert text in f.read(), "%s no longer holds `%s`: update tests/onehot_grid.py's mirror" % (source, text)
+
+
+def test_the_compiled_variants_are_the_product_of_vecs_and_tprs():
+    """the one dispatch definition of the row kernels names every (VEC, TPR) cell once, and both row launchers of
+    basis_onehot.hip go through it"""
+    with open(os.path.join(CSRC, "row_walk.h")) as f:
+        macro = f.read().split("#define RGCN_LAUNCH_ROWS(")
+    assert len(macro) == 2
+    have = [(int(v), int(t)) for v, t in re.findall(r"kernel<(\d+), (\d+)>", macro[1])]
+    assert sorted(have) == sorted((vec, tpr) for vec in og.VECS for tpr in og.TPRS)
+    with open(os.path.join(CSRC, "basis_onehot.hip")) as f:
+        text = f.read()
+    for kernel in ("k_onehot_fwd", "k_onehot_tables"):
+        assert len(re.findall(r"RGCN_LAUNCH_ROWS\(%s, vec4, tpr, grid, block, c->stream, a, nlb\);" % kernel, text)) == 1, kernel
+        assert not re.findall(kernel + r"<\d", text), kernel

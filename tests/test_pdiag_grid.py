@@ -153,14 +153,19 @@ def test_case_names_are_unique():
 
 # ----------------------------------------------------------------------------- the mirrors follow the sources
 @pytest.mark.parametrize("source,pattern,count", [
-    ("basis_pdiag.hip", r"inline int row_lanes\(int nvec\) \{ return nvec <= 64 \? 64 : \(nvec <= 128 \? 128 : 256\); \}", 1),
+    ("row_walk.h", r"inline int row_lanes\(int nvec\) \{ return nvec <= 64 \? 64 : \(nvec <= 128 \? 128 : 256\); \}", 1),
     ("basis_pdiag.hip", r"const int tpr = row_lanes\(nvec\);", 2),
-    ("basis_pdiag.hip", r"constexpr int kRowThreads = 1024;", 1),
+    ("row_walk.h", r"constexpr int kRowThreads = 1024;", 1),
     ("basis_pdiag.hip", r"constexpr int kMixLanes = 128;", 1),
-    ("basis_pdiag.hip", r"inline int long_blocks\(const rgcn_ctx\* c\) \{ return 2 \* c->g\.E > 65536 \? 512 : 64; \}", 1),
-    ("basis_pdiag.hip", r"__shared__ float red\[8\]\[128 \* VEC\];", 2),
-    ("basis_pdiag.hip", r"for \(int c0 = 0; c0 < nvec; c0 \+= 128\) \{", 2),
-    ("basis_pdiag.hip", r"for \(int cidx = lane; cidx < nvec; cidx \+= TPR\) \{", 2),
+    ("row_walk.h", r"inline int long_blocks\(const rgcn_ctx\* c\) \{ return 2 \* c->g\.E > 65536 \? 512 : 64; \}", 1),
+    # (k_pdiag_rows keeps its own walk; k_pdiag_dh_join's is the single-accumulator form of row_walk.h, which holds the
+    # banked form as well)
+    ("basis_pdiag.hip", r"__shared__ float red\[8\]\[128 \* VEC\];", 1),
+    ("row_walk.h", r"__shared__ float red\[8\]\[128 \* VEC\];", 2),
+    ("basis_pdiag.hip", r"for \(int c0 = 0; c0 < nvec; c0 \+= 128\) \{", 1),
+    ("row_walk.h", r"for \(int c0 = 0; c0 < nvec; c0 \+= 128\) \{", 2),
+    ("basis_pdiag.hip", r"for \(int cidx = lane; cidx < nvec; cidx \+= TPR\) \{", 1),
+    ("row_walk.h", r"for \(int cidx = lane; cidx < nvec; cidx \+= TPR\) \{", 2),
     ("basis_pdiag.hip", r"for \(int j = lane; j < nmix; j \+= TPR\) \{", 1),
     ("basis_pdiag.hip", r"for \(int cidx = lane; cidx < nvec; cidx \+= 64\) \{", 3),
     ("basis_pdiag.hip", r"for \(int e = threadIdx\.x \* VEC; e < a\.d; e \+= 256 \* VEC\) \{", 1),
@@ -175,12 +180,21 @@ def test_host_mirrors_follow_the_kernel_sources(source, pattern, count):
     assert found == count, "%s holds `%s` %d times, not %d: update tests/pdiag_grid.py's mirror" % (source, pattern, found, count)
 
 
+def row_dispatch_cells():
+    """the (VEC, TPR) instantiations the one dispatch definition of the row kernels, RGCN_LAUNCH_ROWS, names"""
+    with open(os.path.join(CSRC, "row_walk.h")) as f:
+        text = f.read()
+    assert text.count("#define RGCN_LAUNCH_ROWS(") == 1
+    return [(int(v), int(t)) for v, t in re.findall(r"kernel<(\d+), (\d+)>", text.split("#define RGCN_LAUNCH_ROWS(")[1])]
+
+
 def test_the_compiled_variants_are_the_product_of_vecs_and_tprs():
+    assert sorted(row_dispatch_cells()) == sorted((vec, tpr) for vec in pg.VECS for tpr in pg.TPRS)      # each cell once
     with open(os.path.join(CSRC, "basis_pdiag.hip")) as f:
         text = f.read()
-    for macro in ("RGCN_LAUNCH_PR", "RGCN_LAUNCH_PJ"):
-        have = {(int(v), int(t)) for v, t in re.findall(macro + r"\((\d+), (\d+)\)", text)}
-        assert have == {(vec, tpr) for vec in pg.VECS for tpr in pg.TPRS}, macro
+    for kernel in ("k_pdiag_rows", "k_pdiag_dh_join"):      # every row launcher goes through it, and launches no other way
+        assert len(re.findall(r"RGCN_LAUNCH_ROWS\(%s, vec4, tpr, grid, block, c->stream, a, nlb\);" % kernel, text)) == 1, kernel
+        assert not re.findall(kernel + r"<\d", text), kernel
     for kernel in ("k_pdiag_epilogue", "k_pdiag_row_bwd", "k_pdiag_ddiag"):
         assert set(re.findall(kernel + r"<(\d)>", text)) == {"4", "1"}, kernel
 

@@ -175,13 +175,15 @@ def test_case_names_are_unique():
 
 # ----------------------------------------------------------------------------- the mirrors follow the sources
 @pytest.mark.parametrize("source,pattern,count", [
-    ("basis_tdiag.hip", r"const int tpr = nvec <= 64 \? 64 : \(nvec <= 128 \? 128 : 256\);", 2),
-    ("basis_tdiag.hip", r"constexpr int BT = 8;", 1),
-    ("basis_tdiag.hip", r"constexpr int kRowThreads = 1024;", 1),
-    ("basis_tdiag.hip", r"inline int long_blocks\(const rgcn_ctx\* c\) \{ return 2 \* c->g\.E > 65536 \? 512 : 64; \}", 1),
-    ("basis_tdiag.hip", r"__shared__ float red\[8\]\[128 \* VEC\];", 2),
-    ("basis_tdiag.hip", r"for \(int c0 = 0; c0 < nvec; c0 \+= 128\) \{", 2),
-    ("basis_tdiag.hip", r"for \(int cidx = lane; cidx < nvec; cidx \+= TPR\) \{", 2),
+    ("row_walk.h", r"inline int row_lanes\(int nvec\) \{ return nvec <= 64 \? 64 : \(nvec <= 128 \? 128 : 256\); \}", 1),
+    ("basis_tdiag.hip", r"const int tpr = row_lanes\(nvec\);", 2),
+    ("row_walk.h", r"constexpr int BT = 8;", 1),
+    ("row_walk.h", r"constexpr int kRowThreads = 1024;", 1),
+    ("row_walk.h", r"inline int long_blocks\(const rgcn_ctx\* c\) \{ return 2 \* c->g\.E > 65536 \? 512 : 64; \}", 1),
+    # (the two forms of the row walk: single accumulator, k_tdiag_rows; banked, k_tdiag_dp)
+    ("row_walk.h", r"__shared__ float red\[8\]\[128 \* VEC\];", 2),
+    ("row_walk.h", r"for \(int c0 = 0; c0 < nvec; c0 \+= 128\) \{", 2),
+    ("row_walk.h", r"for \(int cidx = lane; cidx < nvec; cidx \+= TPR\) \{", 2),
     ("basis_tdiag.hip", r"for \(int e = threadIdx\.x \* VEC; e < Bd; e \+= 256 \* VEC\) \{", 1),
     ("basis_tdiag.hip", r"int64_t blocks = \(nvec \+ 255\) / 256;\s+if \(blocks > 8192\) blocks = 8192;", 1),
     ("basis_tdiag.hip", r"for \(int b0 = 0; b0 < c->B; b0 \+= BT\) \{", 1),
@@ -199,12 +201,21 @@ def test_host_mirrors_follow_the_kernel_sources(source, pattern, count):
     assert found == count, "%s holds `%s` %d times, not %d: update tests/tdiag_grid.py's mirror" % (source, pattern, found, count)
 
 
+def row_dispatch_cells():
+    """the (VEC, TPR) instantiations the one dispatch definition of the row kernels, RGCN_LAUNCH_ROWS, names"""
+    with open(os.path.join(CSRC, "row_walk.h")) as f:
+        text = f.read()
+    assert text.count("#define RGCN_LAUNCH_ROWS(") == 1
+    return [(int(v), int(t)) for v, t in re.findall(r"kernel<(\d+), (\d+)>", text.split("#define RGCN_LAUNCH_ROWS(")[1])]
+
+
 def test_the_compiled_variants_are_the_product_of_vecs_and_tprs():
+    assert sorted(row_dispatch_cells()) == sorted((vec, tpr) for vec in tg.VECS for tpr in tg.TPRS)      # each cell once
     with open(os.path.join(CSRC, "basis_tdiag.hip")) as f:
         text = f.read()
-    for macro in ("RGCN_LAUNCH_TR", "RGCN_LAUNCH_DP"):
-        have = {(int(v), int(t)) for v, t in re.findall(macro + r"\((\d+), (\d+)\)", text)}
-        assert have == {(vec, tpr) for vec in tg.VECS for tpr in tg.TPRS}, macro
+    for kernel in ("k_tdiag_rows", "k_tdiag_dp"):      # every row launcher goes through it, and launches no other way
+        assert len(re.findall(r"RGCN_LAUNCH_ROWS\(%s, vec4, tpr, grid, block, c->stream, a, nlb\);" % kernel, text)) == 1, kernel
+        assert not re.findall(kernel + r"<\d", text), kernel
     assert set(re.findall(r"k_tdiag_dcoef<(\d)>", text)) == set(re.findall(r"k_tdiag_dh_join<(\d)>", text)) == {"4", "1"}
 
 

@@ -7,6 +7,7 @@ or no GPU is visible, construction fails loudly.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -571,41 +572,85 @@ class Engine:
     def ranks(self, triples, predict_object, filter_ptr, filter_idx):
         """Raw and filtered ranks (include/rgcn.h rgcn_rank_device) of the gold subject / object of every
         query triple on the codes of the last forward.  filter_ptr int64 [N+1], filter_idx int32 [nnz]."""
-        x = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
+        return self._ranks_staged(triples, filter_ptr, filter_idx, lambda n, x, ptr, idx, raw, filt: self.lib.rgcn_rank_device(
+            self.ctx, x, n, 1 if predict_object else 0, ptr, idx, raw, filt))
+
+    def _stage_queries(self, x, list_ptr, list_idx, out_bytes):
+        """ONE upload (list pointers | queries | list, packed) into a buffer the engine keeps, with room for out_bytes of
+        answers behind it for ONE download: a call used to cost five device allocations, three blocking uploads and two
+        downloads -- more host time than the scoring itself.  list_ptr int64 [N+1], list_idx int32 [nnz]: the filter or
+        exclusion lists.  Returns the device addresses of (list pointers, queries, list, answers)."""
         n = len(x)
-        if n == 0:
-            return np.zeros(0, np.int32), np.zeros(0, np.int32)
-        fp = np.ascontiguousarray(filter_ptr, dtype=np.int64)
-        fi = np.ascontiguousarray(filter_idx, dtype=np.int32)
+        fp = np.ascontiguousarray(list_ptr, dtype=np.int64)
+        fi = np.ascontiguousarray(list_idx, dtype=np.int32)
         assert fp.shape == (n + 1,) and fp[-1] == len(fi)
-        # ONE upload (filter pointers | queries | filter list, packed) into a buffer the engine keeps, ONE download (raw |
-        # filtered ranks): a call used to cost five device allocations, three blocking uploads and two downloads --
-        # more host time than the scoring itself
-        nnz = max(len(fi), 1)
         off_x, off_fi = 8 * (n + 1), 8 * (n + 1) + 12 * n
-        off_out = (off_fi + 4 * nnz + 7) // 8 * 8
-        total = off_out + 8 * n
+        off_out = (off_fi + 4 * max(len(fi), 1) + 7) // 8 * 8
+        total = off_out + out_bytes
         if getattr(self, "_rank_buf", None) is None or self._rank_buf.nbytes < total:
             if getattr(self, "_rank_buf", None) is not None:
                 self._rank_buf.free()
             self._rank_buf = DeviceBuffer(self, max(total, 1 << 20))
-        base = self._rank_buf.ptr.value if hasattr(self._rank_buf.ptr, "value") else int(self._rank_buf.ptr)
-        # staged through the library's pinned slots (<= 1 MB each), ordered on the main stream, no host wait: the filter
-        # list (megabytes for the subject side of FB15k-237) travels while the queries are being scored
-        head = np.empty(off_fi, dtype=np.uint8)
-        head[:off_x] = fp.view(np.uint8)
-        head[off_x:] = x.reshape(-1).view(np.uint8)
-        self._check(self.lib.rgcn_copy_to_device_async(self.ctx, C.c_void_p(base), _ptr(head), off_fi, 0))
-        fb = fi.view(np.uint8)
-        for lo in range(0, len(fb), 1 << 20):
-            part = fb[lo:lo + (1 << 20)]
-            self._check(self.lib.rgcn_copy_to_device_async(self.ctx, C.c_void_p(base + off_fi + lo), _ptr(part), len(part), 0))
-        self._check(self.lib.rgcn_rank_device(self.ctx, C.c_void_p(base + off_x), n, 1 if predict_object else 0,
-                                              C.c_void_p(base), C.c_void_p(base + off_fi), C.c_void_p(base + off_out),
-                                              C.c_void_p(base + off_out + 4 * n)))
-        out = np.empty(2 * n, dtype=np.int32)
-        self._check(self.lib.rgcn_copy_to_host(self.ctx, _ptr(out), C.c_void_p(base + off_out), 8 * n))
-        return out[:n].copy(), out[n:].copy()
+        base = self._rank_buf.ptr.value
+        # staged through the library's pinned slots (<= 1 MB each), ordered on the main stream, no host wait: the list
+        # (megabytes for the subject side of FB15k-237) travels while the queries are being scored
+        head = np.concatenate([fp.view(np.uint8), x.reshape(-1).view(np.uint8)])
+        for off, data in ((0, head), (off_fi, fi.view(np.uint8))):
+            for lo in range(0, len(data), 1 << 20):
+                part = data[lo:lo + (1 << 20)]
+                self._check(self.lib.rgcn_copy_to_device_async(self.ctx, C.c_void_p(base + off + lo), _ptr(part), len(part), 0))
+        return C.c_void_p(base), C.c_void_p(base + off_x), C.c_void_p(base + off_fi), base + off_out
+
+    def _read_staged(self, address, count):
+        out = np.empty(count, dtype=np.int32)
+        self._check(self.lib.rgcn_copy_to_host(self.ctx, _ptr(out), C.c_void_p(address), out.nbytes))
+        return out
+
+    def _ranks_staged(self, triples, filter_ptr, filter_idx, call):
+        """ranks and ranks_mixed: call(n, queries, filter pointers, filter list, raw out, filtered out) -> status"""
+        x = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
+        n = len(x)
+        if n == 0:
+            return np.zeros(0, np.int32), np.zeros(0, np.int32)
+        ptr, xd, idx, out = self._stage_queries(x, filter_ptr, filter_idx, 8 * n)
+        self._check(call(n, xd, ptr, idx, C.c_void_p(out), C.c_void_p(out + 4 * n)))
+        r = self._read_staged(out, 2 * n)
+        return r[:n].copy(), r[n:].copy()
+
+    def _topk_staged(self, queries, k, exclude_ptr, exclude_idx, call):
+        """topk and topk_mixed: call(n, k, queries, exclusion pointers, exclusion list, ids out, values out) -> status"""
+        x = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1, 3)
+        n, k = len(x), int(k)
+        if (exclude_ptr is None) != (exclude_idx is None):
+            raise ValueError("exclude_ptr and exclude_idx come together")
+        if n == 0:
+            return np.zeros((0, max(k, 0)), np.int32), np.zeros((0, max(k, 0)), np.float32)
+        has = exclude_ptr is not None
+        room = min(max(k, 0), 1024)        # (a k outside [1, RGCN_MAX_TOPK] is the library's to refuse: it writes nothing)
+        ptr, xd, idx, out = self._stage_queries(x, exclude_ptr if has else np.zeros(n + 1),
+                                                exclude_idx if has else np.zeros(0), 8 * n * room)
+        self._check(call(n, k, xd, ptr if has else None, idx if has else None, C.c_void_p(out),
+                         C.c_void_p(out + 4 * n * room)))
+        r = self._read_staged(out, 2 * n * k)
+        return r[:n * k].reshape(n, k).copy(), r[n * k:].view(np.float32).reshape(n, k).copy()
+
+    @contextlib.contextmanager
+    def _partner_energies(self, partner, n):
+        """the device address of `partner` -- a float32 [n, V] array (uploaded for the length of the `with`), a DeviceBuffer
+        or a device address (n = 0: not looked at, the call returns its empty answer)"""
+        if n == 0:
+            yield None
+        elif isinstance(partner, np.ndarray):
+            e = np.ascontiguousarray(partner, dtype=np.float32)
+            if e.shape != (n, self.V):
+                raise ValueError("partner energies must be [%d, %d], not %s" % (n, self.V, e.shape))
+            own = DeviceBuffer(self, e.nbytes).upload(e)
+            try:
+                yield own.ptr
+            finally:
+                own.free()
+        else:
+            yield partner.ptr if isinstance(partner, DeviceBuffer) else C.c_void_p(int(partner))
 
     def rank_energies_device(self):
         """device address of RGCN_BUF_RANK_ENERGIES (the [reserved queries, V] energies of the chunk scored last), or None
@@ -618,88 +663,20 @@ class Engine:
         rgcn_rank_mixed_device).  partner: the other model's energies for the same queries in the same order -- a
         float32 [N, V] numpy array (uploaded), a DeviceBuffer, or a device address (rank_energies_device() of another
         engine on the same GPU, complete and left alone until this call returns).  One chunk: N <= the reserve."""
-        x = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
-        n = len(x)
-        if n == 0:
-            return np.zeros(0, np.int32), np.zeros(0, np.int32)
-        fp = np.ascontiguousarray(filter_ptr, dtype=np.int64)
-        fi = np.ascontiguousarray(filter_idx, dtype=np.int32)
-        assert fp.shape == (n + 1,) and fp[-1] == len(fi)
-        own = None
-        if isinstance(partner, np.ndarray):
-            e = np.ascontiguousarray(partner, dtype=np.float32)
-            if e.shape != (n, self.V):
-                raise ValueError("partner energies must be [%d, %d], not %s" % (n, self.V, e.shape))
-            own = DeviceBuffer(self, e.nbytes).upload(e)
-            pp = own.ptr
-        elif isinstance(partner, DeviceBuffer):
-            pp = partner.ptr
-        else:
-            pp = C.c_void_p(int(partner))
-        try:
-            xd = DeviceBuffer(self, x.nbytes).upload(x)
-            fpd = DeviceBuffer(self, fp.nbytes).upload(fp)
-            fid = DeviceBuffer(self, max(fi.nbytes, 4))
-            if fi.nbytes:
-                self.copy_to_device(fid, fi)
-            out = DeviceBuffer(self, 8 * n)
-            base = out.ptr.value
-            try:
-                self._check(self.lib.rgcn_rank_mixed_device(self.ctx, xd.ptr, n, 1 if predict_object else 0, pp,
-                                                            C.c_float(float(weight)), fpd.ptr, fid.ptr, C.c_void_p(base),
-                                                            C.c_void_p(base + 4 * n)))
-                r = out.download(np.int32, (2 * n,))
-            finally:
-                for b in (xd, fpd, fid, out):
-                    b.free()
-        finally:
-            if own is not None:
-                own.free()
-        return r[:n].copy(), r[n:].copy()
+        with self._partner_energies(partner, np.size(triples) // 3) as pp:
+            return self._ranks_staged(triples, filter_ptr, filter_idx,
+                                      lambda n, x, ptr, idx, raw, filt: self.lib.rgcn_rank_mixed_device(
+                                          self.ctx, x, n, 1 if predict_object else 0, pp, C.c_float(float(weight)), ptr, idx,
+                                          raw, filt))
 
     def topk(self, queries, predict_object, k, exclude_ptr=None, exclude_idx=None):
         """The k best completions of every query on the codes of the last forward, best first (include/rgcn.h
         rgcn_topk_device): (idx int32 [N,k], energy float32 [N,k]), rows short of k answers padded with (-1, -inf).
         queries [N,3] rows (s, r, o) of which the column being predicted is not read; exclude_ptr int64 [N+1] /
         exclude_idx int32 [nnz]: per-row ids that may not be answered (both None: none)."""
-        x = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1, 3)
-        n, k = len(x), int(k)
-        if (exclude_ptr is None) != (exclude_idx is None):
-            raise ValueError("exclude_ptr and exclude_idx come together")
-        if n == 0:
-            return np.zeros((0, max(k, 0)), np.int32), np.zeros((0, max(k, 0)), np.float32)
-        has = exclude_ptr is not None
-        fp = np.ascontiguousarray(exclude_ptr if has else np.zeros(n + 1), dtype=np.int64)
-        fi = np.ascontiguousarray(exclude_idx if has else np.zeros(0), dtype=np.int32)
-        assert fp.shape == (n + 1,) and fp[-1] == len(fi)
-        # one staging buffer as in ranks(): exclusion pointers | queries | exclusion list | ids out | energies out
-        nnz = max(len(fi), 1)
-        off_x, off_fi = 8 * (n + 1), 8 * (n + 1) + 12 * n
-        off_out = (off_fi + 4 * nnz + 7) // 8 * 8
-        room = min(max(k, 0), 1024)        # (a k outside [1, RGCN_MAX_TOPK] is the library's to refuse: it writes nothing)
-        total = off_out + 8 * n * room
-        if getattr(self, "_rank_buf", None) is None or self._rank_buf.nbytes < total:
-            if getattr(self, "_rank_buf", None) is not None:
-                self._rank_buf.free()
-            self._rank_buf = DeviceBuffer(self, max(total, 1 << 20))
-        base = self._rank_buf.ptr.value if hasattr(self._rank_buf.ptr, "value") else int(self._rank_buf.ptr)
-        head = np.empty(off_fi, dtype=np.uint8)
-        head[:off_x] = fp.view(np.uint8)
-        head[off_x:] = x.reshape(-1).view(np.uint8)
-        for lo in range(0, off_fi, 1 << 20):
-            part = head[lo:lo + (1 << 20)]
-            self._check(self.lib.rgcn_copy_to_device_async(self.ctx, C.c_void_p(base + lo), _ptr(part), len(part), 0))
-        fb = fi.view(np.uint8)
-        for lo in range(0, len(fb), 1 << 20):
-            part = fb[lo:lo + (1 << 20)]
-            self._check(self.lib.rgcn_copy_to_device_async(self.ctx, C.c_void_p(base + off_fi + lo), _ptr(part), len(part), 0))
-        self._check(self.lib.rgcn_topk_device(self.ctx, C.c_void_p(base + off_x), n, 1 if predict_object else 0, k,
-                                              C.c_void_p(base) if has else None,
-                                              C.c_void_p(base + off_fi) if has else None, C.c_void_p(base + off_out),
-                                              C.c_void_p(base + off_out + 4 * n * k)))
-        out = np.empty(2 * n * k, dtype=np.int32)
-        self._check(self.lib.rgcn_copy_to_host(self.ctx, _ptr(out), C.c_void_p(base + off_out), 8 * n * k))
-        return out[:n * k].reshape(n, k).copy(), out[n * k:].view(np.float32).reshape(n, k).copy()
+        return self._topk_staged(queries, k, exclude_ptr, exclude_idx,
+                                 lambda n, k, x, ptr, idx, ids, energies: self.lib.rgcn_topk_device(
+                                     self.ctx, x, n, 1 if predict_object else 0, k, ptr, idx, ids, energies))
 
     def score_queries(self, queries, predict_object):
         """Energies of every entity for each query into RGCN_BUF_RANK_ENERGIES and nothing else (include/rgcn.h
@@ -722,49 +699,11 @@ class Engine:
         same order -- a float32 [N, V] numpy array (uploaded), a DeviceBuffer, or a device address
         (rank_energies_device() of another engine on the same GPU after its score_queries, left alone until this call
         returns).  One chunk: N <= the reserve."""
-        x = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1, 3)
-        n, k = len(x), int(k)
-        if (exclude_ptr is None) != (exclude_idx is None):
-            raise ValueError("exclude_ptr and exclude_idx come together")
-        if n == 0:
-            return np.zeros((0, max(k, 0)), np.int32), np.zeros((0, max(k, 0)), np.float32)
-        has = exclude_ptr is not None
-        fp = np.ascontiguousarray(exclude_ptr if has else np.zeros(n + 1), dtype=np.int64)
-        fi = np.ascontiguousarray(exclude_idx if has else np.zeros(0), dtype=np.int32)
-        assert fp.shape == (n + 1,) and fp[-1] == len(fi)
-        own = None
-        if isinstance(partner, np.ndarray):
-            e = np.ascontiguousarray(partner, dtype=np.float32)
-            if e.shape != (n, self.V):
-                raise ValueError("partner energies must be [%d, %d], not %s" % (n, self.V, e.shape))
-            own = DeviceBuffer(self, e.nbytes).upload(e)
-            pp = own.ptr
-        elif isinstance(partner, DeviceBuffer):
-            pp = partner.ptr
-        else:
-            pp = C.c_void_p(int(partner))
-        room = min(max(k, 0), 1024)        # (a k outside [1, RGCN_MAX_TOPK] is the library's to refuse: it writes nothing)
-        try:
-            xd = DeviceBuffer(self, x.nbytes).upload(x)
-            fpd = DeviceBuffer(self, fp.nbytes).upload(fp)
-            fid = DeviceBuffer(self, max(fi.nbytes, 4))
-            if fi.nbytes:
-                self.copy_to_device(fid, fi)
-            out = DeviceBuffer(self, max(8 * n * room, 8))
-            base = out.ptr.value
-            try:
-                self._check(self.lib.rgcn_topk_mixed_device(self.ctx, xd.ptr, n, 1 if predict_object else 0, k, pp,
-                                                            C.c_float(float(weight)), fpd.ptr if has else None,
-                                                            fid.ptr if has else None, C.c_void_p(base),
-                                                            C.c_void_p(base + 4 * n * room)))
-                r = out.download(np.int32, (2 * n * room,))
-            finally:
-                for b in (xd, fpd, fid, out):
-                    b.free()
-        finally:
-            if own is not None:
-                own.free()
-        return r[:n * k].reshape(n, k).copy(), r[n * k:].view(np.float32).reshape(n, k).copy()
+        with self._partner_energies(partner, np.size(queries) // 3) as pp:
+            return self._topk_staged(queries, k, exclude_ptr, exclude_idx,
+                                     lambda n, k, x, ptr, idx, ids, scores: self.lib.rgcn_topk_mixed_device(
+                                         self.ctx, x, n, 1 if predict_object else 0, k, pp, C.c_float(float(weight)), ptr,
+                                         idx, ids, scores))
 
     def optimizer_config(self, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, max_grad_norm=1.0):
         self._check(self.lib.rgcn_optimizer_config(self.ctx, lr, beta1, beta2, eps, max_grad_norm))

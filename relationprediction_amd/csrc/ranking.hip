@@ -32,7 +32,12 @@
 // Ensemble top-k (rgcn_topk_mixed_device) is the two together: k_mix_rows writes m for every entity of every query into a
 // scratch of its own, through the mixed_score k_rank_rows_mixed compares with, and k_topk_rows selects from that scratch
 // exactly as it selects from energies (it orders any floats).  rgcn_score_queries_device is how the partner produces its
-// energies for queries that have no gold entity: the top-k call's check, query kernel and GEMM, nothing after them.
+// energies for queries that have no gold entity: the shared scoring and nothing after it.
+//
+// One scoring path: all five calls are run_queries (bottom of the file) -- clear the verdict and launch k_rank_check,
+// then per chunk score_chunk (k_rank_query + the NT GEMM into ranking.q / ranking.s) and the call's own tail, then read
+// the verdict back -- and differ in the tail they hand it.  The two rank kernels are wrappers round one row template
+// (rank_row) and differ in the comparison they hand it.
 #include "rgcn_internal.h"
 
 namespace rgcn {
@@ -88,81 +93,27 @@ __global__ void k_rank_threshold(const float* __restrict__ S, int V, const int32
   thr[row] = key_float(hi);
 }
 
-__global__ void __launch_bounds__(256) k_rank_rows(const float* __restrict__ S, int V, const int32_t* __restrict__ X,
-                                                   int n, int predict_object, const int64_t* __restrict__ filt_ptr,
-                                                   const int32_t* __restrict__ filt_idx, const float* __restrict__ thr,
-                                                   int32_t* __restrict__ raw_rank, int32_t* __restrict__ filt_rank,
-                                                   int32_t* __restrict__ bad, const int64_t* __restrict__ filt_end) {
-  const int row = blockIdx.x;
-  if (row >= n) return;
-  __shared__ int red[2][256];
-  const float* s = S + (size_t)row * V;
-  const float t = thr[row];
+// Both ranks of ONE query row, by one workgroup of four wave64s: reaches(e) says whether entity e scores at least what the
+// gold entity does.  The row is walked once (lane-consecutive entities), the filter list 256 entries at a time, and the two
+// integer counts are summed by shuffles inside each wave and through eight LDS words across the four.
+template <class Reaches>
+__device__ __forceinline__ void rank_row(int row, int V, Reaches reaches, const int64_t* __restrict__ filt_ptr,
+                                         const int32_t* __restrict__ filt_idx, const int64_t* __restrict__ filt_end,
+                                         int32_t* __restrict__ raw_rank, int32_t* __restrict__ filt_rank,
+                                         int32_t* __restrict__ bad) {
+  __shared__ int red[2][4];
   int cnt = 0, fcnt = 0;
-  for (int e = threadIdx.x; e < V; e += 256) cnt += s[e] >= t ? 1 : 0;
+  for (int e = threadIdx.x; e < V; e += 256) cnt += reaches(e) ? 1 : 0;
   int64_t fb = filt_ptr[row], fe = filt_ptr[row + 1];
   // a negative, decreasing or overlong range (k_rank_check has flagged it: the call fails) is not walked at all --
   // nothing may fault before the verdict is read back
   if (fb < 0 || fe < fb || fe > *filt_end) fb = fe = 0;
-  bool oob = false;          // a filter entry out of range fails the call (k_rank_check holds the other checks)
-  for (int64_t j = fb + threadIdx.x; j < fe; j += 256) {
-    const int fi = filt_idx[j];
-    oob = oob || (unsigned)fi >= (unsigned)V;
-    fcnt += ((unsigned)fi < (unsigned)V && s[fi] >= t) ? 1 : 0;
-  }
-  if (oob) atomicAdd(bad, 1);
-  red[0][threadIdx.x] = cnt;
-  red[1][threadIdx.x] = fcnt;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      red[0][threadIdx.x] += red[0][threadIdx.x + w];
-      red[1][threadIdx.x] += red[1][threadIdx.x + w];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    raw_rank[row] = red[0][0];
-    filt_rank[row] = red[0][0] - red[1][0] + 1;
-  }
-}
-
-// m = (float)(w s_a + (1 - w) s_b), both products and the sum in double, rounded once: numpy's float64 expression gives the
-// same bits (no fused multiply-add: a contraction would round the first product differently from the host)
-__device__ __forceinline__ float mixed_score(double w, float ea, float eb) {
-#pragma clang fp contract(off)
-  const double a = w * (double)sigmoid_f32(ea);
-  const double b = (1.0 - w) * (double)sigmoid_f32(eb);
-  return (float)(a + b);
-}
-
-// One workgroup of four wave64s per query, k_rank_rows' shape: the two energy rows are read once (lane-consecutive
-// entities), the filter list is walked 256 entries at a time, and the two counts are summed by shuffles inside each wave
-// and through eight LDS words across the four.  Sb = the partner's rows, same queries in the same order, row stride V.
-__global__ void __launch_bounds__(256)
-k_rank_rows_mixed(const float* __restrict__ Sa, const float* __restrict__ Sb, int V, const int32_t* __restrict__ X, int n,
-                  int predict_object, double w, const int64_t* __restrict__ filt_ptr, const int32_t* __restrict__ filt_idx,
-                  int32_t* __restrict__ raw_rank, int32_t* __restrict__ filt_rank, int32_t* __restrict__ bad,
-                  const int64_t* __restrict__ filt_end) {
-  const int row = blockIdx.x;
-  if (row >= n) return;
-  __shared__ int red[2][4];
-  const float* a = Sa + (size_t)row * V;
-  const float* b = Sb + (size_t)row * V;
-  int gold = X[3 * row + (predict_object ? 2 : 0)];
-  if ((unsigned)gold >= (unsigned)V) gold = 0;      // (k_rank_check has flagged it: the call fails, nothing may fault)
-  const float mg = mixed_score(w, a[gold], b[gold]);
-  int cnt = 0, fcnt = 0;
-  for (int e = threadIdx.x; e < V; e += 256) cnt += mixed_score(w, a[e], b[e]) >= mg ? 1 : 0;
-  int64_t fb = filt_ptr[row], fe = filt_ptr[row + 1];
-  // as k_rank_rows: a flagged range is not walked, an entry out of range fails the call and is never dereferenced
-  if (fb < 0 || fe < fb || fe > *filt_end) fb = fe = 0;
-  bool oob = false;
+  bool oob = false;          // a filter entry out of range fails the call and is never dereferenced
   for (int64_t j = fb + threadIdx.x; j < fe; j += 256) {
     const int fi = filt_idx[j];
     const bool in = (unsigned)fi < (unsigned)V;
     oob = oob || !in;
-    if (in) fcnt += mixed_score(w, a[fi], b[fi]) >= mg ? 1 : 0;
+    if (in) fcnt += reaches(fi) ? 1 : 0;
   }
   if (oob) atomicAdd(bad, 1);
 #pragma unroll
@@ -182,6 +133,44 @@ k_rank_rows_mixed(const float* __restrict__ Sa, const float* __restrict__ Sb, in
   }
 }
 
+// (the wrappers' lambdas capture their scalars by value)
+__global__ void __launch_bounds__(256)
+k_rank_rows(const float* __restrict__ S, int V, int n, const int64_t* __restrict__ filt_ptr,
+            const int32_t* __restrict__ filt_idx, const float* __restrict__ thr, int32_t* __restrict__ raw_rank,
+            int32_t* __restrict__ filt_rank, int32_t* __restrict__ bad, const int64_t* __restrict__ filt_end) {
+  const int row = blockIdx.x;
+  if (row >= n) return;
+  const float* s = S + (size_t)row * V;
+  const float t = thr[row];
+  rank_row(row, V, [=](int e) { return s[e] >= t; }, filt_ptr, filt_idx, filt_end, raw_rank, filt_rank, bad);
+}
+
+// m = (float)(w s_a + (1 - w) s_b), both products and the sum in double, rounded once: numpy's float64 expression gives the
+// same bits (no fused multiply-add: a contraction would round the first product differently from the host)
+__device__ __forceinline__ float mixed_score(double w, float ea, float eb) {
+#pragma clang fp contract(off)
+  const double a = w * (double)sigmoid_f32(ea);
+  const double b = (1.0 - w) * (double)sigmoid_f32(eb);
+  return (float)(a + b);
+}
+
+// Sb = the partner's rows, same queries in the same order, row stride V
+__global__ void __launch_bounds__(256)
+k_rank_rows_mixed(const float* __restrict__ Sa, const float* __restrict__ Sb, int V, const int32_t* __restrict__ X, int n,
+                  int predict_object, double w, const int64_t* __restrict__ filt_ptr, const int32_t* __restrict__ filt_idx,
+                  int32_t* __restrict__ raw_rank, int32_t* __restrict__ filt_rank, int32_t* __restrict__ bad,
+                  const int64_t* __restrict__ filt_end) {
+  const int row = blockIdx.x;
+  if (row >= n) return;
+  const float* a = Sa + (size_t)row * V;
+  const float* b = Sb + (size_t)row * V;
+  int gold = X[3 * row + (predict_object ? 2 : 0)];
+  if ((unsigned)gold >= (unsigned)V) gold = 0;      // (k_rank_check has flagged it: the call fails, nothing may fault)
+  const float mg = mixed_score(w, a[gold], b[gold]);
+  rank_row(row, V, [=](int e) { return mixed_score(w, a[e], b[e]) >= mg; }, filt_ptr, filt_idx, filt_end, raw_rank,
+           filt_rank, bad);
+}
+
 // M[row, e] = mixed_score(w, Sa[row, e], Sb[row, e]): the mixed scores rgcn_topk_mixed_device selects from, the very
 // floats k_rank_rows_mixed compares.  Its shape -- one workgroup of four wave64s per query, both energy rows read once with
 // lane-consecutive entities -- and its cost, two double-precision exponentials per entity; the one write is the addition.
@@ -195,16 +184,23 @@ k_mix_rows(const float* __restrict__ Sa, const float* __restrict__ Sb, int V, in
   for (int e = threadIdx.x; e < V; e += 256) m[e] = mixed_score(w, a[e], b[e]);
 }
 
-// (the last entry of filt_ptr is the list's declared length: no range may end beyond it)
-__global__ void k_rank_check(const int32_t* __restrict__ X, int n, int V, int R, const int64_t* __restrict__ filt_ptr,
-                             const int32_t* __restrict__ filt_idx, int32_t* __restrict__ bad) {
+// The ids of a query that its call reads -- the given entity and the relation, and the gold entity where there is one
+// (with_gold: the rank forms; the top-k forms never look at the predicted column) -- and the ranges of its filter or
+// exclusion list, which may be absent (the last entry of list_ptr is the list's declared length: no range may end
+// beyond it).  The list's entries are range-checked where they are read, 256 lanes wide, in the row kernels: one thread
+// walking a list of 1,700 entries here was most of a call's time on the subject side of FB15k-237.
+__global__ void k_rank_check(const int32_t* __restrict__ X, int n, int V, int R, int predict_object, int with_gold,
+                             const int64_t* __restrict__ list_ptr, int32_t* __restrict__ bad) {
   const int row = blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n) return;
-  const int s = X[3 * row], r = X[3 * row + 1], o = X[3 * row + 2];
-  // (the filter entries themselves are range-checked where they are read, 256 lanes wide, in k_rank_rows: one thread
-  // walking a list of 1,700 entries here was most of a call's time on the subject side of FB15k-237)
-  const bool ok = s >= 0 && s < V && o >= 0 && o < V && r >= 0 && r < R && filt_ptr[row] >= 0 &&
-                  filt_ptr[row] <= filt_ptr[row + 1] && filt_ptr[row + 1] <= filt_ptr[n];
+  const int ent = X[3 * row + (predict_object ? 0 : 2)], rel = X[3 * row + 1];
+  bool ok = ent >= 0 && ent < V && rel >= 0 && rel < R;
+  if (with_gold) {
+    const int gold = X[3 * row + (predict_object ? 2 : 0)];
+    ok = ok && gold >= 0 && gold < V;
+  }
+  if (list_ptr)
+    ok = ok && list_ptr[row] >= 0 && list_ptr[row] <= list_ptr[row + 1] && list_ptr[row + 1] <= list_ptr[n];
   if (!ok) atomicAdd(bad, 1);
 }
 
@@ -263,7 +259,7 @@ k_topk_rows(const float* __restrict__ S, int V, int n, int k, const int64_t* __r
   __syncthreads();
   if (excl_ptr) {
     int64_t fb = excl_ptr[row], fe = excl_ptr[row + 1];
-    // (a negative, decreasing or overlong range has been flagged by k_topk_check: it is not walked at all)
+    // (a negative, decreasing or overlong range has been flagged by k_rank_check: it is not walked at all)
     if (fb < 0 || fe < fb || fe > *excl_end) fb = fe = 0;
     bool oob = false;
     for (int64_t j = fb + tid; j < fe; j += TOPK_THREADS) {
@@ -422,18 +418,6 @@ k_topk_rows(const float* __restrict__ S, int V, int n, int k, const int64_t* __r
   }
 }
 
-// the two ids of a query that are read, and the exclusion ranges (their entries are checked where they are read)
-__global__ void k_topk_check(const int32_t* __restrict__ X, int n, int V, int R, int predict_object,
-                             const int64_t* __restrict__ excl_ptr, int32_t* __restrict__ bad) {
-  const int row = blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= n) return;
-  const int ent = X[3 * row + (predict_object ? 0 : 2)], rel = X[3 * row + 1];
-  bool ok = ent >= 0 && ent < V && rel >= 0 && rel < R;
-  if (excl_ptr)
-    ok = ok && excl_ptr[row] >= 0 && excl_ptr[row] <= excl_ptr[row + 1] && excl_ptr[row + 1] <= excl_ptr[n];
-  if (!ok) atomicAdd(bad, 1);
-}
-
 }  // namespace
 
 void rank_free(rgcn_ctx* c) {
@@ -453,72 +437,82 @@ rgcn_status rank_reserve(rgcn_ctx* c, int64_t max_queries) {
   return RGCN_OK;
 }
 
-rgcn_status rank_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, const int64_t* filt_ptr,
-                         const int32_t* filt_idx, int32_t* raw_out, int32_t* filt_out) {
-  const float* codes = c->H[c->L];
-  // ids are validated on the device (out-of-range ids are rejected, never clamped): the verdict is read back at the END
-  // of the call, with no host wait in the middle -- until then the kernels below substitute id 0 for a bad id so that
-  // nothing faults, and the (meaningless) ranks of a rejected call are never returned
+// ---------------------------------------------------------------- the scoring path of all five calls
+// Ids are validated on the device (out-of-range ids are rejected, never clamped) and the verdict is read back at the END of
+// the call, with no host wait in the middle: until then the kernels substitute id 0 for a bad id and skip a bad range so
+// that nothing faults, and the (meaningless) answers of a rejected call are not to be used.
+static rgcn_status verdict_begin(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, bool with_gold,
+                                 const int64_t* list_ptr) {
   RGCN_HIP(c, hipMemsetAsync(c->ranking.bad, 0, sizeof(int32_t), c->stream));
-  hipLaunchKernelGGL(k_rank_check, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, X_dev, (int)N, c->V,
-                     c->R, filt_ptr, filt_idx, c->ranking.bad);
+  hipLaunchKernelGGL(k_rank_check, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, X_dev, (int)N, c->V, c->R,
+                     predict_object, with_gold ? 1 : 0, list_ptr, c->ranking.bad);
   RGCN_HIP(c, hipGetLastError());
-  for (int64_t b = 0; b < N; b += c->ranking.max) {
-    const int n = (int)std::min<int64_t>(c->ranking.max, N - b);
-    const int32_t* X = X_dev + 3 * b;
-    {
-      ProfScope ps(c, "rank_query", 4.0 * 3 * n * c->d, 0);
-      hipLaunchKernelGGL(k_rank_query, dim3((unsigned)n), dim3(128), 0, c->stream, codes, c->w_rel, X, n, c->d,
-                         predict_object, c->ranking.q, c->V, c->R);
-      RGCN_HIP(c, hipGetLastError());
-    }
-    RGCN_TRY(gemm_f32(c, "rank_scores", true, true, n, c->V, c->d, c->ranking.q, c->d, codes, c->d, c->ranking.s, c->V, 1));
-    {
-      ProfScope ps(c, "rank_rows", 4.0 * n * c->V, 0);
-      hipLaunchKernelGGL(k_rank_threshold, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, c->ranking.s, c->V, X, n,
-                         predict_object, c->ranking.thr);
-      hipLaunchKernelGGL(k_rank_rows, dim3((unsigned)n), dim3(256), 0, c->stream, c->ranking.s, c->V, X, n,
-                         predict_object, filt_ptr + b, filt_idx, c->ranking.thr, raw_out + b, filt_out + b, c->ranking.bad,
-                         filt_ptr + N);
-      RGCN_HIP(c, hipGetLastError());
-    }
-  }
-  int32_t bad = 0;
-  RGCN_HIP(c, hipMemcpyAsync(&bad, c->ranking.bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  RGCN_HIP(c, hipStreamSynchronize(c->stream));
-  if (bad) RGCN_FAIL(c, RGCN_ERR_INVALID, "rank: entity / relation / filter index out of range");
   return RGCN_OK;
 }
 
-// rank_compute's scoring (same check kernel, query kernel, GEMM and buffer) for ONE chunk, then the counts on the mixed
-// score.  c->ranking.s holds the context's own energies afterwards, unmodified; the partner's rows are only read.
-rgcn_status rank_mixed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, const float* partner,
-                               float weight, const int64_t* filt_ptr, const int32_t* filt_idx, int32_t* raw_out,
-                               int32_t* filt_out) {
-  const float* codes = c->H[c->L];
-  const int n = (int)N;
-  RGCN_HIP(c, hipMemsetAsync(c->ranking.bad, 0, sizeof(int32_t), c->stream));
-  hipLaunchKernelGGL(k_rank_check, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, X_dev, n, c->V, c->R,
-                     filt_ptr, filt_idx, c->ranking.bad);
-  RGCN_HIP(c, hipGetLastError());
-  {
-    ProfScope ps(c, "rank_query", 4.0 * 3 * n * c->d, 0);
-    hipLaunchKernelGGL(k_rank_query, dim3((unsigned)n), dim3(128), 0, c->stream, codes, c->w_rel, X_dev, n, c->d,
-                       predict_object, c->ranking.q, c->V, c->R);
-    RGCN_HIP(c, hipGetLastError());
-  }
-  RGCN_TRY(gemm_f32(c, "rank_scores", true, true, n, c->V, c->d, c->ranking.q, c->d, codes, c->d, c->ranking.s, c->V, 1));
-  {
-    ProfScope ps(c, "rank_rows_mixed", 8.0 * n * c->V, 0);
-    hipLaunchKernelGGL(k_rank_rows_mixed, dim3((unsigned)n), dim3(256), 0, c->stream, c->ranking.s, partner, c->V, X_dev, n,
-                       predict_object, (double)weight, filt_ptr, filt_idx, raw_out, filt_out, c->ranking.bad, filt_ptr + N);
-    RGCN_HIP(c, hipGetLastError());
-  }
+static rgcn_status verdict_end(rgcn_ctx* c, const char* refusal) {
   int32_t bad = 0;
   RGCN_HIP(c, hipMemcpyAsync(&bad, c->ranking.bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   RGCN_HIP(c, hipStreamSynchronize(c->stream));
-  if (bad) RGCN_FAIL(c, RGCN_ERR_INVALID, "rank (mixed): entity / relation / filter index out of range");
+  if (bad) RGCN_FAIL(c, RGCN_ERR_INVALID, refusal);
   return RGCN_OK;
+}
+
+// the query rows of X[0, n) into ranking.q, their energies against every entity into ranking.s
+static rgcn_status score_chunk(rgcn_ctx* c, const int32_t* X, int n, int predict_object) {
+  const float* codes = c->H[c->L];
+  {
+    ProfScope ps(c, "rank_query", 4.0 * 3 * n * c->d, 0);
+    hipLaunchKernelGGL(k_rank_query, dim3((unsigned)n), dim3(128), 0, c->stream, codes, c->w_rel, X, n, c->d,
+                       predict_object, c->ranking.q, c->V, c->R);
+    RGCN_HIP(c, hipGetLastError());
+  }
+  return gemm_f32(c, "rank_scores", true, true, n, c->V, c->d, c->ranking.q, c->d, codes, c->d, c->ranking.s, c->V, 1);
+}
+
+// One call: the check, then chunk by chunk of the reserve the scoring and tail(b, n, X) -- what the call does with the
+// energies of its queries [b, b + n), whose rows start at X -- then the verdict.  A call whose entry admits one chunk only
+// (the mixed forms, score queries) runs the loop once, with b = 0.
+template <class Tail>
+static rgcn_status run_queries(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, bool with_gold,
+                               const int64_t* list_ptr, const char* refusal, Tail tail) {
+  RGCN_TRY(verdict_begin(c, X_dev, N, predict_object, with_gold, list_ptr));
+  for (int64_t b = 0; b < N; b += c->ranking.max) {
+    const int n = (int)std::min<int64_t>(c->ranking.max, N - b);
+    RGCN_TRY(score_chunk(c, X_dev + 3 * b, n, predict_object));
+    RGCN_TRY(tail(b, n, X_dev + 3 * b));
+  }
+  return verdict_end(c, refusal);
+}
+
+rgcn_status rank_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, const int64_t* filt_ptr,
+                         const int32_t* filt_idx, int32_t* raw_out, int32_t* filt_out) {
+  return run_queries(c, X_dev, N, predict_object, true, filt_ptr, "rank: entity / relation / filter index out of range",
+                     [=](int64_t b, int n, const int32_t* X) -> rgcn_status {
+    ProfScope ps(c, "rank_rows", 4.0 * n * c->V, 0);
+    hipLaunchKernelGGL(k_rank_threshold, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, c->ranking.s, c->V, X, n,
+                       predict_object, c->ranking.thr);
+    hipLaunchKernelGGL(k_rank_rows, dim3((unsigned)n), dim3(256), 0, c->stream, c->ranking.s, c->V, n, filt_ptr + b,
+                       filt_idx, c->ranking.thr, raw_out + b, filt_out + b, c->ranking.bad, filt_ptr + N);
+    RGCN_HIP(c, hipGetLastError());
+    return RGCN_OK;
+  });
+}
+
+// The counts on the mixed score.  c->ranking.s holds the context's own energies afterwards, unmodified; the partner's rows
+// are only read.
+rgcn_status rank_mixed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, const float* partner,
+                               float weight, const int64_t* filt_ptr, const int32_t* filt_idx, int32_t* raw_out,
+                               int32_t* filt_out) {
+  return run_queries(c, X_dev, N, predict_object, true, filt_ptr,
+                     "rank (mixed): entity / relation / filter index out of range",
+                     [=](int64_t, int n, const int32_t* X) -> rgcn_status {
+    ProfScope ps(c, "rank_rows_mixed", 8.0 * n * c->V, 0);
+    hipLaunchKernelGGL(k_rank_rows_mixed, dim3((unsigned)n), dim3(256), 0, c->stream, c->ranking.s, partner, c->V, X, n,
+                       predict_object, (double)weight, filt_ptr, filt_idx, raw_out, filt_out, c->ranking.bad, filt_ptr + N);
+    RGCN_HIP(c, hipGetLastError());
+    return RGCN_OK;
+  });
 }
 
 // k_topk_rows' exclusion mask is dynamic LDS, above the default limit for large V: raise the kernel's limit on the context's
@@ -535,108 +529,57 @@ static rgcn_status topk_rows_configure(rgcn_ctx* c) {
   return RGCN_OK;
 }
 
+// k_topk_rows on the rows of `scores` (energies or mixed scores: it orders any floats) for the queries [b, b + n) of a call
+// of N, under the ProfScope `scope`.  Design bytes: four select passes and the gather read the row (from L2 after the first).
+static rgcn_status topk_rows_launch(rgcn_ctx* c, const char* scope, const float* scores, int64_t b, int n, int64_t N, int k,
+                                    const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out, float* val_out) {
+  const size_t mask_bytes = (size_t)((c->V + 31) / 32) * sizeof(uint32_t);
+  ProfScope ps(c, scope, 5.0 * 4.0 * n * c->V + 8.0 * n * k, 0, 4.0 * n * c->V + 8.0 * n * k);
+  hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)n), dim3(TOPK_THREADS), mask_bytes, c->stream, scores, c->V, n, k,
+                     excl_ptr ? excl_ptr + b : nullptr, excl_idx, excl_ptr ? excl_ptr + N : nullptr,
+                     idx_out + (size_t)b * k, val_out + (size_t)b * k, c->ranking.bad);
+  RGCN_HIP(c, hipGetLastError());
+  return RGCN_OK;
+}
+
 rgcn_status topk_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, int k,
                          const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out, float* energy_out) {
-  const float* codes = c->H[c->L];
-  const size_t mask_bytes = (size_t)((c->V + 31) / 32) * sizeof(uint32_t);
   RGCN_TRY(topk_rows_configure(c));
-  // as rank_compute: ids are validated on the device, id 0 stands in for a bad one until the verdict is read back at the
-  // end of the call, and the (meaningless) answers of a rejected call are not to be used
-  RGCN_HIP(c, hipMemsetAsync(c->ranking.bad, 0, sizeof(int32_t), c->stream));
-  hipLaunchKernelGGL(k_topk_check, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, X_dev, (int)N, c->V, c->R,
-                     predict_object, excl_ptr, c->ranking.bad);
-  RGCN_HIP(c, hipGetLastError());
-  for (int64_t b = 0; b < N; b += c->ranking.max) {
-    const int n = (int)std::min<int64_t>(c->ranking.max, N - b);
-    const int32_t* X = X_dev + 3 * b;
-    {
-      ProfScope ps(c, "rank_query", 4.0 * 3 * n * c->d, 0);
-      hipLaunchKernelGGL(k_rank_query, dim3((unsigned)n), dim3(128), 0, c->stream, codes, c->w_rel, X, n, c->d,
-                         predict_object, c->ranking.q, c->V, c->R);
-      RGCN_HIP(c, hipGetLastError());
-    }
-    RGCN_TRY(gemm_f32(c, "rank_scores", true, true, n, c->V, c->d, c->ranking.q, c->d, codes, c->d, c->ranking.s, c->V, 1));
-    {
-      // design bytes: four select passes and the gather read the row (from L2 after the first)
-      ProfScope ps(c, "topk_rows", 5.0 * 4.0 * n * c->V + 8.0 * n * k, 0, 4.0 * n * c->V + 8.0 * n * k);
-      hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)n), dim3(TOPK_THREADS), mask_bytes, c->stream, c->ranking.s, c->V, n, k,
-                         excl_ptr ? excl_ptr + b : nullptr, excl_idx, excl_ptr ? excl_ptr + N : nullptr,
-                         idx_out + (size_t)b * k, energy_out + (size_t)b * k, c->ranking.bad);
-      RGCN_HIP(c, hipGetLastError());
-    }
-  }
-  int32_t bad = 0;
-  RGCN_HIP(c, hipMemcpyAsync(&bad, c->ranking.bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  RGCN_HIP(c, hipStreamSynchronize(c->stream));
-  if (bad) RGCN_FAIL(c, RGCN_ERR_INVALID, "topk: entity / relation / exclusion index out of range");
-  return RGCN_OK;
+  return run_queries(c, X_dev, N, predict_object, false, excl_ptr, "topk: entity / relation / exclusion index out of range",
+                     [=](int64_t b, int n, const int32_t*) {
+    return topk_rows_launch(c, "topk_rows", c->ranking.s, b, n, N, k, excl_ptr, excl_idx, idx_out, energy_out);
+  });
 }
 
-// topk_compute's validation, query kernel and GEMM for ONE chunk and nothing after them: c->ranking.s holds the energies of
-// queries that have no gold entity -- what the partner model of an ensemble top-k hands over
+// The scoring and nothing after it: c->ranking.s holds the energies of queries that have no gold entity -- what the partner
+// model of an ensemble top-k hands over
 rgcn_status score_queries_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object) {
-  const float* codes = c->H[c->L];
-  const int n = (int)N;
-  RGCN_HIP(c, hipMemsetAsync(c->ranking.bad, 0, sizeof(int32_t), c->stream));
-  hipLaunchKernelGGL(k_topk_check, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, X_dev, n, c->V, c->R,
-                     predict_object, (const int64_t*)nullptr, c->ranking.bad);
-  RGCN_HIP(c, hipGetLastError());
-  {
-    ProfScope ps(c, "rank_query", 4.0 * 3 * n * c->d, 0);
-    hipLaunchKernelGGL(k_rank_query, dim3((unsigned)n), dim3(128), 0, c->stream, codes, c->w_rel, X_dev, n, c->d,
-                       predict_object, c->ranking.q, c->V, c->R);
-    RGCN_HIP(c, hipGetLastError());
-  }
-  RGCN_TRY(gemm_f32(c, "rank_scores", true, true, n, c->V, c->d, c->ranking.q, c->d, codes, c->d, c->ranking.s, c->V, 1));
-  int32_t bad = 0;
-  RGCN_HIP(c, hipMemcpyAsync(&bad, c->ranking.bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  RGCN_HIP(c, hipStreamSynchronize(c->stream));
-  if (bad) RGCN_FAIL(c, RGCN_ERR_INVALID, "score queries: entity / relation index out of range");
-  return RGCN_OK;
+  return run_queries(c, X_dev, N, predict_object, false, nullptr, "score queries: entity / relation index out of range",
+                     [](int64_t, int, const int32_t*) { return RGCN_OK; });
 }
 
-// topk_compute's scoring for ONE chunk, then the mixed scores of every entity into c->ranking.mixed (k_mix_rows) and
-// k_topk_rows, as it stands, on those instead of on the energies.  c->ranking.s holds the context's own energies afterwards,
-// unmodified; the partner's rows are only read.  The [reserved queries, V] scratch is allocated here, on the first call
-// after a (growing) rank_reserve: a context that never asks the ensemble never holds it.
+// The mixed scores of every entity into c->ranking.mixed (k_mix_rows), then k_topk_rows, as it stands, on those instead of
+// on the energies.  c->ranking.s holds the context's own energies afterwards, unmodified; the partner's rows are only read.
+// The [reserved queries, V] scratch is allocated here, on the first call after a (growing) rank_reserve: a context that
+// never asks the ensemble never holds it.
 rgcn_status topk_mixed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, int k, const float* partner,
                                float weight, const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out,
                                float* score_out) {
-  const float* codes = c->H[c->L];
-  const int n = (int)N;
-  const size_t mask_bytes = (size_t)((c->V + 31) / 32) * sizeof(uint32_t);
   RGCN_TRY(topk_rows_configure(c));
   RankBufs& q = c->ranking;
   if (!q.mixed) RGCN_TRY(dmalloc(c, q.pool, &q.mixed, (size_t)q.max * c->V, false));
-  RGCN_HIP(c, hipMemsetAsync(q.bad, 0, sizeof(int32_t), c->stream));
-  hipLaunchKernelGGL(k_topk_check, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, X_dev, n, c->V, c->R,
-                     predict_object, excl_ptr, q.bad);
-  RGCN_HIP(c, hipGetLastError());
-  {
-    ProfScope ps(c, "rank_query", 4.0 * 3 * n * c->d, 0);
-    hipLaunchKernelGGL(k_rank_query, dim3((unsigned)n), dim3(128), 0, c->stream, codes, c->w_rel, X_dev, n, c->d,
-                       predict_object, q.q, c->V, c->R);
-    RGCN_HIP(c, hipGetLastError());
-  }
-  RGCN_TRY(gemm_f32(c, "rank_scores", true, true, n, c->V, c->d, q.q, c->d, codes, c->d, q.s, c->V, 1));
-  {
-    // two rows read, one written, each byte once
-    ProfScope ps(c, "topk_mix_rows", 12.0 * n * c->V, 0);
-    hipLaunchKernelGGL(k_mix_rows, dim3((unsigned)n), dim3(256), 0, c->stream, q.s, partner, c->V, n, (double)weight, q.mixed);
-    RGCN_HIP(c, hipGetLastError());
-  }
-  {
-    // design bytes: as topk_rows -- four select passes and the gather read the row (from L2 after the first)
-    ProfScope ps(c, "topk_rows_mixed", 5.0 * 4.0 * n * c->V + 8.0 * n * k, 0, 4.0 * n * c->V + 8.0 * n * k);
-    hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)n), dim3(TOPK_THREADS), mask_bytes, c->stream, q.mixed, c->V, n, k, excl_ptr,
-                       excl_idx, excl_ptr ? excl_ptr + N : nullptr, idx_out, score_out, q.bad);
-    RGCN_HIP(c, hipGetLastError());
-  }
-  int32_t bad = 0;
-  RGCN_HIP(c, hipMemcpyAsync(&bad, q.bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  RGCN_HIP(c, hipStreamSynchronize(c->stream));
-  if (bad) RGCN_FAIL(c, RGCN_ERR_INVALID, "topk (mixed): entity / relation / exclusion index out of range");
-  return RGCN_OK;
+  return run_queries(c, X_dev, N, predict_object, false, excl_ptr,
+                     "topk (mixed): entity / relation / exclusion index out of range",
+                     [=](int64_t b, int n, const int32_t*) -> rgcn_status {
+    {
+      // two rows read, one written, each byte once
+      ProfScope ps(c, "topk_mix_rows", 12.0 * n * c->V, 0);
+      hipLaunchKernelGGL(k_mix_rows, dim3((unsigned)n), dim3(256), 0, c->stream, c->ranking.s, partner, c->V, n,
+                         (double)weight, c->ranking.mixed);
+      RGCN_HIP(c, hipGetLastError());
+    }
+    return topk_rows_launch(c, "topk_rows_mixed", c->ranking.mixed, b, n, N, k, excl_ptr, excl_idx, idx_out, score_out);
+  });
 }
 
 }  // namespace rgcn

@@ -1015,16 +1015,37 @@ rgcn_status rgcn_rank_reserve(rgcn_ctx* c, int64_t max_queries) {
   return rank_reserve(c, max_queries);
 }
 
+// What the five query entries below require before any device work, in this order; `checks` names the ones that apply to
+// `entry` beside those that apply to all (arguments, no capture, a forward, a reserve).  world > 1: the codes are
+// replicated after the last exchange, so the queries need no collective -- each rank passes its own slice of them and the
+// caller concatenates.
+enum : unsigned { QUERY_WEIGHT = 1, QUERY_TOPK = 2, QUERY_ONE_CHUNK = 4 };
+static rgcn_status query_preconditions(rgcn_ctx* c, const char* entry, unsigned checks, bool args_ok, int64_t n,
+                                       float weight = 0.f, int32_t k = 0) {
+  const std::string name(entry);
+  if (!args_ok) RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
+  if ((checks & QUERY_WEIGHT) && !(weight >= 0.0f && weight <= 1.0f))
+    RGCN_FAIL(c, RGCN_ERR_INVALID, name + ": weight must be in [0, 1]");
+  if ((checks & QUERY_TOPK) && (k < 1 || k > c->V || k > RGCN_MAX_TOPK))
+    RGCN_FAIL(c, RGCN_ERR_INVALID, name + ": k must be in [1, min(EntityCount, " + std::to_string(RGCN_MAX_TOPK) + ")]");
+  if ((checks & QUERY_TOPK) && c->V > RGCN_MAX_TOPK_ENTITIES)
+    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, name + ": EntityCount above " + std::to_string(RGCN_MAX_TOPK_ENTITIES) +
+                                           " (a row's exclusion mask must fit in LDS)");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "this call synchronises with the device: not allowed between rgcn_capture_begin and rgcn_capture_end");
+  if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, name + " needs a completed rgcn_forward (test mode on the full graph)");
+  if (c->ranking.max <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_rank_reserve first");
+  if ((checks & QUERY_ONE_CHUNK) && n > c->ranking.max)
+    RGCN_FAIL(c, RGCN_ERR_INVALID, name + ": one chunk only -- num_queries above what rgcn_rank_reserve sized (the score "
+                                          "buffers, this context's and a partner's, hold one chunk)");
+  return RGCN_OK;
+}
+
 rgcn_status rgcn_rank_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32_t predict_object,
                              const int64_t* filter_ptr_dev, const int32_t* filter_idx_dev, int32_t* raw_rank_dev,
                              int32_t* filtered_rank_dev) {
   RGCN_NEED(c);
-  if (n < 0 || (n > 0 && (!x_dev || !filter_ptr_dev || !raw_rank_dev || !filtered_rank_dev)))
-    RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
-  if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_rank_device needs a completed rgcn_forward (test mode on the full graph)");
-  // world > 1: the codes are replicated after the last exchange, so ranking needs no collective -- each rank
-  // passes its own slice of the queries and the caller concatenates
-  if (c->ranking.max <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_rank_reserve first");
+  RGCN_TRY(query_preconditions(c, "rgcn_rank_device", 0,
+                               n >= 0 && (n == 0 || (x_dev && filter_ptr_dev && raw_rank_dev && filtered_rank_dev)), n));
   if (n == 0) return RGCN_OK;
   return rank_compute(c, x_dev, n, predict_object ? 1 : 0, filter_ptr_dev, filter_idx_dev, raw_rank_dev, filtered_rank_dev);
 }
@@ -1035,15 +1056,10 @@ rgcn_status rgcn_rank_mixed_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n,
                                    const float* partner_energies_dev, float weight, const int64_t* filter_ptr_dev,
                                    const int32_t* filter_idx_dev, int32_t* raw_rank_dev, int32_t* filtered_rank_dev) {
   RGCN_NEED(c);
-  if (n < 0 || (n > 0 && (!x_dev || !partner_energies_dev || !filter_ptr_dev || !raw_rank_dev || !filtered_rank_dev)))
-    RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
-  if (!(weight >= 0.0f && weight <= 1.0f)) RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_rank_mixed_device: weight must be in [0, 1]");
-  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "this call synchronises with the device: not allowed between rgcn_capture_begin and rgcn_capture_end");
-  if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_rank_mixed_device needs a completed rgcn_forward (test mode on the full graph)");
-  if (c->ranking.max <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_rank_reserve first");
-  if (n > c->ranking.max)
-    RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_rank_mixed_device: one chunk only -- num_queries above what rgcn_rank_reserve sized "
-                                   "(the partner's buffer has its own chunking)");
+  RGCN_TRY(query_preconditions(c, "rgcn_rank_mixed_device", QUERY_WEIGHT | QUERY_ONE_CHUNK,
+                               n >= 0 && (n == 0 || (x_dev && partner_energies_dev && filter_ptr_dev && raw_rank_dev &&
+                                                     filtered_rank_dev)),
+                               n, weight));
   if (n == 0) return RGCN_OK;
   return rank_mixed_compute(c, x_dev, n, predict_object ? 1 : 0, partner_energies_dev, weight, filter_ptr_dev, filter_idx_dev,
                             raw_rank_dev, filtered_rank_dev);
@@ -1053,30 +1069,17 @@ rgcn_status rgcn_topk_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32
                              const int64_t* exclude_ptr_dev, const int32_t* exclude_idx_dev, int32_t* topk_idx_dev,
                              float* topk_energy_dev) {
   RGCN_NEED(c);
-  if (n < 0 || (n > 0 && (!x_dev || !topk_idx_dev || !topk_energy_dev)) || (!exclude_ptr_dev != !exclude_idx_dev))
-    RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
-  if (k < 1 || k > c->V || k > RGCN_MAX_TOPK)
-    RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_topk_device: k must be in [1, min(EntityCount, " + std::to_string(RGCN_MAX_TOPK) + ")]");
-  if (c->V > RGCN_MAX_TOPK_ENTITIES)
-    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "rgcn_topk_device: EntityCount above " + std::to_string(RGCN_MAX_TOPK_ENTITIES) +
-                                           " (a row's exclusion mask must fit in LDS)");
-  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "this call synchronises with the device: not allowed between rgcn_capture_begin and rgcn_capture_end");
-  if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_topk_device needs a completed rgcn_forward (test mode on the full graph)");
-  // world > 1: as rgcn_rank_device -- the codes are replicated after the last exchange, every rank answers its own queries
-  if (c->ranking.max <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_rank_reserve first");
+  RGCN_TRY(query_preconditions(c, "rgcn_topk_device", QUERY_TOPK,
+                               n >= 0 && (n == 0 || (x_dev && topk_idx_dev && topk_energy_dev)) &&
+                                   !exclude_ptr_dev == !exclude_idx_dev,
+                               n, 0.f, k));
   if (n == 0) return RGCN_OK;
   return topk_compute(c, x_dev, n, predict_object ? 1 : 0, k, exclude_ptr_dev, exclude_idx_dev, topk_idx_dev, topk_energy_dev);
 }
 
 rgcn_status rgcn_score_queries_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32_t predict_object) {
   RGCN_NEED(c);
-  if (n < 0 || (n > 0 && !x_dev)) RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
-  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "this call synchronises with the device: not allowed between rgcn_capture_begin and rgcn_capture_end");
-  if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_score_queries_device needs a completed rgcn_forward (test mode on the full graph)");
-  if (c->ranking.max <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_rank_reserve first");
-  if (n > c->ranking.max)
-    RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_score_queries_device: one chunk only -- num_queries above what rgcn_rank_reserve "
-                                   "sized (the buffer holds one chunk)");
+  RGCN_TRY(query_preconditions(c, "rgcn_score_queries_device", QUERY_ONE_CHUNK, n >= 0 && (n == 0 || x_dev), n));
   if (n == 0) return RGCN_OK;
   return score_queries_compute(c, x_dev, n, predict_object ? 1 : 0);
 }
@@ -1085,21 +1088,10 @@ rgcn_status rgcn_topk_mixed_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n,
                                    const float* partner_energies_dev, float weight, const int64_t* exclude_ptr_dev,
                                    const int32_t* exclude_idx_dev, int32_t* topk_idx_dev, float* topk_score_dev) {
   RGCN_NEED(c);
-  if (n < 0 || (n > 0 && (!x_dev || !partner_energies_dev || !topk_idx_dev || !topk_score_dev)) ||
-      (!exclude_ptr_dev != !exclude_idx_dev))
-    RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
-  if (!(weight >= 0.0f && weight <= 1.0f)) RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_topk_mixed_device: weight must be in [0, 1]");
-  if (k < 1 || k > c->V || k > RGCN_MAX_TOPK)
-    RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_topk_mixed_device: k must be in [1, min(EntityCount, " + std::to_string(RGCN_MAX_TOPK) + ")]");
-  if (c->V > RGCN_MAX_TOPK_ENTITIES)
-    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "rgcn_topk_mixed_device: EntityCount above " + std::to_string(RGCN_MAX_TOPK_ENTITIES) +
-                                           " (a row's exclusion mask must fit in LDS)");
-  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "this call synchronises with the device: not allowed between rgcn_capture_begin and rgcn_capture_end");
-  if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_topk_mixed_device needs a completed rgcn_forward (test mode on the full graph)");
-  if (c->ranking.max <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_rank_reserve first");
-  if (n > c->ranking.max)
-    RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_topk_mixed_device: one chunk only -- num_queries above what rgcn_rank_reserve sized "
-                                   "(the partner's buffer has its own chunking)");
+  RGCN_TRY(query_preconditions(c, "rgcn_topk_mixed_device", QUERY_WEIGHT | QUERY_TOPK | QUERY_ONE_CHUNK,
+                               n >= 0 && (n == 0 || (x_dev && partner_energies_dev && topk_idx_dev && topk_score_dev)) &&
+                                   !exclude_ptr_dev == !exclude_idx_dev,
+                               n, weight, k));
   if (n == 0) return RGCN_OK;
   return topk_mixed_compute(c, x_dev, n, predict_object ? 1 : 0, k, partner_energies_dev, weight, exclude_ptr_dev,
                             exclude_idx_dev, topk_idx_dev, topk_score_dev);

@@ -735,6 +735,7 @@ void neighborhood_free(rgcn_ctx* c);
 // ---- ranking.hip
 rgcn_status rank_reserve(rgcn_ctx* c, int64_t max_queries);
 void rank_free(rgcn_ctx* c);
+// the five query calls: one scoring path (run_queries) and the call's own tail; each synchronises and returns the verdict
 rgcn_status rank_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, const int64_t* filt_ptr,
                          const int32_t* filt_idx, int32_t* raw_out, int32_t* filt_out);
 rgcn_status rank_mixed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, const float* partner_dev,

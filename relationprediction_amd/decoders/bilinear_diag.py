@@ -104,59 +104,45 @@ class BilinearDiag(Model):
     def device_loss(self):
         return self.next_component.get_runtime().loss()
 
+    def _scoring_runtime(self, graph):
+        """the runtime with `graph` fed: re-encoded only when the graph or the weights changed"""
+        variables = self.get_test_input_variables()
+        if self.needs_graph() and (getattr(self, '_ranks_graph', None) is not graph or variables[0].value is None):
+            variables[0].feed(graph)
+            self._ranks_graph = graph
+        return self.next_component.get_runtime()
+
     def device_ranks(self, graph, triplets, predict_object, filter_ptr, filter_idx):
         """Ranks of the gold subjects / objects of `triplets` against every entity, codes from a test-mode
         pass over `graph` (what score_all_subjects / score_all_objects + MrrScore.append_line compute)."""
-        variables = self.get_test_input_variables()
-        if self.needs_graph() and (getattr(self, '_ranks_graph', None) is not graph or variables[0].value is None):
-            variables[0].feed(graph)          # re-encoded only when the graph or the weights changed
-            self._ranks_graph = graph
-        return self.next_component.get_runtime().ranks(triplets, predict_object, filter_ptr, filter_idx)
+        return self._scoring_runtime(graph).ranks(triplets, predict_object, filter_ptr, filter_idx)
 
     def device_ranks_mixed(self, graph, triplets, predict_object, partner, weight, filter_ptr, filter_idx):
         """device_ranks under weight * this model's score + (1 - weight) * another model's (rgcn_rank_mixed_device):
         partner = that model's energies for the same triplets in the same order, a float32 [N, EntityCount] array or the
         device address of its engine's score buffer (Engine.rank_energies_device, same GPU); one chunk of at most
         Scorer.chunk_size triplets."""
-        variables = self.get_test_input_variables()
-        if self.needs_graph() and (getattr(self, '_ranks_graph', None) is not graph or variables[0].value is None):
-            variables[0].feed(graph)
-            self._ranks_graph = graph
-        return self.next_component.get_runtime().ranks_mixed(triplets, predict_object, partner, weight, filter_ptr,
-                                                             filter_idx)
+        return self._scoring_runtime(graph).ranks_mixed(triplets, predict_object, partner, weight, filter_ptr, filter_idx)
 
     def device_topk(self, graph, queries, predict_object, k, exclude_ptr=None, exclude_idx=None):
         """The k most plausible objects of (s, r, ?) (predict_object) or subjects of (?, r, o) for every row of
         `queries`, best first, leaving out row i's exclude_idx[exclude_ptr[i]:exclude_ptr[i + 1]]; codes from a
         test-mode pass over `graph`.  Returns (entity ids int32 [N,k], energies float32 [N,k]); the column being
         predicted is not read; rows short of k answers end in (-1, -inf).  Scores are _sigmoid(energies)."""
-        variables = self.get_test_input_variables()
-        if self.needs_graph() and (getattr(self, '_ranks_graph', None) is not graph or variables[0].value is None):
-            variables[0].feed(graph)          # re-encoded only when the graph or the weights changed
-            self._ranks_graph = graph
-        return self.next_component.get_runtime().topk(queries, predict_object, k, exclude_ptr, exclude_idx)
+        return self._scoring_runtime(graph).topk(queries, predict_object, k, exclude_ptr, exclude_idx)
 
     def device_score_queries(self, graph, queries, predict_object):
         """Energies of every entity for each row of `queries` (the column being predicted is not read), left in the
         engine's score buffer (rgcn_score_queries_device; Engine.rank_energies_device is its address): what the other
         model of an ensemble hands to device_topk_mixed.  One chunk of at most Scorer.chunk_size queries."""
-        variables = self.get_test_input_variables()
-        if self.needs_graph() and (getattr(self, '_ranks_graph', None) is not graph or variables[0].value is None):
-            variables[0].feed(graph)          # re-encoded only when the graph or the weights changed
-            self._ranks_graph = graph
-        self.next_component.get_runtime().score_queries(queries, predict_object)
+        self._scoring_runtime(graph).score_queries(queries, predict_object)
 
     def device_topk_mixed(self, graph, queries, predict_object, k, partner, weight, exclude_ptr=None, exclude_idx=None):
         """device_topk under weight * this model's score + (1 - weight) * another model's (rgcn_topk_mixed_device):
         partner = that model's energies for the same queries in the same order, a float32 [N, EntityCount] array or the
         device address of its engine's score buffer (same GPU).  Returns (entity ids int32 [N,k], mixed scores float32
         [N,k]) ordered by (mixed score descending, entity id ascending); one chunk of at most Scorer.chunk_size queries."""
-        variables = self.get_test_input_variables()
-        if self.needs_graph() and (getattr(self, '_ranks_graph', None) is not graph or variables[0].value is None):
-            variables[0].feed(graph)
-            self._ranks_graph = graph
-        return self.next_component.get_runtime().topk_mixed(queries, predict_object, k, partner, weight, exclude_ptr,
-                                                            exclude_idx)
+        return self._scoring_runtime(graph).topk_mixed(queries, predict_object, k, partner, weight, exclude_ptr, exclude_idx)
 
     def predict_top(self, predict_object, k, exclude_ptr=None, exclude_idx=None):
         """device_topk restated eagerly on predict_all_object_scores / predict_all_subject_scores of the triples fed

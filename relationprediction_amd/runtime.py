@@ -297,50 +297,38 @@ class EncoderRuntime(object):
     def loss(self):
         return self.engine.loss()
 
-    def ranks(self, triples, predict_object, filter_ptr, filter_idx, chunk=2048):
-        """Raw / filtered ranks on the codes of a test-mode forward over the fed graph."""
+    def _scoring_engine(self, chunk):
+        """the engine after a test-mode forward over the fed graph, with room for `chunk` queries at a time"""
         self.forward('test')
         if self._rank_reserved < chunk:
             self.engine.rank_reserve(chunk)
             self._rank_reserved = chunk
-        return self.engine.ranks(triples, predict_object, filter_ptr, filter_idx)
+        return self.engine
+
+    def ranks(self, triples, predict_object, filter_ptr, filter_idx, chunk=2048):
+        """Raw / filtered ranks on the codes of a test-mode forward over the fed graph."""
+        return self._scoring_engine(chunk).ranks(triples, predict_object, filter_ptr, filter_idx)
 
     def ranks_mixed(self, triples, predict_object, partner, weight, filter_ptr, filter_idx, chunk=2048):
         """ranks() on weight * own score + (1 - weight) * partner score (rgcn_rank_mixed_device); partner: the other
         model's [N, V] energies for the same triples, an array or a device address; N <= chunk."""
-        self.forward('test')
-        if self._rank_reserved < chunk:
-            self.engine.rank_reserve(chunk)
-            self._rank_reserved = chunk
-        return self.engine.ranks_mixed(triples, predict_object, partner, weight, filter_ptr, filter_idx)
+        return self._scoring_engine(chunk).ranks_mixed(triples, predict_object, partner, weight, filter_ptr, filter_idx)
 
     def topk(self, queries, predict_object, k, exclude_ptr=None, exclude_idx=None, chunk=2048):
         """The k best completions of every query, best first, on the codes of a test-mode forward over the fed graph
         (rgcn_topk_device): (entity ids int32 [N,k], energies float32 [N,k])."""
-        self.forward('test')
-        if self._rank_reserved < chunk:
-            self.engine.rank_reserve(chunk)
-            self._rank_reserved = chunk
-        return self.engine.topk(queries, predict_object, k, exclude_ptr, exclude_idx)
+        return self._scoring_engine(chunk).topk(queries, predict_object, k, exclude_ptr, exclude_idx)
 
     def score_queries(self, queries, predict_object, chunk=2048):
         """The energies of every entity for each query, left in the engine's score buffer (rgcn_score_queries_device):
         what another runtime's topk_mixed reads through engine.rank_energies_device(); N <= chunk."""
-        self.forward('test')
-        if self._rank_reserved < chunk:
-            self.engine.rank_reserve(chunk)
-            self._rank_reserved = chunk
-        self.engine.score_queries(queries, predict_object)
+        self._scoring_engine(chunk).score_queries(queries, predict_object)
 
     def topk_mixed(self, queries, predict_object, k, partner, weight, exclude_ptr=None, exclude_idx=None, chunk=2048):
         """topk() on weight * own score + (1 - weight) * partner score (rgcn_topk_mixed_device): (entity ids int32 [N,k],
         mixed scores float32 [N,k]); partner: the other model's [N, V] energies for the same queries, an array or a
         device address; N <= chunk."""
-        self.forward('test')
-        if self._rank_reserved < chunk:
-            self.engine.rank_reserve(chunk)
-            self._rank_reserved = chunk
-        return self.engine.topk_mixed(queries, predict_object, k, partner, weight, exclude_ptr, exclude_idx)
+        return self._scoring_engine(chunk).topk_mixed(queries, predict_object, k, partner, weight, exclude_ptr, exclude_idx)
 
     def backward(self, dcodes):
         if self._state is None or self._state[1] != 'train':

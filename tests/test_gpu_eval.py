@@ -175,6 +175,140 @@ def test_rank_argument_checks(native):
         eng.close()
 
 
+STATE = 4                                                          # RGCN_ERR_STATE
+
+
+def embedding_engine(native, V, R, d, w_emb, w_rel, reserve):
+    eng = native.Engine(V, R, d, 0, "embedding", 1)
+    eng.set_params({"W_emb": w_emb, "b_emb": np.zeros(d, np.float32), "W_relation": w_rel})
+    eng.forward(train=False)
+    eng.rank_reserve(reserve)
+    return eng
+
+
+@pytest.mark.parametrize("V", [3, 63, 64, 65, 255, 256, 257, 513])
+def test_rank_counts_at_the_reduction_and_filter_walk_boundaries(native, V):
+    """One workgroup of 256 threads walks a row of V energies and a filter list 256 entries at a time and sums its two
+    counts over four waves: V below, at and above one wave, one walk and two walks; lists of 0, 1 (the gold alone), 255,
+    256, 257 and V entries (duplicates among them, which count each time they appear).  Every entity but at most one has
+    a twin with the same embedding, so every row holds ties with the gold's energy, and every query is asked twice.  The
+    counts are integer counts: the reference's rank definition (oracle.ranks_from_energies) on the device's OWN energies,
+    read back, must give exactly the device's ranks, no case excused -- and rgcn_rank_mixed_device at weight 1 compares
+    the fp32 sigmoid of those same energies, whatever the partner, so its ranks are rgcn_rank_device's."""
+    R, d = 3, 8
+    rng = np.random.RandomState(V)
+    half = (V + 1) // 2
+    w_emb = rng.randn(half, d).astype(np.float32)[np.arange(V) % half]
+    twinless = half - 1 if V % 2 else -1                           # (V odd: the one entity whose embedding is its own)
+    w_rel = rng.randn(V, d).astype(np.float32)
+    lengths = [0, 1, 255, 256, 257, V]
+    queries = np.repeat(np.stack([rng.randint(0, V, 6), rng.randint(0, R, 6), rng.randint(0, V, 6)], 1), 2, axis=0)
+    queries = queries.astype(np.int32)
+    n = len(queries)
+    eng = embedding_engine(native, V, R, d, w_emb, w_rel, n)
+    try:
+        for object_side in (True, False):
+            gold = queries[:, 2] if object_side else queries[:, 0]
+            lists = []
+            for i in range(n):
+                length = lengths[i // 2]
+                rest = rng.permutation(V) if length == V else rng.randint(0, V, max(length - 1, 0))
+                rest = rest[rest != gold[i]] if length == V else rest
+                lists.append(np.concatenate([[gold[i]][:length], rest]).astype(np.int64))
+            assert [len(l) for l in lists] == [l for l in lengths for _ in (0, 1)]
+            ptr = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int64)
+            idx = np.concatenate(lists).astype(np.int32)
+            raw, filt = eng.ranks(queries, object_side, ptr, idx)
+            energies = eng.read_buffer(native.BUF_RANK_ENERGIES)
+            assert energies.shape == (n, V)
+            want = [oracle.ranks_from_energies(energies[i], gold[i], lists[i]) for i in range(n)]
+            assert list(zip(raw.tolist(), filt.tolist())) == want, (V, object_side)
+            assert (raw[gold != twinless] >= 2).all()                 # the gold's twin ties with it
+            assert (filt[-2:] == 1).all() and (filt[:2] == raw[:2] + 1).all()      # every entity listed; nobody listed
+            partner = rng.randn(n, V).astype(np.float32)
+            mixed = eng.ranks_mixed(queries, object_side, partner, 1.0, ptr, idx)
+            np.testing.assert_array_equal(mixed[0], raw)
+            np.testing.assert_array_equal(mixed[1], filt)
+    finally:
+        eng.close()
+
+
+def test_more_than_one_chunk_plus_one_query(native):
+    """Reserve 4, N = 9: two whole chunks and a chunk of one.  Ranks and top-k answers are those of nine single-query
+    calls: every chunk reads its own slice of the queries, of the lists' pointers and of the outputs.  The tables hold
+    small integers, so every energy is exact whatever shape the GEMM runs at, and ties are everywhere."""
+    V, R, d, N, k = 65, 3, 8, 9, 5
+    rng = np.random.RandomState(9)
+    w_emb = rng.randint(-2, 3, (V, d)).astype(np.float32)
+    w_rel = rng.randint(-2, 3, (V, d)).astype(np.float32)
+    queries = np.stack([rng.randint(0, V, N), rng.randint(0, R, N), rng.randint(0, V, N)], 1).astype(np.int32)
+    eng = embedding_engine(native, V, R, d, w_emb, w_rel, 4)
+    try:
+        for object_side in (True, False):
+            gold = queries[:, 2] if object_side else queries[:, 0]
+            lists = [np.concatenate([[gold[i]], rng.randint(0, V, 3 * i)]).astype(np.int32) for i in range(N)]
+            ptr = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int64)
+            idx = np.concatenate(lists)
+            raw, filt = eng.ranks(queries, object_side, ptr, idx)
+            ids, energies = eng.topk(queries, object_side, k, ptr, idx)
+            for i in range(N):
+                one = np.array([0, len(lists[i])], np.int64)
+                r1, f1 = eng.ranks(queries[i:i + 1], object_side, one, lists[i])
+                assert (int(raw[i]), int(filt[i])) == (int(r1[0]), int(f1[0])), (object_side, i)
+                i1, e1 = eng.topk(queries[i:i + 1], object_side, k, one, lists[i])
+                np.testing.assert_array_equal(ids[i], i1[0])
+                np.testing.assert_array_equal(energies[i], e1[0])
+            assert not np.isin(ids, -1).any() and all(not np.isin(ids[i], lists[i]).any() for i in range(N))
+    finally:
+        eng.close()
+
+
+def test_ranks_are_refused_while_a_graph_is_captured(native):
+    """rgcn_rank_device synchronises with the device, like the other four query calls: between rgcn_capture_begin and
+    rgcn_capture_end it is RGCN_ERR_STATE before any device work -- through Engine.ranks and through the C entry itself,
+    on buffers staged beforehand -- and the capture ends and its graph is destroyed as if nothing had been asked."""
+    V, R, d, E = 80, 6, 8, 300
+    params, triples, _, _ = make_case(V, R, d, 1, "block", 2, E, seed=4)
+    eng = native.Engine(V, R, d, 1, "block", 2, max_edges=E)
+    held = []
+    try:
+        eng.set_params(params)
+        rng = np.random.RandomState(1)
+        X = np.concatenate([triples[:40], triples[rng.permutation(E)[:40]]]).astype(np.int32)
+        X[40:, 2] = rng.randint(0, V, 40)
+        Y = np.concatenate([np.ones(40), np.zeros(40)]).astype(np.float32)
+        eng.decoder_reserve(len(X))
+        eng.optimizer_config(lr=0.01, max_grad_norm=1.0)
+        q = triples[:4].astype(np.int32)
+        ptr, idx = np.arange(5, dtype=np.int64), q[:, 2].astype(np.int32)
+        held = [eng.to_device(a) for a in (triples, X, Y, q, ptr, idx)] + [native.DeviceBuffer(eng, 16) for _ in (0, 1)]
+        T, Xd, Yd, qd, ptrd, idxd, rawd, filtd = held
+        eng.set_graph(triples)
+        eng.forward(train=False)
+        eng.rank_reserve(4)
+        before = eng.ranks(q, True, ptr, idx)                       # (the engine's staging buffer exists from here on)
+        eng.train_step_device(T, E, Xd, Yd, len(X), seed=5, reg_param=0.01)       # warm-up: lazy allocations happen here
+        eng.sync()
+        eng.capture_begin()
+        eng.train_step_device(T, E, Xd, Yd, len(X), seed=50, reg_param=0.01)
+        with pytest.raises(native.RgcnError) as err:
+            eng.ranks(q, True, ptr, idx)
+        assert err.value.status == STATE
+        with pytest.raises(native.RgcnError) as err:
+            eng._check(eng.lib.rgcn_rank_device(eng.ctx, qd.ptr, 4, 1, ptrd.ptr, idxd.ptr, rawd.ptr, filtd.ptr))
+        assert err.value.status == STATE and "rgcn_capture_end" in str(err.value)
+        gid = eng.capture_end()
+        eng.graph_destroy(gid)
+        eng.set_graph(triples)
+        eng.forward(train=False)
+        after = eng.ranks(q, True, ptr, idx)                        # and the call works again
+        assert after[0].shape == before[0].shape == (4,)
+    finally:
+        for b in held:
+            b.free()
+        eng.close()
+
+
 def test_ranks_at_baseline_scale_equal_the_reference_scorer(native):
     """tests/golden/reference_ranks_fullscale.npz: the REFERENCE'S OWN Scorer (common/evaluation.py, run by
     tests/golden/make_reference_rank_fixture.py) ranked 1,200 real FB15k-237 triples on both sides against all 14,541

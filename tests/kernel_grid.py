@@ -16,7 +16,7 @@ BLOCK_SIZES = (1, 2, 3, 4, 5, 8)      # block_msgs.hip:184-192 (dispatch_sd) and
 GROUP_WIDTHS = (8, 16, 32, 64)
 TILE_SIZES = (64, 32, 16, 8)
 LONG_ROW = 32                         # rgcn_internal.h:93 (kLongRow): a row with more slots takes the long-row path
-GIANT_ROW = 2048                      # rgcn_internal.h:96 (kGiantRow): full-graph scale only, never reached here
+GIANT_ROW = 2048                      # rgcn_internal.h:98 (kGiantRow): full-graph scale only; tests/giant_grid.py reaches it
 MAX_BLOCKS = 512                      # config_check.h (check_config)
 MAX_BASES = 64                        # config_check.h (check_config)
 BASIS_BT = 8                          # row_walk.h:15 (BT): basis functions per pass

@@ -76,10 +76,11 @@ enum { RGCN_KIND_BLOCK = 0, RGCN_KIND_BASIS = 1, RGCN_KIND_BASIS_TDIAG = 2, RGCN
  *     non-NULL triple pointer or num_edges != 0 is RGCN_ERR_INVALID;
  *   - RGCN_ERR_UNSUPPORTED, the message naming the kind: rgcn_set_graph*, rgcn_prefetch_graph*, rgcn_step_device,
  *     rgcn_train_step_minibatch_device, rgcn_neighborhood_reserve, the phase API (rgcn_forward_begin ... rgcn_backward_end),
- *     rgcn_set_relation_owner, rgcn_capture_begin; rgcn_read_buffer knows RGCN_BUF_RANK_ENERGIES and
- *     RGCN_BUF_RANK_MIXED_SCORES only (RGCN_ERR_STATE);
+ *     rgcn_set_relation_owner, rgcn_capture_begin; rgcn_read_buffer knows RGCN_BUF_RANK_ENERGIES,
+ *     RGCN_BUF_RANK_MIXED_SCORES and RGCN_BUF_RELATION_ENERGIES only (RGCN_ERR_STATE);
  *   - unchanged: rgcn_decoder_*, rgcn_negative_sample_device, rgcn_optimizer_*, rgcn_rank_device, rgcn_rank_mixed_device,
- *     rgcn_topk_device, rgcn_score_queries_device, rgcn_topk_mixed_device, parameters, device memory, timer and profile. */
+ *     rgcn_topk_device, rgcn_score_queries_device, rgcn_topk_mixed_device, rgcn_rank_relation_device,
+ *     rgcn_topk_relation_device, rgcn_score_relation_queries_device, parameters, device memory, timer and profile. */
 /* RGCN_KIND_BASIS_TDIAG = Encoder.DiagonalCoefficients=Yes -> BasisGcnTimesDiag
  * (code/encoders/message_gcns/gcn_basis_times_diag.py; model_builder.py:287-288, ahead of Concatenation): the
  * coefficient of a message is a VECTOR per (relation, basis) over the output channels,
@@ -185,9 +186,14 @@ enum {
    * RGCN_ERR_STATE before any layer has run and on every other context: */
   RGCN_BUF_PDIAG_MIX = 15,      /* float [2][V][B]: a_dir[v,b] = sum over the row's messages of direction dir of n C_dir[r,b] */
   RGCN_BUF_PDIAG_AGG = 16,      /* float [V,d]: the diagonal aggregate sum over the row's messages of n D[rho] * H_{l-1}[src] */
-  RGCN_BUF_RANK_MIXED_SCORES = 17 /* float [reserved queries, V]: the mixed scores of the last rgcn_topk_mixed_device (what
+  RGCN_BUF_RANK_MIXED_SCORES = 17, /* float [reserved queries, V]: the mixed scores of the last rgcn_topk_mixed_device (what
                                    it selected from, bit for bit).  RGCN_ERR_STATE before the first such call, and again
                                    after a growing rgcn_rank_reserve until the next one */
+  RGCN_BUF_RELATION_ENERGIES = 18 /* float [reserved queries, RelationCount]: energies of the last chunk
+                                   rgcn_rank_relation_device, rgcn_topk_relation_device or
+                                   rgcn_score_relation_queries_device scored (what the counts and the selection are integer
+                                   work on).  RGCN_ERR_STATE before the first such call, and again after a growing
+                                   rgcn_rank_reserve until the next one */
 };
 
 /*
@@ -485,6 +491,50 @@ rgcn_status rgcn_topk_mixed_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t 
                                    int32_t k, const float* partner_energies_dev, float weight,
                                    const int64_t* exclude_ptr_dev, const int32_t* exclude_idx_dev,
                                    int32_t* topk_idx_dev, float* topk_score_dev);
+
+/* ---- relation queries: which relation holds between two given entities ------------------------------------
+ * The decoder's third question: (s, ?, o).  The reference scores subjects and objects only; the energy is the same
+ * DistMult sum with the relation as the free index,
+ *     energy[r'] = sum_k (codes[s] * codes[o])[k] W_relation[r', k]      for r' in [0, RelationCount),
+ * on the codes of the last rgcn_forward.  The pair row codes[s] * codes[o] is rounded to fp32 once, then the same NT GEMM
+ * as rgcn_rank_device's runs against W_relation instead of the codes.  The energies go to a buffer of their own,
+ * RGCN_BUF_RELATION_ENERGIES (float [reserved queries, RelationCount], row stride RelationCount, the last chunk's):
+ * RGCN_BUF_RANK_ENERGIES is not touched by any of these calls, nor this buffer by an entity-side call.  The buffer is
+ * allocated by the first relation call after rgcn_rank_reserve (RGCN_ERR_NOMEM if it does not fit) and released with the
+ * other ranking buffers: a context that is never asked about relations never holds it.
+ * rgcn_relation_energies_device = its device pointer, NULL before the first relation call.
+ * x = int32 [N,3] rows (s, r, o).  rgcn_rank_relation_device reads all three columns, r being the gold relation;
+ * rgcn_topk_relation_device and rgcn_score_relation_queries_device read s and o only, the r column may hold anything
+ * (e.g. -1).  The ids that are read are validated on the device, s and o in [0, V), a gold r in [0, RelationCount)
+ * (RGCN_ERR_INVALID, no usable result).
+ * Ranks: comparison and tie rule of rgcn_rank_device (fp32 sigmoid evaluated in double and rounded once, so saturated
+ * scores tie):
+ *   raw_rank[i]      = #{r' : score[r'] >= score[gold]}
+ *   filtered_rank[i] = raw_rank[i] - #{r' in filter_idx[filter_ptr[i] : filter_ptr[i+1]] : score[r'] >= score[gold]} + 1
+ * (the filter list holds the relations known between the pair, the gold one among them); ranges validated as
+ * rgcn_rank_device's, entries in [0, RelationCount).
+ * Top-k: rgcn_topk_device's selection over the relations.  1 <= k <= min(RelationCount, RGCN_MAX_TOPK), else
+ * RGCN_ERR_INVALID.  Row i holds the min(k, RelationCount - #distinct excluded) best remaining relation ids ordered by
+ * (energy descending, id ascending), energies compared as floats in their numeric order with -0.0 below +0.0;
+ * topk_energy holds the buffer's values bit for bit, slots a row cannot fill hold id -1 and energy -INFINITY.
+ * exclude_ptr / exclude_idx: CSR of relation ids in [0, RelationCount), both NULL = exclude nothing (one NULL:
+ * RGCN_ERR_INVALID).  RelationCount above RGCN_MAX_TOPK_ENTITIES is RGCN_ERR_UNSUPPORTED (the mask lives in LDS).
+ * RelationCount above EntityCount is RGCN_ERR_UNSUPPORTED for all three calls: W_relation is stored [EntityCount, d] as
+ * in the reference, and its first RelationCount rows are the candidates.
+ * Rank and top-k chunk inputs longer than the reserve; score is ONE chunk only (num_queries above the reserve:
+ * RGCN_ERR_INVALID).  num_queries = 0 is RGCN_OK.  RGCN_ERR_STATE before a forward pass, before rgcn_rank_reserve and
+ * between rgcn_capture_begin and rgcn_capture_end: the calls synchronise at the end (they read the validation verdict).
+ * RGCN_KIND_EMBEDDING and relation-sharded contexts: as rgcn_topk_device (codes and W_relation are replicated, every rank
+ * answers its own queries, no collective).  The 2R directed relations of the encoder are not candidates, and there is no
+ * mixed form. */
+rgcn_status rgcn_score_relation_queries_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t num_queries);
+const float* rgcn_relation_energies_device(rgcn_ctx* ctx);
+rgcn_status rgcn_rank_relation_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t num_queries,
+                                      const int64_t* filter_ptr_dev, const int32_t* filter_idx_dev,
+                                      int32_t* raw_rank_dev, int32_t* filtered_rank_dev);
+rgcn_status rgcn_topk_relation_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t num_queries, int32_t k,
+                                      const int64_t* exclude_ptr_dev, const int32_t* exclude_idx_dev,
+                                      int32_t* topk_idx_dev, float* topk_energy_dev);
 
 /* GradientClipping(max_norm) + Adam(lr) of the Converge chain (optimization/tensorflow_backend/
  * algorithms.py:27-42,58-68).  max_grad_norm = 0 disables clipping. */

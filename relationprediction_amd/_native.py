@@ -27,6 +27,7 @@ BUF_TDIAG_PRODUCTS = 14      # basis_tdiag contexts: [2, V, B*d], P_f then P_b o
 BUF_PDIAG_MIX = 15           # basis_pdiag contexts: [2, V, B], the mixing table a of the layer run last
 BUF_PDIAG_AGG = 16           # basis_pdiag contexts: [V, d], the diagonal aggregate of the layer run last
 BUF_RANK_MIXED_SCORES = 17   # [reserved queries, V], the mixed scores the last topk_mixed selected from
+BUF_RELATION_ENERGIES = 18   # [reserved queries, R], the energies of the chunk a relation query scored last
 
 KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS, "basis_tdiag": KIND_BASIS_TDIAG,
          "basis_pdiag": KIND_BASIS_PDIAG, "embedding": KIND_EMBEDDING}
@@ -116,6 +117,10 @@ _SIGS = {
     "rgcn_topk_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rgcn_score_queries_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32]),
     "rgcn_topk_mixed_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_float, _P, _P, _P, _P]),
+    "rgcn_score_relation_queries_device": (C.c_int32, [_P, _P, C.c_int64]),
+    "rgcn_relation_energies_device": (_P, [_P]),
+    "rgcn_rank_relation_device": (C.c_int32, [_P, _P, C.c_int64, _P, _P, _P, _P]),
+    "rgcn_topk_relation_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
     "rgcn_optimizer_step": (C.c_int32, [_P]),
     "rgcn_optimizer_norm_partial": (C.c_int32, [_P]),
     "rgcn_optimizer_apply": (C.c_int32, [_P]),
@@ -705,6 +710,42 @@ class Engine:
                                          self.ctx, x, n, 1 if predict_object else 0, k, pp, C.c_float(float(weight)), ptr,
                                          idx, ids, scores))
 
+    def score_relation_queries(self, queries):
+        """Energies of every relation between s and o of each query into RGCN_BUF_RELATION_ENERGIES and nothing else
+        (include/rgcn.h rgcn_score_relation_queries_device).  queries [N,3] rows (s, r, o) of which the r column is not
+        read; one chunk: N <= the reserve.  Synchronises."""
+        x = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1, 3)
+        if len(x) == 0:
+            return
+        xd = DeviceBuffer(self, x.nbytes).upload(x)
+        try:
+            self._check(self.lib.rgcn_score_relation_queries_device(self.ctx, xd.ptr, len(x)))
+        finally:
+            xd.free()
+
+    def relation_energies_device(self):
+        """device address of RGCN_BUF_RELATION_ENERGIES (the [reserved queries, R] energies of the chunk a relation query
+        scored last), or None before the first relation query since rank_reserve"""
+        p = self.lib.rgcn_relation_energies_device(self.ctx)
+        return int(p) if p else None
+
+    def ranks_relation(self, triples, filter_ptr, filter_idx):
+        """Raw and filtered ranks (include/rgcn.h rgcn_rank_relation_device) of the gold relation of every query triple
+        among all relations between its subject and object, on the codes of the last forward.  filter_ptr int64 [N+1],
+        filter_idx int32 [nnz]: relation ids."""
+        return self._ranks_staged(triples, filter_ptr, filter_idx,
+                                  lambda n, x, ptr, idx, raw, filt: self.lib.rgcn_rank_relation_device(
+                                      self.ctx, x, n, ptr, idx, raw, filt))
+
+    def topk_relation(self, queries, k, exclude_ptr=None, exclude_idx=None):
+        """The k best relations between s and o of every query, best first (include/rgcn.h rgcn_topk_relation_device):
+        (idx int32 [N,k], energy float32 [N,k]), rows short of k answers padded with (-1, -inf).  queries [N,3] rows
+        (s, r, o) of which r is not read; exclude_ptr int64 [N+1] / exclude_idx int32 [nnz]: per-row relation ids that
+        may not be answered (both None: none)."""
+        return self._topk_staged(queries, k, exclude_ptr, exclude_idx,
+                                 lambda n, k, x, ptr, idx, ids, energies: self.lib.rgcn_topk_relation_device(
+                                     self.ctx, x, n, k, ptr, idx, ids, energies))
+
     def optimizer_config(self, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, max_grad_norm=1.0):
         self._check(self.lib.rgcn_optimizer_config(self.ctx, lr, beta1, beta2, eps, max_grad_norm))
 
@@ -763,6 +804,8 @@ class Engine:
             out = np.empty(2 * self.num_edges, dtype=np.float32)
         elif which in (BUF_RANK_ENERGIES, BUF_RANK_MIXED_SCORES):
             out = np.empty((getattr(self, "_rank_reserved", 0), self.V), dtype=np.float32)
+        elif which == BUF_RELATION_ENERGIES:
+            out = np.empty((getattr(self, "_rank_reserved", 0), self.R), dtype=np.float32)
         elif which == BUF_DSELF_EXCHANGE:
             out = np.empty((self.d, self.d), dtype=np.float32)
         elif which == BUF_NORM_EXCHANGE:

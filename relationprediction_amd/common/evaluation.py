@@ -166,6 +166,8 @@ def known_completions_csr(pairs, known):
     pairs: [N,2] rows (entity, relation): the fixed entity of the query -- the subject when objects are predicted, the
     object when subjects are -- and its relation.  known: the matching dictionary of a Scorer after register_data
     (known_object_triples / known_subject_triples), {(entity, relation): [completing entity ids]}.
+    Relation queries (rgcn_topk_relation_device): pairs are rows (subject, object) and known is known_relation_triples,
+    {(subject, object): [relation ids]}.
     Returns (ptr int64 [N+1], idx int32 [nnz]); a pair with no known completion gets an empty range."""
     ptr, idx = np.zeros(len(pairs) + 1, dtype=np.int64), []
     for i, (e, r) in enumerate(pairs):
@@ -180,6 +182,7 @@ class Scorer(object):
     def __init__(self, settings):
         self.known_object_triples = {}
         self.known_subject_triples = {}
+        self.known_relation_triples = {}
         self.in_degree = {}
         self.out_degree = {}
         self.relation_freqs = {}
@@ -203,6 +206,10 @@ class Scorer(object):
             self.relation_freqs[int(r)] = self.relation_freqs.get(int(r), 0) + 1
         self.extend_triple_dict(self.known_subject_triples, triples, object_list=False)
         self.extend_triple_dict(self.known_object_triples, triples)
+        for s, r, o in np.asarray(triples):
+            lst = self.known_relation_triples.setdefault((int(s), int(o)), [])
+            if int(r) not in lst:
+                lst.append(int(r))
 
     def register_degrees(self, triples):
         for s, _, o in np.asarray(triples):
@@ -271,3 +278,24 @@ class Scorer(object):
                                [self.in_degree[int(v)] for v in fixed], [self.out_degree[int(v)] for v in fixed],
                                [self.avg_freq.get(int(v), 0.0) for v in fixed],
                                [self.relation_freqs[int(r)] for r in triples[:, 1]])
+
+    def compute_relation_mrr_scores(self, triples, verbose=False):
+        """Ranks of the gold relation of every triple among all relations between its subject and object
+        (rgcn_rank_relation_device), filtered by the relations known for the pair: one line per triple.  The degree and
+        vertex-frequency columns are the subject's, the relation frequency the gold relation's.  The reference has no
+        such evaluation; compute_scores does not call it."""
+        triples = np.asarray(triples)
+        score = MrrScore(triples)
+        graph = self.model.test_graph
+        for lo in range(0, len(triples), self.chunk_size):
+            chunk = triples[lo:lo + self.chunk_size]
+            if verbose:
+                print("Evaluating relations...")
+            ptr, idx = known_completions_csr(chunk[:, [0, 2]], self.known_relation_triples)
+            raw, filtered = self.model.device_relation_ranks(graph, chunk, ptr, idx)
+            subjects = chunk[:, 0]
+            score.append_lines(raw, filtered,
+                               [self.in_degree[int(v)] for v in subjects], [self.out_degree[int(v)] for v in subjects],
+                               [self.avg_freq.get(int(v), 0.0) for v in subjects],
+                               [self.relation_freqs[int(r)] for r in chunk[:, 1]])
+        return score

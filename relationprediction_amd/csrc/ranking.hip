@@ -34,15 +34,28 @@
 // exactly as it selects from energies (it orders any floats).  rgcn_score_queries_device is how the partner produces its
 // energies for queries that have no gold entity: the shared scoring and nothing after it.
 //
-// One scoring path: all five calls are run_queries (bottom of the file) -- clear the verdict and launch k_rank_check,
+// One scoring path: all calls are run_queries (bottom of the file) -- clear the verdict and launch k_rank_check,
 // then per chunk score_chunk (k_rank_query + the NT GEMM into ranking.q / ranking.s) and the call's own tail, then read
 // the verdict back -- and differ in the tail they hand it.  The two rank kernels are wrappers round one row template
 // (rank_row) and differ in the comparison they hand it.
+//
+// Relation queries (rgcn_rank_relation_device, rgcn_topk_relation_device, rgcn_score_relation_queries_device): which
+// relation holds between s and o.  The same path with another candidate table: side SIDE_RELATION makes k_rank_check read
+// (s, o) as the given ids and r as the gold one, score_chunk form P = codes[s] * codes[o] (k_rank_pair) and multiply it
+// with W_relation instead of the codes -- the same NT GEMM, N = R -- into ranking.rel, a [reserved queries, R] buffer of
+// its own (ranking.s is never touched), and the tails run k_rank_threshold / k_rank_rows / k_topk_rows as they stand,
+// with R where the entity side passes V: candidate count, row stride, range of the list entries, bits of the mask.
 #include "rgcn_internal.h"
 
 namespace rgcn {
 
 namespace {
+
+// What a query asks for: the values of the entity sides are the entries' predict_object.  The candidates fill one column
+// of the (s, r, o) rows -- the gold id of a rank query sits there, the top-k forms never read it -- and the two others
+// are given.
+enum : int { SIDE_SUBJECT = 0, SIDE_OBJECT = 1, SIDE_RELATION = 2 };
+inline int gold_column(int side) { return side == SIDE_OBJECT ? 2 : side == SIDE_RELATION ? 1 : 0; }
 
 __device__ __forceinline__ float sigmoid_f32(float x) {
   return (float)(1.0 / (1.0 + exp(-(double)x)));
@@ -63,6 +76,20 @@ __global__ void k_rank_query(const float* __restrict__ codes, const float* __res
   for (int k = threadIdx.x; k < d; k += blockDim.x) Q[(size_t)row * d + k] = e[k] * r[k];
 }
 
+// P[n,:] = codes[s_n] * codes[o_n]: the relation side's query row, one rounding per element
+__global__ void k_rank_pair(const float* __restrict__ codes, const int32_t* __restrict__ X, int n, int d,
+                            float* __restrict__ P, int V) {
+  const int row = blockIdx.x;
+  if (row >= n) return;
+  int s = X[3 * row], o = X[3 * row + 2];
+  // (as in k_rank_query: a bad id fails the call at the end and must not fault before)
+  if ((unsigned)s >= (unsigned)V) s = 0;
+  if ((unsigned)o >= (unsigned)V) o = 0;
+  const float* a = codes + (size_t)s * d;
+  const float* b = codes + (size_t)o * d;
+  for (int k = threadIdx.x; k < d; k += blockDim.x) P[(size_t)row * d + k] = a[k] * b[k];
+}
+
 // floats in their numeric order as unsigned integers (and back)
 __device__ __forceinline__ uint32_t float_key(float x) {
   const uint32_t b = __float_as_uint(x);
@@ -72,12 +99,13 @@ __device__ __forceinline__ float key_float(uint32_t k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
-// thr[row] = the smallest float energy whose fp32 sigmoid is >= the gold entity's: one thread per query
+// thr[row] = the smallest float energy whose fp32 sigmoid is >= the gold candidate's: one thread per query.  V: the
+// candidates of a row (and its stride); gold_col: the column of X that holds the gold id (gold_column)
 __global__ void k_rank_threshold(const float* __restrict__ S, int V, const int32_t* __restrict__ X, int n,
-                                 int predict_object, float* __restrict__ thr) {
+                                 int gold_col, float* __restrict__ thr) {
   const int row = blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n) return;
-  int gold = X[3 * row + (predict_object ? 2 : 0)];
+  int gold = X[3 * row + gold_col];
   if ((unsigned)gold >= (unsigned)V) gold = 0;
   const float xg = S[(size_t)row * V + gold];
   const float g = sigmoid_f32(xg);
@@ -189,15 +217,26 @@ k_mix_rows(const float* __restrict__ Sa, const float* __restrict__ Sb, int V, in
 // exclusion list, which may be absent (the last entry of list_ptr is the list's declared length: no range may end
 // beyond it).  The list's entries are range-checked where they are read, 256 lanes wide, in the row kernels: one thread
 // walking a list of 1,700 entries here was most of a call's time on the subject side of FB15k-237.
-__global__ void k_rank_check(const int32_t* __restrict__ X, int n, int V, int R, int predict_object, int with_gold,
+// The relation form (side SIDE_RELATION): both entities are given, the gold id is the relation.
+__global__ void k_rank_check(const int32_t* __restrict__ X, int n, int V, int R, int side, int with_gold,
                              const int64_t* __restrict__ list_ptr, int32_t* __restrict__ bad) {
   const int row = blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n) return;
-  const int ent = X[3 * row + (predict_object ? 0 : 2)], rel = X[3 * row + 1];
-  bool ok = ent >= 0 && ent < V && rel >= 0 && rel < R;
-  if (with_gold) {
-    const int gold = X[3 * row + (predict_object ? 2 : 0)];
-    ok = ok && gold >= 0 && gold < V;
+  bool ok;
+  if (side == SIDE_RELATION) {
+    const int s = X[3 * row], o = X[3 * row + 2];
+    ok = s >= 0 && s < V && o >= 0 && o < V;
+    if (with_gold) {
+      const int gold = X[3 * row + 1];
+      ok = ok && gold >= 0 && gold < R;
+    }
+  } else {
+    const int ent = X[3 * row + (side == SIDE_OBJECT ? 0 : 2)], rel = X[3 * row + 1];
+    ok = ent >= 0 && ent < V && rel >= 0 && rel < R;
+    if (with_gold) {
+      const int gold = X[3 * row + (side == SIDE_OBJECT ? 2 : 0)];
+      ok = ok && gold >= 0 && gold < V;
+    }
   }
   if (list_ptr)
     ok = ok && list_ptr[row] >= 0 && list_ptr[row] <= list_ptr[row + 1] && list_ptr[row + 1] <= list_ptr[n];
@@ -437,15 +476,15 @@ rgcn_status rank_reserve(rgcn_ctx* c, int64_t max_queries) {
   return RGCN_OK;
 }
 
-// ---------------------------------------------------------------- the scoring path of all five calls
+// ---------------------------------------------------------------- the scoring path of all calls
 // Ids are validated on the device (out-of-range ids are rejected, never clamped) and the verdict is read back at the END of
 // the call, with no host wait in the middle: until then the kernels substitute id 0 for a bad id and skip a bad range so
 // that nothing faults, and the (meaningless) answers of a rejected call are not to be used.
-static rgcn_status verdict_begin(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, bool with_gold,
+static rgcn_status verdict_begin(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int side, bool with_gold,
                                  const int64_t* list_ptr) {
   RGCN_HIP(c, hipMemsetAsync(c->ranking.bad, 0, sizeof(int32_t), c->stream));
   hipLaunchKernelGGL(k_rank_check, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, X_dev, (int)N, c->V, c->R,
-                     predict_object, with_gold ? 1 : 0, list_ptr, c->ranking.bad);
+                     side, with_gold ? 1 : 0, list_ptr, c->ranking.bad);
   RGCN_HIP(c, hipGetLastError());
   return RGCN_OK;
 }
@@ -458,13 +497,36 @@ static rgcn_status verdict_end(rgcn_ctx* c, const char* refusal) {
   return RGCN_OK;
 }
 
-// the query rows of X[0, n) into ranking.q, their energies against every entity into ranking.s
-static rgcn_status score_chunk(rgcn_ctx* c, const int32_t* X, int n, int predict_object) {
+// What a side's tails are launched with: how many candidates a row has (its stride, the range of its list's entries, the
+// bits of its mask) and where score_chunk leaves their energies
+static int candidates(const rgcn_ctx* c, int side) { return side == SIDE_RELATION ? c->R : c->V; }
+static const float* energies(const rgcn_ctx* c, int side) { return side == SIDE_RELATION ? c->ranking.rel : c->ranking.s; }
+
+// The relation side's [reserved queries, R] energies, allocated on the first relation call after a (growing) rank_reserve
+// as ranking.mixed is: a context that is never asked about relations never holds them.
+static rgcn_status relation_energies_reserve(rgcn_ctx* c) {
+  RankBufs& q = c->ranking;
+  if (!q.rel) RGCN_TRY(dmalloc(c, q.pool, &q.rel, (size_t)q.max * c->R, false));
+  return RGCN_OK;
+}
+
+// the query rows of X[0, n) into ranking.q, their energies against every candidate into the side's buffer: every entity
+// into ranking.s, or (SIDE_RELATION) every relation into ranking.rel
+static rgcn_status score_chunk(rgcn_ctx* c, const int32_t* X, int n, int side) {
   const float* codes = c->H[c->L];
+  if (side == SIDE_RELATION) {
+    {
+      ProfScope ps(c, "rank_query_relation", 4.0 * 3 * n * c->d, 0);
+      hipLaunchKernelGGL(k_rank_pair, dim3((unsigned)n), dim3(128), 0, c->stream, codes, X, n, c->d, c->ranking.q, c->V);
+      RGCN_HIP(c, hipGetLastError());
+    }
+    return gemm_f32(c, "rank_scores_relation", true, true, n, c->R, c->d, c->ranking.q, c->d, c->w_rel, c->d, c->ranking.rel,
+                    c->R, 1);
+  }
   {
     ProfScope ps(c, "rank_query", 4.0 * 3 * n * c->d, 0);
     hipLaunchKernelGGL(k_rank_query, dim3((unsigned)n), dim3(128), 0, c->stream, codes, c->w_rel, X, n, c->d,
-                       predict_object, c->ranking.q, c->V, c->R);
+                       side, c->ranking.q, c->V, c->R);
     RGCN_HIP(c, hipGetLastError());
   }
   return gemm_f32(c, "rank_scores", true, true, n, c->V, c->d, c->ranking.q, c->d, codes, c->d, c->ranking.s, c->V, 1);
@@ -474,29 +536,44 @@ static rgcn_status score_chunk(rgcn_ctx* c, const int32_t* X, int n, int predict
 // energies of its queries [b, b + n), whose rows start at X -- then the verdict.  A call whose entry admits one chunk only
 // (the mixed forms, score queries) runs the loop once, with b = 0.
 template <class Tail>
-static rgcn_status run_queries(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, bool with_gold,
+static rgcn_status run_queries(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int side, bool with_gold,
                                const int64_t* list_ptr, const char* refusal, Tail tail) {
-  RGCN_TRY(verdict_begin(c, X_dev, N, predict_object, with_gold, list_ptr));
+  if (side == SIDE_RELATION) RGCN_TRY(relation_energies_reserve(c));
+  RGCN_TRY(verdict_begin(c, X_dev, N, side, with_gold, list_ptr));
   for (int64_t b = 0; b < N; b += c->ranking.max) {
     const int n = (int)std::min<int64_t>(c->ranking.max, N - b);
-    RGCN_TRY(score_chunk(c, X_dev + 3 * b, n, predict_object));
+    RGCN_TRY(score_chunk(c, X_dev + 3 * b, n, side));
     RGCN_TRY(tail(b, n, X_dev + 3 * b));
   }
   return verdict_end(c, refusal);
 }
 
-rgcn_status rank_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, const int64_t* filt_ptr,
-                         const int32_t* filt_idx, int32_t* raw_out, int32_t* filt_out) {
-  return run_queries(c, X_dev, N, predict_object, true, filt_ptr, "rank: entity / relation / filter index out of range",
-                     [=](int64_t b, int n, const int32_t* X) -> rgcn_status {
-    ProfScope ps(c, "rank_rows", 4.0 * n * c->V, 0);
-    hipLaunchKernelGGL(k_rank_threshold, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, c->ranking.s, c->V, X, n,
-                       predict_object, c->ranking.thr);
-    hipLaunchKernelGGL(k_rank_rows, dim3((unsigned)n), dim3(256), 0, c->stream, c->ranking.s, c->V, n, filt_ptr + b,
-                       filt_idx, c->ranking.thr, raw_out + b, filt_out + b, c->ranking.bad, filt_ptr + N);
+// k_rank_threshold + k_rank_rows on the side's energies
+static rgcn_status rank_side(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int side, const char* scope, const char* refusal,
+                             const int64_t* filt_ptr, const int32_t* filt_idx, int32_t* raw_out, int32_t* filt_out) {
+  const int cands = candidates(c, side);
+  return run_queries(c, X_dev, N, side, true, filt_ptr, refusal, [=](int64_t b, int n, const int32_t* X) -> rgcn_status {
+    const float* S = energies(c, side);
+    ProfScope ps(c, scope, 4.0 * n * cands, 0);
+    hipLaunchKernelGGL(k_rank_threshold, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, S, cands, X, n,
+                       gold_column(side), c->ranking.thr);
+    hipLaunchKernelGGL(k_rank_rows, dim3((unsigned)n), dim3(256), 0, c->stream, S, cands, n, filt_ptr + b, filt_idx,
+                       c->ranking.thr, raw_out + b, filt_out + b, c->ranking.bad, filt_ptr + N);
     RGCN_HIP(c, hipGetLastError());
     return RGCN_OK;
   });
+}
+
+rgcn_status rank_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, const int64_t* filt_ptr,
+                         const int32_t* filt_idx, int32_t* raw_out, int32_t* filt_out) {
+  return rank_side(c, X_dev, N, predict_object, "rank_rows", "rank: entity / relation / filter index out of range", filt_ptr,
+                   filt_idx, raw_out, filt_out);
+}
+
+rgcn_status rank_relation_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, const int64_t* filt_ptr,
+                                  const int32_t* filt_idx, int32_t* raw_out, int32_t* filt_out) {
+  return rank_side(c, X_dev, N, SIDE_RELATION, "rank_rows_relation",
+                   "rank (relation): entity / relation / filter index out of range", filt_ptr, filt_idx, raw_out, filt_out);
 }
 
 // The counts on the mixed score.  c->ranking.s holds the context's own energies afterwards, unmodified; the partner's rows
@@ -529,32 +606,53 @@ static rgcn_status topk_rows_configure(rgcn_ctx* c) {
   return RGCN_OK;
 }
 
-// k_topk_rows on the rows of `scores` (energies or mixed scores: it orders any floats) for the queries [b, b + n) of a call
-// of N, under the ProfScope `scope`.  Design bytes: four select passes and the gather read the row (from L2 after the first).
-static rgcn_status topk_rows_launch(rgcn_ctx* c, const char* scope, const float* scores, int64_t b, int n, int64_t N, int k,
-                                    const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out, float* val_out) {
-  const size_t mask_bytes = (size_t)((c->V + 31) / 32) * sizeof(uint32_t);
-  ProfScope ps(c, scope, 5.0 * 4.0 * n * c->V + 8.0 * n * k, 0, 4.0 * n * c->V + 8.0 * n * k);
-  hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)n), dim3(TOPK_THREADS), mask_bytes, c->stream, scores, c->V, n, k,
+// k_topk_rows on the rows of `scores` (energies or mixed scores: it orders any floats), `cands` candidates each, for the
+// queries [b, b + n) of a call of N, under the ProfScope `scope`.  Design bytes: four select passes and the gather read the
+// row (from L2 after the first).
+static rgcn_status topk_rows_launch(rgcn_ctx* c, const char* scope, const float* scores, int cands, int64_t b, int n,
+                                    int64_t N, int k, const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out,
+                                    float* val_out) {
+  const size_t mask_bytes = (size_t)((cands + 31) / 32) * sizeof(uint32_t);
+  ProfScope ps(c, scope, 5.0 * 4.0 * n * cands + 8.0 * n * k, 0, 4.0 * n * cands + 8.0 * n * k);
+  hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)n), dim3(TOPK_THREADS), mask_bytes, c->stream, scores, cands, n, k,
                      excl_ptr ? excl_ptr + b : nullptr, excl_idx, excl_ptr ? excl_ptr + N : nullptr,
                      idx_out + (size_t)b * k, val_out + (size_t)b * k, c->ranking.bad);
   RGCN_HIP(c, hipGetLastError());
   return RGCN_OK;
 }
 
+// k_topk_rows on the side's energies
+static rgcn_status topk_side(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int side, const char* scope, const char* refusal,
+                             int k, const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out, float* energy_out) {
+  RGCN_TRY(topk_rows_configure(c));
+  return run_queries(c, X_dev, N, side, false, excl_ptr, refusal, [=](int64_t b, int n, const int32_t*) {
+    return topk_rows_launch(c, scope, energies(c, side), candidates(c, side), b, n, N, k, excl_ptr, excl_idx, idx_out,
+                            energy_out);
+  });
+}
+
 rgcn_status topk_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, int k,
                          const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out, float* energy_out) {
-  RGCN_TRY(topk_rows_configure(c));
-  return run_queries(c, X_dev, N, predict_object, false, excl_ptr, "topk: entity / relation / exclusion index out of range",
-                     [=](int64_t b, int n, const int32_t*) {
-    return topk_rows_launch(c, "topk_rows", c->ranking.s, b, n, N, k, excl_ptr, excl_idx, idx_out, energy_out);
-  });
+  return topk_side(c, X_dev, N, predict_object, "topk_rows", "topk: entity / relation / exclusion index out of range", k,
+                   excl_ptr, excl_idx, idx_out, energy_out);
+}
+
+rgcn_status topk_relation_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int k, const int64_t* excl_ptr,
+                                  const int32_t* excl_idx, int32_t* idx_out, float* energy_out) {
+  return topk_side(c, X_dev, N, SIDE_RELATION, "topk_rows_relation", "topk (relation): entity / exclusion index out of range",
+                   k, excl_ptr, excl_idx, idx_out, energy_out);
 }
 
 // The scoring and nothing after it: c->ranking.s holds the energies of queries that have no gold entity -- what the partner
 // model of an ensemble top-k hands over
 rgcn_status score_queries_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object) {
   return run_queries(c, X_dev, N, predict_object, false, nullptr, "score queries: entity / relation index out of range",
+                     [](int64_t, int, const int32_t*) { return RGCN_OK; });
+}
+
+// The same for pairs: c->ranking.rel holds the energies of every relation between s and o
+rgcn_status score_relation_queries_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N) {
+  return run_queries(c, X_dev, N, SIDE_RELATION, false, nullptr, "score relation queries: entity index out of range",
                      [](int64_t, int, const int32_t*) { return RGCN_OK; });
 }
 
@@ -578,7 +676,7 @@ rgcn_status topk_mixed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int
                          (double)weight, c->ranking.mixed);
       RGCN_HIP(c, hipGetLastError());
     }
-    return topk_rows_launch(c, "topk_rows_mixed", c->ranking.mixed, b, n, N, k, excl_ptr, excl_idx, idx_out, score_out);
+    return topk_rows_launch(c, "topk_rows_mixed", c->ranking.mixed, c->V, b, n, N, k, excl_ptr, excl_idx, idx_out, score_out);
   });
 }
 

@@ -1015,22 +1015,28 @@ rgcn_status rgcn_rank_reserve(rgcn_ctx* c, int64_t max_queries) {
   return rank_reserve(c, max_queries);
 }
 
-// What the five query entries below require before any device work, in this order; `checks` names the ones that apply to
+// What the query entries below require before any device work, in this order; `checks` names the ones that apply to
 // `entry` beside those that apply to all (arguments, no capture, a forward, a reserve).  world > 1: the codes are
 // replicated after the last exchange, so the queries need no collective -- each rank passes its own slice of them and the
 // caller concatenates.
-enum : unsigned { QUERY_WEIGHT = 1, QUERY_TOPK = 2, QUERY_ONE_CHUNK = 4 };
+// QUERY_RELATION: the candidates of the top-k limits are the relations, not the entities.
+enum : unsigned { QUERY_WEIGHT = 1, QUERY_TOPK = 2, QUERY_ONE_CHUNK = 4, QUERY_RELATION = 8 };
 static rgcn_status query_preconditions(rgcn_ctx* c, const char* entry, unsigned checks, bool args_ok, int64_t n,
                                        float weight = 0.f, int32_t k = 0) {
   const std::string name(entry);
+  const int candidates = (checks & QUERY_RELATION) ? c->R : c->V;
+  const std::string count_name = (checks & QUERY_RELATION) ? "RelationCount" : "EntityCount";
   if (!args_ok) RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
   if ((checks & QUERY_WEIGHT) && !(weight >= 0.0f && weight <= 1.0f))
     RGCN_FAIL(c, RGCN_ERR_INVALID, name + ": weight must be in [0, 1]");
-  if ((checks & QUERY_TOPK) && (k < 1 || k > c->V || k > RGCN_MAX_TOPK))
-    RGCN_FAIL(c, RGCN_ERR_INVALID, name + ": k must be in [1, min(EntityCount, " + std::to_string(RGCN_MAX_TOPK) + ")]");
-  if ((checks & QUERY_TOPK) && c->V > RGCN_MAX_TOPK_ENTITIES)
-    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, name + ": EntityCount above " + std::to_string(RGCN_MAX_TOPK_ENTITIES) +
+  if ((checks & QUERY_TOPK) && (k < 1 || k > candidates || k > RGCN_MAX_TOPK))
+    RGCN_FAIL(c, RGCN_ERR_INVALID, name + ": k must be in [1, min(" + count_name + ", " + std::to_string(RGCN_MAX_TOPK) + ")]");
+  if ((checks & QUERY_TOPK) && candidates > RGCN_MAX_TOPK_ENTITIES)
+    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, name + ": " + count_name + " above " + std::to_string(RGCN_MAX_TOPK_ENTITIES) +
                                            " (a row's exclusion mask must fit in LDS)");
+  // (W_relation is stored [EntityCount, d] as in the reference: the relation GEMM reads its first RelationCount rows)
+  if ((checks & QUERY_RELATION) && c->R > c->V)
+    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, name + ": RelationCount above EntityCount (W_relation holds EntityCount rows)");
   if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "this call synchronises with the device: not allowed between rgcn_capture_begin and rgcn_capture_end");
   if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, name + " needs a completed rgcn_forward (test mode on the full graph)");
   if (c->ranking.max <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_rank_reserve first");
@@ -1095,6 +1101,37 @@ rgcn_status rgcn_topk_mixed_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n,
   if (n == 0) return RGCN_OK;
   return topk_mixed_compute(c, x_dev, n, predict_object ? 1 : 0, k, partner_energies_dev, weight, exclude_ptr_dev,
                             exclude_idx_dev, topk_idx_dev, topk_score_dev);
+}
+
+rgcn_status rgcn_score_relation_queries_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n) {
+  RGCN_NEED(c);
+  RGCN_TRY(query_preconditions(c, "rgcn_score_relation_queries_device", QUERY_RELATION | QUERY_ONE_CHUNK,
+                               n >= 0 && (n == 0 || x_dev), n));
+  if (n == 0) return RGCN_OK;
+  return score_relation_queries_compute(c, x_dev, n);
+}
+
+const float* rgcn_relation_energies_device(rgcn_ctx* c) { return c ? c->ranking.rel : nullptr; }
+
+rgcn_status rgcn_rank_relation_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, const int64_t* filter_ptr_dev,
+                                      const int32_t* filter_idx_dev, int32_t* raw_rank_dev, int32_t* filtered_rank_dev) {
+  RGCN_NEED(c);
+  RGCN_TRY(query_preconditions(c, "rgcn_rank_relation_device", QUERY_RELATION,
+                               n >= 0 && (n == 0 || (x_dev && filter_ptr_dev && raw_rank_dev && filtered_rank_dev)), n));
+  if (n == 0) return RGCN_OK;
+  return rank_relation_compute(c, x_dev, n, filter_ptr_dev, filter_idx_dev, raw_rank_dev, filtered_rank_dev);
+}
+
+rgcn_status rgcn_topk_relation_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32_t k,
+                                      const int64_t* exclude_ptr_dev, const int32_t* exclude_idx_dev, int32_t* topk_idx_dev,
+                                      float* topk_energy_dev) {
+  RGCN_NEED(c);
+  RGCN_TRY(query_preconditions(c, "rgcn_topk_relation_device", QUERY_RELATION | QUERY_TOPK,
+                               n >= 0 && (n == 0 || (x_dev && topk_idx_dev && topk_energy_dev)) &&
+                                   !exclude_ptr_dev == !exclude_idx_dev,
+                               n, 0.f, k));
+  if (n == 0) return RGCN_OK;
+  return topk_relation_compute(c, x_dev, n, k, exclude_ptr_dev, exclude_idx_dev, topk_idx_dev, topk_energy_dev);
 }
 
 rgcn_status rgcn_optimizer_config(rgcn_ctx* c, float lr, float beta1, float beta2, float eps, float max_grad_norm) {
@@ -1514,7 +1551,8 @@ rgcn_status rgcn_backward_end(rgcn_ctx* c) { RGCN_NEED(c); return bwd_end(c); }
 
 static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* bytes) {
   const int64_t Vd = (int64_t)c->V * c->d * 4;
-  if (c->embedding && which != RGCN_BUF_RANK_ENERGIES && which != RGCN_BUF_RANK_MIXED_SCORES)
+  if (c->embedding && which != RGCN_BUF_RANK_ENERGIES && which != RGCN_BUF_RANK_MIXED_SCORES &&
+      which != RGCN_BUF_RELATION_ENERGIES)
     RGCN_FAIL(c, RGCN_ERR_STATE, "an RGCN_KIND_EMBEDDING context has the ranking buffers only (no graph, no layer buffers)");
   switch (which) {
     case RGCN_BUF_EXCHANGE:
@@ -1547,6 +1585,9 @@ static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* byte
     case RGCN_BUF_RANK_MIXED_SCORES:
       if (!c->ranking.mixed) RGCN_FAIL(c, RGCN_ERR_STATE, "no mixed scores (no rgcn_topk_mixed_device since the last rgcn_rank_reserve)");
       *p = c->ranking.mixed; *bytes = (int64_t)c->ranking.max * c->V * 4; return RGCN_OK;
+    case RGCN_BUF_RELATION_ENERGIES:
+      if (!c->ranking.rel) RGCN_FAIL(c, RGCN_ERR_STATE, "no relation energies (no relation query since the last rgcn_rank_reserve)");
+      *p = c->ranking.rel; *bytes = (int64_t)c->ranking.max * c->R * 4; return RGCN_OK;
     case RGCN_BUF_HIGHWAY_INNER:
     case RGCN_BUF_HIGHWAY_GATE:
       if (!c->highway) RGCN_FAIL(c, RGCN_ERR_STATE, "not an RGCN_SKIP_HIGHWAY context");

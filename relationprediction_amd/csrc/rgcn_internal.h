@@ -347,6 +347,7 @@ struct RankBufs {
   int32_t* bad = nullptr;
   float* thr = nullptr;                  // per query: the smallest energy whose fp32 sigmoid reaches the gold entity's
   float* mixed = nullptr;                // mixed scores [max,V]: null until the first rgcn_topk_mixed_device at this size
+  float* rel = nullptr;                  // relation-side energies [max,R]: null until the first relation query at this size
   int64_t max = 0;
 };
 
@@ -735,7 +736,8 @@ void neighborhood_free(rgcn_ctx* c);
 // ---- ranking.hip
 rgcn_status rank_reserve(rgcn_ctx* c, int64_t max_queries);
 void rank_free(rgcn_ctx* c);
-// the five query calls: one scoring path (run_queries) and the call's own tail; each synchronises and returns the verdict
+// the five entity-side query calls: one scoring path (run_queries) and the call's own tail; each synchronises and returns
+// the verdict
 rgcn_status rank_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, const int64_t* filt_ptr,
                          const int32_t* filt_idx, int32_t* raw_out, int32_t* filt_out);
 rgcn_status rank_mixed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, const float* partner_dev,
@@ -747,6 +749,13 @@ rgcn_status score_queries_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, 
 rgcn_status topk_mixed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, int k,
                                const float* partner_dev, float weight, const int64_t* excl_ptr, const int32_t* excl_idx,
                                int32_t* idx_out, float* score_out);
+// the relation forms of rank, top-k and score: the same path, the candidates are the R relations of the pair (s, o) and
+// their energies land in ranking.rel (allocated by the first of these calls after a growing rank_reserve)
+rgcn_status rank_relation_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, const int64_t* filt_ptr,
+                                  const int32_t* filt_idx, int32_t* raw_out, int32_t* filt_out);
+rgcn_status topk_relation_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int k, const int64_t* excl_ptr,
+                                  const int32_t* excl_idx, int32_t* idx_out, float* energy_out);
+rgcn_status score_relation_queries_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N);
 void optimizer_free(rgcn_ctx* c);
 
 // ---- comm.cpp (RCCL via dlopen)

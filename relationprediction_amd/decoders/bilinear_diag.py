@@ -70,6 +70,12 @@ class BilinearDiag(Model):
         all_object_codes = self.next_component.get_all_object_codes(mode='test')
         return _sigmoid(np.matmul(e1s * rs, all_object_codes.T))
 
+    def predict_all_relation_scores(self):
+        """score of every relation between the subject and object of the triples fed to X: [N, RelationCount]"""
+        e1s, rs, e2s = self.compute_codes(mode='test')
+        relation_codes = self.next_component.get_all_codes(mode='test')[1]
+        return _sigmoid(np.matmul(e1s * e2s, relation_codes[:self.relation_count].T))
+
     # ---- fused device paths: what the training driver and the scorer use (the eager numpy methods above
     # keep the reference's call-by-call surface and serve as their small-size cross-check)
     def configure_device_optimizer(self, learning_rate, beta1=0.9, beta2=0.999, epsilon=1e-8, max_grad_norm=0.0):
@@ -143,6 +149,19 @@ class BilinearDiag(Model):
         device address of its engine's score buffer (same GPU).  Returns (entity ids int32 [N,k], mixed scores float32
         [N,k]) ordered by (mixed score descending, entity id ascending); one chunk of at most Scorer.chunk_size queries."""
         return self._scoring_runtime(graph).topk_mixed(queries, predict_object, k, partner, weight, exclude_ptr, exclude_idx)
+
+    def device_relation_ranks(self, graph, triplets, filter_ptr, filter_idx):
+        """Ranks of the gold relations of `triplets` against every relation between their subject and object, codes
+        from a test-mode pass over `graph` (rgcn_rank_relation_device): (raw int32 [N], filtered int32 [N]).  filter_ptr /
+        filter_idx: CSR of the relations known for each pair, the gold one among them."""
+        return self._scoring_runtime(graph).ranks_relation(triplets, filter_ptr, filter_idx)
+
+    def device_relation_topk(self, graph, queries, k, exclude_ptr=None, exclude_idx=None):
+        """The k most plausible relations of (s, ?, o) for every row of `queries`, best first, leaving out row i's
+        exclude_idx[exclude_ptr[i]:exclude_ptr[i + 1]]; codes from a test-mode pass over `graph`
+        (rgcn_topk_relation_device).  Returns (relation ids int32 [N,k], energies float32 [N,k]); the relation column is
+        not read; rows short of k answers end in (-1, -inf).  Scores are _sigmoid(energies)."""
+        return self._scoring_runtime(graph).topk_relation(queries, k, exclude_ptr, exclude_idx)
 
     def predict_top(self, predict_object, k, exclude_ptr=None, exclude_idx=None):
         """device_topk restated eagerly on predict_all_object_scores / predict_all_subject_scores of the triples fed

@@ -134,6 +134,10 @@ class Model(object):
         self._feed_test(self.test_graph, triplets)
         return self.predict_all_object_scores()
 
+    def score_all_relations(self, triplets):
+        self._feed_test(self.test_graph, triplets)
+        return self.predict_all_relation_scores()
+
     def register_for_test(self, triplets):
         self.test_graph = triplets
 
@@ -180,6 +184,9 @@ class Model(object):
     def predict_all_object_scores(self):
         return self.__delegate__('predict_all_object_scores')
 
+    def predict_all_relation_scores(self):
+        return self.__delegate__('predict_all_relation_scores')
+
     def get_graph(self):
         return self.__delegate__('get_graph')
 
@@ -221,6 +228,12 @@ class Model(object):
 
     def device_topk_mixed(self, *args, **kwargs):
         return self.__delegate__('device_topk_mixed', *args, **kwargs)
+
+    def device_relation_ranks(self, *args):
+        return self.__delegate__('device_relation_ranks', *args)
+
+    def device_relation_topk(self, *args, **kwargs):
+        return self.__delegate__('device_relation_topk', *args, **kwargs)
 
     def predict_top(self, *args, **kwargs):
         return self.__delegate__('predict_top', *args, **kwargs)

@@ -1,8 +1,9 @@
-"""Ask a trained model: the k most plausible completions of (entity, relation, ?) or (?, relation, entity).
+"""Ask a trained model: the k most plausible completions of (entity, relation, ?), (?, relation, entity) or
+(subject, ?, object).
 
     python -m relationprediction_amd.predict --settings settings/gcn_block.exp --dataset data/FB-Toutanova \
-        --model models/GcnBlock-3.npz --queries queries.txt --k 10 [--side object|subject] [--keep-known] [--out FILE] \
-        [--settings2 settings/distmult.exp --model2 models/Distmult-3.npz [--weight 0.5]]
+        --model models/GcnBlock-3.npz --queries queries.txt --k 10 [--side object|subject|relation] [--keep-known] \
+        [--out FILE] [--settings2 settings/distmult.exp --model2 models/Distmult-3.npz [--weight 0.5]]
 
 The model is built exactly as train.py builds it (same settings merge, same chain), the checkpoint is one written by
 Model.save, the training graph is encoded once in test mode and the selection runs on the device (rgcn_topk_device:
@@ -18,6 +19,16 @@ Completions already known from train / valid / test are left out unless --keep-k
 
 position counts from 1 (best); score = sigmoid(energy), evaluated in double and rounded once to float32 as everywhere
 else (csrc/ranking.hip).  Answers are ordered by (energy descending, entity id ascending).
+
+--side relation asks which relation holds between two entities (rgcn_topk_relation_device: the energies of every
+relation for the pair, selected on the device alike).  --queries lines are then `subject<TAB>object`, --k is bounded by
+the number of relations, the relations known for the pair from train / valid / test are left out unless --keep-known,
+and the output lines are
+
+    subject<TAB>answer_relation<TAB>object<TAB>position<TAB>score
+
+ordered by (energy descending, relation id ascending).  There is no ensemble form: with --settings2 / --model2 it is a
+ValueError.
 
 --settings2 and --model2 (together) ask the R-GCN+ ensemble instead: a second model, built and loaded the same way on the
 same GPU, is scored with the first as `weight * score_1 + (1 - weight) * score_2` (ensemble.py's mixture; --weight is
@@ -54,6 +65,23 @@ def read_queries(path, entity_ids, relation_ids):
     return pairs
 
 
+def read_pair_queries(path, entity_ids):
+    """[(subject id, object id)] of a --side relation query file; errors as read_queries'"""
+    pairs = []
+    with open(path, "r") as f:
+        for number, line in enumerate(f, start=1):
+            if not line.strip():
+                continue
+            fields = line.rstrip("\r\n").split("\t")
+            if len(fields) != 2:
+                raise ValueError("%s line %d: expected subject<TAB>object, got %d field(s)" % (path, number, len(fields)))
+            for entity in fields:
+                if entity not in entity_ids:
+                    raise ValueError("%s line %d: unknown entity %r" % (path, number, entity))
+            pairs.append((entity_ids[fields[0]], entity_ids[fields[1]]))
+    return pairs
+
+
 def build_model(settings, splits, n_entities, n_relations):
     """The training driver's own chain (train.build_model, train.initialize_model), ready for test-mode calls."""
     from . import train
@@ -72,10 +100,12 @@ def main(argv=None, out=None):
     parser.add_argument("--settings", help="Filepath for settings file.", required=True)
     parser.add_argument("--dataset", help="Filepath for dataset.", required=True)
     parser.add_argument("--model", help="checkpoint written by Model.save (.npz)", required=True)
-    parser.add_argument("--queries", help="file of entity<TAB>relation lines (names)", required=True)
+    parser.add_argument("--queries", help="file of entity<TAB>relation lines (names); --side relation: subject<TAB>object",
+                        required=True)
     parser.add_argument("--k", type=int, default=10, help="answers per query (at most %d)" % MAX_K)
-    parser.add_argument("--side", choices=("object", "subject"), default="object",
-                        help="what is predicted: the object of (entity, relation, ?) or the subject of (?, relation, entity)")
+    parser.add_argument("--side", choices=("object", "subject", "relation"), default="object",
+                        help="what is predicted: the object of (entity, relation, ?), the subject of (?, relation, entity) "
+                             "or the relation of (subject, ?, object)")
     parser.add_argument("--keep-known", action="store_true",
                         help="do not leave out the completions known from train / valid / test")
     parser.add_argument("--out", default=None, help="write the answers here instead of standard output")
@@ -87,6 +117,8 @@ def main(argv=None, out=None):
     if (args.settings2 is None) != (args.model2 is None):
         raise ValueError("--settings2 and --model2 come together")
     ensemble = args.settings2 is not None
+    if ensemble and args.side == "relation":
+        raise ValueError("--side relation has no ensemble form: drop --settings2 / --model2")
     if args.weight is not None and not ensemble:
         raise ValueError("--weight needs --settings2 and --model2")
     weight = 0.5 if args.weight is None else args.weight
@@ -96,6 +128,8 @@ def main(argv=None, out=None):
     settings = settings_reader.read(args.settings)
     from .train import load_dataset
     splits, entities, relations = load_dataset(args.dataset, settings['Evaluation']['Metric'])
+    if args.side == "relation":
+        return predict_relations(args, settings, splits, entities, relations, out)
     if not 1 <= args.k <= min(len(entities), MAX_K):
         raise ValueError("--k %d: must be between 1 and min(number of entities = %d, %d)"
                          % (args.k, len(entities), MAX_K))
@@ -148,6 +182,42 @@ def main(argv=None, out=None):
                 if answer < 0:
                     break                                            # fewer than k entities were left to answer
                 sink.write("%s\t%s\t%s\t%d\t%.9g\n" % (entities[entity], relations[relation], entities[int(answer)],
+                                                       position, score))
+    finally:
+        if args.out:
+            sink.close()
+    return top, scores
+
+
+def predict_relations(args, settings, splits, entities, relations, out):
+    """main() for --side relation: (relation ids int32 [N,k], scores float32 [N,k])"""
+    if not 1 <= args.k <= min(len(relations), MAX_K):
+        raise ValueError("--k %d: must be between 1 and min(number of relations = %d, %d)"
+                         % (args.k, len(relations), MAX_K))
+    pairs = read_pair_queries(args.queries, {name: i for i, name in entities.items()})
+    ptr = idx = None
+    if not args.keep_known:
+        scorer = evaluation.Scorer(settings['Evaluation'])
+        for part in ('train', 'valid', 'test'):
+            scorer.register_data(splits[part])
+        ptr, idx = evaluation.known_completions_csr(pairs, scorer.known_relation_triples)
+
+    model = build_model(settings, splits, len(entities), len(relations))
+    model.load(args.model)
+    queries = np.full((len(pairs), 3), -1, dtype=np.int32)         # the relation column is not read
+    if pairs:
+        queries[:, 0] = [p[0] for p in pairs]
+        queries[:, 2] = [p[1] for p in pairs]
+    top, energies = model.device_relation_topk(model.test_graph, queries, args.k, ptr, idx)
+    scores = sigmoid_f32(energies)
+
+    sink = open(args.out, "w") if args.out else (out or sys.stdout)
+    try:
+        for (subject, obj), ids, row in zip(pairs, top, scores):
+            for position, (answer, score) in enumerate(zip(ids, row), start=1):
+                if answer < 0:
+                    break                                            # fewer than k relations were left to answer
+                sink.write("%s\t%s\t%s\t%d\t%.9g\n" % (entities[subject], relations[int(answer)], entities[obj],
                                                        position, score))
     finally:
         if args.out:

@@ -330,6 +330,21 @@ class EncoderRuntime(object):
         device address; N <= chunk."""
         return self._scoring_engine(chunk).topk_mixed(queries, predict_object, k, partner, weight, exclude_ptr, exclude_idx)
 
+    def ranks_relation(self, triples, filter_ptr, filter_idx, chunk=2048):
+        """Raw / filtered ranks of the gold relation among all relations between each triple's subject and object
+        (rgcn_rank_relation_device), on the codes of a test-mode forward over the fed graph."""
+        return self._scoring_engine(chunk).ranks_relation(triples, filter_ptr, filter_idx)
+
+    def topk_relation(self, queries, k, exclude_ptr=None, exclude_idx=None, chunk=2048):
+        """The k best relations between the subject and object of every query, best first (rgcn_topk_relation_device):
+        (relation ids int32 [N,k], energies float32 [N,k])."""
+        return self._scoring_engine(chunk).topk_relation(queries, k, exclude_ptr, exclude_idx)
+
+    def score_relation_queries(self, queries, chunk=2048):
+        """The energies of every relation for each query's pair, left in the engine's relation buffer
+        (rgcn_score_relation_queries_device; engine.relation_energies_device() is its address); N <= chunk."""
+        self._scoring_engine(chunk).score_relation_queries(queries)
+
     def backward(self, dcodes):
         if self._state is None or self._state[1] != 'train':
             raise RuntimeError("backward() needs a train-mode forward pass on the current graph")

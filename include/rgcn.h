@@ -189,11 +189,14 @@ enum {
   RGCN_BUF_RANK_MIXED_SCORES = 17, /* float [reserved queries, V]: the mixed scores of the last rgcn_topk_mixed_device (what
                                    it selected from, bit for bit).  RGCN_ERR_STATE before the first such call, and again
                                    after a growing rgcn_rank_reserve until the next one */
-  RGCN_BUF_RELATION_ENERGIES = 18 /* float [reserved queries, RelationCount]: energies of the last chunk
+  RGCN_BUF_RELATION_ENERGIES = 18, /* float [reserved queries, RelationCount]: energies of the last chunk
                                    rgcn_rank_relation_device, rgcn_topk_relation_device or
                                    rgcn_score_relation_queries_device scored (what the counts and the selection are integer
                                    work on).  RGCN_ERR_STATE before the first such call, and again after a growing
                                    rgcn_rank_reserve until the next one */
+  RGCN_BUF_OUT_DH = 19          /* float [V,d], contexts with an output transform (rgcn_config_ext::code_dim > 0): dL/dH_L of
+                                   the last backward pass = dcodes . W_out^T, what the layer stack received as its dcodes.
+                                   RGCN_ERR_STATE on every other context and before the first backward pass */
 };
 
 /*
@@ -207,7 +210,7 @@ typedef struct rgcn_config {
   int32_t device;         /* HIP device ordinal */
   int32_t num_entities;   /* V = EntityCount */
   int32_t num_relations;  /* R = RelationCount */
-  int32_t dim;            /* d = InternalEncoderDimension (= CodeDimension, UseOutputTransform=No) */
+  int32_t dim;            /* d = InternalEncoderDimension (the code width too, unless rgcn_config_ext::code_dim says otherwise) */
   int32_t num_layers;     /* L = NumberOfLayers (RGCN_KIND_EMBEDDING: 0) */
   int32_t kind;           /* RGCN_KIND_* */
   int32_t num_bases;      /* NumberOfBasisFunctions: block count nb (BLOCK, d % nb == 0) or B (BASIS, BASIS_TDIAG, BASIS_PDIAG) */
@@ -220,10 +223,26 @@ typedef struct rgcn_config {
 } rgcn_config;
 
 /* rgcn_config is full (64 bytes, pinned): what came later is passed beside it.  struct_size must be
- * sizeof(rgcn_config_ext), else RGCN_ERR_INVALID. */
+ * sizeof(rgcn_config_ext), or 8 -- the layout before code_dim, read as code_dim = 0 -- else RGCN_ERR_INVALID.
+ *
+ * code_dim: the encoder's output transform (UseOutputTransform=Yes, code/common/model_builder.py:131-135,170-177,
+ * code/encoders/affine_transform.py:63-83): a dense AffineTransform on top of the last graph convolution,
+ *     codes = H_L . W_out + b_out        W_out [d, c], b_out [c], no relu, no dropout, train and test mode alike.
+ *   0   no output layer: the codes are H_L, c = d, everything as rgcn_create builds it;
+ *   c > 0   the layer exists (also when c == d: the reference applies it whenever the flag says Yes).  W_out and b_out sit
+ *       between the last layer's parameters (its highway pair included) and W_relation, which becomes [EntityCount, c]
+ *       (Model.get_weights() order).  Everything on the code side is c wide: rgcn_get_codes, rgcn_codes_device,
+ *       rgcn_dcodes_device, the dcodes of rgcn_backward / _device / rgcn_step_device, the decoder, and the query rows of
+ *       every rgcn_rank_*, rgcn_topk_* and rgcn_score_* call.  rgcn_get_activation(L) stays H_L [V,d].
+ *       The layer sees H_L only: every kind but RGCN_KIND_EMBEDDING (the reference's embedding branch has no such layer),
+ *       both rgcn_set_fusion forms, one-hot input, highway, every RGCN_NORM_* and every rgcn_set_gemm_mode work.  With
+ *       world > 1 (W_out's gradient has no exchange point), with RGCN_KIND_EMBEDDING or with EntityCount x c >= 2^31
+ *       rgcn_create_ex returns RGCN_ERR_UNSUPPORTED, and so does rgcn_capture_begin on such a context.
+ *   c < 0   RGCN_ERR_INVALID. */
 typedef struct rgcn_config_ext {
   int32_t struct_size;
   int32_t skip_mode;      /* RGCN_SKIP_* */
+  int32_t code_dim;       /* c = CodeDimension of the output transform; 0: none (the codes are H_L) */
 } rgcn_config_ext;
 
 /* ---- lifecycle ------------------------------------------------------------------------------ */
@@ -235,8 +254,8 @@ int32_t rgcn_abi_version(void);
  * draws the reference's numpy initialisers (shared_functions.py:16-29) and pushes them. */
 rgcn_status rgcn_create(const rgcn_config* cfg, rgcn_ctx** out);
 /* The same with the extended settings; ext == NULL: their defaults (RGCN_SKIP_NONE) -- rgcn_create(cfg, out) is
- * rgcn_create_ex(cfg, NULL, out).  A wrong struct_size or an unknown skip_mode: RGCN_ERR_INVALID; RGCN_SKIP_HIGHWAY
- * with world > 1 or with RGCN_INPUT_ONEHOT: RGCN_ERR_UNSUPPORTED. */
+ * rgcn_create_ex(cfg, NULL, out).  A wrong struct_size, an unknown skip_mode or a negative code_dim: RGCN_ERR_INVALID;
+ * RGCN_SKIP_HIGHWAY with world > 1 or with RGCN_INPUT_ONEHOT: RGCN_ERR_UNSUPPORTED; code_dim > 0: see rgcn_config_ext. */
 rgcn_status rgcn_create_ex(const rgcn_config* cfg, const rgcn_config_ext* ext, rgcn_ctx** out);
 rgcn_status rgcn_destroy(rgcn_ctx* ctx);
 
@@ -308,19 +327,22 @@ rgcn_status rgcn_get_graph_edges(rgcn_ctx* ctx, int32_t* host, int64_t count);
  *   - dropout_masks_host != NULL: the caller's uint8 [L,V,d] 0/1 masks (parity testing), else
  *   - a counter-based generator keyed by (dropout_seed, layer, element) -- nothing is stored;
  *     rgcn_get_dropout_mask() re-materialises what the last forward used.
- * The result H_L [V,d] is the subject AND object code matrix (relation_embedding.py:23-25). */
+ * The result H_L [V,d] is the subject AND object code matrix (relation_embedding.py:23-25); on a context with an output
+ * transform (rgcn_config_ext::code_dim = c > 0) the code matrix is H_L . W_out + b_out [V,c] and H_L stays readable
+ * through rgcn_get_activation(L). */
 rgcn_status rgcn_forward(rgcn_ctx* ctx, int32_t train, uint64_t dropout_seed,
                          const uint8_t* dropout_masks_host);
-rgcn_status rgcn_get_codes(rgcn_ctx* ctx, float* host, int64_t count);              /* H_L  */
+rgcn_status rgcn_get_codes(rgcn_ctx* ctx, float* host, int64_t count);              /* the codes: H_L [V,d], or [V,c] */
 /* RGCN_INPUT_ONEHOT: there is no H_0 (message_gcn.py:28-36 hands the layer the vertex ids); layer 0 is RGCN_ERR_INVALID */
 rgcn_status rgcn_get_activation(rgcn_ctx* ctx, int32_t layer, float* host, int64_t count); /* H_0..H_L */
 rgcn_status rgcn_get_dropout_mask(rgcn_ctx* ctx, int32_t layer /*1..L*/, uint8_t* host, int64_t count);
-const float* rgcn_codes_device(rgcn_ctx* ctx);                                      /* device H_L (RGCN_KIND_EMBEDDING: W_emb's
+const float* rgcn_codes_device(rgcn_ctx* ctx);                                      /* device codes (RGCN_KIND_EMBEDDING: W_emb's
                                                                                        own storage -- after an optimizer step the
                                                                                        updated table) */
 
 /* ---- backward: tf.gradients(loss, weights) restricted to the encoder (abstract.py:117-118) -----
- * dcodes = dL/dH_L [V,d] (the decoder's gradient w.r.t. subject+object codes, already summed).
+ * dcodes = dL/dcodes: dL/dH_L [V,d], or [V,c] under an output transform (the decoder's gradient w.r.t. subject+object
+ * codes, already summed).
  * Needs a preceding rgcn_forward on the same graph.  Gradients are then readable by rgcn_get_grad. */
 rgcn_status rgcn_backward(rgcn_ctx* ctx, const float* dcodes_host, int64_t count);
 rgcn_status rgcn_backward_device(rgcn_ctx* ctx, const float* dcodes_dev);

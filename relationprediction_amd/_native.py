@@ -28,6 +28,7 @@ BUF_PDIAG_MIX = 15           # basis_pdiag contexts: [2, V, B], the mixing table
 BUF_PDIAG_AGG = 16           # basis_pdiag contexts: [V, d], the diagonal aggregate of the layer run last
 BUF_RANK_MIXED_SCORES = 17   # [reserved queries, V], the mixed scores the last topk_mixed selected from
 BUF_RELATION_ENERGIES = 18   # [reserved queries, R], the energies of the chunk a relation query scored last
+BUF_OUT_DH = 19              # contexts with an output transform: [V, d], dL/dH_L of the last backward pass
 
 KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS, "basis_tdiag": KIND_BASIS_TDIAG,
          "basis_pdiag": KIND_BASIS_PDIAG, "embedding": KIND_EMBEDDING}
@@ -67,7 +68,7 @@ class RgcnConfig(C.Structure):
 
 
 class RgcnConfigExt(C.Structure):
-    _fields_ = [("struct_size", C.c_int32), ("skip_mode", C.c_int32)]
+    _fields_ = [("struct_size", C.c_int32), ("skip_mode", C.c_int32), ("code_dim", C.c_int32)]
 
 
 _lib = None
@@ -322,11 +323,15 @@ class Engine:
     first basis layer reads per-entity tables (UseInputTransform=No; include/rgcn.h RGCN_INPUT_ONEHOT).
     skip "highway": every layer wrapped in a highway layer (SkipConnections=Highway; RGCN_SKIP_HIGHWAY), created through
     rgcn_create_ex; skip "none" goes through rgcn_create.  create_ex (tests): True = rgcn_create_ex with the extension
-    struct whatever `skip` is, "null" = rgcn_create_ex with a NULL extension."""
+    struct whatever `skip` is, "null" = rgcn_create_ex with a NULL extension.
+    code_dim c (UseOutputTransform=Yes; rgcn_config_ext::code_dim): a dense output layer codes = H_L . W_out + b_out on top
+    of the last layer, also when c == dim; the code side -- codes(), backward(), dcodes(), W_relation, every ranking and
+    top-k call -- is self.dc = c wide, the layer stack keeps self.d.  None or 0: no such layer, self.dc == self.d.
+    ext_struct_size (tests): the struct_size the extension struct announces instead of its own size."""
 
     def __init__(self, num_entities, num_relations, dim, num_layers, kind, num_bases, keep_prob=0.8,
                  norm_mode="intended", max_edges=0, device=0, rank=0, world=1, devtools=False, input_mode="embedding",
-                 skip="none", create_ex=None):
+                 skip="none", create_ex=None, code_dim=None, ext_struct_size=None):
         self.lib = load_library(devtools=devtools)
         self.ctx = None
         cfg = RgcnConfig()
@@ -349,15 +354,22 @@ class Engine:
         skip_mode = SKIP_MODES[skip] if isinstance(skip, str) else int(skip)
         if create_ex == "null":
             st = self.lib.rgcn_create_ex(C.byref(cfg), None, C.byref(ctx))
-        elif skip_mode == SKIP_NONE and not create_ex:
+        elif skip_mode == SKIP_NONE and not create_ex and code_dim is None and ext_struct_size is None:
             st = self.lib.rgcn_create(C.byref(cfg), C.byref(ctx))
         else:
-            ext = RgcnConfigExt(C.sizeof(RgcnConfigExt), skip_mode)
+            ext = RgcnConfigExt(C.sizeof(RgcnConfigExt) if ext_struct_size is None else int(ext_struct_size), skip_mode,
+                                int(code_dim or 0))
             st = self.lib.rgcn_create_ex(C.byref(cfg), C.byref(ext), C.byref(ctx))
         if st != 0:
             raise RgcnError(st, (self.lib.rgcn_last_error(None) or b"").decode())
         self.ctx = ctx
         self.V, self.R, self.d, self.L = cfg.num_entities, cfg.num_relations, cfg.dim, cfg.num_layers
+        # the code width: the library read code_dim only from an extension struct of the current size
+        self.dc = int(code_dim) if code_dim and create_ex != "null" and ext_struct_size in (None, C.sizeof(RgcnConfigExt)) \
+            else self.d
+        # what the methods below size their arrays by: callers hang attributes of their own on an engine (the sharded test
+        # worker keeps its dcodes buffer in `e.dc`), which must not change what the binding hands the library
+        self._code_width = self.dc
         self.max_edges = int(cfg.max_edges)
         self.param_names, self.param_shapes = [], []
         for i in range(self.lib.rgcn_param_count(self.ctx)):
@@ -491,7 +503,9 @@ class Engine:
         self._check(self.lib.rgcn_forward(self.ctx, 1 if train else 0, C.c_uint64(seed), p))
 
     def codes(self):
-        return self.activation(self.L)
+        out = np.empty((self.V, self._code_width), dtype=np.float32)
+        self._check(self.lib.rgcn_get_codes(self.ctx, _ptr(out), out.size))
+        return out
 
     def activation(self, layer):
         out = np.empty((self.V, self.d), dtype=np.float32)
@@ -505,8 +519,8 @@ class Engine:
 
     def backward(self, dcodes):
         g = np.ascontiguousarray(dcodes, dtype=np.float32)
-        if g.shape != (self.V, self.d):
-            raise ValueError("dcodes must be [V,d]")
+        if g.shape != (self.V, self._code_width):
+            raise ValueError("dcodes must be [V,d] ([V,code_dim] under an output transform)")
         self._check(self.lib.rgcn_backward(self.ctx, _ptr(g), g.size))
 
     def backward_device(self, dev_buffer):
@@ -530,7 +544,7 @@ class Engine:
         self._check(self.lib.rgcn_backward_device(self.ctx, self.lib.rgcn_dcodes_device(self.ctx)))
 
     def dcodes(self):
-        out = np.empty((self.V, self.d), dtype=np.float32)
+        out = np.empty((self.V, self._code_width), dtype=np.float32)
         self._check(self.lib.rgcn_copy_to_host(self.ctx, _ptr(out), self.lib.rgcn_dcodes_device(self.ctx), out.nbytes))
         return out
 

@@ -1,5 +1,7 @@
 """Plugin registry (reference: code/common/model_builder.py): maps `Encoder.Name` and its flags to a
-chain of components.  Only the hot-path family is built: `Name=gcn_basis` with UseOutputTransform=No, SkipConnections
+chain of components.  Only the hot-path family is built: `Name=gcn_basis` with UseOutputTransform=No or -- for the
+Concatenation=No stacks (BasisGcn, BasisGcnTimesDiag, BasisGcnWithDiag) -- Yes (the dense AffineTransform
+[InternalEncoderDimension, CodeDimension] over the top layer, :131-135,170-177), SkipConnections
 None or Highway (every layer wrapped in extras/highway_layer.py; UseInputTransform=Yes only) and none of the
 experimental layer flags except DiagonalCoefficients=Yes (BasisGcnTimesDiag, with the reference's precedence over
 Concatenation; UseInputTransform=Yes and SkipConnections=None only) and AddDiagonal=Yes (BasisGcnWithDiag; the same two
@@ -70,9 +72,15 @@ def build_encoder(encoder_settings, triples):
     if input_transform == "No" and concat:
         raise NotImplementedError("UseInputTransform=No with Concatenation=Yes: the reference's one-hot branch of "
                                   "ConcatGcn cannot execute (gcn_basis_concat.py:18-19,42-46)")
-    for key in ('UseOutputTransform', 'StoreEdgeData', 'RandomInput', 'PartiallyRandomInput'):
+    for key in ('StoreEdgeData', 'RandomInput', 'PartiallyRandomInput'):
         if _flag(encoder_settings, key) == "Yes":
             raise NotImplementedError("%s=Yes selects a reference variant outside the hot path" % key)
+    output_transform = _flag(encoder_settings, 'UseOutputTransform') == "Yes"
+    if output_transform and concat:
+        # (the engine runs the layer over the block kind too; the plugin holds it back: the block kind is the one with
+        # sharding, capture and the deferred-join schedule, none of which is built for the layer -- INTEGRATION.md)
+        raise NotImplementedError("UseOutputTransform=Yes selects a reference variant outside the hot path beside "
+                                  "Concatenation=Yes (the plugin builds the output transform over Concatenation=No stacks)")
     skip = _flag(encoder_settings, 'SkipConnections', 'None')
     if skip not in ('None', 'Highway'):
         raise NotImplementedError("SkipConnections other than None")
@@ -99,8 +107,9 @@ def build_encoder(encoder_settings, triples):
     input_shape = [int(encoder_settings['EntityCount']), int(encoder_settings['InternalEncoderDimension'])]
     internal_shape = [int(encoder_settings['InternalEncoderDimension']),
                       int(encoder_settings['InternalEncoderDimension'])]
+    projection_shape = [int(encoder_settings['InternalEncoderDimension']), int(encoder_settings['CodeDimension'])]
     relation_shape = [int(encoder_settings['EntityCount']), int(encoder_settings['CodeDimension'])]
-    if int(encoder_settings['CodeDimension']) != internal_shape[1]:
+    if not output_transform and int(encoder_settings['CodeDimension']) != internal_shape[1]:
         raise NotImplementedError("CodeDimension != InternalEncoderDimension needs UseOutputTransform=Yes")
     layers = int(encoder_settings['NumberOfLayers'])
 
@@ -111,6 +120,9 @@ def build_encoder(encoder_settings, triples):
         encoding = graph      # RandomInput / PartiallyRandomInput are refused above: the layers sit on the graph itself
     encoding = apply_basis_gcn(encoder_settings, encoding, internal_shape, layers,
                                onehot_first=input_transform == "No")
+    if output_transform:      # (model_builder.py:170-177: applied whenever the flag says Yes, also at equal dimensions)
+        encoding = AffineTransform(projection_shape, encoder_settings, next_component=encoding, onehot_input=False,
+                                   use_nonlinearity=False, use_bias=True)
     return RelationEmbedding(relation_shape, encoder_settings, next_component=encoding)
 
 

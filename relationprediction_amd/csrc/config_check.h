@@ -109,4 +109,21 @@ inline ConfigVerdict check_config(const rgcn_config& f, bool highway) {
   return ConfigVerdict{RGCN_OK, ""};
 }
 
+// The output transform (rgcn_config_ext::code_dim; 0: no such layer): what rgcn_create_ex refuses of it, asked AFTER
+// check_config has accepted the configuration -- whatever breaks a rule above is refused for that rule first
+// (tests/sanitize/output_transform_config_driver.cpp prints the answers, tests/test_output_transform_config.py holds them).
+inline ConfigVerdict check_output_transform(const rgcn_config& f, bool highway, int32_t code_dim) {
+  (void)highway;      // (the layer sits above H_L whatever wraps the layers: a highway context takes it like any other)
+  if (code_dim < 0) return refuse(RGCN_ERR_INVALID, "code_dim must be 0 (no output transform) or the positive CodeDimension");
+  if (code_dim == 0) return ConfigVerdict{RGCN_OK, ""};
+  if (f.kind == RGCN_KIND_EMBEDDING)
+    return refuse(RGCN_ERR_UNSUPPORTED, "code_dim > 0 with RGCN_KIND_EMBEDDING (the reference's embedding encoder has no "
+                                        "output transform, model_builder.py:27-41)");
+  if (f.world > 1)
+    return refuse(RGCN_ERR_UNSUPPORTED, "code_dim > 0 on a sharded context (the gradient of W_out has no exchange point)");
+  if ((int64_t)f.num_entities * (int64_t)code_dim >= ((int64_t)1 << 31))
+    return refuse(RGCN_ERR_UNSUPPORTED, "code_dim > 0: EntityCount x CodeDimension must be below 2^31");
+  return ConfigVerdict{RGCN_OK, ""};
+}
+
 }  // namespace rgcn

@@ -811,7 +811,7 @@ rgcn_status decoder_reserve(rgcn_ctx* c, int64_t maxN) {
   DecoderBufs& q = c->dec;
   if (q.maxN >= maxN && q.maxN > 0) return RGCN_OK;
   decoder_free(c);
-  const size_t N = (size_t)maxN, V = c->V, R = c->R, d = c->d;
+  const size_t N = (size_t)maxN, V = c->V, R = c->R, d = c->dc;      // (the decoder works at the code width)
   RGCN_TRY(dmalloc(c, q.pool, &q.keyv, 2 * N, false));
   RGCN_TRY(dmalloc(c, q.pool, &q.keyv_s, 2 * N, false));
   RGCN_TRY(dmalloc(c, q.pool, &q.valv, 2 * N, false));
@@ -931,7 +931,7 @@ rgcn_status decoder_prepare(rgcn_ctx* c, const int32_t* X, int64_t N64, int64_t 
 rgcn_status decoder_compute(rgcn_ctx* c, const float* codes, const float* Y, float reg_param, float* dcodes_drop,
                             const DropSpec* drop) {
   DecoderBufs& q = c->dec;
-  const int N = q.N, V = c->V, R = c->R, d = c->d;
+  const int N = q.N, V = c->V, R = c->R, d = c->dc;
   const int Nt = q.N_total > 0 ? (int)q.N_total : N;      // denominator of the batch mean
   const float* Wr = c->w_rel;
   float* gWr = c->g_rel;
@@ -1051,8 +1051,8 @@ rgcn_status decoder_compute(rgcn_ctx* c, const float* codes, const float* Y, flo
 // (bilinear_diag.py:27-34,63-69), which is what makes the split exact up to summation order.
 rgcn_status decoder_allreduce(rgcn_ctx* c) {
   DecoderBufs& q = c->dec;
-  RGCN_TRY(comm_allreduce(c, c->dcodes_own, (int64_t)c->V * c->d));
-  RGCN_TRY(comm_allreduce(c, c->g_rel, (int64_t)c->R * c->d));
+  RGCN_TRY(comm_allreduce(c, c->dcodes_own, (int64_t)c->V * c->dc));
+  RGCN_TRY(comm_allreduce(c, c->g_rel, (int64_t)c->R * c->dc));
   hipLaunchKernelGGL(k_loss_narrow, dim3(1), dim3(1), 0, c->stream, q.loss, q.loss_part);
   RGCN_TRY(comm_allreduce(c, q.loss_part, 1));
   hipLaunchKernelGGL(k_loss_widen, dim3(1), dim3(1), 0, c->stream, q.loss_part, q.loss);

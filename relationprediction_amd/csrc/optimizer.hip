@@ -180,7 +180,7 @@ rgcn_status build_table(rgcn_ctx* c, OptTable& tab, int* nrep, double* total) {
       if (p.no_grad) continue;                       // the never-used layer bias: TF returns None for it
       if ((int)is_sharded_param(c, p) != pass) continue;
       int64_t n = p.count;
-      if (p.name == "W_relation") n = (int64_t)c->R * c->d;     // rows >= RelationCount never get a gradient
+      if (p.name == "W_relation") n = (int64_t)c->R * c->dc;    // rows >= RelationCount never get a gradient
       if (!o.m[i]) {
         RGCN_TRY(dmalloc(c, o.pool, &o.m[i], (size_t)n, true));
         RGCN_TRY(dmalloc(c, o.pool, &o.v[i], (size_t)n, true));

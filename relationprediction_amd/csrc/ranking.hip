@@ -468,7 +468,7 @@ rgcn_status rank_reserve(rgcn_ctx* c, int64_t max_queries) {
   RankBufs& q = c->ranking;
   if (max_queries <= q.max) return RGCN_OK;
   rank_free(c);
-  RGCN_TRY(dmalloc(c, q.pool, &q.q, (size_t)max_queries * c->d, false));
+  RGCN_TRY(dmalloc(c, q.pool, &q.q, (size_t)max_queries * c->dc, false));
   RGCN_TRY(dmalloc(c, q.pool, &q.s, (size_t)max_queries * c->V, false));
   RGCN_TRY(dmalloc(c, q.pool, &q.bad, 1, false));
   RGCN_TRY(dmalloc(c, q.pool, &q.thr, (size_t)max_queries, false));
@@ -513,23 +513,24 @@ static rgcn_status relation_energies_reserve(rgcn_ctx* c) {
 // the query rows of X[0, n) into ranking.q, their energies against every candidate into the side's buffer: every entity
 // into ranking.s, or (SIDE_RELATION) every relation into ranking.rel
 static rgcn_status score_chunk(rgcn_ctx* c, const int32_t* X, int n, int side) {
-  const float* codes = c->H[c->L];
+  const float* codes = c->codes;
+  const int dc = c->dc;      // the code width: the query rows, W_relation and the codes
   if (side == SIDE_RELATION) {
     {
-      ProfScope ps(c, "rank_query_relation", 4.0 * 3 * n * c->d, 0);
-      hipLaunchKernelGGL(k_rank_pair, dim3((unsigned)n), dim3(128), 0, c->stream, codes, X, n, c->d, c->ranking.q, c->V);
+      ProfScope ps(c, "rank_query_relation", 4.0 * 3 * n * dc, 0);
+      hipLaunchKernelGGL(k_rank_pair, dim3((unsigned)n), dim3(128), 0, c->stream, codes, X, n, dc, c->ranking.q, c->V);
       RGCN_HIP(c, hipGetLastError());
     }
-    return gemm_f32(c, "rank_scores_relation", true, true, n, c->R, c->d, c->ranking.q, c->d, c->w_rel, c->d, c->ranking.rel,
+    return gemm_f32(c, "rank_scores_relation", true, true, n, c->R, dc, c->ranking.q, dc, c->w_rel, dc, c->ranking.rel,
                     c->R, 1);
   }
   {
-    ProfScope ps(c, "rank_query", 4.0 * 3 * n * c->d, 0);
-    hipLaunchKernelGGL(k_rank_query, dim3((unsigned)n), dim3(128), 0, c->stream, codes, c->w_rel, X, n, c->d,
+    ProfScope ps(c, "rank_query", 4.0 * 3 * n * dc, 0);
+    hipLaunchKernelGGL(k_rank_query, dim3((unsigned)n), dim3(128), 0, c->stream, codes, c->w_rel, X, n, dc,
                        side, c->ranking.q, c->V, c->R);
     RGCN_HIP(c, hipGetLastError());
   }
-  return gemm_f32(c, "rank_scores", true, true, n, c->V, c->d, c->ranking.q, c->d, codes, c->d, c->ranking.s, c->V, 1);
+  return gemm_f32(c, "rank_scores", true, true, n, c->V, dc, c->ranking.q, dc, codes, dc, c->ranking.s, c->V, 1);
 }
 
 // One call: the check, then chunk by chunk of the reserve the scoring and tail(b, n, X) -- what the call does with the

@@ -357,6 +357,7 @@ static rgcn_status create_embedding(rgcn_ctx* c) {
   add_param(c, "W_relation", {(int64_t)V, (int64_t)d}, c->w_rel, c->g_rel, LAYOUT_PLAIN);
   c->layers.resize(1);
   c->H.assign(1, c->w_emb);             // the codes ARE the table
+  c->codes = c->w_emb;
   c->dcodes_own = c->g_emb;             // the decoder's dL/dcodes lands where the optimizer reads dL/dW_emb
   // the ranking GEMM's launcher wants the zero page and a slab pointer (split_k = 1: no slab is ever written)
   c->slab_floats = 1024;
@@ -565,12 +566,26 @@ static rgcn_status create_params(rgcn_ctx* c) {
 
 // W_relation (the decoder's, behind the layers in get_weights()) and what every kind keeps per layer and per pass
 static rgcn_status create_activations(rgcn_ctx* c) {
-  const size_t V = c->V, d = c->d, Vd = (size_t)c->V_pad * d;
-  RGCN_TRY(dmalloc(c, c->pool, &c->w_rel, Vd, true));
-  RGCN_TRY(dmalloc(c, c->pool, &c->g_rel, Vd, true));
-  add_param(c, "W_relation", {(int64_t)V, (int64_t)d}, c->w_rel, c->g_rel, LAYOUT_PLAIN);
+  const size_t V = c->V, d = c->d, dc = c->dc, Vd = (size_t)c->V_pad * d, Vc = (size_t)c->V_pad * dc;
+  if (c->out_layer) {      // the output transform (model_builder.py:170-177): [W, b] of the AffineTransform under RelationEmbedding
+    RGCN_TRY(dmalloc(c, c->pool, &c->w_out, d * dc, true));
+    RGCN_TRY(dmalloc(c, c->pool, &c->g_w_out, d * dc, true));
+    RGCN_TRY(dmalloc(c, c->pool, &c->b_out, dc, true));
+    RGCN_TRY(dmalloc(c, c->pool, &c->g_b_out, dc, true));
+    RGCN_TRY(dmalloc(c, c->pool, &c->wout_nn, 16 * gemm_bfrag_words((int)d, (int)dc), false));
+    add_param(c, "W_out", {(int64_t)d, (int64_t)dc}, c->w_out, c->g_w_out, LAYOUT_PLAIN);
+    add_param(c, "b_out", {(int64_t)dc}, c->b_out, c->g_b_out, LAYOUT_PLAIN);
+  }
+  RGCN_TRY(dmalloc(c, c->pool, &c->w_rel, Vc, true));
+  RGCN_TRY(dmalloc(c, c->pool, &c->g_rel, Vc, true));
+  add_param(c, "W_relation", {(int64_t)V, (int64_t)dc}, c->w_rel, c->g_rel, LAYOUT_PLAIN);
   c->H.assign(c->L + 1, nullptr);
   for (int l = c->onehot ? 1 : 0; l <= c->L; ++l) RGCN_TRY(dmalloc(c, c->pool, &c->H[l], Vd, true));   // (one-hot input: no H_0)
+  c->codes = c->H[c->L];
+  if (c->out_layer) {
+    RGCN_TRY(dmalloc(c, c->pool, &c->codes, Vc, true));
+    RGCN_TRY(dmalloc(c, c->pool, &c->out_dh, Vd, true));
+  }
   RGCN_TRY(dmalloc(c, c->pool, &c->self_buf, Vd, true));
   if (c->highway) {
     c->hw_N.assign(c->L + 1, nullptr);
@@ -649,7 +664,7 @@ static rgcn_status create_basis_scratch(rgcn_ctx* c, size_t max_rel_chunks, size
 // what every kind ends with: the split-K slabs, the staging buffer of the layout conversions, the column-sum scratch, the
 // zero page, the two graph sets, the relation owner table
 static rgcn_status create_shared_tail(rgcn_ctx* c, size_t slab) {
-  const size_t V = c->V, d = c->d, R = c->R, Vd = (size_t)c->V_pad * d;
+  const size_t V = c->V, d = std::max(c->d, c->dc), R = c->R, Vd = (size_t)c->V_pad * d;      // (d: the wider of the two widths)
   c->slab_floats = slab;
   RGCN_TRY(dmalloc(c, c->pool, &c->slab, slab, true));
   size_t stage = Vd;
@@ -679,7 +694,11 @@ static rgcn_status create_impl(rgcn_ctx* c) {
   const rgcn_config& f = c->cfg;
   const ConfigVerdict verdict = check_config(f, c->highway);
   if (verdict.status != RGCN_OK) RGCN_FAIL(c, verdict.status, verdict.message);
+  const ConfigVerdict out_verdict = check_output_transform(f, c->highway, c->dc);      // (dc: still the caller's code_dim)
+  if (out_verdict.status != RGCN_OK) RGCN_FAIL(c, out_verdict.status, out_verdict.message);
   c->V = f.num_entities; c->R = f.num_relations; c->d = f.dim; c->L = f.num_layers; c->kind = f.kind;
+  c->out_layer = c->dc > 0;
+  if (!c->out_layer) c->dc = c->d;
   c->rank = f.rank; c->world = f.world;
   c->onehot = f.input_mode == RGCN_INPUT_ONEHOT;
   c->embedding = f.kind == RGCN_KIND_EMBEDDING;
@@ -706,6 +725,7 @@ static rgcn_status create_impl(rgcn_ctx* c) {
   RGCN_TRY(create_activations(c));
   const size_t M = 2 * (size_t)f.max_edges;
   size_t slab = 64 * (size_t)c->d * c->d;   // split-K slabs of the dW_self GEMM
+  if (c->out_layer) slab = std::max(slab, 64 * (size_t)c->d * c->dc);      // ... and of the dW_out GEMM ([d, dc], as many slabs at most)
   // most relation chunks any graph that fits the context can have: the chunk size follows the graph's own size
   // (graph_build), so a graph of 65536 messages cut at 48 can have more chunks than the largest graph cut coarser
   const size_t max_rel_chunks = std::max((M + c->chunk - 1) / c->chunk, (std::min<size_t>(M, 65536) + 47) / 48) + 2 * (size_t)c->R;
@@ -749,8 +769,10 @@ rgcn_status rgcn_create(const rgcn_config* cfg, rgcn_ctx** out) { return rgcn_cr
 rgcn_status rgcn_create_ex(const rgcn_config* cfg, const rgcn_config_ext* ext, rgcn_ctx** out) {
   if (!cfg || !out) { set_global_error("rgcn_create: NULL argument"); return RGCN_ERR_INVALID; }
   *out = nullptr;
-  if (ext && ext->struct_size != (int32_t)sizeof(rgcn_config_ext)) {
-    set_global_error("rgcn_create_ex: rgcn_config_ext::struct_size is not sizeof(rgcn_config_ext)");
+  // 8: the layout before code_dim (struct_size, skip_mode), read as code_dim = 0
+  if (ext && ext->struct_size != (int32_t)sizeof(rgcn_config_ext) && ext->struct_size != 8) {
+    set_global_error("rgcn_create_ex: rgcn_config_ext::struct_size is neither sizeof(rgcn_config_ext) nor 8 (the layout "
+                     "before code_dim)");
     return RGCN_ERR_INVALID;
   }
   if (ext && ext->skip_mode != RGCN_SKIP_NONE && ext->skip_mode != RGCN_SKIP_HIGHWAY) {
@@ -761,6 +783,7 @@ rgcn_status rgcn_create_ex(const rgcn_config* cfg, const rgcn_config_ext* ext, r
   if (!c) { set_global_error("out of host memory"); return RGCN_ERR_NOMEM; }
   c->cfg = *cfg;
   c->highway = ext && ext->skip_mode == RGCN_SKIP_HIGHWAY;
+  c->dc = ext && ext->struct_size == (int32_t)sizeof(rgcn_config_ext) ? ext->code_dim : 0;      // (create_impl checks it)
   rgcn_status s = create_impl(c);
   if (s != RGCN_OK) {
     set_global_error(c->err);
@@ -870,9 +893,14 @@ rgcn_status rgcn_get_activation(rgcn_ctx* c, int32_t layer, float* host, int64_t
 }
 rgcn_status rgcn_get_codes(rgcn_ctx* c, float* host, int64_t count) {
   if (!c) return RGCN_ERR_INVALID;
-  return rgcn_get_activation(c, c->L, host, count);
+  if (!c->out_layer) return rgcn_get_activation(c, c->L, host, count);
+  RGCN_NEED(c);
+  if (!host || count != (int64_t)c->V * c->dc) RGCN_FAIL(c, RGCN_ERR_INVALID, "need a [V,CodeDimension] host buffer");
+  if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "no completed forward pass");
+  RGCN_TRY(check_dev_flag(c));
+  return to_host(c, host, c->codes, sizeof(float) * (size_t)count);
 }
-const float* rgcn_codes_device(rgcn_ctx* c) { return c ? c->H[c->L] : nullptr; }
+const float* rgcn_codes_device(rgcn_ctx* c) { return c ? c->codes : nullptr; }
 
 rgcn_status rgcn_get_dropout_mask(rgcn_ctx* c, int32_t layer, uint8_t* host, int64_t count) {
   RGCN_NEED(c);
@@ -890,7 +918,7 @@ rgcn_status rgcn_backward_device(rgcn_ctx* c, const float* dcodes_dev) {
 }
 rgcn_status rgcn_backward(rgcn_ctx* c, const float* dcodes_host, int64_t count) {
   RGCN_NEED(c);
-  if (!dcodes_host || count != (int64_t)c->V * c->d) RGCN_FAIL(c, RGCN_ERR_INVALID, "dcodes must be [V,d]");
+  if (!dcodes_host || count != (int64_t)c->V * c->dc) RGCN_FAIL(c, RGCN_ERR_INVALID, "dcodes must be [V,d] ([V,CodeDimension] under an output transform)");
   if (!c->dcodes_own) RGCN_TRY(dmalloc(c, c->pool, &c->dcodes_own, (size_t)count, false));
   RGCN_TRY(join_abandoned_side_work(c));      // (unjoined side kernels may read the previous dcodes)
   RGCN_TRY(to_dev(c, c->dcodes_own, dcodes_host, sizeof(float) * (size_t)count));
@@ -973,7 +1001,7 @@ rgcn_status rgcn_decoder_loss_backward_device(rgcn_ctx* c, const int32_t* X_dev,
   // pass on the same batch and holds identical dL/dcodes and dL/dW_relation (the kernels are deterministic)
   if (c->dec.maxN < N) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_decoder_reserve(ctx, max_triples) first");
   RGCN_TRY(decoder_prepare(c, X_dev, N));
-  RGCN_TRY(decoder_compute(c, c->H[c->L], Y_dev, reg_param));
+  RGCN_TRY(decoder_compute(c, c->codes, Y_dev, reg_param));
   RGCN_TRY(stream_join(c, 2));      // the relation gradient ran on its own side stream
   c->dec.loss_valid = true;
   return RGCN_OK;
@@ -1193,9 +1221,10 @@ static rgcn_status train_step_tail(rgcn_ctx* c, const int32_t* X_dev, const floa
   // one GPU: the decoder's entity-gradient kernel also writes dL/dcodes * dropout_L, the operand of the top layer's
   // self-loop GEMMs (a sharded run scales after the all-reduce of the partial dL/dcodes, in bwd_begin)
   const DropSpec top_drop = make_drop(c, c->L, true);
-  // (a highway context forms dS_L itself, from G_L T_L: bwd_layer_partial)
-  float* ds_ready = (c->world == 1 && !c->highway && top_drop.mode != DROP_NONE) ? c->dsbuf[c->L & 1] : nullptr;
-  RGCN_TRY(decoder_compute(c, c->H[c->L], Y_loc, reg_param, ds_ready, &top_drop));
+  // (a highway context forms dS_L itself, from G_L T_L: bwd_layer_partial; under an output transform the top layer's D is
+  // dcodes . W_out^T, which bwd_begin forms and scales: a dropout copy of the [V,dc] dcodes is of no use)
+  float* ds_ready = (c->world == 1 && !c->highway && !c->out_layer && top_drop.mode != DROP_NONE) ? c->dsbuf[c->L & 1] : nullptr;
+  RGCN_TRY(decoder_compute(c, c->codes, Y_loc, reg_param, ds_ready, &top_drop));
   if (c->world > 1) {
     RGCN_TRY(stream_join(c, 2));    // the relation gradient's reduce ran on its own side stream: it is all-reduced too
     RGCN_TRY(decoder_allreduce(c));
@@ -1378,6 +1407,9 @@ rgcn_status rgcn_capture_begin(rgcn_ctx* c) {
   if (c->highway)
     RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "rgcn_capture_begin: capture on an RGCN_SKIP_HIGHWAY context is not supported (a captured "
                                        "highway step has never been replayed against a reference)");
+  if (c->out_layer)
+    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "rgcn_capture_begin: capture on a context with an output transform (code_dim > 0) is not "
+                                       "supported (a captured step with the layer has never been replayed against a reference)");
   if (c->kind == RGCN_KIND_BASIS_TDIAG)
     RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "rgcn_capture_begin: capture on an RGCN_KIND_BASIS_TDIAG context is not supported (a "
                                        "captured step of this kind has never been replayed against a reference)");
@@ -1604,6 +1636,10 @@ static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* byte
       if (which == RGCN_BUF_PDIAG_MIX) { *p = c->pdiag_a[c->pdiag_last]; *bytes = (int64_t)2 * c->V * c->B * 4; }
       else { *p = c->pdiag_agg; *bytes = Vd; }
       return RGCN_OK;
+    case RGCN_BUF_OUT_DH:
+      if (!c->out_layer) RGCN_FAIL(c, RGCN_ERR_STATE, "not a context with an output transform (rgcn_config_ext::code_dim > 0)");
+      if (!c->out_dh_valid) RGCN_FAIL(c, RGCN_ERR_STATE, "no backward pass has run");
+      *p = c->out_dh; *bytes = Vd; return RGCN_OK;
     default: RGCN_FAIL(c, RGCN_ERR_INVALID, "unknown buffer id");
   }
 }

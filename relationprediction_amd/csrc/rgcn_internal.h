@@ -343,7 +343,7 @@ struct OptimizerState {
 // ranking scratch (csrc/ranking.hip)
 struct RankBufs {
   DevPool pool;
-  float *q = nullptr, *s = nullptr;      // query rows [max,d], energies [max,V]
+  float *q = nullptr, *s = nullptr;      // query rows [max,dc], energies [max,V]
   int32_t* bad = nullptr;
   float* thr = nullptr;                  // per query: the smallest energy whose fp32 sigmoid reaches the gold entity's
   float* mixed = nullptr;                // mixed scores [max,V]: null until the first rgcn_topk_mixed_device at this size
@@ -360,6 +360,18 @@ struct rgcn_ctx {
   // sets, the decoder batch, the sampler, the optimizer and the ranking scratch own theirs (their structs' pools).
   rgcn::DevPool pool;
   int V = 0, R = 0, d = 0, L = 0, nb = 0, sd = 0, kind = 0, B = 0;
+  // The code width (CodeDimension): what the decoder, the ranking calls, W_relation and dcodes are wide.  dc == d and
+  // codes == H[L] unless the context has an output transform (rgcn_config_ext::code_dim > 0; output_transform.hip):
+  //   codes = H_L . W_out + b_out [V,dc]; the backward pass opens with out_dh = dcodes . W_out^T [V,d], which the layer
+  //   stack takes for its dcodes (RGCN_BUF_OUT_DH), g_w_out = H_L^T . dcodes and g_b_out = the column sums of dcodes.
+  // The layer stack keeps d.
+  int dc = 0;
+  bool out_layer = false;
+  float *w_out = nullptr, *g_w_out = nullptr, *b_out = nullptr, *g_b_out = nullptr;
+  void* wout_nn = nullptr;                // W_out's fragment table (the B operand of H_L . W_out; split arithmetic only)
+  float* codes = nullptr;                 // [V,dc]; H[L] itself on a context without the layer
+  float* out_dh = nullptr;                // [V,d]
+  bool out_dh_valid = false;              // a backward pass has written out_dh
   int rank = 0, world = 1;
   // highway skip connections around every layer (rgcn_config_ext::skip_mode == RGCN_SKIP_HIGHWAY; highway.hip; one GPU,
   // embedding input): the layers write N_l, the highway pass T_l and H_l; all four buffers exist on such a context only
@@ -424,7 +436,7 @@ struct rgcn_ctx {
   std::vector<rgcn::Param> params;
   std::vector<rgcn::LayerBufs> layers;   // index 1..L (0 unused)
   float *w_emb = nullptr, *g_emb = nullptr, *b_emb = nullptr, *gb_emb = nullptr;
-  float *w_rel = nullptr, *g_rel = nullptr;   // W_relation [EntityCount, d] (decoder weight)
+  float *w_rel = nullptr, *g_rel = nullptr;   // W_relation [EntityCount, dc] (decoder weight)
   rgcn::DecoderBufs dec;
   rgcn::NeighborhoodBufs nbr;
   rgcn::OptimizerState opt;
@@ -490,7 +502,7 @@ struct rgcn_ctx {
   std::vector<hipGraph_t> graph_defs;
   float* giant_slab = nullptr;           // [piece_cap][d] partial sums of giant-row pieces (scratch of one combine launch)
   rgcn::RankBufs ranking;
-  float* dcodes_own = nullptr;           // [V,d] staging for the host variant of backward
+  float* dcodes_own = nullptr;           // [V,dc] staging for the host variant of backward
 
   // comm
   void* comm = nullptr;                  // ncclComm_t
@@ -699,6 +711,8 @@ rgcn_status column_sum_finish(rgcn_ctx* c, float* out, int nparts, int cols);
 rgcn_status input_forward(rgcn_ctx* c);                      // H0 = relu(W_emb + b_emb)
 rgcn_status scale_dropout(rgcn_ctx* c, const float* in, float* out, const DropSpec& ds);
 rgcn_status column_sum(rgcn_ctx* c, const float* in, float* out, int rows, int cols);
+// ---- output_transform.hip: x[v][:] += b over the [rows, cols] array x, in place (the bias of the output transform)
+rgcn_status add_row_bias(rgcn_ctx* c, float* x, const float* b, int rows, int cols);
 rgcn_status relu_copy(rgcn_ctx* c, const float* in, float* out, int64_t n, int relu);
 rgcn_status materialize_mask(rgcn_ctx* c, const DropSpec& ds, uint8_t* out_dev, int64_t n);
 

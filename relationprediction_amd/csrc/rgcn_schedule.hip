@@ -88,6 +88,7 @@ static rgcn_status refresh_weight_fragments(rgcn_ctx* c) {
         jobs.push_back(PresplitJob{W, static_cast<char*>(lb.wrel_nt) + 16 * g * gemm_bfrag_words(d, Bd), d, d, Bd, 1});
       }
   }
+  if (c->out_layer) jobs.push_back(PresplitJob{c->w_out, c->wout_nn, c->dc, d, c->dc, 0});      // H_L . W_out: B (k, n) = W[k][n]
   if (!jobs.empty()) RGCN_TRY(gemm_presplit_b(c, jobs.data(), (int)jobs.size()));
   c->frag_fresh = true;
   c->frag_version = c->capturing ? ~0ull : c->weights_version;
@@ -313,6 +314,33 @@ rgcn_status fwd_layer_partial(rgcn_ctx* c, int l) {
   }
 }
 
+// The output transform (output_transform.hip), the tail of the forward pass whatever the layer kind: codes = H_L . W_out +
+// b_out -- the product with W_out as the pre-split B operand, wide like the other forward products, then the bias in place.
+// No dropout: train and test mode run the same two launches.
+static rgcn_status output_forward(rgcn_ctx* c) {
+  const int d = c->d, dc = c->dc, V = c->V;
+  RGCN_TRY(refresh_weight_fragments(c));      // (a one-hot single-layer stack launches no other product)
+  GemmBatch b;
+  if (c->gemm_mode != 0) b.bfrag = c->wout_nn;
+  b.wide = 1;
+  RGCN_TRY(gemm_f32(c, "gemm_out_fwd", true, false, V, dc, d, c->H[c->L], d, c->w_out, dc, c->codes, dc, 1, &b));
+  return add_row_bias(c, c->codes, c->b_out, V, dc);
+}
+
+// The layer's backward pass, ahead of the stack's (bwd_begin): three launches on the main stream, in this order --
+//   out_dh  = dcodes . W_out^T     (NT; what the layer stack takes for its dcodes)
+//   g_W_out = H_L^T . dcodes       (TN, split-K)
+//   g_b_out = the column sums of dcodes
+static rgcn_status output_backward(rgcn_ctx* c, const float* dcodes) {
+  const int d = c->d, dc = c->dc, V = c->V;
+  RGCN_TRY(gemm_f32(c, "gemm_out_dh", true, true, V, d, dc, dcodes, dc, c->w_out, dc, c->out_dh, d, 1));
+  RGCN_TRY(gemm_f32(c, "gemm_out_dw", false, false, d, dc, V, c->H[c->L], d, dcodes, dc, c->g_w_out, dc,
+                    auto_split_k(d, dc, V)));
+  RGCN_TRY(column_sum(c, dcodes, c->g_b_out, V, dc));
+  c->out_dh_valid = true;
+  return RGCN_OK;
+}
+
 rgcn_status fwd_layer_finish(rgcn_ctx* c, int l) {
   RGCN_NO_EMBEDDING(c, "rgcn_forward_layer_finish");
   if (l < 1 || l > c->L) RGCN_FAIL(c, RGCN_ERR_INVALID, "layer out of range");
@@ -328,6 +356,7 @@ rgcn_status fwd_layer_finish(rgcn_ctx* c, int l) {
   }
   if (c->kind == RGCN_KIND_BASIS_TDIAG) c->tdiag_last = l;
   if (c->kind == RGCN_KIND_BASIS_PDIAG) c->pdiag_last = l;
+  if (l == c->L && c->out_layer) RGCN_TRY(output_forward(c));
   if (l == c->L) c->fwd_done = true;
   return RGCN_OK;
 }
@@ -339,7 +368,7 @@ rgcn_status fwd_layer_finish(rgcn_ctx* c, int l) {
 // pass that starts while the previous one's side kernels are unjoined queues its own behind them IN STREAM ORDER: the
 // slabs and the gradients they share need no event.
 static bool deferred_schedule(const rgcn_ctx* c) {
-  return !c->highway && c->defer_end_joins && c->kind == RGCN_KIND_BLOCK && c->fuse == 1 && block_rows_available(c) && c->world == 1 &&
+  return !c->highway && !c->out_layer && c->defer_end_joins && c->kind == RGCN_KIND_BLOCK && c->fuse == 1 && block_rows_available(c) && c->world == 1 &&
          c->g.E <= 65536 && c->use_aux && !c->capturing && c->L >= 2 && c->stream == c->main_stream;
 }
 
@@ -354,6 +383,13 @@ rgcn_status bwd_begin(rgcn_ctx* c, const float* dcodes_dev, const float* ds_read
   // kernel that reads (SIDE_READS_JOINED), this pass's side kernels follow the pending ones in stream order, and its
   // column-sum partials go to the other half of the scratch (bwd_end): the main stream waits for nothing.
   if (!(c->side_state == rgcn_ctx::SIDE_READS_JOINED && deferred_schedule(c))) RGCN_TRY(join_abandoned_side_work(c));
+  if (c->out_layer) {
+    // the output transform first; the pass then continues with dL/dH_L in the place of dcodes (a ready-made dS would be a
+    // dropout copy of the [V,dc] dcodes: of no use)
+    RGCN_TRY(output_backward(c, dcodes_dev));
+    dcodes_dev = c->out_dh;
+    ds_ready = nullptr;
+  }
   c->bwd_layer = c->L;
   c->bwd_D = dcodes_dev;
   if (c->highway) {      // dcodes is G_L; D_L and dS_L are the highway pass's (bwd_layer_partial), a ready-made dS is of no use
@@ -772,7 +808,7 @@ rgcn_status backward_all(rgcn_ctx* c, const float* dcodes_dev, const float* ds_r
     if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_backward needs a completed rgcn_forward");
     if (!dcodes_dev) RGCN_FAIL(c, RGCN_ERR_INVALID, "dcodes is NULL");
     if (dcodes_dev != c->g_emb)
-      RGCN_HIP(c, hipMemcpyAsync(c->g_emb, dcodes_dev, sizeof(float) * (size_t)c->V * c->d, hipMemcpyDeviceToDevice, c->stream));
+      RGCN_HIP(c, hipMemcpyAsync(c->g_emb, dcodes_dev, sizeof(float) * (size_t)c->V * c->dc, hipMemcpyDeviceToDevice, c->stream));
     return RGCN_OK;
   }
   if (c->world > 1 && !c->comm)

@@ -6,12 +6,16 @@ gcn_basis settings build (UseInputTransform=Yes, model_builder.py:141-146), wire
 kernel k_input_fwd.  The second one built is the bias-free lookup of `Name=embedding`
 (model_builder.py:27-41: onehot_input=True, use_bias=False, use_nonlinearity=False, nothing beneath
 it): the codes ARE `W`, `b` is created and checkpointed but never read, and the component owns a
-graph-less runtime (runtime.EmbeddingRuntime, an RGCN_KIND_EMBEDDING engine context).  The dense
-branch (`matmul(code, W)`, used only by UseOutputTransform=Yes) is out of scope.
+graph-less runtime (runtime.EmbeddingRuntime, an RGCN_KIND_EMBEDDING engine context).  The third is
+the dense branch of UseOutputTransform=Yes (model_builder.py:170-177: onehot_input=False,
+use_bias=True, use_nonlinearity=False, over the graph-convolution stack): `codes = H_L . W + b`, run
+by the stack's engine context (rgcn_config_ext::code_dim, csrc/output_transform.hip); the component
+contributes `W_out [d, c]` and `b_out [c]` and returns the engine's codes.
 """
 from ..common.shared_functions import glorot_variance, make_variable, make_bias
+from ..extras.graph_representations import Representation
 from ..model import Model, Variable
-from ..runtime import EmbeddingRuntime
+from ..runtime import EmbeddingRuntime, EncoderRuntime
 
 
 class AffineTransform(Model):
@@ -32,17 +36,30 @@ class AffineTransform(Model):
         # the lookup of Name=embedding: bias-free, linear, with no component beneath it
         self.lookup = bool(onehot_input and not use_bias and not use_nonlinearity and next_component is None)
         self._lookup_runtime = None         # (the graph's runtime lives on the Representation; only the lookup owns one)
-        if not (onehot_input and use_bias and use_nonlinearity) and not self.lookup:
+        # the output transform of UseOutputTransform=Yes: dense, biased, linear, over a component chain
+        self.dense = bool(not onehot_input and use_bias and not use_nonlinearity and next_component is not None)
+        if not (onehot_input and use_bias and use_nonlinearity) and not self.lookup and not self.dense:
             raise NotImplementedError(
                 "AffineTransform is implemented as the encoder's input layer (onehot_input=True, use_bias=True, "
-                "use_nonlinearity=True) and as the 'embedding' encoder's lookup (onehot_input=True, use_bias=False, "
-                "use_nonlinearity=False, no component beneath it); the dense variants belong to "
-                "UseOutputTransform=Yes (out of scope)")
+                "use_nonlinearity=True), as the 'embedding' encoder's lookup (onehot_input=True, use_bias=False, "
+                "use_nonlinearity=False, no component beneath it) and as the output transform of "
+                "UseOutputTransform=Yes (onehot_input=False, use_bias=True, use_nonlinearity=False, over a layer stack)")
+
+    def _representation(self):
+        comp = self.next_component
+        while comp is not None and not isinstance(comp, Representation):
+            comp = comp.next_component
+        if comp is None:
+            raise NotImplementedError("the output transform sits over a graph-convolution stack")
+        return comp
 
     def local_initialize_train(self):
         variance = glorot_variance(self.shape)
-        self.W = Variable("W_emb", self.shape, make_variable(0, variance, tuple(self.shape)))
-        self.b = Variable("b_emb", (self.shape[1],), make_bias(self.shape[1]))
+        w_name, b_name = ("W_out", "b_out") if self.dense else ("W_emb", "b_emb")
+        self.W = Variable(w_name, self.shape, make_variable(0, variance, tuple(self.shape)))
+        self.b = Variable(b_name, (self.shape[1],), make_bias(self.shape[1]))
+        if self.dense:      # the stack's runtime, built when the first layer is asked, finds the layer here
+            self._representation()._output_transform = self
 
     def local_get_weights(self):
         return [self.W, self.b]
@@ -66,7 +83,10 @@ class AffineTransform(Model):
         return rep.runtime
 
     def get_all_codes(self, mode='train'):
-        h = self._runtime().forward(mode).activation(0)
+        if self.dense:
+            h = self.next_component.get_runtime().forward(mode).codes()
+        else:
+            h = self._runtime().forward(mode).activation(0)
         return h, None, h
 
     def get_all_subject_codes(self, mode='train'):
@@ -76,6 +96,9 @@ class AffineTransform(Model):
         return self.get_all_codes(mode)[2]
 
     def backward(self, runtime):
+        if self.dense:       # `runtime` is dL/dcodes [V,c]: it starts the engine's backward pass, the stack reports below
+            rt = runtime if isinstance(runtime, EncoderRuntime) else self.next_component.get_runtime().backward(runtime)
+            return self.next_component.backward(rt) + [rt.grad("W_out"), rt.grad("b_out")]
         if self.lookup:      # `runtime` is dL/dcodes [V,d], handed down by RelationEmbedding: it IS W's gradient
             rt = self._runtime().backward(runtime)
             return [rt.grad("W_emb"), rt.grad("b_emb")]

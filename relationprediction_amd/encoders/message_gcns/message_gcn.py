@@ -55,7 +55,8 @@ class MessageGcn(Model):
             while isinstance(c, MessageGcn):
                 layers.append(c)
                 c = _under(c)
-            rep.runtime = EncoderRuntime(list(reversed(layers)), affine, rep)
+            rep.runtime = EncoderRuntime(list(reversed(layers)), affine, rep,
+                                         output=getattr(rep, '_output_transform', None))
         return rep.runtime
 
     def local_initialize_train(self):

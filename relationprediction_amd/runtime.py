@@ -11,11 +11,13 @@ from . import _native
 
 
 class EncoderRuntime(object):
-    def __init__(self, layers, affine, representation):
+    def __init__(self, layers, affine, representation, output=None):
         """layers: MessageGcn components bottom -> top.  affine: the input layer under them, or None when the bottom
-        layer is featureless (onehot_input=True, UseInputTransform=No: it reads entity ids, there is no H_0)."""
+        layer is featureless (onehot_input=True, UseInputTransform=No: it reads entity ids, there is no H_0).  output:
+        the dense AffineTransform over the top layer (UseOutputTransform=Yes), or None: the codes are H_L."""
         self.layers = layers
         self.affine = affine
+        self.output = output
         self.representation = representation
         kinds = {type(l).KIND for l in layers}
         if len(kinds) != 1:
@@ -49,6 +51,10 @@ class EncoderRuntime(object):
         s = top.settings
         self.V, self.R = top.entity_count, top.relation_count
         self.d = int(top.shape[1])
+        if output is not None and int(output.shape[0]) != self.d:
+            raise ValueError("the output transform's shape %s does not start with InternalEncoderDimension %d"
+                             % (list(output.shape), self.d))
+        self.dc = int(output.shape[1]) if output is not None else self.d      # the code width
         norm = s['IncidenceNormalization'] if 'IncidenceNormalization' in s else 'intended'
         _native.norm_mode_value(norm)        # an unknown name: ValueError naming the accepted ones, before any engine exists
         device = int(s['Device']) if 'Device' in s else 0
@@ -59,7 +65,8 @@ class EncoderRuntime(object):
                                      keep_prob=top.dropout_keep_probability, norm_mode=norm,
                                      max_edges=max_edges, device=device,
                                      input_mode="embedding" if affine is not None else "onehot",
-                                     skip="highway" if self.highway else "none")
+                                     skip="highway" if self.highway else "none",
+                                     code_dim=self.dc if output is not None else None)
         self._state = None        # (graph version, mode) of the activations held by the engine
         self._dev = {}            # persistent device buffers of the fused train step (name -> DeviceBuffer)
         self._dec_reserved = 0
@@ -75,6 +82,9 @@ class EncoderRuntime(object):
             l.layer_index = i
             for var, base in l.engine_variables() + (self.highways[i - 1].engine_variables() if self.highway else []):
                 var.bind(*self._accessors("%s%d" % (base, i)))
+        if output is not None:
+            output.W.bind(*self._accessors("W_out"))
+            output.b.bind(*self._accessors("b_out"))
 
     def _accessors(self, name):
         eng = self.engine
@@ -106,6 +116,10 @@ class EncoderRuntime(object):
 
     def activation(self, layer):
         return self.engine.activation(layer)
+
+    def codes(self):
+        """[V, code width]: H_L, or the output transform's result"""
+        return self.engine.codes()
 
     # ---- fused device paths (include/rgcn.h: rgcn_train_step_device, rgcn_rank_device)
     def _upload(self, name, arr):
@@ -367,7 +381,8 @@ class EmbeddingRuntime(EncoderRuntime):
         self.highway = False
         s = affine.settings
         self.V, self.R = affine.entity_count, affine.relation_count
-        self.d = int(affine.shape[1])
+        self.d = self.dc = int(affine.shape[1])
+        self.output = None
         device = int(s['Device']) if 'Device' in s else 0
         self.engine = _native.Engine(self.V, self.R, self.d, 0, "embedding", 1, keep_prob=1.0, max_edges=0, device=device)
         self._state = None

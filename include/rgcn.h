@@ -562,12 +562,41 @@ rgcn_status rgcn_topk_relation_device(rgcn_ctx* ctx, const int32_t* x_dev, int64
  * algorithms.py:27-42,58-68).  max_grad_norm = 0 disables clipping. */
 rgcn_status rgcn_optimizer_config(rgcn_ctx* ctx, float learning_rate, float beta1, float beta2, float epsilon,
                                   float max_grad_norm);
+/* The reference's three [Algorithm] Name= values of the TensorFlow backend (algorithms.py:5-55) behind the same clip.
+ * With scale = the clip's factor (1 when max_grad_norm = 0) and g = scale * gradient:
+ *   RGCN_OPT_ADAM              as rgcn_optimizer_config; two state slots per parameter (0: m, 1: v), zeros at first;
+ *   RGCN_OPT_GRADIENT_DESCENT  tf.train.GradientDescentOptimizer(lr): w -= lr g; no state;
+ *   RGCN_OPT_ADAGRAD           tf.train.AdagradOptimizer(lr): a += g^2, w -= lr g / sqrt(a); one slot (the accumulator),
+ *                              filled with initial_accumulator (TensorFlow's default: 0.1) at first; there is no epsilon.
+ * An algorithm reads its own fields only (beta1, beta2, epsilon: Adam; initial_accumulator: AdaGrad).  struct_size must be
+ * sizeof(rgcn_optimizer_params).  Configuring the algorithm a context already has keeps its state and step count (a new
+ * initial_accumulator fills only slots created afterwards); another algorithm releases the state, restarts the count at 0
+ * and is RGCN_ERR_STATE during a capture (a graph captured before it must not be launched again). */
+enum { RGCN_OPT_ADAM = 0, RGCN_OPT_GRADIENT_DESCENT = 1, RGCN_OPT_ADAGRAD = 2 };
+typedef struct rgcn_optimizer_params {
+  int32_t struct_size, algorithm;
+  float learning_rate, beta1, beta2, epsilon, max_grad_norm, initial_accumulator;
+} rgcn_optimizer_params;
+rgcn_status rgcn_optimizer_config_ex(rgcn_ctx* ctx, const rgcn_optimizer_params* params);
+/* The optimizer's state, for inspection and for continuing a run.  A slot has its parameter's shape and travels in the
+ * parameter's host layout (as rgcn_get_param / rgcn_set_param; count = the parameter's element count).  W_relation carries
+ * state for its first RelationCount rows only: the other rows read as the slot's initial value and are ignored when
+ * written.  A slot that no step has created yet is created by the call (zeros, or initial_accumulator).  The step count is
+ * the DEVICE's (it advances inside the step, so a replayed hipGraph counts too): rgcn_get_optimizer_step synchronises.
+ * RGCN_ERR_STATE before rgcn_optimizer_config(_ex) and during a capture; RGCN_ERR_INVALID for a parameter that has no
+ * gradient (the unused layer bias) and for slot outside [0, rgcn_optimizer_slot_count); RGCN_ERR_UNSUPPORTED on a
+ * world > 1 context (a relation's state is current on its owner only). */
+int32_t     rgcn_optimizer_slot_count(const rgcn_ctx* ctx);      /* Adam 2 (m, v), AdaGrad 1, GradientDescent 0 */
+rgcn_status rgcn_get_optimizer_slot(rgcn_ctx* ctx, int32_t param, int32_t slot, float* host, int64_t count);
+rgcn_status rgcn_set_optimizer_slot(rgcn_ctx* ctx, int32_t param, int32_t slot, const float* host, int64_t count);
+rgcn_status rgcn_get_optimizer_step(rgcn_ctx* ctx, int64_t* t);
+rgcn_status rgcn_set_optimizer_step(rgcn_ctx* ctx, int64_t t);   /* 0 <= t < 2^24 */
 rgcn_status rgcn_optimizer_step(rgcn_ctx* ctx);
 /* The same step in two phases around its one exchange point on a relation-sharded context: the
  * squared norm of the relation-sharded gradients (block W_forward / W_backward, basis C_forward / C_backward:
  * owner-only, zero elsewhere) is a sum over ranks.  _norm_partial leaves this rank's share in
  * RGCN_BUF_NORM_EXCHANGE; the caller sum-all-reduces it (rgcn_optimizer_step does, with RCCL); _apply clips by
- * the global norm and runs Adam.  Replicated tensors receive identical updates on every rank; a relation's
+ * the global norm and runs the configured algorithm.  Replicated tensors receive identical updates on every rank; a relation's
  * weights are current on its owner only, so the owner map must stay fixed over a sharded training run.  The
  * stand-alone decoder pass (rgcn_decoder_loss_backward_device) is replicated: same batch, same result on every rank;
  * inside rgcn_train_step_device / rgcn_train_step_minibatch_device on a context with a communicator the decoder is

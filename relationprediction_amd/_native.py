@@ -71,6 +71,18 @@ class RgcnConfigExt(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("skip_mode", C.c_int32), ("code_dim", C.c_int32)]
 
 
+class RgcnOptimizerParams(C.Structure):
+    """rgcn_optimizer_params of include/rgcn.h"""
+    _fields_ = [("struct_size", C.c_int32), ("algorithm", C.c_int32), ("learning_rate", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("epsilon", C.c_float), ("max_grad_norm", C.c_float),
+                ("initial_accumulator", C.c_float)]
+
+
+# [Algorithm] Name= of the settings file -> RGCN_OPT_*
+OPT_ADAM, OPT_GRADIENT_DESCENT, OPT_ADAGRAD = 0, 1, 2
+ALGORITHMS = {"Adam": OPT_ADAM, "GradientDescent": OPT_GRADIENT_DESCENT, "AdaGrad": OPT_ADAGRAD}
+STATUS_INVALID = 1
+
 _lib = None
 
 _P = C.c_void_p
@@ -122,6 +134,12 @@ _SIGS = {
     "rgcn_relation_energies_device": (_P, [_P]),
     "rgcn_rank_relation_device": (C.c_int32, [_P, _P, C.c_int64, _P, _P, _P, _P]),
     "rgcn_topk_relation_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
+    "rgcn_optimizer_config_ex": (C.c_int32, [_P, C.POINTER(RgcnOptimizerParams)]),
+    "rgcn_optimizer_slot_count": (C.c_int32, [_P]),
+    "rgcn_get_optimizer_slot": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, C.c_int64]),
+    "rgcn_set_optimizer_slot": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, C.c_int64]),
+    "rgcn_get_optimizer_step": (C.c_int32, [_P, C.POINTER(C.c_int64)]),
+    "rgcn_set_optimizer_step": (C.c_int32, [_P, C.c_int64]),
     "rgcn_optimizer_step": (C.c_int32, [_P]),
     "rgcn_optimizer_norm_partial": (C.c_int32, [_P]),
     "rgcn_optimizer_apply": (C.c_int32, [_P]),
@@ -760,8 +778,78 @@ class Engine:
                                  lambda n, k, x, ptr, idx, ids, energies: self.lib.rgcn_topk_relation_device(
                                      self.ctx, x, n, k, ptr, idx, ids, energies))
 
-    def optimizer_config(self, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, max_grad_norm=1.0):
-        self._check(self.lib.rgcn_optimizer_config(self.ctx, lr, beta1, beta2, eps, max_grad_norm))
+    def optimizer_config(self, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, max_grad_norm=1.0, algorithm="Adam",
+                         initial_accumulator=0.1, struct_size=None):
+        """algorithm: "Adam", "GradientDescent" or "AdaGrad" (the settings' [Algorithm] Name=) or an RGCN_OPT_* number.
+        Adam goes through rgcn_optimizer_config, the other two through rgcn_optimizer_config_ex.  struct_size (tests):
+        rgcn_optimizer_config_ex whatever the algorithm, with a struct that announces this size."""
+        if isinstance(algorithm, str):
+            if algorithm not in ALGORITHMS:
+                raise ValueError("Algorithm.Name must be one of %s, not %r" % (", ".join(ALGORITHMS), algorithm))
+            algorithm = ALGORITHMS[algorithm]
+        if algorithm == OPT_ADAM and struct_size is None:
+            self._check(self.lib.rgcn_optimizer_config(self.ctx, lr, beta1, beta2, eps, max_grad_norm))
+        else:
+            p = RgcnOptimizerParams(C.sizeof(RgcnOptimizerParams) if struct_size is None else int(struct_size),
+                                    int(algorithm), lr, beta1, beta2, eps, max_grad_norm, initial_accumulator)
+            self._check(self.lib.rgcn_optimizer_config_ex(self.ctx, C.byref(p)))
+        self._algorithm = int(algorithm)
+
+    def optimizer_algorithm(self):
+        """name of the configured algorithm"""
+        number = getattr(self, "_algorithm", OPT_ADAM)
+        return [k for k, v in ALGORITHMS.items() if v == number][0]
+
+    def optimizer_slot_count(self):
+        return int(self.lib.rgcn_optimizer_slot_count(self.ctx))
+
+    def get_optimizer_slot(self, key, slot):
+        i = self._index(key)
+        out = np.empty(self.param_shapes[i], dtype=np.float32)
+        self._check(self.lib.rgcn_get_optimizer_slot(self.ctx, i, int(slot), _ptr(out), out.size))
+        return out
+
+    def set_optimizer_slot(self, key, slot, value):
+        i = self._index(key)
+        a = np.ascontiguousarray(value, dtype=np.float32)
+        if tuple(a.shape) != self.param_shapes[i]:
+            raise ValueError("%s slot %d: shape %s != %s" % (self.param_names[i], slot, a.shape, self.param_shapes[i]))
+        self._check(self.lib.rgcn_set_optimizer_slot(self.ctx, i, int(slot), _ptr(a), a.size))
+
+    def optimizer_step_count(self):
+        """steps taken, as the device counts them (replays of a captured graph included); synchronises"""
+        t = C.c_int64()
+        self._check(self.lib.rgcn_get_optimizer_step(self.ctx, C.byref(t)))
+        return int(t.value)
+
+    def set_optimizer_step_count(self, t):
+        self._check(self.lib.rgcn_set_optimizer_step(self.ctx, int(t)))
+
+    def optimizer_state(self):
+        """{"algorithm": name, "step": count, "slots": {parameter name: [one array per slot, the parameter's shape]}} of
+        every parameter the optimizer moves (a parameter without a gradient -- the unused layer bias -- has no entry);
+        Adam: [m, v], AdaGrad: [accumulator], GradientDescent: []"""
+        slots, count = {}, self.optimizer_slot_count()
+        for name in self.param_names if count else ():
+            try:
+                slots[name] = [self.get_optimizer_slot(name, s) for s in range(count)]
+            except RgcnError as e:
+                if e.status != STATUS_INVALID:      # (RGCN_ERR_INVALID: the library's answer for a parameter without state)
+                    raise
+        return {"algorithm": self.optimizer_algorithm(), "step": self.optimizer_step_count(), "slots": slots}
+
+    def set_optimizer_state(self, state):
+        """Continue from an optimizer_state(): its algorithm must be the configured one (ValueError naming both)."""
+        if state["algorithm"] != self.optimizer_algorithm():
+            raise ValueError("optimizer state of %s, the configured algorithm is %s"
+                             % (state["algorithm"], self.optimizer_algorithm()))
+        for name, arrays in state["slots"].items():
+            if len(arrays) != self.optimizer_slot_count():
+                raise ValueError("%s: %d slots, %s has %d" % (name, len(arrays), state["algorithm"],
+                                                              self.optimizer_slot_count()))
+            for s, a in enumerate(arrays):
+                self.set_optimizer_slot(name, s, a)
+        self.set_optimizer_step_count(state["step"])
 
     def optimizer_step(self):
         self._check(self.lib.rgcn_optimizer_step(self.ctx))

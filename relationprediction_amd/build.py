@@ -27,7 +27,8 @@ ARCH = "gfx950"
 SOURCES = ["rgcn_api.hip", "rgcn_schedule.hip", "rgcn_devtools.hip", "graph_prep.hip", "csr_sort.hip", "gemm_f32.hip", "gemm_bf16x3.hip", "gemm_bf16x3_w8.hip", "block_msgs.hip", "block_rows.hip", "basis.hip", "basis_onehot.hip", "basis_tdiag.hip", "basis_pdiag.hip",
            "elementwise.hip", "highway.hip", "output_transform.hip", "decoder.hip", "optimizer.hip", "ranking.hip", "sampler.hip", "neighborhood.hip", "comm.hip"]
 HEADERS = [os.path.join(CSRC, "rgcn_internal.h"), os.path.join(CSRC, "rgcn_api_internal.h"), os.path.join(CSRC, "gemm_split.h"), os.path.join(CSRC, "gemm_plan.h"),
-           os.path.join(CSRC, "dev_pool.h"), os.path.join(CSRC, "config_check.h"), os.path.join(CSRC, "row_walk.h"),
+           os.path.join(CSRC, "dev_pool.h"), os.path.join(CSRC, "config_check.h"), os.path.join(CSRC, "optimizer_check.h"),
+           os.path.join(CSRC, "row_walk.h"),
            os.path.join(ROOT, "include", "rgcn.h"),
            os.path.join(ROOT, "include", "rgcn_devtools.h")]
 DEVTOOLS_SOURCES = ["rgcn_api.hip", "rgcn_schedule.hip", "rgcn_devtools.hip", "comm.hip", "decoder.hip", "gemm_f32.hip"]       # the translation units the flag changes (knob())

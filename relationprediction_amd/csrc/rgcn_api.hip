@@ -7,6 +7,7 @@
 #include <new>
 
 #include "config_check.h"
+#include "optimizer_check.h"
 #include "rgcn_api_internal.h"
 
 namespace rgcn {
@@ -1162,13 +1163,105 @@ rgcn_status rgcn_topk_relation_device(rgcn_ctx* c, const int32_t* x_dev, int64_t
   return topk_relation_compute(c, x_dev, n, k, exclude_ptr_dev, exclude_idx_dev, topk_idx_dev, topk_energy_dev);
 }
 
-rgcn_status rgcn_optimizer_config(rgcn_ctx* c, float lr, float beta1, float beta2, float eps, float max_grad_norm) {
+rgcn_status rgcn_optimizer_config_ex(rgcn_ctx* c, const rgcn_optimizer_params* p) {
   RGCN_NEED(c);
-  if (!(lr > 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps > 0.f) ||
-      max_grad_norm < 0.f)
-    RGCN_FAIL(c, RGCN_ERR_INVALID, "bad optimizer hyper-parameters");
-  c->opt.lr = lr; c->opt.beta1 = beta1; c->opt.beta2 = beta2; c->opt.eps = eps; c->opt.max_norm = max_grad_norm;
-  c->opt.configured = true;
+  const OptimizerVerdict verdict = check_optimizer_params(p);
+  if (verdict.status != RGCN_OK) RGCN_FAIL(c, verdict.status, verdict.message);
+  OptimizerState& o = c->opt;
+  if (p->algorithm != o.algorithm) {
+    // the state of one algorithm means nothing to another: released, and the count starts over
+    if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "the optimizer's algorithm cannot change while a hipGraph is being captured");
+    RGCN_HIP(c, hipStreamSynchronize(c->stream));
+    optimizer_release_state(c);
+    o.algorithm = p->algorithm;
+  }
+  o.lr = p->learning_rate;
+  o.max_norm = p->max_grad_norm;
+  if (p->algorithm == RGCN_OPT_ADAM) { o.beta1 = p->beta1; o.beta2 = p->beta2; o.eps = p->epsilon; }
+  if (p->algorithm == RGCN_OPT_ADAGRAD) o.init_acc = p->initial_accumulator;
+  o.configured = true;
+  return RGCN_OK;
+}
+
+rgcn_status rgcn_optimizer_config(rgcn_ctx* c, float lr, float beta1, float beta2, float eps, float max_grad_norm) {
+  const rgcn_optimizer_params p = {(int32_t)sizeof(rgcn_optimizer_params), RGCN_OPT_ADAM, lr, beta1, beta2, eps,
+                                   max_grad_norm, 0.1f};
+  return rgcn_optimizer_config_ex(c, &p);
+}
+
+int32_t rgcn_optimizer_slot_count(const rgcn_ctx* c) { return c ? optimizer_slot_count(c) : 0; }
+
+// what every call on the optimizer's state refuses; param < 0: a call on the step count, which has no parameter
+static rgcn_status optimizer_state_check(rgcn_ctx* c, int32_t param, int32_t slot, const void* host, int64_t count) {
+  if (!c->opt.configured) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_optimizer_config was not called");
+  if (c->world > 1)
+    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "optimizer state on a sharded context (a relation's state is current on its owner only)");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "this call synchronises with the device: not allowed between rgcn_capture_begin and rgcn_capture_end");
+  if (param < 0) return RGCN_OK;
+  RGCN_TRY(param_check(c, param, host, count));
+  if (c->params[param].no_grad)
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "parameter " + c->params[param].name + " has no gradient and no optimizer state");
+  if (slot < 0 || slot >= optimizer_slot_count(c)) RGCN_FAIL(c, RGCN_ERR_INVALID, "optimizer slot out of range");
+  return RGCN_OK;
+}
+
+// A slot in its parameter's clothes: the same layout and, but for W_relation, the same element count -- W_relation's slot
+// holds the first RelationCount rows, which are the head of its (plain) host layout.
+static Param slot_as_param(const rgcn_ctx* c, int32_t param, int64_t n) {
+  Param q = c->params[param];
+  q.count = n;
+  return q;
+}
+
+rgcn_status rgcn_get_optimizer_slot(rgcn_ctx* c, int32_t param, int32_t slot, float* host, int64_t count) {
+  RGCN_NEED(c);
+  RGCN_TRY(optimizer_state_check(c, param, slot, host, count));
+  RGCN_TRY(check_dev_flag(c));
+  float* dev = nullptr;
+  int64_t n = 0;
+  RGCN_TRY(optimizer_slot(c, param, slot, &dev, &n));
+  RGCN_TRY(param_download(c, slot_as_param(c, param, n), dev, host));
+  const float initial = optimizer_slot_initial(c);
+  for (int64_t i = n; i < count; ++i) host[i] = initial;      // (W_relation's rows without state)
+  return RGCN_OK;
+}
+
+rgcn_status rgcn_set_optimizer_slot(rgcn_ctx* c, int32_t param, int32_t slot, const float* host, int64_t count) {
+  RGCN_NEED(c);
+  RGCN_TRY(optimizer_state_check(c, param, slot, host, count));
+  float* dev = nullptr;
+  int64_t n = 0;
+  RGCN_TRY(optimizer_slot(c, param, slot, &dev, &n));
+  const uint64_t version = c->weights_version;
+  RGCN_TRY(param_upload(c, slot_as_param(c, param, n), dev, host));
+  c->weights_version = version;      // (no weight changed: the tables derived from the weights are still right)
+  return RGCN_OK;
+}
+
+rgcn_status rgcn_get_optimizer_step(rgcn_ctx* c, int64_t* t) {
+  RGCN_NEED(c);
+  if (!t) RGCN_FAIL(c, RGCN_ERR_INVALID, "NULL pointer");
+  RGCN_TRY(optimizer_state_check(c, -1, 0, nullptr, 0));
+  RGCN_TRY(check_dev_flag(c));
+  float* state = nullptr;
+  RGCN_TRY(optimizer_state_array(c, &state));
+  float count = 0.f;
+  RGCN_TRY(to_host(c, &count, state + 2, sizeof(float)));
+  *t = (int64_t)count;
+  c->opt.t = *t;
+  return RGCN_OK;
+}
+
+rgcn_status rgcn_set_optimizer_step(rgcn_ctx* c, int64_t t) {
+  RGCN_NEED(c);
+  RGCN_TRY(optimizer_state_check(c, -1, 0, nullptr, 0));
+  // the device keeps the count as a float (state[2], beside the clip scale and the rate): exact below 2^24
+  if (t < 0 || t >= ((int64_t)1 << 24)) RGCN_FAIL(c, RGCN_ERR_INVALID, "optimizer step count outside [0, 2^24)");
+  float* state = nullptr;
+  RGCN_TRY(optimizer_state_array(c, &state));
+  const float count = (float)t;
+  RGCN_TRY(to_dev(c, state + 2, &count, sizeof(float)));
+  c->opt.t = t;
   return RGCN_OK;
 }
 

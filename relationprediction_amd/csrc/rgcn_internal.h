@@ -330,9 +330,11 @@ struct OptimizerState {
   DevPool pool;              // moments, state, shard_sq
   DevPool part_pool;         // `part` alone: it is the one buffer that grows
   bool configured = false;
+  int32_t algorithm = RGCN_OPT_ADAM;
   float lr = 0.01f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f, max_norm = 0.f;
+  float init_acc = 0.1f;     // AdaGrad: what a new accumulator is filled with
   int64_t t = 0;
-  std::vector<float*> m, v;
+  std::vector<float*> m, v;  // per parameter: Adam's moments (slots 0, 1); AdaGrad's accumulator is m (slot 0), v stays null
   float* part = nullptr;
   size_t part_cap = 0;
   float* state = nullptr;    // [clip scale, global norm, step count t, bias-corrected rate]
@@ -742,6 +744,15 @@ rgcn_status decoder_allreduce(rgcn_ctx* c);      // sharded run: sum the per-ran
 rgcn_status optimizer_step(rgcn_ctx* c);
 rgcn_status optimizer_norm_partial(rgcn_ctx* c);
 rgcn_status optimizer_apply(rgcn_ctx* c);
+// the state behind rgcn_get/set_optimizer_slot and _step: slots of the configured algorithm (Adam 2, AdaGrad 1, else 0);
+// the device array of slot `slot` of parameter `param` and its element count (W_relation: RelationCount rows), created
+// with its initial value if no step has yet; the [clip scale, norm, step count, rate] array, created zeroed likewise
+int optimizer_slot_count(const rgcn_ctx* c);
+float optimizer_slot_initial(const rgcn_ctx* c);
+rgcn_status optimizer_slot(rgcn_ctx* c, int32_t param, int32_t slot, float** dev, int64_t* n);
+rgcn_status optimizer_state_array(rgcn_ctx* c, float** state);
+rgcn_status optimizer_fill(rgcn_ctx* c, float* dev, int64_t n, float value);
+void optimizer_release_state(rgcn_ctx* c);      // another algorithm was configured: no slots, no count, the settings stay
 // ---- neighborhood.hip: sample_edge_neighborhood on the device (parallel first-passage percolation)
 rgcn_status neighborhood_reserve(rgcn_ctx* c, const int32_t* triples_host, int64_t n);
 rgcn_status neighborhood_sample(rgcn_ctx* c, int64_t sample_size, uint64_t seed, int32_t* batch_out_dev,

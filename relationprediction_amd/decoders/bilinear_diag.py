@@ -78,8 +78,15 @@ class BilinearDiag(Model):
 
     # ---- fused device paths: what the training driver and the scorer use (the eager numpy methods above
     # keep the reference's call-by-call surface and serve as their small-size cross-check)
-    def configure_device_optimizer(self, learning_rate, beta1=0.9, beta2=0.999, epsilon=1e-8, max_grad_norm=0.0):
-        self.next_component.get_runtime().configure_optimizer(learning_rate, beta1, beta2, epsilon, max_grad_norm)
+    def configure_device_optimizer(self, learning_rate, beta1=0.9, beta2=0.999, epsilon=1e-8, max_grad_norm=0.0,
+                                   algorithm="Adam", initial_accumulator=0.1):
+        self.next_component.get_runtime().configure_optimizer(learning_rate, beta1, beta2, epsilon, max_grad_norm,
+                                                              algorithm=algorithm,
+                                                              initial_accumulator=initial_accumulator)
+
+    def device_optimizer_engine(self):
+        """the engine whose optimizer state Model.save_optimizer / load_optimizer read and write"""
+        return self.next_component.get_runtime().engine
 
     def device_train_step(self, graph_edges, x, y, seed):
         """loss + regularisation, all gradients, clip and Adam in one asynchronous device step (graph_edges None: a

@@ -113,6 +113,43 @@ class Model(object):
         for w, v in zip(weights, stored):
             w.assign(v)
 
+    # ---- the optimizer's state beside the weights: what continuing a run needs (the reference cannot: its Saver holds the
+    # weights alone).  A file of its own, so that the weight checkpoint's format stays what it is.
+    def save_optimizer(self, npz_path):
+        """`.npz` of the device optimizer's state: `algorithm`, `step`, and one array per parameter and slot under
+        "<position in the engine's parameter list, 4 digits>_<parameter name>_<slot>" (Adam: slots 0 = m, 1 = v; AdaGrad:
+        0 = the accumulator; GradientDescent: none)."""
+        engine = self.device_optimizer_engine()
+        state = engine.optimizer_state()
+        arrays = {"%04d_%s_%d" % (engine.param_names.index(name), name, slot): a
+                  for name, slots in state["slots"].items() for slot, a in enumerate(slots)}
+        parent = os.path.dirname(npz_path)
+        if parent:
+            os.makedirs(parent, exist_ok=True)
+        with open(npz_path, "wb") as f:        # (a file object: np.savez must not append ".npz" to "<name>.opt.npz")
+            np.savez(f, algorithm=np.array(state["algorithm"]), step=np.array(state["step"], dtype=np.int64), **arrays)
+
+    def load_optimizer(self, npz_path):
+        """Continue from a save_optimizer file.  The optimizer must be configured already, with the file's algorithm:
+        another one is a ValueError naming both."""
+        engine = self.device_optimizer_engine()
+        with np.load(npz_path) as z:
+            algorithm, step = str(z["algorithm"]), int(z["step"])
+            configured = engine.optimizer_algorithm()
+            if algorithm != configured:
+                raise ValueError("%s holds the state of %s, the configured Algorithm is %s"
+                                 % (npz_path, algorithm, configured))
+            slots = {}
+            for key in sorted(k for k in z.files if k not in ("algorithm", "step")):
+                name, slot = key.split("_", 1)[1].rsplit("_", 1)
+                slots.setdefault(name, {})[int(slot)] = z[key]
+        engine.set_optimizer_state({"algorithm": algorithm, "step": step,
+                                    "slots": {n: [s[i] for i in range(len(s))] for n, s in slots.items()}})
+        return step
+
+    def device_optimizer_engine(self):
+        return self.__delegate__('device_optimizer_engine')
+
     # ---- high-level scoring (model.py:46-81): encode the graph, then the decoder's predict_*
     def _feed_test(self, graph, triplets):
         variables = self.get_test_input_variables()

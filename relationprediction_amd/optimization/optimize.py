@@ -2,10 +2,11 @@
 tensorflow_backend/algorithms.py) on top of the fused device train step.
 
 The reference composes the loop from a stack of components, each wrapping the next: data flows down
-(`next_batch`, `process_data`), the loss flows back up (`postprocess`), and two of them (GradientClipping, Adam)
-rewrite the TF gradient / update ops.  The same components exist here with the same parameters and the same
-reporting / stopping behaviour; clipping and Adam become the configuration of the device optimizer
-(rgcn_optimizer_config) and `update_from_batch` is ONE asynchronous device call (rgcn_train_step_device).
+(`next_batch`, `process_data`), the loss flows back up (`postprocess`), and two of them (GradientClipping and the
+Algorithm: Adam, AdaGrad or GradientDescent) rewrite the TF gradient / update ops.  The same components exist here with
+the same parameters and the same reporting / stopping behaviour; clipping and the algorithm become the configuration of
+the device optimizer (rgcn_optimizer_config / _config_ex) and `update_from_batch` is ONE asynchronous device call
+(rgcn_train_step_device).
 
 One deliberate reordering: the host work of the NEXT batch (neighbourhood sampling, negative sampling) is
 done while the GPU runs the current step, and the loss is fetched afterwards; per iteration the reference's order
@@ -144,8 +145,41 @@ class Adam(IOptimizer):                        # tensorflow_backend/algorithms.p
         return self.learning_rate is not None
 
     def configure_device(self, cfg):
+        _claim_algorithm(cfg, 'Adam')
         cfg.update(learning_rate=float(self.learning_rate), beta1=float(self.historical_moment_weight),
                    beta2=float(self.historical_second_moment_weight), epsilon=float(self.epsilon))
+        IOptimizer.configure_device(self, cfg)
+
+
+def _claim_algorithm(cfg, name):
+    """an Algorithm component puts its name into the device configuration; the device runs one"""
+    if 'algorithm' in cfg:
+        raise ValueError("two Algorithm components in one optimizer stack: %s and %s" % (name, cfg['algorithm']))
+    cfg['algorithm'] = name
+
+
+class GradientDescent(IOptimizer):             # tensorflow_backend/algorithms.py:5-16 (tf.train.GradientDescentOptimizer)
+    learning_rate = None
+
+    def valid(self):
+        return self.learning_rate is not None
+
+    def configure_device(self, cfg):
+        _claim_algorithm(cfg, 'GradientDescent')
+        cfg.update(learning_rate=float(self.learning_rate))
+        IOptimizer.configure_device(self, cfg)
+
+
+class AdaGrad(IOptimizer):                     # tensorflow_backend/algorithms.py:44-55 (tf.train.AdagradOptimizer)
+    learning_rate = None
+    initial_accumulator_value = 0.1            # tf.train.AdagradOptimizer's default, under TensorFlow's own name
+
+    def valid(self):
+        return self.learning_rate is not None
+
+    def configure_device(self, cfg):
+        _claim_algorithm(cfg, 'AdaGrad')
+        cfg.update(learning_rate=float(self.learning_rate), initial_accumulator=float(self.initial_accumulator_value))
         IOptimizer.configure_device(self, cfg)
 
 
@@ -247,7 +281,8 @@ class EarlyStopper(PostStepHook):              # shared/algorithms.py:118-159
 
 
 COMPONENTS = {c.__name__: c for c in (IterationCounter, Minibatches, SampleTransformer, GradientClipping, Adam,
-                                      AdditionalOp, ModelSaver, TrainLossReporter, EarlyStopper)}
+                                      GradientDescent, AdaGrad, AdditionalOp, ModelSaver, TrainLossReporter,
+                                      EarlyStopper)}
 
 
 def build_stack(parameters):
@@ -257,7 +292,8 @@ def build_stack(parameters):
     stack = BaseOptimizer()
     for name, params in parameters:
         if name not in COMPONENTS:
-            raise NotImplementedError("optimizer component '%s' (only Adam is built as Algorithm.Name)" % name)
+            raise NotImplementedError("optimizer component '%s' (Adam, AdaGrad and GradientDescent are built as "
+                                      "Algorithm.Name; RmsProp belongs to the reference's Theano backend)" % name)
         stack = COMPONENTS[name](stack, params)
     if not stack.verify():
         raise ValueError("optimizer parameters do not describe a valid stack")
@@ -298,8 +334,13 @@ class HipOptimizer(object):
         stack.configure_device(cfg)
         if 'learning_rate' not in cfg:
             raise ValueError("the optimizer stack has no Algorithm")
-        model.configure_device_optimizer(cfg['learning_rate'], cfg['beta1'], cfg['beta2'], cfg['epsilon'],
-                                         cfg.get('max_grad_norm', 0.0))
+        if cfg['algorithm'] == 'Adam':
+            model.configure_device_optimizer(cfg['learning_rate'], cfg['beta1'], cfg['beta2'], cfg['epsilon'],
+                                             cfg.get('max_grad_norm', 0.0))
+        else:                                    # (beta1, beta2 and epsilon are Adam's: the defaults ride along unread)
+            extra = {'initial_accumulator': cfg['initial_accumulator']} if cfg['algorithm'] == 'AdaGrad' else {}
+            model.configure_device_optimizer(cfg['learning_rate'], 0.9, 0.999, 1e-8, cfg.get('max_grad_norm', 0.0),
+                                             algorithm=cfg['algorithm'], **extra)
 
     def update_from_batch(self, processed_batch, seed):
         """Enqueue one train step; processed_batch = (graph_edges, X, Y) as the transform function returns."""

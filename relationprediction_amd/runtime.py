@@ -251,8 +251,10 @@ class EncoderRuntime(object):
             return st
         return None
 
-    def configure_optimizer(self, learning_rate, beta1=0.9, beta2=0.999, epsilon=1e-8, max_grad_norm=0.0):
-        self.engine.optimizer_config(learning_rate, beta1, beta2, epsilon, max_grad_norm)
+    def configure_optimizer(self, learning_rate, beta1=0.9, beta2=0.999, epsilon=1e-8, max_grad_norm=0.0,
+                            algorithm="Adam", initial_accumulator=0.1):
+        self.engine.optimizer_config(learning_rate, beta1, beta2, epsilon, max_grad_norm, algorithm=algorithm,
+                                     initial_accumulator=initial_accumulator)
 
     def train_step(self, graph_edges, x, y, reg_param, seed):
         """One update_from_batch (optimize.py:81-88) on the device: graph prep, encoder forward, DistMult

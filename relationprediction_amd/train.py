@@ -10,8 +10,17 @@ iteration is one asynchronous device step (graph prep, R-GCN forward, DistMult l
 the host draws the next minibatch meanwhile (neighbourhood sampler in librgcn.so, O(log V) per pick); validation
 encodes the training graph once and ranks on the device.  `Name=embedding` (settings/distmult.exp, the DistMult baseline)
 has no graph: every iteration's positives are the whole training set, resident on the device, and the step is the
-decoder's loss and gradients, clip and Adam."""
+decoder's loss and gradients, clip and Adam.
+
+Continuing a run (not in the reference, whose checkpoints hold the weights alone): `--save-optimizer-state` writes
+`<ExperimentName>-<n>.opt.npz` -- the algorithm's name, its step count and its moments or accumulators -- beside every
+checkpoint `<ExperimentName>-<n>.npz`; `--resume <ExperimentName>-<n>.npz` loads the weights and, if it is there, that
+sibling (otherwise it says that the optimizer starts fresh), and numbers its own checkpoints from n + 1.  Only the model
+and the optimizer continue: whatever counts ITERATIONS -- MaxIterations, the early stopper's burn-in and last score,
+the loss reports -- starts over at 1, and the random streams are the new process's."""
 import argparse
+import os
+import re
 
 import numpy as np
 
@@ -125,6 +134,43 @@ def initialize_model(model, train_triplets):
     model.initialize_train()
 
 
+def optimizer_state_path(checkpoint):
+    """<ExperimentName>-<n>.npz -> <ExperimentName>-<n>.opt.npz, the optimizer's state beside a weight checkpoint"""
+    return (checkpoint[:-4] if checkpoint.endswith('.npz') else checkpoint) + '.opt.npz'
+
+
+def save_with_optimizer_state(model):
+    """Model.save, and the optimizer's state beside every checkpoint it writes (--save-optimizer-state)"""
+    def save(path):
+        n = model.save_iter
+        model.save(path)
+        model.save_optimizer(optimizer_state_path("%s-%d.npz" % (path, n)))
+    return save
+
+
+def resume_weights(model, checkpoint):
+    """--resume, first half (after initialize_model): the checkpoint's weights, and the checkpoint numbering continues
+    behind the <n> of <ExperimentName>-<n>.npz so that the run overwrites nothing it started from."""
+    model.load(checkpoint)
+    m = re.search(r'-(\d+)\.npz$', checkpoint)
+    if m is None:
+        print("resume: %s is not named <ExperimentName>-<n>.npz, checkpoints are numbered from %d"
+              % (checkpoint, model.save_iter))
+    else:
+        model.save_iter = int(m.group(1)) + 1
+
+
+def resume_optimizer(model, checkpoint):
+    """--resume, second half (after the optimizer is configured): the state beside the checkpoint, if there is one"""
+    path = optimizer_state_path(checkpoint)
+    if not os.path.exists(path):
+        print("resume: no %s, the optimizer starts fresh" % path)
+        return None
+    step = model.load_optimizer(path)
+    print("resume: optimizer state of %s, %d steps taken" % (path, step))
+    return step
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description="Train a model on a given dataset.")
     parser.add_argument("--settings", help="Filepath for settings file.", required=True)
@@ -141,6 +187,13 @@ def main(argv=None):
                              "sample_edge_neighborhood, built ahead by --batch-workers threads) instead of on the device")
     parser.add_argument("--batch-workers", type=int, default=8,
                         help="background threads that build minibatches ahead of the device (0: build in line)")
+    parser.add_argument("--save-optimizer-state", action="store_true",
+                        help="write <ExperimentName>-<n>.opt.npz (the optimizer's moments / accumulators and step count) "
+                             "beside every checkpoint <ExperimentName>-<n>.npz")
+    parser.add_argument("--resume", metavar="CHECKPOINT.npz", default=None,
+                        help="start from this checkpoint's weights and, if CHECKPOINT.opt.npz lies beside it, its "
+                             "optimizer state; new checkpoints are numbered behind it.  What counts iterations "
+                             "(MaxIterations, the burn-in, the reports) starts over")
     args = parser.parse_args(argv)
 
     settings = settings_reader.read(args.settings)
@@ -161,7 +214,7 @@ def main(argv=None):
         optimizer_settings.put('MaxIterations', args.max_iterations)
 
     opp = optimizer_parameter_parser.Parser(optimizer_settings)
-    opp.set_save_function(model.save)
+    opp.set_save_function(save_with_optimizer_state(model) if args.save_optimizer_state else model.save)
 
     scorer = evaluation.Scorer(evaluation_settings)
     scorer.register_data(train_triplets)
@@ -191,9 +244,13 @@ def main(argv=None):
                                                          device_sampler=not args.host_sampler))
 
     initialize_model(model, train_triplets)
+    if args.resume is not None:
+        resume_weights(model, args.resume)
     print(model.get_train_input_variables())
 
     optimizer = build_hip(model, opp.get_parametrization(), batch_workers=args.batch_workers)
+    if args.resume is not None:
+        resume_optimizer(model, args.resume)
     iterations = optimizer.fit(train_triplets, validation_data=valid_triplets)
     return model, iterations
 

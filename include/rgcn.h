@@ -77,8 +77,9 @@ enum { RGCN_KIND_BLOCK = 0, RGCN_KIND_BASIS = 1, RGCN_KIND_BASIS_TDIAG = 2, RGCN
  *   - RGCN_ERR_UNSUPPORTED, the message naming the kind: rgcn_set_graph*, rgcn_prefetch_graph*, rgcn_step_device,
  *     rgcn_train_step_minibatch_device, rgcn_neighborhood_reserve, the phase API (rgcn_forward_begin ... rgcn_backward_end),
  *     rgcn_set_relation_owner, rgcn_capture_begin; rgcn_read_buffer knows RGCN_BUF_RANK_ENERGIES,
- *     RGCN_BUF_RANK_MIXED_SCORES and RGCN_BUF_RELATION_ENERGIES only (RGCN_ERR_STATE);
- *   - unchanged: rgcn_decoder_*, rgcn_negative_sample_device, rgcn_optimizer_*, rgcn_rank_device, rgcn_rank_mixed_device,
+ *     RGCN_BUF_RANK_MIXED_SCORES, RGCN_BUF_RELATION_ENERGIES and RGCN_BUF_NEGATIVE_UNRESOLVED only (RGCN_ERR_STATE);
+ *   - unchanged: rgcn_decoder_*, rgcn_negative_sample_device, rgcn_known_positives_reserve,
+ *     rgcn_negative_sample_exclusive_device, rgcn_optimizer_*, rgcn_rank_device, rgcn_rank_mixed_device,
  *     rgcn_topk_device, rgcn_score_queries_device, rgcn_topk_mixed_device, rgcn_rank_relation_device,
  *     rgcn_topk_relation_device, rgcn_score_relation_queries_device, parameters, device memory, timer and profile. */
 /* RGCN_KIND_BASIS_TDIAG = Encoder.DiagonalCoefficients=Yes -> BasisGcnTimesDiag
@@ -194,9 +195,13 @@ enum {
                                    rgcn_score_relation_queries_device scored (what the counts and the selection are integer
                                    work on).  RGCN_ERR_STATE before the first such call, and again after a growing
                                    rgcn_rank_reserve until the next one */
-  RGCN_BUF_OUT_DH = 19          /* float [V,d], contexts with an output transform (rgcn_config_ext::code_dim > 0): dL/dH_L of
+  RGCN_BUF_OUT_DH = 19,         /* float [V,d], contexts with an output transform (rgcn_config_ext::code_dim > 0): dL/dH_L of
                                    the last backward pass = dcodes . W_out^T, what the layer stack received as its dcodes.
                                    RGCN_ERR_STATE on every other context and before the first backward pass */
+  RGCN_BUF_NEGATIVE_UNRESOLVED = 20 /* int64 [1]: negative rows, since the last rgcn_known_positives_reserve, for which EVERY
+                                   entity was a known positive and which therefore kept their first draw (exclusive
+                                   sampler, stand-alone and fused; replayed hipGraphs count too).  Every kind,
+                                   RGCN_KIND_EMBEDDING included; RGCN_ERR_STATE without an index */
 };
 
 /*
@@ -409,6 +414,51 @@ rgcn_status rgcn_sample_neighborhood_device(rgcn_ctx* ctx, int64_t sample_size, 
 rgcn_status rgcn_negative_sample_device(rgcn_ctx* ctx, const int32_t* batch_dev, int64_t n, int32_t rate, uint64_t seed,
                                         int32_t* x_out_dev, float* y_out_dev);
 
+/* NegativeSampler.transform_exclusive (code/common/auxilliaries.py:35-73) on the device: the corruptions above, redrawn
+ * while they are known positives.
+ *
+ * rgcn_known_positives_reserve hands over the set K of known positives once (the reference registers the training
+ * triples: set_known_positives, code/train.py), int32 [num_triples,3] rows (s, r, o) in host memory:
+ *   - ids are checked on the host: an s or o outside [0, EntityCount) or an r outside [0, RelationCount) is
+ *     RGCN_ERR_INVALID, and an index reserved earlier stays in place and keeps answering;
+ *   - duplicates collapse.  The index is the sorted array of the unique packed keys (r V + s) V + o, built on the host,
+ *     deterministically, and copied to device memory the context owns; a lookup is a branch-free binary search;
+ *   - RelationCount x EntityCount^2 >= 2^63, or num_triples >= 2^31 (the bound of the key count, checked before
+ *     duplicates collapse): RGCN_ERR_UNSUPPORTED;
+ *   - num_triples == 0 releases the index and switches rgcn_set_exclusive_negatives off; a new K replaces the old one,
+ *     keeps the mode and restarts RGCN_BUF_NEGATIVE_UNRESOLVED at 0;
+ *   - RGCN_ERR_STATE between rgcn_capture_begin and rgcn_capture_end (it reads host memory and synchronises); a graph
+ *     captured with one index must not be launched after that index was replaced or released;
+ *   - every kind, RGCN_KIND_EMBEDDING included, and sharded contexts: the index is replicated, there is no collective,
+ *     every rank draws the same rows.
+ *
+ * rgcn_negative_sample_exclusive_device: arguments, layout and labels of rgcn_negative_sample_device.  For negative row
+ * i >= n let j = i - n, (s, r, o) = batch[i mod n] and T = RGCN_NEG_MAX_DRAWS; all draws are 24-bit counter draws
+ * bits(tag, index) of `seed`:
+ *   - the coin is the plain sampler's, bits(0x6e65, 2 j) & 1 (1: the object is replaced), and is never redrawn (the
+ *     reference redraws only the value);
+ *   - attempt 0 is the plain sampler's draw bit for bit: u = bits(0x6e66, 2 j) << 24 | bits(0x6e67, 2 j + 1), candidate
+ *     (u V) >> 48;
+ *   - a candidate e is KNOWN iff (s, r, e) (object side) or (e, r, o) (subject side) is in K; a known candidate is
+ *     redrawn: attempt t = 1 .. T - 1 draws u from bits(0x6e68, 2 (j T + t)) << 24 | bits(0x6e69, 2 (j T + t) + 1);
+ *   - if all T candidates are known the row takes the first entity that is not, scanning upward cyclically from the last
+ *     candidate (at most V lookups; probability p^T for a pair with known fraction p);
+ *   - if every entity is known the row keeps attempt 0's candidate and RGCN_BUF_NEGATIVE_UNRESOLVED grows by one;
+ *   - a batch row with an id out of range is corrupted as the plain sampler corrupts it, without a lookup; nothing is read
+ *     out of bounds and the decoder rejects the row when it consumes x_out.
+ * The result is a function of (K, batch, seed) alone; it differs from rgcn_negative_sample_device's for the same seed only
+ * in rows whose plain draw is known, and there only in the corrupted column; no negative row is in K unless the counter
+ * counted it.  Asynchronous, capturable (replay k draws with seed + k, as the plain call).  RGCN_ERR_STATE without an index.
+ *
+ * rgcn_set_exclusive_negatives(ctx, 1): the negative sampling inside rgcn_train_step_minibatch_device is the exclusive one,
+ * with that call's negative_seed.  RGCN_ERR_STATE without an index and during a capture.  Default 0: every call produces
+ * the bytes it produced before these entry points existed. */
+#define RGCN_NEG_MAX_DRAWS 32
+rgcn_status rgcn_known_positives_reserve(rgcn_ctx* ctx, const int32_t* triples_host, int64_t num_triples);
+rgcn_status rgcn_negative_sample_exclusive_device(rgcn_ctx* ctx, const int32_t* batch_dev, int64_t n, int32_t rate,
+                                                  uint64_t seed, int32_t* x_out_dev, float* y_out_dev);
+rgcn_status rgcn_set_exclusive_negatives(rgcn_ctx* ctx, int32_t on);
+
 /* ---- evaluation: raw and filtered link-prediction ranks -------------------------------
  * Replaces Model.score_all_subjects / score_all_objects + Scorer.evaluate_mrr + MrrScore.append_line
  * (code/model.py:59-81, code/decoders/bilinear_diag.py:51-61, code/common/evaluation.py:148-153,349-389).
@@ -615,7 +665,7 @@ rgcn_status rgcn_train_step_device(rgcn_ctx* ctx, const int32_t* triples_dev, in
 /* The reference's t_func after the neighbourhood sampling + update_from_batch (code/train.py:227-245,
  * optimize.py:81-88) in ONE asynchronous call on a graph batch that is resident in HBM: edge dropout (exact `keep`
  * of the n batch edges -> message graph, as rgcn_set_graph_dropout_device with edge_seed), negative sampling
- * (rgcn_negative_sample_device on ALL n batch edges -> x_scratch_dev int32 [n*(rate+1),3], y_scratch_dev float
+ * (rgcn_negative_sample_device -- under rgcn_set_exclusive_negatives its exclusive form -- on ALL n batch edges -> x_scratch_dev int32 [n*(rate+1),3], y_scratch_dev float
  * [n*(rate+1)]), then the train step of rgcn_train_step_device.  Only the n batch triples cross PCIe per step. */
 rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* ctx, const int32_t* batch_dev, int64_t num_edges, int64_t keep,
                                              uint64_t edge_seed, int32_t negative_rate, uint64_t negative_seed,

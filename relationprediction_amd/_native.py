@@ -29,7 +29,7 @@ BUF_PDIAG_AGG = 16           # basis_pdiag contexts: [V, d], the diagonal aggreg
 BUF_RANK_MIXED_SCORES = 17   # [reserved queries, V], the mixed scores the last topk_mixed selected from
 BUF_RELATION_ENERGIES = 18   # [reserved queries, R], the energies of the chunk a relation query scored last
 BUF_OUT_DH = 19              # contexts with an output transform: [V, d], dL/dH_L of the last backward pass
-
+BUF_NEGATIVE_UNRESOLVED = 20 # int64 [1]: negative rows every entity was a known positive for, since the reserve
 KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS, "basis_tdiag": KIND_BASIS_TDIAG,
          "basis_pdiag": KIND_BASIS_PDIAG, "embedding": KIND_EMBEDDING}
 NORMS = {"intended": NORM_INTENDED, "tf_as_executed": NORM_TF_AS_EXECUTED, "none": NORM_NONE, "local": NORM_LOCAL}
@@ -123,6 +123,9 @@ _SIGS = {
     "rgcn_graph_launch": (C.c_int32, [_P, C.c_int32]),
     "rgcn_graph_destroy": (C.c_int32, [_P, C.c_int32]),
     "rgcn_negative_sample_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, _P, _P]),
+    "rgcn_known_positives_reserve": (C.c_int32, [_P, _P, C.c_int64]),
+    "rgcn_negative_sample_exclusive_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, _P, _P]),
+    "rgcn_set_exclusive_negatives": (C.c_int32, [_P, C.c_int32]),
     "rgcn_rank_reserve": (C.c_int32, [_P, C.c_int64]),
     "rgcn_rank_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
     "rgcn_rank_energies_device": (_P, [_P]),
@@ -597,10 +600,27 @@ class Engine:
         self._check(self.lib.rgcn_sample_neighborhood_device(self.ctx, int(sample_size), C.c_uint64(int(seed)),
                                                              batch_dev.ptr, 1 if on_prefetch_stream else 0))
 
-    def negative_sample_device(self, batch_dev, n, rate, seed, x_dev, y_dev):
-        """X [n*(rate+1),3] and Y [n*(rate+1)] from the batch of n triples, all on the device."""
-        self._check(self.lib.rgcn_negative_sample_device(self.ctx, batch_dev.ptr, int(n), int(rate), C.c_uint64(int(seed)),
-                                                         x_dev.ptr, y_dev.ptr))
+    def negative_sample_device(self, batch_dev, n, rate, seed, x_dev, y_dev, exclusive=False):
+        """X [n*(rate+1),3] and Y [n*(rate+1)] from the batch of n triples, all on the device.  exclusive: corruptions
+        that are known positives (known_positives_reserve) are redrawn (rgcn_negative_sample_exclusive_device)."""
+        fn = self.lib.rgcn_negative_sample_exclusive_device if exclusive else self.lib.rgcn_negative_sample_device
+        self._check(fn(self.ctx, batch_dev.ptr, int(n), int(rate), C.c_uint64(int(seed)), x_dev.ptr, y_dev.ptr))
+
+    def known_positives_reserve(self, triples):
+        """the set of known positives to the device, once (NegativeSampler.set_known_positives); an empty set releases
+        the index and switches the exclusive mode off"""
+        t = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
+        self._check(self.lib.rgcn_known_positives_reserve(self.ctx, _ptr(t) if len(t) else None, len(t)))
+
+    def set_exclusive_negatives(self, on):
+        """the negative sampling inside train_step_minibatch_device: the exclusive one (True) or the plain one"""
+        self._check(self.lib.rgcn_set_exclusive_negatives(self.ctx, 1 if on else 0))
+
+    def negative_unresolved(self):
+        """negative rows, since the reserve, for which every entity was a known positive (they kept their first draw)"""
+        out = np.zeros(1, dtype=np.int64)
+        self._check(self.lib.rgcn_read_buffer(self.ctx, BUF_NEGATIVE_UNRESOLVED, _ptr(out), out.nbytes))
+        return int(out[0])
 
     def rank_reserve(self, max_queries):
         self._check(self.lib.rgcn_rank_reserve(self.ctx, int(max_queries)))

@@ -17,6 +17,7 @@
 // forward pass runs (rgcn_train_step_device).
 #include <algorithm>
 
+#include "known_positives_index.h"
 #include "rgcn_internal.h"
 #include "row_walk.h"
 
@@ -171,6 +172,30 @@ __global__ void k_negative_sample(const int32_t* __restrict__ batch, int n, int 
     const uint64_t u = ((uint64_t)a << 24) | c;                        // 48 random bits
     const int32_t ent = (int32_t)((u * (uint64_t)num_entities) >> 48); // uniform in [0, num_entities)
     if (coin & 1u) o = ent; else s = ent;
+  }
+  X[3 * i] = s; X[3 * i + 1] = r; X[3 * i + 2] = o;
+  Y[i] = i < n ? 1.0f : 0.0f;
+}
+
+// NegativeSampler.transform_exclusive (code/common/auxilliaries.py:35-73): the same layout, labels, coin and first draw;
+// a corruption that is a known positive is redrawn (negative_exclusive.h holds the decision, shared with the host).  One
+// thread per row; a search of the sorted key array is 19 dependent loads at FB15k-237, from L2, and that chain is the
+// kernel's length (profiles/r19_exclusive_negatives_time.md).  Rows whose first draw is free -- nearly all -- make one
+// search; the rare scan is a loop of this thread alone.
+__global__ void k_negative_sample_exclusive(const int32_t* __restrict__ batch, int n, int rate, KnownIndex known,
+                                            uint64_t seed, const uint64_t* __restrict__ seed_offset,
+                                            int32_t* __restrict__ X, float* __restrict__ Y,
+                                            unsigned long long* __restrict__ unresolved) {
+  if (seed_offset) seed += *seed_offset;      // as k_negative_sample: replay k draws with (captured seed + k)
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t total = (int64_t)n * (rate + 1);
+  if (i >= total) return;
+  const int b = (int)(i % n);
+  int s = batch[3 * b], r = batch[3 * b + 1], o = batch[3 * b + 2];
+  if (i >= n) {
+    const NegativeChoice ch = negative_exclusive_choice(known, seed, (uint64_t)(i - n), s, r, o);
+    if (ch.object_side) o = ch.entity; else s = ch.entity;
+    if (ch.unresolved) atomicAdd(unresolved, 1ull);
   }
   X[3 * i] = s; X[3 * i + 1] = r; X[3 * i + 2] = o;
   Y[i] = i < n ? 1.0f : 0.0f;
@@ -804,6 +829,49 @@ rgcn_status negative_sample(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, in
   c->dec.tiled_X = X;
   c->dec.tiled_period = n;
   c->dec.tiled_N = total;
+  return RGCN_OK;
+}
+
+rgcn_status negative_sample_exclusive(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int rate, uint64_t seed,
+                                      int32_t* X, float* Y) {
+  const KnownPositives& k = c->known;
+  if (k.count <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_known_positives_reserve first");
+  const int64_t total = n * (rate + 1);
+  if (total <= 0) return RGCN_OK;
+  // (the searches' bytes are not in the figure: 8 per probe, from L2)
+  ProfScope ps(c, "negative_sample_exclusive", 12.0 * n + 16.0 * total, 0);
+  const KnownIndex index{k.keys, k.count, c->V, c->R};
+  hipLaunchKernelGGL(k_negative_sample_exclusive, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
+                     batch_dev, (int)n, rate, index, seed, c->capturing ? c->replay_counter : nullptr, X, Y,
+                     k.unresolved);
+  RGCN_HIP(c, hipGetLastError());
+  c->dec.tiled_X = X;
+  c->dec.tiled_period = n;
+  c->dec.tiled_N = total;
+  return RGCN_OK;
+}
+
+void known_positives_free(rgcn_ctx* c) {
+  c->known.pool.release();
+  c->known = KnownPositives();
+}
+
+rgcn_status known_positives_reserve(rgcn_ctx* c, const int32_t* triples_host, int64_t n) {
+  if (n == 0) {
+    known_positives_free(c);
+    return RGCN_OK;
+  }
+  std::vector<uint64_t> keys;
+  const rgcn_status built = known_index_build(triples_host, n, c->V, c->R, &keys, &c->err);
+  if (built != RGCN_OK) return built;                 // (the earlier index, if any, still answers)
+  KnownPositives fresh;
+  RGCN_TRY(dmalloc(c, fresh.pool, &fresh.keys, keys.size(), false));
+  RGCN_TRY(dmalloc(c, fresh.pool, &fresh.unresolved, 1, true));
+  RGCN_HIP(c, hipMemcpyAsync(fresh.keys, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+  RGCN_HIP(c, hipStreamSynchronize(c->stream));       // `keys` is a local; the counter's memset is ahead of the copy
+  fresh.count = (int64_t)keys.size();
+  fresh.exclusive = c->known.exclusive;               // a new K under a mode that is on keeps it on
+  c->known = std::move(fresh);
   return RGCN_OK;
 }
 

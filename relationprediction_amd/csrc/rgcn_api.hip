@@ -316,6 +316,7 @@ static void free_all(rgcn_ctx* c) {
   graph_free(c);
   decoder_free(c);
   neighborhood_free(c);
+  known_positives_free(c);
   optimizer_free(c);
   rank_free(c);
   c->pool.release();
@@ -1037,6 +1038,32 @@ rgcn_status rgcn_negative_sample_device(rgcn_ctx* c, const int32_t* batch_dev, i
   return negative_sample(c, batch_dev, n, rate, seed, x_out_dev, y_out_dev);
 }
 
+// ---- exclusive negative sampling: the index of known positives, the stand-alone call, the mode of the fused step
+rgcn_status rgcn_known_positives_reserve(rgcn_ctx* c, const int32_t* triples_host, int64_t n) {
+  RGCN_NEED(c);
+  if (n < 0 || (n > 0 && !triples_host)) RGCN_FAIL(c, RGCN_ERR_INVALID, "need the known positives (or num_triples = 0 to release them)");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
+  RGCN_TRY(sync_all(c));      // (a sampling kernel in flight may still be reading the index this call replaces)
+  return known_positives_reserve(c, triples_host, n);
+}
+
+rgcn_status rgcn_negative_sample_exclusive_device(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int32_t rate,
+                                                  uint64_t seed, int32_t* x_out_dev, float* y_out_dev) {
+  RGCN_NEED(c);
+  if (n < 0 || rate < 0 || rate > 1024 || (n > 0 && (!batch_dev || !x_out_dev || !y_out_dev)))
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
+  if (n * (int64_t)(rate + 1) > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "batch too large");
+  return negative_sample_exclusive(c, batch_dev, n, rate, seed, x_out_dev, y_out_dev);
+}
+
+rgcn_status rgcn_set_exclusive_negatives(rgcn_ctx* c, int32_t on) {
+  RGCN_NEED(c);
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
+  if (on && c->known.count <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_known_positives_reserve first");
+  c->known.exclusive = on != 0;
+  return RGCN_OK;
+}
+
 rgcn_status rgcn_rank_reserve(rgcn_ctx* c, int64_t max_queries) {
   RGCN_NEED(c);
   if (max_queries <= 0) RGCN_FAIL(c, RGCN_ERR_INVALID, "max_queries must be positive");
@@ -1444,7 +1471,10 @@ rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* c, const int32_t* batch_d
   // the message graph: adopted from the prefetch of this very (batch, keep, seed), or drawn and prepared in line
   RGCN_TRY(step_begin(c, batch_dev, n, false, keep, edge_seed));   // (the fork point is recorded below)
   // the decoder batch: all n batch edges as positives (the dropped ones included) + their corruptions
-  RGCN_TRY(negative_sample(c, batch_dev, n, negative_rate, negative_seed, x_scratch_dev, y_scratch_dev));
+  if (c->known.exclusive)
+    RGCN_TRY(negative_sample_exclusive(c, batch_dev, n, negative_rate, negative_seed, x_scratch_dev, y_scratch_dev));
+  else
+    RGCN_TRY(negative_sample(c, batch_dev, n, negative_rate, negative_seed, x_scratch_dev, y_scratch_dev));
   // the decoder's batch preparation forks from ev_step_begin onto a side stream: it must see the sampled batch
   RGCN_HIP(c, hipEventRecord(c->ev_step_begin, c->main_stream));
   return train_step_tail(c, x_scratch_dev, y_scratch_dev, N, dropout_seed, reg_param);
@@ -1677,9 +1707,12 @@ rgcn_status rgcn_backward_end(rgcn_ctx* c) { RGCN_NEED(c); return bwd_end(c); }
 static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* bytes) {
   const int64_t Vd = (int64_t)c->V * c->d * 4;
   if (c->embedding && which != RGCN_BUF_RANK_ENERGIES && which != RGCN_BUF_RANK_MIXED_SCORES &&
-      which != RGCN_BUF_RELATION_ENERGIES)
+      which != RGCN_BUF_RELATION_ENERGIES && which != RGCN_BUF_NEGATIVE_UNRESOLVED)
     RGCN_FAIL(c, RGCN_ERR_STATE, "an RGCN_KIND_EMBEDDING context has the ranking buffers only (no graph, no layer buffers)");
   switch (which) {
+    case RGCN_BUF_NEGATIVE_UNRESOLVED:
+      if (c->known.count <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "no known positives (rgcn_known_positives_reserve first)");
+      *p = c->known.unresolved; *bytes = 8; return RGCN_OK;
     case RGCN_BUF_EXCHANGE:
       if (!c->exch) RGCN_FAIL(c, RGCN_ERR_STATE, "no exchange buffer on a world == 1 context");
       *p = c->exch; *bytes = Vd; return RGCN_OK;

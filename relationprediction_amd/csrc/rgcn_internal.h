@@ -12,8 +12,10 @@
 #include <vector>
 
 #include "../../include/rgcn.h"
+#include "counter_rng.h"
 #include "dev_pool.h"
 #include "gemm_plan.h"
+#include "negative_exclusive.h"
 
 namespace rgcn {
 
@@ -61,14 +63,7 @@ void set_global_error(const std::string& s);
 // below since round 4: a 64-bit key per (seed, layer) from splitmix64 -- uniform over a launch -- and a 32-bit
 // two-multiply hash per element keyed at both rounds (9 VALU operations instead of ~40: the per-element 64-bit
 // multiplies were a third of the VALU work of the single-pass layer kernels); keep iff the top 24 bits < keep * 2^24.
-__host__ __device__ inline uint64_t splitmix64_mix(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__host__ __device__ inline uint32_t drop_bits(uint64_t seed, uint32_t layer, uint64_t idx) {
-  return (uint32_t)(splitmix64_mix(seed + 0x9E3779B97F4A7C15ull * (idx + ((uint64_t)layer << 44) + 1ull)) >> 40);
-}
+// (splitmix64_mix and drop_bits themselves: counter_rng.h, which a plain C++ compiler reads too)
 struct DropKey {
   uint32_t k0, k1;
 };
@@ -326,6 +321,15 @@ struct NeighborhoodBufs {
   int32_t ncomp = 0;
 };
 
+// index of known positives of the exclusive negative sampler (rgcn_known_positives_reserve; negative_exclusive.h)
+struct KnownPositives {
+  DevPool pool;                            // keys, unresolved
+  uint64_t* keys = nullptr;                // [count] sorted unique packed keys (r V + s) V + o
+  int64_t count = 0;                       // 0: no index
+  unsigned long long* unresolved = nullptr;  // rows every entity was known for, since the reserve (RGCN_BUF_NEGATIVE_UNRESOLVED)
+  bool exclusive = false;                  // rgcn_set_exclusive_negatives: the fused minibatch step draws exclusively
+};
+
 struct OptimizerState {
   DevPool pool;              // moments, state, shard_sq
   DevPool part_pool;         // `part` alone: it is the one buffer that grows
@@ -441,6 +445,7 @@ struct rgcn_ctx {
   float *w_rel = nullptr, *g_rel = nullptr;   // W_relation [EntityCount, dc] (decoder weight)
   rgcn::DecoderBufs dec;
   rgcn::NeighborhoodBufs nbr;
+  rgcn::KnownPositives known;
   rgcn::OptimizerState opt;
 
   std::vector<float*> H;                 // H[0..L], [V,d] each
@@ -733,6 +738,13 @@ rgcn_status highway_join(rgcn_ctx* c, float* out, const float* gz, const float* 
 // ---- decoder.hip / optimizer.hip
 rgcn_status negative_sample(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int rate, uint64_t seed, int32_t* X,
                             float* Y);
+// the same against the context's index of known positives (c->known.count > 0): negative_exclusive.h decides every row
+rgcn_status negative_sample_exclusive(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int rate, uint64_t seed,
+                                      int32_t* X, float* Y);
+// the index: built on the host from validated limits (known_positives_index.h), swapped in only when complete;
+// n == 0 releases it and switches the exclusive mode off
+rgcn_status known_positives_reserve(rgcn_ctx* c, const int32_t* triples_host, int64_t n);
+void known_positives_free(rgcn_ctx* c);
 rgcn_status decoder_reserve(rgcn_ctx* c, int64_t max_triples);
 void decoder_free(rgcn_ctx* c);
 // N_total > N: X_dev is one rank's slice of a batch of N_total triples (relation-sharded train step); 0: N

@@ -251,6 +251,9 @@ class Model(object):
     def device_loss(self):
         return self.__delegate__('device_loss')
 
+    def device_negative_unresolved(self):
+        return self.__delegate__('device_negative_unresolved')
+
     def device_ranks(self, *args):
         return self.__delegate__('device_ranks', *args)
 

@@ -303,10 +303,13 @@ def build_stack(parameters):
 class DeviceNegatives(object):
     """A processed batch whose decoder triples are still to be drawn — on the device, at step time — from
     `batch` (NegativeSampler.transform's distribution: rgcn_negative_sample_device).  graph_edges None: the model has no
-    graph (Name=embedding) and `batch`, the whole training set, stays resident on the device while the same array is fed."""
+    graph (Name=embedding) and `batch`, the whole training set, stays resident on the device while the same array is fed.
+    `known`: the known positives (ExclusiveNegativeSampling=Yes: the training triples, the same array every iteration) --
+    corruptions among them are redrawn (rgcn_negative_sample_exclusive_device); None: the plain sampler."""
 
-    def __init__(self, graph_edges, batch, rate):
+    def __init__(self, graph_edges, batch, rate, known=None):
         self.graph_edges, self.batch, self.rate = graph_edges, batch, int(rate)
+        self.known = known
 
 
 class DeviceMinibatch(object):
@@ -316,11 +319,14 @@ class DeviceMinibatch(object):
 
     With `sample = (train_triplets, sample_size, sampler_seed)` and `batch = None` the THIRD draw happens on the device
     too -- the neighbourhood edge sampler (train.py:161-198; rgcn_sample_neighborhood_device): nothing is built on the
-    host and nothing is uploaded, an iteration is three seeds."""
+    host and nothing is uploaded, an iteration is three seeds.
 
-    def __init__(self, batch, keep, edge_seed, rate, sample=None):
+    `known` as in DeviceNegatives: the step's corruptions avoid these triples (rgcn_set_exclusive_negatives)."""
+
+    def __init__(self, batch, keep, edge_seed, rate, sample=None, known=None):
         self.batch, self.keep, self.edge_seed, self.rate = batch, int(keep), int(edge_seed), int(rate)
         self.sample = sample
+        self.known = known
 
 
 class HipOptimizer(object):
@@ -348,8 +354,9 @@ class HipOptimizer(object):
             self.model.device_train_step_minibatch(processed_batch, seed)
             return
         if isinstance(processed_batch, DeviceNegatives):
+            known = () if processed_batch.known is None else (processed_batch.known,)
             self.model.device_train_step_negatives(processed_batch.graph_edges, processed_batch.batch,
-                                                   processed_batch.rate, seed)
+                                                   processed_batch.rate, seed, *known)
             return
         if len(processed_batch) == 2:             # a graph-less model's (X, Y), as the reference's t_func returns it
             processed_batch = (None,) + tuple(processed_batch)

@@ -144,6 +144,23 @@ class EncoderRuntime(object):
             self._dev[name] = buf
         return buf
 
+    def _exclusive(self, known):
+        """ExclusiveNegativeSampling: `known` (the training triples, the same array every iteration) moves to the device
+        once (rgcn_known_positives_reserve) and the fused minibatch step's mode follows it; None: the plain sampler.
+        Returns whether the stand-alone sampling call is to be the exclusive one."""
+        on = known is not None
+        if on and getattr(self, "_known", None) is not known:
+            self.engine.known_positives_reserve(known)
+            self._known = known
+        if on != getattr(self, "_exclusive_on", False):
+            self.engine.set_exclusive_negatives(on)
+            self._exclusive_on = on
+        return on
+
+    def negative_unresolved(self):
+        """negative rows every entity was a known positive for, since the known positives were reserved (0 without them)"""
+        return self.engine.negative_unresolved() if getattr(self, "_known", None) is not None else 0
+
     def stage(self, graph_edges, batch=None):
         """Feed the NEXT train step while the current one runs: its triples go to the inactive one of two device
         buffer pairs without the host waiting (pinned staging), the message graph on the prefetch stream where
@@ -237,6 +254,7 @@ class EncoderRuntime(object):
         else:
             bd = self._upload("mbatch", b)
         xd, yd = self._buffer("X", 12 * n), self._buffer("Y", 4 * n)
+        self._exclusive(getattr(mb, "known", None))
         self.engine.train_step_minibatch_device(bd, nb, mb.keep, mb.edge_seed, mb.rate, seed ^ 0x5bd1e995, xd, yd,
                                                 seed=seed, reg_param=reg_param)
         self._state = None
@@ -278,9 +296,10 @@ class EncoderRuntime(object):
         self._graph_version = None
         self.weights_version += 1
 
-    def train_step_device_negatives(self, graph_edges, batch, rate, reg_param, seed):
+    def train_step_device_negatives(self, graph_edges, batch, rate, reg_param, seed, known=None):
         """As train_step, with the decoder batch (positives + `rate` corruptions each) drawn on the device from
-        `batch` (rgcn_negative_sample_device): only the two triple lists cross the PCIe bus."""
+        `batch` (rgcn_negative_sample_device): only the two triple lists cross the PCIe bus.  known: the known positives
+        the corruptions avoid (rgcn_negative_sample_exclusive_device), None for the plain sampler."""
         g = np.ascontiguousarray(graph_edges, dtype=np.int32).reshape(-1, 3)
         b = np.ascontiguousarray(batch, dtype=np.int32).reshape(-1, 3)
         n = len(b) * (int(rate) + 1)
@@ -304,7 +323,7 @@ class EncoderRuntime(object):
                     buf.free()
                 self._dev[name] = _native.DeviceBuffer(self.engine, nbytes)
         xd, yd = self._dev["X"], self._dev["Y"]
-        self.engine.negative_sample_device(bd, len(b), rate, seed ^ 0x5bd1e995, xd, yd)
+        self.engine.negative_sample_device(bd, len(b), rate, seed ^ 0x5bd1e995, xd, yd, exclusive=self._exclusive(known))
         self.engine.train_step_device(gd, len(g), xd, yd, n, seed=seed, reg_param=reg_param)
         self._state = None
         self._graph_version = None
@@ -422,9 +441,10 @@ class EmbeddingRuntime(EncoderRuntime):
         self._state = None
         self.weights_version += 1
 
-    def train_step_device_negatives(self, graph_edges, batch, rate, reg_param, seed):
+    def train_step_device_negatives(self, graph_edges, batch, rate, reg_param, seed, known=None):
         """The positives are uploaded once and stay resident while the SAME array object is fed (the training set, every
-        iteration); the corruptions are drawn on the device.  A caller that rewrites the array in place feeds a new one."""
+        iteration); the corruptions are drawn on the device, avoiding `known` if given.  A caller that rewrites the array
+        in place feeds a new one."""
         if graph_edges is not None:
             raise ValueError("a graph-less encoder takes no graph_edges")
         nb = len(batch)
@@ -438,7 +458,8 @@ class EmbeddingRuntime(EncoderRuntime):
             self._upload("batch", np.ascontiguousarray(batch, dtype=np.int32).reshape(-1, 3))
             self._resident = batch
         xd, yd = self._buffer("X", 12 * n), self._buffer("Y", 4 * n)
-        self.engine.negative_sample_device(self._dev["batch"], nb, rate, seed ^ 0x5bd1e995, xd, yd)
+        self.engine.negative_sample_device(self._dev["batch"], nb, rate, seed ^ 0x5bd1e995, xd, yd,
+                                           exclusive=self._exclusive(known))
         self.engine.train_step_device(None, 0, xd, yd, n, seed=seed, reg_param=reg_param)
         self._state = None
         self.weights_version += 1

@@ -44,9 +44,22 @@ def load_dataset(dataset, metric='MRR'):
     return splits, io.read_dictionary(entities_path), io.read_dictionary(relations_path)
 
 
+def exclusive_negative_sampling(general_settings):
+    """[General] ExclusiveNegativeSampling=Yes|No (absent from the reference's settings files; default No): redraw every
+    corruption that is a training triple, NegativeSampler.transform_exclusive instead of .transform"""
+    value = general_settings['ExclusiveNegativeSampling'] if 'ExclusiveNegativeSampling' in general_settings else 'No'
+    if value not in ('Yes', 'No'):
+        raise ValueError("General.ExclusiveNegativeSampling must be Yes or No, not %r" % (value,))
+    return value == 'Yes'
+
+
 def make_transform(train_triplets, general_settings, encoder, device_negatives=False, device_dropout=False,
                    device_sampler=False):
     """The reference's t_func (train.py:201-247): minibatch -> (graph_split, X, Y).
+
+    ExclusiveNegativeSampling=Yes: the corruptions avoid the training triples -- on the host path through
+    ns.transform_exclusive, on the device paths through `known=` of the batch objects (the runtime reserves the training
+    triples on the device once).
 
     Every batch is a function of ONE seed drawn from numpy's global generator when the batch is requested, so
     batches can be built ahead of time by background threads (`t_func.seeded(data, seed)`, used by
@@ -55,6 +68,8 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
     import threading
     ns = auxilliaries.NegativeSampler(int(general_settings['NegativeSampleRate']), general_settings['EntityCount'])
     ns.set_known_positives(train_triplets)
+    exclusive = exclusive_negative_sampling(general_settings)
+    host_negatives = ns.transform_exclusive if exclusive else ns.transform
     # (a graph-less encoder never reaches the sampler: settings/distmult.exp carries a GraphBatchSize it does not use)
     use_sampler = 'GraphBatchSize' in general_settings and encoder.needs_graph()
     if use_sampler and int(general_settings['GraphBatchSize']) > len(train_triplets):
@@ -64,6 +79,7 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
                                                                     len(train_triplets)))
     local = threading.local()            # the native sampler keeps per-sample state: one per thread
     train_arr = np.ascontiguousarray(train_triplets, dtype=np.int32)     # (what the device sampler keeps resident)
+    known = train_arr if exclusive else None      # K is the training set alone, as the reference registers it
 
     def seeded(x, seed):
         rng = np.random.RandomState(seed)
@@ -73,15 +89,16 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
             # whole training set.  Device negatives: the array itself is handed on, so that the step finds it resident
             if device_negatives:
                 from .optimization.optimize import DeviceNegatives
-                return DeviceNegatives(None, arr, ns.negative_sample_rate)
-            return ns.transform(arr, rng)
+                return DeviceNegatives(None, arr, ns.negative_sample_rate, known=known)
+            return host_negatives(arr, rng)
         if use_sampler and device_sampler and device_dropout:
             # all three draws on the device: the iteration is three seeds, nothing is built on the host or uploaded
             from .optimization.optimize import DeviceMinibatch
             size = int(general_settings['GraphBatchSize'])
             split_size = int(float(general_settings['GraphSplitSize']) * size)
             sample = (train_arr, size, rng.randint(0, 2 ** 31 - 1))
-            return DeviceMinibatch(None, split_size, rng.randint(0, 2 ** 31 - 1), ns.negative_sample_rate, sample=sample)
+            return DeviceMinibatch(None, split_size, rng.randint(0, 2 ** 31 - 1), ns.negative_sample_rate, sample=sample,
+                                   known=known)
         if use_sampler:
             if not hasattr(local, 'sampler'):
                 local.sampler = _native.NeighborhoodSampler(train_triplets, int(general_settings['EntityCount']))
@@ -93,13 +110,14 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
         split_size = int(float(general_settings['GraphSplitSize']) * graph_batch.shape[0])
         if device_dropout:            # both draws (kept edges, corruptions) are made by the device step
             from .optimization.optimize import DeviceMinibatch
-            return DeviceMinibatch(graph_batch, split_size, rng.randint(0, 2 ** 31 - 1), ns.negative_sample_rate)
+            return DeviceMinibatch(graph_batch, split_size, rng.randint(0, 2 ** 31 - 1), ns.negative_sample_rate,
+                                   known=known)
         graph_split_ids = rng.choice(graph_batch_ids, size=split_size, replace=False)
         graph_split = train_triplets[graph_split_ids]
         if device_negatives:          # corruptions are drawn by the device step (optimize.DeviceNegatives)
             from .optimization.optimize import DeviceNegatives
-            return DeviceNegatives(graph_split, graph_batch, ns.negative_sample_rate)
-        t = ns.transform(graph_batch, rng)
+            return DeviceNegatives(graph_split, graph_batch, ns.negative_sample_rate, known=known)
+        t = host_negatives(graph_batch, rng)
         return (graph_split, t[0], t[1])
 
     def t_func(x):
@@ -107,6 +125,15 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
 
     t_func.seeded = seeded
     return t_func
+
+
+def report_unresolved_negatives(model):
+    """with each validation report: how many negative rows the exclusive device sampler had to leave as drawn because
+    every entity was a known positive for them -- printed only when there are any"""
+    count = model.device_negative_unresolved()
+    if count:
+        print("Exclusive negative sampling: %d rows so far had no entity that is not a known positive" % count)
+    return count
 
 
 def build_model(settings, train_triplets, entity_count, relation_count):
@@ -231,6 +258,7 @@ def main(argv=None):
         early_stopping = score_summary.results['Filtered'][lookup_string]
         score_summary = scorer.compute_scores(test_triplets, verbose=False).get_summary()
         score_summary.pretty_print()
+        report_unresolved_negatives(model)
         return early_stopping
 
     opp.set_early_stopping_score_function(score_validation_data)

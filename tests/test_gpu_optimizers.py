@@ -1,13 +1,16 @@
-"""Algorithm.Name = AdaGrad and GradientDescent on the GPU (csrc/optimizer.hip k_adagrad, k_sgd) and the optimizer's state
-through the C ABI (rgcn_get/set_optimizer_slot, _step): every update against the float64 mirror of
-tests/optimizer_reference.py fed with the DEVICE's gradients, pre-step weights and pre-step accumulators; the sharded phase
-API; state handed from one context to another; a captured step; the training driver with --save-optimizer-state / --resume.
+"""The three algorithms of Algorithm.Name on the GPU (csrc/optimizer.hip k_adam, k_adagrad, k_sgd behind k_sqnorm_part and
+k_clip_scale) and the optimizer's state through the C ABI (rgcn_get/set_optimizer_slot, _step): every update against the
+float64 mirror of tests/optimizer_reference.py fed with the DEVICE's gradients, pre-step weights and pre-step slots, within
+the bounds that module counts from the kernels, no element excused; the sharded phase API, rank by rank; state handed from
+one context to another; a captured step; the training driver with --save-optimizer-state / --resume.
 
-Shapes of the update cases, with 256 x 8 = 2048 elements per workgroup and 4 per lane and load:
+Shapes of the real-gradient cases, with 256 x 8 = 2048 elements per workgroup and 4 per lane and load:
   block  V 257, R 5, d 9, 3 blocks, L 2: W_emb 2313 = one full workgroup + a tail of 265 (66 quads and one element: the
          one-by-one path inside a vectorised tensor), W_self 81 and b_emb 9 (less than a workgroup, odd), W_f / W_b 135;
   basis  B 2, V 130, R 8, d 20, L 2: W_emb 2600 (a second workgroup), the [d, B, d] tensors in their device layout;
-  embedding  V 300, d 12: W_emb 3600, W_relation 3600 of which the first R rows (72 elements) are updated."""
+  embedding  V 300, d 12: W_emb 3600, W_relation 3600 of which the first R rows (72 elements) are updated.
+Shapes of the injected-gradient cases (an embedding engine hands backward()'s argument to the optimizer as dL/dW_emb, bit
+for bit, so a [V, d] tensor of any size gets any gradient): INJECTED below."""
 import os
 
 import numpy as np
@@ -108,69 +111,399 @@ class Run(object):
         self.close()
 
 
+# ------------------------------------------------------------------ one step held to the mirror
+ADAM_DEFAULTS = dict(beta1=ref.f32(0.9), beta2=ref.f32(0.999), eps=ref.f32(1e-8))
+
+
+def excess(err, bound):
+    """max err / bound; an error where nothing is allowed is infinite"""
+    return float((err / np.maximum(bound, 1e-300)).max()) if err.size else 0.0
+
+
+def read_slots(eng, names):
+    return {n: tuple(eng.get_optimizer_slot(n, s) for s in range(eng.optimizer_slot_count())) for n in names}
+
+
+def mirror_state(algorithm, slots):
+    if algorithm == "Adam":
+        return {n: (s[0], s[1]) for n, s in slots.items()}
+    return {n: s[0] for n, s in slots.items()} if algorithm == "AdaGrad" else None
+
+
+def hold_step(label, algorithm, names, cur, grads, pre, new, post, lr, max_norm, step_count=0, hyper=None, scale=None,
+              select=None, per_tensor_size=True, accumulator_rtol=None):
+    """Mirrors one step from the pre-step values and asserts the bounds of optimizer_reference on EVERY element of the
+    change and (post given) of the slots; prints max err / bound per tensor and quantity first.  select: {name: index}, the
+    elements of a tensor that are this context's to move; accumulator_rtol: AdaGrad's, where a test holds a tighter one than
+    optimizer_reference.accumulator_rtol.  Returns (mirrored change, mirrored state, {name: bound})."""
+    clipped = max_norm > 0
+    hyper = hyper or (ADAM_DEFAULTS if algorithm == "Adam" else {})
+    want, state = ref.step(algorithm, cur, grads, mirror_state(algorithm, pre) if pre is not None else None, names, lr,
+                           max_norm, step_count=step_count, scale=scale, **hyper)
+    bounds, largest, widest = {}, 0.0, 0.0
+    for n in names:
+        pick = (select or {}).get(n, Ellipsis)
+        old = cur[n].astype(np.float64)
+        got = new[n].astype(np.float64) - old
+        bounds[n] = ref.update_bound(old, state[n].U if algorithm == "Adam" else want[n], clipped)
+        ratios = [("change", excess(np.abs(got - want[n])[pick], bounds[n][pick]))]
+        zero = old[pick] == 0                      # there the bound is the update's alone: no rounding of w to hide behind
+        ratios.append(("change(w=0)", excess(np.abs(got - want[n])[pick][zero], bounds[n][pick][zero])))
+        if post is not None and algorithm == "Adam":
+            ratios.append(("m", excess(np.abs(post[n][0] - state[n].m)[pick], ref.adam_m_bound(state[n].A, clipped)[pick])))
+            ratios.append(("v", excess(np.abs(post[n][1] - state[n].v)[pick], ref.adam_v_bound(state[n].v, clipped)[pick])))
+        if post is not None and algorithm == "AdaGrad":
+            ratios.append(("accumulator", excess(np.abs(post[n][0] - state[n])[pick],
+                                                 (accumulator_rtol or ref.accumulator_rtol(clipped)) * np.abs(state[n])[pick])))
+        big, wide = float(np.abs(want[n][pick]).max()), float(bounds[n][pick].max())
+        print("HELD %s %s %s %-10s max|d_ref| %.3e  max bound %.3e  max err/bound %s"
+              % (algorithm, "clip" if clipped else "noclip", label, n, big, wide,
+                 "  ".join("%s %.3f" % r for r in ratios)))
+        if per_tensor_size:
+            assert big >= 100 * wide, (label, n, big, wide)
+        largest, widest = max(largest, big), max(widest, wide)
+        for what, ratio in ratios:
+            assert ratio <= 1.0, (label, n, what, ratio)
+    assert largest >= 100 * widest, (label, largest, widest)          # the comparison could fail: a change 100 bounds large
+    return want, state, bounds
+
+
+def worst_miss(got_change, wrong_change, bounds, names, select=None):
+    """by how many bounds a wrong mirror misses the device's change, at the element where it misses most"""
+    return max(excess(np.abs(got_change[n] - np.nan_to_num(wrong_change[n], nan=np.inf))[(select or {}).get(n, Ellipsis)],
+                      bounds[n][(select or {}).get(n, Ellipsis)]) for n in names)
+
+
 # ------------------------------------------------------------------ the update against the float64 mirror
 @pytest.mark.parametrize("max_norm", [0.0, 1.0], ids=["unclipped", "clip-1"])
-@pytest.mark.parametrize("algorithm", ["AdaGrad", "GradientDescent"])
+@pytest.mark.parametrize("algorithm", ["Adam", "AdaGrad", "GradientDescent"])
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_update_matches_the_float64_mirror(native, case, algorithm, max_norm):
-    """Three train steps.  After each: the device's gradients, weights and accumulators; the step mirrored in float64 from
-    those gradients and the PRE-step weights and accumulators; compared is the CHANGE new - old (an update is about 1e-4
-    of a weight: at a tolerance made for weights no update at all would pass), per element, within
+    """Three train steps.  After each: the device's gradients, weights and slots; the step mirrored in float64 from those
+    gradients and the PRE-step weights and slots; compared is the CHANGE new - old (an update is about 1e-4 of a weight: at
+    a tolerance made for weights no update at all would pass), per element, within
         2^-23 |w| + 8 x 2^-23 |d_ref|      (max_grad_norm 0: the rounding of w - u, and at most eight roundings in u)
-        2^-23 |w| + 2e-5 |d_ref|           (max_grad_norm 1: the project's allowance for the fp32 norm, as the Adam replay)
-    and the accumulators within 8 x 2^-23 relative.  Every comparison first shows that it could fail: the largest mirrored
-    change is at least 100 times the largest error allowed.  AdaGrad: the mirror started from accumulators 0.1 lower (an
-    initial accumulator of 0) misses the bound by more than 100 times.  What has no gradient does not change by a bit."""
-    c, lr, clipped = CASES[case], RATES[algorithm], max_norm > 0
+        2^-23 |w| + 13 x 2^-23 |d_ref|     (max_grad_norm 1: the clip scale's 5 x 2^-23 on top)
+    with Adam's U (the update before its two terms cancel) in place of |d_ref|; AdaGrad's accumulators within 8 x 2^-23
+    relative, clipped or not, Adam's m and v within optimizer_reference's bounds.  Every comparison first shows that
+    it could fail: the largest mirrored change is at least 100 times the largest error allowed.  AdaGrad: the mirror
+    started from accumulators 0.1 lower (an initial accumulator of 0) misses the bound by more than 100 times; Adam: so do
+    the three wrong Adams of optimizer_reference.ADAM_VARIANTS.  What has no gradient does not change by a bit."""
+    c, lr = CASES[case], ref.f32(RATES[algorithm])
     with Run(native, c, algorithm, max_norm) as run:
         eng = run.eng
         names = moved_names(eng)
         slots = eng.optimizer_slot_count()
-        assert slots == (1 if algorithm == "AdaGrad" else 0)
+        assert slots == {"Adam": 2, "AdaGrad": 1, "GradientDescent": 0}[algorithm]
         cur = eng.get_params()
-        acc = {n: eng.get_optimizer_slot(n, 0) for n in names} if slots else None
+        pre = read_slots(eng, names)
         if slots:
-            assert all((a == np.float32(0.1)).all() for a in acc.values())
+            initial = np.float32(0.1 if algorithm == "AdaGrad" else 0.0)
+            assert all((a == initial).all() for held in pre.values() for a in held)
         for step in range(3):
             run.step(seed=500 + step)
             assert np.isfinite(eng.loss())
             grads = eng.get_grads()
             new = eng.get_params()
-            new_acc = {n: eng.get_optimizer_slot(n, 0) for n in names} if slots else None
+            post = read_slots(eng, names)
             assert eng.optimizer_step_count() == step + 1
-            want, want_acc = ref.step(algorithm, cur, grads, acc, names, lr, max_norm)
-            if slots:
-                zero_start = {n: acc[n].astype(np.float64) - 0.1 for n in names}
+            want, _, bounds = hold_step("%s step %d" % (case, step + 1), algorithm, names, cur, grads, pre, new, post, lr,
+                                        max_norm, step_count=step, accumulator_rtol=ref.ACCUMULATOR_RTOL)
+            got = {n: new[n].astype(np.float64) - cur[n] for n in names}
+            if algorithm == "AdaGrad":
+                zero_start = {n: pre[n][0].astype(np.float64) - 0.1 for n in names}
                 with np.errstate(invalid="ignore", divide="ignore"):
                     unfilled, _ = ref.step(algorithm, cur, grads, zero_start, names, lr, max_norm)
-            worst_unfilled = 0.0
-            for n in names:
-                old = cur[n].astype(np.float64)
-                got = new[n].astype(np.float64) - old
-                bound = ref.update_bound(old, want[n], clipped)
-                largest = float(np.abs(want[n]).max())
-                print("%s %s step %d %-10s max|d_ref| %.3e  max bound %.3e  max err/bound %.3f"
-                      % (case, algorithm, step, n, largest, float(bound.max()),
-                         float((np.abs(got - want[n]) / np.maximum(bound, 1e-300)).max())))
-                assert largest >= 100 * float(bound.max()), (step, n, largest, float(bound.max()))
-                err = np.abs(got - want[n])
-                assert (err <= bound).all(), (step, n, float((err / np.maximum(bound, 1e-300)).max()))
-                if slots:
-                    a_ref = want_acc[n]
-                    assert (np.abs(new_acc[n] - a_ref) <= ref.ACCUMULATOR_RTOL * a_ref).all(), (step, n)
-                    miss = np.abs(got - np.nan_to_num(unfilled[n], nan=np.inf)) / np.maximum(bound, 1e-300)
-                    worst_unfilled = max(worst_unfilled, float(miss.max()))
-            if slots:
-                assert worst_unfilled > 100, (step, worst_unfilled)
+                assert worst_miss(got, unfilled, bounds, names) > 100, step
+            if algorithm == "Adam":
+                for variant in ref.ADAM_VARIANTS:
+                    wrong, _ = ref.step(algorithm, cur, grads, mirror_state(algorithm, pre), names, lr, max_norm,
+                                        step_count=step, variant=variant, **ADAM_DEFAULTS)
+                    assert worst_miss(got, wrong, bounds, names) > 100, (step, variant)
             for n in eng.param_names:
                 if n not in names:
                     assert np.array_equal(new[n], cur[n]), n                         # no gradient: not a bit
             R = c["R"]
             assert np.array_equal(new["W_relation"][R:], cur["W_relation"][R:])        # rows past RelationCount
             assert not np.array_equal(new["W_relation"][:R], cur["W_relation"][:R])
-            if slots:
-                assert (new_acc["W_relation"][R:] == np.float32(0.1)).all()
-            cur, acc = new, new_acc
+            for slot in post["W_relation"]:
+                assert (slot[R:] == initial).all()
+            cur, pre = new, post
+
+
+# ------------------------------------------------------------------ injected gradients at the kernels' boundaries
+# (V, d) of an embedding engine, R = 3: W_emb has n = V d elements; a workgroup takes 2048, a lane 4 per load
+INJECTED = [(3, 5),         # 15: less than one wave
+            (89, 23),       # 2047: the last quad short by one
+            (64, 32),       # 2048: exactly one workgroup
+            (241, 17),      # 4097 = 2 x 2048 + 1: a workgroup of one element
+            (82, 25),       # 2050 = 2048 + 2
+            (683, 9),       # 6147 = 3 x 2048 + 3
+            (8400, 500)]    # 4,200,000: 2051 + 1 block partials, the second trip of k_clip_scale's eight-at-a-time loop
+INJECTED_R = 3
+_inputs = {}
+
+
+def injected_inputs(n):
+    """optimizer_reference.injected_case(n, seed n), made once and shared read-only"""
+    if n not in _inputs:
+        w, grads = ref.injected_case(n, seed=n, steps=3 if n < 1000000 else 1)
+        for a in [w] + grads:
+            a.setflags(write=False)
+        _inputs[n] = (w, grads)
+    return _inputs[n]
+
+
+def heads(tensors, names):
+    """the elements the optimizer moves: of W_relation the first R rows"""
+    return {n: tensors[n][:INJECTED_R] if n == "W_relation" else tensors[n] for n in names}
+
+
+class Injected(object):
+    """An embedding engine [V, d] with an optimizer.  step(w, g): W_emb = w, a forward pass, the decoder's pass over a
+    50-triple batch (it leaves W_relation's first R rows a real gradient; decoder=False: none, the gradient is g alone),
+    backward(g) -- which makes dL/dW_emb = g -- and optimizer_step() alone; everything read back before and after."""
+    names = ["W_emb", "W_relation"]
+
+    def __init__(self, native, V, d, algorithm, max_norm, lr=None, **hyper):
+        self.V, self.d, self.algorithm, self.max_norm = V, d, algorithm, max_norm
+        self.lr = ref.f32(RATES[algorithm] if lr is None else lr)
+        self.hyper = {k: ref.f32(v) for k, v in hyper.items()} or None
+        rng = np.random.RandomState(1000 + V)
+        self.eng = native.Engine(V, INJECTED_R, d, 0, "embedding", 1)
+        self.bufs = []
+        try:
+            assert moved_names(self.eng) == self.names
+            self.eng.set_params({"W_emb": np.zeros((V, d), np.float32), "b_emb": (0.05 * rng.randn(d)).astype(np.float32),
+                                 "W_relation": rng.randn(V, d).astype(np.float32)})
+            X = np.stack([rng.randint(0, V, 50), rng.randint(0, INJECTED_R, 50), rng.randint(0, V, 50)], 1).astype(np.int32)
+            Y = (rng.rand(50) < 0.3).astype(np.float32)
+            self.eng.decoder_reserve(50)
+            self.eng.optimizer_config(lr=self.lr, max_grad_norm=max_norm, algorithm=algorithm, **(self.hyper or {}))
+            self.bufs = [self.eng.to_device(X), self.eng.to_device(Y)]
+        except Exception:
+            self.close()
+            raise
+
+    def step(self, w, g, seed=0, decoder=True):
+        eng, shape = self.eng, (self.V, self.d)
+        eng.set_param("W_emb", w.reshape(shape))
+        eng.forward(train=True, seed=seed)
+        if decoder:
+            eng.decoder_loss_backward_device(self.bufs[0], self.bufs[1], 50, 0.01)
+        eng.backward(g.reshape(shape))
+        self.grads, self.cur, self.pre, self.t0 = eng.get_grads(), eng.get_params(), read_slots(eng, self.names), \
+            eng.optimizer_step_count()
+        assert np.array_equal(self.grads["W_emb"], g.reshape(shape))                 # the gradient is the one handed in
+        assert not self.grads["W_relation"][INJECTED_R:].any() and self.grads["W_relation"][:INJECTED_R].any() == decoder
+        eng.optimizer_step()
+        self.new, self.post, self.t1 = eng.get_params(), read_slots(eng, self.names), eng.optimizer_step_count()
+        assert self.t1 == self.t0 + 1
+        self.got = {n: self.new[n][:len(self.head(self.cur)[n])].astype(np.float64) - self.head(self.cur)[n] for n in self.names}
+
+    def head(self, tensors):
+        return heads(tensors, self.names)
+
+    def head_slots(self, slots):
+        return {n: tuple(a[:INJECTED_R] if n == "W_relation" else a for a in slots[n]) for n in self.names}
+
+    def mirror(self, max_norm=None, **kw):
+        """ref.step from the values read before the last step; keywords: a wrong mirror's"""
+        return ref.step(self.algorithm, self.head(self.cur), self.head(self.grads),
+                        mirror_state(self.algorithm, self.head_slots(self.pre)), self.names, self.lr,
+                        self.max_norm if max_norm is None else max_norm, step_count=self.t0,
+                        **dict(self.hyper or (ADAM_DEFAULTS if self.algorithm == "Adam" else {}), **kw))
+
+    def hold(self, label):
+        """the last step against the mirror, every element; then what must not have moved by a bit"""
+        R, clipped, algorithm = INJECTED_R, self.max_norm > 0, self.algorithm
+        hyper = self.hyper or ADAM_DEFAULTS
+        scale = ref.clip_scale(self.head(self.grads), self.names, self.max_norm)
+        if algorithm == "Adam":                       # the inputs keep every non-zero intermediate a normal float32
+            for n in self.names:
+                g = self.head(self.grads)[n].astype(np.float64) * scale
+                small = (1.0 - hyper["beta2"]) * g[g != 0] ** 2
+                assert not small.size or small.min() >= 2.0 ** -126, (label, n, float(small.min()))
+        want, state, bounds = hold_step(label, algorithm, self.names, self.head(self.cur), self.head(self.grads),
+                                        self.head_slots(self.pre), self.head(self.new), self.head_slots(self.post), self.lr,
+                                        self.max_norm, step_count=self.t0, hyper=self.hyper, per_tensor_size=False)
+        for n in self.names:                           # a zero gradient on zero momentum: nothing moves
+            g, w0, w1 = (self.head(x)[n] for x in (self.grads, self.cur, self.new))
+            still = g == 0
+            if algorithm == "Adam":
+                m0, v0 = self.head_slots(self.pre)[n]
+                m1, v1 = self.head_slots(self.post)[n]
+                still = still & (m0 == 0)
+                assert not m1[still].any(), (label, n)
+                decayed = hyper["beta2"] * v0[still].astype(np.float64)
+                assert (np.abs(v1[still] - decayed) <= 2 * ref.U24 * decayed).all(), (label, n)
+            elif algorithm == "AdaGrad":
+                assert np.array_equal(self.head_slots(self.post)[n][0][still], self.head_slots(self.pre)[n][0][still]), (label, n)
+            assert still.any() or n != "W_emb" or g.size < 100
+            assert np.array_equal(w1[still], w0[still]), (label, n)
+        assert np.array_equal(self.new["W_relation"][R:], self.cur["W_relation"][R:]), label
+        for before, after in zip(self.pre["W_relation"], self.post["W_relation"]):
+            assert np.array_equal(after[R:], before[R:]), label
+        assert np.array_equal(self.new["b_emb"], self.cur["b_emb"]) and self.new["b_emb"].any(), label
+        return want, state, bounds, scale
+
+    def tells_wrong_adams(self, bounds, label, variants=ref.ADAM_VARIANTS):
+        for variant in variants:
+            wrong, _ = self.mirror(variant=variant)
+            assert worst_miss(self.got, wrong, bounds, self.names) > 100, (label, variant)
+
+    def close(self):
+        for b in self.bufs:
+            b.free()
+        self.bufs = []
+        self.eng.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+@pytest.mark.parametrize("max_norm", [0.0, 1.0], ids=["unclipped", "clip-1"])
+@pytest.mark.parametrize("algorithm", ["Adam", "AdaGrad", "GradientDescent"])
+@pytest.mark.parametrize("shape", INJECTED, ids=["%dx%d" % s for s in INJECTED])
+def test_injected_gradients_at_the_kernels_boundaries(native, shape, algorithm, max_norm):
+    """Three optimizer steps (one at 4.2 M elements) on gradients of optimizer_reference.injected_case: fifteen decades of
+    magnitude, exact zeros, a tenth where Adam's eps decides, a tenth whose m cancels, a step-2 gradient a thousand times
+    smaller (another clip scale); half of the weights exactly 0 before every step, where the bound is the update's alone.
+    After every step every element of the change, of m and v and of AdaGrad's accumulator is inside the bounds counted in
+    optimizer_reference, and the largest mirrored change is 100 times the largest bound.  Adam: the three wrong Adams miss
+    the bound by more than 100 times somewhere, and so does the unclipped mirror on a clipped step after the first.  A zero
+    gradient on zero momentum moves nothing by a bit (v decays to b2 v0 within 2 x 2^-24); nor do W_relation's rows past
+    R, their slots, or b_emb."""
+    V, d = shape
+    w, grads = injected_inputs(V * d)
+    with Injected(native, V, d, algorithm, max_norm) as run:
+        assert (w == 0).sum() == (V * d) // 2
+        clipped_later = 0
+        for step, g in enumerate(grads):
+            label = "%dx%d step %d" % (V, d, step + 1)
+            run.step(w, g, seed=step)
+            _, _, bounds, scale = run.hold(label)
+            if algorithm == "Adam":
+                run.tells_wrong_adams(bounds, label)
+                if max_norm > 0 and step >= 1 and scale < 0.99:     # (a norm below the threshold: the two mirrors are one)
+                    unclipped, _ = run.mirror(max_norm=0.0)
+                    assert worst_miss(run.got, unclipped, bounds, run.names) > 100, label
+                    clipped_later += 1
+        assert run.eng.optimizer_step_count() == len(grads)
+        if algorithm == "Adam" and max_norm > 0 and len(grads) == 3:
+            assert clipped_later >= (1 if V * d < 100 else 2)
+
+
+def preset_state(n, g, seed):
+    """m0 of the gradient's magnitude and the opposite sign, v0 log-uniform in [1e-30, 1e6]"""
+    rng = np.random.RandomState(seed)
+    return (-g).astype(np.float32), (10.0 ** rng.uniform(-30, 6, n)).astype(np.float32)
+
+
+def put_state(run, m0, v0):
+    shape = (run.V, run.d)
+    run.eng.set_optimizer_slot("W_emb", 0, m0.reshape(shape))
+    run.eng.set_optimizer_slot("W_emb", 1, v0.reshape(shape))
+    assert np.array_equal(run.eng.get_optimizer_slot("W_emb", 1), v0.reshape(shape))
+
+
+TWO_SHAPES = [(89, 23), (241, 17)]
+two_shapes = pytest.mark.parametrize("shape", TWO_SHAPES, ids=["%dx%d" % s for s in TWO_SHAPES])
+
+
+@pytest.mark.parametrize("max_norm", [0.0, 1.0], ids=["unclipped", "clip-1"])
+@two_shapes
+def test_adam_from_a_preset_state(native, shape, max_norm):
+    """one step from an m0 that opposes the gradient and a v0 spread over thirty-six decades"""
+    V, d = shape
+    w, grads = injected_inputs(V * d)
+    with Injected(native, V, d, "Adam", max_norm) as run:
+        put_state(run, *preset_state(V * d, grads[0], seed=V))
+        run.step(w, grads[0])
+        assert run.pre["W_emb"][0].any() and run.pre["W_emb"][1].all()
+        _, _, bounds, _ = run.hold("%dx%d preset" % shape)
+        run.tells_wrong_adams(bounds, "preset")
+
+
+@pytest.mark.parametrize("t0", [9, 999, 99999, 2 ** 24 - 2])
+@two_shapes
+def test_adam_at_a_set_step_count(native, shape, t0):
+    """rgcn_set_optimizer_step puts t0 in front of the step: the mirror's rate is that of t0 + 1, the count afterwards is
+    t0 + 1 -- 2^24 - 1 at the last value, the largest the device's float holds exactly -- and is accepted back.  Up to a
+    thousand steps a rate one step late or uncorrected misses by more than 100 bounds; from 1e5 steps on the correction is
+    1 to the last bit of a double and there is nothing left to tell."""
+    V, d = shape
+    w, grads = injected_inputs(V * d)
+    with Injected(native, V, d, "Adam", 1.0) as run:
+        run.eng.set_optimizer_step_count(t0)
+        run.step(w, grads[0])
+        assert run.t0 == t0 and run.t1 == t0 + 1
+        _, _, bounds, _ = run.hold("%dx%d t0 %d" % (V, d, t0))
+        if t0 < 1000:
+            run.tells_wrong_adams(bounds, t0)
+        else:
+            assert ref.adam_rate(run.lr, ADAM_DEFAULTS["beta1"], ADAM_DEFAULTS["beta2"], t0 + 1) == run.lr
+            run.tells_wrong_adams(bounds, t0, variants=("eps_under_root",))
+        run.eng.set_optimizer_step_count(run.eng.optimizer_step_count())
+        assert run.eng.optimizer_step_count() == t0 + 1
+
+
+@pytest.mark.parametrize("max_norm", [0.0, 1.0], ids=["unclipped", "clip-1"])
+@two_shapes
+def test_adam_with_other_hyper_parameters(native, shape, max_norm):
+    """beta1 0.5, beta2 0.9, eps 1e-3, lr 0.003, from a preset state (the betas weigh it; m0 is half the gradient's
+    magnitude: at the full one b1 m0 + (1 - b1) g would be 0 everywhere) at step count 4"""
+    V, d = shape
+    w, grads = injected_inputs(V * d)
+    with Injected(native, V, d, "Adam", max_norm, lr=0.003, beta1=0.5, beta2=0.9, eps=1e-3) as run:
+        m0, v0 = preset_state(V * d, grads[0], seed=V + 1)
+        put_state(run, np.float32(0.5) * m0, v0)
+        run.eng.set_optimizer_step_count(4)
+        run.step(w, grads[0])
+        _, _, bounds, _ = run.hold("%dx%d hyper" % shape)
+        run.tells_wrong_adams(bounds, "hyper")
+        defaults, _ = run.mirror(**ADAM_DEFAULTS)
+        assert worst_miss(run.got, defaults, bounds, run.names) > 100
+
+
+@pytest.mark.parametrize("algorithm", ["Adam", "GradientDescent"])
+@two_shapes
+def test_clip_threshold(native, shape, algorithm):
+    """A gradient whose only non-zero element, the tensor's last, equals max_grad_norm = 1 (no decoder pass: W_relation's
+    gradient is zero): the norm is exactly the threshold, the scale exactly 1, and weights and slots are bitwise those of
+    the same step without a clip.  The element doubled: the scale is 0.5, and the change matches the mirror at that scale.
+    The element's weight is 0, so GradientDescent shows the scale itself: d = -lr s g."""
+    V, d = shape
+    n = V * d
+    w = injected_inputs(n)[0].copy()
+    w[-1] = 0.0
+    seen = {}
+    for max_norm, value in ((1.0, 1.0), (0.0, 1.0), (1.0, 2.0)):
+        g = np.zeros(n, np.float32)
+        g[-1] = value
+        with Injected(native, V, d, algorithm, max_norm) as run:
+            run.step(w, g, decoder=False)
+            scale = ref.clip_scale(run.head(run.grads), run.names, max_norm)
+            assert scale == (0.5 if value == 2.0 else 1.0)
+            label = "%dx%d threshold norm %g max_norm %g" % (V, d, value, max_norm)
+            hold_step(label, algorithm, ["W_emb"], run.cur, run.grads, run.pre, run.new, run.post, run.lr, max_norm,
+                      hyper=run.hyper)
+            assert np.array_equal(run.new["W_relation"], run.cur["W_relation"])
+            moved = np.flatnonzero(run.new["W_emb"].ravel() != run.cur["W_emb"].ravel())
+            assert moved.tolist() == [n - 1]
+            if algorithm == "GradientDescent":
+                d_ref = -run.lr * scale * value
+                assert abs(float(run.new["W_emb"].ravel()[-1]) - d_ref) <= 13 * ref.EPS32 * abs(d_ref)
+            seen[(max_norm, value)] = (run.new, run.post)
+    on, off = seen[(1.0, 1.0)], seen[(0.0, 1.0)]
+    for name in on[0]:
+        assert np.array_equal(on[0][name], off[0][name]), name
+    for name in on[1]:
+        for a, b in zip(on[1][name], off[1][name]):
+            assert np.array_equal(a, b), name
 
 
 # ------------------------------------------------------------------ sharded: the phase API with the host as the collective
@@ -263,6 +596,105 @@ def test_sharded_steps_match_the_unsharded_run(native, algorithm):
             for b in t:
                 b.free()
         for e in [single] + engs:
+            e.close()
+
+
+@pytest.mark.parametrize("algorithm,steps", [("Adam", 1), ("AdaGrad", 1), ("GradientDescent", 3)])
+def test_sharded_steps_rank_by_rank_against_the_mirror(native, algorithm, steps):
+    """The world-2 loop of test_sharded_steps_match_the_unsharded_run, max_grad_norm 1, each rank held to the float64 mirror.
+    After optimizer_norm_partial a rank's BUF_NORM_EXCHANGE is the squared norm of ITS W_f* / W_b* gradients (k_sum_range
+    over k_sqnorm_part's partials) within 17 x 2^-24.  The mirror's global norm counts the replicated tensors once and
+    sums the sharded ones over the ranks; each rank's change, on the relations it owns and on every replicated tensor, is
+    inside the clipped bounds, and off-owner relations do not change by a bit.  The slots of a sharded context cannot be
+    read, so Adam and AdaGrad run the one step whose state is known (zeros, 0.1) and GradientDescent runs three."""
+    from relationprediction_amd.sharding import lpt_partition
+    V, R, d, nb, L, E, world = 90, 10, 9, 3, 2, 600, 2
+    kind, lr = "block", ref.f32(RATES[algorithm])
+    params, triples, _, _ = make_case(V, R, d, L, kind, nb, E, seed=21)
+    X, Y = decoder_batch(np.random.RandomState(2), triples[:200], V)
+    owner = lpt_partition(np.bincount(triples[:, 1], minlength=R), world)
+    engs = [native.Engine(V, R, d, L, kind, nb, max_edges=E, rank=r, world=world) for r in range(world)]
+    held = []
+
+    def exchange(which):
+        total = sum(e.read_buffer(which) for e in engs)
+        for e in engs:
+            e.write_buffer(which, total)
+
+    try:
+        for e in engs:
+            e.set_params(params)
+            e.decoder_reserve(len(X))
+            e.optimizer_config(lr=lr, max_grad_norm=1.0, algorithm=algorithm)
+            held.append((e.to_device(X), e.to_device(Y)))
+            e.set_relation_owner(owner)
+        names = moved_names(engs[0])
+        sharded = [n for n in names if n.startswith(("W_f", "W_b"))]
+        assert len(sharded) == 2 * L and all(params[n].shape[0] == R for n in sharded)
+        for step in range(steps):
+            for e in engs:
+                e.set_graph(triples)
+                e.forward_begin(train=True, seed=100 + step)
+            for l in range(1, L + 1):
+                for e in engs:
+                    e.forward_layer_partial(l)
+                exchange(native.BUF_EXCHANGE)
+                for e in engs:
+                    e.forward_layer_finish(l)
+            for e, (Xd, Yd) in zip(engs, held):
+                e.decoder_loss_backward_device(Xd, Yd, len(X), 0.01)
+                e.backward_begin()
+            for l in range(L, 0, -1):
+                for e in engs:
+                    e.backward_layer_partial(l)
+                exchange(native.BUF_EXCHANGE)
+                exchange(native.BUF_DSELF_EXCHANGE)
+                for e in engs:
+                    e.backward_layer_finish(l)
+            for e in engs:
+                e.backward_end()
+            grads = [e.get_grads() for e in engs]
+            cur = [e.get_params() for e in engs]
+            for e in engs:
+                e.optimizer_norm_partial()
+            shard_sq = []
+            for r, e in enumerate(engs):
+                for n in sharded:
+                    assert not grads[r][n][owner != r].any(), (r, n)          # a rank holds the gradient of what it owns
+                sq = sum(float((grads[r][n].astype(np.float64) ** 2).sum()) for n in sharded)
+                got = float(e.read_buffer(native.BUF_NORM_EXCHANGE)[0])
+                print("HELD %s clip sharded step %d rank %d shard norm^2 %.6e  err/bound %.3f"
+                      % (algorithm, step + 1, r, sq, abs(got - sq) / (ref.SHARD_NORM_RTOL * sq)))
+                assert sq > 0 and abs(got - sq) <= ref.SHARD_NORM_RTOL * sq, (r, got, sq)
+                shard_sq.append(sq)
+            exchange(native.BUF_NORM_EXCHANGE)
+            for e in engs:
+                e.optimizer_apply()
+            for r, e in enumerate(engs):
+                new = e.get_params()
+                mine = owner == r
+                assert mine.any() and not mine.all()
+                replicated_sq = sum(float((grads[r][n].astype(np.float64) ** 2).sum()) for n in names if n not in sharded)
+                scale = ref.scale_of_norm(float(np.sqrt(replicated_sq + sum(shard_sq))), 1.0)
+                pre = None
+                if algorithm != "GradientDescent":
+                    fill = np.float32(0.1 if algorithm == "AdaGrad" else 0.0)
+                    pre = {n: tuple(np.full(params[n].shape, fill, np.float32) for _ in range(2)) for n in names}
+                print("rank %d step %d clip scale %.6f" % (r, step + 1, scale))
+                assert step > 0 or scale < 0.9                                     # the first step's norm is above the threshold
+                hold_step("sharded step %d rank %d" % (step + 1, r), algorithm, names, cur[r], grads[r], pre, new, None, lr,
+                          1.0, step_count=step, scale=scale, select={n: mine for n in sharded}, per_tensor_size=False)
+                for n in sharded:
+                    assert np.array_equal(new[n][~mine], cur[r][n][~mine]), (r, n)
+                    assert not np.array_equal(new[n][mine], cur[r][n][mine]), (r, n)
+                for n in e.param_names:
+                    if n not in names:
+                        assert np.array_equal(new[n], cur[r][n]), (r, n)
+    finally:
+        for t in held:
+            for b in t:
+                b.free()
+        for e in engs:
             e.close()
 
 

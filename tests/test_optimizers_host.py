@@ -1,6 +1,7 @@
 """Algorithm.Name = AdaGrad and GradientDescent beside Adam, without a GPU: the optimizer stack and what it hands the model,
 the optimizer-state files of Model.save_optimizer / load_optimizer, train.py's --resume helpers, the float64 mirror the GPU
-tests measure the kernels by (tests/optimizer_reference.py) against values computed by hand, and the hyper-parameter check of
+tests measure the kernels by (tests/optimizer_reference.py) against values computed by hand, its error bounds against the
+kernels' arithmetic redone in numpy float32, and the hyper-parameter check of
 rgcn_optimizer_config_ex (csrc/optimizer_check.h) under AddressSanitizer and UndefinedBehaviorSanitizer."""
 import os
 import shutil
@@ -255,7 +256,140 @@ def test_mirror_norm_runs_over_all_named_tensors():
     assert ref.clip_scale(grads, ["a", "b"], 1.0) == pytest.approx(0.2) and ref.clip_scale(grads, ["a", "b"], 0.0) == 1.0
     b = ref.update_bound(np.array([2.0]), np.array([0.5]), clipped=False)
     assert b[0] == pytest.approx(2.0 ** -23 * 2 + 8 * 2.0 ** -23 * 0.5)
-    assert ref.update_bound(np.array([2.0]), np.array([0.5]), clipped=True)[0] == pytest.approx(2.0 ** -22 + 1e-5)
+    # clipped: the scale's own error, 5 x 2^-23 (sixteen roundings under a square root, one to float, one divide), on top
+    assert ref.SCALE_RTOL == 5 * 2.0 ** -23
+    b = ref.update_bound(np.array([2.0]), np.array([0.5]), clipped=True)
+    assert b[0] == pytest.approx(2.0 ** -22 + 13 * 2.0 ** -23 * 0.5, rel=1e-12)
+    assert ref.accumulator_rtol(False) == 8 * 2.0 ** -23 and ref.accumulator_rtol(True) == 28 * 2.0 ** -24
+    three, u = np.array([3.0]), 2.0 ** -24
+    assert ref.adam_m_bound(three, False)[0] == 12 * u and ref.adam_m_bound(three, True)[0] == 48 * u
+    assert ref.adam_v_bound(three, False)[0] == 12 * u and ref.adam_v_bound(three, True)[0] == 84 * u
+
+
+ZEROS = {"w": (np.zeros(1), np.zeros(1))}
+
+
+@pytest.mark.parametrize("clipped", [False, True], ids=["unclipped", "clip-1"])
+def test_mirror_adam_by_hand_with_the_defaults(clipped):
+    """one element, two steps, lr 0.01, b1 0.9, b2 0.999, eps 1e-8; gradients 2 and -1, or under max_norm 1 (a norm of 2 and
+    of 4: scales 1/2 and 1/4) twice those, which the clip turns into the same two"""
+    k = dict(lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, max_norm=1.0 if clipped else 0.0)
+    g1, g2 = ({"w": np.array([2.0])}, {"w": np.array([-4.0])}) if clipped else ({"w": np.array([1.0])}, {"w": np.array([-1.0])})
+    w = {"w": np.array([0.25])}
+    d, s = ref.step("Adam", w, g1, ZEROS, ["w"], step_count=0, **k)                 # g' = 1
+    s = s["w"]
+    np.testing.assert_allclose([s.m[0], s.A[0], s.v[0]], [0.1, 0.1, 0.001], rtol=1e-15)
+    rate1 = 0.01 * np.sqrt(0.001) / 0.1
+    np.testing.assert_allclose(d["w"], [-rate1 * 0.1 / (np.sqrt(0.001) + 1e-8)], rtol=1e-15)
+    np.testing.assert_allclose(d["w"], [-0.01 / (1 + 1e-8 / np.sqrt(0.001))], rtol=1e-14)     # lr, but for eps
+    np.testing.assert_allclose(s.U, -d["w"], rtol=1e-15)
+    d2, s2 = ref.step("Adam", w, g2, {"w": (s.m, s.v)}, ["w"], step_count=1, **k)       # g' = -1
+    s2 = s2["w"]
+    np.testing.assert_allclose([s2.m[0], s2.A[0], s2.v[0]], [-0.01, 0.19, 0.001999], rtol=1e-14)
+    rate2 = 0.01 * np.sqrt(1 - 0.998001) / 0.19
+    np.testing.assert_allclose(d2["w"], [rate2 * 0.01 / (np.sqrt(0.001999) + 1e-8)], rtol=1e-13)
+    np.testing.assert_allclose(s2.U, [rate2 * 0.19 / (np.sqrt(0.001999) + 1e-8)], rtol=1e-13)
+    assert ZEROS["w"][0][0] == 0 and s.m[0] == pytest.approx(0.1)                   # inputs are left alone
+    # the three wrong Adams are other numbers
+    for variant, want in (("rate_uncorrected", -0.01 * 0.1 / (np.sqrt(0.001) + 1e-8)),
+                          ("step_late", -rate2 * 0.1 / (np.sqrt(0.001) + 1e-8)),
+                          ("eps_under_root", -rate1 * 0.1 / np.sqrt(0.001 + 1e-8))):
+        wrong, _ = ref.step("Adam", w, g1, ZEROS, ["w"], step_count=0, variant=variant, **k)
+        np.testing.assert_allclose(wrong["w"], [want], rtol=1e-14)
+
+
+def test_mirror_adam_by_hand_with_other_hyper_parameters():
+    """b1 0.5, b2 0.9, eps 1e-3, lr 0.003; gradients 2 and -2: on the second step m cancels to nothing, A and U do not"""
+    k = dict(lr=0.003, beta1=0.5, beta2=0.9, eps=1e-3)
+    w = {"w": np.array([0.25])}
+    d, s = ref.step("Adam", w, {"w": np.array([2.0])}, ZEROS, ["w"], step_count=0, **k)
+    s = s["w"]
+    np.testing.assert_allclose([s.m[0], s.A[0], s.v[0]], [1.0, 1.0, 0.4], rtol=1e-15)
+    rate1 = 0.003 * np.sqrt(0.1) / 0.5
+    np.testing.assert_allclose(d["w"], [-rate1 / (np.sqrt(0.4) + 1e-3)], rtol=1e-14)
+    d2, s2 = ref.step("Adam", w, {"w": np.array([-1.0])}, {"w": (s.m, s.v)}, ["w"], step_count=1, **k)
+    s2 = s2["w"]
+    assert s2.m[0] == 0.0 and d2["w"][0] == 0.0
+    np.testing.assert_allclose([s2.A[0], s2.v[0]], [1.0, 0.46], rtol=1e-14)
+    rate2 = 0.003 * np.sqrt(0.19) / 0.75
+    np.testing.assert_allclose(s2.U, [rate2 / (np.sqrt(0.46) + 1e-3)], rtol=1e-14)
+    # the hyper-parameters as the ABI receives them: float32, and 1 - b exact
+    assert ref.f32(0.999) == 0.9990000128746033 and 1.0 - ref.f32(0.999) == float(np.float32(1) - np.float32(0.999))
+    assert ref.adam_rate(0.01, 0.9, 0.999, 2 ** 24 - 1) == 0.01
+
+
+# ------------------------------------------------------------------ the bounds against the kernels' arithmetic in numpy float32
+HYPER = dict(lr=ref.f32(0.01), beta1=ref.f32(0.9), beta2=ref.f32(0.999), eps=ref.f32(1e-8))
+
+
+def excess(err, bound):
+    return float((err / np.maximum(bound, 1e-300)).max())
+
+
+@pytest.mark.parametrize("max_norm", [0.0, 1.0], ids=["unclipped", "clip-1"])
+@pytest.mark.parametrize("n", [15, 2047, 4097])
+def test_fp32_emulation_stays_inside_the_bounds_and_wrong_mirrors_do_not(n, max_norm):
+    """ref.emulated_adam / emulated_clip_scale do in numpy float32 what k_sqnorm_part, k_clip_scale and k_adam do, operation
+    by operation, on the inputs the GPU test injects (ref.injected_case), three steps.  Mirrored in float64 from the
+    emulation's own pre-step values, every element of the change, of m and of v is inside the bounds, so the bounds are
+    not too tight for correct fp32 arithmetic; each of the three wrong Adams, and with the clip on the unclipped mirror from
+    step 2 (wherever the step's norm is above the threshold: there is nothing to miss otherwise), is outside the change's
+    bound by 100 times or more on some element, so they are not too wide to tell.  The weights start every step as they
+    were: half of them stay exactly 0, where the bound is the update's alone."""
+    clipped = max_norm > 0
+    w, grads = ref.injected_case(n, seed=n, steps=3)
+    m, v = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    worst = {"d": 0.0, "m": 0.0, "v": 0.0, "d0": 0.0}
+    told_unclipped = 0
+    for t0, g in enumerate(grads):
+        scale = ref.emulated_clip_scale([g], max_norm)
+        assert abs(float(scale) - ref.clip_scale({"w": g}, ["w"], max_norm)) <= ref.SCALE_RTOL * float(scale)
+        w1, m1, v1 = ref.emulated_adam(w, g, m, v, step_count=t0, scale=scale, **HYPER)
+        a = ({"w": w}, {"w": g}, {"w": (m, v)}, ["w"])
+        d, s = ref.step("Adam", *a, max_norm=max_norm, step_count=t0, **HYPER)
+        s = s["w"]
+        got = w1.astype(np.float64) - w
+        bound = ref.update_bound(w, s.U, clipped)
+        worst["d"] = max(worst["d"], excess(np.abs(got - d["w"]), bound))
+        worst["d0"] = max(worst["d0"], excess(np.abs(got - d["w"])[w == 0], bound[w == 0]))
+        worst["m"] = max(worst["m"], excess(np.abs(m1 - s.m), ref.adam_m_bound(s.A, clipped)))
+        worst["v"] = max(worst["v"], excess(np.abs(v1 - s.v), ref.adam_v_bound(s.v, clipped)))
+        assert (np.abs(got - d["w"]) <= bound).all() and (np.abs(m1 - s.m) <= ref.adam_m_bound(s.A, clipped)).all()
+        assert (np.abs(v1 - s.v) <= ref.adam_v_bound(s.v, clipped)).all()
+        assert float(np.abs(d["w"]).max()) >= 100 * float(bound.max())
+        for variant in ref.ADAM_VARIANTS:
+            wrong, _ = ref.step("Adam", *a, max_norm=max_norm, step_count=t0, variant=variant, **HYPER)
+            assert excess(np.abs(got - wrong["w"]), bound) >= 100, (t0, variant)
+        if clipped and t0 >= 1 and float(scale) < 0.99:     # (15 elements of step 2 can have a norm below 1: no clip to miss)
+            wrong, _ = ref.step("Adam", *a, max_norm=0.0, step_count=t0, **HYPER)
+            assert excess(np.abs(got - wrong["w"]), bound) >= 100, t0
+            told_unclipped += 1
+        m, v = m1, v1                            # (the weights start every step as they were: half of them stay 0)
+    assert told_unclipped >= (1 if n == 15 else 2) or not clipped
+    print("n %d max_norm %g: max err / bound  change %.3f (zero weights %.3f)  m %.3f  v %.3f"
+          % (n, max_norm, worst["d"], worst["d0"], worst["m"], worst["v"]))
+
+
+def test_injected_case_is_what_its_docstring_says():
+    n = 4097
+    w, grads = ref.injected_case(n, seed=1, steps=3)
+    assert (w == 0).sum() == n // 2 and len(grads) == 3 and all(g.dtype == np.float32 for g in grads)
+    tenth = n // 10
+    for s, g in enumerate(grads):
+        top = 1e3 * (1e-3 if s == 1 else 1.0)
+        nz = np.abs(g[g != 0]).astype(np.float64)
+        assert 0.07 <= (g == 0).mean() <= 0.13 and nz.min() >= 0.99e-12 * top / 1e3 and nz.max() <= 1.01 * top
+        first = np.abs(g[:tenth][g[:tenth] != 0]).astype(np.float64) * (1e3 / top)
+        assert first.min() >= 0.99e-9 and first.max() <= 1.01e-7
+    second = slice(tenth, 2 * tenth)
+    both = (grads[0][second] != 0) & (grads[1][second] != 0) & (grads[2][second] != 0)
+    assert both.sum() > tenth // 2
+    assert (np.sign(grads[0][second][both]) == np.sign(grads[2][second][both])).all()
+    assert (np.sign(grads[0][second][both]) == -np.sign(grads[1][second][both])).all()
+    # the tail weighs in the norm
+    assert all(np.abs(g[-3:]).min() >= 99.0 * (1e-3 if s == 1 else 1.0) for s, g in enumerate(grads))
+    stay = (grads[0] == 0) & (grads[1] == 0) & (grads[2] == 0)
+    assert stay.sum() >= n // 40                                                    # state that stays zero
 
 
 # ------------------------------------------------------------------ csrc/optimizer_check.h under ASan + UBSan

@@ -77,9 +77,10 @@ enum { RGCN_KIND_BLOCK = 0, RGCN_KIND_BASIS = 1, RGCN_KIND_BASIS_TDIAG = 2, RGCN
  *   - RGCN_ERR_UNSUPPORTED, the message naming the kind: rgcn_set_graph*, rgcn_prefetch_graph*, rgcn_step_device,
  *     rgcn_train_step_minibatch_device, rgcn_neighborhood_reserve, the phase API (rgcn_forward_begin ... rgcn_backward_end),
  *     rgcn_set_relation_owner, rgcn_capture_begin; rgcn_read_buffer knows RGCN_BUF_RANK_ENERGIES,
- *     RGCN_BUF_RANK_MIXED_SCORES, RGCN_BUF_RELATION_ENERGIES and RGCN_BUF_NEGATIVE_UNRESOLVED only (RGCN_ERR_STATE);
+ *     RGCN_BUF_RANK_MIXED_SCORES, RGCN_BUF_RELATION_ENERGIES, RGCN_BUF_NEGATIVE_UNRESOLVED and
+ *     RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED only (RGCN_ERR_STATE);
  *   - unchanged: rgcn_decoder_*, rgcn_negative_sample_device, rgcn_known_positives_reserve,
- *     rgcn_negative_sample_exclusive_device, rgcn_optimizer_*, rgcn_rank_device, rgcn_rank_mixed_device,
+ *     rgcn_negative_sample_exclusive_device, rgcn_negative_sample_relation_device, rgcn_optimizer_*, rgcn_rank_device, rgcn_rank_mixed_device,
  *     rgcn_topk_device, rgcn_score_queries_device, rgcn_topk_mixed_device, rgcn_rank_relation_device,
  *     rgcn_topk_relation_device, rgcn_score_relation_queries_device, parameters, device memory, timer and profile. */
 /* RGCN_KIND_BASIS_TDIAG = Encoder.DiagonalCoefficients=Yes -> BasisGcnTimesDiag
@@ -198,10 +199,14 @@ enum {
   RGCN_BUF_OUT_DH = 19,         /* float [V,d], contexts with an output transform (rgcn_config_ext::code_dim > 0): dL/dH_L of
                                    the last backward pass = dcodes . W_out^T, what the layer stack received as its dcodes.
                                    RGCN_ERR_STATE on every other context and before the first backward pass */
-  RGCN_BUF_NEGATIVE_UNRESOLVED = 20 /* int64 [1]: negative rows, since the last rgcn_known_positives_reserve, for which EVERY
+  RGCN_BUF_NEGATIVE_UNRESOLVED = 20,/* int64 [1]: negative rows, since the last rgcn_known_positives_reserve, for which EVERY
                                    entity was a known positive and which therefore kept their first draw (exclusive
                                    sampler, stand-alone and fused; replayed hipGraphs count too).  Every kind,
                                    RGCN_KIND_EMBEDDING included; RGCN_ERR_STATE without an index */
+  RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED = 21 /* int64 [1]: relation rows (rgcn_negative_sample_relation_device with
+                                   exclusive != 0, stand-alone and fused), since the last rgcn_known_positives_reserve, for
+                                   which EVERY other relation was a known positive for the pair and which therefore kept
+                                   their first draw.  Every kind; RGCN_ERR_STATE without an index */
 };
 
 /*
@@ -459,6 +464,48 @@ rgcn_status rgcn_negative_sample_exclusive_device(rgcn_ctx* ctx, const int32_t* 
                                                   uint64_t seed, int32_t* x_out_dev, float* y_out_dev);
 rgcn_status rgcn_set_exclusive_negatives(rgcn_ctx* ctx, int32_t on);
 
+/* Relation corruptions: negative rows (s, r', o) with a wrong RELATION, behind the entity corruptions above.  Not in the
+ * reference, whose sampler replaces entities only: W_relation is then trained to separate entities under a fixed
+ * relation, never relations for a fixed pair -- the question rgcn_rank_relation_device asks.
+ *
+ * rgcn_negative_sample_relation_device: a batch with relation_rate = m > 0 has N = n (1 + rate + m) rows;
+ * x_out_dev int32 [N,3], y_out_dev float [N].
+ *   - rows [0, n (rate + 1)) are exactly what rgcn_negative_sample_device writes for the same (batch, n, rate, seed) --
+ *     with exclusive != 0 what rgcn_negative_sample_exclusive_device writes -- bit for bit: the same kernels write them;
+ *   - row i >= n (rate + 1), with j = i - n (rate + 1) and (s, r, o) = batch[j mod n], has label 0, s and o unchanged and
+ *     the relation r'.  All draws are 24-bit counter draws bits(tag, index) of `seed`, T = RGCN_NEG_MAX_DRAWS:
+ *       - attempt 0 draws u = bits(0x6e6a, 2 j) << 24 | bits(0x6e6b, 2 j + 1), c = (u (R - 1)) >> 48, and the candidate is
+ *         r' = c + (c >= r): uniform over the R - 1 OTHER relations, the row's own relation is never drawn (at R = 18 a
+ *         uniform draw over all R would label a positive as negative in 1 row of 18);
+ *       - exclusive == 0: attempt 0 is the row;
+ *       - exclusive != 0: a candidate is KNOWN iff (s, r', o) is in K; a known candidate is redrawn, attempt t = 1 .. T - 1
+ *         from bits(0x6e6c, 2 (j T + t)) << 24 | bits(0x6e6d, 2 (j T + t) + 1);
+ *       - if all T candidates are known the row takes the first relation that is not, scanning upward cyclically from the
+ *         last candidate and passing over r (at most R - 1 lookups);
+ *       - if every other relation is known the row keeps attempt 0's candidate and RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED
+ *         grows by one (RGCN_BUF_NEGATIVE_UNRESOLVED counts the entity rows only, as before);
+ *       - a batch row with an id out of range takes r' = c of attempt 0, without the skip and without a lookup; nothing is
+ *         read out of bounds and the decoder rejects the row when it consumes x_out.
+ *   - the result is a function of (K, batch, seed) alone; the exclusive relation rows differ from the plain ones for the
+ *     same seed only in rows whose attempt-0 candidate is known, and there only in column 1;
+ *   - relation_rate in [0, 1024]; relation_rate == 0 is rgcn_negative_sample_device (exclusive != 0: its exclusive form);
+ *     relation_rate > 0 with RelationCount < 2, and N above RGCN_MAX_DECODER_TRIPLES: RGCN_ERR_INVALID; exclusive != 0
+ *     without an index: RGCN_ERR_STATE;
+ *   - RGCN_ERR_STATE between rgcn_capture_begin and rgcn_capture_end: capture is not built for it;
+ *   - asynchronous on the main stream; every kind, RGCN_KIND_EMBEDDING included;
+ *   - a batch with relation rows is not the tiled batch of rgcn_negative_sample_device (copies of a triple no longer share
+ *     a relation): the decoder prepares it as it prepares any caller's X.
+ *
+ * rgcn_set_relation_negatives(ctx, m): rgcn_train_step_minibatch_device appends m relation rows per batch edge, exclusive
+ * iff rgcn_set_exclusive_negatives is on, with that call's negative_seed.  The step's N is n (1 + rate + m): the scratch
+ * buffers and rgcn_decoder_reserve must cover it (RGCN_ERR_STATE).  RGCN_ERR_STATE during a capture, from this call and
+ * from the step while m > 0; m > 0 on a context with world > 1: RGCN_ERR_UNSUPPORTED; RelationCount < 2: RGCN_ERR_INVALID.
+ * Default 0: every call produces the bytes it produced before these entry points existed, the tiled path included. */
+rgcn_status rgcn_negative_sample_relation_device(rgcn_ctx* ctx, const int32_t* batch_dev, int64_t n, int32_t rate,
+                                                 int32_t relation_rate, int32_t exclusive, uint64_t seed,
+                                                 int32_t* x_out_dev, float* y_out_dev);
+rgcn_status rgcn_set_relation_negatives(rgcn_ctx* ctx, int32_t relation_rate);
+
 /* ---- evaluation: raw and filtered link-prediction ranks -------------------------------
  * Replaces Model.score_all_subjects / score_all_objects + Scorer.evaluate_mrr + MrrScore.append_line
  * (code/model.py:59-81, code/decoders/bilinear_diag.py:51-61, code/common/evaluation.py:148-153,349-389).
@@ -666,7 +713,7 @@ rgcn_status rgcn_train_step_device(rgcn_ctx* ctx, const int32_t* triples_dev, in
  * optimize.py:81-88) in ONE asynchronous call on a graph batch that is resident in HBM: edge dropout (exact `keep`
  * of the n batch edges -> message graph, as rgcn_set_graph_dropout_device with edge_seed), negative sampling
  * (rgcn_negative_sample_device -- under rgcn_set_exclusive_negatives its exclusive form -- on ALL n batch edges -> x_scratch_dev int32 [n*(rate+1),3], y_scratch_dev float
- * [n*(rate+1)]), then the train step of rgcn_train_step_device.  Only the n batch triples cross PCIe per step. */
+ * [n*(rate+1)]), under rgcn_set_relation_negatives(m) n*m relation rows behind them and n*(rate+1+m) rows in all), then the train step of rgcn_train_step_device.  Only the n batch triples cross PCIe per step. */
 rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* ctx, const int32_t* batch_dev, int64_t num_edges, int64_t keep,
                                              uint64_t edge_seed, int32_t negative_rate, uint64_t negative_seed,
                                              int32_t* x_scratch_dev, float* y_scratch_dev, uint64_t dropout_seed,

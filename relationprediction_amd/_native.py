@@ -30,6 +30,7 @@ BUF_RANK_MIXED_SCORES = 17   # [reserved queries, V], the mixed scores the last 
 BUF_RELATION_ENERGIES = 18   # [reserved queries, R], the energies of the chunk a relation query scored last
 BUF_OUT_DH = 19              # contexts with an output transform: [V, d], dL/dH_L of the last backward pass
 BUF_NEGATIVE_UNRESOLVED = 20 # int64 [1]: negative rows every entity was a known positive for, since the reserve
+BUF_NEGATIVE_RELATION_UNRESOLVED = 21  # int64 [1]: relation rows every other relation was a known positive for
 KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS, "basis_tdiag": KIND_BASIS_TDIAG,
          "basis_pdiag": KIND_BASIS_PDIAG, "embedding": KIND_EMBEDDING}
 NORMS = {"intended": NORM_INTENDED, "tf_as_executed": NORM_TF_AS_EXECUTED, "none": NORM_NONE, "local": NORM_LOCAL}
@@ -126,6 +127,9 @@ _SIGS = {
     "rgcn_known_positives_reserve": (C.c_int32, [_P, _P, C.c_int64]),
     "rgcn_negative_sample_exclusive_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, _P, _P]),
     "rgcn_set_exclusive_negatives": (C.c_int32, [_P, C.c_int32]),
+    "rgcn_negative_sample_relation_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint64,
+                                                         _P, _P]),
+    "rgcn_set_relation_negatives": (C.c_int32, [_P, C.c_int32]),
     "rgcn_rank_reserve": (C.c_int32, [_P, C.c_int64]),
     "rgcn_rank_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
     "rgcn_rank_energies_device": (_P, [_P]),
@@ -600,11 +604,29 @@ class Engine:
         self._check(self.lib.rgcn_sample_neighborhood_device(self.ctx, int(sample_size), C.c_uint64(int(seed)),
                                                              batch_dev.ptr, 1 if on_prefetch_stream else 0))
 
-    def negative_sample_device(self, batch_dev, n, rate, seed, x_dev, y_dev, exclusive=False):
+    def negative_sample_device(self, batch_dev, n, rate, seed, x_dev, y_dev, exclusive=False, relation_rate=0):
         """X [n*(rate+1),3] and Y [n*(rate+1)] from the batch of n triples, all on the device.  exclusive: corruptions
-        that are known positives (known_positives_reserve) are redrawn (rgcn_negative_sample_exclusive_device)."""
+        that are known positives (known_positives_reserve) are redrawn (rgcn_negative_sample_exclusive_device).
+        relation_rate = m > 0: n*m rows (s, r', o) with a wrong relation follow, n*(rate+1+m) rows in all
+        (rgcn_negative_sample_relation_device)."""
+        if relation_rate:
+            self._check(self.lib.rgcn_negative_sample_relation_device(
+                self.ctx, batch_dev.ptr, int(n), int(rate), int(relation_rate), 1 if exclusive else 0,
+                C.c_uint64(int(seed)), x_dev.ptr, y_dev.ptr))
+            return
         fn = self.lib.rgcn_negative_sample_exclusive_device if exclusive else self.lib.rgcn_negative_sample_device
         self._check(fn(self.ctx, batch_dev.ptr, int(n), int(rate), C.c_uint64(int(seed)), x_dev.ptr, y_dev.ptr))
+
+    def set_relation_negatives(self, relation_rate):
+        """relation rows per batch edge the negative sampling inside train_step_minibatch_device appends (0: none)"""
+        self._check(self.lib.rgcn_set_relation_negatives(self.ctx, int(relation_rate)))
+
+    def negative_relation_unresolved(self):
+        """relation rows, since the reserve, for which every other relation was a known positive (they kept their first
+        draw)"""
+        out = np.zeros(1, dtype=np.int64)
+        self._check(self.lib.rgcn_read_buffer(self.ctx, BUF_NEGATIVE_RELATION_UNRESOLVED, _ptr(out), out.nbytes))
+        return int(out[0])
 
     def known_positives_reserve(self, triples):
         """the set of known positives to the device, once (NegativeSampler.set_known_positives); an empty set releases

@@ -28,7 +28,7 @@ SOURCES = ["rgcn_api.hip", "rgcn_schedule.hip", "rgcn_devtools.hip", "graph_prep
            "elementwise.hip", "highway.hip", "output_transform.hip", "decoder.hip", "optimizer.hip", "ranking.hip", "sampler.hip", "neighborhood.hip", "comm.hip"]
 HEADERS = [os.path.join(CSRC, "rgcn_internal.h"), os.path.join(CSRC, "rgcn_api_internal.h"), os.path.join(CSRC, "gemm_split.h"), os.path.join(CSRC, "gemm_plan.h"),
            os.path.join(CSRC, "dev_pool.h"), os.path.join(CSRC, "config_check.h"), os.path.join(CSRC, "optimizer_check.h"),
-           os.path.join(CSRC, "row_walk.h"), os.path.join(CSRC, "counter_rng.h"), os.path.join(CSRC, "negative_exclusive.h"),
+           os.path.join(CSRC, "row_walk.h"), os.path.join(CSRC, "counter_rng.h"), os.path.join(CSRC, "negative_exclusive.h"), os.path.join(CSRC, "negative_relation.h"),
            os.path.join(CSRC, "known_positives_index.h"),
            os.path.join(ROOT, "include", "rgcn.h"),
            os.path.join(ROOT, "include", "rgcn_devtools.h")]

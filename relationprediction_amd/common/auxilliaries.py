@@ -6,7 +6,12 @@ drawn entity.  Row (i, j) of the reference's double loop reads `choices[i + j*si
 and writes row `size + i + j*size` — one draw per negative row, in row order — so the vectorised form below
 is the same function of the same random streams (`np.random.binomial` then `np.random.randint`).
 Corrupted triples are NOT checked against known positives (that is `transform_exclusive`, which no
-BASELINE setting calls; `[General] ExclusiveNegativeSampling=Yes` selects it, on the host and on the device)."""
+BASELINE setting calls; `[General] ExclusiveNegativeSampling=Yes` selects it, on the host and on the device).
+
+`relation_rate = m > 0` (`[General] RelationNegativeSampleRate`, not in the reference): both transforms append m further
+copies of the batch with label 0 whose RELATION is replaced by one of the `relation_count - 1` others, uniformly -- the
+distribution of the device's k_negative_sample_relation, from numpy's stream.  They are drawn after the entity draws, so
+with m = 0 the generator is consumed exactly as before."""
 import numpy as np
 
 
@@ -14,9 +19,45 @@ class NegativeSampler(object):
     negative_sample_rate = None
     n_entities = None
 
-    def __init__(self, negative_sample_rate, n_entities):
+    relation_rate = 0
+    relation_count = None
+    max_relation_draws = 32         # RGCN_NEG_MAX_DRAWS: then the first free relation upward, as on the device
+
+    def __init__(self, negative_sample_rate, n_entities, relation_rate=0, relation_count=None):
         self.negative_sample_rate = int(negative_sample_rate)
         self.n_entities = int(n_entities)
+        self.relation_rate = int(relation_rate)
+        if self.relation_rate < 0:
+            raise ValueError("relation_rate must not be negative")
+        if self.relation_rate > 0 and (relation_count is None or int(relation_count) < 2):
+            raise ValueError("relation corruptions need relation_count >= 2")
+        self.relation_count = None if relation_count is None else int(relation_count)
+
+    def _other_relations(self, relations, rng):
+        """one relation other than its own for every entry: a draw in [0, R - 1), stepped past the own relation"""
+        draws = rng.randint(self.relation_count - 1, size=len(relations))
+        return (draws + (draws >= relations)).astype(np.int32)
+
+    def _append_relation_rows(self, triplets, new_indexes, new_labels, rng, exclusive):
+        """the relation_rate further copies (s, r', o), label 0, behind the rows of transform / transform_exclusive"""
+        if self.relation_rate == 0:
+            return new_indexes, new_labels
+        rows = np.tile(np.asarray(triplets), (self.relation_rate, 1)).astype(np.int32)
+        own = rows[:, 1].copy()
+        rows[:, 1] = self._other_relations(own, rng)
+        if exclusive:
+            R = self.relation_count
+            for row, r in zip(rows, own):
+                known = self.objs.get(row[0], ())
+                first, draws = row[1], 1
+                while (row[1], row[2]) in known and draws < self.max_relation_draws:
+                    row[1] = self._other_relations(np.array([r]), rng)[0]
+                    draws += 1
+                if (row[1], row[2]) in known:        # every draw was known: scan; none free: the first draw stays
+                    free = [e % R for e in range(row[1] + 1, row[1] + R) if e % R != r and (e % R, row[2]) not in known]
+                    row[1] = free[0] if free else first
+        return (np.concatenate([new_indexes, rows]),
+                np.concatenate([new_labels, np.zeros(len(rows), dtype=np.float32)]))
 
     def transform(self, triplets, rng=None):
         """`rng`: a numpy RandomState to draw from instead of the global one (background batch producers)."""
@@ -32,7 +73,7 @@ class NegativeSampler(object):
         negatives = new_indexes[size_of_batch:]
         negatives[choices, 2] = values[choices]
         negatives[~choices, 0] = values[~choices]
-        return new_indexes, new_labels
+        return self._append_relation_rows(triplets, new_indexes, new_labels, rng, False)
 
     def set_known_positives(self, triplets):
         self.objs, self.subs = {}, {}
@@ -61,4 +102,4 @@ class NegativeSampler(object):
                 row[0] = rng.randint(self.n_entities)
                 while (row[1], row[0]) in self.subs.get(row[2], ()):
                     row[0] = rng.randint(self.n_entities)
-        return new_indexes, new_labels
+        return self._append_relation_rows(triplets, new_indexes, new_labels, rng, True)

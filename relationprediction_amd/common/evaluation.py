@@ -236,8 +236,10 @@ class Scorer(object):
             return self.compute_mrr_scores(triples, verbose=verbose)
         if self.settings['Metric'] == 'Accuracy':
             return self.compute_accuracy_scores(triples, verbose=verbose)
-        raise NotImplementedError("Evaluation.Metric=%s (MRR and Accuracy are what the reference has)"
-                                  % self.settings['Metric'])
+        if self.settings['Metric'] == 'RelationMRR':
+            return self.compute_relation_mrr_scores(triples, verbose=verbose)
+        raise NotImplementedError("Evaluation.Metric=%s (MRR and Accuracy are what the reference has, RelationMRR is this "
+                                  "project's)" % self.settings['Metric'])
 
     def compute_accuracy_scores(self, triples, verbose=False):
         """code/common/evaluation.py:311-326: rows 2k / 2k + 1 are a (positive, negative) pair; a tie counts as wrong"""
@@ -283,7 +285,7 @@ class Scorer(object):
         """Ranks of the gold relation of every triple among all relations between its subject and object
         (rgcn_rank_relation_device), filtered by the relations known for the pair: one line per triple.  The degree and
         vertex-frequency columns are the subject's, the relation frequency the gold relation's.  The reference has no
-        such evaluation; compute_scores does not call it."""
+        such evaluation; compute_scores calls it for Metric=RelationMRR."""
         triples = np.asarray(triples)
         score = MrrScore(triples)
         graph = self.model.test_graph

@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "known_positives_index.h"
+#include "negative_relation.h"
 #include "rgcn_internal.h"
 #include "row_walk.h"
 
@@ -199,6 +200,26 @@ __global__ void k_negative_sample_exclusive(const int32_t* __restrict__ batch, i
   }
   X[3 * i] = s; X[3 * i + 1] = r; X[3 * i + 2] = o;
   Y[i] = i < n ? 1.0f : 0.0f;
+}
+
+// Relation corruptions ([General] RelationNegativeSampleRate; negative_relation.h holds the decision, shared with the
+// host): relation row j of the batch goes to row `first + j`, first = n (rate + 1) -- behind the rows the kernels above
+// wrote, which this one neither reads nor writes.  One thread per row.  The plain form draws once and reads no index; the
+// exclusive form searches K as k_negative_sample_exclusive does, with stride V V between the keys of two candidates.
+__global__ void __launch_bounds__(256) k_negative_sample_relation(const int32_t* __restrict__ batch, int n, int64_t first,
+                                                                  int64_t rows, KnownIndex known, int exclusive,
+                                                                  uint64_t seed, int32_t* __restrict__ X,
+                                                                  float* __restrict__ Y,
+                                                                  unsigned long long* __restrict__ unresolved) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= rows) return;
+  const int b = (int)(j % n);
+  const int s = batch[3 * b], r = batch[3 * b + 1], o = batch[3 * b + 2];
+  const RelationChoice ch = negative_relation_choice(known, exclusive, seed, (uint64_t)j, s, r, o);
+  if (ch.unresolved) atomicAdd(unresolved, 1ull);
+  const int64_t i = first + j;
+  X[3 * i] = s; X[3 * i + 1] = ch.relation; X[3 * i + 2] = o;
+  Y[i] = 0.0f;
 }
 
 // ---- K1: energies, dx, loss terms ---------------------------------------------------------------
@@ -851,6 +872,27 @@ rgcn_status negative_sample_exclusive(rgcn_ctx* c, const int32_t* batch_dev, int
   return RGCN_OK;
 }
 
+// The entity samplers' rows first, by their own kernels (so those bytes cannot drift), then the relation rows behind them.
+rgcn_status negative_sample_relation(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int rate, int relation_rate,
+                                     bool exclusive, uint64_t seed, int32_t* X, float* Y) {
+  if (exclusive)
+    RGCN_TRY(negative_sample_exclusive(c, batch_dev, n, rate, seed, X, Y));
+  else
+    RGCN_TRY(negative_sample(c, batch_dev, n, rate, seed, X, Y));
+  const int64_t first = n * (rate + 1), rows = n * (int64_t)relation_rate;
+  if (rows <= 0) return RGCN_OK;
+  const KnownPositives& k = c->known;
+  ProfScope ps(c, "negative_sample_relation", 12.0 * n + 16.0 * rows, 0);
+  const KnownIndex index{exclusive ? k.keys : nullptr, exclusive ? k.count : 0, c->V, c->R};
+  hipLaunchKernelGGL(k_negative_sample_relation, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, batch_dev,
+                     (int)n, first, rows, index, exclusive ? 1 : 0, seed, X, Y,
+                     exclusive ? k.relation_unresolved : nullptr);
+  RGCN_HIP(c, hipGetLastError());
+  // copies of a triple no longer share a relation: the batch is not the tiled one, decoder_prepare takes its general path
+  c->dec.tiled_X = nullptr;
+  return RGCN_OK;
+}
+
 void known_positives_free(rgcn_ctx* c) {
   c->known.pool.release();
   c->known = KnownPositives();
@@ -867,6 +909,7 @@ rgcn_status known_positives_reserve(rgcn_ctx* c, const int32_t* triples_host, in
   KnownPositives fresh;
   RGCN_TRY(dmalloc(c, fresh.pool, &fresh.keys, keys.size(), false));
   RGCN_TRY(dmalloc(c, fresh.pool, &fresh.unresolved, 1, true));
+  RGCN_TRY(dmalloc(c, fresh.pool, &fresh.relation_unresolved, 1, true));
   RGCN_HIP(c, hipMemcpyAsync(fresh.keys, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
   RGCN_HIP(c, hipStreamSynchronize(c->stream));       // `keys` is a local; the counter's memset is ahead of the copy
   fresh.count = (int64_t)keys.size();

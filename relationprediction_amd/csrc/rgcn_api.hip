@@ -1064,6 +1064,45 @@ rgcn_status rgcn_set_exclusive_negatives(rgcn_ctx* c, int32_t on) {
   return RGCN_OK;
 }
 
+// ---- relation corruptions: the stand-alone call and the mode of the fused step
+// whether [dev, dev + bytes) lies inside one device allocation; a pointer the runtime cannot place is taken on trust
+static bool allocation_covers(const void* dev, size_t bytes) {
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void*>(dev)) != hipSuccess) {
+    (void)hipGetLastError();
+    return true;
+  }
+  const char* lo = reinterpret_cast<const char*>(base);
+  const char* p = reinterpret_cast<const char*>(dev);
+  return p >= lo && p + bytes <= lo + size;
+}
+
+rgcn_status rgcn_negative_sample_relation_device(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int32_t rate,
+                                                 int32_t relation_rate, int32_t exclusive, uint64_t seed,
+                                                 int32_t* x_out_dev, float* y_out_dev) {
+  RGCN_NEED(c);
+  if (n < 0 || rate < 0 || rate > 1024 || relation_rate < 0 || relation_rate > 1024 ||
+      (n > 0 && (!batch_dev || !x_out_dev || !y_out_dev)))
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
+  if (relation_rate > 0 && c->R < 2) RGCN_FAIL(c, RGCN_ERR_INVALID, "relation corruptions need at least two relations");
+  if (n * (int64_t)(rate + 1 + relation_rate) > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "batch too large");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
+  if (exclusive && c->known.count <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_known_positives_reserve first");
+  return negative_sample_relation(c, batch_dev, n, rate, relation_rate, exclusive != 0, seed, x_out_dev, y_out_dev);
+}
+
+rgcn_status rgcn_set_relation_negatives(rgcn_ctx* c, int32_t relation_rate) {
+  RGCN_NEED(c);
+  if (relation_rate < 0 || relation_rate > 1024) RGCN_FAIL(c, RGCN_ERR_INVALID, "relation_rate outside [0, 1024]");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
+  if (relation_rate > 0 && c->world > 1)
+    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "relation corruptions in the fused step of a relation-sharded context (world > 1)");
+  if (relation_rate > 0 && c->R < 2) RGCN_FAIL(c, RGCN_ERR_INVALID, "relation corruptions need at least two relations");
+  c->relation_negatives = relation_rate;
+  return RGCN_OK;
+}
+
 rgcn_status rgcn_rank_reserve(rgcn_ctx* c, int64_t max_queries) {
   RGCN_NEED(c);
   if (max_queries <= 0) RGCN_FAIL(c, RGCN_ERR_INVALID, "max_queries must be positive");
@@ -1464,14 +1503,26 @@ rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* c, const int32_t* batch_d
   if (n >= ((int64_t)1 << 24)) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "edge dropout: more than 2^24 batch edges");
   if (negative_rate < 0 || negative_rate > 1024 || !batch_dev || !x_scratch_dev || !y_scratch_dev)
     RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
-  const int64_t N = n * (int64_t)(negative_rate + 1);
+  const int32_t relation_rate = c->relation_negatives;      // rgcn_set_relation_negatives; 0: the step as it always was
+  const int64_t N = n * (int64_t)(negative_rate + 1 + relation_rate);
   if (c->world > 1 && !c->comm)
     RGCN_FAIL(c, RGCN_ERR_STATE, "world > 1: call rgcn_comm_init first (or drive the phase API yourself)");
   if (c->dec.maxN < N) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_decoder_reserve(ctx, max_triples) first");
+  if (relation_rate > 0) {
+    if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "relation corruptions are not built for a hipGraph capture");
+    if (N > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "batch too large");
+    // the relation rows lie behind the n (rate + 1) rows a caller sized its scratch for before the mode existed
+    if (!allocation_covers(x_scratch_dev, sizeof(int32_t) * 3 * (size_t)N) ||
+        !allocation_covers(y_scratch_dev, sizeof(float) * (size_t)N))
+      RGCN_FAIL(c, RGCN_ERR_STATE, "the scratch buffers must hold num_edges x (1 + negative_rate + relation_rate) rows");
+  }
   // the message graph: adopted from the prefetch of this very (batch, keep, seed), or drawn and prepared in line
   RGCN_TRY(step_begin(c, batch_dev, n, false, keep, edge_seed));   // (the fork point is recorded below)
   // the decoder batch: all n batch edges as positives (the dropped ones included) + their corruptions
-  if (c->known.exclusive)
+  if (relation_rate > 0)
+    RGCN_TRY(negative_sample_relation(c, batch_dev, n, negative_rate, relation_rate, c->known.exclusive, negative_seed,
+                                      x_scratch_dev, y_scratch_dev));
+  else if (c->known.exclusive)
     RGCN_TRY(negative_sample_exclusive(c, batch_dev, n, negative_rate, negative_seed, x_scratch_dev, y_scratch_dev));
   else
     RGCN_TRY(negative_sample(c, batch_dev, n, negative_rate, negative_seed, x_scratch_dev, y_scratch_dev));
@@ -1707,12 +1758,16 @@ rgcn_status rgcn_backward_end(rgcn_ctx* c) { RGCN_NEED(c); return bwd_end(c); }
 static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* bytes) {
   const int64_t Vd = (int64_t)c->V * c->d * 4;
   if (c->embedding && which != RGCN_BUF_RANK_ENERGIES && which != RGCN_BUF_RANK_MIXED_SCORES &&
-      which != RGCN_BUF_RELATION_ENERGIES && which != RGCN_BUF_NEGATIVE_UNRESOLVED)
+      which != RGCN_BUF_RELATION_ENERGIES && which != RGCN_BUF_NEGATIVE_UNRESOLVED &&
+      which != RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED)
     RGCN_FAIL(c, RGCN_ERR_STATE, "an RGCN_KIND_EMBEDDING context has the ranking buffers only (no graph, no layer buffers)");
   switch (which) {
     case RGCN_BUF_NEGATIVE_UNRESOLVED:
       if (c->known.count <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "no known positives (rgcn_known_positives_reserve first)");
       *p = c->known.unresolved; *bytes = 8; return RGCN_OK;
+    case RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED:
+      if (c->known.count <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "no known positives (rgcn_known_positives_reserve first)");
+      *p = c->known.relation_unresolved; *bytes = 8; return RGCN_OK;
     case RGCN_BUF_EXCHANGE:
       if (!c->exch) RGCN_FAIL(c, RGCN_ERR_STATE, "no exchange buffer on a world == 1 context");
       *p = c->exch; *bytes = Vd; return RGCN_OK;

@@ -327,6 +327,8 @@ struct KnownPositives {
   uint64_t* keys = nullptr;                // [count] sorted unique packed keys (r V + s) V + o
   int64_t count = 0;                       // 0: no index
   unsigned long long* unresolved = nullptr;  // rows every entity was known for, since the reserve (RGCN_BUF_NEGATIVE_UNRESOLVED)
+  unsigned long long* relation_unresolved = nullptr;  // relation rows every other relation was known for
+                                                      // (RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED)
   bool exclusive = false;                  // rgcn_set_exclusive_negatives: the fused minibatch step draws exclusively
 };
 
@@ -446,6 +448,7 @@ struct rgcn_ctx {
   rgcn::DecoderBufs dec;
   rgcn::NeighborhoodBufs nbr;
   rgcn::KnownPositives known;
+  int32_t relation_negatives = 0;        // rgcn_set_relation_negatives: relation rows per positive in the fused minibatch step
   rgcn::OptimizerState opt;
 
   std::vector<float*> H;                 // H[0..L], [V,d] each
@@ -741,6 +744,10 @@ rgcn_status negative_sample(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, in
 // the same against the context's index of known positives (c->known.count > 0): negative_exclusive.h decides every row
 rgcn_status negative_sample_exclusive(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int rate, uint64_t seed,
                                       int32_t* X, float* Y);
+// the entity rows by one of the two calls above, then relation_rate relation corruptions of every batch row behind them
+// (negative_relation.h decides every row); relation_rate > 0 clears DecoderBufs::tiled_X
+rgcn_status negative_sample_relation(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int rate, int relation_rate,
+                                     bool exclusive, uint64_t seed, int32_t* X, float* Y);
 // the index: built on the host from validated limits (known_positives_index.h), swapped in only when complete;
 // n == 0 releases it and switches the exclusive mode off
 rgcn_status known_positives_reserve(rgcn_ctx* c, const int32_t* triples_host, int64_t n);

@@ -93,15 +93,21 @@ class BilinearDiag(Model):
         graph-less encoder, Name=embedding)."""
         self.next_component.get_runtime().train_step(graph_edges, x, y, self.regularization_parameter, seed)
 
-    def device_train_step_negatives(self, graph_edges, batch, rate, seed, known=None):
+    def device_train_step_negatives(self, graph_edges, batch, rate, seed, known=None, relation_rate=0):
         """device_train_step with the negatives drawn on the device from `batch`; known: the known positives they avoid
-        (ExclusiveNegativeSampling=Yes), None for the plain sampler."""
+        (ExclusiveNegativeSampling=Yes), None for the plain sampler; relation_rate: relation corruptions per positive
+        (RelationNegativeSampleRate)."""
         self.next_component.get_runtime().train_step_device_negatives(graph_edges, batch, rate,
-                                                                      self.regularization_parameter, seed, known=known)
+                                                                      self.regularization_parameter, seed, known=known,
+                                                                      relation_rate=relation_rate)
 
     def device_negative_unresolved(self):
         """negative rows the exclusive device sampler could not resolve since its known positives were reserved"""
         return self.next_component.get_runtime().negative_unresolved()
+
+    def device_negative_relation_unresolved(self):
+        """relation rows the exclusive device sampler could not resolve since its known positives were reserved"""
+        return self.next_component.get_runtime().negative_relation_unresolved()
 
     def device_stage(self, graph_edges, batch=None):
         """feed the next train step beside the running one (runtime.stage); a graph-less encoder has nothing to stage"""

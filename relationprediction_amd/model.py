@@ -254,6 +254,9 @@ class Model(object):
     def device_negative_unresolved(self):
         return self.__delegate__('device_negative_unresolved')
 
+    def device_negative_relation_unresolved(self):
+        return self.__delegate__('device_negative_relation_unresolved')
+
     def device_ranks(self, *args):
         return self.__delegate__('device_ranks', *args)
 

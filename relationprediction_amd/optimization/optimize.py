@@ -305,11 +305,14 @@ class DeviceNegatives(object):
     `batch` (NegativeSampler.transform's distribution: rgcn_negative_sample_device).  graph_edges None: the model has no
     graph (Name=embedding) and `batch`, the whole training set, stays resident on the device while the same array is fed.
     `known`: the known positives (ExclusiveNegativeSampling=Yes: the training triples, the same array every iteration) --
-    corruptions among them are redrawn (rgcn_negative_sample_exclusive_device); None: the plain sampler."""
+    corruptions among them are redrawn (rgcn_negative_sample_exclusive_device); None: the plain sampler.
+    `relation_rate`: relation corruptions (s, r', o) per positive behind the entity corruptions (RelationNegativeSampleRate;
+    rgcn_negative_sample_relation_device); 0: none."""
 
-    def __init__(self, graph_edges, batch, rate, known=None):
+    def __init__(self, graph_edges, batch, rate, known=None, relation_rate=0):
         self.graph_edges, self.batch, self.rate = graph_edges, batch, int(rate)
         self.known = known
+        self.relation_rate = int(relation_rate)
 
 
 class DeviceMinibatch(object):
@@ -321,12 +324,14 @@ class DeviceMinibatch(object):
     too -- the neighbourhood edge sampler (train.py:161-198; rgcn_sample_neighborhood_device): nothing is built on the
     host and nothing is uploaded, an iteration is three seeds.
 
-    `known` as in DeviceNegatives: the step's corruptions avoid these triples (rgcn_set_exclusive_negatives)."""
+    `known` as in DeviceNegatives: the step's corruptions avoid these triples (rgcn_set_exclusive_negatives);
+    `relation_rate` as there: the step appends that many relation rows per batch edge (rgcn_set_relation_negatives)."""
 
-    def __init__(self, batch, keep, edge_seed, rate, sample=None, known=None):
+    def __init__(self, batch, keep, edge_seed, rate, sample=None, known=None, relation_rate=0):
         self.batch, self.keep, self.edge_seed, self.rate = batch, int(keep), int(edge_seed), int(rate)
         self.sample = sample
         self.known = known
+        self.relation_rate = int(relation_rate)
 
 
 class HipOptimizer(object):
@@ -355,6 +360,8 @@ class HipOptimizer(object):
             return
         if isinstance(processed_batch, DeviceNegatives):
             known = () if processed_batch.known is None else (processed_batch.known,)
+            if processed_batch.relation_rate:
+                known = (processed_batch.known, processed_batch.relation_rate)
             self.model.device_train_step_negatives(processed_batch.graph_edges, processed_batch.batch,
                                                    processed_batch.rate, seed, *known)
             return

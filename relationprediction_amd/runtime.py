@@ -157,9 +157,22 @@ class EncoderRuntime(object):
             self._exclusive_on = on
         return on
 
+    def _relation_negatives(self, relation_rate):
+        """RelationNegativeSampleRate: the fused minibatch step appends this many relation rows per batch edge
+        (rgcn_set_relation_negatives); the engine is told when the rate changes.  Returns the rate."""
+        relation_rate = int(relation_rate)
+        if relation_rate != getattr(self, "_relation_rate", 0):
+            self.engine.set_relation_negatives(relation_rate)
+            self._relation_rate = relation_rate
+        return relation_rate
+
     def negative_unresolved(self):
         """negative rows every entity was a known positive for, since the known positives were reserved (0 without them)"""
         return self.engine.negative_unresolved() if getattr(self, "_known", None) is not None else 0
+
+    def negative_relation_unresolved(self):
+        """relation rows every other relation was a known positive for, since the reserve (0 without known positives)"""
+        return self.engine.negative_relation_unresolved() if getattr(self, "_known", None) is not None else 0
 
     def stage(self, graph_edges, batch=None):
         """Feed the NEXT train step while the current one runs: its triples go to the inactive one of two device
@@ -237,7 +250,8 @@ class EncoderRuntime(object):
         else:
             b = np.ascontiguousarray(mb.batch, dtype=np.int32).reshape(-1, 3)
             nb = len(b)
-        n = nb * (int(mb.rate) + 1)
+        relation_rate = int(getattr(mb, "relation_rate", 0))
+        n = nb * (int(mb.rate) + 1 + relation_rate)
         if n == 0:
             raise ValueError("empty decoder batch")
         if nb > self.engine.max_edges:
@@ -255,6 +269,7 @@ class EncoderRuntime(object):
             bd = self._upload("mbatch", b)
         xd, yd = self._buffer("X", 12 * n), self._buffer("Y", 4 * n)
         self._exclusive(getattr(mb, "known", None))
+        self._relation_negatives(relation_rate)
         self.engine.train_step_minibatch_device(bd, nb, mb.keep, mb.edge_seed, mb.rate, seed ^ 0x5bd1e995, xd, yd,
                                                 seed=seed, reg_param=reg_param)
         self._state = None
@@ -296,13 +311,15 @@ class EncoderRuntime(object):
         self._graph_version = None
         self.weights_version += 1
 
-    def train_step_device_negatives(self, graph_edges, batch, rate, reg_param, seed, known=None):
+    def train_step_device_negatives(self, graph_edges, batch, rate, reg_param, seed, known=None, relation_rate=0):
         """As train_step, with the decoder batch (positives + `rate` corruptions each) drawn on the device from
         `batch` (rgcn_negative_sample_device): only the two triple lists cross the PCIe bus.  known: the known positives
-        the corruptions avoid (rgcn_negative_sample_exclusive_device), None for the plain sampler."""
+        the corruptions avoid (rgcn_negative_sample_exclusive_device), None for the plain sampler.  relation_rate: relation
+        corruptions per positive behind them (rgcn_negative_sample_relation_device)."""
         g = np.ascontiguousarray(graph_edges, dtype=np.int32).reshape(-1, 3)
         b = np.ascontiguousarray(batch, dtype=np.int32).reshape(-1, 3)
-        n = len(b) * (int(rate) + 1)
+        relation_rate = int(relation_rate)
+        n = len(b) * (int(rate) + 1 + relation_rate)
         if n == 0:
             raise ValueError("empty decoder batch")
         if len(g) > self.engine.max_edges:
@@ -323,7 +340,8 @@ class EncoderRuntime(object):
                     buf.free()
                 self._dev[name] = _native.DeviceBuffer(self.engine, nbytes)
         xd, yd = self._dev["X"], self._dev["Y"]
-        self.engine.negative_sample_device(bd, len(b), rate, seed ^ 0x5bd1e995, xd, yd, exclusive=self._exclusive(known))
+        self.engine.negative_sample_device(bd, len(b), rate, seed ^ 0x5bd1e995, xd, yd, exclusive=self._exclusive(known),
+                                           relation_rate=relation_rate)
         self.engine.train_step_device(gd, len(g), xd, yd, n, seed=seed, reg_param=reg_param)
         self._state = None
         self._graph_version = None
@@ -441,14 +459,15 @@ class EmbeddingRuntime(EncoderRuntime):
         self._state = None
         self.weights_version += 1
 
-    def train_step_device_negatives(self, graph_edges, batch, rate, reg_param, seed, known=None):
+    def train_step_device_negatives(self, graph_edges, batch, rate, reg_param, seed, known=None, relation_rate=0):
         """The positives are uploaded once and stay resident while the SAME array object is fed (the training set, every
-        iteration); the corruptions are drawn on the device, avoiding `known` if given.  A caller that rewrites the array
-        in place feeds a new one."""
+        iteration); the corruptions are drawn on the device, avoiding `known` if given, `relation_rate` relation
+        corruptions per positive behind them.  A caller that rewrites the array in place feeds a new one."""
         if graph_edges is not None:
             raise ValueError("a graph-less encoder takes no graph_edges")
         nb = len(batch)
-        n = nb * (int(rate) + 1)
+        relation_rate = int(relation_rate)
+        n = nb * (int(rate) + 1 + relation_rate)
         if n == 0:
             raise ValueError("empty decoder batch")
         if n > self._dec_reserved:
@@ -459,7 +478,7 @@ class EmbeddingRuntime(EncoderRuntime):
             self._resident = batch
         xd, yd = self._buffer("X", 12 * n), self._buffer("Y", 4 * n)
         self.engine.negative_sample_device(self._dev["batch"], nb, rate, seed ^ 0x5bd1e995, xd, yd,
-                                           exclusive=self._exclusive(known))
+                                           exclusive=self._exclusive(known), relation_rate=relation_rate)
         self.engine.train_step_device(None, 0, xd, yd, n, seed=seed, reg_param=reg_param)
         self._state = None
         self.weights_version += 1

@@ -31,10 +31,12 @@ from .optimization.optimize import build_hip
 
 def load_dataset(dataset, metric='MRR'):
     """code/train.py:21-47.  Metric 'Accuracy' reads valid_accuracy.txt / test_accuracy.txt instead of valid.txt /
-    test.txt (:32-35).  A metric the reference does not have is refused HERE, at start-up, not at the first
-    early-stopping check thousands of iterations in."""
-    if metric not in ('MRR', 'Accuracy'):
-        raise NotImplementedError("Evaluation.Metric = %r: the reference has 'MRR' and 'Accuracy'" % (metric,))
+    test.txt (:32-35); 'RelationMRR' (this project's: the rank of the gold relation for a pair, Scorer.
+    compute_relation_mrr_scores) reads valid.txt / test.txt as 'MRR' does.  A metric that does not exist is refused HERE,
+    at start-up, not at the first early-stopping check thousands of iterations in."""
+    if metric not in ('MRR', 'Accuracy', 'RelationMRR'):
+        raise NotImplementedError("Evaluation.Metric = %r: the reference has 'MRR' and 'Accuracy', this project adds "
+                                  "'RelationMRR'" % (metric,))
     relations_path = dataset + '/relations.dict'
     entities_path = dataset + '/entities.dict'
     splits = {}
@@ -53,6 +55,21 @@ def exclusive_negative_sampling(general_settings):
     return value == 'Yes'
 
 
+def relation_negative_sample_rate(general_settings):
+    """[General] RelationNegativeSampleRate=m (absent from the reference's settings files; default 0): m further negative
+    rows (s, r', o) per positive, with a relation other than r -- what trains W_relation to tell relations apart for a
+    fixed pair.  A non-negative integer; m > 0 needs two relations."""
+    value = general_settings['RelationNegativeSampleRate'] if 'RelationNegativeSampleRate' in general_settings else 0
+    text = str(value).strip()
+    if isinstance(value, bool) or isinstance(value, float) or not text.isdigit():
+        raise ValueError("General.RelationNegativeSampleRate must be a non-negative integer, not %r" % (value,))
+    rate = int(text)
+    if rate > 0 and 'RelationCount' in general_settings and int(general_settings['RelationCount']) < 2:
+        raise ValueError("General.RelationNegativeSampleRate = %d needs at least two relations, the dataset has %d"
+                         % (rate, int(general_settings['RelationCount'])))
+    return rate
+
+
 def make_transform(train_triplets, general_settings, encoder, device_negatives=False, device_dropout=False,
                    device_sampler=False):
     """The reference's t_func (train.py:201-247): minibatch -> (graph_split, X, Y).
@@ -61,12 +78,18 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
     ns.transform_exclusive, on the device paths through `known=` of the batch objects (the runtime reserves the training
     triples on the device once).
 
+    RelationNegativeSampleRate=m: m relation corruptions per positive follow the entity corruptions, on the host path
+    through the sampler's relation_rate, on the device paths through `relation_rate=` of the batch objects.
+
     Every batch is a function of ONE seed drawn from numpy's global generator when the batch is requested, so
     batches can be built ahead of time by background threads (`t_func.seeded(data, seed)`, used by
     optimization.optimize.HipOptimizer) and still come out in a reproducible order; `t_func(data)` itself
     draws the seed and builds the batch in place, like the reference's function."""
     import threading
-    ns = auxilliaries.NegativeSampler(int(general_settings['NegativeSampleRate']), general_settings['EntityCount'])
+    relation_rate = relation_negative_sample_rate(general_settings)
+    ns = auxilliaries.NegativeSampler(int(general_settings['NegativeSampleRate']), general_settings['EntityCount'],
+                                      relation_rate=relation_rate,
+                                      relation_count=int(general_settings['RelationCount']) if relation_rate else None)
     ns.set_known_positives(train_triplets)
     exclusive = exclusive_negative_sampling(general_settings)
     host_negatives = ns.transform_exclusive if exclusive else ns.transform
@@ -89,7 +112,7 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
             # whole training set.  Device negatives: the array itself is handed on, so that the step finds it resident
             if device_negatives:
                 from .optimization.optimize import DeviceNegatives
-                return DeviceNegatives(None, arr, ns.negative_sample_rate, known=known)
+                return DeviceNegatives(None, arr, ns.negative_sample_rate, known=known, relation_rate=relation_rate)
             return host_negatives(arr, rng)
         if use_sampler and device_sampler and device_dropout:
             # all three draws on the device: the iteration is three seeds, nothing is built on the host or uploaded
@@ -98,7 +121,7 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
             split_size = int(float(general_settings['GraphSplitSize']) * size)
             sample = (train_arr, size, rng.randint(0, 2 ** 31 - 1))
             return DeviceMinibatch(None, split_size, rng.randint(0, 2 ** 31 - 1), ns.negative_sample_rate, sample=sample,
-                                   known=known)
+                                   known=known, relation_rate=relation_rate)
         if use_sampler:
             if not hasattr(local, 'sampler'):
                 local.sampler = _native.NeighborhoodSampler(train_triplets, int(general_settings['EntityCount']))
@@ -111,12 +134,13 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
         if device_dropout:            # both draws (kept edges, corruptions) are made by the device step
             from .optimization.optimize import DeviceMinibatch
             return DeviceMinibatch(graph_batch, split_size, rng.randint(0, 2 ** 31 - 1), ns.negative_sample_rate,
-                                   known=known)
+                                   known=known, relation_rate=relation_rate)
         graph_split_ids = rng.choice(graph_batch_ids, size=split_size, replace=False)
         graph_split = train_triplets[graph_split_ids]
         if device_negatives:          # corruptions are drawn by the device step (optimize.DeviceNegatives)
             from .optimization.optimize import DeviceNegatives
-            return DeviceNegatives(graph_split, graph_batch, ns.negative_sample_rate, known=known)
+            return DeviceNegatives(graph_split, graph_batch, ns.negative_sample_rate, known=known,
+                                   relation_rate=relation_rate)
         t = host_negatives(graph_batch, rng)
         return (graph_split, t[0], t[1])
 
@@ -134,6 +158,30 @@ def report_unresolved_negatives(model):
     if count:
         print("Exclusive negative sampling: %d rows so far had no entity that is not a known positive" % count)
     return count
+
+
+def report_unresolved_relation_negatives(model):
+    """as report_unresolved_negatives, for the relation corruptions: rows every other relation was a known positive for"""
+    count = model.device_negative_relation_unresolved()
+    if count:
+        print("Exclusive relation negative sampling: %d rows so far had no relation that is not a known positive" % count)
+    return count
+
+
+def make_validation_function(scorer, metric, test_triplets, model):
+    """code/train.py:114-128: the early-stopping score is the validation split's filtered MRR (Metric=MRR), its filtered
+    relation MRR (RelationMRR) or its accuracy; the test split's table is printed with every report."""
+    def score_validation_data(validation_data):
+        score_summary = scorer.compute_scores(validation_data, verbose=False).get_summary()
+        lookup_string = (score_summary.mrr_string() if metric in ('MRR', 'RelationMRR')
+                         else score_summary.accuracy_string())               # code/train.py:116-121
+        early_stopping = score_summary.results['Filtered'][lookup_string]
+        score_summary = scorer.compute_scores(test_triplets, verbose=False).get_summary()
+        score_summary.pretty_print()
+        report_unresolved_negatives(model)
+        report_unresolved_relation_negatives(model)
+        return early_stopping
+    return score_validation_data
 
 
 def build_model(settings, train_triplets, entity_count, relation_count):
@@ -251,15 +299,7 @@ def main(argv=None):
     scorer.register_model(model)
     scorer.finalize_frequency_computation(np.concatenate((train_triplets, valid_triplets, test_triplets), axis=0))
 
-    def score_validation_data(validation_data):
-        score_summary = scorer.compute_scores(validation_data, verbose=False).get_summary()
-        lookup_string = (score_summary.mrr_string() if evaluation_settings['Metric'] == 'MRR'
-                         else score_summary.accuracy_string())               # code/train.py:116-121
-        early_stopping = score_summary.results['Filtered'][lookup_string]
-        score_summary = scorer.compute_scores(test_triplets, verbose=False).get_summary()
-        score_summary.pretty_print()
-        report_unresolved_negatives(model)
-        return early_stopping
+    score_validation_data = make_validation_function(scorer, evaluation_settings['Metric'], test_triplets, model)
 
     opp.set_early_stopping_score_function(score_validation_data)
     print(len(train_triplets))

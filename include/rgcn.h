@@ -203,10 +203,16 @@ enum {
                                    entity was a known positive and which therefore kept their first draw (exclusive
                                    sampler, stand-alone and fused; replayed hipGraphs count too).  Every kind,
                                    RGCN_KIND_EMBEDDING included; RGCN_ERR_STATE without an index */
-  RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED = 21 /* int64 [1]: relation rows (rgcn_negative_sample_relation_device with
+  RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED = 21,/* int64 [1]: relation rows (rgcn_negative_sample_relation_device with
                                    exclusive != 0, stand-alone and fused), since the last rgcn_known_positives_reserve, for
                                    which EVERY other relation was a known positive for the pair and which therefore kept
                                    their first draw.  Every kind; RGCN_ERR_STATE without an index */
+  /* the relation-softmax term (rgcn_relation_softmax_device and the fused steps under rgcn_set_relation_softmax), of
+   * the LAST chunk it walked: every kind, RGCN_KIND_EMBEDDING included; RGCN_ERR_STATE before
+   * rgcn_relation_softmax_reserve.  chunk and padded R: rgcn_relation_softmax_plan */
+  RGCN_BUF_RELATION_SOFTMAX_ENERGIES = 22, /* float [chunk, padded R]: E[n, r'] = q_n . W_relation[r']; pad columns zero */
+  RGCN_BUF_RELATION_SOFTMAX_G = 23,        /* float [chunk, padded R]: G[n, r'], the term's gradient w.r.t. E; pad columns zero */
+  RGCN_BUF_RELATION_SOFTMAX_DQ = 24        /* float [chunk, code width]: dq_n = sum over r' of G[n, r'] W_relation[r'] */
 };
 
 /*
@@ -505,6 +511,62 @@ rgcn_status rgcn_negative_sample_relation_device(rgcn_ctx* ctx, const int32_t* b
                                                  int32_t relation_rate, int32_t exclusive, uint64_t seed,
                                                  int32_t* x_out_dev, float* y_out_dev);
 rgcn_status rgcn_set_relation_negatives(rgcn_ctx* ctx, int32_t relation_rate);
+
+/* The softmax-over-relations loss term: for every positive (s_n, r_n, o_n), n < P, the gold relation against ALL the
+ * others at once -- the objective rgcn_rank_relation_device evaluates, which relation corruptions only sample.  Not in
+ * the reference.  With c = the codes the decoder reads ([V, code width]; RGCN_KIND_EMBEDDING: W_emb) and W = rows
+ * [0, RelationCount) of W_relation:
+ *     q_n      = c[s_n] * c[o_n]                 elementwise, rounded once (the query row of rgcn_rank_relation_device)
+ *     E[n,r']  = q_n . W[r']
+ *     ell_n    = log sum_{r' in C_n} exp(E[n,r']) - E[n,r_n]            (the row maximum over C_n is subtracted)
+ *     term     = weight / P * sum_n ell_n
+ *     G[n,r']  = weight / P * (softmax over C_n of E[n,:] at r' - [r' = r_n]),  0 outside C_n
+ *     dL/dW_relation[r'] += sum_n G[n,r'] q_n
+ *     dq_n = sum_r' G[n,r'] W[r'];   dL/dcodes[s_n] += dq_n * c[o_n];   dL/dcodes[o_n] += dq_n * c[s_n]
+ * (both on the same row when s_n = o_n).  C_n is every relation; with exclusive != 0 it is {r_n} and every r' for which
+ * (s_n, r', o_n) is NOT in the set K of rgcn_known_positives_reserve: a relation that is a known fact for the pair is
+ * neither a competitor nor a gradient target.  A row with C_n = {r_n} contributes exactly 0.  The regulariser does not
+ * change.  Every sum has a fixed order (no atomics on floats): two calls return the same bytes.
+ *
+ * rgcn_relation_softmax_reserve(max_positives) sizes the term's buffers: query rows, their gradients and the energies of
+ * ONE chunk of positives (rgcn_relation_softmax_plan: min(max_positives, 65536, what a 64 MB energy buffer holds)); longer
+ * inputs are walked chunk by chunk, which is exact up to summation order.  max_positives <= 0 or above
+ * RGCN_MAX_DECODER_TRIPLES, and RelationCount < 2: RGCN_ERR_INVALID; EntityCount >= 2^24: RGCN_ERR_UNSUPPORTED;
+ * RGCN_ERR_STATE during a capture (it synchronises).
+ *
+ * rgcn_relation_softmax_device(positives_dev int32 [P,3], P, weight, exclusive): stand-alone.  Adds the term to the loss
+ * (rgcn_get_loss) and to the gradients (rgcn_dcodes_device, W_relation's gradient) that the last
+ * rgcn_decoder_loss_backward_device left; RGCN_ERR_STATE without one, before rgcn_relation_softmax_reserve, during a
+ * capture, and with exclusive != 0 without an index.  weight negative or not finite, P <= 0, NULL positives,
+ * RelationCount < 2: RGCN_ERR_INVALID; weight == 0: nothing is launched.  world > 1: RGCN_ERR_UNSUPPORTED.  Ids are
+ * validated on the device: a positive with an id out of range fails the next synchronising call (rgcn_get_loss,
+ * rgcn_sync) with RGCN_ERR_INVALID, nothing is read out of bounds, and the context stays usable.  Asynchronous on the
+ * main stream.
+ *
+ * rgcn_set_relation_softmax(weight, num_positives, exclusive): the term inside the fused steps.  Under weight > 0
+ *   - rgcn_train_step_minibatch_device takes its num_edges batch rows as the positives;
+ *   - rgcn_train_step_device takes the first num_positives rows of its X, whose labels must be 1 (checked on the device:
+ *     RGCN_ERR_INVALID at the next synchronising call); num_positives == 0 means "the minibatch step only" and such a
+ *     step returns RGCN_ERR_STATE; num_positives above the step's N: RGCN_ERR_INVALID;
+ *   - the steps need rgcn_relation_softmax_reserve (RGCN_ERR_STATE), return RGCN_ERR_UNSUPPORTED on a context with
+ *     world > 1 and RGCN_ERR_STATE during a capture;
+ *   - the top layer's dropout-scaled operand is formed by the backward pass from the complete dL/dcodes, not by the
+ *     decoder's entity-gradient kernel.
+ * weight == 0 (the default) restores every byte the steps produced before these entry points existed.  weight negative
+ * or not finite, num_positives < 0, and weight > 0 with RelationCount < 2: RGCN_ERR_INVALID; weight > 0 during a capture,
+ * and exclusive != 0 without an index: RGCN_ERR_STATE.
+ *
+ * rgcn_relation_softmax_plan: the term's host-side decisions as a context with these sizes runs them, context-free.
+ * out[0] = chunk, out[1] = padded R (R up to a multiple of 4: the leading dimension of
+ * RGCN_BUF_RELATION_SOFTMAX_ENERGIES / _G), out[2] = the split over the positives of the relation gradient's product at
+ * a full chunk (its split-K slabs are the term's own, at most 2^23 floats), out[3] = the long-row cut of the entity side
+ * (entity rows with more incidences in a chunk are summed in pieces), out[4] = the incidences per piece.  A non-positive
+ * argument or NULL out: RGCN_ERR_INVALID. */
+rgcn_status rgcn_relation_softmax_reserve(rgcn_ctx* ctx, int64_t max_positives);
+rgcn_status rgcn_relation_softmax_device(rgcn_ctx* ctx, const int32_t* positives_dev, int64_t num_positives, float weight,
+                                         int32_t exclusive);
+rgcn_status rgcn_set_relation_softmax(rgcn_ctx* ctx, float weight, int64_t num_positives, int32_t exclusive);
+rgcn_status rgcn_relation_softmax_plan(int64_t max_positives, int32_t num_relations, int32_t code_dim, int64_t out[5]);
 
 /* ---- evaluation: raw and filtered link-prediction ranks -------------------------------
  * Replaces Model.score_all_subjects / score_all_objects + Scorer.evaluate_mrr + MrrScore.append_line

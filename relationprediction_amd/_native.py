@@ -31,6 +31,9 @@ BUF_RELATION_ENERGIES = 18   # [reserved queries, R], the energies of the chunk 
 BUF_OUT_DH = 19              # contexts with an output transform: [V, d], dL/dH_L of the last backward pass
 BUF_NEGATIVE_UNRESOLVED = 20 # int64 [1]: negative rows every entity was a known positive for, since the reserve
 BUF_NEGATIVE_RELATION_UNRESOLVED = 21  # int64 [1]: relation rows every other relation was a known positive for
+BUF_RELATION_SOFTMAX_ENERGIES = 22  # [chunk, padded R]: the energies of the chunk the relation-softmax term walked last
+BUF_RELATION_SOFTMAX_G = 23         # [chunk, padded R]: their gradients
+BUF_RELATION_SOFTMAX_DQ = 24        # [chunk, code width]: the gradients of that chunk's query rows
 KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS, "basis_tdiag": KIND_BASIS_TDIAG,
          "basis_pdiag": KIND_BASIS_PDIAG, "embedding": KIND_EMBEDDING}
 NORMS = {"intended": NORM_INTENDED, "tf_as_executed": NORM_TF_AS_EXECUTED, "none": NORM_NONE, "local": NORM_LOCAL}
@@ -130,6 +133,10 @@ _SIGS = {
     "rgcn_negative_sample_relation_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint64,
                                                          _P, _P]),
     "rgcn_set_relation_negatives": (C.c_int32, [_P, C.c_int32]),
+    "rgcn_relation_softmax_reserve": (C.c_int32, [_P, C.c_int64]),
+    "rgcn_relation_softmax_device": (C.c_int32, [_P, _P, C.c_int64, C.c_float, C.c_int32]),
+    "rgcn_set_relation_softmax": (C.c_int32, [_P, C.c_float, C.c_int64, C.c_int32]),
+    "rgcn_relation_softmax_plan": (C.c_int32, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "rgcn_rank_reserve": (C.c_int32, [_P, C.c_int64]),
     "rgcn_rank_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
     "rgcn_rank_energies_device": (_P, [_P]),
@@ -227,6 +234,19 @@ class DebugGemmPlan(C.Structure):
         out["kernel"] = GEMM_KERNEL_NAMES[out["kernel"]]
         return out
 _lib_devtools = None
+
+
+def relation_softmax_plan(max_positives, num_relations, code_dim):
+    """rgcn_relation_softmax_plan: how a context of these sizes cuts the relation-softmax term's work (context-free, no
+    GPU): the chunk of positives, the padded relation count, the split of the relation gradient's product, the entity side's
+    long-row cut and piece"""
+    lib = load_library()
+    out = (C.c_int64 * 5)()
+    st = lib.rgcn_relation_softmax_plan(int(max_positives), int(num_relations), int(code_dim), out)
+    if st != 0:
+        raise RgcnError(st, "rgcn_relation_softmax_plan: arguments must be positive")
+    return {"chunk": int(out[0]), "padded_r": int(out[1]), "split_k": int(out[2]), "long_row": int(out[3]),
+            "piece": int(out[4])}
 
 
 def exported_symbols():
@@ -621,6 +641,26 @@ class Engine:
         """relation rows per batch edge the negative sampling inside train_step_minibatch_device appends (0: none)"""
         self._check(self.lib.rgcn_set_relation_negatives(self.ctx, int(relation_rate)))
 
+    def relation_softmax_reserve(self, max_positives):
+        """size the relation-softmax term's buffers (rgcn_relation_softmax_reserve): one chunk of positives"""
+        self._check(self.lib.rgcn_relation_softmax_reserve(self.ctx, int(max_positives)))
+        # (a smaller request leaves the buffers as they are: the plan is that of the largest one)
+        self._relsm_reserved = max(getattr(self, "_relsm_reserved", 0), int(max_positives))
+        self._relsm_plan = relation_softmax_plan(self._relsm_reserved, self.R, self._code_width)
+
+    def relation_softmax_device(self, positives_dev, num_positives, weight, exclusive=False):
+        """add weight / P * sum_n [logsumexp over the relations of E[n, :] - E[n, r_n]] and its gradients to what the last
+        decoder_loss_backward_device left (rgcn_relation_softmax_device); exclusive: relations known for the pair
+        (known_positives_reserve) leave the candidate set"""
+        self._check(self.lib.rgcn_relation_softmax_device(self.ctx, positives_dev.ptr, int(num_positives),
+                                                         C.c_float(weight), 1 if exclusive else 0))
+
+    def set_relation_softmax(self, weight, num_positives=0, exclusive=False):
+        """the relation-softmax term inside the fused steps (rgcn_set_relation_softmax): train_step_minibatch_device takes
+        its batch rows as the positives, train_step_device the first num_positives rows of X; weight 0 switches it off"""
+        self._check(self.lib.rgcn_set_relation_softmax(self.ctx, C.c_float(weight), int(num_positives),
+                                                      1 if exclusive else 0))
+
     def negative_relation_unresolved(self):
         """relation rows, since the reserve, for which every other relation was a known positive (they kept their first
         draw)"""
@@ -950,6 +990,10 @@ class Engine:
             out = np.empty((getattr(self, "_rank_reserved", 0), self.V), dtype=np.float32)
         elif which == BUF_RELATION_ENERGIES:
             out = np.empty((getattr(self, "_rank_reserved", 0), self.R), dtype=np.float32)
+        elif which in (BUF_RELATION_SOFTMAX_ENERGIES, BUF_RELATION_SOFTMAX_G, BUF_RELATION_SOFTMAX_DQ):
+            plan = getattr(self, "_relsm_plan", {"chunk": 0, "padded_r": 0})
+            cols = self._code_width if which == BUF_RELATION_SOFTMAX_DQ else plan["padded_r"]
+            out = np.empty((plan["chunk"], cols), dtype=np.float32)
         elif which == BUF_DSELF_EXCHANGE:
             out = np.empty((self.d, self.d), dtype=np.float32)
         elif which == BUF_NORM_EXCHANGE:

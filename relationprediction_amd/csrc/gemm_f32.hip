@@ -351,7 +351,7 @@ rgcn_status gemm_run(rgcn_ctx* c, const char* tag, const GemmCall& q, const Gemm
   if (p.refused) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, p.refused);
   if (p.kernel == GEMM_NONE) return RGCN_OK;
   const int M = q.M, N = q.N, K = q.K, groups = q.batch.groups;
-  if (p.slabs && (size_t)groups * p.splits * M * N > c->slab_floats) RGCN_FAIL(c, RGCN_ERR_STATE, "internal: split-K slab too small");
+  if (p.slabs && (size_t)groups * p.splits * M * N > (q.slab_floats ? q.slab_floats : c->slab_floats)) RGCN_FAIL(c, RGCN_ERR_STATE, "internal: split-K slab too small");
   gx::XArgs g;
   g.A = q.A; g.B = q.B; g.zeros = c->zeros;
   g.M = M; g.N = N; g.K = K; g.lda = q.lda; g.ldb = q.ldb;

@@ -58,6 +58,7 @@ struct GemmCall {
   int split_k = 1;
   float* slab = nullptr;      // the context's split-K slabs: their alignment decides vecC where slabs are used
   GemmBatch batch;
+  size_t slab_floats = 0;     // capacity of `slab` in floats where it is the caller's own; 0: the context's slabs
 };
 
 enum GemmKernel {

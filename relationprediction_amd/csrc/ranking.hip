@@ -45,6 +45,7 @@
 // with W_relation instead of the codes -- the same NT GEMM, N = R -- into ranking.rel, a [reserved queries, R] buffer of
 // its own (ranking.s is never touched), and the tails run k_rank_threshold / k_rank_rows / k_topk_rows as they stand,
 // with R where the entity side passes V: candidate count, row stride, range of the list entries, bits of the mask.
+#include "pair_query.h"
 #include "rgcn_internal.h"
 
 namespace rgcn {
@@ -81,13 +82,9 @@ __global__ void k_rank_pair(const float* __restrict__ codes, const int32_t* __re
                             float* __restrict__ P, int V) {
   const int row = blockIdx.x;
   if (row >= n) return;
-  int s = X[3 * row], o = X[3 * row + 2];
-  // (as in k_rank_query: a bad id fails the call at the end and must not fault before)
-  if ((unsigned)s >= (unsigned)V) s = 0;
-  if ((unsigned)o >= (unsigned)V) o = 0;
-  const float* a = codes + (size_t)s * d;
-  const float* b = codes + (size_t)o * d;
-  for (int k = threadIdx.x; k < d; k += blockDim.x) P[(size_t)row * d + k] = a[k] * b[k];
+  // (as in k_rank_query: a bad id fails the call at the end and must not fault before; pair_query.h holds the arithmetic,
+  // shared with the relation-softmax term)
+  pair_query_row(codes, X, row, d, P, V);
 }
 
 // floats in their numeric order as unsigned integers (and back)

@@ -222,6 +222,7 @@ static rgcn_status check_dev_flag(rgcn_ctx* c, bool main_only = false) {
                                                "(a graph of very large diameter: use the host sampler); " : "") +
                                    (flag & 32 ? "device neighbourhood sampler: the compacted batch does not hold the requested number "
                                                 "of edges (internal error: two draws sharing the sampler's state?); " : "") +
+                                   (flag & 64 ? "relation softmax: a row taken as a positive does not carry the label 1; " : "") +
                                    (flag & 16 ? "the decoder batch is no longer the tiled batch rgcn_negative_sample_device wrote into that "
                                                 "buffer (rewritten by the caller's own kernels?): pass it in another buffer; " : "") +
                                    (flag & 3 ? "graph_edges / the decoder batch contains a vertex id outside [0,EntityCount) or a "
@@ -318,6 +319,7 @@ static void free_all(rgcn_ctx* c) {
   neighborhood_free(c);
   known_positives_free(c);
   optimizer_free(c);
+  relation_softmax_free(c);
   rank_free(c);
   c->pool.release();
   for (ProfRec& r : c->prof) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
@@ -1103,6 +1105,67 @@ rgcn_status rgcn_set_relation_negatives(rgcn_ctx* c, int32_t relation_rate) {
   return RGCN_OK;
 }
 
+// ---- the relation-softmax term: reserve, the stand-alone call, the mode of the fused steps, the host plan
+rgcn_status rgcn_relation_softmax_reserve(rgcn_ctx* c, int64_t max_positives) {
+  RGCN_NEED(c);
+  if (max_positives <= 0 || max_positives > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "max_positives out of range");
+  if (c->R < 2) RGCN_FAIL(c, RGCN_ERR_INVALID, "the relation softmax needs at least two relations");
+  if (c->V >= (1 << 24)) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "relation softmax: 2^24 entities or more");
+  RGCN_TRY(sync_all(c));
+  return relation_softmax_reserve(c, max_positives);
+}
+
+static bool relsm_weight_ok(float w) { return w >= 0.f && w <= 3.0e38f; }      // (false for NaN and for infinity)
+
+rgcn_status rgcn_relation_softmax_device(rgcn_ctx* c, const int32_t* pos_dev, int64_t P, float weight, int32_t exclusive) {
+  RGCN_NEED(c);
+  if (!pos_dev || P <= 0 || P > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "bad positives");
+  if (!relsm_weight_ok(weight)) RGCN_FAIL(c, RGCN_ERR_INVALID, "the weight must be finite and not negative");
+  if (c->R < 2) RGCN_FAIL(c, RGCN_ERR_INVALID, "the relation softmax needs at least two relations");
+  if (c->world > 1) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "the relation softmax on a relation-sharded context (world > 1)");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
+  if (!c->dec.loss_valid || !c->fwd_done)
+    RGCN_FAIL(c, RGCN_ERR_STATE, "the term is added to a decoder pass: call rgcn_decoder_loss_backward_device first");
+  if (c->relsm.maxP <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_relation_softmax_reserve first");
+  if (exclusive && c->known.count <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_known_positives_reserve first");
+  if (weight == 0.f) return RGCN_OK;
+  RGCN_TRY(stream_join(c, 2));
+  c->relsm.csr_X = nullptr;      // (a CSR a fused step prepared and never used is not this call's)
+  RGCN_TRY(relation_softmax_compute(c, c->embedding ? c->H[0] : c->codes, pos_dev, nullptr, P, weight, exclusive != 0));
+  return stream_join(c, 2);      // the last chunk's relation gradient ran on its own side stream
+}
+
+rgcn_status rgcn_set_relation_softmax(rgcn_ctx* c, float weight, int64_t num_positives, int32_t exclusive) {
+  RGCN_NEED(c);
+  if (!relsm_weight_ok(weight)) RGCN_FAIL(c, RGCN_ERR_INVALID, "the weight must be finite and not negative");
+  if (num_positives < 0 || num_positives > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "num_positives out of range");
+  if (weight > 0.f) {
+    if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
+    if (c->R < 2) RGCN_FAIL(c, RGCN_ERR_INVALID, "the relation softmax needs at least two relations");
+    if (exclusive && c->known.count <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_known_positives_reserve first");
+  }
+  c->relsm.weight = weight;
+  c->relsm.step_positives = num_positives;
+  c->relsm.exclusive = exclusive != 0;
+  return RGCN_OK;
+}
+
+rgcn_status rgcn_relation_softmax_plan(int64_t max_positives, int32_t num_relations, int32_t code_dim, int64_t out[5]) {
+  if (!out || max_positives <= 0 || num_relations <= 0 || code_dim <= 0) return RGCN_ERR_INVALID;
+  const RelsmPlan p = relsm_plan(max_positives, num_relations, code_dim, kRelsmSlabFloats);      // what a context runs
+  out[0] = p.chunk; out[1] = p.padded_r; out[2] = p.split_k; out[3] = kRelsmLongRow; out[4] = kRelsmPiece;
+  return RGCN_OK;
+}
+
+// what a fused step checks before it queues anything while the term is on (rgcn_set_relation_softmax, weight > 0)
+static rgcn_status relsm_step_check(rgcn_ctx* c) {
+  if (c->world > 1) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "the relation softmax in the step of a relation-sharded context (world > 1)");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "the relation softmax is not built for a hipGraph capture");
+  if (c->relsm.maxP <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_relation_softmax_reserve first");
+  if (c->relsm.exclusive && c->known.count <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_known_positives_reserve first");
+  return RGCN_OK;
+}
+
 rgcn_status rgcn_rank_reserve(rgcn_ctx* c, int64_t max_queries) {
   RGCN_NEED(c);
   if (max_queries <= 0) RGCN_FAIL(c, RGCN_ERR_INVALID, "max_queries must be positive");
@@ -1347,8 +1410,9 @@ rgcn_status rgcn_optimizer_apply(rgcn_ctx* c) { RGCN_NEED(c); return optimizer_a
 
 // everything of a train step behind the graph preparation: encoder forward, decoder loss + gradients, encoder
 // backward, clip + Adam
+// n_pos > 0: the leading n_pos rows of X are the positives of the relation-softmax term (one GPU; relsm_step_check)
 static rgcn_status train_step_tail(rgcn_ctx* c, const int32_t* X_dev, const float* Y_dev, int64_t N, uint64_t seed,
-                                   float reg_param) {
+                                   float reg_param, int64_t n_pos = 0) {
   RGCN_TRY(forward_all(c, 1, seed, nullptr));
   // Relation-sharded run: the decoder is divided by TRIPLES -- rank g takes the slice [g ceil(N / world), ...) of the
   // batch (the codes are replicated after the last forward exchange), its loss terms and gradients are normalised by
@@ -1370,11 +1434,14 @@ static rgcn_status train_step_tail(rgcn_ctx* c, const int32_t* X_dev, const floa
     RGCN_HIP(c, hipStreamWaitEvent(c->aux[1], c->ev_step_begin, 0));
     c->stream = c->aux[1];
     c->aux_dirty[1] = true;
-    const rgcn_status ps = decoder_prepare(c, X_loc, n_loc, N);
+    rgcn_status ps = decoder_prepare(c, X_loc, n_loc, N);
+    // (the relation-softmax term's CSR depends on X only too: beside the decoder's)
+    if (ps == RGCN_OK && n_pos > 0) ps = relation_softmax_prepare(c, X_dev, n_pos);
     c->stream = c->main_stream;
     RGCN_TRY(ps);
   } else {
     RGCN_TRY(decoder_prepare(c, X_loc, n_loc, N));
+    if (n_pos > 0) RGCN_TRY(relation_softmax_prepare(c, X_dev, n_pos));
   }
   RGCN_TRY(stream_join(c, 1));
   // one GPU: the decoder's entity-gradient kernel also writes dL/dcodes * dropout_L, the operand of the top layer's
@@ -1382,8 +1449,15 @@ static rgcn_status train_step_tail(rgcn_ctx* c, const int32_t* X_dev, const floa
   const DropSpec top_drop = make_drop(c, c->L, true);
   // (a highway context forms dS_L itself, from G_L T_L: bwd_layer_partial; under an output transform the top layer's D is
   // dcodes . W_out^T, which bwd_begin forms and scales: a dropout copy of the [V,dc] dcodes is of no use)
-  float* ds_ready = (c->world == 1 && !c->highway && !c->out_layer && top_drop.mode != DROP_NONE) ? c->dsbuf[c->L & 1] : nullptr;
+  // (with the relation-softmax term on, dL/dcodes is complete only behind the term: bwd_begin scales it)
+  float* ds_ready = (c->world == 1 && !c->highway && !c->out_layer && top_drop.mode != DROP_NONE && n_pos <= 0)
+                        ? c->dsbuf[c->L & 1] : nullptr;
   RGCN_TRY(decoder_compute(c, c->codes, Y_loc, reg_param, ds_ready, &top_drop));
+  if (n_pos > 0) {
+    // the term adds to what the decoder left, W_relation's gradient on side stream 2 included: join it first
+    RGCN_TRY(stream_join(c, 2));
+    RGCN_TRY(relation_softmax_compute(c, c->codes, X_dev, Y_dev, n_pos, c->relsm.weight, c->relsm.exclusive));
+  }
   if (c->world > 1) {
     RGCN_TRY(stream_join(c, 2));    // the relation gradient's reduce ran on its own side stream: it is all-reduced too
     RGCN_TRY(decoder_allreduce(c));
@@ -1440,9 +1514,18 @@ rgcn_status rgcn_train_step_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t 
     RGCN_FAIL(c, RGCN_ERR_INVALID, "an RGCN_KIND_EMBEDDING context takes no graph: pass NULL triples and num_edges 0");
   if (E < 0 || E > c->cfg.max_edges) RGCN_FAIL(c, RGCN_ERR_INVALID, "num_edges outside [0, max_edges]");
   if (!X_dev || !Y_dev || N <= 0) RGCN_FAIL(c, RGCN_ERR_INVALID, "bad decoder batch");
+  // (the term's refusals first: a sharded context is refused whether or not it has its communicator yet)
+  if (c->relsm.weight > 0.f) RGCN_TRY(relsm_step_check(c));
   if (c->world > 1 && !c->comm)
     RGCN_FAIL(c, RGCN_ERR_STATE, "world > 1: call rgcn_comm_init first (or drive the phase API yourself)");
   if (c->dec.maxN < N) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_decoder_reserve(ctx, max_triples) first");
+  int64_t n_pos = 0;
+  if (c->relsm.weight > 0.f) {
+    if (c->relsm.step_positives <= 0)
+      RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_set_relation_softmax was given num_positives = 0: the minibatch step only");
+    if (c->relsm.step_positives > N) RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_set_relation_softmax: num_positives above the batch's rows");
+    n_pos = c->relsm.step_positives;
+  }
   if (c->embedding) {
     // the DistMult baseline's step: decoder loss + gradients on the table itself (dL/dcodes is written into W_emb's
     // gradient), then clip + Adam.  One chain on the main stream but for the relation gradient's side stream.
@@ -1450,12 +1533,17 @@ rgcn_status rgcn_train_step_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t 
     RGCN_TRY(decoder_prepare(c, X_dev, N));
     RGCN_TRY(decoder_compute(c, c->H[0], Y_dev, reg_param));
     RGCN_TRY(stream_join(c, 2));
+    if (n_pos > 0) {
+      c->relsm.csr_X = nullptr;
+      RGCN_TRY(relation_softmax_compute(c, c->H[0], X_dev, Y_dev, n_pos, c->relsm.weight, c->relsm.exclusive));
+    }
+    RGCN_TRY(stream_join(c, 2));
     c->dec.loss_valid = true;
     if (c->opt.configured) RGCN_TRY(optimizer_step(c));
     return RGCN_OK;
   }
   RGCN_TRY(step_begin(c, tri_dev, E, true));
-  return train_step_tail(c, X_dev, Y_dev, N, seed, reg_param);
+  return train_step_tail(c, X_dev, Y_dev, N, seed, reg_param, n_pos);
 }
 
 rgcn_status rgcn_prefetch_graph_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t E) {
@@ -1505,6 +1593,8 @@ rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* c, const int32_t* batch_d
     RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
   const int32_t relation_rate = c->relation_negatives;      // rgcn_set_relation_negatives; 0: the step as it always was
   const int64_t N = n * (int64_t)(negative_rate + 1 + relation_rate);
+  const bool relsm_on = c->relsm.weight > 0.f;      // rgcn_set_relation_softmax; off: the step as it always was
+  if (relsm_on) RGCN_TRY(relsm_step_check(c));      // (ahead of the communicator's check, as in rgcn_train_step_device)
   if (c->world > 1 && !c->comm)
     RGCN_FAIL(c, RGCN_ERR_STATE, "world > 1: call rgcn_comm_init first (or drive the phase API yourself)");
   if (c->dec.maxN < N) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_decoder_reserve(ctx, max_triples) first");
@@ -1528,7 +1618,7 @@ rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* c, const int32_t* batch_d
     RGCN_TRY(negative_sample(c, batch_dev, n, negative_rate, negative_seed, x_scratch_dev, y_scratch_dev));
   // the decoder's batch preparation forks from ev_step_begin onto a side stream: it must see the sampled batch
   RGCN_HIP(c, hipEventRecord(c->ev_step_begin, c->main_stream));
-  return train_step_tail(c, x_scratch_dev, y_scratch_dev, N, dropout_seed, reg_param);
+  return train_step_tail(c, x_scratch_dev, y_scratch_dev, N, dropout_seed, reg_param, relsm_on ? n : 0);
 }
 
 // ---- neighbourhood edge sampler on the device ------------------------------------------
@@ -1759,7 +1849,8 @@ static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* byte
   const int64_t Vd = (int64_t)c->V * c->d * 4;
   if (c->embedding && which != RGCN_BUF_RANK_ENERGIES && which != RGCN_BUF_RANK_MIXED_SCORES &&
       which != RGCN_BUF_RELATION_ENERGIES && which != RGCN_BUF_NEGATIVE_UNRESOLVED &&
-      which != RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED)
+      which != RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED && which != RGCN_BUF_RELATION_SOFTMAX_ENERGIES &&
+      which != RGCN_BUF_RELATION_SOFTMAX_G && which != RGCN_BUF_RELATION_SOFTMAX_DQ)
     RGCN_FAIL(c, RGCN_ERR_STATE, "an RGCN_KIND_EMBEDDING context has the ranking buffers only (no graph, no layer buffers)");
   switch (which) {
     case RGCN_BUF_NEGATIVE_UNRESOLVED:
@@ -1768,6 +1859,16 @@ static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* byte
     case RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED:
       if (c->known.count <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "no known positives (rgcn_known_positives_reserve first)");
       *p = c->known.relation_unresolved; *bytes = 8; return RGCN_OK;
+    case RGCN_BUF_RELATION_SOFTMAX_ENERGIES:
+    case RGCN_BUF_RELATION_SOFTMAX_G:
+    case RGCN_BUF_RELATION_SOFTMAX_DQ:
+      if (c->relsm.maxP <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "no relation-softmax buffers (rgcn_relation_softmax_reserve first)");
+      if (which == RGCN_BUF_RELATION_SOFTMAX_DQ) { *p = c->relsm.dQ; *bytes = c->relsm.plan.chunk * c->dc * 4; }
+      else {
+        *p = which == RGCN_BUF_RELATION_SOFTMAX_G ? c->relsm.G : c->relsm.E;
+        *bytes = c->relsm.plan.chunk * c->relsm.plan.padded_r * 4;
+      }
+      return RGCN_OK;
     case RGCN_BUF_EXCHANGE:
       if (!c->exch) RGCN_FAIL(c, RGCN_ERR_STATE, "no exchange buffer on a world == 1 context");
       *p = c->exch; *bytes = Vd; return RGCN_OK;

@@ -16,6 +16,7 @@
 #include "dev_pool.h"
 #include "gemm_plan.h"
 #include "negative_exclusive.h"
+#include "relation_softmax_plan.h"
 
 namespace rgcn {
 
@@ -332,6 +333,37 @@ struct KnownPositives {
   bool exclusive = false;                  // rgcn_set_exclusive_negatives: the fused minibatch step draws exclusively
 };
 
+// the relation-softmax term (csrc/relation_softmax.hip; rgcn_relation_softmax_reserve): buffers of ONE chunk of positives
+struct RelsmBufs {
+  DevPool pool;
+  int64_t maxP = 0;                       // what the reserve was asked for
+  RelsmPlan plan;                         // chunk, padded R, split (relation_softmax_plan.h)
+  float *Q = nullptr, *dQ = nullptr;      // [chunk, dc] query rows codes[s] * codes[o] and their gradients
+  float *E = nullptr, *G = nullptr;       // [chunk, padded R] each: the energies, and their gradients (the row pass reads
+                                          // one and writes the other, so both stay readable); pad columns stay zero
+  float* Wp = nullptr;                    // [padded R, dc] rows [0, R) of W_relation, pad rows zero (copied every call)
+  float* dW = nullptr;                    // [padded R, dc] G^T Q of the chunk
+  float* loss_part = nullptr;             // one partial per workgroup of the row pass
+  float* slab = nullptr;                  // split-K slabs of dW = G^T Q (GemmCall::slab), plan.split_k x [padded R, dc]
+  size_t slab_floats = 0;
+  // by-entity CSR of the chunk's 2n incidences (subject side first), built with the library's stable sort
+  uint32_t *key = nullptr, *key_s = nullptr, *key_t = nullptr;
+  int32_t *perm = nullptr, *val_t = nullptr;
+  uint16_t* table = nullptr;
+  int32_t *row_ptr = nullptr, *e_other = nullptr, *e_trip = nullptr;
+  int32_t *long_rows = nullptr, *long_first = nullptr, *long_cnt = nullptr, *nlong = nullptr;   // nlong[0] rows, [1] pieces
+  int32_t *piece_row = nullptr, *piece_k = nullptr;
+  float* piece_slab = nullptr;            // [piece_cap][dc]
+  int32_t long_cap = 0, piece_cap = 0;
+  const int32_t* csr_X = nullptr;         // relation_softmax_prepare built the CSR of these positives' first csr_n rows
+  int csr_n = 0;                          // (consumed, or rebuilt, by the next relation_softmax_compute)
+  int64_t last_n = 0;                     // positives of the chunk the buffers hold (RGCN_BUF_RELATION_SOFTMAX_*); 0: none
+  // rgcn_set_relation_softmax: the term inside the fused steps
+  float weight = 0.f;
+  int64_t step_positives = 0;             // leading rows of an X/Y step's batch; 0: the minibatch step only
+  bool exclusive = false;
+};
+
 struct OptimizerState {
   DevPool pool;              // moments, state, shard_sq
   DevPool part_pool;         // `part` alone: it is the one buffer that grows
@@ -449,6 +481,7 @@ struct rgcn_ctx {
   rgcn::NeighborhoodBufs nbr;
   rgcn::KnownPositives known;
   int32_t relation_negatives = 0;        // rgcn_set_relation_negatives: relation rows per positive in the fused minibatch step
+  rgcn::RelsmBufs relsm;
   rgcn::OptimizerState opt;
 
   std::vector<float*> H;                 // H[0..L], [V,d] each
@@ -801,6 +834,17 @@ rgcn_status topk_relation_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, 
                                   const int32_t* excl_idx, int32_t* idx_out, float* energy_out);
 rgcn_status score_relation_queries_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N);
 void optimizer_free(rgcn_ctx* c);
+// ---- relation_softmax.hip: the softmax-over-relations loss term of the positives (s, r, o) of a step
+rgcn_status relation_softmax_reserve(rgcn_ctx* c, int64_t max_positives);
+void relation_softmax_free(rgcn_ctx* c);
+// adds weight / P * sum_n ell_n to dec.loss and its gradients to dcodes_own and to W_relation's gradient, on the current
+// stream, which must be behind the decoder's kernels on every stream; the last chunk's relation gradient is left on side
+// stream 2 (stream_join(c, 2) before anything reads W_relation's gradient or calls this again).  Y_dev (optional): the labels of the rows, which
+// must all be 1 (error flag 64).  exclusive: relations known for the pair leave the candidate set (c->known)
+// the by-entity CSR of the first chunk of these positives, on the current stream (depends on X only)
+rgcn_status relation_softmax_prepare(rgcn_ctx* c, const int32_t* pos_dev, int64_t P);
+rgcn_status relation_softmax_compute(rgcn_ctx* c, const float* codes, const int32_t* pos_dev, const float* Y_dev, int64_t P,
+                                     float weight, bool exclusive);
 
 // ---- comm.cpp (RCCL via dlopen)
 rgcn_status comm_unique_id(uint8_t id[128]);

@@ -20,12 +20,68 @@ def _sigmoid(x):
     return np.where(x >= 0, 1.0 / (1.0 + e), e / (1.0 + e)).astype(np.float32)
 
 
+def parse_relation_softmax_weight(settings):
+    """[Decoder] RelationSoftmaxWeight=lambda (not in the reference; absent: 0): the weight of the softmax-over-relations
+    loss term of the positives (include/rgcn.h, rgcn_relation_softmax_device).  A non-negative finite float."""
+    if 'RelationSoftmaxWeight' not in settings:
+        return 0.0
+    value = settings['RelationSoftmaxWeight']
+    try:
+        if isinstance(value, bool):
+            raise ValueError
+        weight = float(str(value).strip())
+    except ValueError:
+        raise ValueError("Decoder.RelationSoftmaxWeight must be a non-negative number, not %r" % (value,))
+    if not np.isfinite(weight) or weight < 0:
+        raise ValueError("Decoder.RelationSoftmaxWeight must be a non-negative finite number, not %r" % (value,))
+    return weight
+
+
+def relation_softmax_terms(codes, relation_codes, positives, relation_count, weight):
+    """The unmasked term evaluated eagerly in float64: (term, dcodes [V,dc], d_rel [rows of relation_codes, dc])."""
+    pos = np.asarray(positives, dtype=np.int64).reshape(-1, 3)
+    c = np.asarray(codes, dtype=np.float64)
+    W = np.asarray(relation_codes, dtype=np.float64)
+    P = len(pos)
+    dcodes, d_rel = np.zeros_like(c), np.zeros_like(W)
+    if P == 0 or weight == 0:
+        return 0.0, dcodes, d_rel
+    q = (np.asarray(codes, dtype=np.float32)[pos[:, 0]] * np.asarray(codes, dtype=np.float32)[pos[:, 2]]).astype(np.float64)
+    E = q @ W[:relation_count].T
+    m = E.max(axis=1, keepdims=True)
+    ex = np.exp(E - m)
+    ssum = ex.sum(axis=1, keepdims=True)
+    ell = np.log(ssum[:, 0]) + m[:, 0] - E[np.arange(P), pos[:, 1]]
+    G = ex / ssum
+    G[np.arange(P), pos[:, 1]] -= 1.0
+    G *= weight / P
+    d_rel[:relation_count] = G.T @ q
+    dq = G @ W[:relation_count]
+    np.add.at(dcodes, pos[:, 0], dq * c[pos[:, 2]])
+    np.add.at(dcodes, pos[:, 2], dq * c[pos[:, 0]])
+    return weight / P * float(ell.sum()), dcodes, d_rel
+
+
 class BilinearDiag(Model):
     X = None
     Y = None
+    relation_softmax_known = None      # the known positives the term's mask reads (ExclusiveNegativeSampling=Yes)
 
     def parse_settings(self):
         self.regularization_parameter = float(self.settings['RegularizationParameter'])
+        self.relation_softmax_weight = parse_relation_softmax_weight(self.settings)
+
+    def set_relation_softmax_known(self, known):
+        """the triples whose relations leave a pair's candidate set on the device paths (the training set, under
+        ExclusiveNegativeSampling=Yes); None: every relation competes"""
+        self.relation_softmax_known = None if known is None else np.ascontiguousarray(known, dtype=np.int32)
+
+    def _relation_softmax(self):
+        """tell the runtime the term's weight and mask before a device step (nothing to tell while the key is absent)"""
+        rt = self.next_component.get_runtime()
+        if self.relation_softmax_weight > 0 or getattr(rt, "_relsm_weight", 0.0) > 0:
+            rt.set_relation_softmax(self.relation_softmax_weight, self.relation_softmax_known)
+        return rt
 
     def local_initialize_train(self):
         self.Y = Placeholder('Y', np.float32)
@@ -48,7 +104,13 @@ class BilinearDiag(Model):
         z = self.Y.value
         # tf.nn.weighted_cross_entropy_with_logits(targets=z, logits=x, pos_weight=1)
         per = (1 - z) * energies + np.log1p(np.exp(-np.abs(energies))) + np.maximum(-energies, 0)
-        return float(np.mean(per, dtype=np.float64))
+        loss = float(np.mean(per, dtype=np.float64))
+        if self.relation_softmax_weight > 0:
+            # the unmasked softmax-over-relations term over the rows with label 1 (the device paths' small-size cross-check)
+            subject_codes, relation_codes, _ = self.next_component.get_all_codes(mode=mode)
+            loss += relation_softmax_terms(subject_codes, relation_codes, self.X.value[np.asarray(z) == 1],
+                                           self.relation_count, self.relation_softmax_weight)[0]
+        return loss
 
     def local_get_regularization(self):
         e1s, rs, e2s = self.compute_codes(mode='train')
@@ -91,15 +153,14 @@ class BilinearDiag(Model):
     def device_train_step(self, graph_edges, x, y, seed):
         """loss + regularisation, all gradients, clip and Adam in one asynchronous device step (graph_edges None: a
         graph-less encoder, Name=embedding)."""
-        self.next_component.get_runtime().train_step(graph_edges, x, y, self.regularization_parameter, seed)
+        self._relation_softmax().train_step(graph_edges, x, y, self.regularization_parameter, seed)
 
     def device_train_step_negatives(self, graph_edges, batch, rate, seed, known=None, relation_rate=0):
         """device_train_step with the negatives drawn on the device from `batch`; known: the known positives they avoid
         (ExclusiveNegativeSampling=Yes), None for the plain sampler; relation_rate: relation corruptions per positive
         (RelationNegativeSampleRate)."""
-        self.next_component.get_runtime().train_step_device_negatives(graph_edges, batch, rate,
-                                                                      self.regularization_parameter, seed, known=known,
-                                                                      relation_rate=relation_rate)
+        self._relation_softmax().train_step_device_negatives(graph_edges, batch, rate, self.regularization_parameter, seed,
+                                                             known=known, relation_rate=relation_rate)
 
     def device_negative_unresolved(self):
         """negative rows the exclusive device sampler could not resolve since its known positives were reserved"""
@@ -117,7 +178,7 @@ class BilinearDiag(Model):
 
     def device_train_step_minibatch(self, minibatch, seed):
         """the whole iteration from the graph batch on: edge dropout, negatives, train step, all on the device"""
-        self.next_component.get_runtime().train_step_minibatch(minibatch, self.regularization_parameter, seed)
+        self._relation_softmax().train_step_minibatch(minibatch, self.regularization_parameter, seed)
 
     def device_stage_minibatch(self, minibatch):
         self.next_component.get_runtime().stage_minibatch(minibatch)
@@ -215,4 +276,9 @@ class BilinearDiag(Model):
         np.add.at(dcodes, x[:, 2], g_e2)
         d_rel = np.zeros_like(relation_codes)
         np.add.at(d_rel, x[:, 1], g_r)
+        if self.relation_softmax_weight > 0:
+            _, t_codes, t_rel = relation_softmax_terms(subject_codes, relation_codes, x[np.asarray(z) == 1],
+                                                       self.relation_count, self.relation_softmax_weight)
+            dcodes = (dcodes + t_codes).astype(dcodes.dtype)
+            d_rel = (d_rel + t_rel).astype(d_rel.dtype)
         return self.next_component.backward((dcodes, d_rel))

@@ -166,6 +166,29 @@ class EncoderRuntime(object):
             self._relation_rate = relation_rate
         return relation_rate
 
+    def set_relation_softmax(self, weight, known=None):
+        """[Decoder] RelationSoftmaxWeight: the weight of the softmax-over-relations term every later train step adds
+        (rgcn_set_relation_softmax) and, under ExclusiveNegativeSampling, the known positives its mask reads; 0: off."""
+        self._relsm_weight, self._relsm_known = float(weight), known
+
+    def _relation_softmax(self, num_positives):
+        """before a step: the term's buffers, the index of its mask and the engine's setting follow what
+        set_relation_softmax asked for; the engine is told only when something changed"""
+        weight = getattr(self, "_relsm_weight", 0.0)
+        known = getattr(self, "_relsm_known", None) if weight > 0 else None
+        if weight > 0:
+            # (an index the exclusive sampler reserved is the same training set: it serves the mask too)
+            if known is not None and getattr(self, "_known", None) is None:
+                self.engine.known_positives_reserve(known)
+                self._known = known
+            if num_positives > getattr(self, "_relsm_reserved", 0):
+                self.engine.relation_softmax_reserve(num_positives)
+                self._relsm_reserved = num_positives
+        state = (weight, int(num_positives), known is not None) if weight > 0 else (0.0, 0, False)
+        if state != getattr(self, "_relsm_state", (0.0, 0, False)):
+            self.engine.set_relation_softmax(*state)
+            self._relsm_state = state
+
     def negative_unresolved(self):
         """negative rows every entity was a known positive for, since the known positives were reserved (0 without them)"""
         return self.engine.negative_unresolved() if getattr(self, "_known", None) is not None else 0
@@ -270,6 +293,7 @@ class EncoderRuntime(object):
         xd, yd = self._buffer("X", 12 * n), self._buffer("Y", 4 * n)
         self._exclusive(getattr(mb, "known", None))
         self._relation_negatives(relation_rate)
+        self._relation_softmax(nb)
         self.engine.train_step_minibatch_device(bd, nb, mb.keep, mb.edge_seed, mb.rate, seed ^ 0x5bd1e995, xd, yd,
                                                 seed=seed, reg_param=reg_param)
         self._state = None
@@ -306,6 +330,7 @@ class EncoderRuntime(object):
         st = self._take_staged(graph_edges, None)
         gd = st[3] if st is not None else self._upload("graph", g)
         xd, yd = self._upload("X", x), self._upload("Y", y)
+        self._relation_softmax(int(np.count_nonzero(y == 1)))      # (the sampler's positives lead the batch)
         self.engine.train_step_device(gd, len(g), xd, yd, len(x), seed=seed, reg_param=reg_param)
         self._state = None            # activations now belong to this train step's graph
         self._graph_version = None
@@ -342,6 +367,7 @@ class EncoderRuntime(object):
         xd, yd = self._dev["X"], self._dev["Y"]
         self.engine.negative_sample_device(bd, len(b), rate, seed ^ 0x5bd1e995, xd, yd, exclusive=self._exclusive(known),
                                            relation_rate=relation_rate)
+        self._relation_softmax(len(b))
         self.engine.train_step_device(gd, len(g), xd, yd, n, seed=seed, reg_param=reg_param)
         self._state = None
         self._graph_version = None
@@ -455,6 +481,7 @@ class EmbeddingRuntime(EncoderRuntime):
             self.engine.decoder_reserve(len(x))
             self._dec_reserved = len(x)
         xd, yd = self._upload("X", x), self._upload("Y", y)
+        self._relation_softmax(int(np.count_nonzero(y == 1)))
         self.engine.train_step_device(None, 0, xd, yd, len(x), seed=seed, reg_param=reg_param)
         self._state = None
         self.weights_version += 1
@@ -479,6 +506,7 @@ class EmbeddingRuntime(EncoderRuntime):
         xd, yd = self._buffer("X", 12 * n), self._buffer("Y", 4 * n)
         self.engine.negative_sample_device(self._dev["batch"], nb, rate, seed ^ 0x5bd1e995, xd, yd,
                                            exclusive=self._exclusive(known), relation_rate=relation_rate)
+        self._relation_softmax(nb)
         self.engine.train_step_device(None, 0, xd, yd, n, seed=seed, reg_param=reg_param)
         self._state = None
         self.weights_version += 1

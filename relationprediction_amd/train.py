@@ -70,6 +70,18 @@ def relation_negative_sample_rate(general_settings):
     return rate
 
 
+def relation_softmax_weight(decoder_settings, relation_count):
+    """[Decoder] RelationSoftmaxWeight=lambda (absent from the reference's settings files; default 0): the weight of the
+    softmax-over-relations loss term of every step's positives.  A non-negative finite float
+    (decoders.bilinear_diag.parse_relation_softmax_weight); lambda > 0 needs two relations."""
+    from .decoders.bilinear_diag import parse_relation_softmax_weight
+    weight = parse_relation_softmax_weight(decoder_settings)
+    if weight > 0 and int(relation_count) < 2:
+        raise ValueError("Decoder.RelationSoftmaxWeight = %g needs at least two relations, the dataset has %d"
+                         % (weight, int(relation_count)))
+    return weight
+
+
 def make_transform(train_triplets, general_settings, encoder, device_negatives=False, device_dropout=False,
                    device_sampler=False):
     """The reference's t_func (train.py:201-247): minibatch -> (graph_split, X, Y).
@@ -198,8 +210,13 @@ def build_model(settings, train_triplets, entity_count, relation_count):
     decoder_settings.merge(general_settings)
     settings['Optimizer'].merge(general_settings)
     settings['Evaluation'].merge(general_settings)
+    weight = relation_softmax_weight(decoder_settings, relation_count)
     encoder = model_builder.build_encoder(encoder_settings, train_triplets)
-    return encoder, model_builder.build_decoder(encoder, decoder_settings)
+    model = model_builder.build_decoder(encoder, decoder_settings)
+    if weight > 0 and exclusive_negative_sampling(general_settings) and hasattr(model, 'set_relation_softmax_known'):
+        # the term's mask follows ExclusiveNegativeSampling: relations that are training facts for a pair do not compete
+        model.set_relation_softmax_known(np.ascontiguousarray(train_triplets, dtype=np.int32))
+    return encoder, model
 
 
 def initialize_model(model, train_triplets):

@@ -212,7 +212,10 @@ enum {
    * rgcn_relation_softmax_reserve.  chunk and padded R: rgcn_relation_softmax_plan */
   RGCN_BUF_RELATION_SOFTMAX_ENERGIES = 22, /* float [chunk, padded R]: E[n, r'] = q_n . W_relation[r']; pad columns zero */
   RGCN_BUF_RELATION_SOFTMAX_G = 23,        /* float [chunk, padded R]: G[n, r'], the term's gradient w.r.t. E; pad columns zero */
-  RGCN_BUF_RELATION_SOFTMAX_DQ = 24        /* float [chunk, code width]: dq_n = sum over r' of G[n, r'] W_relation[r'] */
+  RGCN_BUF_RELATION_SOFTMAX_DQ = 24,       /* float [chunk, code width]: dq_n = sum over r' of G[n, r'] W_relation[r'] */
+  RGCN_BUF_ADVERSARIAL_WEIGHTS = 25        /* float [N]: the row weights of the last fused step that ran under
+                                   rgcn_set_adversarial_negatives, N that step's decoder rows.  Every kind,
+                                   RGCN_KIND_EMBEDDING included; RGCN_ERR_STATE before such a step */
 };
 
 /*
@@ -567,6 +570,47 @@ rgcn_status rgcn_relation_softmax_device(rgcn_ctx* ctx, const int32_t* positives
                                          int32_t exclusive);
 rgcn_status rgcn_set_relation_softmax(rgcn_ctx* ctx, float weight, int64_t num_positives, int32_t exclusive);
 rgcn_status rgcn_relation_softmax_plan(int64_t max_positives, int32_t num_relations, int32_t code_dim, int64_t out[5]);
+
+/* Self-adversarial negatives (Sun et al., RotatE, 2019) and the weighted decoder under them.  Not in the reference, which
+ * weighs every row 1.  A decoder batch of N rows is laid out as every sampler here writes it: the first P rows are the
+ * positives (label 1), every later row i (label 0) is a negative of positive i mod P; K = N / P - 1.  With temperature
+ * alpha, energies x and G_b = {b + t P, t = 1..K}:
+ *     p_i  = exp(alpha x_i - M_b) / sum_{j in G_b} exp(alpha x_j - M_b),   M_b = max_{j in G_b} alpha x_j
+ *     w_i  = K p_i for a negative,   w_b = 1 for a positive
+ *     loss = (1/N) sum_n w_n xent(x_n, y_n) + the regulariser (unweighted);   dx_n = w_n ((sigmoid(x_n) - y_n) / N)
+ * The weights are constants: nothing differentiates through them.  A group's weights sum to K, so sum w = N and the
+ * scale of the loss stays what it is; alpha -> 0 gives the unweighted loss.  The softmax is evaluated in double from the
+ * float energies and rounded once, every sum has a fixed order (no atomics on floats): two calls return the same bytes.
+ *
+ * rgcn_decoder_loss_backward_weighted_device: rgcn_decoder_loss_backward_device with a caller's weight per row
+ * (w_dev float [N]) on the row's loss term and gradient.  w_dev == NULL is that call; weights of 1.0f reproduce its bytes.
+ * Weights must be finite and >= 0, checked on the device: RGCN_ERR_INVALID at the next synchronising call.
+ *
+ * rgcn_adversarial_weights_device: writes the weights above, for the codes of the last forward pass (RGCN_KIND_EMBEDDING:
+ * W_emb), into w_out_dev (float [N]).  Asynchronous on the main stream; reads x_dev only, no rgcn_decoder_reserve needed.
+ * num_triples % num_positives != 0, num_positives <= 0, a NULL pointer, a temperature that is negative or not finite:
+ * RGCN_ERR_INVALID.  K = 0 or temperature == 0: all ones (a fill).  Before a forward pass: RGCN_ERR_STATE.  A row with
+ * an id out of range reads nothing out of bounds, takes no part in its group and gets weight 0 (the decoder rejects
+ * such a batch).
+ *
+ * rgcn_set_adversarial_negatives(temperature, num_positives): the weights inside the fused steps.  Under temperature > 0
+ *   - rgcn_train_step_minibatch_device takes its num_edges batch rows as the positives;
+ *   - rgcn_train_step_device takes num_positives; 0 means "the minibatch step only" and such a step returns
+ *     RGCN_ERR_STATE; a value that does not divide the step's N: RGCN_ERR_INVALID (RGCN_KIND_EMBEDDING included);
+ *   - the labels are checked on the device (1 for the positives, 0 behind them): RGCN_ERR_INVALID at the next
+ *     synchronising call;
+ *   - the steps return RGCN_ERR_UNSUPPORTED on a context with world > 1 (the sharded decoder cuts the batch by rows, and
+ *     the groups with them) and RGCN_ERR_STATE during a capture;
+ *   - the step's weights stay readable as RGCN_BUF_ADVERSARIAL_WEIGHTS.
+ * The relation-softmax term is not weighted.  temperature == 0 (the default) restores every byte and launch the steps
+ * produced before these entry points existed.  temperature negative or not finite, num_positives < 0: RGCN_ERR_INVALID;
+ * temperature > 0 during a capture: RGCN_ERR_STATE. */
+rgcn_status rgcn_decoder_loss_backward_weighted_device(rgcn_ctx* ctx, const int32_t* x_dev, const float* y_dev,
+                                                       const float* w_dev, int64_t num_triples,
+                                                       float regularization_parameter);
+rgcn_status rgcn_adversarial_weights_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t num_triples, int64_t num_positives,
+                                            float temperature, float* w_out_dev);
+rgcn_status rgcn_set_adversarial_negatives(rgcn_ctx* ctx, float temperature, int64_t num_positives);
 
 /* ---- evaluation: raw and filtered link-prediction ranks -------------------------------
  * Replaces Model.score_all_subjects / score_all_objects + Scorer.evaluate_mrr + MrrScore.append_line

@@ -34,6 +34,7 @@ BUF_NEGATIVE_RELATION_UNRESOLVED = 21  # int64 [1]: relation rows every other re
 BUF_RELATION_SOFTMAX_ENERGIES = 22  # [chunk, padded R]: the energies of the chunk the relation-softmax term walked last
 BUF_RELATION_SOFTMAX_G = 23         # [chunk, padded R]: their gradients
 BUF_RELATION_SOFTMAX_DQ = 24        # [chunk, code width]: the gradients of that chunk's query rows
+BUF_ADVERSARIAL_WEIGHTS = 25        # [N]: the row weights of the last fused step under set_adversarial_negatives
 KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS, "basis_tdiag": KIND_BASIS_TDIAG,
          "basis_pdiag": KIND_BASIS_PDIAG, "embedding": KIND_EMBEDDING}
 NORMS = {"intended": NORM_INTENDED, "tf_as_executed": NORM_TF_AS_EXECUTED, "none": NORM_NONE, "local": NORM_LOCAL}
@@ -137,6 +138,9 @@ _SIGS = {
     "rgcn_relation_softmax_device": (C.c_int32, [_P, _P, C.c_int64, C.c_float, C.c_int32]),
     "rgcn_set_relation_softmax": (C.c_int32, [_P, C.c_float, C.c_int64, C.c_int32]),
     "rgcn_relation_softmax_plan": (C.c_int32, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "rgcn_decoder_loss_backward_weighted_device": (C.c_int32, [_P, _P, _P, _P, C.c_int64, C.c_float]),
+    "rgcn_adversarial_weights_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int64, C.c_float, _P]),
+    "rgcn_set_adversarial_negatives": (C.c_int32, [_P, C.c_float, C.c_int64]),
     "rgcn_rank_reserve": (C.c_int32, [_P, C.c_int64]),
     "rgcn_rank_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
     "rgcn_rank_energies_device": (_P, [_P]),
@@ -529,6 +533,7 @@ class Engine:
             self.ctx, batch_buffer.ptr, int(num_edges), int(keep), C.c_uint64(edge_seed), int(rate),
             C.c_uint64(negative_seed), x_dev.ptr, y_dev.ptr, C.c_uint64(seed), C.c_float(reg_param)))
         self.num_edges = int(keep)
+        self._decoder_rows = int(num_edges) * (int(rate) + 1 + getattr(self, "_relation_rate", 0))
 
     def set_relation_owner(self, owner):
         o = np.ascontiguousarray(owner, dtype=np.int32)
@@ -640,6 +645,7 @@ class Engine:
     def set_relation_negatives(self, relation_rate):
         """relation rows per batch edge the negative sampling inside train_step_minibatch_device appends (0: none)"""
         self._check(self.lib.rgcn_set_relation_negatives(self.ctx, int(relation_rate)))
+        self._relation_rate = int(relation_rate)
 
     def relation_softmax_reserve(self, max_positives):
         """size the relation-softmax term's buffers (rgcn_relation_softmax_reserve): one chunk of positives"""
@@ -660,6 +666,27 @@ class Engine:
         its batch rows as the positives, train_step_device the first num_positives rows of X; weight 0 switches it off"""
         self._check(self.lib.rgcn_set_relation_softmax(self.ctx, C.c_float(weight), int(num_positives),
                                                       1 if exclusive else 0))
+
+    def decoder_loss_backward_weighted_device(self, x_dev, y_dev, w_dev, num_triples, reg_param):
+        """decoder_loss_backward_device with a weight per row (a float [N] device buffer) on the row's loss term and
+        gradient (rgcn_decoder_loss_backward_weighted_device); w_dev None: that call itself"""
+        self._check(self.lib.rgcn_decoder_loss_backward_weighted_device(
+            self.ctx, x_dev.ptr, y_dev.ptr, w_dev.ptr if w_dev is not None else None, int(num_triples),
+            C.c_float(reg_param)))
+
+    def adversarial_weights(self, x_dev, num_triples, num_positives, temperature, w_out_dev):
+        """the self-adversarial weights of a decoder batch whose first num_positives rows are the positives, for the codes
+        of the last forward pass, into w_out_dev (rgcn_adversarial_weights_device): 1 for a positive, K softmax(temperature
+        x energy) over its group for a negative"""
+        self._check(self.lib.rgcn_adversarial_weights_device(self.ctx, x_dev.ptr if x_dev is not None else None,
+                                                            int(num_triples), int(num_positives), C.c_float(temperature),
+                                                            w_out_dev.ptr if w_out_dev is not None else None))
+
+    def set_adversarial_negatives(self, temperature, num_positives=0):
+        """self-adversarial weights inside the fused steps (rgcn_set_adversarial_negatives): train_step_minibatch_device
+        takes its batch rows as the positives, train_step_device the first num_positives rows of X; temperature 0
+        switches the mode off"""
+        self._check(self.lib.rgcn_set_adversarial_negatives(self.ctx, C.c_float(temperature), int(num_positives)))
 
     def negative_relation_unresolved(self):
         """relation rows, since the reserve, for which every other relation was a known positive (they kept their first
@@ -948,6 +975,7 @@ class Engine:
                                                     int(num_edges), x_dev.ptr, y_dev.ptr,
                                                     int(num_triples), C.c_uint64(seed), C.c_float(reg_param)))
         self.num_edges = int(num_edges)
+        self._decoder_rows = int(num_triples)
 
     def prefetch_graph_device(self, triples_dev, num_edges):
         self._check(self.lib.rgcn_prefetch_graph_device(self.ctx, triples_dev.ptr, int(num_edges)))
@@ -994,6 +1022,8 @@ class Engine:
             plan = getattr(self, "_relsm_plan", {"chunk": 0, "padded_r": 0})
             cols = self._code_width if which == BUF_RELATION_SOFTMAX_DQ else plan["padded_r"]
             out = np.empty((plan["chunk"], cols), dtype=np.float32)
+        elif which == BUF_ADVERSARIAL_WEIGHTS:
+            out = np.empty(getattr(self, "_decoder_rows", 0), dtype=np.float32)
         elif which == BUF_DSELF_EXCHANGE:
             out = np.empty((self.d, self.d), dtype=np.float32)
         elif which == BUF_NORM_EXCHANGE:

@@ -223,11 +223,14 @@ __global__ void __launch_bounds__(256) k_negative_sample_relation(const int32_t*
 }
 
 // ---- K1: energies, dx, loss terms ---------------------------------------------------------------
-template <int VEC>
+// WEIGHTED: a weight per row (Wt, read where Y is) multiplies the row's loss term and its dx -- a constant of the loss
+// (the self-adversarial weights of adversarial.hip, or a caller's).  w * ((sig - y) / N) in exactly that order: weights
+// of 1.0f reproduce the unweighted bytes.  The regulariser is not weighted.
+template <int VEC, bool WEIGHTED>
 __global__ void __launch_bounds__(256) k_dec_energy(const float* __restrict__ codes, const float* __restrict__ Wr,
                                                     const int32_t* __restrict__ X, const float* __restrict__ Y,
-                                                    int N, int Nt, int V, int R, int d, float* __restrict__ dx,
-                                                    float* __restrict__ part /* [gridDim.x][2] */) {
+                                                    const float* __restrict__ Wt, int N, int Nt, int V, int R, int d,
+                                                    float* __restrict__ dx, float* __restrict__ part /* [gridDim.x][2] */) {
   // N = triples of this launch; Nt = triples of the whole batch (the mean's denominator: a relation-sharded run cuts
   // the batch into per-rank slices and adds the partial results up)
   __shared__ float red[4][2];
@@ -264,10 +267,19 @@ __global__ void __launch_bounds__(256) k_dec_energy(const float* __restrict__ co
       const float ax = fabsf(x);
       const float ex = __expf(-ax);
       const float sig = x >= 0.f ? 1.0f / (1.0f + ex) : ex / (1.0f + ex);
-      dx[n] = ok ? (sig - y) / (float)Nt : 0.f;
-      if (ok) {
-        xent += (1.0f - y) * x + log1pf(ex) + fmaxf(-x, 0.f);
-        sq += q;
+      if constexpr (WEIGHTED) {
+        const float wt = Wt[n];
+        dx[n] = ok ? wt * ((sig - y) / (float)Nt) : 0.f;
+        if (ok) {
+          xent += wt * ((1.0f - y) * x + log1pf(ex) + fmaxf(-x, 0.f));
+          sq += q;
+        }
+      } else {
+        dx[n] = ok ? (sig - y) / (float)Nt : 0.f;
+        if (ok) {
+          xent += (1.0f - y) * x + log1pf(ex) + fmaxf(-x, 0.f);
+          sq += q;
+        }
       }
     }
   }
@@ -686,10 +698,10 @@ __global__ void __launch_bounds__(kRowThreads) k_dec_rel_partial(const float* __
 // encoder's backward pass and slow its GEMMs).  The four waves' accumulators are summed in a fixed order into the
 // chunk's slab row; k_dec_rel_reduce finishes as before.  T = ceil(d / VEC / 64) <= 4; wider rows use the two
 // separate kernels.
-template <int VEC, int T>
+template <int VEC, int T, bool WEIGHTED>
 __global__ void __launch_bounds__(256) k_dec_energy_rel(const float* __restrict__ codes, const float* __restrict__ Wr,
                                                         const int32_t* __restrict__ X, const float* __restrict__ Y,
-                                                        const int32_t* __restrict__ permr,
+                                                        const float* __restrict__ Wt, const int32_t* __restrict__ permr,
                                                         const int32_t* __restrict__ rel_ptr,
                                                         const int32_t* __restrict__ chunk_ptr, int N, int R, int d,
                                                         float* __restrict__ dx, float* __restrict__ part,
@@ -743,6 +755,8 @@ __global__ void __launch_bounds__(256) k_dec_energy_rel(const float* __restrict_
     }
     const int m0 = n0, m1 = n1;
     const float y0 = Y[m0], y1 = two ? Y[m1] : 0.f;
+    float w0 = 1.0f, w1 = 1.0f;
+    if constexpr (WEIGHTED) { w0 = Wt[m0]; w1 = two ? Wt[m1] : 0.f; }
     j += 8;
     n0 = j < end ? permr[j] : -1;
     n1 = j + 4 < end ? permr[j + 4] : -1;
@@ -779,9 +793,15 @@ __global__ void __launch_bounds__(256) k_dec_energy_rel(const float* __restrict_
         const float ax = fabsf(x[u]);
         const float ex = __expf(-ax);
         const float sig = x[u] >= 0.f ? 1.0f / (1.0f + ex) : ex / (1.0f + ex);
-        g[u] = (sig - y) / (float)N;
+        if constexpr (WEIGHTED) {
+          const float wt = u ? w1 : w0;
+          g[u] = wt * ((sig - y) / (float)N);
+          xent += wt * ((1.0f - y) * x[u] + log1pf(ex) + fmaxf(-x[u], 0.f));
+        } else {
+          g[u] = (sig - y) / (float)N;
+          xent += (1.0f - y) * x[u] + log1pf(ex) + fmaxf(-x[u], 0.f);
+        }
         dx[u ? m1 : m0] = g[u];
-        xent += (1.0f - y) * x[u] + log1pf(ex) + fmaxf(-x[u], 0.f);
         sq += q[u];
       }
     }
@@ -1040,7 +1060,7 @@ rgcn_status decoder_prepare(rgcn_ctx* c, const int32_t* X, int64_t N64, int64_t 
 
 // loss + gradients w.r.t. the codes (-> c->dcodes_own) and W_relation (-> its grad buffer)
 rgcn_status decoder_compute(rgcn_ctx* c, const float* codes, const float* Y, float reg_param, float* dcodes_drop,
-                            const DropSpec* drop) {
+                            const DropSpec* drop, const float* row_weights) {
   DecoderBufs& q = c->dec;
   const int N = q.N, V = c->V, R = c->R, d = c->dc;
   const int Nt = q.N_total > 0 ? (int)q.N_total : N;      // denominator of the batch mean
@@ -1061,23 +1081,31 @@ rgcn_status decoder_compute(rgcn_ctx* c, const float* codes, const float* Y, flo
     // rows and the batch once, the per-triple gradients and chunk partials once
     ProfScope ps(c, "dec_energy_rel", 12.0 * N * d + 20.0 * N + 4.0 * q.max_chunks * d, 9.0 * N * d,
                  4.0 * d * ((double)V + R) + 20.0 * N + 4.0 * q.max_chunks * d);
-#define RGCN_LAUNCH_ER(VEC, TT)                                                                                    \
-  hipLaunchKernelGGL((k_dec_energy_rel<VEC, TT>), dim3(q.max_chunks), dim3(256), lds, c->stream, codes, Wr, q.X, Y, \
-                     q.permr, q.rel_ptr, q.chunk_ptr, Nt, R, d, q.dx, q.loss_part, q.slab)
-    if (vec4) {
-      if (T == 1) RGCN_LAUNCH_ER(4, 1); else if (T == 2) RGCN_LAUNCH_ER(4, 2); else RGCN_LAUNCH_ER(4, 4);
+#define RGCN_LAUNCH_ER(VEC, TT, WT)                                                                                   \
+  hipLaunchKernelGGL((k_dec_energy_rel<VEC, TT, WT>), dim3(q.max_chunks), dim3(256), lds, c->stream, codes, Wr, q.X, Y, \
+                     row_weights, q.permr, q.rel_ptr, q.chunk_ptr, Nt, R, d, q.dx, q.loss_part, q.slab)
+#define RGCN_LAUNCH_ER_T(VEC, WT)                                                                \
+  do {                                                                                           \
+    if (T == 1) RGCN_LAUNCH_ER(VEC, 1, WT); else if (T == 2) RGCN_LAUNCH_ER(VEC, 2, WT); else RGCN_LAUNCH_ER(VEC, 4, WT); \
+  } while (0)
+    if (row_weights == nullptr) {
+      if (vec4) RGCN_LAUNCH_ER_T(4, false); else RGCN_LAUNCH_ER_T(1, false);
     } else {
-      if (T == 1) RGCN_LAUNCH_ER(1, 1); else if (T == 2) RGCN_LAUNCH_ER(1, 2); else RGCN_LAUNCH_ER(1, 4);
+      if (vec4) RGCN_LAUNCH_ER_T(4, true); else RGCN_LAUNCH_ER_T(1, true);
     }
+#undef RGCN_LAUNCH_ER_T
 #undef RGCN_LAUNCH_ER
   } else {
     ProfScope ps(c, "dec_energy", 12.0 * N * d + 20.0 * N, 6.0 * N * d, 4.0 * d * ((double)V + R) + 20.0 * N);
-    if (vec4)
-      hipLaunchKernelGGL((k_dec_energy<4>), dim3(q.energy_blocks), dim3(256), 0, c->stream, codes, Wr, q.X, Y, N, Nt, V,
-                         R, d, q.dx, q.loss_part);
-    else
-      hipLaunchKernelGGL((k_dec_energy<1>), dim3(q.energy_blocks), dim3(256), 0, c->stream, codes, Wr, q.X, Y, N, Nt, V,
-                         R, d, q.dx, q.loss_part);
+#define RGCN_LAUNCH_E(VEC, WT)                                                                                        \
+  hipLaunchKernelGGL((k_dec_energy<VEC, WT>), dim3(q.energy_blocks), dim3(256), 0, c->stream, codes, Wr, q.X, Y, \
+                     row_weights, N, Nt, V, R, d, q.dx, q.loss_part)
+    if (row_weights == nullptr) {
+      if (vec4) RGCN_LAUNCH_E(4, false); else RGCN_LAUNCH_E(1, false);
+    } else {
+      if (vec4) RGCN_LAUNCH_E(4, true); else RGCN_LAUNCH_E(1, true);
+    }
+#undef RGCN_LAUNCH_E
   }
   {
     // dL/dW_relation depends on dx only and is not needed before the optimizer: side stream 2, so that it runs

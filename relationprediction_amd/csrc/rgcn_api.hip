@@ -223,6 +223,9 @@ static rgcn_status check_dev_flag(rgcn_ctx* c, bool main_only = false) {
                                    (flag & 32 ? "device neighbourhood sampler: the compacted batch does not hold the requested number "
                                                 "of edges (internal error: two draws sharing the sampler's state?); " : "") +
                                    (flag & 64 ? "relation softmax: a row taken as a positive does not carry the label 1; " : "") +
+                                   (flag & 128 ? "adversarial negatives: the labels are not 1 for the leading positives and 0 for every "
+                                                 "row behind them; " : "") +
+                                   (flag & 256 ? "weighted decoder: a row weight is negative or not finite; " : "") +
                                    (flag & 16 ? "the decoder batch is no longer the tiled batch rgcn_negative_sample_device wrote into that "
                                                 "buffer (rewritten by the caller's own kernels?): pass it in another buffer; " : "") +
                                    (flag & 3 ? "graph_edges / the decoder batch contains a vertex id outside [0,EntityCount) or a "
@@ -320,6 +323,7 @@ static void free_all(rgcn_ctx* c) {
   known_positives_free(c);
   optimizer_free(c);
   relation_softmax_free(c);
+  adversarial_free(c);
   rank_free(c);
   c->pool.release();
   for (ProfRec& r : c->prof) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
@@ -1011,6 +1015,61 @@ rgcn_status rgcn_decoder_loss_backward_device(rgcn_ctx* c, const int32_t* X_dev,
   return RGCN_OK;
 }
 
+rgcn_status rgcn_decoder_loss_backward_weighted_device(rgcn_ctx* c, const int32_t* X_dev, const float* Y_dev,
+                                                       const float* w_dev, int64_t N, float reg_param) {
+  if (!w_dev) return rgcn_decoder_loss_backward_device(c, X_dev, Y_dev, N, reg_param);
+  RGCN_NEED(c);
+  if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "the decoder needs a completed rgcn_forward");
+  if (!X_dev || !Y_dev || N <= 0) RGCN_FAIL(c, RGCN_ERR_INVALID, "bad decoder batch");
+  if (c->dec.maxN < N) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_decoder_reserve(ctx, max_triples) first");
+  RGCN_TRY(adversarial_check_weights(c, w_dev, N));
+  RGCN_TRY(decoder_prepare(c, X_dev, N));
+  RGCN_TRY(decoder_compute(c, c->codes, Y_dev, reg_param, nullptr, nullptr, w_dev));
+  RGCN_TRY(stream_join(c, 2));      // the relation gradient ran on its own side stream
+  c->dec.loss_valid = true;
+  return RGCN_OK;
+}
+
+// ---- self-adversarial negatives: the stand-alone weights, the mode of the fused steps
+static bool adv_temperature_ok(float t) { return t >= 0.f && t <= 3.0e38f; }      // (false for NaN and for infinity)
+
+rgcn_status rgcn_adversarial_weights_device(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int64_t P, float temperature,
+                                            float* w_out_dev) {
+  RGCN_NEED(c);
+  if (!X_dev || !w_out_dev) RGCN_FAIL(c, RGCN_ERR_INVALID, "NULL batch or output");
+  if (N <= 0 || N > RGCN_MAX_DECODER_TRIPLES || P <= 0 || N % P != 0)
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "num_triples must be a positive multiple of num_positives");
+  if (!adv_temperature_ok(temperature)) RGCN_FAIL(c, RGCN_ERR_INVALID, "the temperature must be finite and not negative");
+  if (!c->fwd_done) RGCN_FAIL(c, RGCN_ERR_STATE, "the weights are those of the last forward pass's codes: call rgcn_forward first");
+  return adversarial_weights(c, c->embedding ? c->H[0] : c->codes, X_dev, nullptr, N, P, temperature, w_out_dev);
+}
+
+rgcn_status rgcn_set_adversarial_negatives(rgcn_ctx* c, float temperature, int64_t num_positives) {
+  RGCN_NEED(c);
+  if (!adv_temperature_ok(temperature)) RGCN_FAIL(c, RGCN_ERR_INVALID, "the temperature must be finite and not negative");
+  if (num_positives < 0 || num_positives > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "num_positives out of range");
+  if (temperature > 0.f && c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
+  c->adv.temperature = temperature;
+  c->adv.step_positives = num_positives;
+  return RGCN_OK;
+}
+
+// what a fused step checks before it queues anything while the mode is on (rgcn_set_adversarial_negatives, temperature
+// > 0), P the step's positives; then the weight buffer follows the decoder's reserve
+static rgcn_status adv_step_check(rgcn_ctx* c, int64_t N, int64_t P) {
+  // (a sharded step cuts the batch by rows, and with them the groups)
+  if (c->world > 1) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "adversarial negatives in the step of a relation-sharded context (world > 1)");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "adversarial negatives are not built for a hipGraph capture");
+  if (P <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_set_adversarial_negatives was given num_positives = 0: the minibatch step only");
+  if (N % P != 0) RGCN_FAIL(c, RGCN_ERR_INVALID, "adversarial negatives: the batch's rows are no multiple of num_positives");
+  return RGCN_OK;
+}
+static rgcn_status adv_step_buffer(rgcn_ctx* c) {
+  if (c->adv.w && c->adv.cap >= c->dec.maxN) return RGCN_OK;
+  RGCN_TRY(sync_all(c));      // (an earlier step may still read the buffer this replaces)
+  return adversarial_reserve(c, c->dec.maxN);
+}
+
 const float* rgcn_dcodes_device(rgcn_ctx* c) { return c ? c->dcodes_own : nullptr; }
 
 rgcn_status rgcn_get_loss(rgcn_ctx* c, double* loss) {
@@ -1412,8 +1471,16 @@ rgcn_status rgcn_optimizer_apply(rgcn_ctx* c) { RGCN_NEED(c); return optimizer_a
 // backward, clip + Adam
 // n_pos > 0: the leading n_pos rows of X are the positives of the relation-softmax term (one GPU; relsm_step_check)
 static rgcn_status train_step_tail(rgcn_ctx* c, const int32_t* X_dev, const float* Y_dev, int64_t N, uint64_t seed,
-                                   float reg_param, int64_t n_pos = 0) {
+                                   float reg_param, int64_t n_pos = 0, int64_t adv_pos = 0) {
   RGCN_TRY(forward_all(c, 1, seed, nullptr));
+  // adv_pos > 0: self-adversarial weights of the negatives (one GPU; adv_step_check), from the codes the forward pass just
+  // left.  On the main stream: the pass reads X alone, so it runs beside the decoder's preparation on side stream 1.
+  const float* row_w = nullptr;
+  if (adv_pos > 0) {
+    RGCN_TRY(adversarial_weights(c, c->codes, X_dev, Y_dev, N, adv_pos, c->adv.temperature, c->adv.w));
+    c->adv.last_N = N;
+    row_w = c->adv.w;
+  }
   // Relation-sharded run: the decoder is divided by TRIPLES -- rank g takes the slice [g ceil(N / world), ...) of the
   // batch (the codes are replicated after the last forward exchange), its loss terms and gradients are normalised by
   // the whole batch's N, and the partial dL/dcodes [V,d], dL/dW_relation [R,d] and loss are summed over the ranks
@@ -1452,7 +1519,7 @@ static rgcn_status train_step_tail(rgcn_ctx* c, const int32_t* X_dev, const floa
   // (with the relation-softmax term on, dL/dcodes is complete only behind the term: bwd_begin scales it)
   float* ds_ready = (c->world == 1 && !c->highway && !c->out_layer && top_drop.mode != DROP_NONE && n_pos <= 0)
                         ? c->dsbuf[c->L & 1] : nullptr;
-  RGCN_TRY(decoder_compute(c, c->codes, Y_loc, reg_param, ds_ready, &top_drop));
+  RGCN_TRY(decoder_compute(c, c->codes, Y_loc, reg_param, ds_ready, &top_drop, row_w));
   if (n_pos > 0) {
     // the term adds to what the decoder left, W_relation's gradient on side stream 2 included: join it first
     RGCN_TRY(stream_join(c, 2));
@@ -1516,6 +1583,7 @@ rgcn_status rgcn_train_step_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t 
   if (!X_dev || !Y_dev || N <= 0) RGCN_FAIL(c, RGCN_ERR_INVALID, "bad decoder batch");
   // (the term's refusals first: a sharded context is refused whether or not it has its communicator yet)
   if (c->relsm.weight > 0.f) RGCN_TRY(relsm_step_check(c));
+  if (c->adv.temperature > 0.f) RGCN_TRY(adv_step_check(c, N, c->adv.step_positives));
   if (c->world > 1 && !c->comm)
     RGCN_FAIL(c, RGCN_ERR_STATE, "world > 1: call rgcn_comm_init first (or drive the phase API yourself)");
   if (c->dec.maxN < N) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_decoder_reserve(ctx, max_triples) first");
@@ -1526,12 +1594,20 @@ rgcn_status rgcn_train_step_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t 
     if (c->relsm.step_positives > N) RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_set_relation_softmax: num_positives above the batch's rows");
     n_pos = c->relsm.step_positives;
   }
+  const int64_t adv_pos = c->adv.temperature > 0.f ? c->adv.step_positives : 0;
+  if (c->adv.temperature > 0.f) RGCN_TRY(adv_step_buffer(c));
   if (c->embedding) {
     // the DistMult baseline's step: decoder loss + gradients on the table itself (dL/dcodes is written into W_emb's
     // gradient), then clip + Adam.  One chain on the main stream but for the relation gradient's side stream.
     RGCN_TRY(forward_all(c, 1, seed, nullptr));
+    const float* row_w = nullptr;
+    if (adv_pos > 0) {
+      RGCN_TRY(adversarial_weights(c, c->H[0], X_dev, Y_dev, N, adv_pos, c->adv.temperature, c->adv.w));
+      c->adv.last_N = N;
+      row_w = c->adv.w;
+    }
     RGCN_TRY(decoder_prepare(c, X_dev, N));
-    RGCN_TRY(decoder_compute(c, c->H[0], Y_dev, reg_param));
+    RGCN_TRY(decoder_compute(c, c->H[0], Y_dev, reg_param, nullptr, nullptr, row_w));
     RGCN_TRY(stream_join(c, 2));
     if (n_pos > 0) {
       c->relsm.csr_X = nullptr;
@@ -1543,7 +1619,7 @@ rgcn_status rgcn_train_step_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t 
     return RGCN_OK;
   }
   RGCN_TRY(step_begin(c, tri_dev, E, true));
-  return train_step_tail(c, X_dev, Y_dev, N, seed, reg_param, n_pos);
+  return train_step_tail(c, X_dev, Y_dev, N, seed, reg_param, n_pos, adv_pos);
 }
 
 rgcn_status rgcn_prefetch_graph_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t E) {
@@ -1595,9 +1671,12 @@ rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* c, const int32_t* batch_d
   const int64_t N = n * (int64_t)(negative_rate + 1 + relation_rate);
   const bool relsm_on = c->relsm.weight > 0.f;      // rgcn_set_relation_softmax; off: the step as it always was
   if (relsm_on) RGCN_TRY(relsm_step_check(c));      // (ahead of the communicator's check, as in rgcn_train_step_device)
+  const bool adv_on = c->adv.temperature > 0.f;     // rgcn_set_adversarial_negatives; off: the step as it always was
+  if (adv_on) RGCN_TRY(adv_step_check(c, N, n));
   if (c->world > 1 && !c->comm)
     RGCN_FAIL(c, RGCN_ERR_STATE, "world > 1: call rgcn_comm_init first (or drive the phase API yourself)");
   if (c->dec.maxN < N) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_decoder_reserve(ctx, max_triples) first");
+  if (adv_on) RGCN_TRY(adv_step_buffer(c));
   if (relation_rate > 0) {
     if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "relation corruptions are not built for a hipGraph capture");
     if (N > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "batch too large");
@@ -1618,7 +1697,7 @@ rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* c, const int32_t* batch_d
     RGCN_TRY(negative_sample(c, batch_dev, n, negative_rate, negative_seed, x_scratch_dev, y_scratch_dev));
   // the decoder's batch preparation forks from ev_step_begin onto a side stream: it must see the sampled batch
   RGCN_HIP(c, hipEventRecord(c->ev_step_begin, c->main_stream));
-  return train_step_tail(c, x_scratch_dev, y_scratch_dev, N, dropout_seed, reg_param, relsm_on ? n : 0);
+  return train_step_tail(c, x_scratch_dev, y_scratch_dev, N, dropout_seed, reg_param, relsm_on ? n : 0, adv_on ? n : 0);
 }
 
 // ---- neighbourhood edge sampler on the device ------------------------------------------
@@ -1850,7 +1929,8 @@ static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* byte
   if (c->embedding && which != RGCN_BUF_RANK_ENERGIES && which != RGCN_BUF_RANK_MIXED_SCORES &&
       which != RGCN_BUF_RELATION_ENERGIES && which != RGCN_BUF_NEGATIVE_UNRESOLVED &&
       which != RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED && which != RGCN_BUF_RELATION_SOFTMAX_ENERGIES &&
-      which != RGCN_BUF_RELATION_SOFTMAX_G && which != RGCN_BUF_RELATION_SOFTMAX_DQ)
+      which != RGCN_BUF_RELATION_SOFTMAX_G && which != RGCN_BUF_RELATION_SOFTMAX_DQ &&
+      which != RGCN_BUF_ADVERSARIAL_WEIGHTS)
     RGCN_FAIL(c, RGCN_ERR_STATE, "an RGCN_KIND_EMBEDDING context has the ranking buffers only (no graph, no layer buffers)");
   switch (which) {
     case RGCN_BUF_NEGATIVE_UNRESOLVED:
@@ -1869,6 +1949,10 @@ static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* byte
         *bytes = c->relsm.plan.chunk * c->relsm.plan.padded_r * 4;
       }
       return RGCN_OK;
+    case RGCN_BUF_ADVERSARIAL_WEIGHTS:
+      if (!c->adv.w || c->adv.last_N <= 0)
+        RGCN_FAIL(c, RGCN_ERR_STATE, "no fused step has run under rgcn_set_adversarial_negatives");
+      *p = c->adv.w; *bytes = c->adv.last_N * 4; return RGCN_OK;
     case RGCN_BUF_EXCHANGE:
       if (!c->exch) RGCN_FAIL(c, RGCN_ERR_STATE, "no exchange buffer on a world == 1 context");
       *p = c->exch; *bytes = Vd; return RGCN_OK;

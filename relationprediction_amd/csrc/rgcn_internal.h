@@ -364,6 +364,16 @@ struct RelsmBufs {
   bool exclusive = false;
 };
 
+// self-adversarial negatives (csrc/adversarial.hip; rgcn_set_adversarial_negatives)
+struct AdversarialState {
+  DevPool pool;
+  float* w = nullptr;                     // [cap] the weights of the last fused step under the mode (RGCN_BUF_ADVERSARIAL_WEIGHTS)
+  int64_t cap = 0;
+  int64_t last_N = 0;                     // rows of that step; 0: none yet
+  float temperature = 0.f;                // 0: off
+  int64_t step_positives = 0;             // leading rows of an X/Y step's batch; 0: the minibatch step only
+};
+
 struct OptimizerState {
   DevPool pool;              // moments, state, shard_sq
   DevPool part_pool;         // `part` alone: it is the one buffer that grows
@@ -482,6 +492,7 @@ struct rgcn_ctx {
   rgcn::KnownPositives known;
   int32_t relation_negatives = 0;        // rgcn_set_relation_negatives: relation rows per positive in the fused minibatch step
   rgcn::RelsmBufs relsm;
+  rgcn::AdversarialState adv;
   rgcn::OptimizerState opt;
 
   std::vector<float*> H;                 // H[0..L], [V,d] each
@@ -790,9 +801,22 @@ void decoder_free(rgcn_ctx* c);
 // N_total > N: X_dev is one rank's slice of a batch of N_total triples (relation-sharded train step); 0: N
 rgcn_status decoder_prepare(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int64_t N_total = 0);
 // dcodes_drop / drop (optional): also write dL/dcodes * drop, the dropout-scaled copy the encoder's top layer consumes
+// row_weights (optional, float [N]): a weight per row of the batch on its loss term and its dx (the weighted kernels)
 rgcn_status decoder_compute(rgcn_ctx* c, const float* codes, const float* Y_dev, float reg_param,
-                            float* dcodes_drop = nullptr, const DropSpec* drop = nullptr);
+                            float* dcodes_drop = nullptr, const DropSpec* drop = nullptr,
+                            const float* row_weights = nullptr);
 rgcn_status decoder_allreduce(rgcn_ctx* c);      // sharded run: sum the per-rank partial decoder results
+// ---- adversarial.hip: self-adversarial weights of the decoder's negatives (adversarial_weights.h)
+// w_out[i] = 1 for the P positives that lead the batch, K softmax_alpha(x) over its group for negative i of positive
+// i mod P, K = N / P - 1 (N % P == 0, checked by the caller); the energies from `codes` and W_relation.  On the current
+// stream; reads X only, so it needs no decoder_prepare.  Y_dev (optional): the labels, which must be 1 for the positives
+// and 0 after them (error flag 128).  Ids out of range: weight 0, nothing read out of bounds.
+rgcn_status adversarial_weights(rgcn_ctx* c, const float* codes, const int32_t* X_dev, const float* Y_dev, int64_t N,
+                                int64_t P, float alpha, float* w_out);
+rgcn_status adversarial_check_weights(rgcn_ctx* c, const float* w_dev, int64_t N);      // finite and >= 0, or error flag 256
+rgcn_status adversarial_reserve(rgcn_ctx* c, int64_t rows);      // the fused steps' weight buffer (the caller has synchronised)
+void adversarial_free(rgcn_ctx* c);
+int adversarial_lds_cap();      // energies of one group the weight kernel keeps in LDS
 rgcn_status optimizer_step(rgcn_ctx* c);
 rgcn_status optimizer_norm_partial(rgcn_ctx* c);
 rgcn_status optimizer_apply(rgcn_ctx* c);

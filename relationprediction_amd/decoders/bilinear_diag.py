@@ -37,6 +37,47 @@ def parse_relation_softmax_weight(settings):
     return weight
 
 
+def parse_adversarial_temperature(settings):
+    """[General] AdversarialTemperature=alpha (not in the reference; absent: 0): the temperature of the self-adversarial
+    weights of the negatives (include/rgcn.h, rgcn_set_adversarial_negatives).  A non-negative finite float."""
+    if 'AdversarialTemperature' not in settings:
+        return 0.0
+    value = settings['AdversarialTemperature']
+    try:
+        if isinstance(value, bool):
+            raise ValueError
+        alpha = float(str(value).strip())
+    except ValueError:
+        raise ValueError("General.AdversarialTemperature must be a non-negative number, not %r" % (value,))
+    if not np.isfinite(alpha) or alpha < 0:
+        raise ValueError("General.AdversarialTemperature must be a non-negative finite number, not %r" % (value,))
+    return alpha
+
+
+def adversarial_row_weights(energies, labels, temperature):
+    """The numpy port of csrc/adversarial_weights.h over a whole batch: float32 weights [N] from float32 energies.  The
+    batch is laid out as the samplers write it -- P = the leading rows with label 1, every later row i a negative of
+    positive i mod P, K = N / P - 1 -- and a negative's weight is K times the softmax of temperature x energy over its
+    group, evaluated in float64 and rounded once; a positive's weight is 1.  ValueError for any other layout."""
+    x = np.asarray(energies, dtype=np.float32).reshape(-1)
+    z = np.asarray(labels).reshape(-1)
+    N = len(x)
+    w = np.ones(N, dtype=np.float32)
+    P = int(np.count_nonzero(z == 1))
+    if temperature == 0 or N == 0:
+        return w
+    if P == 0 or N % P != 0 or not (z[:P] == 1).all() or not (z[P:] == 0).all():
+        raise ValueError("adversarial weights need the positives (label 1) first and a whole number of negatives "
+                         "(label 0) per positive behind them: %d rows, %d with label 1" % (N, P))
+    K = N // P - 1
+    if K == 0:
+        return w
+    a = np.float64(np.float32(temperature)) * x[P:].astype(np.float64).reshape(K, P)
+    t = np.exp(a - a.max(axis=0, keepdims=True))
+    w[P:] = (K * t / t.sum(axis=0, keepdims=True)).astype(np.float32).reshape(-1)
+    return w
+
+
 def relation_softmax_terms(codes, relation_codes, positives, relation_count, weight):
     """The unmasked term evaluated eagerly in float64: (term, dcodes [V,dc], d_rel [rows of relation_codes, dc])."""
     pos = np.asarray(positives, dtype=np.int64).reshape(-1, 3)
@@ -70,6 +111,7 @@ class BilinearDiag(Model):
     def parse_settings(self):
         self.regularization_parameter = float(self.settings['RegularizationParameter'])
         self.relation_softmax_weight = parse_relation_softmax_weight(self.settings)
+        self.adversarial_temperature = parse_adversarial_temperature(self.settings)
 
     def set_relation_softmax_known(self, known):
         """the triples whose relations leave a pair's candidate set on the device paths (the training set, under
@@ -81,6 +123,8 @@ class BilinearDiag(Model):
         rt = self.next_component.get_runtime()
         if self.relation_softmax_weight > 0 or getattr(rt, "_relsm_weight", 0.0) > 0:
             rt.set_relation_softmax(self.relation_softmax_weight, self.relation_softmax_known)
+        if self.adversarial_temperature > 0 or getattr(rt, "_adv_temperature", 0.0) > 0:
+            rt.set_adversarial_temperature(self.adversarial_temperature)
         return rt
 
     def local_initialize_train(self):
@@ -104,6 +148,8 @@ class BilinearDiag(Model):
         z = self.Y.value
         # tf.nn.weighted_cross_entropy_with_logits(targets=z, logits=x, pos_weight=1)
         per = (1 - z) * energies + np.log1p(np.exp(-np.abs(energies))) + np.maximum(-energies, 0)
+        if self.adversarial_temperature > 0:
+            per = adversarial_row_weights(energies, z, self.adversarial_temperature) * per
         loss = float(np.mean(per, dtype=np.float64))
         if self.relation_softmax_weight > 0:
             # the unmasked softmax-over-relations term over the rows with label 1 (the device paths' small-size cross-check)
@@ -268,7 +314,10 @@ class BilinearDiag(Model):
         e1s, rs, e2s = subject_codes[x[:, 0]], relation_codes[x[:, 1]], object_codes[x[:, 2]]
         n, d = e1s.shape
         energies = np.sum(e1s * rs * e2s, axis=1)
-        dx = ((_sigmoid(energies) - z) / n).astype(np.float32)[:, None]
+        dx = ((_sigmoid(energies) - z) / n).astype(np.float32)
+        if self.adversarial_temperature > 0:
+            dx = adversarial_row_weights(energies, z, self.adversarial_temperature) * dx      # the weights are constants
+        dx = dx[:, None]
         k = np.float32(self.regularization_parameter * 2.0 / (n * d))
         g_e1, g_r, g_e2 = dx * (rs * e2s) + k * e1s, dx * (e1s * e2s) + k * rs, dx * (e1s * rs) + k * e2s
         dcodes = np.zeros_like(subject_codes)

@@ -189,6 +189,24 @@ class EncoderRuntime(object):
             self.engine.set_relation_softmax(*state)
             self._relsm_state = state
 
+    def set_adversarial_temperature(self, temperature):
+        """[General] AdversarialTemperature: every later train step weighs each negative by the softmax of its group's
+        energies at this temperature (rgcn_set_adversarial_negatives); 0: off."""
+        self._adv_temperature = float(temperature)
+
+    def _adversarial(self, num_positives):
+        """before a step: the engine's setting follows set_adversarial_temperature; told only when something changed"""
+        temperature = getattr(self, "_adv_temperature", 0.0)
+        state = (temperature, int(num_positives)) if temperature > 0 else (0.0, 0)
+        if state != getattr(self, "_adv_state", (0.0, 0)):
+            self.engine.set_adversarial_negatives(*state)
+            self._adv_state = state
+
+    def adversarial_weights(self):
+        """the row weights of the last train step under AdversarialTemperature > 0 (RGCN_BUF_ADVERSARIAL_WEIGHTS)"""
+        from . import _native
+        return self.engine.read_buffer(_native.BUF_ADVERSARIAL_WEIGHTS)
+
     def negative_unresolved(self):
         """negative rows every entity was a known positive for, since the known positives were reserved (0 without them)"""
         return self.engine.negative_unresolved() if getattr(self, "_known", None) is not None else 0
@@ -294,6 +312,7 @@ class EncoderRuntime(object):
         self._exclusive(getattr(mb, "known", None))
         self._relation_negatives(relation_rate)
         self._relation_softmax(nb)
+        self._adversarial(nb)
         self.engine.train_step_minibatch_device(bd, nb, mb.keep, mb.edge_seed, mb.rate, seed ^ 0x5bd1e995, xd, yd,
                                                 seed=seed, reg_param=reg_param)
         self._state = None
@@ -331,6 +350,7 @@ class EncoderRuntime(object):
         gd = st[3] if st is not None else self._upload("graph", g)
         xd, yd = self._upload("X", x), self._upload("Y", y)
         self._relation_softmax(int(np.count_nonzero(y == 1)))      # (the sampler's positives lead the batch)
+        self._adversarial(int(np.count_nonzero(y == 1)))
         self.engine.train_step_device(gd, len(g), xd, yd, len(x), seed=seed, reg_param=reg_param)
         self._state = None            # activations now belong to this train step's graph
         self._graph_version = None
@@ -368,6 +388,7 @@ class EncoderRuntime(object):
         self.engine.negative_sample_device(bd, len(b), rate, seed ^ 0x5bd1e995, xd, yd, exclusive=self._exclusive(known),
                                            relation_rate=relation_rate)
         self._relation_softmax(len(b))
+        self._adversarial(len(b))
         self.engine.train_step_device(gd, len(g), xd, yd, n, seed=seed, reg_param=reg_param)
         self._state = None
         self._graph_version = None
@@ -482,6 +503,7 @@ class EmbeddingRuntime(EncoderRuntime):
             self._dec_reserved = len(x)
         xd, yd = self._upload("X", x), self._upload("Y", y)
         self._relation_softmax(int(np.count_nonzero(y == 1)))
+        self._adversarial(int(np.count_nonzero(y == 1)))
         self.engine.train_step_device(None, 0, xd, yd, len(x), seed=seed, reg_param=reg_param)
         self._state = None
         self.weights_version += 1
@@ -507,6 +529,7 @@ class EmbeddingRuntime(EncoderRuntime):
         self.engine.negative_sample_device(self._dev["batch"], nb, rate, seed ^ 0x5bd1e995, xd, yd,
                                            exclusive=self._exclusive(known), relation_rate=relation_rate)
         self._relation_softmax(nb)
+        self._adversarial(nb)
         self.engine.train_step_device(None, 0, xd, yd, n, seed=seed, reg_param=reg_param)
         self._state = None
         self.weights_version += 1

@@ -70,6 +70,14 @@ def relation_negative_sample_rate(general_settings):
     return rate
 
 
+def adversarial_temperature(general_settings):
+    """[General] AdversarialTemperature=alpha (absent from the reference's settings files; default 0): the temperature of
+    the self-adversarial weights of every step's negatives.  A non-negative finite float
+    (decoders.bilinear_diag.parse_adversarial_temperature), checked when the model is built."""
+    from .decoders.bilinear_diag import parse_adversarial_temperature
+    return parse_adversarial_temperature(general_settings)
+
+
 def relation_softmax_weight(decoder_settings, relation_count):
     """[Decoder] RelationSoftmaxWeight=lambda (absent from the reference's settings files; default 0): the weight of the
     softmax-over-relations loss term of every step's positives.  A non-negative finite float
@@ -211,6 +219,7 @@ def build_model(settings, train_triplets, entity_count, relation_count):
     settings['Optimizer'].merge(general_settings)
     settings['Evaluation'].merge(general_settings)
     weight = relation_softmax_weight(decoder_settings, relation_count)
+    adversarial_temperature(general_settings)
     encoder = model_builder.build_encoder(encoder_settings, train_triplets)
     model = model_builder.build_decoder(encoder, decoder_settings)
     if weight > 0 and exclusive_negative_sampling(general_settings) and hasattr(model, 'set_relation_softmax_known'):

@@ -213,9 +213,15 @@ enum {
   RGCN_BUF_RELATION_SOFTMAX_ENERGIES = 22, /* float [chunk, padded R]: E[n, r'] = q_n . W_relation[r']; pad columns zero */
   RGCN_BUF_RELATION_SOFTMAX_G = 23,        /* float [chunk, padded R]: G[n, r'], the term's gradient w.r.t. E; pad columns zero */
   RGCN_BUF_RELATION_SOFTMAX_DQ = 24,       /* float [chunk, code width]: dq_n = sum over r' of G[n, r'] W_relation[r'] */
-  RGCN_BUF_ADVERSARIAL_WEIGHTS = 25        /* float [N]: the row weights of the last fused step that ran under
+  RGCN_BUF_ADVERSARIAL_WEIGHTS = 25,       /* float [N]: the row weights of the last fused step that ran under
                                    rgcn_set_adversarial_negatives, N that step's decoder rows.  Every kind,
                                    RGCN_KIND_EMBEDDING included; RGCN_ERR_STATE before such a step */
+  /* the entity-softmax term (rgcn_entity_softmax_device and the fused steps under rgcn_set_entity_softmax), of the LAST
+   * chunk of rows it walked: every kind, RGCN_KIND_EMBEDDING included; RGCN_ERR_STATE before
+   * rgcn_entity_softmax_reserve.  chunk and padded V: rgcn_entity_softmax_plan.  (The energies are not readable: G
+   * overwrites them in place.) */
+  RGCN_BUF_ENTITY_SOFTMAX_G = 26,          /* float [chunk, padded V]: G[m, e], the term's gradient w.r.t. E; pad columns zero */
+  RGCN_BUF_ENTITY_SOFTMAX_DQ = 27          /* float [chunk, code width]: dq_m = sum over e of G[m, e] c[e] */
 };
 
 /*
@@ -570,6 +576,65 @@ rgcn_status rgcn_relation_softmax_device(rgcn_ctx* ctx, const int32_t* positives
                                          int32_t exclusive);
 rgcn_status rgcn_set_relation_softmax(rgcn_ctx* ctx, float weight, int64_t num_positives, int32_t exclusive);
 rgcn_status rgcn_relation_softmax_plan(int64_t max_positives, int32_t num_relations, int32_t code_dim, int64_t out[5]);
+
+/* The softmax-over-entities loss term ("1-N" scoring): for every positive (s_n, r_n, o_n), n < P, the gold object of
+ * (s_n, r_n, ?) and the gold subject of (?, r_n, o_n) against ALL entities at once -- the objective rgcn_rank_device
+ * evaluates, which the sampled corruptions only sample.  Not in the reference.  With c = the codes the decoder reads
+ * ([V, code width]; RGCN_KIND_EMBEDDING: W_emb) and W = W_relation, every positive gives two rows, 2P in all: the object
+ * row m = n (query entity a_m = s_n, gold g_m = o_n) and the subject row m = P + n (a_m = o_n, g_m = s_n):
+ *     q_m      = c[a_m] * W[r_m]                 elementwise, rounded once (the query row of rgcn_rank_device)
+ *     E[m,e]   = q_m . c[e]                      e in [0, V)
+ *     ell_m    = log sum_{e in C_m} exp(E[m,e]) - E[m,g_m]               (the row maximum over C_m is subtracted)
+ *     term     = weight / (2P) * sum_m ell_m
+ *     G[m,e]   = weight / (2P) * (softmax over C_m of E[m,:] at e - [e = g_m]),  0 outside C_m
+ *     dL/dcodes[e] += sum_m G[m,e] q_m           (the candidate side, all V rows)
+ *     dq_m = sum_e G[m,e] c[e];   dL/dcodes[a_m] += dq_m * W[r_m];   dL/dW_relation[r_m] += dq_m * c[a_m]
+ * The codes are a variable in both roles: there is no stop-gradient.  C_m is every entity; with exclusive != 0 it is
+ * {g_m} and every e for which the completed triple -- (s_n, r_n, e) for an object row, (e, r_n, o_n) for a subject row --
+ * is NOT in the set K of rgcn_known_positives_reserve.  A row with C_m = {g_m} contributes exactly 0.  The regulariser
+ * does not change.  Every sum has a fixed order (no atomics on floats): two calls return the same bytes.
+ *
+ * rgcn_entity_softmax_reserve(max_positives) sizes the term's buffers: query rows, their gradients and the energies of
+ * ONE chunk of rows (rgcn_entity_softmax_plan: min(2 max_positives, 65536, what a 256 MB energy buffer holds)); longer
+ * inputs are walked chunk by chunk, which is exact up to summation order.  max_positives <= 0 or above
+ * RGCN_MAX_DECODER_TRIPLES, and EntityCount < 2: RGCN_ERR_INVALID; EntityCount or RelationCount >= 2^24:
+ * RGCN_ERR_UNSUPPORTED; RGCN_ERR_STATE during a capture (it synchronises).
+ *
+ * rgcn_entity_softmax_device(positives_dev int32 [P,3], P, weight, exclusive): stand-alone.  Adds the term to the loss
+ * (rgcn_get_loss) and to the gradients (rgcn_dcodes_device, W_relation's gradient) that the last
+ * rgcn_decoder_loss_backward_device left; RGCN_ERR_STATE without one, before rgcn_entity_softmax_reserve, during a
+ * capture, and with exclusive != 0 without an index.  weight negative or not finite, P <= 0, NULL positives,
+ * EntityCount < 2: RGCN_ERR_INVALID; weight == 0: nothing is launched.  world > 1: RGCN_ERR_UNSUPPORTED.  Ids are
+ * validated on the device: a positive with an id out of range fails the next synchronising call (rgcn_get_loss,
+ * rgcn_sync) with RGCN_ERR_INVALID, its rows of G are zero, nothing is read out of bounds, and the context stays usable.
+ * Asynchronous on the main stream.
+ *
+ * rgcn_set_entity_softmax(weight, num_positives, exclusive): the term inside the fused steps.  Under weight > 0
+ *   - rgcn_train_step_minibatch_device takes its num_edges batch rows as the positives (the leading num_positives of
+ *     them where num_positives > 0 is smaller);
+ *   - rgcn_train_step_device takes the first num_positives rows of its X, whose labels must be 1 (checked on the device:
+ *     RGCN_ERR_INVALID at the next synchronising call); num_positives == 0 means "the minibatch step only" and such a
+ *     step returns RGCN_ERR_STATE; num_positives above the step's N: RGCN_ERR_INVALID;
+ *   - the steps need rgcn_entity_softmax_reserve (RGCN_ERR_STATE), return RGCN_ERR_UNSUPPORTED on a context with
+ *     world > 1 and RGCN_ERR_STATE during a capture;
+ *   - the term runs on the main stream behind the decoder (and behind the relation-softmax term where that is on), and
+ *     the top layer's dropout-scaled operand is formed by the backward pass from the complete dL/dcodes.
+ * weight == 0 (the default) restores every byte the steps produced before these entry points existed.  weight negative
+ * or not finite, num_positives < 0, and weight > 0 with EntityCount < 2: RGCN_ERR_INVALID; weight > 0 during a capture,
+ * and exclusive != 0 without an index: RGCN_ERR_STATE.  The term may be on together with rgcn_set_relation_softmax,
+ * rgcn_set_relation_negatives and rgcn_set_adversarial_negatives: the terms add.
+ *
+ * rgcn_entity_softmax_plan: the term's host-side decisions as a context with these sizes runs them, context-free.
+ * out[0] = chunk (ROWS, two per positive), out[1] = padded V (V up to a multiple of 4: the leading dimension of
+ * RGCN_BUF_ENTITY_SOFTMAX_G), out[2] = the split over the rows of the candidate gradient's product at a full chunk (its
+ * split-K slabs are the term's own, at most 2^24 floats), out[3] = the long-row cut of the query side (query entities
+ * and relations with more rows in a chunk are summed in pieces), out[4] = the rows per piece.  A non-positive argument
+ * or NULL out: RGCN_ERR_INVALID. */
+rgcn_status rgcn_entity_softmax_reserve(rgcn_ctx* ctx, int64_t max_positives);
+rgcn_status rgcn_entity_softmax_device(rgcn_ctx* ctx, const int32_t* positives_dev, int64_t num_positives, float weight,
+                                       int32_t exclusive);
+rgcn_status rgcn_set_entity_softmax(rgcn_ctx* ctx, float weight, int64_t num_positives, int32_t exclusive);
+rgcn_status rgcn_entity_softmax_plan(int64_t max_positives, int32_t num_entities, int32_t code_dim, int64_t out[5]);
 
 /* Self-adversarial negatives (Sun et al., RotatE, 2019) and the weighted decoder under them.  Not in the reference, which
  * weighs every row 1.  A decoder batch of N rows is laid out as every sampler here writes it: the first P rows are the

@@ -35,6 +35,8 @@ BUF_RELATION_SOFTMAX_ENERGIES = 22  # [chunk, padded R]: the energies of the chu
 BUF_RELATION_SOFTMAX_G = 23         # [chunk, padded R]: their gradients
 BUF_RELATION_SOFTMAX_DQ = 24        # [chunk, code width]: the gradients of that chunk's query rows
 BUF_ADVERSARIAL_WEIGHTS = 25        # [N]: the row weights of the last fused step under set_adversarial_negatives
+BUF_ENTITY_SOFTMAX_G = 26           # [chunk, padded V]: the gradients of the chunk of rows the entity-softmax term walked last
+BUF_ENTITY_SOFTMAX_DQ = 27          # [chunk, code width]: the gradients of that chunk's query rows
 KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS, "basis_tdiag": KIND_BASIS_TDIAG,
          "basis_pdiag": KIND_BASIS_PDIAG, "embedding": KIND_EMBEDDING}
 NORMS = {"intended": NORM_INTENDED, "tf_as_executed": NORM_TF_AS_EXECUTED, "none": NORM_NONE, "local": NORM_LOCAL}
@@ -141,6 +143,10 @@ _SIGS = {
     "rgcn_decoder_loss_backward_weighted_device": (C.c_int32, [_P, _P, _P, _P, C.c_int64, C.c_float]),
     "rgcn_adversarial_weights_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int64, C.c_float, _P]),
     "rgcn_set_adversarial_negatives": (C.c_int32, [_P, C.c_float, C.c_int64]),
+    "rgcn_entity_softmax_reserve": (C.c_int32, [_P, C.c_int64]),
+    "rgcn_entity_softmax_device": (C.c_int32, [_P, _P, C.c_int64, C.c_float, C.c_int32]),
+    "rgcn_set_entity_softmax": (C.c_int32, [_P, C.c_float, C.c_int64, C.c_int32]),
+    "rgcn_entity_softmax_plan": (C.c_int32, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "rgcn_rank_reserve": (C.c_int32, [_P, C.c_int64]),
     "rgcn_rank_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
     "rgcn_rank_energies_device": (_P, [_P]),
@@ -250,6 +256,19 @@ def relation_softmax_plan(max_positives, num_relations, code_dim):
     if st != 0:
         raise RgcnError(st, "rgcn_relation_softmax_plan: arguments must be positive")
     return {"chunk": int(out[0]), "padded_r": int(out[1]), "split_k": int(out[2]), "long_row": int(out[3]),
+            "piece": int(out[4])}
+
+
+def entity_softmax_plan(max_positives, num_entities, code_dim):
+    """rgcn_entity_softmax_plan: how a context of these sizes cuts the entity-softmax term's work (context-free, no GPU):
+    the chunk of rows (two per positive), the padded entity count, the split of the candidate gradient's product, the
+    query side's long-row cut and piece"""
+    lib = load_library()
+    out = (C.c_int64 * 5)()
+    st = lib.rgcn_entity_softmax_plan(int(max_positives), int(num_entities), int(code_dim), out)
+    if st != 0:
+        raise RgcnError(st, "rgcn_entity_softmax_plan: arguments must be positive")
+    return {"chunk": int(out[0]), "padded_v": int(out[1]), "split_k": int(out[2]), "long_row": int(out[3]),
             "piece": int(out[4])}
 
 
@@ -688,6 +707,27 @@ class Engine:
         switches the mode off"""
         self._check(self.lib.rgcn_set_adversarial_negatives(self.ctx, C.c_float(temperature), int(num_positives)))
 
+    def entity_softmax_reserve(self, max_positives):
+        """size the entity-softmax term's buffers (rgcn_entity_softmax_reserve): one chunk of rows, two per positive"""
+        self._check(self.lib.rgcn_entity_softmax_reserve(self.ctx, int(max_positives)))
+        # (a smaller request leaves the buffers as they are: the plan is that of the largest one)
+        self._entsm_reserved = max(getattr(self, "_entsm_reserved", 0), int(max_positives))
+        self._entsm_plan = entity_softmax_plan(self._entsm_reserved, self.V, self._code_width)
+
+    def entity_softmax_device(self, positives_dev, num_positives, weight, exclusive=False):
+        """add weight / (2 P) * sum over the object and subject rows of [logsumexp over the entities of E[m, :] - E[m, g_m]]
+        and its gradients to what the last decoder_loss_backward_device left (rgcn_entity_softmax_device); exclusive:
+        entities known for the row's pair (known_positives_reserve) leave the candidate set"""
+        self._check(self.lib.rgcn_entity_softmax_device(self.ctx, positives_dev.ptr, int(num_positives),
+                                                       C.c_float(weight), 1 if exclusive else 0))
+
+    def set_entity_softmax(self, weight, num_positives=0, exclusive=False):
+        """the entity-softmax term inside the fused steps (rgcn_set_entity_softmax): train_step_minibatch_device takes its
+        batch rows as the positives (the leading num_positives where that is smaller), train_step_device the first
+        num_positives rows of X; weight 0 switches it off"""
+        self._check(self.lib.rgcn_set_entity_softmax(self.ctx, C.c_float(weight), int(num_positives),
+                                                    1 if exclusive else 0))
+
     def negative_relation_unresolved(self):
         """relation rows, since the reserve, for which every other relation was a known positive (they kept their first
         draw)"""
@@ -1024,6 +1064,10 @@ class Engine:
             out = np.empty((plan["chunk"], cols), dtype=np.float32)
         elif which == BUF_ADVERSARIAL_WEIGHTS:
             out = np.empty(getattr(self, "_decoder_rows", 0), dtype=np.float32)
+        elif which in (BUF_ENTITY_SOFTMAX_G, BUF_ENTITY_SOFTMAX_DQ):
+            plan = getattr(self, "_entsm_plan", {"chunk": 0, "padded_v": 0})
+            cols = self._code_width if which == BUF_ENTITY_SOFTMAX_DQ else plan["padded_v"]
+            out = np.empty((plan["chunk"], cols), dtype=np.float32)
         elif which == BUF_DSELF_EXCHANGE:
             out = np.empty((self.d, self.d), dtype=np.float32)
         elif which == BUF_NORM_EXCHANGE:

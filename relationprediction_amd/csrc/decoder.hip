@@ -926,11 +926,18 @@ rgcn_status known_positives_reserve(rgcn_ctx* c, const int32_t* triples_host, in
   std::vector<uint64_t> keys;
   const rgcn_status built = known_index_build(triples_host, n, c->V, c->R, &keys, &c->err);
   if (built != RGCN_OK) return built;                 // (the earlier index, if any, still answers)
+  // the same set by (r, o): the entity-softmax term's mask finds a subject row's known subjects as one range of it
+  std::vector<uint64_t> keys_by_object;
+  const rgcn_status built2 = known_index_build_by_object(triples_host, n, c->V, c->R, &keys_by_object, &c->err);
+  if (built2 != RGCN_OK) return built2;
   KnownPositives fresh;
   RGCN_TRY(dmalloc(c, fresh.pool, &fresh.keys, keys.size(), false));
+  RGCN_TRY(dmalloc(c, fresh.pool, &fresh.keys_by_object, keys_by_object.size(), false));
   RGCN_TRY(dmalloc(c, fresh.pool, &fresh.unresolved, 1, true));
   RGCN_TRY(dmalloc(c, fresh.pool, &fresh.relation_unresolved, 1, true));
   RGCN_HIP(c, hipMemcpyAsync(fresh.keys, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+  RGCN_HIP(c, hipMemcpyAsync(fresh.keys_by_object, keys_by_object.data(), keys_by_object.size() * sizeof(uint64_t),
+                             hipMemcpyHostToDevice, c->stream));
   RGCN_HIP(c, hipStreamSynchronize(c->stream));       // `keys` is a local; the counter's memset is ahead of the copy
   fresh.count = (int64_t)keys.size();
   fresh.exclusive = c->known.exclusive;               // a new K under a mode that is on keeps it on

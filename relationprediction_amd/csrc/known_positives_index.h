@@ -58,4 +58,32 @@ inline rgcn_status known_index_build(const int32_t* triples, int64_t num_triples
   return RGCN_OK;
 }
 
+// The same set in the other order: keys <- the sorted unique packed keys (r V + o) V + s, so that the known SUBJECTS of
+// a pair (r, o) are one contiguous range (entity_softmax_range.h), as the known objects of (s, r) are one range of
+// known_index_build's keys.  Same checks, same size; *keys untouched on an error.
+inline rgcn_status known_index_build_by_object(const int32_t* triples, int64_t num_triples, int32_t V, int32_t R,
+                                               std::vector<uint64_t>* keys, std::string* err) {
+  const rgcn_status lim = known_index_limits(V, R, num_triples, err);
+  if (lim != RGCN_OK) return lim;
+  if (num_triples > 0 && !triples) {
+    if (err) *err = "known positives: NULL triples";
+    return RGCN_ERR_INVALID;
+  }
+  for (int64_t e = 0; e < num_triples; ++e) {
+    const int32_t s = triples[3 * e], r = triples[3 * e + 1], o = triples[3 * e + 2];
+    if (s < 0 || s >= V || o < 0 || o >= V || r < 0 || r >= R) {
+      if (err) *err = "known positive " + std::to_string(e) + " has an id out of range";
+      return RGCN_ERR_INVALID;
+    }
+  }
+  std::vector<uint64_t> k((size_t)num_triples);
+  for (int64_t e = 0; e < num_triples; ++e)
+    k[(size_t)e] = ((uint64_t)triples[3 * e + 1] * (uint64_t)V + (uint64_t)triples[3 * e + 2]) * (uint64_t)V +
+                   (uint64_t)triples[3 * e];
+  std::sort(k.begin(), k.end());
+  k.erase(std::unique(k.begin(), k.end()), k.end());
+  keys->swap(k);
+  return RGCN_OK;
+}
+
 }  // namespace rgcn

@@ -68,13 +68,9 @@ __global__ void k_rank_query(const float* __restrict__ codes, const float* __res
                              float* __restrict__ Q, int V, int R) {
   const int row = blockIdx.x;
   if (row >= n) return;
-  int ent = X[3 * row + (predict_object ? 0 : 2)], rel = X[3 * row + 1];
-  // (an id out of range makes the whole call fail -- k_rank_check, read back at the end; until then nothing may fault)
-  if ((unsigned)ent >= (unsigned)V) ent = 0;
-  if ((unsigned)rel >= (unsigned)R) rel = 0;
-  const float* e = codes + (size_t)ent * d;
-  const float* r = wrel + (size_t)rel * d;
-  for (int k = threadIdx.x; k < d; k += blockDim.x) Q[(size_t)row * d + k] = e[k] * r[k];
+  // (an id out of range makes the whole call fail -- k_rank_check, read back at the end; until then nothing may fault;
+  // pair_query.h holds the arithmetic, shared with the entity-softmax term)
+  entity_query_row(codes, wrel, X[3 * row + (predict_object ? 0 : 2)], X[3 * row + 1], row, d, Q, V, R);
 }
 
 // P[n,:] = codes[s_n] * codes[o_n]: the relation side's query row, one rounding per element

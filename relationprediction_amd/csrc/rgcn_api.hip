@@ -323,6 +323,7 @@ static void free_all(rgcn_ctx* c) {
   known_positives_free(c);
   optimizer_free(c);
   relation_softmax_free(c);
+  entity_softmax_free(c);
   adversarial_free(c);
   rank_free(c);
   c->pool.release();
@@ -1225,6 +1226,64 @@ static rgcn_status relsm_step_check(rgcn_ctx* c) {
   return RGCN_OK;
 }
 
+// ---- the entity-softmax term: the relation term's four entry points and rules, over the entities
+rgcn_status rgcn_entity_softmax_reserve(rgcn_ctx* c, int64_t max_positives) {
+  RGCN_NEED(c);
+  if (max_positives <= 0 || max_positives > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "max_positives out of range");
+  if (c->V < 2) RGCN_FAIL(c, RGCN_ERR_INVALID, "the entity softmax needs at least two entities");
+  if (c->V >= (1 << 24) || c->R >= (1 << 24)) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "entity softmax: 2^24 entities or relations, or more");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
+  RGCN_TRY(sync_all(c));
+  return entity_softmax_reserve(c, max_positives);
+}
+
+rgcn_status rgcn_entity_softmax_device(rgcn_ctx* c, const int32_t* pos_dev, int64_t P, float weight, int32_t exclusive) {
+  RGCN_NEED(c);
+  if (!pos_dev || P <= 0 || P > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "bad positives");
+  if (!relsm_weight_ok(weight)) RGCN_FAIL(c, RGCN_ERR_INVALID, "the weight must be finite and not negative");
+  if (c->V < 2) RGCN_FAIL(c, RGCN_ERR_INVALID, "the entity softmax needs at least two entities");
+  if (c->world > 1) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "the entity softmax on a relation-sharded context (world > 1)");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
+  if (!c->dec.loss_valid || !c->fwd_done)
+    RGCN_FAIL(c, RGCN_ERR_STATE, "the term is added to a decoder pass: call rgcn_decoder_loss_backward_device first");
+  if (c->entsm.maxP <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_entity_softmax_reserve first");
+  if (exclusive && c->known.count <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_known_positives_reserve first");
+  if (weight == 0.f) return RGCN_OK;
+  RGCN_TRY(stream_join(c, 2));      // W_relation's gradient may still be on its side stream: the term adds to it
+  return entity_softmax_compute(c, c->embedding ? c->H[0] : c->codes, pos_dev, nullptr, P, weight, exclusive != 0);
+}
+
+rgcn_status rgcn_set_entity_softmax(rgcn_ctx* c, float weight, int64_t num_positives, int32_t exclusive) {
+  RGCN_NEED(c);
+  if (!relsm_weight_ok(weight)) RGCN_FAIL(c, RGCN_ERR_INVALID, "the weight must be finite and not negative");
+  if (num_positives < 0 || num_positives > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "num_positives out of range");
+  if (weight > 0.f) {
+    if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
+    if (c->V < 2) RGCN_FAIL(c, RGCN_ERR_INVALID, "the entity softmax needs at least two entities");
+    if (exclusive && c->known.count <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_known_positives_reserve first");
+  }
+  c->entsm.weight = weight;
+  c->entsm.step_positives = num_positives;
+  c->entsm.exclusive = exclusive != 0;
+  return RGCN_OK;
+}
+
+rgcn_status rgcn_entity_softmax_plan(int64_t max_positives, int32_t num_entities, int32_t code_dim, int64_t out[5]) {
+  if (!out || max_positives <= 0 || num_entities <= 0 || code_dim <= 0) return RGCN_ERR_INVALID;
+  const EntsmPlan p = entsm_plan(max_positives, num_entities, code_dim, kEntsmSlabFloats);      // what a context runs
+  out[0] = p.chunk; out[1] = p.padded_v; out[2] = p.split_k; out[3] = kEntsmLongRow; out[4] = kEntsmPiece;
+  return RGCN_OK;
+}
+
+// what a fused step checks before it queues anything while the term is on (rgcn_set_entity_softmax, weight > 0)
+static rgcn_status entsm_step_check(rgcn_ctx* c) {
+  if (c->world > 1) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "the entity softmax in the step of a relation-sharded context (world > 1)");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "the entity softmax is not built for a hipGraph capture");
+  if (c->entsm.maxP <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_entity_softmax_reserve first");
+  if (c->entsm.exclusive && c->known.count <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_known_positives_reserve first");
+  return RGCN_OK;
+}
+
 rgcn_status rgcn_rank_reserve(rgcn_ctx* c, int64_t max_queries) {
   RGCN_NEED(c);
   if (max_queries <= 0) RGCN_FAIL(c, RGCN_ERR_INVALID, "max_queries must be positive");
@@ -1470,8 +1529,9 @@ rgcn_status rgcn_optimizer_apply(rgcn_ctx* c) { RGCN_NEED(c); return optimizer_a
 // everything of a train step behind the graph preparation: encoder forward, decoder loss + gradients, encoder
 // backward, clip + Adam
 // n_pos > 0: the leading n_pos rows of X are the positives of the relation-softmax term (one GPU; relsm_step_check)
+// n_ent > 0: the leading n_ent rows of X are the positives of the entity-softmax term (one GPU; entsm_step_check)
 static rgcn_status train_step_tail(rgcn_ctx* c, const int32_t* X_dev, const float* Y_dev, int64_t N, uint64_t seed,
-                                   float reg_param, int64_t n_pos = 0, int64_t adv_pos = 0) {
+                                   float reg_param, int64_t n_pos = 0, int64_t adv_pos = 0, int64_t n_ent = 0) {
   RGCN_TRY(forward_all(c, 1, seed, nullptr));
   // adv_pos > 0: self-adversarial weights of the negatives (one GPU; adv_step_check), from the codes the forward pass just
   // left.  On the main stream: the pass reads X alone, so it runs beside the decoder's preparation on side stream 1.
@@ -1517,13 +1577,20 @@ static rgcn_status train_step_tail(rgcn_ctx* c, const int32_t* X_dev, const floa
   // (a highway context forms dS_L itself, from G_L T_L: bwd_layer_partial; under an output transform the top layer's D is
   // dcodes . W_out^T, which bwd_begin forms and scales: a dropout copy of the [V,dc] dcodes is of no use)
   // (with the relation-softmax term on, dL/dcodes is complete only behind the term: bwd_begin scales it)
-  float* ds_ready = (c->world == 1 && !c->highway && !c->out_layer && top_drop.mode != DROP_NONE && n_pos <= 0)
+  // (and likewise with the entity-softmax term on)
+  float* ds_ready = (c->world == 1 && !c->highway && !c->out_layer && top_drop.mode != DROP_NONE && n_pos <= 0 && n_ent <= 0)
                         ? c->dsbuf[c->L & 1] : nullptr;
   RGCN_TRY(decoder_compute(c, c->codes, Y_loc, reg_param, ds_ready, &top_drop, row_w));
   if (n_pos > 0) {
     // the term adds to what the decoder left, W_relation's gradient on side stream 2 included: join it first
     RGCN_TRY(stream_join(c, 2));
     RGCN_TRY(relation_softmax_compute(c, c->codes, X_dev, Y_dev, n_pos, c->relsm.weight, c->relsm.exclusive));
+  }
+  if (n_ent > 0) {
+    // on the main stream behind the decoder and the relation term; it adds to W_relation's gradient, whose last writers
+    // (the decoder's reduce, the relation term's last chunk) are on side stream 2: join it first
+    RGCN_TRY(stream_join(c, 2));
+    RGCN_TRY(entity_softmax_compute(c, c->codes, X_dev, Y_dev, n_ent, c->entsm.weight, c->entsm.exclusive));
   }
   if (c->world > 1) {
     RGCN_TRY(stream_join(c, 2));    // the relation gradient's reduce ran on its own side stream: it is all-reduced too
@@ -1584,6 +1651,7 @@ rgcn_status rgcn_train_step_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t 
   // (the term's refusals first: a sharded context is refused whether or not it has its communicator yet)
   if (c->relsm.weight > 0.f) RGCN_TRY(relsm_step_check(c));
   if (c->adv.temperature > 0.f) RGCN_TRY(adv_step_check(c, N, c->adv.step_positives));
+  if (c->entsm.weight > 0.f) RGCN_TRY(entsm_step_check(c));
   if (c->world > 1 && !c->comm)
     RGCN_FAIL(c, RGCN_ERR_STATE, "world > 1: call rgcn_comm_init first (or drive the phase API yourself)");
   if (c->dec.maxN < N) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_decoder_reserve(ctx, max_triples) first");
@@ -1593,6 +1661,13 @@ rgcn_status rgcn_train_step_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t 
       RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_set_relation_softmax was given num_positives = 0: the minibatch step only");
     if (c->relsm.step_positives > N) RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_set_relation_softmax: num_positives above the batch's rows");
     n_pos = c->relsm.step_positives;
+  }
+  int64_t n_ent = 0;
+  if (c->entsm.weight > 0.f) {
+    if (c->entsm.step_positives <= 0)
+      RGCN_FAIL(c, RGCN_ERR_STATE, "rgcn_set_entity_softmax was given num_positives = 0: the minibatch step only");
+    if (c->entsm.step_positives > N) RGCN_FAIL(c, RGCN_ERR_INVALID, "rgcn_set_entity_softmax: num_positives above the batch's rows");
+    n_ent = c->entsm.step_positives;
   }
   const int64_t adv_pos = c->adv.temperature > 0.f ? c->adv.step_positives : 0;
   if (c->adv.temperature > 0.f) RGCN_TRY(adv_step_buffer(c));
@@ -1614,12 +1689,13 @@ rgcn_status rgcn_train_step_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t 
       RGCN_TRY(relation_softmax_compute(c, c->H[0], X_dev, Y_dev, n_pos, c->relsm.weight, c->relsm.exclusive));
     }
     RGCN_TRY(stream_join(c, 2));
+    if (n_ent > 0) RGCN_TRY(entity_softmax_compute(c, c->H[0], X_dev, Y_dev, n_ent, c->entsm.weight, c->entsm.exclusive));
     c->dec.loss_valid = true;
     if (c->opt.configured) RGCN_TRY(optimizer_step(c));
     return RGCN_OK;
   }
   RGCN_TRY(step_begin(c, tri_dev, E, true));
-  return train_step_tail(c, X_dev, Y_dev, N, seed, reg_param, n_pos, adv_pos);
+  return train_step_tail(c, X_dev, Y_dev, N, seed, reg_param, n_pos, adv_pos, n_ent);
 }
 
 rgcn_status rgcn_prefetch_graph_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t E) {
@@ -1673,6 +1749,8 @@ rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* c, const int32_t* batch_d
   if (relsm_on) RGCN_TRY(relsm_step_check(c));      // (ahead of the communicator's check, as in rgcn_train_step_device)
   const bool adv_on = c->adv.temperature > 0.f;     // rgcn_set_adversarial_negatives; off: the step as it always was
   if (adv_on) RGCN_TRY(adv_step_check(c, N, n));
+  const bool entsm_on = c->entsm.weight > 0.f;      // rgcn_set_entity_softmax; off: the step as it always was
+  if (entsm_on) RGCN_TRY(entsm_step_check(c));
   if (c->world > 1 && !c->comm)
     RGCN_FAIL(c, RGCN_ERR_STATE, "world > 1: call rgcn_comm_init first (or drive the phase API yourself)");
   if (c->dec.maxN < N) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_decoder_reserve(ctx, max_triples) first");
@@ -1697,7 +1775,9 @@ rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* c, const int32_t* batch_d
     RGCN_TRY(negative_sample(c, batch_dev, n, negative_rate, negative_seed, x_scratch_dev, y_scratch_dev));
   // the decoder's batch preparation forks from ev_step_begin onto a side stream: it must see the sampled batch
   RGCN_HIP(c, hipEventRecord(c->ev_step_begin, c->main_stream));
-  return train_step_tail(c, x_scratch_dev, y_scratch_dev, N, dropout_seed, reg_param, relsm_on ? n : 0, adv_on ? n : 0);
+  return train_step_tail(c, x_scratch_dev, y_scratch_dev, N, dropout_seed, reg_param, relsm_on ? n : 0, adv_on ? n : 0,
+                         // (the batch rows, or the leading num_positives of them where rgcn_set_entity_softmax named a count)
+                         entsm_on ? (c->entsm.step_positives > 0 ? std::min<int64_t>(c->entsm.step_positives, n) : n) : 0);
 }
 
 // ---- neighbourhood edge sampler on the device ------------------------------------------
@@ -1930,7 +2010,7 @@ static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* byte
       which != RGCN_BUF_RELATION_ENERGIES && which != RGCN_BUF_NEGATIVE_UNRESOLVED &&
       which != RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED && which != RGCN_BUF_RELATION_SOFTMAX_ENERGIES &&
       which != RGCN_BUF_RELATION_SOFTMAX_G && which != RGCN_BUF_RELATION_SOFTMAX_DQ &&
-      which != RGCN_BUF_ADVERSARIAL_WEIGHTS)
+      which != RGCN_BUF_ADVERSARIAL_WEIGHTS && which != RGCN_BUF_ENTITY_SOFTMAX_G && which != RGCN_BUF_ENTITY_SOFTMAX_DQ)
     RGCN_FAIL(c, RGCN_ERR_STATE, "an RGCN_KIND_EMBEDDING context has the ranking buffers only (no graph, no layer buffers)");
   switch (which) {
     case RGCN_BUF_NEGATIVE_UNRESOLVED:
@@ -1953,6 +2033,12 @@ static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* byte
       if (!c->adv.w || c->adv.last_N <= 0)
         RGCN_FAIL(c, RGCN_ERR_STATE, "no fused step has run under rgcn_set_adversarial_negatives");
       *p = c->adv.w; *bytes = c->adv.last_N * 4; return RGCN_OK;
+    case RGCN_BUF_ENTITY_SOFTMAX_G:
+    case RGCN_BUF_ENTITY_SOFTMAX_DQ:
+      if (c->entsm.maxP <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "no entity-softmax buffers (rgcn_entity_softmax_reserve first)");
+      if (which == RGCN_BUF_ENTITY_SOFTMAX_DQ) { *p = c->entsm.dQ; *bytes = c->entsm.plan.chunk * c->dc * 4; }
+      else { *p = c->entsm.E; *bytes = c->entsm.plan.chunk * c->entsm.plan.padded_v * 4; }
+      return RGCN_OK;
     case RGCN_BUF_EXCHANGE:
       if (!c->exch) RGCN_FAIL(c, RGCN_ERR_STATE, "no exchange buffer on a world == 1 context");
       *p = c->exch; *bytes = Vd; return RGCN_OK;

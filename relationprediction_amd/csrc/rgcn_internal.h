@@ -16,6 +16,7 @@
 #include "dev_pool.h"
 #include "gemm_plan.h"
 #include "negative_exclusive.h"
+#include "entity_softmax_plan.h"
 #include "relation_softmax_plan.h"
 
 namespace rgcn {
@@ -326,6 +327,8 @@ struct NeighborhoodBufs {
 struct KnownPositives {
   DevPool pool;                            // keys, unresolved
   uint64_t* keys = nullptr;                // [count] sorted unique packed keys (r V + s) V + o
+  uint64_t* keys_by_object = nullptr;      // [count] the same set sorted by (r V + o) V + s (known_index_build_by_object):
+                                           // the known subjects of a pair (r, o) are one range (the entity-softmax mask)
   int64_t count = 0;                       // 0: no index
   unsigned long long* unresolved = nullptr;  // rows every entity was known for, since the reserve (RGCN_BUF_NEGATIVE_UNRESOLVED)
   unsigned long long* relation_unresolved = nullptr;  // relation rows every other relation was known for
@@ -372,6 +375,38 @@ struct AdversarialState {
   int64_t last_N = 0;                     // rows of that step; 0: none yet
   float temperature = 0.f;                // 0: off
   int64_t step_positives = 0;             // leading rows of an X/Y step's batch; 0: the minibatch step only
+};
+
+// the entity-softmax term (csrc/entity_softmax.hip; rgcn_entity_softmax_reserve): buffers of ONE chunk of rows, two rows
+// per positive (object row m = n, subject row m = P + n)
+struct EntsmBufs {
+  DevPool pool;
+  int64_t maxP = 0;                       // what the reserve was asked for
+  EntsmPlan plan;                         // chunk, padded V, split, form of the NN product (entity_softmax_plan.h)
+  float *Q = nullptr, *dQ = nullptr;      // [chunk, dc] query rows codes[a] * W_relation[r] and their gradients
+  float* E = nullptr;                     // [chunk, padded V]: the energies, overwritten in place by their gradients G;
+                                          // pad columns stay zero
+  float* Cp = nullptr;                    // plan.nn_padded: [padded V, dc] the codes, pad rows zero (copied every call)
+  float* dC = nullptr;                    // [padded V, dc] G^T Q of the chunk
+  float* loss_part = nullptr;             // one partial per workgroup of the row pass
+  float* slab = nullptr;                  // split-K slabs of dC (GemmCall::slab), plan.split_k x [padded V, dc]
+  size_t slab_floats = 0;
+  int32_t* rows = nullptr;                // [chunk, 4] (query entity, relation, gold, side) of every row; gold -1: a bad row
+  // CSR of the chunk's rows by query entity, then by relation (one after the other through the same buffers), built
+  // with the library's stable sort
+  uint32_t *key = nullptr, *key_s = nullptr, *key_t = nullptr;
+  int32_t *perm = nullptr, *val_t = nullptr;
+  uint16_t* table = nullptr;
+  int32_t *row_ptr = nullptr, *e_other = nullptr;      // [max(V, R) + 1]; the other factor's row of every slot
+  int32_t *long_rows = nullptr, *long_first = nullptr, *long_cnt = nullptr, *nlong = nullptr;   // nlong[0] rows, [1] pieces
+  int32_t *piece_row = nullptr, *piece_k = nullptr;
+  float* piece_slab = nullptr;            // [piece_cap][dc]
+  int32_t long_cap = 0, piece_cap = 0;
+  int64_t last_n = 0;                     // rows of the chunk the buffers hold (RGCN_BUF_ENTITY_SOFTMAX_*); 0: none
+  // rgcn_set_entity_softmax: the term inside the fused steps
+  float weight = 0.f;
+  int64_t step_positives = 0;             // leading rows of an X/Y step's batch; 0: the minibatch step only
+  bool exclusive = false;
 };
 
 struct OptimizerState {
@@ -492,6 +527,7 @@ struct rgcn_ctx {
   rgcn::KnownPositives known;
   int32_t relation_negatives = 0;        // rgcn_set_relation_negatives: relation rows per positive in the fused minibatch step
   rgcn::RelsmBufs relsm;
+  rgcn::EntsmBufs entsm;
   rgcn::AdversarialState adv;
   rgcn::OptimizerState opt;
 
@@ -869,6 +905,15 @@ void relation_softmax_free(rgcn_ctx* c);
 rgcn_status relation_softmax_prepare(rgcn_ctx* c, const int32_t* pos_dev, int64_t P);
 rgcn_status relation_softmax_compute(rgcn_ctx* c, const float* codes, const int32_t* pos_dev, const float* Y_dev, int64_t P,
                                      float weight, bool exclusive);
+// ---- entity_softmax.hip: the softmax-over-entities loss term of the positives (s, r, o) of a step
+rgcn_status entity_softmax_reserve(rgcn_ctx* c, int64_t max_positives);
+void entity_softmax_free(rgcn_ctx* c);
+// adds weight / (2 P) * sum_m ell_m to dec.loss and its gradients to dcodes_own and to W_relation's gradient, all on the
+// current stream, which must be behind the decoder's kernels (and the relation-softmax term's) on every stream.  Y_dev
+// (optional): the labels of the rows, which must all be 1 (error flag 64).  exclusive: entities known for the row's
+// pair leave its candidate set (c->known, both orders)
+rgcn_status entity_softmax_compute(rgcn_ctx* c, const float* codes, const int32_t* pos_dev, const float* Y_dev, int64_t P,
+                                   float weight, bool exclusive);
 
 // ---- comm.cpp (RCCL via dlopen)
 rgcn_status comm_unique_id(uint8_t id[128]);

@@ -37,6 +37,40 @@ def parse_relation_softmax_weight(settings):
     return weight
 
 
+def parse_entity_softmax_weight(settings):
+    """[Decoder] EntitySoftmaxWeight=lambda (not in the reference; absent: 0): the weight of the softmax-over-entities loss
+    term of the positives (include/rgcn.h, rgcn_entity_softmax_device).  A non-negative finite float."""
+    if 'EntitySoftmaxWeight' not in settings:
+        return 0.0
+    value = settings['EntitySoftmaxWeight']
+    try:
+        if isinstance(value, bool):
+            raise ValueError
+        weight = float(str(value).strip())
+    except ValueError:
+        raise ValueError("Decoder.EntitySoftmaxWeight must be a non-negative number, not %r" % (value,))
+    if not np.isfinite(weight) or weight < 0:
+        raise ValueError("Decoder.EntitySoftmaxWeight must be a non-negative finite number, not %r" % (value,))
+    return weight
+
+
+def parse_entity_softmax_positives(settings):
+    """[Decoder] EntitySoftmaxPositives=k (absent: 0, meaning all): the term takes the leading min(k, P) positives of a
+    step -- batches are drawn at random, so a uniform subsample.  A non-negative integer."""
+    if 'EntitySoftmaxPositives' not in settings:
+        return 0
+    value = settings['EntitySoftmaxPositives']
+    try:
+        if isinstance(value, (bool, float)):
+            raise ValueError
+        k = int(str(value).strip())
+    except ValueError:
+        raise ValueError("Decoder.EntitySoftmaxPositives must be a non-negative integer, not %r" % (value,))
+    if k < 0:
+        raise ValueError("Decoder.EntitySoftmaxPositives must be a non-negative integer, not %r" % (value,))
+    return k
+
+
 def parse_adversarial_temperature(settings):
     """[General] AdversarialTemperature=alpha (not in the reference; absent: 0): the temperature of the self-adversarial
     weights of the negatives (include/rgcn.h, rgcn_set_adversarial_negatives).  A non-negative finite float."""
@@ -103,6 +137,38 @@ def relation_softmax_terms(codes, relation_codes, positives, relation_count, wei
     return weight / P * float(ell.sum()), dcodes, d_rel
 
 
+def entity_softmax_terms(codes, relation_codes, positives, weight):
+    """The unmasked entity-softmax term evaluated eagerly in float64 (the numpy port of csrc/entity_softmax.hip): every
+    positive gives an object row (query s, gold o) and a subject row (query o, gold s), each the cross-entropy of its gold
+    entity against all.  Returns (term, dcodes [V,dc], d_rel [rows of relation_codes, dc])."""
+    pos = np.asarray(positives, dtype=np.int64).reshape(-1, 3)
+    c32 = np.asarray(codes, dtype=np.float32)
+    c = c32.astype(np.float64)
+    W = np.asarray(relation_codes, dtype=np.float64)
+    P = len(pos)
+    dcodes, d_rel = np.zeros_like(c), np.zeros_like(W)
+    if P == 0 or weight == 0:
+        return 0.0, dcodes, d_rel
+    a = np.concatenate([pos[:, 0], pos[:, 2]])
+    g = np.concatenate([pos[:, 2], pos[:, 0]])
+    r = np.concatenate([pos[:, 1], pos[:, 1]])
+    q = (c32[a] * np.asarray(relation_codes, dtype=np.float32)[r]).astype(np.float64)      # rounded once, as the device's
+    E = q @ c.T
+    m = E.max(axis=1, keepdims=True)
+    ex = np.exp(E - m)
+    ssum = ex.sum(axis=1, keepdims=True)
+    rows = np.arange(2 * P)
+    ell = np.log(ssum[:, 0]) + m[:, 0] - E[rows, g]
+    G = ex / ssum
+    G[rows, g] -= 1.0
+    G *= weight / (2 * P)
+    dcodes += G.T @ q
+    dq = G @ c
+    np.add.at(dcodes, a, dq * W[r])
+    np.add.at(d_rel, r, dq * c[a])
+    return weight / (2 * P) * float(ell.sum()), dcodes, d_rel
+
+
 class BilinearDiag(Model):
     X = None
     Y = None
@@ -112,6 +178,13 @@ class BilinearDiag(Model):
         self.regularization_parameter = float(self.settings['RegularizationParameter'])
         self.relation_softmax_weight = parse_relation_softmax_weight(self.settings)
         self.adversarial_temperature = parse_adversarial_temperature(self.settings)
+        self.entity_softmax_weight = parse_entity_softmax_weight(self.settings)
+        self.entity_softmax_positives = parse_entity_softmax_positives(self.settings)
+
+    def _entity_softmax_rows(self, x, z):
+        """the positives the eager entity-softmax term takes: the rows with label 1, the leading EntitySoftmaxPositives"""
+        pos = np.asarray(x)[np.asarray(z) == 1]
+        return pos[:self.entity_softmax_positives] if self.entity_softmax_positives > 0 else pos
 
     def set_relation_softmax_known(self, known):
         """the triples whose relations leave a pair's candidate set on the device paths (the training set, under
@@ -125,6 +198,9 @@ class BilinearDiag(Model):
             rt.set_relation_softmax(self.relation_softmax_weight, self.relation_softmax_known)
         if self.adversarial_temperature > 0 or getattr(rt, "_adv_temperature", 0.0) > 0:
             rt.set_adversarial_temperature(self.adversarial_temperature)
+        if self.entity_softmax_weight > 0 or getattr(rt, "_entsm_weight", 0.0) > 0:
+            # (the mask reads the same known positives as the relation term's: ExclusiveNegativeSampling=Yes)
+            rt.set_entity_softmax(self.entity_softmax_weight, self.relation_softmax_known, self.entity_softmax_positives)
         return rt
 
     def local_initialize_train(self):
@@ -156,6 +232,11 @@ class BilinearDiag(Model):
             subject_codes, relation_codes, _ = self.next_component.get_all_codes(mode=mode)
             loss += relation_softmax_terms(subject_codes, relation_codes, self.X.value[np.asarray(z) == 1],
                                            self.relation_count, self.relation_softmax_weight)[0]
+        if self.entity_softmax_weight > 0:
+            # the unmasked softmax-over-entities term over the rows with label 1 (the device paths' small-size cross-check)
+            subject_codes, relation_codes, _ = self.next_component.get_all_codes(mode=mode)
+            loss += entity_softmax_terms(subject_codes, relation_codes, self._entity_softmax_rows(self.X.value, z),
+                                         self.entity_softmax_weight)[0]
         return loss
 
     def local_get_regularization(self):
@@ -328,6 +409,11 @@ class BilinearDiag(Model):
         if self.relation_softmax_weight > 0:
             _, t_codes, t_rel = relation_softmax_terms(subject_codes, relation_codes, x[np.asarray(z) == 1],
                                                        self.relation_count, self.relation_softmax_weight)
+            dcodes = (dcodes + t_codes).astype(dcodes.dtype)
+            d_rel = (d_rel + t_rel).astype(d_rel.dtype)
+        if self.entity_softmax_weight > 0:
+            _, t_codes, t_rel = entity_softmax_terms(subject_codes, relation_codes, self._entity_softmax_rows(x, z),
+                                                     self.entity_softmax_weight)
             dcodes = (dcodes + t_codes).astype(dcodes.dtype)
             d_rel = (d_rel + t_rel).astype(d_rel.dtype)
         return self.next_component.backward((dcodes, d_rel))

@@ -189,6 +189,33 @@ class EncoderRuntime(object):
             self.engine.set_relation_softmax(*state)
             self._relsm_state = state
 
+    def set_entity_softmax(self, weight, known=None, positives=0):
+        """[Decoder] EntitySoftmaxWeight: the weight of the softmax-over-entities term every later train step adds
+        (rgcn_set_entity_softmax), under ExclusiveNegativeSampling the known positives its mask reads, and
+        EntitySoftmaxPositives: how many leading positives of a step the term takes (0: all); weight 0: off."""
+        self._entsm_weight, self._entsm_known, self._entsm_positives = float(weight), known, int(positives)
+
+    def _entity_softmax(self, num_positives):
+        """before a step: the term's buffers, the index of its mask and the engine's setting follow what
+        set_entity_softmax asked for; the engine is told only when something changed"""
+        weight = getattr(self, "_entsm_weight", 0.0)
+        known = getattr(self, "_entsm_known", None) if weight > 0 else None
+        limit = getattr(self, "_entsm_positives", 0)
+        if limit > 0:
+            num_positives = min(int(num_positives), limit)
+        if weight > 0:
+            # (an index the exclusive sampler or the relation term reserved is the same training set: it serves this mask too)
+            if known is not None and getattr(self, "_known", None) is None:
+                self.engine.known_positives_reserve(known)
+                self._known = known
+            if num_positives > getattr(self, "_entsm_reserved", 0):
+                self.engine.entity_softmax_reserve(num_positives)
+                self._entsm_reserved = num_positives
+        state = (weight, int(num_positives), known is not None) if weight > 0 else (0.0, 0, False)
+        if state != getattr(self, "_entsm_state", (0.0, 0, False)):
+            self.engine.set_entity_softmax(*state)
+            self._entsm_state = state
+
     def set_adversarial_temperature(self, temperature):
         """[General] AdversarialTemperature: every later train step weighs each negative by the softmax of its group's
         energies at this temperature (rgcn_set_adversarial_negatives); 0: off."""
@@ -312,6 +339,7 @@ class EncoderRuntime(object):
         self._exclusive(getattr(mb, "known", None))
         self._relation_negatives(relation_rate)
         self._relation_softmax(nb)
+        self._entity_softmax(nb)
         self._adversarial(nb)
         self.engine.train_step_minibatch_device(bd, nb, mb.keep, mb.edge_seed, mb.rate, seed ^ 0x5bd1e995, xd, yd,
                                                 seed=seed, reg_param=reg_param)
@@ -350,6 +378,7 @@ class EncoderRuntime(object):
         gd = st[3] if st is not None else self._upload("graph", g)
         xd, yd = self._upload("X", x), self._upload("Y", y)
         self._relation_softmax(int(np.count_nonzero(y == 1)))      # (the sampler's positives lead the batch)
+        self._entity_softmax(int(np.count_nonzero(y == 1)))
         self._adversarial(int(np.count_nonzero(y == 1)))
         self.engine.train_step_device(gd, len(g), xd, yd, len(x), seed=seed, reg_param=reg_param)
         self._state = None            # activations now belong to this train step's graph
@@ -388,6 +417,7 @@ class EncoderRuntime(object):
         self.engine.negative_sample_device(bd, len(b), rate, seed ^ 0x5bd1e995, xd, yd, exclusive=self._exclusive(known),
                                            relation_rate=relation_rate)
         self._relation_softmax(len(b))
+        self._entity_softmax(len(b))
         self._adversarial(len(b))
         self.engine.train_step_device(gd, len(g), xd, yd, n, seed=seed, reg_param=reg_param)
         self._state = None
@@ -503,6 +533,7 @@ class EmbeddingRuntime(EncoderRuntime):
             self._dec_reserved = len(x)
         xd, yd = self._upload("X", x), self._upload("Y", y)
         self._relation_softmax(int(np.count_nonzero(y == 1)))
+        self._entity_softmax(int(np.count_nonzero(y == 1)))
         self._adversarial(int(np.count_nonzero(y == 1)))
         self.engine.train_step_device(None, 0, xd, yd, len(x), seed=seed, reg_param=reg_param)
         self._state = None
@@ -529,6 +560,7 @@ class EmbeddingRuntime(EncoderRuntime):
         self.engine.negative_sample_device(self._dev["batch"], nb, rate, seed ^ 0x5bd1e995, xd, yd,
                                            exclusive=self._exclusive(known), relation_rate=relation_rate)
         self._relation_softmax(nb)
+        self._entity_softmax(nb)
         self._adversarial(nb)
         self.engine.train_step_device(None, 0, xd, yd, n, seed=seed, reg_param=reg_param)
         self._state = None

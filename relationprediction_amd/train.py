@@ -90,6 +90,20 @@ def relation_softmax_weight(decoder_settings, relation_count):
     return weight
 
 
+def entity_softmax_settings(decoder_settings, entity_count):
+    """[Decoder] EntitySoftmaxWeight=lambda and EntitySoftmaxPositives=k (absent from the reference's settings files;
+    defaults 0 and 0 = all): the weight of the softmax-over-entities loss term of every step's positives and how many
+    leading positives of a step it takes (decoders.bilinear_diag.parse_entity_softmax_*); lambda > 0 needs two entities.
+    Returns (lambda, k)."""
+    from .decoders.bilinear_diag import parse_entity_softmax_positives, parse_entity_softmax_weight
+    weight = parse_entity_softmax_weight(decoder_settings)
+    positives = parse_entity_softmax_positives(decoder_settings)
+    if weight > 0 and int(entity_count) < 2:
+        raise ValueError("Decoder.EntitySoftmaxWeight = %g needs at least two entities, the dataset has %d"
+                         % (weight, int(entity_count)))
+    return weight, positives
+
+
 def make_transform(train_triplets, general_settings, encoder, device_negatives=False, device_dropout=False,
                    device_sampler=False):
     """The reference's t_func (train.py:201-247): minibatch -> (graph_split, X, Y).
@@ -220,10 +234,13 @@ def build_model(settings, train_triplets, entity_count, relation_count):
     settings['Evaluation'].merge(general_settings)
     weight = relation_softmax_weight(decoder_settings, relation_count)
     adversarial_temperature(general_settings)
+    entity_weight, _ = entity_softmax_settings(decoder_settings, entity_count)
     encoder = model_builder.build_encoder(encoder_settings, train_triplets)
     model = model_builder.build_decoder(encoder, decoder_settings)
-    if weight > 0 and exclusive_negative_sampling(general_settings) and hasattr(model, 'set_relation_softmax_known'):
-        # the term's mask follows ExclusiveNegativeSampling: relations that are training facts for a pair do not compete
+    if (weight > 0 or entity_weight > 0) and exclusive_negative_sampling(general_settings) \
+            and hasattr(model, 'set_relation_softmax_known'):
+        # the terms' masks follow ExclusiveNegativeSampling: relations (entities) that are training facts for a pair (for a
+        # row's query) do not compete
         model.set_relation_softmax_known(np.ascontiguousarray(train_triplets, dtype=np.int32))
     return encoder, model
 

@@ -77,9 +77,10 @@ enum { RGCN_KIND_BLOCK = 0, RGCN_KIND_BASIS = 1, RGCN_KIND_BASIS_TDIAG = 2, RGCN
  *   - RGCN_ERR_UNSUPPORTED, the message naming the kind: rgcn_set_graph*, rgcn_prefetch_graph*, rgcn_step_device,
  *     rgcn_train_step_minibatch_device, rgcn_neighborhood_reserve, the phase API (rgcn_forward_begin ... rgcn_backward_end),
  *     rgcn_set_relation_owner, rgcn_capture_begin; rgcn_read_buffer knows RGCN_BUF_RANK_ENERGIES,
- *     RGCN_BUF_RANK_MIXED_SCORES, RGCN_BUF_RELATION_ENERGIES, RGCN_BUF_NEGATIVE_UNRESOLVED and
- *     RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED only (RGCN_ERR_STATE);
- *   - unchanged: rgcn_decoder_*, rgcn_negative_sample_device, rgcn_known_positives_reserve,
+ *     RGCN_BUF_RANK_MIXED_SCORES, RGCN_BUF_RELATION_ENERGIES, RGCN_BUF_NEGATIVE_UNRESOLVED,
+ *     RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED and RGCN_BUF_NEGATIVE_TYPED_OPEN only (RGCN_ERR_STATE);
+ *   - unchanged: rgcn_decoder_*, rgcn_negative_sample_device, rgcn_known_positives_reserve, rgcn_type_sets_reserve,
+ *     rgcn_negative_sample_typed_device, rgcn_rank_typed_device, rgcn_topk_typed_device,
  *     rgcn_negative_sample_exclusive_device, rgcn_negative_sample_relation_device, rgcn_optimizer_*, rgcn_rank_device, rgcn_rank_mixed_device,
  *     rgcn_topk_device, rgcn_score_queries_device, rgcn_topk_mixed_device, rgcn_rank_relation_device,
  *     rgcn_topk_relation_device, rgcn_score_relation_queries_device, parameters, device memory, timer and profile. */
@@ -221,7 +222,12 @@ enum {
    * rgcn_entity_softmax_reserve.  chunk and padded V: rgcn_entity_softmax_plan.  (The energies are not readable: G
    * overwrites them in place.) */
   RGCN_BUF_ENTITY_SOFTMAX_G = 26,          /* float [chunk, padded V]: G[m, e], the term's gradient w.r.t. E; pad columns zero */
-  RGCN_BUF_ENTITY_SOFTMAX_DQ = 27          /* float [chunk, code width]: dq_m = sum over e of G[m, e] c[e] */
+  RGCN_BUF_ENTITY_SOFTMAX_DQ = 27,         /* float [chunk, code width]: dq_m = sum over e of G[m, e] c[e] */
+  RGCN_BUF_NEGATIVE_TYPED_OPEN = 28        /* int64 [1]: negative rows, since the last rgcn_type_sets_reserve, that the
+                                   type-constrained sampler (stand-alone and fused) drew over ALL entities: the list of
+                                   the row's (side, relation) is open, the row's own entity is its only member, an id of
+                                   the row is out of range, or (exclusive) every other member was a known positive.  Every
+                                   kind, RGCN_KIND_EMBEDDING included; RGCN_ERR_STATE without type sets */
 };
 
 /*
@@ -520,6 +526,76 @@ rgcn_status rgcn_negative_sample_relation_device(rgcn_ctx* ctx, const int32_t* b
                                                  int32_t relation_rate, int32_t exclusive, uint64_t seed,
                                                  int32_t* x_out_dev, float* y_out_dev);
 rgcn_status rgcn_set_relation_negatives(rgcn_ctx* ctx, int32_t relation_rate);
+
+/* Type-constrained negatives and queries: corruptions and candidates from the entities the training set has seen in that
+ * slot of that relation (the local closed-world assumption of Krompass et al., 2015; PyKEEN's "pseudo-typed" sampler).
+ * Not in the reference.
+ *
+ * rgcn_type_sets_reserve hands over the triples T once (the training triples, as for rgcn_known_positives_reserve), int32
+ * [num_triples,3] rows (s, r, o) in host memory.  domain(r) = the sorted unique subjects of r in T, range(r) = the sorted
+ * unique objects; list l = side R + r with side 0 = subjects, side 1 = objects (the sampler's coin, the queries'
+ * predict_object).  A list with fewer than RGCN_TYPED_MIN_CANDIDATES members is OPEN and stands for all V entities
+ * everywhere below: a relation T never saw, or a slot with a single filler, constrains nothing.
+ *   - ids are checked on the host: an s or o outside [0, EntityCount) or an r outside [0, RelationCount) is
+ *     RGCN_ERR_INVALID naming the row, and sets reserved earlier stay in place and keep answering;
+ *   - the sets are built on the host, deterministically, and copied to device memory the context owns: ptr int64 [2R+1],
+ *     idx int32 [ptr[2R]], and a bit mask uint32 [2R][W], W = ceil(V/32), bit e of row l set iff e is in list l (an open
+ *     list: all V bits; the pad bits of the last word are clear);
+ *   - 2 R W >= 2^31 or num_triples >= 2^31: RGCN_ERR_UNSUPPORTED (arithmetic, nothing is allocated);
+ *   - num_triples == 0 releases the sets and switches rgcn_set_typed_negatives off; a new T replaces the old one, keeps
+ *     the mode and restarts RGCN_BUF_NEGATIVE_TYPED_OPEN at 0;
+ *   - RGCN_ERR_STATE between rgcn_capture_begin and rgcn_capture_end (it reads host memory and synchronises);
+ *   - every kind, RGCN_KIND_EMBEDDING included, and sharded contexts: the sets are replicated.
+ *
+ * rgcn_negative_sample_typed_device: arguments, layout and labels of rgcn_negative_sample_device, and `exclusive`.  For
+ * negative row i >= n let j = i - n, (s, r, o) = batch[i mod n], T = RGCN_NEG_MAX_DRAWS; draws are bits(tag, index) of `seed`:
+ *   - the coin is the plain sampler's, bits(0x6e65, 2 j) & 1, never redrawn.  L = list (coin, r), m its length, own = the
+ *     entity the coin replaces, p = the position of own in L (a branch-free binary search; -1: absent);
+ *   - the row is TYPED iff its ids are in range, L is not open and n' = m - (p >= 0) >= 1.  Otherwise it is OPEN: drawn
+ *     exactly as rgcn_negative_sample_device draws it -- exclusive != 0: as rgcn_negative_sample_exclusive_device, its
+ *     unresolved count feeding RGCN_BUF_NEGATIVE_UNRESOLVED -- bit for bit, and RGCN_BUF_NEGATIVE_TYPED_OPEN grows by one;
+ *   - a typed row's attempt 0 reads the plain sampler's 48 bits u = bits(0x6e66, 2 j) << 24 | bits(0x6e67, 2 j + 1):
+ *     c = (u n') >> 48, c += (p >= 0 && c >= p), candidate L[c] -- uniform over the OTHER members of L, never own (with
+ *     m = 2 a uniform draw over L would label the positive negative in half the rows; rgcn_negative_sample_relation_device
+ *     skips r the same way);
+ *   - exclusive != 0 on a typed row: a candidate is KNOWN as for the exclusive sampler and is redrawn, attempt
+ *     t = 1 .. T - 1 from bits(0x6e68, 2 (j T + t)) << 24 | bits(0x6e69, 2 (j T + t) + 1) with the same skip; after T
+ *     known candidates the row takes the first member of L that is not known, scanning positions upward cyclically from
+ *     the last candidate and passing over p; if every other member is known the row becomes open (the open exclusive
+ *     decision above, counted).  No typed row is ever left as a known positive;
+ *   - a batch row with an id out of range is open and makes no lookup; nothing is read out of bounds.
+ * The result is a function of (T, K, batch, seed) alone.  Asynchronous.  RGCN_ERR_STATE without sets, with exclusive != 0
+ * and no index of known positives, and between rgcn_capture_begin and rgcn_capture_end (capture is not built for it).
+ * The batch is the tiled one: copies of a triple still share their relation.
+ *
+ * rgcn_rank_typed_device: arguments, validation, comparison, tie rule and chunking of rgcn_rank_device.  Row i's
+ * candidates are C = list (predict_object, r_i) + {gold_i}:
+ *     raw      = #{e in C : score[e] >= score[gold]}
+ *     filtered = raw - #{e in filter and in C : score[e] >= score[gold]} + 1
+ * (a filter entry outside C is not subtracted).  With every list open: rgcn_rank_device's ranks bit for bit.
+ *
+ * rgcn_topk_typed_device: arguments, validation and selection of rgcn_topk_device; a row's exclusion mask starts from the
+ * complement of its list instead of empty, so row i holds the min(k, |list \ excluded|) best members of the list, same
+ * order, same fill values (-1 / -inf).  With every list open: rgcn_topk_device's bytes.
+ * Both: RGCN_ERR_STATE without sets; no mixed form and no relation form; on a relation-sharded context every rank answers
+ * its own queries, as rgcn_rank_device.
+ *
+ * rgcn_set_typed_negatives(ctx, 1): the negative sampling inside rgcn_train_step_minibatch_device is the typed one,
+ * exclusive iff rgcn_set_exclusive_negatives is on, with that call's negative_seed; relation rows
+ * (rgcn_set_relation_negatives) stay as they are, behind the typed entity rows.  RGCN_ERR_STATE without sets and during a
+ * capture, and from the step itself during a capture while the mode is on; world > 1: RGCN_ERR_UNSUPPORTED.  Default 0:
+ * every call produces the bytes and launches it produced before these entry points existed. */
+#define RGCN_TYPED_MIN_CANDIDATES 2
+rgcn_status rgcn_type_sets_reserve(rgcn_ctx* ctx, const int32_t* triples_host, int64_t num_triples);
+rgcn_status rgcn_negative_sample_typed_device(rgcn_ctx* ctx, const int32_t* batch_dev, int64_t n, int32_t rate,
+                                              int32_t exclusive, uint64_t seed, int32_t* x_out_dev, float* y_out_dev);
+rgcn_status rgcn_set_typed_negatives(rgcn_ctx* ctx, int32_t on);
+rgcn_status rgcn_rank_typed_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t num_queries, int32_t predict_object,
+                                   const int64_t* filter_ptr_dev, const int32_t* filter_idx_dev, int32_t* raw_rank_dev,
+                                   int32_t* filtered_rank_dev);
+rgcn_status rgcn_topk_typed_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t num_queries, int32_t predict_object,
+                                   int32_t k, const int64_t* exclude_ptr_dev, const int32_t* exclude_idx_dev,
+                                   int32_t* topk_idx_dev, float* topk_energy_dev);
 
 /* The softmax-over-relations loss term: for every positive (s_n, r_n, o_n), n < P, the gold relation against ALL the
  * others at once -- the objective rgcn_rank_relation_device evaluates, which relation corruptions only sample.  Not in
@@ -883,7 +959,8 @@ rgcn_status rgcn_train_step_device(rgcn_ctx* ctx, const int32_t* triples_dev, in
 /* The reference's t_func after the neighbourhood sampling + update_from_batch (code/train.py:227-245,
  * optimize.py:81-88) in ONE asynchronous call on a graph batch that is resident in HBM: edge dropout (exact `keep`
  * of the n batch edges -> message graph, as rgcn_set_graph_dropout_device with edge_seed), negative sampling
- * (rgcn_negative_sample_device -- under rgcn_set_exclusive_negatives its exclusive form -- on ALL n batch edges -> x_scratch_dev int32 [n*(rate+1),3], y_scratch_dev float
+ * (rgcn_negative_sample_device -- under rgcn_set_exclusive_negatives its exclusive form, under rgcn_set_typed_negatives
+ * rgcn_negative_sample_typed_device -- on ALL n batch edges -> x_scratch_dev int32 [n*(rate+1),3], y_scratch_dev float
  * [n*(rate+1)]), under rgcn_set_relation_negatives(m) n*m relation rows behind them and n*(rate+1+m) rows in all), then the train step of rgcn_train_step_device.  Only the n batch triples cross PCIe per step. */
 rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* ctx, const int32_t* batch_dev, int64_t num_edges, int64_t keep,
                                              uint64_t edge_seed, int32_t negative_rate, uint64_t negative_seed,

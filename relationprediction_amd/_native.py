@@ -37,6 +37,7 @@ BUF_RELATION_SOFTMAX_DQ = 24        # [chunk, code width]: the gradients of that
 BUF_ADVERSARIAL_WEIGHTS = 25        # [N]: the row weights of the last fused step under set_adversarial_negatives
 BUF_ENTITY_SOFTMAX_G = 26           # [chunk, padded V]: the gradients of the chunk of rows the entity-softmax term walked last
 BUF_ENTITY_SOFTMAX_DQ = 27          # [chunk, code width]: the gradients of that chunk's query rows
+BUF_NEGATIVE_TYPED_OPEN = 28        # int64 [1]: negative rows the typed sampler drew over all entities, since the reserve
 KINDS = {"block": KIND_BLOCK, "basis": KIND_BASIS, "basis_tdiag": KIND_BASIS_TDIAG,
          "basis_pdiag": KIND_BASIS_PDIAG, "embedding": KIND_EMBEDDING}
 NORMS = {"intended": NORM_INTENDED, "tf_as_executed": NORM_TF_AS_EXECUTED, "none": NORM_NONE, "local": NORM_LOCAL}
@@ -136,6 +137,11 @@ _SIGS = {
     "rgcn_negative_sample_relation_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint64,
                                                          _P, _P]),
     "rgcn_set_relation_negatives": (C.c_int32, [_P, C.c_int32]),
+    "rgcn_type_sets_reserve": (C.c_int32, [_P, _P, C.c_int64]),
+    "rgcn_negative_sample_typed_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, _P, _P]),
+    "rgcn_set_typed_negatives": (C.c_int32, [_P, C.c_int32]),
+    "rgcn_rank_typed_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
+    "rgcn_topk_typed_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rgcn_relation_softmax_reserve": (C.c_int32, [_P, C.c_int64]),
     "rgcn_relation_softmax_device": (C.c_int32, [_P, _P, C.c_int64, C.c_float, C.c_int32]),
     "rgcn_set_relation_softmax": (C.c_int32, [_P, C.c_float, C.c_int64, C.c_int32]),
@@ -660,6 +666,43 @@ class Engine:
             return
         fn = self.lib.rgcn_negative_sample_exclusive_device if exclusive else self.lib.rgcn_negative_sample_device
         self._check(fn(self.ctx, batch_dev.ptr, int(n), int(rate), C.c_uint64(int(seed)), x_dev.ptr, y_dev.ptr))
+
+    def type_sets_reserve(self, triples):
+        """the per-relation entity sets of `triples` (the training triples) to the device, once (rgcn_type_sets_reserve);
+        an empty array releases them and switches the typed mode off"""
+        t = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
+        self._check(self.lib.rgcn_type_sets_reserve(self.ctx, _ptr(t) if len(t) else None, len(t)))
+
+    def negative_sample_typed_device(self, batch_dev, n, rate, seed, x_dev, y_dev, exclusive=False):
+        """negative_sample_device with every corruption drawn from the entities the type sets hold for that slot of the
+        row's relation (rgcn_negative_sample_typed_device); exclusive: known positives are redrawn inside the list"""
+        self._check(self.lib.rgcn_negative_sample_typed_device(self.ctx, batch_dev.ptr, int(n), int(rate),
+                                                              1 if exclusive else 0, C.c_uint64(int(seed)), x_dev.ptr,
+                                                              y_dev.ptr))
+
+    def set_typed_negatives(self, on):
+        """the negative sampling inside train_step_minibatch_device: the type-constrained one (True) or not"""
+        self._check(self.lib.rgcn_set_typed_negatives(self.ctx, 1 if on else 0))
+
+    def negative_typed_open(self):
+        """negative rows, since the type sets were reserved, that the typed sampler drew over all entities"""
+        out = np.zeros(1, dtype=np.int64)
+        self._check(self.lib.rgcn_read_buffer(self.ctx, BUF_NEGATIVE_TYPED_OPEN, _ptr(out), out.nbytes))
+        return int(out[0])
+
+    def ranks_typed(self, triples, predict_object, filter_ptr, filter_idx):
+        """ranks() among the members of the type set of (predict_object, relation) and the gold entity (include/rgcn.h
+        rgcn_rank_typed_device)"""
+        return self._ranks_staged(triples, filter_ptr, filter_idx,
+                                  lambda n, x, ptr, idx, raw, filt: self.lib.rgcn_rank_typed_device(
+                                      self.ctx, x, n, 1 if predict_object else 0, ptr, idx, raw, filt))
+
+    def topk_typed(self, queries, predict_object, k, exclude_ptr=None, exclude_idx=None):
+        """topk() among the members of the type set of (predict_object, relation) (include/rgcn.h
+        rgcn_topk_typed_device)"""
+        return self._topk_staged(queries, k, exclude_ptr, exclude_idx,
+                                 lambda n, k, x, ptr, idx, ids, energies: self.lib.rgcn_topk_typed_device(
+                                     self.ctx, x, n, 1 if predict_object else 0, k, ptr, idx, ids, energies))
 
     def set_relation_negatives(self, relation_rate):
         """relation rows per batch edge the negative sampling inside train_step_minibatch_device appends (0: none)"""

@@ -11,7 +11,13 @@ BASELINE setting calls; `[General] ExclusiveNegativeSampling=Yes` selects it, on
 `relation_rate = m > 0` (`[General] RelationNegativeSampleRate`, not in the reference): both transforms append m further
 copies of the batch with label 0 whose RELATION is replaced by one of the `relation_count - 1` others, uniformly -- the
 distribution of the device's k_negative_sample_relation, from numpy's stream.  They are drawn after the entity draws, so
-with m = 0 the generator is consumed exactly as before."""
+with m = 0 the generator is consumed exactly as before.
+
+`transform_typed` (`[General] TypeConstrainedNegatives=Yes`, not in the reference): the entity corruptions are drawn from
+the entities `set_type_sets`' triples have seen in that slot of the row's relation, uniformly over the members other than
+the row's own entity -- the decision of the device's k_negative_sample_typed (csrc/negative_typed.h) from numpy's stream:
+a list with fewer than two members, or with no member but the row's own, is open (all entities); `exclusive` redraws known
+positives inside the list up to max_relation_draws times, then scans the list, then falls open."""
 import numpy as np
 
 
@@ -74,6 +80,69 @@ class NegativeSampler(object):
         negatives[choices, 2] = values[choices]
         negatives[~choices, 0] = values[~choices]
         return self._append_relation_rows(triplets, new_indexes, new_labels, rng, False)
+
+    min_typed_candidates = 2        # RGCN_TYPED_MIN_CANDIDATES
+    typed_open = 0                  # rows transform_typed drew over all entities, so far
+
+    def set_type_sets(self, triplets):
+        """domain(r) / range(r) of `triplets`: (subjects by relation, objects by relation), each a sorted array"""
+        subjects, objects = {}, {}
+        for s, r, o in np.asarray(triplets):
+            subjects.setdefault(int(r), set()).add(int(s))
+            objects.setdefault(int(r), set()).add(int(o))
+        self.type_lists = ({r: np.array(sorted(v), dtype=np.int64) for r, v in subjects.items()},
+                           {r: np.array(sorted(v), dtype=np.int64) for r, v in objects.items()})
+
+    def transform_typed(self, triplets, rng=None, exclusive=False):
+        """As `transform`, every corruption from the type list of its (side, relation); `exclusive`: known positives
+        (set_known_positives) are redrawn.  `rng` as in `transform`."""
+        rng = np.random if rng is None else rng
+        triplets = np.asarray(triplets)
+        size_of_batch = len(triplets)
+        number_to_generate = size_of_batch * self.negative_sample_rate
+        new_labels = np.zeros(size_of_batch * (self.negative_sample_rate + 1), dtype=np.float32)
+        new_indexes = np.tile(triplets, (self.negative_sample_rate + 1, 1)).astype(np.int32)
+        new_labels[:size_of_batch] = 1
+        choices = rng.binomial(1, 0.5, number_to_generate)
+        for k in range(number_to_generate):
+            row = new_indexes[size_of_batch + k]
+            coin = int(choices[k])
+            col = 2 if coin else 0
+            s, r, o = int(row[0]), int(row[1]), int(row[2])
+            if coin:
+                def known(e):
+                    return (r, e) in self.objs.get(s, ())
+            else:
+                def known(e):
+                    return (r, e) in self.subs.get(o, ())
+            L = self.type_lists[coin].get(r)
+            done = False
+            if L is not None and len(L) >= self.min_typed_candidates:
+                own = o if coin else s
+                at = int(np.searchsorted(L, own))
+                p = at if at < len(L) and L[at] == own else -1
+                n = len(L) - (1 if p >= 0 else 0)
+                if n >= 1:
+                    for _ in range(self.max_relation_draws if exclusive else 1):
+                        c = int(rng.randint(n))
+                        c += 1 if p >= 0 and c >= p else 0
+                        if not exclusive or not known(int(L[c])):
+                            done = True
+                            break
+                    if not done:            # every draw was known: the first other member that is not, upward from the last
+                        for _ in range(1, len(L)):
+                            c = 0 if c + 1 == len(L) else c + 1
+                            if c != p and not known(int(L[c])):
+                                done = True
+                                break
+                    if done:
+                        row[col] = L[c]
+            if not done:                    # open: the plain (or the exclusive) draw over all entities
+                self.typed_open += 1
+                row[col] = rng.randint(self.n_entities)
+                while exclusive and known(int(row[col])):
+                    row[col] = rng.randint(self.n_entities)
+        return self._append_relation_rows(triplets, new_indexes, new_labels, rng, exclusive)
 
     def set_known_positives(self, triplets):
         self.objs, self.subs = {}, {}

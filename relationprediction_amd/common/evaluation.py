@@ -10,7 +10,11 @@ and materialises a [1000, V] score matrix in numpy for every chunk and side; her
 
 Metric=Accuracy (the *_accuracy.txt datasets: (positive, negative) pairs on consecutive lines; no BASELINE config uses
 it) is the share of pairs whose positive outscores its negative, from one `model.score` of the listed triples (:178-209,
-:311-326)."""
+:311-326).
+
+`[Evaluation] TypeConstrained=Yes` (not in the reference; default No): the ranks of Metric=MRR are taken among the entities
+the training triples have seen in the predicted slot of the triple's relation, and the gold entity (rgcn_rank_typed_device;
+`register_type_sets` hands the training triples over) -- the type-constrained protocol of Krompass et al., 2015."""
 import math
 
 import numpy as np
@@ -176,6 +180,19 @@ def known_completions_csr(pairs, known):
     return ptr, np.asarray(idx, dtype=np.int32)
 
 
+def type_constrained(settings):
+    """[Evaluation] TypeConstrained=Yes|No (default No); it is defined for Metric=MRR only: with RelationMRR or Accuracy
+    it is refused here, when the scorer is built, not at the first report"""
+    value = settings['TypeConstrained'] if 'TypeConstrained' in settings else 'No'
+    if value not in ('Yes', 'No'):
+        raise ValueError("Evaluation.TypeConstrained must be Yes or No, not %r" % (value,))
+    metric = settings['Metric'] if 'Metric' in settings else 'MRR'
+    if value == 'Yes' and metric in ('RelationMRR', 'Accuracy'):
+        raise NotImplementedError("Evaluation.TypeConstrained=Yes with Metric=%s: type-constrained ranks are entity ranks "
+                                  "(Metric=MRR)" % (metric,))
+    return value == 'Yes'
+
+
 class Scorer(object):
     chunk_size = 1000
 
@@ -189,6 +206,12 @@ class Scorer(object):
         self.avg_freq = {}
         self.settings = settings
         self.model = None
+        self.type_constrained = type_constrained(settings)
+        self.type_triples = None
+
+    def register_type_sets(self, train_triples):
+        """the triples whose per-relation subject and object sets the type-constrained ranks are taken among"""
+        self.type_triples = np.ascontiguousarray(train_triples, dtype=np.int32)
 
     @staticmethod
     def extend_triple_dict(dictionary, triplets, object_list=True):
@@ -274,7 +297,13 @@ class Scorer(object):
             if verbose:
                 print("Evaluating %s..." % ("subjects" if subject_side else "objects"))
             ptr, idx = self._filter_csr(triples, subject_side)
-            raw, filtered = self.model.device_ranks(graph, triples, not subject_side, ptr, idx)
+            if self.type_constrained:
+                if self.type_triples is None:
+                    raise ValueError("Evaluation.TypeConstrained=Yes: call register_type_sets(training triples) first")
+                raw, filtered = self.model.device_ranks_typed(graph, triples, not subject_side, ptr, idx,
+                                                              self.type_triples)
+            else:
+                raw, filtered = self.model.device_ranks(graph, triples, not subject_side, ptr, idx)
             fixed = triples[:, 2] if subject_side else triples[:, 0]
             score.append_lines(raw, filtered,
                                [self.in_degree[int(v)] for v in fixed], [self.out_degree[int(v)] for v in fixed],

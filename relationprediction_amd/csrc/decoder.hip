@@ -19,8 +19,10 @@
 
 #include "known_positives_index.h"
 #include "negative_relation.h"
+#include "negative_typed.h"
 #include "rgcn_internal.h"
 #include "row_walk.h"
+#include "type_sets.h"
 
 namespace rgcn {
 
@@ -220,6 +222,35 @@ __global__ void __launch_bounds__(256) k_negative_sample_relation(const int32_t*
   const int64_t i = first + j;
   X[3 * i] = s; X[3 * i + 1] = ch.relation; X[3 * i + 2] = o;
   Y[i] = 0.0f;
+}
+
+// Type-constrained corruptions ([General] TypeConstrainedNegatives; negative_typed.h holds the decision, shared with the
+// host): layout, labels and coin of k_negative_sample; the entity comes from the list of the row's (coin, relation) -- a
+// binary search for the row's own entity (at most 14 dependent loads at FB15k-237, from L2) and one gather -- or, for an
+// open row, from the plain or the exclusive decision, bit for bit.  One thread per row; the open rows of a wave are
+// counted by one atomic.
+__global__ void __launch_bounds__(256) k_negative_sample_typed(const int32_t* __restrict__ batch, int n, int rate,
+                                                               TypeSets sets, KnownIndex known, int exclusive,
+                                                               uint64_t seed, int32_t* __restrict__ X,
+                                                               float* __restrict__ Y,
+                                                               unsigned long long* __restrict__ open,
+                                                               unsigned long long* __restrict__ unresolved) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t total = (int64_t)n * (rate + 1);
+  if (i >= total) return;
+  const int b = (int)(i % n);
+  int s = batch[3 * b], r = batch[3 * b + 1], o = batch[3 * b + 2];
+  bool is_open = false;
+  if (i >= n) {
+    const TypedChoice ch = negative_typed_choice(sets, known, exclusive, seed, (uint64_t)(i - n), s, r, o);
+    if (ch.object_side) o = ch.entity; else s = ch.entity;
+    if (ch.unresolved) atomicAdd(unresolved, 1ull);
+    is_open = ch.open != 0;
+  }
+  const uint64_t opens = __ballot(is_open);
+  if (is_open && (opens & ((1ull << (threadIdx.x & 63u)) - 1ull)) == 0) atomicAdd(open, (unsigned long long)__popcll(opens));
+  X[3 * i] = s; X[3 * i + 1] = r; X[3 * i + 2] = o;
+  Y[i] = i < n ? 1.0f : 0.0f;
 }
 
 // ---- K1: energies, dx, loss terms ---------------------------------------------------------------
@@ -892,6 +923,9 @@ rgcn_status negative_sample_exclusive(rgcn_ctx* c, const int32_t* batch_dev, int
   return RGCN_OK;
 }
 
+static rgcn_status negative_relation_rows(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int rate, int relation_rate,
+                                          bool exclusive, uint64_t seed, int32_t* X, float* Y);
+
 // The entity samplers' rows first, by their own kernels (so those bytes cannot drift), then the relation rows behind them.
 rgcn_status negative_sample_relation(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int rate, int relation_rate,
                                      bool exclusive, uint64_t seed, int32_t* X, float* Y) {
@@ -899,6 +933,11 @@ rgcn_status negative_sample_relation(rgcn_ctx* c, const int32_t* batch_dev, int6
     RGCN_TRY(negative_sample_exclusive(c, batch_dev, n, rate, seed, X, Y));
   else
     RGCN_TRY(negative_sample(c, batch_dev, n, rate, seed, X, Y));
+  return negative_relation_rows(c, batch_dev, n, rate, relation_rate, exclusive, seed, X, Y);
+}
+
+static rgcn_status negative_relation_rows(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int rate, int relation_rate,
+                                          bool exclusive, uint64_t seed, int32_t* X, float* Y) {
   const int64_t first = n * (rate + 1), rows = n * (int64_t)relation_rate;
   if (rows <= 0) return RGCN_OK;
   const KnownPositives& k = c->known;
@@ -910,6 +949,61 @@ rgcn_status negative_sample_relation(rgcn_ctx* c, const int32_t* batch_dev, int6
   RGCN_HIP(c, hipGetLastError());
   // copies of a triple no longer share a relation: the batch is not the tiled one, decoder_prepare takes its general path
   c->dec.tiled_X = nullptr;
+  return RGCN_OK;
+}
+
+// The typed entity rows, then (relation_rate > 0) the relation rows as they always were, behind them.
+rgcn_status negative_sample_typed(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int rate, int relation_rate,
+                                  bool exclusive, uint64_t seed, int32_t* X, float* Y) {
+  const TypeSetsDev& t = c->types;
+  const KnownPositives& k = c->known;
+  if (!t.ready) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_type_sets_reserve first");
+  if (exclusive && k.count <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_known_positives_reserve first");
+  const int64_t total = n * (rate + 1);
+  if (total <= 0) return RGCN_OK;
+  {
+    // (the searches' and the gather's bytes are not in the figure: 4 per probe, from L2)
+    ProfScope ps(c, "negative_sample_typed", 12.0 * n + 16.0 * total, 0);
+    const TypeSets sets{t.ptr, t.idx, c->V, c->R};
+    const KnownIndex index{exclusive ? k.keys : nullptr, exclusive ? k.count : 0, c->V, c->R};
+    hipLaunchKernelGGL(k_negative_sample_typed, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, batch_dev,
+                       (int)n, rate, sets, index, exclusive ? 1 : 0, seed, X, Y, t.open,
+                       exclusive ? k.unresolved : nullptr);
+    RGCN_HIP(c, hipGetLastError());
+  }
+  // copies of a triple still share their relation: the batch is the tiled one
+  c->dec.tiled_X = X;
+  c->dec.tiled_period = n;
+  c->dec.tiled_N = total;
+  return negative_relation_rows(c, batch_dev, n, rate, relation_rate, exclusive, seed, X, Y);
+}
+
+void type_sets_free(rgcn_ctx* c) {
+  c->types.pool.release();
+  c->types = TypeSetsDev();
+}
+
+rgcn_status type_sets_reserve(rgcn_ctx* c, const int32_t* triples_host, int64_t n) {
+  if (n == 0) {
+    type_sets_free(c);
+    return RGCN_OK;
+  }
+  TypeSetsHost h;
+  const rgcn_status built = type_sets_build(triples_host, n, c->V, c->R, &h, &c->err);
+  if (built != RGCN_OK) return built;                 // (the earlier sets, if any, still answer)
+  TypeSetsDev fresh;
+  RGCN_TRY(dmalloc(c, fresh.pool, &fresh.ptr, h.ptr.size(), false));
+  RGCN_TRY(dmalloc(c, fresh.pool, &fresh.idx, h.idx.size(), false));
+  RGCN_TRY(dmalloc(c, fresh.pool, &fresh.mask, h.mask.size(), false));
+  RGCN_TRY(dmalloc(c, fresh.pool, &fresh.open, 1, true));
+  RGCN_HIP(c, hipMemcpyAsync(fresh.ptr, h.ptr.data(), h.ptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  RGCN_HIP(c, hipMemcpyAsync(fresh.idx, h.idx.data(), h.idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  RGCN_HIP(c, hipMemcpyAsync(fresh.mask, h.mask.data(), h.mask.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  RGCN_HIP(c, hipStreamSynchronize(c->stream));       // `h` is a local; the counter's memset is ahead of the copies
+  fresh.words = h.words;
+  fresh.ready = true;
+  fresh.typed = c->types.typed;                       // new sets under a mode that is on keep it on
+  c->types = std::move(fresh);
   return RGCN_OK;
 }
 

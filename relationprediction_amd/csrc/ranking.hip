@@ -56,7 +56,7 @@ namespace {
 // of the (s, r, o) rows -- the gold id of a rank query sits there, the top-k forms never read it -- and the two others
 // are given.
 enum : int { SIDE_SUBJECT = 0, SIDE_OBJECT = 1, SIDE_RELATION = 2 };
-inline int gold_column(int side) { return side == SIDE_OBJECT ? 2 : side == SIDE_RELATION ? 1 : 0; }
+__host__ __device__ inline int gold_column(int side) { return side == SIDE_OBJECT ? 2 : side == SIDE_RELATION ? 1 : 0; }
 
 __device__ __forceinline__ float sigmoid_f32(float x) {
   return (float)(1.0 / (1.0 + exp(-(double)x)));
@@ -166,6 +166,26 @@ k_rank_rows(const float* __restrict__ S, int V, int n, const int64_t* __restrict
   rank_row(row, V, [=](int e) { return s[e] >= t; }, filt_ptr, filt_idx, filt_end, raw_rank, filt_rank, bad);
 }
 
+// The type-constrained twin (rgcn_rank_typed_device): the candidates of a row are the members of list side R + r and the
+// gold entity.  The same lambda serves the filter loop, so a filter entry outside the candidates is not subtracted.  The 32
+// lanes that walk consecutive entities read one mask word (one address per half wave, from L1 / L2: 1/32 of the row's bytes).
+__global__ void __launch_bounds__(256)
+k_rank_rows_typed(const float* __restrict__ S, int V, int n, const int32_t* __restrict__ X, int side, int R,
+                  const uint32_t* __restrict__ type_mask, int words, const int64_t* __restrict__ filt_ptr,
+                  const int32_t* __restrict__ filt_idx, const float* __restrict__ thr, int32_t* __restrict__ raw_rank,
+                  int32_t* __restrict__ filt_rank, int32_t* __restrict__ bad, const int64_t* __restrict__ filt_end) {
+  const int row = blockIdx.x;
+  if (row >= n) return;
+  const float* s = S + (size_t)row * V;
+  const float t = thr[row];
+  int rel = X[3 * row + 1], gold = X[3 * row + gold_column(side)];
+  if ((unsigned)rel >= (unsigned)R) rel = 0;        // (k_rank_check has flagged it: the call fails, nothing may fault)
+  if ((unsigned)gold >= (unsigned)V) gold = 0;
+  const uint32_t* m = type_mask + ((size_t)side * R + rel) * words;
+  rank_row(row, V, [=](int e) { return (((m[e >> 5] >> (e & 31)) & 1u) || e == gold) && s[e] >= t; }, filt_ptr, filt_idx,
+           filt_end, raw_rank, filt_rank, bad);
+}
+
 // m = (float)(w s_a + (1 - w) s_b), both products and the sum in double, rounded once: numpy's float64 expression gives the
 // same bits (no fused multiply-add: a contraction would round the first product differently from the host)
 __device__ __forceinline__ float mixed_score(double w, float ea, float eb) {
@@ -268,10 +288,15 @@ __device__ __forceinline__ void hist_add(uint32_t* hist, uint32_t digit, bool ac
   if (active && (peers & lanes_below()) == 0) atomicAdd(&hist[digit], (uint32_t)__popcll(peers));
 }
 
+// TYPED (rgcn_topk_typed_device): the mask of step 1 starts from the complement of the row of `type_mask` that belongs to
+// list side R + r of the query (X) instead of from zero, so only members of the list are selected; the pad bits of the
+// last word stay clear and `gone` counts entities only.  Everything after step 1 is the same text.
+template <bool TYPED>
 __global__ void __launch_bounds__(TOPK_THREADS)
 k_topk_rows(const float* __restrict__ S, int V, int n, int k, const int64_t* __restrict__ excl_ptr,
             const int32_t* __restrict__ excl_idx, const int64_t* __restrict__ excl_end, int32_t* __restrict__ out_idx,
-            float* __restrict__ out_energy, int32_t* __restrict__ bad) {
+            float* __restrict__ out_energy, int32_t* __restrict__ bad, const int32_t* __restrict__ X, int side, int R,
+            const uint32_t* __restrict__ type_mask) {
   extern __shared__ uint32_t excl_mask[];               // V bits, rounded up to whole words
   __shared__ uint32_t hist[256];
   __shared__ unsigned long long pairs[RGCN_MAX_TOPK];   // key << 32 | ~id
@@ -287,7 +312,15 @@ k_topk_rows(const float* __restrict__ S, int V, int n, int k, const int64_t* __r
   const int words = (V + 31) >> 5;
 
   // 1. exclusion mask
-  for (int w = tid; w < words; w += TOPK_THREADS) excl_mask[w] = 0u;
+  if (TYPED) {
+    int rel = X[3 * row + 1];
+    if ((unsigned)rel >= (unsigned)R) rel = 0;      // (k_rank_check has flagged it: the call fails, nothing may fault)
+    const uint32_t* m = type_mask + ((size_t)side * R + rel) * words;
+    const uint32_t last = (V & 31) ? (1u << (V & 31)) - 1u : 0xffffffffu;
+    for (int w = tid; w < words; w += TOPK_THREADS) excl_mask[w] = ~m[w] & (w + 1 == words ? last : 0xffffffffu);
+  } else {
+    for (int w = tid; w < words; w += TOPK_THREADS) excl_mask[w] = 0u;
+  }
   __syncthreads();
   if (excl_ptr) {
     int64_t fb = excl_ptr[row], fe = excl_ptr[row + 1];
@@ -544,15 +577,21 @@ static rgcn_status run_queries(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int
 
 // k_rank_threshold + k_rank_rows on the side's energies
 static rgcn_status rank_side(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int side, const char* scope, const char* refusal,
-                             const int64_t* filt_ptr, const int32_t* filt_idx, int32_t* raw_out, int32_t* filt_out) {
+                             const int64_t* filt_ptr, const int32_t* filt_idx, int32_t* raw_out, int32_t* filt_out,
+                             bool typed = false) {
   const int cands = candidates(c, side);
   return run_queries(c, X_dev, N, side, true, filt_ptr, refusal, [=](int64_t b, int n, const int32_t* X) -> rgcn_status {
     const float* S = energies(c, side);
     ProfScope ps(c, scope, 4.0 * n * cands, 0);
     hipLaunchKernelGGL(k_rank_threshold, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, S, cands, X, n,
                        gold_column(side), c->ranking.thr);
-    hipLaunchKernelGGL(k_rank_rows, dim3((unsigned)n), dim3(256), 0, c->stream, S, cands, n, filt_ptr + b, filt_idx,
-                       c->ranking.thr, raw_out + b, filt_out + b, c->ranking.bad, filt_ptr + N);
+    if (typed)
+      hipLaunchKernelGGL(k_rank_rows_typed, dim3((unsigned)n), dim3(256), 0, c->stream, S, cands, n, X, side, c->R,
+                         c->types.mask, (int)c->types.words, filt_ptr + b, filt_idx, c->ranking.thr, raw_out + b,
+                         filt_out + b, c->ranking.bad, filt_ptr + N);
+    else
+      hipLaunchKernelGGL(k_rank_rows, dim3((unsigned)n), dim3(256), 0, c->stream, S, cands, n, filt_ptr + b, filt_idx,
+                         c->ranking.thr, raw_out + b, filt_out + b, c->ranking.bad, filt_ptr + N);
     RGCN_HIP(c, hipGetLastError());
     return RGCN_OK;
   });
@@ -562,6 +601,12 @@ rgcn_status rank_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predi
                          const int32_t* filt_idx, int32_t* raw_out, int32_t* filt_out) {
   return rank_side(c, X_dev, N, predict_object, "rank_rows", "rank: entity / relation / filter index out of range", filt_ptr,
                    filt_idx, raw_out, filt_out);
+}
+
+rgcn_status rank_typed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, const int64_t* filt_ptr,
+                               const int32_t* filt_idx, int32_t* raw_out, int32_t* filt_out) {
+  return rank_side(c, X_dev, N, predict_object, "rank_rows_typed", "rank (typed): entity / relation / filter index out of range",
+                   filt_ptr, filt_idx, raw_out, filt_out, true);
 }
 
 rgcn_status rank_relation_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, const int64_t* filt_ptr,
@@ -593,7 +638,9 @@ static rgcn_status topk_rows_configure(rgcn_ctx* c) {
   static uint64_t lds_configured = 0;
   const uint64_t device_bit = c->cfg.device < 64 ? 1ull << c->cfg.device : 0;
   if (!(lds_configured & device_bit)) {
-    RGCN_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_topk_rows), hipFuncAttributeMaxDynamicSharedMemorySize,
+    RGCN_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_topk_rows<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)((size_t)((RGCN_MAX_TOPK_ENTITIES + 31) / 32) * sizeof(uint32_t))));
+    RGCN_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_topk_rows<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)((size_t)((RGCN_MAX_TOPK_ENTITIES + 31) / 32) * sizeof(uint32_t))));
     lds_configured |= device_bit;
   }
@@ -605,12 +652,20 @@ static rgcn_status topk_rows_configure(rgcn_ctx* c) {
 // row (from L2 after the first).
 static rgcn_status topk_rows_launch(rgcn_ctx* c, const char* scope, const float* scores, int cands, int64_t b, int n,
                                     int64_t N, int k, const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out,
-                                    float* val_out) {
+                                    float* val_out, const int32_t* typed_X = nullptr, int side = 0) {
   const size_t mask_bytes = (size_t)((cands + 31) / 32) * sizeof(uint32_t);
   ProfScope ps(c, scope, 5.0 * 4.0 * n * cands + 8.0 * n * k, 0, 4.0 * n * cands + 8.0 * n * k);
-  hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)n), dim3(TOPK_THREADS), mask_bytes, c->stream, scores, cands, n, k,
-                     excl_ptr ? excl_ptr + b : nullptr, excl_idx, excl_ptr ? excl_ptr + N : nullptr,
-                     idx_out + (size_t)b * k, val_out + (size_t)b * k, c->ranking.bad);
+  // typed_X: the rows of the chunk's queries, whose relation picks the list (the type-constrained form)
+  if (typed_X)
+    hipLaunchKernelGGL(k_topk_rows<true>, dim3((unsigned)n), dim3(TOPK_THREADS), mask_bytes, c->stream, scores, cands, n, k,
+                       excl_ptr ? excl_ptr + b : nullptr, excl_idx, excl_ptr ? excl_ptr + N : nullptr,
+                       idx_out + (size_t)b * k, val_out + (size_t)b * k, c->ranking.bad, typed_X, side, c->R,
+                       c->types.mask);
+  else
+    hipLaunchKernelGGL(k_topk_rows<false>, dim3((unsigned)n), dim3(TOPK_THREADS), mask_bytes, c->stream, scores, cands, n, k,
+                       excl_ptr ? excl_ptr + b : nullptr, excl_idx, excl_ptr ? excl_ptr + N : nullptr,
+                       idx_out + (size_t)b * k, val_out + (size_t)b * k, c->ranking.bad, (const int32_t*)nullptr, 0, 0,
+                       (const uint32_t*)nullptr);
   RGCN_HIP(c, hipGetLastError());
   return RGCN_OK;
 }
@@ -629,6 +684,17 @@ rgcn_status topk_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predi
                          const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out, float* energy_out) {
   return topk_side(c, X_dev, N, predict_object, "topk_rows", "topk: entity / relation / exclusion index out of range", k,
                    excl_ptr, excl_idx, idx_out, energy_out);
+}
+
+rgcn_status topk_typed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, int k,
+                               const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out, float* energy_out) {
+  RGCN_TRY(topk_rows_configure(c));
+  return run_queries(c, X_dev, N, predict_object, false, excl_ptr,
+                     "topk (typed): entity / relation / exclusion index out of range",
+                     [=](int64_t b, int n, const int32_t* X) {
+    return topk_rows_launch(c, "topk_rows_typed", c->ranking.s, c->V, b, n, N, k, excl_ptr, excl_idx, idx_out, energy_out,
+                            X, predict_object);
+  });
 }
 
 rgcn_status topk_relation_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int k, const int64_t* excl_ptr,

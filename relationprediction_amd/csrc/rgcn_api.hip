@@ -321,6 +321,7 @@ static void free_all(rgcn_ctx* c) {
   decoder_free(c);
   neighborhood_free(c);
   known_positives_free(c);
+  type_sets_free(c);
   optimizer_free(c);
   relation_softmax_free(c);
   entity_softmax_free(c);
@@ -1165,6 +1166,35 @@ rgcn_status rgcn_set_relation_negatives(rgcn_ctx* c, int32_t relation_rate) {
   return RGCN_OK;
 }
 
+// ---- type-constrained negatives: the per-relation entity sets, the stand-alone call, the mode of the fused step
+rgcn_status rgcn_type_sets_reserve(rgcn_ctx* c, const int32_t* triples_host, int64_t n) {
+  RGCN_NEED(c);
+  if (n < 0 || (n > 0 && !triples_host)) RGCN_FAIL(c, RGCN_ERR_INVALID, "need the triples (or num_triples = 0 to release the type sets)");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
+  RGCN_TRY(sync_all(c));      // (a kernel in flight may still be reading the sets this call replaces)
+  return type_sets_reserve(c, triples_host, n);
+}
+
+rgcn_status rgcn_negative_sample_typed_device(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int32_t rate,
+                                              int32_t exclusive, uint64_t seed, int32_t* x_out_dev, float* y_out_dev) {
+  RGCN_NEED(c);
+  if (n < 0 || rate < 0 || rate > 1024 || (n > 0 && (!batch_dev || !x_out_dev || !y_out_dev)))
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
+  if (n * (int64_t)(rate + 1) > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "batch too large");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
+  return negative_sample_typed(c, batch_dev, n, rate, 0, exclusive != 0, seed, x_out_dev, y_out_dev);
+}
+
+rgcn_status rgcn_set_typed_negatives(rgcn_ctx* c, int32_t on) {
+  RGCN_NEED(c);
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
+  if (on && c->world > 1)
+    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "type-constrained negatives in the fused step of a relation-sharded context (world > 1)");
+  if (on && !c->types.ready) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_type_sets_reserve first");
+  c->types.typed = on != 0;
+  return RGCN_OK;
+}
+
 // ---- the relation-softmax term: reserve, the stand-alone call, the mode of the fused steps, the host plan
 rgcn_status rgcn_relation_softmax_reserve(rgcn_ctx* c, int64_t max_positives) {
   RGCN_NEED(c);
@@ -1330,6 +1360,32 @@ rgcn_status rgcn_rank_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32
                                n >= 0 && (n == 0 || (x_dev && filter_ptr_dev && raw_rank_dev && filtered_rank_dev)), n));
   if (n == 0) return RGCN_OK;
   return rank_compute(c, x_dev, n, predict_object ? 1 : 0, filter_ptr_dev, filter_idx_dev, raw_rank_dev, filtered_rank_dev);
+}
+
+rgcn_status rgcn_rank_typed_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32_t predict_object,
+                                   const int64_t* filter_ptr_dev, const int32_t* filter_idx_dev, int32_t* raw_rank_dev,
+                                   int32_t* filtered_rank_dev) {
+  RGCN_NEED(c);
+  RGCN_TRY(query_preconditions(c, "rgcn_rank_typed_device", 0,
+                               n >= 0 && (n == 0 || (x_dev && filter_ptr_dev && raw_rank_dev && filtered_rank_dev)), n));
+  if (!c->types.ready) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_type_sets_reserve first");
+  if (n == 0) return RGCN_OK;
+  return rank_typed_compute(c, x_dev, n, predict_object ? 1 : 0, filter_ptr_dev, filter_idx_dev, raw_rank_dev,
+                            filtered_rank_dev);
+}
+
+rgcn_status rgcn_topk_typed_device(rgcn_ctx* c, const int32_t* x_dev, int64_t n, int32_t predict_object, int32_t k,
+                                   const int64_t* exclude_ptr_dev, const int32_t* exclude_idx_dev, int32_t* topk_idx_dev,
+                                   float* topk_energy_dev) {
+  RGCN_NEED(c);
+  RGCN_TRY(query_preconditions(c, "rgcn_topk_typed_device", QUERY_TOPK,
+                               n >= 0 && (n == 0 || (x_dev && topk_idx_dev && topk_energy_dev)) &&
+                                   !exclude_ptr_dev == !exclude_idx_dev,
+                               n, 0.f, k));
+  if (!c->types.ready) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_type_sets_reserve first");
+  if (n == 0) return RGCN_OK;
+  return topk_typed_compute(c, x_dev, n, predict_object ? 1 : 0, k, exclude_ptr_dev, exclude_idx_dev, topk_idx_dev,
+                            topk_energy_dev);
 }
 
 const float* rgcn_rank_energies_device(rgcn_ctx* c) { return c ? c->ranking.s : nullptr; }
@@ -1755,6 +1811,8 @@ rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* c, const int32_t* batch_d
     RGCN_FAIL(c, RGCN_ERR_STATE, "world > 1: call rgcn_comm_init first (or drive the phase API yourself)");
   if (c->dec.maxN < N) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_decoder_reserve(ctx, max_triples) first");
   if (adv_on) RGCN_TRY(adv_step_buffer(c));
+  const bool typed = c->types.typed;                 // rgcn_set_typed_negatives; off: the step as it always was
+  if (typed && c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "type-constrained negatives are not built for a hipGraph capture");
   if (relation_rate > 0) {
     if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "relation corruptions are not built for a hipGraph capture");
     if (N > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "batch too large");
@@ -1766,7 +1824,10 @@ rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* c, const int32_t* batch_d
   // the message graph: adopted from the prefetch of this very (batch, keep, seed), or drawn and prepared in line
   RGCN_TRY(step_begin(c, batch_dev, n, false, keep, edge_seed));   // (the fork point is recorded below)
   // the decoder batch: all n batch edges as positives (the dropped ones included) + their corruptions
-  if (relation_rate > 0)
+  if (typed)
+    RGCN_TRY(negative_sample_typed(c, batch_dev, n, negative_rate, relation_rate, c->known.exclusive, negative_seed,
+                                   x_scratch_dev, y_scratch_dev));
+  else if (relation_rate > 0)
     RGCN_TRY(negative_sample_relation(c, batch_dev, n, negative_rate, relation_rate, c->known.exclusive, negative_seed,
                                       x_scratch_dev, y_scratch_dev));
   else if (c->known.exclusive)
@@ -2007,12 +2068,15 @@ rgcn_status rgcn_backward_end(rgcn_ctx* c) { RGCN_NEED(c); return bwd_end(c); }
 static rgcn_status buffer_of(rgcn_ctx* c, int32_t which, void** p, int64_t* bytes) {
   const int64_t Vd = (int64_t)c->V * c->d * 4;
   if (c->embedding && which != RGCN_BUF_RANK_ENERGIES && which != RGCN_BUF_RANK_MIXED_SCORES &&
-      which != RGCN_BUF_RELATION_ENERGIES && which != RGCN_BUF_NEGATIVE_UNRESOLVED &&
+      which != RGCN_BUF_RELATION_ENERGIES && which != RGCN_BUF_NEGATIVE_TYPED_OPEN && which != RGCN_BUF_NEGATIVE_UNRESOLVED &&
       which != RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED && which != RGCN_BUF_RELATION_SOFTMAX_ENERGIES &&
       which != RGCN_BUF_RELATION_SOFTMAX_G && which != RGCN_BUF_RELATION_SOFTMAX_DQ &&
       which != RGCN_BUF_ADVERSARIAL_WEIGHTS && which != RGCN_BUF_ENTITY_SOFTMAX_G && which != RGCN_BUF_ENTITY_SOFTMAX_DQ)
     RGCN_FAIL(c, RGCN_ERR_STATE, "an RGCN_KIND_EMBEDDING context has the ranking buffers only (no graph, no layer buffers)");
   switch (which) {
+    case RGCN_BUF_NEGATIVE_TYPED_OPEN:
+      if (!c->types.ready) RGCN_FAIL(c, RGCN_ERR_STATE, "no type sets (rgcn_type_sets_reserve first)");
+      *p = c->types.open; *bytes = 8; return RGCN_OK;
     case RGCN_BUF_NEGATIVE_UNRESOLVED:
       if (c->known.count <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "no known positives (rgcn_known_positives_reserve first)");
       *p = c->known.unresolved; *bytes = 8; return RGCN_OK;

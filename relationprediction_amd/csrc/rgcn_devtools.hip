@@ -31,7 +31,7 @@ rgcn_status rgcn_debug_device_memory(rgcn_ctx* c, int64_t* blocks, int64_t* byte
   RGCN_NEED(c);
   if (!blocks || !bytes) RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
   *blocks = *bytes = 0;
-  for (const DevPool* p : {&c->pool, &c->g.pool, &c->g_alt.pool, &c->dec.pool, &c->nbr.pool, &c->known.pool, &c->opt.pool,
+  for (const DevPool* p : {&c->pool, &c->g.pool, &c->g_alt.pool, &c->dec.pool, &c->nbr.pool, &c->known.pool, &c->types.pool, &c->opt.pool,
                            &c->opt.part_pool, &c->ranking.pool}) {
     *blocks += p->blocks();
     *bytes += p->bytes();

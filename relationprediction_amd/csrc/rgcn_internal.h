@@ -336,6 +336,19 @@ struct KnownPositives {
   bool exclusive = false;                  // rgcn_set_exclusive_negatives: the fused minibatch step draws exclusively
 };
 
+// per-relation entity sets of the type-constrained sampler and queries (rgcn_type_sets_reserve; type_sets.h builds them,
+// negative_typed.h and ranking.hip read them)
+struct TypeSetsDev {
+  DevPool pool;                            // ptr, idx, mask, open
+  int64_t* ptr = nullptr;                  // [2 R + 1]; list l = side R + r
+  int32_t* idx = nullptr;                  // [ptr[2 R]] members, ascending inside a list
+  uint32_t* mask = nullptr;                // [2 R][words]: bit e of row l (an open list: all V bits; pad bits clear)
+  int64_t words = 0;                       // ceil(V / 32)
+  bool ready = false;                      // false: no sets
+  unsigned long long* open = nullptr;      // rows drawn over all entities, since the reserve (RGCN_BUF_NEGATIVE_TYPED_OPEN)
+  bool typed = false;                      // rgcn_set_typed_negatives: the fused minibatch step draws from the lists
+};
+
 // the relation-softmax term (csrc/relation_softmax.hip; rgcn_relation_softmax_reserve): buffers of ONE chunk of positives
 struct RelsmBufs {
   DevPool pool;
@@ -526,6 +539,7 @@ struct rgcn_ctx {
   rgcn::NeighborhoodBufs nbr;
   rgcn::KnownPositives known;
   int32_t relation_negatives = 0;        // rgcn_set_relation_negatives: relation rows per positive in the fused minibatch step
+  rgcn::TypeSetsDev types;
   rgcn::RelsmBufs relsm;
   rgcn::EntsmBufs entsm;
   rgcn::AdversarialState adv;
@@ -832,6 +846,14 @@ rgcn_status negative_sample_relation(rgcn_ctx* c, const int32_t* batch_dev, int6
 // n == 0 releases it and switches the exclusive mode off
 rgcn_status known_positives_reserve(rgcn_ctx* c, const int32_t* triples_host, int64_t n);
 void known_positives_free(rgcn_ctx* c);
+// the type sets: built on the host from validated limits (type_sets.h), swapped in only when complete; n == 0 releases
+// them and switches the typed mode off
+rgcn_status type_sets_reserve(rgcn_ctx* c, const int32_t* triples_host, int64_t n);
+void type_sets_free(rgcn_ctx* c);
+// the entity rows from the lists of the type sets (c->types.ready; negative_typed.h decides every row), exclusive against
+// the index of known positives; relation_rate > 0: the relation rows of negative_sample_relation behind them
+rgcn_status negative_sample_typed(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int rate, int relation_rate,
+                                  bool exclusive, uint64_t seed, int32_t* X, float* Y);
 rgcn_status decoder_reserve(rgcn_ctx* c, int64_t max_triples);
 void decoder_free(rgcn_ctx* c);
 // N_total > N: X_dev is one rank's slice of a batch of N_total triples (relation-sharded train step); 0: N
@@ -893,6 +915,12 @@ rgcn_status rank_relation_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, 
 rgcn_status topk_relation_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int k, const int64_t* excl_ptr,
                                   const int32_t* excl_idx, int32_t* idx_out, float* energy_out);
 rgcn_status score_relation_queries_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N);
+// the type-constrained forms of rank_compute and topk_compute (c->types.ready): the candidates of a row are the members
+// of list (predict_object, r), and for the ranks the gold entity
+rgcn_status rank_typed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, const int64_t* filt_ptr,
+                               const int32_t* filt_idx, int32_t* raw_out, int32_t* filt_out);
+rgcn_status topk_typed_compute(rgcn_ctx* c, const int32_t* X_dev, int64_t N, int predict_object, int k,
+                               const int64_t* excl_ptr, const int32_t* excl_idx, int32_t* idx_out, float* energy_out);
 void optimizer_free(rgcn_ctx* c);
 // ---- relation_softmax.hip: the softmax-over-relations loss term of the positives (s, r, o) of a step
 rgcn_status relation_softmax_reserve(rgcn_ctx* c, int64_t max_positives);

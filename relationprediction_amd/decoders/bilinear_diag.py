@@ -282,12 +282,18 @@ class BilinearDiag(Model):
         graph-less encoder, Name=embedding)."""
         self._relation_softmax().train_step(graph_edges, x, y, self.regularization_parameter, seed)
 
-    def device_train_step_negatives(self, graph_edges, batch, rate, seed, known=None, relation_rate=0):
+    def device_train_step_negatives(self, graph_edges, batch, rate, seed, known=None, relation_rate=0, types=None):
         """device_train_step with the negatives drawn on the device from `batch`; known: the known positives they avoid
         (ExclusiveNegativeSampling=Yes), None for the plain sampler; relation_rate: relation corruptions per positive
-        (RelationNegativeSampleRate)."""
+        (RelationNegativeSampleRate); types: the triples whose per-relation entity sets the corruptions come from
+        (TypeConstrainedNegatives=Yes), None for all entities."""
+        extra = {} if types is None else {'types': types}
         self._relation_softmax().train_step_device_negatives(graph_edges, batch, rate, self.regularization_parameter, seed,
-                                                             known=known, relation_rate=relation_rate)
+                                                             known=known, relation_rate=relation_rate, **extra)
+
+    def device_negative_typed_open(self):
+        """negative rows the typed device sampler drew over all entities since its type sets were reserved"""
+        return self.next_component.get_runtime().negative_typed_open()
 
     def device_negative_unresolved(self):
         """negative rows the exclusive device sampler could not resolve since its known positives were reserved"""
@@ -328,6 +334,16 @@ class BilinearDiag(Model):
         """Ranks of the gold subjects / objects of `triplets` against every entity, codes from a test-mode
         pass over `graph` (what score_all_subjects / score_all_objects + MrrScore.append_line compute)."""
         return self._scoring_runtime(graph).ranks(triplets, predict_object, filter_ptr, filter_idx)
+
+    def device_ranks_typed(self, graph, triplets, predict_object, filter_ptr, filter_idx, types):
+        """device_ranks among the entities that `types` (the training triples) have seen in the predicted slot of each
+        triple's relation, and the gold entity (rgcn_rank_typed_device): type-constrained ranks."""
+        return self._scoring_runtime(graph).ranks_typed(triplets, predict_object, filter_ptr, filter_idx, types)
+
+    def device_topk_typed(self, graph, queries, predict_object, k, types, exclude_ptr=None, exclude_idx=None):
+        """device_topk among the entities that `types` have seen in the predicted slot of each query's relation
+        (rgcn_topk_typed_device)."""
+        return self._scoring_runtime(graph).topk_typed(queries, predict_object, k, types, exclude_ptr, exclude_idx)
 
     def device_ranks_mixed(self, graph, triplets, predict_object, partner, weight, filter_ptr, filter_idx):
         """device_ranks under weight * this model's score + (1 - weight) * another model's (rgcn_rank_mixed_device):

@@ -257,6 +257,15 @@ class Model(object):
     def device_negative_relation_unresolved(self):
         return self.__delegate__('device_negative_relation_unresolved')
 
+    def device_negative_typed_open(self):
+        return self.__delegate__('device_negative_typed_open')
+
+    def device_ranks_typed(self, *args):
+        return self.__delegate__('device_ranks_typed', *args)
+
+    def device_topk_typed(self, *args, **kwargs):
+        return self.__delegate__('device_topk_typed', *args, **kwargs)
+
     def device_ranks(self, *args):
         return self.__delegate__('device_ranks', *args)
 

@@ -307,12 +307,15 @@ class DeviceNegatives(object):
     `known`: the known positives (ExclusiveNegativeSampling=Yes: the training triples, the same array every iteration) --
     corruptions among them are redrawn (rgcn_negative_sample_exclusive_device); None: the plain sampler.
     `relation_rate`: relation corruptions (s, r', o) per positive behind the entity corruptions (RelationNegativeSampleRate;
-    rgcn_negative_sample_relation_device); 0: none."""
+    rgcn_negative_sample_relation_device); 0: none.
+    `types`: the triples whose per-relation entity sets the entity corruptions are drawn from (TypeConstrainedNegatives=Yes:
+    the training triples, the same array every iteration; rgcn_negative_sample_typed_device); None: all entities."""
 
-    def __init__(self, graph_edges, batch, rate, known=None, relation_rate=0):
+    def __init__(self, graph_edges, batch, rate, known=None, relation_rate=0, types=None):
         self.graph_edges, self.batch, self.rate = graph_edges, batch, int(rate)
         self.known = known
         self.relation_rate = int(relation_rate)
+        self.types = types
 
 
 class DeviceMinibatch(object):
@@ -325,13 +328,15 @@ class DeviceMinibatch(object):
     host and nothing is uploaded, an iteration is three seeds.
 
     `known` as in DeviceNegatives: the step's corruptions avoid these triples (rgcn_set_exclusive_negatives);
-    `relation_rate` as there: the step appends that many relation rows per batch edge (rgcn_set_relation_negatives)."""
+    `relation_rate` as there: the step appends that many relation rows per batch edge (rgcn_set_relation_negatives);
+    `types` as there: the step's entity corruptions come from the type sets (rgcn_set_typed_negatives)."""
 
-    def __init__(self, batch, keep, edge_seed, rate, sample=None, known=None, relation_rate=0):
+    def __init__(self, batch, keep, edge_seed, rate, sample=None, known=None, relation_rate=0, types=None):
         self.batch, self.keep, self.edge_seed, self.rate = batch, int(keep), int(edge_seed), int(rate)
         self.sample = sample
         self.known = known
         self.relation_rate = int(relation_rate)
+        self.types = types
 
 
 class HipOptimizer(object):
@@ -362,6 +367,8 @@ class HipOptimizer(object):
             known = () if processed_batch.known is None else (processed_batch.known,)
             if processed_batch.relation_rate:
                 known = (processed_batch.known, processed_batch.relation_rate)
+            if getattr(processed_batch, 'types', None) is not None:
+                known = (processed_batch.known, processed_batch.relation_rate, processed_batch.types)
             self.model.device_train_step_negatives(processed_batch.graph_edges, processed_batch.batch,
                                                    processed_batch.rate, seed, *known)
             return

@@ -3,7 +3,7 @@
 
     python -m relationprediction_amd.predict --settings settings/gcn_block.exp --dataset data/FB-Toutanova \
         --model models/GcnBlock-3.npz --queries queries.txt --k 10 [--side object|subject|relation] [--keep-known] \
-        [--out FILE] [--settings2 settings/distmult.exp --model2 models/Distmult-3.npz [--weight 0.5]]
+        [--type-constrained] [--out FILE] [--settings2 settings/distmult.exp --model2 models/Distmult-3.npz [--weight 0.5]]
 
 The model is built exactly as train.py builds it (same settings merge, same chain), the checkpoint is one written by
 Model.save, the training graph is encoded once in test mode and the selection runs on the device (rgcn_topk_device:
@@ -19,6 +19,10 @@ Completions already known from train / valid / test are left out unless --keep-k
 
 position counts from 1 (best); score = sigmoid(energy), evaluated in double and rounded once to float32 as everywhere
 else (csrc/ranking.hip).  Answers are ordered by (energy descending, entity id ascending).
+
+--type-constrained (entity sides) answers only entities that the training triples have seen in the predicted slot of
+the query's relation -- the objects of r for --side object, its subjects for --side subject (rgcn_topk_typed_device; a
+relation with fewer than two such entities constrains nothing).  With --side relation or --settings2 it is a ValueError.
 
 --side relation asks which relation holds between two entities (rgcn_topk_relation_device: the energies of every
 relation for the pair, selected on the device alike).  --queries lines are then `subject<TAB>object`, --k is bounded by
@@ -108,6 +112,9 @@ def main(argv=None, out=None):
                              "or the relation of (subject, ?, object)")
     parser.add_argument("--keep-known", action="store_true",
                         help="do not leave out the completions known from train / valid / test")
+    parser.add_argument("--type-constrained", action="store_true",
+                        help="answer only entities the training triples have seen in the predicted slot of the relation "
+                             "(entity sides, one model)")
     parser.add_argument("--out", default=None, help="write the answers here instead of standard output")
     parser.add_argument("--settings2", default=None, help="settings file of model 2: answer under the ensemble of the two")
     parser.add_argument("--model2", default=None, help="checkpoint of model 2")
@@ -119,6 +126,8 @@ def main(argv=None, out=None):
     ensemble = args.settings2 is not None
     if ensemble and args.side == "relation":
         raise ValueError("--side relation has no ensemble form: drop --settings2 / --model2")
+    if args.type_constrained and (ensemble or args.side == "relation"):
+        raise ValueError("--type-constrained is for the entity sides of one model: drop --side relation / --settings2")
     if args.weight is not None and not ensemble:
         raise ValueError("--weight needs --settings2 and --model2")
     weight = 0.5 if args.weight is None else args.weight
@@ -171,6 +180,10 @@ def main(argv=None, out=None):
             partner = second.get_runtime().engine.rank_energies_device()
             top[lo:hi], scores[lo:hi] = model.device_topk_mixed(model.test_graph, queries[lo:hi], predict_object, args.k,
                                                                 partner, weight, chunk_ptr, chunk_idx)
+    elif args.type_constrained:
+        types = np.ascontiguousarray(splits['train'], dtype=np.int32)
+        top, energies = model.device_topk_typed(model.test_graph, queries, predict_object, args.k, types, ptr, idx)
+        scores = sigmoid_f32(energies)
     else:
         top, energies = model.device_topk(model.test_graph, queries, predict_object, args.k, ptr, idx)
         scores = sigmoid_f32(energies)

@@ -157,6 +157,37 @@ class EncoderRuntime(object):
             self._exclusive_on = on
         return on
 
+    def _typed(self, types, fused=False):
+        """TypeConstrainedNegatives: `types` (the training triples, the same array every iteration) moves to the device
+        once (rgcn_type_sets_reserve); None: corruptions over all entities.  fused: the minibatch step's mode follows
+        (rgcn_set_typed_negatives).  Returns whether the stand-alone sampling call is to be the typed one."""
+        on = types is not None
+        cur = getattr(self, "_types", None)
+        # (the same triples under another array object -- the sampler's and the scorer's -- are not reserved again: a
+        # reserve restarts the count of open rows)
+        if on and cur is not types and not (cur is not None and np.shape(cur) == np.shape(types)
+                                            and np.array_equal(cur, types)):
+            self.engine.type_sets_reserve(types)
+            self._types = types
+        if fused and on != getattr(self, "_typed_on", False):
+            self.engine.set_typed_negatives(on)
+            self._typed_on = on
+        return on
+
+    def _draw_negatives(self, bd, nb, rate, seed, xd, yd, known, relation_rate, types):
+        """the stand-alone sampling call of train_step_device_negatives.  types: the entity rows come from the type sets
+        (rgcn_negative_sample_typed_device); with relation rows as well, the call that writes those runs first and the
+        typed entity rows replace the ones it drew (an entity row it could not resolve stays counted)."""
+        exclusive, typed = self._exclusive(known), self._typed(types)
+        if relation_rate or not typed:
+            self.engine.negative_sample_device(bd, nb, rate, seed, xd, yd, exclusive=exclusive, relation_rate=relation_rate)
+        if typed:
+            self.engine.negative_sample_typed_device(bd, nb, rate, seed, xd, yd, exclusive=exclusive)
+
+    def negative_typed_open(self):
+        """negative rows the typed sampler drew over all entities, since the type sets were reserved (0 without them)"""
+        return self.engine.negative_typed_open() if getattr(self, "_types", None) is not None else 0
+
     def _relation_negatives(self, relation_rate):
         """RelationNegativeSampleRate: the fused minibatch step appends this many relation rows per batch edge
         (rgcn_set_relation_negatives); the engine is told when the rate changes.  Returns the rate."""
@@ -337,6 +368,7 @@ class EncoderRuntime(object):
             bd = self._upload("mbatch", b)
         xd, yd = self._buffer("X", 12 * n), self._buffer("Y", 4 * n)
         self._exclusive(getattr(mb, "known", None))
+        self._typed(getattr(mb, "types", None), fused=True)
         self._relation_negatives(relation_rate)
         self._relation_softmax(nb)
         self._entity_softmax(nb)
@@ -385,11 +417,13 @@ class EncoderRuntime(object):
         self._graph_version = None
         self.weights_version += 1
 
-    def train_step_device_negatives(self, graph_edges, batch, rate, reg_param, seed, known=None, relation_rate=0):
+    def train_step_device_negatives(self, graph_edges, batch, rate, reg_param, seed, known=None, relation_rate=0,
+                                    types=None):
         """As train_step, with the decoder batch (positives + `rate` corruptions each) drawn on the device from
         `batch` (rgcn_negative_sample_device): only the two triple lists cross the PCIe bus.  known: the known positives
         the corruptions avoid (rgcn_negative_sample_exclusive_device), None for the plain sampler.  relation_rate: relation
-        corruptions per positive behind them (rgcn_negative_sample_relation_device)."""
+        corruptions per positive behind them (rgcn_negative_sample_relation_device).  types: the triples whose per-relation
+        entity sets the corruptions are drawn from (rgcn_negative_sample_typed_device), None for all entities."""
         g = np.ascontiguousarray(graph_edges, dtype=np.int32).reshape(-1, 3)
         b = np.ascontiguousarray(batch, dtype=np.int32).reshape(-1, 3)
         relation_rate = int(relation_rate)
@@ -414,8 +448,7 @@ class EncoderRuntime(object):
                     buf.free()
                 self._dev[name] = _native.DeviceBuffer(self.engine, nbytes)
         xd, yd = self._dev["X"], self._dev["Y"]
-        self.engine.negative_sample_device(bd, len(b), rate, seed ^ 0x5bd1e995, xd, yd, exclusive=self._exclusive(known),
-                                           relation_rate=relation_rate)
+        self._draw_negatives(bd, len(b), rate, seed ^ 0x5bd1e995, xd, yd, known, relation_rate, types)
         self._relation_softmax(len(b))
         self._entity_softmax(len(b))
         self._adversarial(len(b))
@@ -438,6 +471,20 @@ class EncoderRuntime(object):
     def ranks(self, triples, predict_object, filter_ptr, filter_idx, chunk=2048):
         """Raw / filtered ranks on the codes of a test-mode forward over the fed graph."""
         return self._scoring_engine(chunk).ranks(triples, predict_object, filter_ptr, filter_idx)
+
+    def ranks_typed(self, triples, predict_object, filter_ptr, filter_idx, types, chunk=2048):
+        """ranks() among the entities the per-relation sets of `types` (the training triples) hold for the predicted slot,
+        and the gold entity (rgcn_rank_typed_device)."""
+        engine = self._scoring_engine(chunk)
+        self._typed(types)
+        return engine.ranks_typed(triples, predict_object, filter_ptr, filter_idx)
+
+    def topk_typed(self, queries, predict_object, k, types, exclude_ptr=None, exclude_idx=None, chunk=2048):
+        """topk() among the entities the per-relation sets of `types` hold for the predicted slot
+        (rgcn_topk_typed_device)."""
+        engine = self._scoring_engine(chunk)
+        self._typed(types)
+        return engine.topk_typed(queries, predict_object, k, exclude_ptr, exclude_idx)
 
     def ranks_mixed(self, triples, predict_object, partner, weight, filter_ptr, filter_idx, chunk=2048):
         """ranks() on weight * own score + (1 - weight) * partner score (rgcn_rank_mixed_device); partner: the other
@@ -539,10 +586,12 @@ class EmbeddingRuntime(EncoderRuntime):
         self._state = None
         self.weights_version += 1
 
-    def train_step_device_negatives(self, graph_edges, batch, rate, reg_param, seed, known=None, relation_rate=0):
+    def train_step_device_negatives(self, graph_edges, batch, rate, reg_param, seed, known=None, relation_rate=0,
+                                    types=None):
         """The positives are uploaded once and stay resident while the SAME array object is fed (the training set, every
         iteration); the corruptions are drawn on the device, avoiding `known` if given, `relation_rate` relation
-        corruptions per positive behind them.  A caller that rewrites the array in place feeds a new one."""
+        corruptions per positive behind them, from the type sets of `types` if given.  A caller that rewrites the array in
+        place feeds a new one."""
         if graph_edges is not None:
             raise ValueError("a graph-less encoder takes no graph_edges")
         nb = len(batch)
@@ -557,8 +606,7 @@ class EmbeddingRuntime(EncoderRuntime):
             self._upload("batch", np.ascontiguousarray(batch, dtype=np.int32).reshape(-1, 3))
             self._resident = batch
         xd, yd = self._buffer("X", 12 * n), self._buffer("Y", 4 * n)
-        self.engine.negative_sample_device(self._dev["batch"], nb, rate, seed ^ 0x5bd1e995, xd, yd,
-                                           exclusive=self._exclusive(known), relation_rate=relation_rate)
+        self._draw_negatives(self._dev["batch"], nb, rate, seed ^ 0x5bd1e995, xd, yd, known, relation_rate, types)
         self._relation_softmax(nb)
         self._entity_softmax(nb)
         self._adversarial(nb)

@@ -55,6 +55,16 @@ def exclusive_negative_sampling(general_settings):
     return value == 'Yes'
 
 
+def type_constrained_negatives(general_settings):
+    """[General] TypeConstrainedNegatives=Yes|No (absent from the reference's settings files; default No): every entity
+    corruption is drawn from the entities the training triples have seen in that slot of the row's relation
+    (NegativeSampler.transform_typed; on the device rgcn_negative_sample_typed_device)"""
+    value = general_settings['TypeConstrainedNegatives'] if 'TypeConstrainedNegatives' in general_settings else 'No'
+    if value not in ('Yes', 'No'):
+        raise ValueError("General.TypeConstrainedNegatives must be Yes or No, not %r" % (value,))
+    return value == 'Yes'
+
+
 def relation_negative_sample_rate(general_settings):
     """[General] RelationNegativeSampleRate=m (absent from the reference's settings files; default 0): m further negative
     rows (s, r', o) per positive, with a relation other than r -- what trains W_relation to tell relations apart for a
@@ -115,6 +125,10 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
     RelationNegativeSampleRate=m: m relation corruptions per positive follow the entity corruptions, on the host path
     through the sampler's relation_rate, on the device paths through `relation_rate=` of the batch objects.
 
+    TypeConstrainedNegatives=Yes: the entity corruptions come from the per-relation entity sets of the training triples --
+    on the host path through ns.transform_typed, on the device paths through `types=` of the batch objects (the runtime
+    reserves the sets on the device once).
+
     Every batch is a function of ONE seed drawn from numpy's global generator when the batch is requested, so
     batches can be built ahead of time by background threads (`t_func.seeded(data, seed)`, used by
     optimization.optimize.HipOptimizer) and still come out in a reproducible order; `t_func(data)` itself
@@ -127,6 +141,12 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
     ns.set_known_positives(train_triplets)
     exclusive = exclusive_negative_sampling(general_settings)
     host_negatives = ns.transform_exclusive if exclusive else ns.transform
+    typed = type_constrained_negatives(general_settings)
+    if typed:
+        ns.set_type_sets(train_triplets)
+
+        def host_negatives(x, rng):
+            return ns.transform_typed(x, rng, exclusive=exclusive)
     # (a graph-less encoder never reaches the sampler: settings/distmult.exp carries a GraphBatchSize it does not use)
     use_sampler = 'GraphBatchSize' in general_settings and encoder.needs_graph()
     if use_sampler and int(general_settings['GraphBatchSize']) > len(train_triplets):
@@ -137,6 +157,7 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
     local = threading.local()            # the native sampler keeps per-sample state: one per thread
     train_arr = np.ascontiguousarray(train_triplets, dtype=np.int32)     # (what the device sampler keeps resident)
     known = train_arr if exclusive else None      # K is the training set alone, as the reference registers it
+    extra = {'types': train_arr} if typed else {}   # (the type sets are the training set's too)
 
     def seeded(x, seed):
         rng = np.random.RandomState(seed)
@@ -146,7 +167,8 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
             # whole training set.  Device negatives: the array itself is handed on, so that the step finds it resident
             if device_negatives:
                 from .optimization.optimize import DeviceNegatives
-                return DeviceNegatives(None, arr, ns.negative_sample_rate, known=known, relation_rate=relation_rate)
+                return DeviceNegatives(None, arr, ns.negative_sample_rate, known=known, relation_rate=relation_rate,
+                                       **extra)
             return host_negatives(arr, rng)
         if use_sampler and device_sampler and device_dropout:
             # all three draws on the device: the iteration is three seeds, nothing is built on the host or uploaded
@@ -155,7 +177,7 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
             split_size = int(float(general_settings['GraphSplitSize']) * size)
             sample = (train_arr, size, rng.randint(0, 2 ** 31 - 1))
             return DeviceMinibatch(None, split_size, rng.randint(0, 2 ** 31 - 1), ns.negative_sample_rate, sample=sample,
-                                   known=known, relation_rate=relation_rate)
+                                   known=known, relation_rate=relation_rate, **extra)
         if use_sampler:
             if not hasattr(local, 'sampler'):
                 local.sampler = _native.NeighborhoodSampler(train_triplets, int(general_settings['EntityCount']))
@@ -168,13 +190,13 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
         if device_dropout:            # both draws (kept edges, corruptions) are made by the device step
             from .optimization.optimize import DeviceMinibatch
             return DeviceMinibatch(graph_batch, split_size, rng.randint(0, 2 ** 31 - 1), ns.negative_sample_rate,
-                                   known=known, relation_rate=relation_rate)
+                                   known=known, relation_rate=relation_rate, **extra)
         graph_split_ids = rng.choice(graph_batch_ids, size=split_size, replace=False)
         graph_split = train_triplets[graph_split_ids]
         if device_negatives:          # corruptions are drawn by the device step (optimize.DeviceNegatives)
             from .optimization.optimize import DeviceNegatives
             return DeviceNegatives(graph_split, graph_batch, ns.negative_sample_rate, known=known,
-                                   relation_rate=relation_rate)
+                                   relation_rate=relation_rate, **extra)
         t = host_negatives(graph_batch, rng)
         return (graph_split, t[0], t[1])
 
@@ -182,6 +204,7 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
         return seeded(x, np.random.randint(0, 2 ** 31 - 1))
 
     t_func.seeded = seeded
+    t_func.sampler = ns
     return t_func
 
 
@@ -202,7 +225,18 @@ def report_unresolved_relation_negatives(model):
     return count
 
 
-def make_validation_function(scorer, metric, test_triplets, model):
+def report_typed_open_negatives(model, sampler=None):
+    """with each validation report under TypeConstrainedNegatives: how many negative rows were drawn over all entities so
+    far because their list is open, holds no entity but the row's own, or (exclusive) held known positives only -- the
+    device sampler's count, with --host-negatives the host sampler's"""
+    count = model.device_negative_typed_open() or 0
+    if sampler is not None:
+        count += sampler.typed_open
+    print("Type-constrained negative sampling: %d rows so far were drawn over all entities (open lists)" % count)
+    return count
+
+
+def make_validation_function(scorer, metric, test_triplets, model, typed_sampler=False):
     """code/train.py:114-128: the early-stopping score is the validation split's filtered MRR (Metric=MRR), its filtered
     relation MRR (RelationMRR) or its accuracy; the test split's table is printed with every report."""
     def score_validation_data(validation_data):
@@ -214,6 +248,8 @@ def make_validation_function(scorer, metric, test_triplets, model):
         score_summary.pretty_print()
         report_unresolved_negatives(model)
         report_unresolved_relation_negatives(model)
+        if typed_sampler is not False:
+            report_typed_open_negatives(model, typed_sampler)
         return early_stopping
     return score_validation_data
 
@@ -342,17 +378,25 @@ def main(argv=None):
     scorer.register_model(model)
     scorer.finalize_frequency_computation(np.concatenate((train_triplets, valid_triplets, test_triplets), axis=0))
 
-    score_validation_data = make_validation_function(scorer, evaluation_settings['Metric'], test_triplets, model)
+    if scorer.type_constrained:
+        scorer.register_type_sets(train_triplets)
+
+    t_func = None
+    if 'NegativeSampleRate' in general_settings:
+        t_func = make_transform(train_triplets, general_settings, encoder, device_negatives=not args.host_negatives,
+                                device_dropout=not (args.host_negatives or args.host_edge_dropout),
+                                device_sampler=not args.host_sampler)
+    typed_sampler = False          # False: no report; None: the device's count; a sampler: the host's beside it
+    if t_func is not None and type_constrained_negatives(general_settings):
+        typed_sampler = t_func.sampler if args.host_negatives else None
+    score_validation_data = make_validation_function(scorer, evaluation_settings['Metric'], test_triplets, model,
+                                                     typed_sampler=typed_sampler)
 
     opp.set_early_stopping_score_function(score_validation_data)
     print(len(train_triplets))
 
-    if 'NegativeSampleRate' in general_settings:
-        opp.set_sample_transform_function(make_transform(train_triplets, general_settings, encoder,
-                                                         device_negatives=not args.host_negatives,
-                                                         device_dropout=not (args.host_negatives or
-                                                                             args.host_edge_dropout),
-                                                         device_sampler=not args.host_sampler))
+    if t_func is not None:
+        opp.set_sample_transform_function(t_func)
 
     initialize_model(model, train_triplets)
     if args.resume is not None:

@@ -1,6 +1,7 @@
 """Float64 mirror of the self-adversarial negative weights and of the weighted DistMult decoder (include/rgcn.h,
 rgcn_adversarial_weights_device, rgcn_decoder_loss_backward_weighted_device, rgcn_set_adversarial_negatives), and the
-inputs of the GPU cases.  numpy only; shared by the host and the GPU tests.
+inputs of the GPU cases.  numpy, and scipy's sparse product for the decoder's scatter-adds (the oracle's own for the fp32 restatement);
+shared by the host and the GPU tests.
 
 A batch of N rows: the first P are the positives, row i >= P is a negative of positive i mod P, K = N / P - 1.
 
@@ -61,8 +62,42 @@ def weights(codes, w_relation, X, P, alpha):
     return {"w": w, "x": x, "tol": tol, "K": K}
 
 
-def weighted_decoder(codes, w_relation, X, Y, w, reg, codes_override=None):
-    """float64 mirror of the weighted decoder: dict loss, dx [N], dcodes [V,dc], dW [rows of w_relation, dc]"""
+def _weighted_decoder_float32(codes, w_relation, X, Y, w, reg):
+    """the same weighted formula as oracle.distmult_loss_and_grads states the unweighted one: float32 products and sums,
+    float64 only where that function uses it (the mean of the per-row terms and the regulariser)"""
+    F = np.float32
+    x = np.asarray(X, dtype=np.int64).reshape(-1, 3)
+    c, W = np.asarray(codes, dtype=F), np.asarray(w_relation, dtype=F)
+    z, wt = np.asarray(Y, dtype=F), np.asarray(w, dtype=F)
+    e1, r, e2 = c[x[:, 0]], W[x[:, 1]], c[x[:, 2]]
+    n, d = e1.shape
+    en = np.sum(e1 * r * e2, axis=1).astype(F)
+    per = (1 - z) * en + (np.log1p(np.exp(-np.abs(en))) + np.maximum(-en, 0))
+    loss = (wt * per).mean(dtype=np.float64) + reg * (np.mean(e1.astype(np.float64) ** 2) + np.mean(r.astype(np.float64) ** 2)
+                                                      + np.mean(e2.astype(np.float64) ** 2))
+    ex = np.exp(-np.abs(en))
+    sig = np.where(en >= 0, 1.0 / (1.0 + ex), ex / (1.0 + ex))
+    dx = (wt * ((sig - z) / n)).astype(F)
+    dcol = n * d
+
+    def segment_sum(index, rows, M):           # the oracle's _segment_sum_rows: a float32 sparse product
+        import scipy.sparse as sp
+        S = sp.csr_matrix((np.ones(n, dtype=F), (index, np.arange(n))), shape=(rows, n), dtype=F)
+        return np.asarray(S @ M.astype(F), dtype=F)
+
+    dcodes = segment_sum(x[:, 0], c.shape[0], dx[:, None] * (r * e2) + reg * 2.0 * e1 / dcol) \
+        + segment_sum(x[:, 2], c.shape[0], dx[:, None] * (e1 * r) + reg * 2.0 * e2 / dcol)
+    dW = segment_sum(x[:, 1], W.shape[0], dx[:, None] * (e1 * e2) + reg * 2.0 * r / dcol)
+    return {"loss": float(loss), "dx": dx, "dcodes": dcodes.astype(F), "dW": dW, "x": en}
+
+
+def weighted_decoder(codes, w_relation, X, Y, w, reg, codes_override=None, dtype=np.float64):
+    """float64 mirror of the weighted decoder: dict loss, dx [N], dcodes [V,dc], dW [rows of w_relation, dc], x [N] the
+    energies, per [N] the unweighted per-row loss terms (loss - mean(w per) + mean(per) is the unit-weight loss).
+    dtype = numpy.float32: the fp32 restatement of the same formula, the yardstick of an l2 comparison."""
+    if np.dtype(dtype) == np.float32:
+        return _weighted_decoder_float32(codes, w_relation, X, Y, w, reg)
+    assert np.dtype(dtype) == np.float64, dtype
     x = np.asarray(X, dtype=np.int64).reshape(-1, 3)
     y = np.asarray(Y, dtype=np.float64)
     w = np.asarray(w, dtype=np.float64)
@@ -75,12 +110,14 @@ def weighted_decoder(codes, w_relation, X, Y, w, reg, codes_override=None):
     loss = (w * per).mean() + reg * (np.mean(e1 ** 2) + np.mean(r ** 2) + np.mean(e2 ** 2))
     dx = w * (1.0 / (1.0 + np.exp(-en)) - y) / n
     k = reg * 2.0 / (n * d)
-    dcodes = np.zeros_like(c)
-    np.add.at(dcodes, x[:, 0], dx[:, None] * (r * e2) + k * e1)
-    np.add.at(dcodes, x[:, 2], dx[:, None] * (e1 * r) + k * e2)
-    dW = np.zeros_like(W)
-    np.add.at(dW, x[:, 1], dx[:, None] * (e1 * e2) + k * r)
-    return {"loss": float(loss), "dx": dx, "dcodes": dcodes, "dW": dW, "x": en}
+    def scatter_add(index, rows, M):            # out[index[i]] += M[i], as a float64 sparse product (helpers.chunked_distmult_float64's)
+        import scipy.sparse as sp
+        return np.asarray(sp.csr_matrix((np.ones(n), (index, np.arange(n))), shape=(rows, n)) @ M)
+
+    dcodes = scatter_add(x[:, 0], c.shape[0], dx[:, None] * (r * e2) + k * e1) \
+        + scatter_add(x[:, 2], c.shape[0], dx[:, None] * (e1 * r) + k * e2)
+    dW = scatter_add(x[:, 1], W.shape[0], dx[:, None] * (e1 * e2) + k * r)
+    return {"loss": float(loss), "dx": dx, "dcodes": dcodes, "dW": dW, "x": en, "per": per}
 
 
 def adversarial_decoder(codes, w_relation, X, Y, P, alpha, reg):

@@ -7,10 +7,14 @@ decoder_compute (relationprediction_amd/csrc/decoder.hip) picks, from d, R and t
              in LDS when R * 128 B <= 64 KB), else k_dec_entity_grad<1, TPR>; rows of more than kDecLongRow incidences
              in pieces of kDecPiece, added up by k_dec_long_finish<VEC>;
   relation   chunks of kDecChunk triples per relation, summed by k_dec_rel_reduce (4 chunks per turn + a tail);
-  tiled      a batch the negative sampler wrote: only the first copies sorted by relation (k_dec_expand).
+  tiled      a batch the negative sampler wrote: only the first copies sorted by relation (k_dec_expand);
+  weighted   row_weights != nullptr: the WEIGHTED instantiation of either energy kernel (a weight per row on its loss
+             term and its dx).
 The functions below mirror those formulas on the host, so that a test can state which cell a case reaches; DECODER_CASES
-is one case per cell and per boundary of the formulas, each with a batch of exact incidence and relation counts.
-tests/test_decoder_grid.py keeps the table honest without a GPU; tests/test_gpu_train_step.py runs it.
+is one case per cell and per boundary of the formulas, each with a batch of exact incidence and relation counts;
+WEIGHTED_CASES holds every energy cell under both orders, with case_weights' built weights.
+tests/test_decoder_grid.py keeps the table honest without a GPU; tests/test_gpu_train_step.py and
+tests/test_gpu_decoder_weighted_grid.py run it.
 """
 import numpy as np
 
@@ -149,6 +153,11 @@ DECODER_GRID = [
     # and a single triple (period 1: decoded as an ordinary batch)
     _case(20, tag="_rate10", rate=10, n=1500), _case(66, tag="_rate1", rate=1, n=1500),
     _case(20, tag="_rate0", rate=0, n=N_DEC), _case(20, tag="_n1", rate=10, n=1),
+    # the tiled order at every other energy cell (rate 1: TILED_REL_COUNTS[2]): scalar T 1 / T 4, the unfused <1>, vec4 T 2
+    # (two band passes) and T 4 (three), the unfused <4> (five band passes, k_dec_rel_partial in the tiled order)
+    _case(9, tag="_rate1", rate=1, n=1500), _case(130, tag="_rate1", rate=1, n=1500),
+    _case(258, tag="_rate1", rate=1, n=1500), _case(260, tag="_rate1", rate=1, n=1500),
+    _case(516, tag="_rate1", rate=1, n=1500), _case(1028, tag="_rate1", rate=1, n=1500),
 ]
 
 DECODER_CASES = {c["name"]: c for c in DECODER_GRID}
@@ -217,3 +226,144 @@ def host_tiled(batch, rate, V, seed):
     Y = np.zeros(n * (rate + 1), np.float32)
     Y[:n] = 1
     return X.astype(np.int32), Y
+
+
+# ----------------------------------------------------------------------------- row weights
+# decoder_compute launches k_dec_energy_rel<VEC, T, WEIGHTED> / k_dec_energy<VEC, WEIGHTED> with WEIGHTED = (row_weights
+# != nullptr): every energy cell exists twice.  A weight is read by ROW ID (Wt[m0], Wt[m1], Wt[n]) while the fused kernel
+# walks the relation order (permr), which for a tiled batch is another order again: the weighted cells are held at both.
+def is_tiled(case):
+    """decoder.hip:1118-1119: decoder_prepare orders a batch the sampler wrote by its first copies when its period is > 1
+    (rate 0, a single copy, included)."""
+    return case.get("rate") is not None and case["n"] > 1
+
+
+def weighted_cell_of(case, weighted=True):
+    """(energy cell, entity-gradient cell, WEIGHTED): decoder.hip:1192, 1204 -- `row_weights == nullptr` picks the plain
+    instantiation of the same cell."""
+    return energy_cell(case["d"]), entity_cell(case["d"], case["R"]), bool(weighted)
+
+
+def weighted_energy_cell(case):
+    """The entry of WEIGHTED_ENERGY_CELLS a weighted run of the case executes."""
+    return energy_cell(case["d"]), "tiled" if is_tiled(case) else "plain"
+
+
+WEIGHTED_ENERGY_CELLS = [(cell, order) for cell in ENERGY_CELLS for order in ("plain", "tiled")]
+
+# one untiled case per energy cell, the saturated energies, the global relation band, and every batch the sampler tiled
+WEIGHTED_CASES = ("dec_d20", "dec_d260", "dec_d516", "dec_d1028", "dec_d9", "dec_d66", "dec_d130", "dec_d258",
+                  "dec_d20_sat", "dec_d260_R513") + \
+    tuple(c["name"] for c in DECODER_GRID if is_tiled(c))
+
+# batches with relation rows behind the entity rows (rgcn_negative_sample_relation_device: N = n (rate + 1 + m), the
+# general path of decoder_prepare): scalar T 2, vec4 T 2, the unfused <4>
+RELATION_ROW_CASES = ("dec_d66_rate1", "dec_d260_rate1", "dec_d1028_rate1")
+RELATION_ROW_RATE, RELATION_ROW_M = 1, 2
+
+HIGH = 2.5                            # a weight above it is one of the constructed `large` ones
+
+
+def relation_order(rel, period=None):
+    """permr (decoder.hip:66-81, 1135): the triples sorted by relation, stably; a tiled batch has only its first `period`
+    rows sorted, with the copies p + period, p + 2 period, ... of row p directly behind it."""
+    rel = np.asarray(rel)
+    if period is None:
+        return np.argsort(rel, kind="stable")
+    first = np.argsort(rel[:period], kind="stable")
+    return (first[:, None] + period * np.arange(len(rel) // period)[None, :]).reshape(-1)
+
+
+def relation_segments(rel, order):
+    """[(relation, rows in relation-sort order)] of the relations that have a triple."""
+    rs = np.asarray(rel)[order]
+    cut = np.flatnonzero(np.diff(rs)) + 1
+    return [(int(rs[a]), order[a:b]) for a, b in zip(np.r_[0, cut], np.r_[cut, len(rs)])]
+
+
+def lone_rows(rows):
+    """k_dec_energy_rel's walk over one relation's rows (decoder.hip:764-765, 791-793): chunks of kDecChunk, wave w of a
+    chunk takes its triples w, w + 4, w + 8, ... two per turn.  A wave with an odd number of them takes its last one
+    alone (`two` false, w1 = 0.f).  Returns, per chunk, the rows taken alone."""
+    out = []
+    for lo in range(0, len(rows), CHUNK):
+        chunk = rows[lo:lo + CHUNK]
+        mine = [chunk[w::4] for w in range(4)]
+        out.append([int(m[-1]) for m in mine if len(m) % 2 == 1])
+    return out
+
+
+def entity_rows(X, e):
+    X = np.asarray(X).reshape(-1, 3)
+    return np.flatnonzero((X[:, 0] == e) | (X[:, 2] == e))
+
+
+def case_weights(case, N, X=None):
+    """float32 [N] row weights for the decoded batch of a case (N = n x copies), BUILT so that a wrong index shows:
+
+      * uniform in [0, 3) from the case's seed; a seventh of the rows exactly 0, another seventh exactly 1 -- copy j of
+        triple g is 0 / 1 when (a_g + j) mod 7 is 0 / 1, a_g drawn per triple, so that the weights of the copies of a
+        triple are pairwise different (up to 7 copies; with more, two zeros or two ones of a triple are 7 copies apart and
+        everything else is pairwise different);
+      * the last triple in relation-sort order of every relation with an odd count is above HIGH;
+      * every relation r < 7 with at least two triples holds an exact 0 and a weight above HIGH, and every chunk of it in
+        which a wave takes a triple alone (lone_rows) has such a triple above HIGH;
+      * every entity e < 7 that at least two rows touch holds a row of weight 0 and one above HIGH.
+
+    Without X the relation of row i is that of row i mod n of case_batch (what the entity samplers keep) and the entities
+    are those of the first copies, which they keep too; the order is the tiled one for a tiled case.  With X (a batch whose
+    later rows changed their relation: the relation rows) relations, entities and the general order are taken from it."""
+    n = case["n"]
+    assert N % n == 0, (N, n)
+    k = N // n
+    if X is None:
+        batch, _ = case_batch(case)
+        assert k == 1 or case.get("rate") is not None
+        rel, ents = np.tile(batch[:, 1], k), batch
+        order = relation_order(rel, n if is_tiled(case) else None)
+    else:
+        X = np.asarray(X).reshape(N, 3)
+        rel, ents = X[:, 1], X
+        order = relation_order(rel)
+    rng = np.random.RandomState(case["seed"] + 100003)
+    w = (rng.rand(N) * 3.0).astype(np.float32)
+    kind = (np.tile(rng.randint(0, 7, n), k) + np.arange(N) // n) % 7
+    w[kind == 0] = 0.0
+    w[kind == 1] = 1.0
+    pinned = np.zeros(N, bool)
+
+    def high(rows):
+        """a row of `rows` above HIGH: one that is already, else the first free one is made so"""
+        have = [i for i in rows if w[i] > HIGH]
+        free = [i for i in rows if not pinned[i]]
+        assert have or free, (case["name"], "no free row for a large weight")
+        i = have[0] if have else free[0]
+        if not have:
+            w[i] = np.float32(HIGH + 0.005 + 0.49 * rng.rand())
+        pinned[i] = True
+
+    def zero(rows):
+        have = [i for i in rows if w[i] == 0]
+        free = [i for i in rows if not pinned[i] and not (w[i % n::n] == 0).any()]
+        assert have or free, (case["name"], "no free row for a zero weight")
+        i = have[0] if have else free[0]
+        w[i] = 0.0
+        pinned[i] = True
+
+    segments = relation_segments(rel, order)
+    for r, rows in segments:
+        if len(rows) % 2 == 1:
+            high(rows[-1:])
+    for r, rows in segments:
+        if r < len(REL_COUNTS) and len(rows) >= 2:
+            high(rows)
+            zero(rows)
+            for alone in lone_rows(rows):
+                if alone:
+                    high(alone)
+    for e in range(len(ENTITY_COUNTS)):
+        rows = entity_rows(ents, e)
+        if len(rows) >= 2:
+            high(rows)
+            zero(rows)
+    return w

@@ -68,8 +68,9 @@ def test_device_decoder_matches_oracle(native, V, R, d, nb, E, hub):
         assert_close(grads[k], og[k], rel=5e-4, name=k)
 
 
-def _decoder_grads(native, V, R, d, nb, X, Y, lines, top_dropout=0.0, seed=3):
-    """loss, dL/dcodes (and its dropped copy's consumer: the encoder's gradients) with the entity-gradient form chosen"""
+def _decoder_grads(native, V, R, d, nb, X, Y, lines, top_dropout=0.0, seed=3, weights=None):
+    """loss, dL/dcodes (and its dropped copy's consumer: the encoder's gradients) with the entity-gradient form chosen;
+    weights (float32 [N]): through rgcn_decoder_loss_backward_weighted_device"""
     import os
     L = 1
     params, triples, _, _ = make_case(V, R, d, L, "block", nb, 4 * V, seed=seed)
@@ -82,9 +83,15 @@ def _decoder_grads(native, V, R, d, nb, X, Y, lines, top_dropout=0.0, seed=3):
         eng.forward(train=False)
         eng.decoder_reserve(len(X))
         xd, yd = eng.to_device(X), eng.to_device(Y)
-        eng.decoder_loss_backward_device(xd, yd, len(X), 0.01)
+        if weights is None:
+            eng.decoder_loss_backward_device(xd, yd, len(X), 0.01)
+        else:
+            wd = eng.to_device(np.ascontiguousarray(weights, dtype=np.float32))
+            eng.decoder_loss_backward_weighted_device(xd, yd, wd, len(X), 0.01)
         out = eng.loss(), eng.dcodes(), eng.get_grad("W_relation")
         xd.free(); yd.free()
+        if weights is not None:
+            wd.free()
     finally:
         eng.close()
         if old is None:
@@ -662,10 +669,17 @@ def _grid_energies(codes, w_rel, X):
     return (c[X[:, 0]] * w[X[:, 1]] * c[X[:, 2]]).sum(1)
 
 
-def _grid_decoder(native, c):
+def _grid_decoder(native, c, runs=None, weights=None, relation_rate=0, temperature=None, reg=0.01):
     """A test-mode forward and the device decoder on a grid case: (codes, W_relation, X, Y, loss, dcodes, dW_relation).
     A tiled case's batch goes through the device negative sampler; a saturating one has W_relation scaled (after a
-    first forward: the codes do not depend on it) until its largest |energy| is c["saturate"]."""
+    first forward: the codes do not depend on it) until its largest |energy| is c["saturate"].
+
+    runs: several decoder calls on that one context and batch instead, each (loss, dcodes, dW_relation), returned as
+    (codes, W_relation, X, Y, w, {run: outputs}): "plain" rgcn_decoder_loss_backward_device, "null" / "ones" / "weighted"
+    rgcn_decoder_loss_backward_weighted_device with a NULL pointer / all ones / w, "flipped" w again with the label of
+    every zero-weight row replaced by 1 - y.  w = weights(c, N, X), or with a temperature the device's own
+    rgcn_adversarial_weights_device(P = n) read back.  relation_rate = m: the sampler's relation rows behind the entity
+    rows, N = n (rate + 1 + m)."""
     V, R, d, nb = c["V"], c["R"], c["d"], c["nb"]
     params, triples, _, _ = make_case(V, R, d, 1, "block", nb, 4 * V, seed=c["seed"])
     batch, Y = dg.case_batch(c)
@@ -687,15 +701,49 @@ def _grid_decoder(native, c):
             xd, yd = eng.to_device(X), eng.to_device(Y)
             bufs += [xd, yd]
         else:
-            N = c["n"] * (c["rate"] + 1)
+            N = c["n"] * (c["rate"] + 1 + relation_rate)
             eng.decoder_reserve(N)
             bd, xd, yd = eng.to_device(batch), eng.alloc(12 * N), eng.alloc(4 * N)
             bufs += [bd, xd, yd]
-            eng.negative_sample_device(bd, c["n"], c["rate"], c["seed"], xd, yd)
+            eng.negative_sample_device(bd, c["n"], c["rate"], c["seed"], xd, yd, relation_rate=relation_rate)
             X, Y = xd.download(np.int32, (N, 3)), yd.download(np.float32, (N,))
             assert np.array_equal(X[:c["n"]], batch)
-        eng.decoder_loss_backward_device(xd, yd, N, 0.01)
-        out = codes, params["W_relation"], X, Y, eng.loss(), eng.dcodes(), eng.get_grad("W_relation")
+        if runs is None:
+            eng.decoder_loss_backward_device(xd, yd, N, 0.01)
+            out = codes, params["W_relation"], X, Y, eng.loss(), eng.dcodes(), eng.get_grad("W_relation")
+        else:
+            w = None
+            if temperature is not None:
+                wd = eng.alloc(4 * N)
+                bufs.append(wd)
+                wd.upload(np.full(N, -7.0, np.float32))
+                eng.adversarial_weights(xd, N, c["n"], temperature, wd)
+                w = wd.download(np.float32, (N,))
+            elif weights is not None:
+                w = np.ascontiguousarray(weights(c, N, X), dtype=np.float32)
+                assert w.shape == (N,)
+                wd = eng.to_device(w)
+                bufs.append(wd)
+            got = {}
+            for run in runs:
+                if run == "plain":
+                    eng.decoder_loss_backward_device(xd, yd, N, reg)
+                elif run == "null":
+                    eng.decoder_loss_backward_weighted_device(xd, yd, None, N, reg)
+                elif run == "ones":
+                    od = eng.to_device(np.ones(N, np.float32))
+                    bufs.append(od)
+                    eng.decoder_loss_backward_weighted_device(xd, yd, od, N, reg)
+                elif run == "weighted":
+                    eng.decoder_loss_backward_weighted_device(xd, yd, wd, N, reg)
+                elif run == "flipped":
+                    fd = eng.to_device(np.where(w == 0, 1 - Y, Y).astype(np.float32))
+                    bufs.append(fd)
+                    eng.decoder_loss_backward_weighted_device(xd, fd, wd, N, reg)
+                else:
+                    raise ValueError(run)
+                got[run] = eng.loss(), eng.dcodes(), eng.get_grad("W_relation")
+            out = codes, params["W_relation"], X, Y, w, got
     finally:
         for b in bufs:
             b.free()

@@ -81,7 +81,8 @@ enum { RGCN_KIND_BLOCK = 0, RGCN_KIND_BASIS = 1, RGCN_KIND_BASIS_TDIAG = 2, RGCN
  *     RGCN_BUF_NEGATIVE_RELATION_UNRESOLVED and RGCN_BUF_NEGATIVE_TYPED_OPEN only (RGCN_ERR_STATE);
  *   - unchanged: rgcn_decoder_*, rgcn_negative_sample_device, rgcn_known_positives_reserve, rgcn_type_sets_reserve,
  *     rgcn_negative_sample_typed_device, rgcn_rank_typed_device, rgcn_topk_typed_device,
- *     rgcn_negative_sample_exclusive_device, rgcn_negative_sample_relation_device, rgcn_optimizer_*, rgcn_rank_device, rgcn_rank_mixed_device,
+ *     rgcn_negative_sample_exclusive_device, rgcn_negative_sample_relation_device, rgcn_reciprocal_rows_device,
+ *     rgcn_set_reciprocal_relations, rgcn_optimizer_*, rgcn_rank_device, rgcn_rank_mixed_device,
  *     rgcn_topk_device, rgcn_score_queries_device, rgcn_topk_mixed_device, rgcn_rank_relation_device,
  *     rgcn_topk_relation_device, rgcn_score_relation_queries_device, parameters, device memory, timer and profile. */
 /* RGCN_KIND_BASIS_TDIAG = Encoder.DiagonalCoefficients=Yes -> BasisGcnTimesDiag
@@ -596,6 +597,49 @@ rgcn_status rgcn_rank_typed_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t 
 rgcn_status rgcn_topk_typed_device(rgcn_ctx* ctx, const int32_t* x_dev, int64_t num_queries, int32_t predict_object,
                                    int32_t k, const int64_t* exclude_ptr_dev, const int32_t* exclude_idx_dev,
                                    int32_t* topk_idx_dev, float* topk_energy_dev);
+
+/* ---- reciprocal relations ([Decoder] ReciprocalRelations; Lacroix et al. 2018, Kazemi & Poole 2018) ------------------
+ * DistMult's sum is symmetric in s and o.  Under the mode every relation has a second vector, used when the subject is
+ * the unknown: (s, r, ?) is asked of W_relation[r], (?, r, o) of W_relation[RelationCount + r].  The storage is what it
+ * always was: W_relation is [EntityCount, d], rows [R, 2 R) simply come into use.  No tensor or checkpoint shape changes.
+ *
+ * rgcn_reciprocal_rows_device: a pass over x_dev / y_dev that one of rgcn_negative_sample_device, its exclusive, relation
+ * or typed form filled with the same n, rate, relation_rate and seed; the buffers hold n (rate + 2 + relation_rate) rows
+ * (RGCN_ERR_STATE where the runtime can tell that they do not).  csrc/negative_reciprocal.h holds the decision, shared
+ * with the host:
+ *     rows [0, n)                      the positives: untouched
+ *     rows [n, n (rate + 1))           the entity corruptions: a row whose SUBJECT was replaced -- the samplers' own coin,
+ *                                      drop_bits(seed, 0x6e65, 2 (row - n)) & 1 == 0 -- has its relation r rewritten to
+ *                                      r + R; no other word of these rows is written
+ *     rows [n (rate + 1), n (rate + 1 + relation_rate))   the relation rows: untouched (forward relations)
+ *     rows behind them, n of them      written: the inverse positives (s, r + R, o) of the batch, label 1
+ * A relation outside [0, R) stays what it is.  The batch is no longer the tiled one: the decoder takes its general path.
+ * Bad arguments and a batch above RGCN_MAX_DECODER_TRIPLES: RGCN_ERR_INVALID; 2 R > EntityCount: RGCN_ERR_UNSUPPORTED;
+ * during a capture: RGCN_ERR_STATE.
+ *
+ * rgcn_set_reciprocal_relations(ctx, 1):
+ *   - rgcn_train_step_minibatch_device runs the pass behind its sampler and trains on N = n (rate + 2 + relation_rate)
+ *     rows, which its scratch buffers must hold (RGCN_ERR_STATE); the loss stays the mean over all N rows.
+ *   - the decoder's relation bound is 2 R: rgcn_decoder_loss_backward_device, its weighted form and both fused steps take
+ *     relations in [0, 2 R), W_relation's gradient has rows [0, 2 R) (the rows behind them stay zero), the optimizer
+ *     updates and keeps state for them.  The buffers sized by the bound are rebuilt by the call: it may come before or
+ *     after rgcn_decoder_reserve, and it waits for the work in flight.
+ *   - the entity-side queries (rgcn_rank_device, rgcn_rank_typed_device, rgcn_rank_mixed_device, rgcn_topk_device,
+ *     rgcn_topk_typed_device, rgcn_topk_mixed_device, rgcn_score_queries_device) with predict_object == 0 read
+ *     W_relation[R + r]; r is validated against R first, as always, and a typed subject query still reads the list of
+ *     (subject side, r).  predict_object != 0 and the relation queries do not change.
+ *   - rgcn_adversarial_weights_device takes relations in [0, 2 R).  In a fused step under
+ *     rgcn_set_adversarial_negatives the weights come from the rows in front of the inverse positives (num_positives
+ *     groups, as ever) and the inverse positives, the last num_positives rows, take weight 1.
+ *   - the relation-softmax term and the relation queries keep their R candidates.
+ * RGCN_ERR_UNSUPPORTED: 2 R > EntityCount; world > 1; while rgcn_set_entity_softmax is on (and that call, and
+ * rgcn_entity_softmax_device, while this mode is on: the term's subject rows and by-relation reduction are not built for
+ * the 2 R rows); during a capture; rgcn_capture_begin while the mode is on.  Default 0: every call produces the bytes and
+ * launches it produced before these entry points existed, and a relation >= R stays the error it was.  A model trained
+ * without the mode and queried with it reads rows no step ever updated. */
+rgcn_status rgcn_reciprocal_rows_device(rgcn_ctx* ctx, const int32_t* batch_dev, int64_t n, int32_t rate,
+                                        int32_t relation_rate, uint64_t seed, int32_t* x_dev, float* y_dev);
+rgcn_status rgcn_set_reciprocal_relations(rgcn_ctx* ctx, int32_t on);
 
 /* The softmax-over-relations loss term: for every positive (s_n, r_n, o_n), n < P, the gold relation against ALL the
  * others at once -- the objective rgcn_rank_relation_device evaluates, which relation corruptions only sample.  Not in

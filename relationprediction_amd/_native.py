@@ -140,6 +140,8 @@ _SIGS = {
     "rgcn_type_sets_reserve": (C.c_int32, [_P, _P, C.c_int64]),
     "rgcn_negative_sample_typed_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, _P, _P]),
     "rgcn_set_typed_negatives": (C.c_int32, [_P, C.c_int32]),
+    "rgcn_reciprocal_rows_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, _P, _P]),
+    "rgcn_set_reciprocal_relations": (C.c_int32, [_P, C.c_int32]),
     "rgcn_rank_typed_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
     "rgcn_topk_typed_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rgcn_relation_softmax_reserve": (C.c_int32, [_P, C.c_int64]),
@@ -558,7 +560,8 @@ class Engine:
             self.ctx, batch_buffer.ptr, int(num_edges), int(keep), C.c_uint64(edge_seed), int(rate),
             C.c_uint64(negative_seed), x_dev.ptr, y_dev.ptr, C.c_uint64(seed), C.c_float(reg_param)))
         self.num_edges = int(keep)
-        self._decoder_rows = int(num_edges) * (int(rate) + 1 + getattr(self, "_relation_rate", 0))
+        self._decoder_rows = int(num_edges) * (int(rate) + 1 + getattr(self, "_relation_rate", 0) +
+                                               (1 if getattr(self, "_reciprocal", False) else 0))
 
     def set_relation_owner(self, owner):
         o = np.ascontiguousarray(owner, dtype=np.int32)
@@ -654,18 +657,35 @@ class Engine:
         self._check(self.lib.rgcn_sample_neighborhood_device(self.ctx, int(sample_size), C.c_uint64(int(seed)),
                                                              batch_dev.ptr, 1 if on_prefetch_stream else 0))
 
-    def negative_sample_device(self, batch_dev, n, rate, seed, x_dev, y_dev, exclusive=False, relation_rate=0):
+    def negative_sample_device(self, batch_dev, n, rate, seed, x_dev, y_dev, exclusive=False, relation_rate=0,
+                               reciprocal=False):
         """X [n*(rate+1),3] and Y [n*(rate+1)] from the batch of n triples, all on the device.  exclusive: corruptions
         that are known positives (known_positives_reserve) are redrawn (rgcn_negative_sample_exclusive_device).
         relation_rate = m > 0: n*m rows (s, r', o) with a wrong relation follow, n*(rate+1+m) rows in all
-        (rgcn_negative_sample_relation_device)."""
+        (rgcn_negative_sample_relation_device).  reciprocal: the reciprocal pass behind them (reciprocal_rows_device),
+        n*(rate+2+m) rows in all."""
         if relation_rate:
             self._check(self.lib.rgcn_negative_sample_relation_device(
                 self.ctx, batch_dev.ptr, int(n), int(rate), int(relation_rate), 1 if exclusive else 0,
                 C.c_uint64(int(seed)), x_dev.ptr, y_dev.ptr))
-            return
-        fn = self.lib.rgcn_negative_sample_exclusive_device if exclusive else self.lib.rgcn_negative_sample_device
-        self._check(fn(self.ctx, batch_dev.ptr, int(n), int(rate), C.c_uint64(int(seed)), x_dev.ptr, y_dev.ptr))
+        else:
+            fn = self.lib.rgcn_negative_sample_exclusive_device if exclusive else self.lib.rgcn_negative_sample_device
+            self._check(fn(self.ctx, batch_dev.ptr, int(n), int(rate), C.c_uint64(int(seed)), x_dev.ptr, y_dev.ptr))
+        if reciprocal:
+            self.reciprocal_rows_device(batch_dev, n, rate, relation_rate, seed, x_dev, y_dev)
+
+    def reciprocal_rows_device(self, batch_dev, n, rate, relation_rate, seed, x_dev, y_dev):
+        """the reciprocal pass over an X, Y one of the sampler calls filled with the same n, rate, relation_rate and seed
+        (rgcn_reciprocal_rows_device): subject-replaced negatives take relation r + R, n inverse positives (s, r + R, o)
+        follow the last row; the buffers hold n*(rate+2+relation_rate) rows"""
+        self._check(self.lib.rgcn_reciprocal_rows_device(self.ctx, batch_dev.ptr, int(n), int(rate), int(relation_rate),
+                                                         C.c_uint64(int(seed)), x_dev.ptr, y_dev.ptr))
+
+    def set_reciprocal_relations(self, on):
+        """reciprocal relations (rgcn_set_reciprocal_relations): (?, r, o) is asked of W_relation[R + r], the decoder takes
+        relations in [0, 2R), the fused minibatch step trains on n*(rate+2+relation_rate) rows"""
+        self._check(self.lib.rgcn_set_reciprocal_relations(self.ctx, 1 if on else 0))
+        self._reciprocal = bool(on)
 
     def type_sets_reserve(self, triples):
         """the per-relation entity sets of `triples` (the training triples) to the device, once (rgcn_type_sets_reserve);

@@ -28,7 +28,7 @@ SOURCES = ["rgcn_api.hip", "rgcn_schedule.hip", "rgcn_devtools.hip", "graph_prep
            "elementwise.hip", "highway.hip", "output_transform.hip", "decoder.hip", "adversarial.hip", "optimizer.hip", "ranking.hip", "relation_softmax.hip", "entity_softmax.hip", "sampler.hip", "neighborhood.hip", "comm.hip"]
 HEADERS = [os.path.join(CSRC, "rgcn_internal.h"), os.path.join(CSRC, "rgcn_api_internal.h"), os.path.join(CSRC, "gemm_split.h"), os.path.join(CSRC, "gemm_plan.h"),
            os.path.join(CSRC, "dev_pool.h"), os.path.join(CSRC, "config_check.h"), os.path.join(CSRC, "optimizer_check.h"),
-           os.path.join(CSRC, "row_walk.h"), os.path.join(CSRC, "counter_rng.h"), os.path.join(CSRC, "negative_exclusive.h"), os.path.join(CSRC, "negative_relation.h"),
+           os.path.join(CSRC, "row_walk.h"), os.path.join(CSRC, "counter_rng.h"), os.path.join(CSRC, "negative_exclusive.h"), os.path.join(CSRC, "negative_relation.h"), os.path.join(CSRC, "negative_reciprocal.h"),
            os.path.join(CSRC, "known_positives_index.h"), os.path.join(CSRC, "negative_typed.h"), os.path.join(CSRC, "type_sets.h"), os.path.join(CSRC, "pair_query.h"), os.path.join(CSRC, "relation_softmax_plan.h"),
            os.path.join(CSRC, "entity_softmax_plan.h"), os.path.join(CSRC, "entity_softmax_range.h"), os.path.join(CSRC, "adversarial_weights.h"),
            os.path.join(ROOT, "include", "rgcn.h"),

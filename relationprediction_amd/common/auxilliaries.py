@@ -17,7 +17,12 @@ with m = 0 the generator is consumed exactly as before.
 the entities `set_type_sets`' triples have seen in that slot of the row's relation, uniformly over the members other than
 the row's own entity -- the decision of the device's k_negative_sample_typed (csrc/negative_typed.h) from numpy's stream:
 a list with fewer than two members, or with no member but the row's own, is open (all entities); `exclusive` redraws known
-positives inside the list up to max_relation_draws times, then scans the list, then falls open."""
+positives inside the list up to max_relation_draws times, then scans the list, then falls open.
+
+`reciprocal=True` (`[Decoder] ReciprocalRelations=Yes`, not in the reference): `transform_reciprocal` runs behind whichever
+transform drew the rows, relation rows included -- the pass of the device's k_reciprocal_rows
+(csrc/negative_reciprocal.h) with the transform's own coin: an entity corruption whose SUBJECT was replaced takes the
+relation r + R, and the inverse positives (s, r + R, o), label 1, follow the last row.  It draws nothing."""
 import numpy as np
 
 
@@ -29,7 +34,9 @@ class NegativeSampler(object):
     relation_count = None
     max_relation_draws = 32         # RGCN_NEG_MAX_DRAWS: then the first free relation upward, as on the device
 
-    def __init__(self, negative_sample_rate, n_entities, relation_rate=0, relation_count=None):
+    reciprocal = False
+
+    def __init__(self, negative_sample_rate, n_entities, relation_rate=0, relation_count=None, reciprocal=False):
         self.negative_sample_rate = int(negative_sample_rate)
         self.n_entities = int(n_entities)
         self.relation_rate = int(relation_rate)
@@ -38,14 +45,45 @@ class NegativeSampler(object):
         if self.relation_rate > 0 and (relation_count is None or int(relation_count) < 2):
             raise ValueError("relation corruptions need relation_count >= 2")
         self.relation_count = None if relation_count is None else int(relation_count)
+        self.reciprocal = bool(reciprocal)
+        if self.reciprocal and (self.relation_count is None or 2 * self.relation_count > self.n_entities):
+            raise ValueError("ReciprocalRelations needs relation_count with 2 x relation_count <= n_entities: W_relation "
+                             "has one row per entity")
 
     def _other_relations(self, relations, rng):
         """one relation other than its own for every entry: a draw in [0, R - 1), stepped past the own relation"""
         draws = rng.randint(self.relation_count - 1, size=len(relations))
         return (draws + (draws >= relations)).astype(np.int32)
 
-    def _append_relation_rows(self, triplets, new_indexes, new_labels, rng, exclusive):
-        """the relation_rate further copies (s, r', o), label 0, behind the rows of transform / transform_exclusive"""
+    def transform_reciprocal(self, triplets, indexes, labels, object_side):
+        """The reciprocal pass over the rows a transform returned for `triplets` (relation rows included): `object_side`
+        is that transform's coin per entity corruption, true where the OBJECT was replaced.  Those rows keep their
+        relation, the others take r + R; the inverse positives (s, r + R, o), label 1, are appended.  A relation outside
+        [0, R) stays what it is.  The inputs are left unchanged."""
+        triplets = np.asarray(triplets).reshape(-1, 3)
+        R, n = self.relation_count, len(triplets)
+        object_side = np.asarray(object_side).astype(bool)
+        if len(object_side) != n * self.negative_sample_rate:
+            raise ValueError("one coin per entity corruption is needed")
+
+        def inverse(r):
+            return np.where((r >= 0) & (r < R), r + R, r).astype(np.int32)
+
+        out = np.concatenate([np.asarray(indexes, dtype=np.int32), triplets.astype(np.int32)])
+        negatives = out[n:n + len(object_side)]
+        negatives[~object_side, 1] = inverse(negatives[~object_side, 1])
+        out[len(indexes):, 1] = inverse(out[len(indexes):, 1])
+        return out, np.concatenate([np.asarray(labels, dtype=np.float32), np.ones(n, dtype=np.float32)])
+
+    def _append_relation_rows(self, triplets, new_indexes, new_labels, rng, exclusive, choices=None):
+        """the relation_rate further copies (s, r', o), label 0, behind the rows of transform / transform_exclusive; then,
+        under `reciprocal`, the reciprocal pass with the transform's coin `choices`"""
+        new_indexes, new_labels = self._relation_rows(triplets, new_indexes, new_labels, rng, exclusive)
+        if self.reciprocal:
+            return self.transform_reciprocal(triplets, new_indexes, new_labels, choices)
+        return new_indexes, new_labels
+
+    def _relation_rows(self, triplets, new_indexes, new_labels, rng, exclusive):
         if self.relation_rate == 0:
             return new_indexes, new_labels
         rows = np.tile(np.asarray(triplets), (self.relation_rate, 1)).astype(np.int32)
@@ -79,7 +117,7 @@ class NegativeSampler(object):
         negatives = new_indexes[size_of_batch:]
         negatives[choices, 2] = values[choices]
         negatives[~choices, 0] = values[~choices]
-        return self._append_relation_rows(triplets, new_indexes, new_labels, rng, False)
+        return self._append_relation_rows(triplets, new_indexes, new_labels, rng, False, choices)
 
     min_typed_candidates = 2        # RGCN_TYPED_MIN_CANDIDATES
     typed_open = 0                  # rows transform_typed drew over all entities, so far
@@ -142,7 +180,7 @@ class NegativeSampler(object):
                 row[col] = rng.randint(self.n_entities)
                 while exclusive and known(int(row[col])):
                     row[col] = rng.randint(self.n_entities)
-        return self._append_relation_rows(triplets, new_indexes, new_labels, rng, exclusive)
+        return self._append_relation_rows(triplets, new_indexes, new_labels, rng, exclusive, choices)
 
     def set_known_positives(self, triplets):
         self.objs, self.subs = {}, {}
@@ -171,4 +209,4 @@ class NegativeSampler(object):
                 row[0] = rng.randint(self.n_entities)
                 while (row[1], row[0]) in self.subs.get(row[2], ()):
                     row[0] = rng.randint(self.n_entities)
-        return self._append_relation_rows(triplets, new_indexes, new_labels, rng, True)
+        return self._append_relation_rows(triplets, new_indexes, new_labels, rng, True, choices)

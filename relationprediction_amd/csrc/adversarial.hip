@@ -205,7 +205,7 @@ rgcn_status adversarial_weights(rgcn_ctx* c, const float* codes, const int32_t* 
                                 float alpha, float* w_out) {
   const int64_t K = N / P - 1;
   if (K == 0 || alpha == 0.f) return optimizer_fill(c, w_out, N, 1.0f);
-  const int V = c->V, R = c->R, d = c->dc;
+  const int V = c->V, R = decoder_relations(c), d = c->dc;      // (2 R under reciprocal relations)
   const float* Wr = c->w_rel;
   const bool vec4 = (d % 4 == 0) && aligned16(codes) && aligned16(Wr);
   const int nvec = vec4 ? d / 4 : d;

@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "known_positives_index.h"
+#include "negative_reciprocal.h"
 #include "negative_relation.h"
 #include "negative_typed.h"
 #include "rgcn_internal.h"
@@ -251,6 +252,29 @@ __global__ void __launch_bounds__(256) k_negative_sample_typed(const int32_t* __
   if (is_open && (opens & ((1ull << (threadIdx.x & 63u)) - 1ull)) == 0) atomicAdd(open, (unsigned long long)__popcll(opens));
   X[3 * i] = s; X[3 * i + 1] = r; X[3 * i + 2] = o;
   Y[i] = i < n ? 1.0f : 0.0f;
+}
+
+// Reciprocal relations ([Decoder] ReciprocalRelations; negative_reciprocal.h holds the decision, shared with the host): a
+// pass behind whichever samplers above filled X and Y.  One thread per row over the n K entity corruptions -- it reads the
+// row's relation and writes r + R back where the coin replaced the subject, no other word of those rows -- and the n tail
+// rows behind the relation rows, which it writes whole: (s, r + R, o) of the batch row, label 1.  As
+// k_negative_sample_relation it takes the seed as it is: the mode is not capturable.
+__global__ void __launch_bounds__(256) k_reciprocal_rows(const int32_t* __restrict__ batch, int64_t n, int K, int m, int R,
+                                                         uint64_t seed, int32_t* __restrict__ X, float* __restrict__ Y) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t negatives = n * K;
+  if (t >= negatives + n) return;
+  const int64_t i = t < negatives ? n + t : n * ((int64_t)K + 1 + m) + (t - negatives);
+  const ReciprocalChoice ch = reciprocal_choice(i, n, K, m, R, seed);
+  if (ch.action == RECIPROCAL_SHIFT) {
+    X[3 * i + 1] = reciprocal_relation(X[3 * i + 1], R);
+  } else if (ch.action == RECIPROCAL_TAIL) {
+    const int64_t b = ch.source;
+    X[3 * i] = batch[3 * b];
+    X[3 * i + 1] = reciprocal_relation(batch[3 * b + 1], R);
+    X[3 * i + 2] = batch[3 * b + 2];
+    Y[i] = 1.0f;
+  }
 }
 
 // ---- K1: energies, dx, loss terms ---------------------------------------------------------------
@@ -978,6 +1002,20 @@ rgcn_status negative_sample_typed(rgcn_ctx* c, const int32_t* batch_dev, int64_t
   return negative_relation_rows(c, batch_dev, n, rate, relation_rate, exclusive, seed, X, Y);
 }
 
+// The reciprocal pass behind the samplers' rows (k_reciprocal_rows): X and Y hold n (rate + 2 + relation_rate) rows.
+rgcn_status reciprocal_rows(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int rate, int relation_rate, uint64_t seed,
+                            int32_t* X, float* Y) {
+  const int64_t threads = n * ((int64_t)rate + 1);
+  if (n <= 0) return RGCN_OK;
+  ProfScope ps(c, "reciprocal_rows", 8.0 * n * rate + 28.0 * n, 0);
+  hipLaunchKernelGGL(k_reciprocal_rows, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, c->stream, batch_dev, n, rate,
+                     relation_rate, c->R, seed, X, Y);
+  RGCN_HIP(c, hipGetLastError());
+  // copies of a triple no longer share a relation row: the batch is not the tiled one, decoder_prepare takes its general path
+  c->dec.tiled_X = nullptr;
+  return RGCN_OK;
+}
+
 void type_sets_free(rgcn_ctx* c) {
   c->types.pool.release();
   c->types = TypeSetsDev();
@@ -1041,9 +1079,10 @@ rgcn_status known_positives_reserve(rgcn_ctx* c, const int32_t* triples_host, in
 
 rgcn_status decoder_reserve(rgcn_ctx* c, int64_t maxN) {
   DecoderBufs& q = c->dec;
-  if (q.maxN >= maxN && q.maxN > 0) return RGCN_OK;
+  if (q.maxN >= maxN && q.maxN > 0 && q.relations == decoder_relations(c)) return RGCN_OK;
   decoder_free(c);
-  const size_t N = (size_t)maxN, V = c->V, R = c->R, d = c->dc;      // (the decoder works at the code width)
+  // (the decoder works at the code width; under reciprocal relations its relation rows are the first 2 R of W_relation)
+  const size_t N = (size_t)maxN, V = c->V, R = (size_t)decoder_relations(c), d = c->dc;
   RGCN_TRY(dmalloc(c, q.pool, &q.keyv, 2 * N, false));
   RGCN_TRY(dmalloc(c, q.pool, &q.keyv_s, 2 * N, false));
   RGCN_TRY(dmalloc(c, q.pool, &q.valv, 2 * N, false));
@@ -1095,6 +1134,7 @@ rgcn_status decoder_reserve(rgcn_ctx* c, int64_t maxN) {
   RGCN_HIP(c, hipEventCreateWithFlags(&q.ev_ready, order_event_flags(c)));
   if (!c->dcodes_own) RGCN_TRY(dmalloc(c, c->pool, &c->dcodes_own, V * d, false));
   q.maxN = maxN;
+  q.relations = (int32_t)R;
   return RGCN_OK;
 }
 
@@ -1108,7 +1148,7 @@ void decoder_free(rgcn_ctx* c) {
 // CSR of the decoder batch (depends on X only).  Runs on whatever stream is current.
 rgcn_status decoder_prepare(rgcn_ctx* c, const int32_t* X, int64_t N64, int64_t N_total) {
   DecoderBufs& q = c->dec;
-  const int N = (int)N64, V = c->V, R = c->R;
+  const int N = (int)N64, V = c->V, R = decoder_relations(c);
   if (N64 > q.maxN) RGCN_FAIL(c, RGCN_ERR_INVALID, "decoder batch larger than rgcn_decoder_reserve'd");
   q.N = N;
   q.N_total = N_total > 0 ? N_total : N64;
@@ -1163,7 +1203,7 @@ rgcn_status decoder_prepare(rgcn_ctx* c, const int32_t* X, int64_t N64, int64_t 
 rgcn_status decoder_compute(rgcn_ctx* c, const float* codes, const float* Y, float reg_param, float* dcodes_drop,
                             const DropSpec* drop, const float* row_weights) {
   DecoderBufs& q = c->dec;
-  const int N = q.N, V = c->V, R = c->R, d = c->dc;
+  const int N = q.N, V = c->V, R = decoder_relations(c), d = c->dc;
   const int Nt = q.N_total > 0 ? (int)q.N_total : N;      // denominator of the batch mean
   const float* Wr = c->w_rel;
   float* gWr = c->g_rel;

@@ -257,7 +257,16 @@ int slot_count_of(int32_t algorithm) {
 // elements of parameter i that the optimizer touches, and that carry state
 int64_t updated_count(const rgcn_ctx* c, size_t i) {
   const Param& p = c->params[i];
-  return p.name == "W_relation" ? (int64_t)c->R * c->dc : p.count;      // rows >= RelationCount never get a gradient
+  // rows >= RelationCount never get a gradient; under reciprocal relations rows >= 2 RelationCount
+  return p.name == "W_relation" ? (int64_t)decoder_relations(c) * c->dc : p.count;
+}
+
+// elements the state slots of parameter i are allocated with: W_relation's hold the reciprocal rows whether or not the
+// mode is on, so that rgcn_set_reciprocal_relations may come before or after the first step
+int64_t slot_elements(const rgcn_ctx* c, size_t i) {
+  const Param& p = c->params[i];
+  if (p.name != "W_relation") return p.count;
+  return (int64_t)(2 * (int64_t)c->R <= c->V ? 2 * c->R : c->R) * c->dc;
 }
 
 // the state slots of parameter i, created at their initial value (Adam: zeros; AdaGrad: init_acc) if they are not there
@@ -268,7 +277,7 @@ rgcn_status ensure_slots(rgcn_ctx* c, size_t i) {
     o.v.assign(c->params.size(), nullptr);
   }
   if (slot_count_of(o.algorithm) == 0 || o.m[i]) return RGCN_OK;
-  const int64_t n = updated_count(c, i);
+  const int64_t n = slot_elements(c, i);
   if (o.algorithm == RGCN_OPT_ADAM) {
     RGCN_TRY(dmalloc(c, o.pool, &o.m[i], (size_t)n, true));
     return dmalloc(c, o.pool, &o.v[i], (size_t)n, true);

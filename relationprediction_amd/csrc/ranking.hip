@@ -62,15 +62,19 @@ __device__ __forceinline__ float sigmoid_f32(float x) {
   return (float)(1.0 / (1.0 + exp(-(double)x)));
 }
 
-// Q[n,:] = codes[s_n] * W_rel[r_n]  (object side)   or   W_rel[r_n] * codes[o_n]  (subject side)
+// Q[n,:] = codes[s_n] * W_rel[r_n]  (object side)   or   W_rel[r_n + shift] * codes[o_n]  (subject side)
+// shift: R on the subject side under reciprocal relations (rgcn_set_reciprocal_relations), else 0: the relation id is held
+// to [0, R) as it always was, then moved to the inverse relation's row
 __global__ void k_rank_query(const float* __restrict__ codes, const float* __restrict__ wrel,
                              const int32_t* __restrict__ X, int n, int d, int predict_object,
-                             float* __restrict__ Q, int V, int R) {
+                             float* __restrict__ Q, int V, int R, int shift) {
   const int row = blockIdx.x;
   if (row >= n) return;
   // (an id out of range makes the whole call fail -- k_rank_check, read back at the end; until then nothing may fault;
   // pair_query.h holds the arithmetic, shared with the entity-softmax term)
-  entity_query_row(codes, wrel, X[3 * row + (predict_object ? 0 : 2)], X[3 * row + 1], row, d, Q, V, R);
+  int rel = X[3 * row + 1];
+  if ((unsigned)rel >= (unsigned)R) rel = 0;
+  entity_query_row(codes, wrel, X[3 * row + (predict_object ? 0 : 2)], rel + shift, row, d, Q, V, R + shift);
 }
 
 // P[n,:] = codes[s_n] * codes[o_n]: the relation side's query row, one rounding per element
@@ -553,7 +557,7 @@ static rgcn_status score_chunk(rgcn_ctx* c, const int32_t* X, int n, int side) {
   {
     ProfScope ps(c, "rank_query", 4.0 * 3 * n * dc, 0);
     hipLaunchKernelGGL(k_rank_query, dim3((unsigned)n), dim3(128), 0, c->stream, codes, c->w_rel, X, n, dc,
-                       side, c->ranking.q, c->V, c->R);
+                       side, c->ranking.q, c->V, c->R, c->reciprocal && side == SIDE_SUBJECT ? c->R : 0);
     RGCN_HIP(c, hipGetLastError());
   }
   return gemm_f32(c, "rank_scores", true, true, n, c->V, dc, c->ranking.q, dc, codes, dc, c->ranking.s, c->V, 1);

@@ -1195,6 +1195,48 @@ rgcn_status rgcn_set_typed_negatives(rgcn_ctx* c, int32_t on) {
   return RGCN_OK;
 }
 
+// ---- reciprocal relations: the stand-alone pass and the mode
+rgcn_status rgcn_reciprocal_rows_device(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int32_t rate, int32_t relation_rate,
+                                        uint64_t seed, int32_t* x_dev, float* y_dev) {
+  RGCN_NEED(c);
+  if (n < 0 || rate < 0 || rate > 1024 || relation_rate < 0 || relation_rate > 1024 ||
+      (n > 0 && (!batch_dev || !x_dev || !y_dev)))
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
+  if (n * (int64_t)(rate + 2 + relation_rate) > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "batch too large");
+  if (2 * (int64_t)c->R > c->V)
+    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "reciprocal relations need 2 x num_relations <= num_entities rows of W_relation");
+  if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
+  if (n > 0 && (!allocation_covers(x_dev, sizeof(int32_t) * 3 * (size_t)(n * (int64_t)(rate + 2 + relation_rate))) ||
+                !allocation_covers(y_dev, sizeof(float) * (size_t)(n * (int64_t)(rate + 2 + relation_rate)))))
+    RGCN_FAIL(c, RGCN_ERR_STATE, "the buffers must hold num_edges x (2 + negative_rate + relation_rate) rows");
+  return reciprocal_rows(c, batch_dev, n, rate, relation_rate, seed, x_dev, y_dev);
+}
+
+rgcn_status rgcn_set_reciprocal_relations(rgcn_ctx* c, int32_t on) {
+  RGCN_NEED(c);
+  if (c->capturing)
+    RGCN_FAIL(c, on ? RGCN_ERR_UNSUPPORTED : RGCN_ERR_STATE, "reciprocal relations: not while a hipGraph is being captured");
+  if (on) {
+    if (c->world > 1)
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "reciprocal relations on a relation-sharded context (world > 1)");
+    if (2 * (int64_t)c->R > c->V)
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "reciprocal relations need 2 x num_relations <= num_entities rows of W_relation");
+    if (c->entsm.weight > 0.f)
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "reciprocal relations under the entity softmax (rgcn_set_entity_softmax): its subject rows "
+                                         "and its by-relation reduction are not built for the 2 R relation rows");
+  }
+  if ((on != 0) == c->reciprocal) return RGCN_OK;
+  RGCN_TRY(sync_all(c));      // (a step in flight still reads the decoder's buffers at their present size)
+  c->reciprocal = on != 0;
+  // off again: the gradient rows [R, 2 R) return to the zeros every row behind the relation bound holds
+  if (!on)
+    RGCN_HIP(c, hipMemsetAsync(c->g_rel + (size_t)c->R * c->dc, 0, sizeof(float) * (size_t)c->R * c->dc, c->main_stream));
+  // everything sized by the relation bound follows it: rel_ptr, chunk_ptr, rb, the slab of the relation gradient
+  const int64_t maxN = c->dec.maxN;
+  if (maxN > 0) RGCN_TRY(decoder_reserve(c, maxN));
+  return RGCN_OK;
+}
+
 // ---- the relation-softmax term: reserve, the stand-alone call, the mode of the fused steps, the host plan
 rgcn_status rgcn_relation_softmax_reserve(rgcn_ctx* c, int64_t max_positives) {
   RGCN_NEED(c);
@@ -1273,6 +1315,7 @@ rgcn_status rgcn_entity_softmax_device(rgcn_ctx* c, const int32_t* pos_dev, int6
   if (!relsm_weight_ok(weight)) RGCN_FAIL(c, RGCN_ERR_INVALID, "the weight must be finite and not negative");
   if (c->V < 2) RGCN_FAIL(c, RGCN_ERR_INVALID, "the entity softmax needs at least two entities");
   if (c->world > 1) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "the entity softmax on a relation-sharded context (world > 1)");
+  if (c->reciprocal) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "the entity softmax under reciprocal relations (rgcn_set_reciprocal_relations)");
   if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
   if (!c->dec.loss_valid || !c->fwd_done)
     RGCN_FAIL(c, RGCN_ERR_STATE, "the term is added to a decoder pass: call rgcn_decoder_loss_backward_device first");
@@ -1290,6 +1333,9 @@ rgcn_status rgcn_set_entity_softmax(rgcn_ctx* c, float weight, int64_t num_posit
   if (weight > 0.f) {
     if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "not while a hipGraph is being captured");
     if (c->V < 2) RGCN_FAIL(c, RGCN_ERR_INVALID, "the entity softmax needs at least two entities");
+    if (c->reciprocal)
+      RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "the entity softmax under reciprocal relations (rgcn_set_reciprocal_relations): its subject "
+                                         "rows and its by-relation reduction are not built for the 2 R relation rows");
     if (exclusive && c->known.count <= 0) RGCN_FAIL(c, RGCN_ERR_STATE, "call rgcn_known_positives_reserve first");
   }
   c->entsm.weight = weight;
@@ -1587,13 +1633,16 @@ rgcn_status rgcn_optimizer_apply(rgcn_ctx* c) { RGCN_NEED(c); return optimizer_a
 // n_pos > 0: the leading n_pos rows of X are the positives of the relation-softmax term (one GPU; relsm_step_check)
 // n_ent > 0: the leading n_ent rows of X are the positives of the entity-softmax term (one GPU; entsm_step_check)
 static rgcn_status train_step_tail(rgcn_ctx* c, const int32_t* X_dev, const float* Y_dev, int64_t N, uint64_t seed,
-                                   float reg_param, int64_t n_pos = 0, int64_t adv_pos = 0, int64_t n_ent = 0) {
+                                   float reg_param, int64_t n_pos = 0, int64_t adv_pos = 0, int64_t n_ent = 0,
+                                   int64_t recip_tail = 0) {
   RGCN_TRY(forward_all(c, 1, seed, nullptr));
   // adv_pos > 0: self-adversarial weights of the negatives (one GPU; adv_step_check), from the codes the forward pass just
   // left.  On the main stream: the pass reads X alone, so it runs beside the decoder's preparation on side stream 1.
   const float* row_w = nullptr;
   if (adv_pos > 0) {
-    RGCN_TRY(adversarial_weights(c, c->codes, X_dev, Y_dev, N, adv_pos, c->adv.temperature, c->adv.w));
+    // recip_tail > 0 (reciprocal relations): the inverse positives behind the groups take weight 1
+    RGCN_TRY(adversarial_weights(c, c->codes, X_dev, Y_dev, N - recip_tail, adv_pos, c->adv.temperature, c->adv.w));
+    RGCN_TRY(optimizer_fill(c, c->adv.w + (N - recip_tail), recip_tail, 1.0f));
     c->adv.last_N = N;
     row_w = c->adv.w;
   }
@@ -1727,13 +1776,18 @@ rgcn_status rgcn_train_step_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t 
   }
   const int64_t adv_pos = c->adv.temperature > 0.f ? c->adv.step_positives : 0;
   if (c->adv.temperature > 0.f) RGCN_TRY(adv_step_buffer(c));
+  // reciprocal relations: the batch ends in its inverse positives, one per positive, which stand outside the groups
+  const int64_t recip_tail = c->reciprocal && adv_pos > 0 ? adv_pos : 0;
+  if (recip_tail > 0 && N < 2 * recip_tail)
+    RGCN_FAIL(c, RGCN_ERR_INVALID, "adversarial negatives under reciprocal relations: the batch has no inverse positives behind its groups");
   if (c->embedding) {
     // the DistMult baseline's step: decoder loss + gradients on the table itself (dL/dcodes is written into W_emb's
     // gradient), then clip + Adam.  One chain on the main stream but for the relation gradient's side stream.
     RGCN_TRY(forward_all(c, 1, seed, nullptr));
     const float* row_w = nullptr;
     if (adv_pos > 0) {
-      RGCN_TRY(adversarial_weights(c, c->H[0], X_dev, Y_dev, N, adv_pos, c->adv.temperature, c->adv.w));
+      RGCN_TRY(adversarial_weights(c, c->H[0], X_dev, Y_dev, N - recip_tail, adv_pos, c->adv.temperature, c->adv.w));
+      RGCN_TRY(optimizer_fill(c, c->adv.w + (N - recip_tail), recip_tail, 1.0f));
       c->adv.last_N = N;
       row_w = c->adv.w;
     }
@@ -1751,7 +1805,7 @@ rgcn_status rgcn_train_step_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t 
     return RGCN_OK;
   }
   RGCN_TRY(step_begin(c, tri_dev, E, true));
-  return train_step_tail(c, X_dev, Y_dev, N, seed, reg_param, n_pos, adv_pos, n_ent);
+  return train_step_tail(c, X_dev, Y_dev, N, seed, reg_param, n_pos, adv_pos, n_ent, recip_tail);
 }
 
 rgcn_status rgcn_prefetch_graph_device(rgcn_ctx* c, const int32_t* tri_dev, int64_t E) {
@@ -1800,7 +1854,8 @@ rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* c, const int32_t* batch_d
   if (negative_rate < 0 || negative_rate > 1024 || !batch_dev || !x_scratch_dev || !y_scratch_dev)
     RGCN_FAIL(c, RGCN_ERR_INVALID, "bad arguments");
   const int32_t relation_rate = c->relation_negatives;      // rgcn_set_relation_negatives; 0: the step as it always was
-  const int64_t N = n * (int64_t)(negative_rate + 1 + relation_rate);
+  const bool reciprocal = c->reciprocal;            // rgcn_set_reciprocal_relations; off: the step as it always was
+  const int64_t N = n * (int64_t)(negative_rate + 1 + relation_rate) + (reciprocal ? n : 0);
   const bool relsm_on = c->relsm.weight > 0.f;      // rgcn_set_relation_softmax; off: the step as it always was
   if (relsm_on) RGCN_TRY(relsm_step_check(c));      // (ahead of the communicator's check, as in rgcn_train_step_device)
   const bool adv_on = c->adv.temperature > 0.f;     // rgcn_set_adversarial_negatives; off: the step as it always was
@@ -1813,13 +1868,15 @@ rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* c, const int32_t* batch_d
   if (adv_on) RGCN_TRY(adv_step_buffer(c));
   const bool typed = c->types.typed;                 // rgcn_set_typed_negatives; off: the step as it always was
   if (typed && c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "type-constrained negatives are not built for a hipGraph capture");
-  if (relation_rate > 0) {
-    if (c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "relation corruptions are not built for a hipGraph capture");
+  if (reciprocal && c->capturing) RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "reciprocal relations are not built for a hipGraph capture");
+  if (relation_rate > 0 || reciprocal) {
+    if (relation_rate > 0 && c->capturing) RGCN_FAIL(c, RGCN_ERR_STATE, "relation corruptions are not built for a hipGraph capture");
     if (N > RGCN_MAX_DECODER_TRIPLES) RGCN_FAIL(c, RGCN_ERR_INVALID, "batch too large");
     // the relation rows lie behind the n (rate + 1) rows a caller sized its scratch for before the mode existed
     if (!allocation_covers(x_scratch_dev, sizeof(int32_t) * 3 * (size_t)N) ||
         !allocation_covers(y_scratch_dev, sizeof(float) * (size_t)N))
-      RGCN_FAIL(c, RGCN_ERR_STATE, "the scratch buffers must hold num_edges x (1 + negative_rate + relation_rate) rows");
+      RGCN_FAIL(c, RGCN_ERR_STATE, reciprocal ? "the scratch buffers must hold num_edges x (2 + negative_rate + relation_rate) rows"
+                                              : "the scratch buffers must hold num_edges x (1 + negative_rate + relation_rate) rows");
   }
   // the message graph: adopted from the prefetch of this very (batch, keep, seed), or drawn and prepared in line
   RGCN_TRY(step_begin(c, batch_dev, n, false, keep, edge_seed));   // (the fork point is recorded below)
@@ -1834,11 +1891,14 @@ rgcn_status rgcn_train_step_minibatch_device(rgcn_ctx* c, const int32_t* batch_d
     RGCN_TRY(negative_sample_exclusive(c, batch_dev, n, negative_rate, negative_seed, x_scratch_dev, y_scratch_dev));
   else
     RGCN_TRY(negative_sample(c, batch_dev, n, negative_rate, negative_seed, x_scratch_dev, y_scratch_dev));
+  if (reciprocal)
+    RGCN_TRY(reciprocal_rows(c, batch_dev, n, negative_rate, relation_rate, negative_seed, x_scratch_dev, y_scratch_dev));
   // the decoder's batch preparation forks from ev_step_begin onto a side stream: it must see the sampled batch
   RGCN_HIP(c, hipEventRecord(c->ev_step_begin, c->main_stream));
   return train_step_tail(c, x_scratch_dev, y_scratch_dev, N, dropout_seed, reg_param, relsm_on ? n : 0, adv_on ? n : 0,
                          // (the batch rows, or the leading num_positives of them where rgcn_set_entity_softmax named a count)
-                         entsm_on ? (c->entsm.step_positives > 0 ? std::min<int64_t>(c->entsm.step_positives, n) : n) : 0);
+                         entsm_on ? (c->entsm.step_positives > 0 ? std::min<int64_t>(c->entsm.step_positives, n) : n) : 0,
+                         reciprocal && adv_on ? n : 0);
 }
 
 // ---- neighbourhood edge sampler on the device ------------------------------------------
@@ -1900,6 +1960,9 @@ rgcn_status rgcn_capture_begin(rgcn_ctx* c) {
   if (c->kind == RGCN_KIND_BASIS_PDIAG)
     RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "rgcn_capture_begin: capture on an RGCN_KIND_BASIS_PDIAG context is not supported (a "
                                        "captured step of this kind has never been replayed against a reference)");
+  if (c->reciprocal)
+    RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "rgcn_capture_begin: reciprocal relations (rgcn_set_reciprocal_relations) are not built "
+                                       "for a hipGraph capture");
   if (c->world > 1 && knob("RGCN_CAPTURE_SHARDED", 0) != 1)
     RGCN_FAIL(c, RGCN_ERR_UNSUPPORTED, "capture on a sharded context is experimental (never run against real RCCL on "
                                        "several GPUs): the devtools build enables it with RGCN_CAPTURE_SHARDED=1");

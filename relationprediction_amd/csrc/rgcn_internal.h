@@ -254,6 +254,7 @@ struct GraphBufs {
 struct DecoderBufs {
   DevPool pool;
   int64_t maxN = 0;
+  int32_t relations = 0;       // the relation bound the buffers were sized for (decoder_relations at the reserve)
   int32_t N = 0;
   int64_t N_total = 0;         // triples of the whole batch when N is one rank's slice of it (denominator of the means)
   // the last batch rgcn_negative_sample_device (or the fused minibatch step) wrote: `tiled_period` rows tiled rate + 1
@@ -538,6 +539,7 @@ struct rgcn_ctx {
   rgcn::DecoderBufs dec;
   rgcn::NeighborhoodBufs nbr;
   rgcn::KnownPositives known;
+  bool reciprocal = false;               // rgcn_set_reciprocal_relations: (?, r, o) is asked of W_relation[R + r]
   int32_t relation_negatives = 0;        // rgcn_set_relation_negatives: relation rows per positive in the fused minibatch step
   rgcn::TypeSetsDev types;
   rgcn::RelsmBufs relsm;
@@ -633,6 +635,9 @@ namespace rgcn {
 inline unsigned order_event_flags(const rgcn_ctx* c, bool kernel_only = false) {
   return hipEventDisableTiming | (kernel_only && c->world == 1 ? hipEventDisableSystemFence : 0u);
 }
+
+// rows of W_relation the decoder, the adversarial weights and the optimizer work on: R, or 2 R under reciprocal relations
+inline int decoder_relations(const rgcn_ctx* c) { return c->reciprocal ? 2 * c->R : c->R; }
 
 // The one way the library allocates device memory: `pool` owns the block (n elements of T, or n bytes through a void**);
 // zero queues a memset of it on the context's current stream.  Out of memory is RGCN_ERR_NOMEM.
@@ -854,6 +859,10 @@ void type_sets_free(rgcn_ctx* c);
 // the index of known positives; relation_rate > 0: the relation rows of negative_sample_relation behind them
 rgcn_status negative_sample_typed(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int rate, int relation_rate,
                                   bool exclusive, uint64_t seed, int32_t* X, float* Y);
+// reciprocal relations (negative_reciprocal.h decides every row): the pass behind one of the sampler calls above that ran
+// with the same n, rate, relation_rate and seed; X and Y hold n (rate + 2 + relation_rate) rows.  Clears tiled_X
+rgcn_status reciprocal_rows(rgcn_ctx* c, const int32_t* batch_dev, int64_t n, int rate, int relation_rate, uint64_t seed,
+                            int32_t* X, float* Y);
 rgcn_status decoder_reserve(rgcn_ctx* c, int64_t max_triples);
 void decoder_free(rgcn_ctx* c);
 // N_total > N: X_dev is one rank's slice of a batch of N_total triples (relation-sharded train step); 0: N

@@ -71,6 +71,40 @@ def parse_entity_softmax_positives(settings):
     return k
 
 
+def parse_reciprocal_relations(settings):
+    """[Decoder] ReciprocalRelations=Yes|No (not in the reference; absent: No): every relation gets a second vector,
+    W_relation[RelationCount + r], which answers (?, r, o) while W_relation[r] answers (s, r, ?) (include/rgcn.h,
+    rgcn_set_reciprocal_relations).  Refused with EntitySoftmaxWeight > 0 and where W_relation has too few rows."""
+    value = settings['ReciprocalRelations'] if 'ReciprocalRelations' in settings else 'No'
+    if value not in ('Yes', 'No'):
+        raise ValueError("Decoder.ReciprocalRelations must be Yes or No, not %r" % (value,))
+    if value == 'No':
+        return False
+    if parse_entity_softmax_weight(settings) > 0:
+        raise ValueError("Decoder.ReciprocalRelations = Yes with Decoder.EntitySoftmaxWeight > 0: the entity-softmax term is "
+                         "not built for the inverse relations' rows; drop one of the two keys")
+    if 'RelationCount' in settings and 'EntityCount' in settings \
+            and 2 * int(settings['RelationCount']) > int(settings['EntityCount']):
+        raise ValueError("Decoder.ReciprocalRelations = Yes needs 2 x RelationCount <= EntityCount (W_relation has one row "
+                         "per entity): the dataset has %d relations and %d entities"
+                         % (int(settings['RelationCount']), int(settings['EntityCount'])))
+    return True
+
+
+def reciprocal_row_weights(energies, labels, temperature, reciprocal):
+    """adversarial_row_weights for a batch that may end in its inverse positives (ReciprocalRelations=Yes: the last n of its
+    2 n rows with label 1): the weights of the rows in front of them, and 1 for them."""
+    if not reciprocal:
+        return adversarial_row_weights(energies, labels, temperature)
+    z = np.asarray(labels).reshape(-1)
+    n = int(np.count_nonzero(z == 1)) // 2
+    head = len(z) - n
+    if n == 0 or not (z[head:] == 1).all():
+        raise ValueError("a reciprocal batch ends in its inverse positives (label 1), as many as it has positives in front")
+    x = np.asarray(energies, dtype=np.float32).reshape(-1)
+    return np.concatenate([adversarial_row_weights(x[:head], z[:head], temperature), np.ones(n, dtype=np.float32)])
+
+
 def parse_adversarial_temperature(settings):
     """[General] AdversarialTemperature=alpha (not in the reference; absent: 0): the temperature of the self-adversarial
     weights of the negatives (include/rgcn.h, rgcn_set_adversarial_negatives).  A non-negative finite float."""
@@ -180,6 +214,13 @@ class BilinearDiag(Model):
         self.adversarial_temperature = parse_adversarial_temperature(self.settings)
         self.entity_softmax_weight = parse_entity_softmax_weight(self.settings)
         self.entity_softmax_positives = parse_entity_softmax_positives(self.settings)
+        self.reciprocal = parse_reciprocal_relations(self.settings)
+
+    def _forward_positives(self, x, z):
+        """the rows with label 1 that the softmax terms take: under ReciprocalRelations the first half of them -- the
+        inverse positives at the end of the batch carry relations >= RelationCount, which are no candidates"""
+        pos = np.asarray(x)[np.asarray(z) == 1]
+        return pos[:len(pos) // 2] if self.reciprocal else pos
 
     def _entity_softmax_rows(self, x, z):
         """the positives the eager entity-softmax term takes: the rows with label 1, the leading EntitySoftmaxPositives"""
@@ -193,7 +234,7 @@ class BilinearDiag(Model):
 
     def _relation_softmax(self):
         """tell the runtime the term's weight and mask before a device step (nothing to tell while the key is absent)"""
-        rt = self.next_component.get_runtime()
+        rt = self._runtime()
         if self.relation_softmax_weight > 0 or getattr(rt, "_relsm_weight", 0.0) > 0:
             rt.set_relation_softmax(self.relation_softmax_weight, self.relation_softmax_known)
         if self.adversarial_temperature > 0 or getattr(rt, "_adv_temperature", 0.0) > 0:
@@ -201,6 +242,13 @@ class BilinearDiag(Model):
         if self.entity_softmax_weight > 0 or getattr(rt, "_entsm_weight", 0.0) > 0:
             # (the mask reads the same known positives as the relation term's: ExclusiveNegativeSampling=Yes)
             rt.set_entity_softmax(self.entity_softmax_weight, self.relation_softmax_known, self.entity_softmax_positives)
+        return rt
+
+    def _runtime(self):
+        """the encoder's runtime, told whether relations are reciprocal (nothing to tell while the key is absent)"""
+        rt = self.next_component.get_runtime()
+        if self.reciprocal or getattr(rt, "_reciprocal_want", False):
+            rt.set_reciprocal_relations(self.reciprocal)
         return rt
 
     def local_initialize_train(self):
@@ -225,12 +273,12 @@ class BilinearDiag(Model):
         # tf.nn.weighted_cross_entropy_with_logits(targets=z, logits=x, pos_weight=1)
         per = (1 - z) * energies + np.log1p(np.exp(-np.abs(energies))) + np.maximum(-energies, 0)
         if self.adversarial_temperature > 0:
-            per = adversarial_row_weights(energies, z, self.adversarial_temperature) * per
+            per = reciprocal_row_weights(energies, z, self.adversarial_temperature, self.reciprocal) * per
         loss = float(np.mean(per, dtype=np.float64))
         if self.relation_softmax_weight > 0:
             # the unmasked softmax-over-relations term over the rows with label 1 (the device paths' small-size cross-check)
             subject_codes, relation_codes, _ = self.next_component.get_all_codes(mode=mode)
-            loss += relation_softmax_terms(subject_codes, relation_codes, self.X.value[np.asarray(z) == 1],
+            loss += relation_softmax_terms(subject_codes, relation_codes, self._forward_positives(self.X.value, z),
                                            self.relation_count, self.relation_softmax_weight)[0]
         if self.entity_softmax_weight > 0:
             # the unmasked softmax-over-entities term over the rows with label 1 (the device paths' small-size cross-check)
@@ -251,6 +299,10 @@ class BilinearDiag(Model):
 
     def predict_all_subject_scores(self):
         e1s, rs, e2s = self.compute_codes(mode='test')
+        if self.reciprocal:
+            # (?, r, o) is asked of the inverse relation's vector, W_relation[RelationCount + r]
+            relation_codes = self.next_component.get_all_codes(mode='test')[1]
+            rs = relation_codes[self.X.value[:, 1] + self.relation_count]
         all_subject_codes = self.next_component.get_all_subject_codes(mode='test')
         return _sigmoid(np.matmul(all_subject_codes, (rs * e2s).T).T)
 
@@ -275,7 +327,7 @@ class BilinearDiag(Model):
 
     def device_optimizer_engine(self):
         """the engine whose optimizer state Model.save_optimizer / load_optimizer read and write"""
-        return self.next_component.get_runtime().engine
+        return self._runtime().engine
 
     def device_train_step(self, graph_edges, x, y, seed):
         """loss + regularisation, all gradients, clip and Adam in one asynchronous device step (graph_edges None: a
@@ -328,7 +380,7 @@ class BilinearDiag(Model):
         if self.needs_graph() and (getattr(self, '_ranks_graph', None) is not graph or variables[0].value is None):
             variables[0].feed(graph)
             self._ranks_graph = graph
-        return self.next_component.get_runtime()
+        return self._runtime()
 
     def device_ranks(self, graph, triplets, predict_object, filter_ptr, filter_idx):
         """Ranks of the gold subjects / objects of `triplets` against every entity, codes from a test-mode
@@ -413,7 +465,8 @@ class BilinearDiag(Model):
         energies = np.sum(e1s * rs * e2s, axis=1)
         dx = ((_sigmoid(energies) - z) / n).astype(np.float32)
         if self.adversarial_temperature > 0:
-            dx = adversarial_row_weights(energies, z, self.adversarial_temperature) * dx      # the weights are constants
+            # (the weights are constants)
+            dx = reciprocal_row_weights(energies, z, self.adversarial_temperature, self.reciprocal) * dx
         dx = dx[:, None]
         k = np.float32(self.regularization_parameter * 2.0 / (n * d))
         g_e1, g_r, g_e2 = dx * (rs * e2s) + k * e1s, dx * (e1s * e2s) + k * rs, dx * (e1s * rs) + k * e2s
@@ -423,7 +476,7 @@ class BilinearDiag(Model):
         d_rel = np.zeros_like(relation_codes)
         np.add.at(d_rel, x[:, 1], g_r)
         if self.relation_softmax_weight > 0:
-            _, t_codes, t_rel = relation_softmax_terms(subject_codes, relation_codes, x[np.asarray(z) == 1],
+            _, t_codes, t_rel = relation_softmax_terms(subject_codes, relation_codes, self._forward_positives(x, z),
                                                        self.relation_count, self.relation_softmax_weight)
             dcodes = (dcodes + t_codes).astype(dcodes.dtype)
             d_rel = (d_rel + t_rel).astype(d_rel.dtype)

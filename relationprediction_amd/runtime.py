@@ -183,6 +183,8 @@ class EncoderRuntime(object):
             self.engine.negative_sample_device(bd, nb, rate, seed, xd, yd, exclusive=exclusive, relation_rate=relation_rate)
         if typed:
             self.engine.negative_sample_typed_device(bd, nb, rate, seed, xd, yd, exclusive=exclusive)
+        if self._reciprocal():
+            self.engine.reciprocal_rows_device(bd, nb, rate, relation_rate, seed, xd, yd)
 
     def negative_typed_open(self):
         """negative rows the typed sampler drew over all entities, since the type sets were reserved (0 without them)"""
@@ -196,6 +198,23 @@ class EncoderRuntime(object):
             self.engine.set_relation_negatives(relation_rate)
             self._relation_rate = relation_rate
         return relation_rate
+
+    def set_reciprocal_relations(self, on):
+        """[Decoder] ReciprocalRelations: (?, r, o) is asked of W_relation[R + r], and every later train step trains on a
+        reciprocal batch -- the samplers' rows through the reciprocal pass, the inverse positives behind them
+        (rgcn_set_reciprocal_relations); the engine is told when the setting changes."""
+        on = bool(on)
+        if on != getattr(self, "_reciprocal_want", False):
+            self.engine.set_reciprocal_relations(on)
+            self._reciprocal_want = on
+
+    def _reciprocal(self):
+        return 1 if getattr(self, "_reciprocal_want", False) else 0
+
+    def _positives(self, y):
+        """the positives that lead a caller's batch: the rows with label 1, but for the inverse positives at its end"""
+        ones = int(np.count_nonzero(y == 1))
+        return ones // 2 if self._reciprocal() else ones
 
     def set_relation_softmax(self, weight, known=None):
         """[Decoder] RelationSoftmaxWeight: the weight of the softmax-over-relations term every later train step adds
@@ -350,7 +369,7 @@ class EncoderRuntime(object):
             b = np.ascontiguousarray(mb.batch, dtype=np.int32).reshape(-1, 3)
             nb = len(b)
         relation_rate = int(getattr(mb, "relation_rate", 0))
-        n = nb * (int(mb.rate) + 1 + relation_rate)
+        n = nb * (int(mb.rate) + 1 + relation_rate + self._reciprocal())
         if n == 0:
             raise ValueError("empty decoder batch")
         if nb > self.engine.max_edges:
@@ -409,9 +428,9 @@ class EncoderRuntime(object):
         st = self._take_staged(graph_edges, None)
         gd = st[3] if st is not None else self._upload("graph", g)
         xd, yd = self._upload("X", x), self._upload("Y", y)
-        self._relation_softmax(int(np.count_nonzero(y == 1)))      # (the sampler's positives lead the batch)
-        self._entity_softmax(int(np.count_nonzero(y == 1)))
-        self._adversarial(int(np.count_nonzero(y == 1)))
+        self._relation_softmax(self._positives(y))      # (the sampler's positives lead the batch)
+        self._entity_softmax(self._positives(y))
+        self._adversarial(self._positives(y))
         self.engine.train_step_device(gd, len(g), xd, yd, len(x), seed=seed, reg_param=reg_param)
         self._state = None            # activations now belong to this train step's graph
         self._graph_version = None
@@ -427,7 +446,7 @@ class EncoderRuntime(object):
         g = np.ascontiguousarray(graph_edges, dtype=np.int32).reshape(-1, 3)
         b = np.ascontiguousarray(batch, dtype=np.int32).reshape(-1, 3)
         relation_rate = int(relation_rate)
-        n = len(b) * (int(rate) + 1 + relation_rate)
+        n = len(b) * (int(rate) + 1 + relation_rate + self._reciprocal())
         if n == 0:
             raise ValueError("empty decoder batch")
         if len(g) > self.engine.max_edges:
@@ -579,9 +598,9 @@ class EmbeddingRuntime(EncoderRuntime):
             self.engine.decoder_reserve(len(x))
             self._dec_reserved = len(x)
         xd, yd = self._upload("X", x), self._upload("Y", y)
-        self._relation_softmax(int(np.count_nonzero(y == 1)))
-        self._entity_softmax(int(np.count_nonzero(y == 1)))
-        self._adversarial(int(np.count_nonzero(y == 1)))
+        self._relation_softmax(self._positives(y))
+        self._entity_softmax(self._positives(y))
+        self._adversarial(self._positives(y))
         self.engine.train_step_device(None, 0, xd, yd, len(x), seed=seed, reg_param=reg_param)
         self._state = None
         self.weights_version += 1
@@ -596,7 +615,7 @@ class EmbeddingRuntime(EncoderRuntime):
             raise ValueError("a graph-less encoder takes no graph_edges")
         nb = len(batch)
         relation_rate = int(relation_rate)
-        n = nb * (int(rate) + 1 + relation_rate)
+        n = nb * (int(rate) + 1 + relation_rate + self._reciprocal())
         if n == 0:
             raise ValueError("empty decoder batch")
         if n > self._dec_reserved:

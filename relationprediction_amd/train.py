@@ -80,6 +80,14 @@ def relation_negative_sample_rate(general_settings):
     return rate
 
 
+def reciprocal_relations(decoder_settings):
+    """[Decoder] ReciprocalRelations=Yes|No (absent from the reference's settings files; default No): a second vector per
+    relation, W_relation[RelationCount + r], answers (?, r, o); every step trains on the samplers' rows through the
+    reciprocal pass and on the inverse positives behind them (decoders.bilinear_diag.parse_reciprocal_relations)."""
+    from .decoders.bilinear_diag import parse_reciprocal_relations
+    return parse_reciprocal_relations(decoder_settings)
+
+
 def adversarial_temperature(general_settings):
     """[General] AdversarialTemperature=alpha (absent from the reference's settings files; default 0): the temperature of
     the self-adversarial weights of every step's negatives.  A non-negative finite float
@@ -115,7 +123,7 @@ def entity_softmax_settings(decoder_settings, entity_count):
 
 
 def make_transform(train_triplets, general_settings, encoder, device_negatives=False, device_dropout=False,
-                   device_sampler=False):
+                   device_sampler=False, reciprocal=False):
     """The reference's t_func (train.py:201-247): minibatch -> (graph_split, X, Y).
 
     ExclusiveNegativeSampling=Yes: the corruptions avoid the training triples -- on the host path through
@@ -129,6 +137,10 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
     on the host path through ns.transform_typed, on the device paths through `types=` of the batch objects (the runtime
     reserves the sets on the device once).
 
+    reciprocal (ReciprocalRelations=Yes, a key of [Decoder]): on the host path the sampler's transform_reciprocal runs
+    behind whichever transform drew the rows; on the device paths the decoder tells the runtime, whose steps run the
+    device's pass, so the batch objects carry nothing.
+
     Every batch is a function of ONE seed drawn from numpy's global generator when the batch is requested, so
     batches can be built ahead of time by background threads (`t_func.seeded(data, seed)`, used by
     optimization.optimize.HipOptimizer) and still come out in a reproducible order; `t_func(data)` itself
@@ -137,7 +149,8 @@ def make_transform(train_triplets, general_settings, encoder, device_negatives=F
     relation_rate = relation_negative_sample_rate(general_settings)
     ns = auxilliaries.NegativeSampler(int(general_settings['NegativeSampleRate']), general_settings['EntityCount'],
                                       relation_rate=relation_rate,
-                                      relation_count=int(general_settings['RelationCount']) if relation_rate else None)
+                                      relation_count=int(general_settings['RelationCount'])
+                                      if relation_rate or reciprocal else None, reciprocal=reciprocal)
     ns.set_known_positives(train_triplets)
     exclusive = exclusive_negative_sampling(general_settings)
     host_negatives = ns.transform_exclusive if exclusive else ns.transform
@@ -385,7 +398,8 @@ def main(argv=None):
     if 'NegativeSampleRate' in general_settings:
         t_func = make_transform(train_triplets, general_settings, encoder, device_negatives=not args.host_negatives,
                                 device_dropout=not (args.host_negatives or args.host_edge_dropout),
-                                device_sampler=not args.host_sampler)
+                                device_sampler=not args.host_sampler,
+                                reciprocal=reciprocal_relations(decoder_settings))
     typed_sampler = False          # False: no report; None: the device's count; a sampler: the host's beside it
     if t_func is not None and type_constrained_negatives(general_settings):
         typed_sampler = t_func.sampler if args.host_negatives else None

@@ -14,6 +14,8 @@ Reverse mode, given G_l = dL/dH_l (G_L = dcodes):
 
 backward() takes the activations H_l, the inner results N_l and the gates T_l as inputs, so that it can be evaluated at
 an engine's own forward pass (its own relu gates)."""
+import os
+
 import numpy as np
 
 import oracle
@@ -79,14 +81,34 @@ def _layer(kind):
     return chunked_block_layer_float64 if kind == "block" else chunked_basis_layer_float64
 
 
-def forward(kind, params, triples, V, L, mode="train", keep=0.8, masks=None, norm_mode=None):
-    """(H [0..L], N [None, 1..L], T [None, 1..L]) in float64"""
+def _layer_with_norms(kind, p, l, L, Hin, triples, n_f, n_b, mode, keep, mask):
+    """layer l's result from the given layer input with the per-edge norms handed in (local_norm_reference's per-edge
+    form: IncidenceNormalization=local is beyond oracle.incidence_values)"""
+    from local_norm_reference import _messages
+    dtype = Hin.dtype.type
+    s, r, o = oracle.split_graph(triples)
+    pre = Hin @ p["W_self%d" % l]
+    if mode == "train":
+        pre = pre * (np.asarray(mask, dtype=dtype) * (dtype(1) / dtype(keep)))
+    if len(s):
+        np.add.at(pre, o, _messages(kind, l, p, Hin, s, r, "f") * n_f[:, None])
+        np.add.at(pre, s, _messages(kind, l, p, Hin, o, r, "b") * n_b[:, None])
+    return np.maximum(pre, dtype(0)) if l < L else pre
+
+
+def forward(kind, params, triples, V, L, mode="train", keep=0.8, masks=None, norm_mode=None, norms=None):
+    """(H [0..L], N [None, 1..L], T [None, 1..L]) in float64; norms = (n_f, n_b): per-edge norms handed in, as
+    local_norm_reference takes them, instead of norm_mode's"""
     p = {k: np.asarray(v, dtype=F64) for k, v in params.items()}
     H = [np.maximum(p["W_emb"] + p["b_emb"], 0.0)]
     N, T = [None], [None]
     for l in range(1, L + 1):
-        n = _layer(kind)(p, l, L, H[l - 1], triples, V, mode=mode, keep=keep,
-                         mask=masks[l - 1] if mode == "train" else None, norm_mode=norm_mode)
+        mask = masks[l - 1] if mode == "train" else None
+        if norms is not None:
+            n = _layer_with_norms(kind, p, l, L, H[l - 1], triples, np.asarray(norms[0], dtype=F64),
+                                  np.asarray(norms[1], dtype=F64), mode, keep, mask)
+        else:
+            n = _layer(kind)(p, l, L, H[l - 1], triples, V, mode=mode, keep=keep, mask=mask, norm_mode=norm_mode)
         t = sigmoid(H[l - 1] @ p["W_highway%d" % l] + p["b_highway%d" % l])
         N.append(n)
         T.append(t)
@@ -94,16 +116,17 @@ def forward(kind, params, triples, V, L, mode="train", keep=0.8, masks=None, nor
     return H, N, T
 
 
-def forward_float32(kind, params, triples, V, L, mode="train", keep=0.8, masks=None):
+def forward_float32(kind, params, triples, V, L, mode="train", keep=0.8, masks=None, norms=None):
     """forward() once more with every array and every operation in numpy float32 (per-edge messages, np.add.at for the
-    scatter; 'intended' normalisation).  Its distance from forward() on the same inputs is the error scale of a correct
-    fp32 evaluation in ONE summation order: what the large-shape GPU test sizes its tolerance with."""
+    scatter; 'intended' normalisation, or the per-edge norms = (n_f, n_b) handed in).  Its distance from forward() on the
+    same inputs is the error scale of a correct fp32 evaluation in ONE summation order: what the large-shape GPU test
+    sizes its tolerance with."""
     f32 = np.float32
     p = {k: np.asarray(v, dtype=f32) for k, v in params.items()}
     s, r, o = oracle.split_graph(triples)
     E = len(s)
-    n_f = np.asarray(oracle.incidence_values(o, V, oracle.NORM_INTENDED), dtype=f32)
-    n_b = np.asarray(oracle.incidence_values(s, V, oracle.NORM_INTENDED), dtype=f32)
+    n_f = np.asarray(oracle.incidence_values(o, V, oracle.NORM_INTENDED) if norms is None else norms[0], dtype=f32)
+    n_b = np.asarray(oracle.incidence_values(s, V, oracle.NORM_INTENDED) if norms is None else norms[1], dtype=f32)
     H = [np.maximum(p["W_emb"] + p["b_emb"], f32(0))]
     N, T = [None], [None]
     for l in range(1, L + 1):
@@ -133,14 +156,44 @@ def forward_float32(kind, params, triples, V, L, mode="train", keep=0.8, masks=N
     return H, N, T
 
 
-def _layer_backward(kind, p, l, Hin, D, dS, triples, V, norm_mode, dtype=F64):
+def _block_messages_backward(W, Hin, gm, r, rows_in, V, chunk=4096):
+    """(sum over the messages e of relation q of gm[e] (x) Hin[rows_in[e]] as [R, nb, sd, sd], sum over the messages e
+    with rows_in[e] = v of W[r[e]]^T . gm[e] as [V, d]) in the arrays' own type, edge chunk by edge chunk so that no
+    [E, nb, sd, sd] array is held whole (33,000 edges at d = 516: tests/fullgraph_grid.py); every sum runs in edge order
+    within a chunk, the chunks are added in order"""
+    import scipy.sparse as sp
+    from concurrent.futures import ThreadPoolExecutor
+    R, nb, sd, _ = W.shape
+    E, dtype = len(r), gm.dtype
+
+    def one(lo):
+        sl = slice(lo, lo + chunk)
+        n = len(r[sl])
+        g3, x3 = gm[sl].reshape(n, nb, sd), Hin[rows_in[sl]].reshape(n, nb, sd)
+        ones, cols = np.ones(n, dtype=dtype), np.arange(n)
+        dw = sp.csr_matrix((ones, (r[sl], cols)), shape=(R, n)) @ np.einsum("ebi,ebj->ebij", g3, x3).reshape(n, nb * sd * sd)
+        dx = sp.csr_matrix((ones, (rows_in[sl], cols)), shape=(V, n)) @ \
+            np.einsum("ebij,ebi->ebj", W[r[sl]], g3).reshape(n, nb * sd)
+        return dw, dx
+
+    gW, dH = np.zeros((R, nb * sd * sd), dtype=dtype), np.zeros((V, nb * sd), dtype=dtype)
+    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:       # numpy drops the GIL inside these calls
+        for dw, dx in ex.map(one, range(0, E, chunk)):
+            gW += dw
+            dH += dx
+    assert gW.dtype == dH.dtype == dtype
+    return gW.reshape(W.shape), dH
+
+
+def _layer_backward(kind, p, l, Hin, D, dS, triples, V, norm_mode, dtype=F64, norms=None):
     """gradients of layer l's own weights from D = dL/dpre_l and dS = D * dropout_l, and the raw dL/dH_{l-1} through the
-    layer (no relu', no dropout copy): tf.gradients of gcn_basis_concat.py:35-83 / gcn_basis.py:39-88"""
+    layer (no relu', no dropout copy): tf.gradients of gcn_basis_concat.py:35-83 / gcn_basis.py:39-88.  norms = (n_f, n_b):
+    per-edge norms handed in instead of norm_mode's"""
     norm_mode = oracle.NORM_INTENDED if norm_mode is None else norm_mode
     s, r, o = oracle.split_graph(triples)
     E = len(s)
-    n_f = np.asarray(oracle.incidence_values(o, V, norm_mode), dtype=dtype)
-    n_b = np.asarray(oracle.incidence_values(s, V, norm_mode), dtype=dtype)
+    n_f = np.asarray(oracle.incidence_values(o, V, norm_mode) if norms is None else norms[0], dtype=dtype)
+    n_b = np.asarray(oracle.incidence_values(s, V, norm_mode) if norms is None else norms[1], dtype=dtype)
     g = {"W_self%d" % l: Hin.T @ dS, "b%d" % l: np.zeros(D.shape[1], dtype=dtype)}
     dHin = dS @ p["W_self%d" % l].T
     for tag, rows_in, rows_out, nrm in (("f", s, o, n_f), ("b", o, s, n_b)):
@@ -148,10 +201,9 @@ def _layer_backward(kind, p, l, Hin, D, dS, triples, V, norm_mode, dtype=F64):
         gW = np.zeros_like(W)
         gm = D[rows_out] * nrm[:, None] if E else np.zeros((0, D.shape[1]), dtype=dtype)
         if kind == "block":
-            R, nb, sd, _ = W.shape
-            g3, x3 = gm.reshape(E, nb, sd), Hin[rows_in].reshape(E, nb, sd)
-            np.add.at(gW, r, np.einsum("ebi,ebj->ebij", g3, x3))
-            np.add.at(dHin, rows_in, np.einsum("ebij,ebi->ebj", W[r], g3).reshape(E, nb * sd))
+            dw, dx = _block_messages_backward(W, Hin, gm, r, rows_in, V)
+            gW += dw
+            dHin += dx
         else:
             C = p["C_%s%d" % (tag, l)]
             gC = np.zeros_like(C)
@@ -167,9 +219,11 @@ def _layer_backward(kind, p, l, Hin, D, dS, triples, V, norm_mode, dtype=F64):
     return g, dHin
 
 
-def backward(kind, params, triples, V, L, H, N, T, dcodes, mode="train", keep=0.8, masks=None, norm_mode=None, dtype=F64):
+def backward(kind, params, triples, V, L, H, N, T, dcodes, mode="train", keep=0.8, masks=None, norm_mode=None, dtype=F64,
+             norms=None):
     """gradient of <dcodes, H_L> w.r.t. every encoder parameter, evaluated at the given H, N and T; dtype=np.float32
-    evaluates the same formulas with every array and every operation in float32 (forward_float32's counterpart)"""
+    evaluates the same formulas with every array and every operation in float32 (forward_float32's counterpart);
+    norms = (n_f, n_b) as in forward()"""
     one = dtype(1)
     p = {k: np.asarray(v, dtype=dtype) for k, v in params.items()}
     H = [np.asarray(a, dtype=dtype) for a in H]
@@ -182,7 +236,7 @@ def backward(kind, params, triples, V, L, H, N, T, dcodes, mode="train", keep=0.
         dZ = G * (n - Hin) * t * (one - t)
         grads["W_highway%d" % l] = Hin.T @ dZ
         grads["b_highway%d" % l] = dZ.sum(axis=0)
-        g, raw = _layer_backward(kind, p, l, Hin, D, dS, triples, V, norm_mode, dtype=dtype)
+        g, raw = _layer_backward(kind, p, l, Hin, D, dS, triples, V, norm_mode, dtype=dtype, norms=norms)
         grads.update(g)
         G = raw + dZ @ p["W_highway%d" % l].T + G * (one - t)
     g0 = G * (H[0] > 0)

@@ -73,47 +73,53 @@ def _messages(kind, l, p, H, rows_in, r, tag):
     return np.einsum("ebk,eb->ek", (H[rows_in] @ W.reshape(d_in, B * d_out)).reshape(E, B, d_out), C[r])
 
 
-def _drop(mode, keep, masks, l, shape):
-    return np.asarray(masks[l - 1], dtype=F64) / F64(keep) if mode == "train" else np.ones(shape, dtype=F64)
+def _drop(mode, keep, masks, l, shape, dtype=F64):
+    return np.asarray(masks[l - 1], dtype=dtype) / dtype(keep) if mode == "train" else np.ones(shape, dtype=dtype)
 
 
-def forward(kind, params, triples, V, L, n_f, n_b, mode="train", keep=0.8, masks=None):
-    """[H0, ..., HL] in float64; kind 'block' | 'basis' | 'onehot' (the featureless basis encoder: H0 is None)"""
-    p = {k: np.asarray(v, dtype=F64) for k, v in params.items()}
+def forward(kind, params, triples, V, L, n_f, n_b, mode="train", keep=0.8, masks=None, dtype=F64):
+    """[H0, ..., HL] in float64; kind 'block' | 'basis' | 'onehot' (the featureless basis encoder: H0 is None).
+    dtype=np.float32: the same formulas with every array and every operation in float32, one summation order (what
+    tests/test_fullgraph_grid.py sizes the full-graph bounds with)"""
+    p = {k: np.asarray(v, dtype=dtype) for k, v in params.items()}
+    n_f, n_b = np.asarray(n_f, dtype=dtype), np.asarray(n_b, dtype=dtype)
     s, r, o = oracle.split_graph(triples)
-    H = None if kind == "onehot" else np.maximum(p["W_emb"] + p["b_emb"], 0.0)
+    H = None if kind == "onehot" else np.maximum(p["W_emb"] + p["b_emb"], dtype(0))
     acts = [H]
     for l in range(1, L + 1):
         Ws = p["W_self%d" % l]
         S = Ws if (kind == "onehot" and l == 1) else H @ Ws
-        pre = S * _drop(mode, keep, masks, l, S.shape)
+        pre = S * _drop(mode, keep, masks, l, S.shape, dtype)
         if len(s):
             np.add.at(pre, o, _messages(kind, l, p, H, s, r, "f") * n_f[:, None])
             np.add.at(pre, s, _messages(kind, l, p, H, o, r, "b") * n_b[:, None])
-        H = np.maximum(pre, 0.0) if l < L else pre
+        H = np.maximum(pre, dtype(0)) if l < L else pre
+        assert H.dtype == dtype
         acts.append(H)
     return acts
 
 
-def backward(kind, params, triples, V, L, n_f, n_b, acts, dcodes, mode="train", keep=0.8, masks=None):
-    """gradient of <dcodes, HL> with respect to every encoder parameter, evaluated at the given activations"""
-    p = {k: np.asarray(v, dtype=F64) for k, v in params.items()}
+def backward(kind, params, triples, V, L, n_f, n_b, acts, dcodes, mode="train", keep=0.8, masks=None, dtype=F64):
+    """gradient of <dcodes, HL> with respect to every encoder parameter, evaluated at the given activations; dtype as in
+    forward()"""
+    p = {k: np.asarray(v, dtype=dtype) for k, v in params.items()}
+    n_f, n_b = np.asarray(n_f, dtype=dtype), np.asarray(n_b, dtype=dtype)
     s, r, o = oracle.split_graph(triples)
     E = len(s)
-    acts = [None if a is None else np.asarray(a, dtype=F64) for a in acts]
+    acts = [None if a is None else np.asarray(a, dtype=dtype) for a in acts]
     grads = {}
-    dH = np.asarray(dcodes, dtype=F64)
+    dH = np.asarray(dcodes, dtype=dtype)
     for l in range(L, 0, -1):
         Hin, table = acts[l - 1], kind == "onehot" and l == 1
         D = dH * (acts[l] > 0) if l < L else dH
-        dS = D * _drop(mode, keep, masks, l, D.shape)
+        dS = D * _drop(mode, keep, masks, l, D.shape, dtype)
         grads["W_self%d" % l] = dS if table else Hin.T @ dS
-        grads["b%d" % l] = np.zeros(D.shape[1])
+        grads["b%d" % l] = np.zeros(D.shape[1], dtype=dtype)
         dHin = None if table else dS @ p["W_self%d" % l].T
         for tag, rows_in, rows_out, nrm in (("f", s, o, n_f), ("b", o, s, n_b)):
             W = p["W_%s%d" % (tag, l)]
             gW = np.zeros_like(W)
-            g = D[rows_out] * nrm[:, None] if E else np.zeros((0, D.shape[1]))
+            g = D[rows_out] * nrm[:, None] if E else np.zeros((0, D.shape[1]), dtype=dtype)
             if kind == "block":
                 R, nb, sd, _ = W.shape
                 g3, x3 = g.reshape(E, nb, sd), Hin[rows_in].reshape(E, nb, sd)
